@@ -957,6 +957,56 @@ def compact_line(line, limit=5600):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6          # --dump-outputs: all .npy files of a run together stay below this
+
+
+def host_copy(v):
+    """What a call returned (dict / tuple / list of tensors, nested), every tensor copied to host memory."""
+    if isinstance(v, torch.Tensor):
+        return v.detach().cpu()
+    if isinstance(v, dict):
+        return type(v)((k, host_copy(x)) for k, x in v.items())
+    if isinstance(v, (tuple, list)):
+        return type(v)(host_copy(x) for x in v)
+    return v
+
+
+def dump_outputs(outs, out_dir, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: every tensor of what the timed path's last call returned -> out_dir/<name>.npy, float32 (float64 stays float64).
+    Names follow the returned structure: `result` for forward()'s [n,3,4h,4w] tensor, result_0 .. result_{B-1} for the B frames of
+    forward_group()'s tuple.  When the arrays exceed `limit` bytes in all, each one is replaced by a fixed sample of its flattened
+    elements -- the sorted positions np.random.default_rng((seed, i)) draws for the i-th array, the same in every run with the same
+    arguments -- so that two builds compare element for element.  Returns the record's description of the files."""
+    import numpy as np
+    flat = {}
+
+    def walk(name, v):
+        if isinstance(v, torch.Tensor):
+            flat[name] = (v.double() if v.dtype == torch.float64 else v.float()).numpy()
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                walk('%s_%s' % (name, k) if name else str(k), x)
+        elif isinstance(v, (tuple, list)):
+            for i, x in enumerate(v):
+                walk('%s_%d' % (name, i), x)
+    walk('', outs)
+    budget = limit - 4096 * len(flat)                     # (npy headers)
+    total = sum(a.nbytes for a in flat.values())
+    os.makedirs(out_dir, exist_ok=True)
+    desc = {}
+    for i, (name, a) in enumerate(flat.items()):
+        d = {'shape': list(a.shape), 'dtype': str(a.dtype), 'sampled_elements': None}
+        if total > budget:
+            k = int(a.size * (budget / float(total)))
+            idx = np.sort(np.random.default_rng((seed, i)).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+            d['sampled_elements'] = k
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        desc[name] = d
+    return {'dir': out_dir, 'arrays': desc, 'sample_seed': seed if total > budget else None,
+            'what': 'what the last call of the last timed pass returned (rank 0)'}
+
+
 def emit(line, args):
     """Complete record -> --full-json (best effort), compact line -> stdout."""
     try:
@@ -1029,6 +1079,8 @@ def main():
     ap.add_argument('--match-margin', type=float, default=None, help='A/B knob: margin of the exact-search flagging (0 = top-2 re-rank only)')
     ap.add_argument('--cpu-baseline-only', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--cpu-baseline-timeout', type=float, default=300.0)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last call of the last timed pass returned to DIR/<name>.npy (rank 0; at most 64 MB in all)')
     args = ap.parse_args()
     H, W_ = [int(v) for v in args.size.lower().split('x')]
     T = args.frames
@@ -1054,7 +1106,9 @@ def main():
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(args.gpus), '--master-addr', '127.0.0.1',
                '--master-port', str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        # a child process, not exec: the device count above has already started the HIP runtime in this process
+        import subprocess
+        raise SystemExit(subprocess.call(cmd))
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit('--gpus %d under a launcher with WORLD_SIZE=%d: launch with --nproc-per-node %d' % (args.gpus, world, args.gpus))
     if not torch.cuda.is_available():
@@ -1106,9 +1160,12 @@ def main():
     torch.cuda.synchronize()
     eng = net.Network.ensure_engines(1, dev)[0]
 
-    def timed_pass(use_ids, pipelined, collect_events, collect_chain=False, timed=True, group=1):
+    kept = {}
+
+    def timed_pass(use_ids, pipelined, collect_events, collect_chain=False, timed=True, group=1, keep=False):
         """W untimed + K timed steps of a new clip; returns (seconds for the K steps, events).  group > 1 (pipelined mode): the
-        steps go through forward_group, `group` consecutive output frames per call (the same frames, the same results)."""
+        steps go through forward_group, `group` consecutive output frames per call (the same frames, the same results).
+        keep: host copies of what the last call returned go to kept['outputs'] (after the clock stopped)."""
         net.Network.reset()
         net.Network.set_pipelined(bool(use_ids and pipelined))
         # pipelined calls: the windows were materialised (and synchronised) before the first pass -- the caller-side assertion
@@ -1118,22 +1175,23 @@ def main():
         def step(f):
             ids = [start + i for i in wins[f]] if use_ids else None
             if ids is None:
-                return net(win_lr[f], win_rf[f], f == 0)['result']                  # the reference's call, verbatim
-            return net(win_lr[f], win_rf[f], f == 0, frame_ids=ids, input_ready=ready)['result']
+                return net(win_lr[f], win_rf[f], f == 0)                             # the reference's call, verbatim
+            return net(win_lr[f], win_rf[f], f == 0, frame_ids=ids, input_ready=ready)
         grouped = group > 1 and use_ids and pipelined
 
         def run_steps(f0, f1):
+            """Calls for frames f0 .. f1-1; returns what the last call returned."""
             o, f = None, f0
             while f < f1:
                 n = min(group, f1 - f) if grouped else 1
                 if n >= 2:
                     ids = [[start + i for i in wins[f + b]] for b in range(n)]
-                    o = net.forward_group(all_lr[f:f + n], all_rf[f:f + n], ids, is_first_frame=(f == 0), input_ready=ready)['result'][-1]
+                    o = net.forward_group(all_lr[f:f + n], all_rf[f:f + n], ids, is_first_frame=(f == 0), input_ready=ready)
                 else:
                     o = step(f)
                 f += n
             return o
-        out = run_steps(0, args.warmup)
+        run_steps(0, args.warmup)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -1144,7 +1202,7 @@ def main():
         eng.chain_events = [] if (collect_events and collect_chain) else None
         eng.stream_events = [] if (use_ids and pipelined) else None                  # 6 events per call: the P / F / M sections
         t0 = time.perf_counter()
-        out = run_steps(args.warmup, nfr)
+        outs = run_steps(args.warmup, nfr)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -1154,7 +1212,10 @@ def main():
             tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == 'nccl' else 'cpu')
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
-        assert bool(torch.isfinite(out).all())
+        res = outs['result']
+        assert bool(torch.isfinite(res[-1] if isinstance(res, tuple) else res).all())
+        if keep:
+            kept['outputs'] = host_copy(outs)
         ev = (eng.kernel_events, eng.chain_events, eng.stream_events)
         eng.kernel_events = eng.chain_events = eng.stream_events = None
         net.Network.set_pipelined(False)
@@ -1225,9 +1286,10 @@ def main():
     # ---- R timed repetitions, the two call modes interleaved (fast / reference surface / fast / ...): every sample is printed,
     # `value` is the MEDIAN of the fast mode's samples
     samples, samples_dropin, samples_percall, sums, ev = [], [], [], [], None
-    for rep in range(max(1, args.repeats)):
+    nrep = max(1, args.repeats)
+    for rep in range(nrep):
         gc.collect()
-        el, e = timed_pass(use_ids, pipelined, True, group=G)
+        el, e = timed_pass(use_ids, pipelined, True, group=G, keep=bool(args.dump_outputs) and rep == nrep - 1)
         samples.append(el)
         sums.append(stream_summary(e[2], el))
         if ev is None or el <= min(samples):
@@ -1239,6 +1301,9 @@ def main():
             el2, _ = timed_pass(False, False, False)
             samples_dropin.append(el2)
     elapsed = med(samples)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(kept.pop('outputs'), args.dump_outputs)
     fps_samples = [world * args.steps / x for x in samples]
     # (round 6, ADVICE r5: the mode is fixed BEFORE the measurement -- frame groups wherever the engine has the multi-map launch list;
     #  rounds 4-5 reported the faster of the two modes measured, a max-of-medians with a small upward bias.  The other mode's rate stays
@@ -1459,6 +1524,8 @@ def main():
             line['roofline']['live_pmc_error'] = live_pmc_err
         line['first_frame_ms'] = first_ms
         line['pcie_inclusive'] = pcie
+        if dumped is not None:
+            line['dump_outputs'] = dumped
         sv = SURVEY_DEDUP_TFLOP.get(args.config) if (H, W_, T) == (270, 480, 5) else None
         line['whole_path'] = {
             'algorithmic_tflop_per_frame': alg, 'breakdown': {k: round(v, 4) for k, v in parts.items()},

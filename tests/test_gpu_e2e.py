@@ -1227,7 +1227,7 @@ def test_frame_groups_are_bit_identical(dev, gsize):
         assert torch.equal(res[f], want[f])
 
 
-def test_bench_gpus_2_self_launches_and_reports_the_sharded_clip(dev):
+def test_bench_gpus_2_self_launches_and_reports_the_sharded_clip(dev, tmp_path):
     """`python bench.py --gpus 2` with no launcher around it (the driver may call it like `--gpus 1`): re-executes
     itself under torch.distributed.run, two ranks -- on this one-GPU box they share the GPU and talk over gloo --, prints ONE
     compact JSON line whose `value` is the strong-scaling sharded-clip rate with the frames verified against a single-rank run,
@@ -1242,7 +1242,7 @@ def test_bench_gpus_2_self_launches_and_reports_the_sharded_clip(dev):
     env.pop('LOCAL_RANK', None)
     env['REFVSR_DIST_BACKEND'] = 'gloo'
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--size', '64x96', '--clip', '12',
-                        '--clip-check', '12', '--repeats', '1', '--warm-seconds', '0.05', '--no-kernels', '--full-json', '/tmp/bench_n2_full.json'],
+                        '--clip-check', '12', '--repeats', '1', '--warm-seconds', '0.05', '--no-kernels', '--full-json', str(tmp_path / 'bench_n2_full.json')],
                        capture_output=True, text=True, timeout=420, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -1256,7 +1256,7 @@ def test_bench_gpus_2_self_launches_and_reports_the_sharded_clip(dev):
     assert abs(d['value'] - 12.0 / d['wavefront']['seconds']) < 2e-2 * d['value']          # (the compact line rounds the seconds)
 
 
-def test_bench_n1_prints_exactly_one_stdout_line(dev):
+def test_bench_n1_prints_exactly_one_stdout_line(dev, tmp_path):
     """The driver parses ONE JSON line from `python bench.py`'s stdout.  Round 6 briefly broke that at N = 1: the one-rank executor leg
     made a world-1 gloo group, whose C++ banner goes to stdout ahead of the line.  The default command (270 x 480, so that the
     wavefront-model legs run; the slow extra legs switched off) must print the line and nothing else, and the line must carry the
@@ -1269,7 +1269,7 @@ def test_bench_n1_prints_exactly_one_stdout_line(dev):
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '8', '--warmup', '3', '--repeats', '1', '--warm-seconds', '0.05',
-                        '--no-other-configs', '--no-cpu-baseline', '--no-kernels', '--full-json', '/tmp/bench_n1_full.json'],
+                        '--no-other-configs', '--no-cpu-baseline', '--no-kernels', '--full-json', str(tmp_path / 'bench_n1_full.json')],
                        capture_output=True, text=True, timeout=420, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     out_lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -1281,7 +1281,46 @@ def test_bench_n1_prints_exactly_one_stdout_line(dev):
     assert d['pcie_inclusive']['result_uint8']['value'] > 0
 
 
-def test_bench_sharded_clip_leg_under_rccl_with_one_rank(dev):
+def test_bench_dump_outputs_hold_the_last_timed_call(dev, tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last call of the last timed pass returned: with --warmup 2 --steps 6 in frame
+    groups of four that is the group of frames 6, 7 (result_0, result_1), equal to what one reference-surface call per frame returns
+    for the same windows; a second run with the same arguments writes the same arrays, and stdout still carries one line."""
+    import json
+    import subprocess
+    import sys
+    from refvsr_amd.synth import make_clip, window_indices
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
+        env.pop(k, None)
+    got = []
+    for r in range(2):
+        out = tmp_path / ('dump%d' % r)
+        p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--size', '64x96', '--steps', '6', '--warmup', '2', '--repeats', '2',
+                            '--warm-seconds', '0.05', '--no-other-configs', '--no-cpu-baseline', '--no-kernels', '--no-live-pmc', '--no-wavefront',
+                            '--no-dropin', '--full-json', str(tmp_path / ('full%d.json' % r)), '--dump-outputs', str(out)],
+                           capture_output=True, text=True, timeout=420, env=env, cwd=root)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1 and json.loads(lines[0])['steps'] == 6, p.stdout[:600]
+        assert json.loads(lines[0])['config']['frames_per_call'] == 4
+        assert sorted(os.listdir(str(out))) == ['result_0.npy', 'result_1.npy']
+        got.append([np.load(str(out / ('result_%d.npy' % i))) for i in range(2)])
+    net, cfg, sd = make_net('config_RefVSR_small_L1', 5, dev)
+    nfr = 8
+    lr, rf, _ = make_clip(nfr, 64, 96, seed=0, want_gt=False)
+    want = []
+    for f in range(nfr):
+        w = window_indices(f, nfr, 5)
+        want.append(net(lr[w][None].to(dev), rf[w][None].to(dev), f == 0)['result'].float().cpu().numpy())
+    for i in range(2):
+        assert got[0][i].dtype == np.float32 and got[0][i].shape == (1, 3, 256, 384)
+        e_run, e_ref = float(np.abs(got[0][i] - got[1][i]).max()), float(np.abs(got[0][i] - want[6 + i]).max())
+        report('bench --dump-outputs frame %d' % (6 + i), vs_second_run=e_run, vs_reference_surface=e_ref)
+        assert e_run <= 1e-6 and e_ref <= 1e-5
+
+
+def test_bench_sharded_clip_leg_under_rccl_with_one_rank(dev, tmp_path):
     """The nccl (= RCCL) branch of bench.py had never executed on this pool's 1-GPU boxes (RCCL refuses two ranks on one device, so the
     two-rank runs use gloo).  `--force-dist` (test aid) brings up the process group with ONE rank on the real backend and runs the
     sharded-clip leg through it: communicator set-up, device-side all_reduce / barrier, comm_dev = the GPU, the executor's lanes, the two
@@ -1295,7 +1334,7 @@ def test_bench_sharded_clip_leg_under_rccl_with_one_rank(dev):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--force-dist', '--steps', '4', '--warmup', '2', '--size', '64x96', '--clip', '14',
                         '--clip-check', '14', '--repeats', '1', '--warm-seconds', '0.05', '--no-kernels', '--no-other-configs', '--no-cpu-baseline',
-                        '--no-live-pmc', '--full-json', '/tmp/bench_rccl1_full.json'],
+                        '--no-live-pmc', '--full-json', str(tmp_path / 'bench_rccl1_full.json')],
                        capture_output=True, text=True, timeout=420, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -1307,7 +1346,7 @@ def test_bench_sharded_clip_leg_under_rccl_with_one_rank(dev):
     assert wf['frames_checked_against_single_rank_run'] == 14 and wf['value'] > 0
 
 
-def test_bench_gpus_2_configs3_at_its_size_all_frames_equal(dev):
+def test_bench_gpus_2_configs3_at_its_size_all_frames_equal(dev, tmp_path):
     """BASELINE configs[3] at its own size inside the test run: `python bench.py --gpus 2` with the 64-frame
     270 x 480 clip of config_RefVSR_small_MFID sharded over two ranks (they share this box's one GPU and talk over gloo; phase A in
     groups of four windows, contexts exchanged, state hand-off) -- and ALL 64 frames compared with the single-rank run."""
@@ -1320,7 +1359,7 @@ def test_bench_gpus_2_configs3_at_its_size_all_frames_equal(dev):
         env.pop(k, None)
     env['REFVSR_DIST_BACKEND'] = 'gloo'
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '2', '--clip', '64', '--clip-check', '64',
-                        '--repeats', '1', '--warm-seconds', '0.05', '--no-kernels', '--full-json', '/tmp/bench_n2_configs3_full.json'],
+                        '--repeats', '1', '--warm-seconds', '0.05', '--no-kernels', '--full-json', str(tmp_path / 'bench_n2_configs3_full.json')],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

@@ -1128,6 +1128,35 @@ def test_bench_compact_line_keeps_the_judged_fields_under_6_kb():
     assert line_bad['value'] == 1700.0 and line_bad['scaling'] == 'weak'
 
 
+def test_bench_dump_outputs_names_budget_and_fixed_sample(tmp_path):
+    """bench.dump_outputs (pure host code, --dump-outputs): one float32 .npy per returned tensor, named after the returned structure;
+    small outputs whole, large ones as the same seeded sample in every run, all files together under the 64 MB limit."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_mod3', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    small = {'result': torch.rand(1, 3, 8, 12, generator=g, dtype=torch.float64)}
+    d = bench.dump_outputs(bench.host_copy(small), str(tmp_path / 'small'))
+    a = np.load(str(tmp_path / 'small' / 'result.npy'))
+    assert a.dtype == np.float64 and np.array_equal(a, small['result'].numpy()) and d['arrays']['result']['sampled_elements'] is None
+    # forward_group's return value at the headline size: four [1,3,1080,1920] frames (~100 MB of float32)
+    big = {'result': tuple(torch.rand(1, 3, 1080, 1920, generator=g).half() for _ in range(4))}
+    runs = []
+    for r in range(2):
+        out = tmp_path / ('big%d' % r)
+        d = bench.dump_outputs(big, str(out))
+        assert sorted(os.listdir(str(out))) == ['result_%d.npy' % i for i in range(4)]
+        assert sum(os.path.getsize(str(out / f)) for f in os.listdir(str(out))) <= bench.DUMP_LIMIT_BYTES
+        assert d['arrays']['result_0']['shape'] == [1, 3, 1080, 1920] and d['arrays']['result_0']['sampled_elements'] > 3 * 10 ** 6
+        runs.append([np.load(str(out / ('result_%d.npy' % i))) for i in range(4)])
+    for i in range(4):
+        assert runs[0][i].dtype == np.float32 and np.array_equal(runs[0][i], runs[1][i])
+        assert set(np.unique(runs[0][i])) <= set(np.unique(big['result'][i].float().numpy()))
+
+
 def test_roll_over_counter_of_a_frame_group():
     """Engine._itr_after (host arithmetic of the frame groups, round 5): the value of frame_itr_num the k-th window from now will find
     -- the counter restarts when it reaches reset_branch (RefVSR.py:168-170, 292-295) -- against a window-by-window simulation; the

@@ -8,6 +8,7 @@ in tools/ref_shims/ (SURVEY.md section 8c / appendix B).  Nothing from the refer
 only input/output tensors are written to tests/golden/*.npz.
 
     python tools/gen_golden.py            # writes tests/golden/*.npz and prints oracle deltas
+    python tools/gen_golden.py --plugin-spec   # only tests/golden/plugin_state_dict.json (the reference shell's state dict)
 """
 import importlib
 import os
@@ -486,6 +487,9 @@ def main():
     if '--spec' in sys.argv:
         gen_spec()
         return
+    if '--plugin-spec' in sys.argv:
+        gen_plugin_spec()
+        return
     if '--full' in sys.argv:
         os.makedirs(GOLD, exist_ok=True)
         torch.set_num_threads(8)
@@ -521,6 +525,7 @@ def main():
     for e in IR:
         gen_e2e_ir(*e[:6], reset_override=e[6])
     gen_spec()
+    gen_plugin_spec()
 
 
 def gen_spec():
@@ -534,6 +539,28 @@ def gen_spec():
         sums[name + '/spec_crc'] = np.int64(wts.spec_checksum(mine))
         sums[name + '/frame_num'] = np.int64(importlib.import_module('configs.' + name).get_config('p', 'm', name).frame_num)
     save('state_spec', **sums)
+
+
+PLUGIN_CONFIGS = ('config_RefVSR_small_L1', 'config_RefVSR_MFID_8K', 'config_RefVSR_IR_L1')
+
+
+def gen_plugin_spec():
+    """The reference shell's own state dict (models/SRNet.py:SRNet on the reference's own config object): [key, shape, dtype] in
+    its order, for the configs tests/test_reference_plugin.py runs the plug-in file with -> tests/golden/plugin_state_dict.json."""
+    import json
+    from models.SRNet import SRNet
+    out = {}
+    for name in PLUGIN_CONFIGS:
+        cfg = importlib.import_module('configs.' + name).get_config('p', 'm', name)
+        cfg.cuda, cfg.device, cfg.dist = False, 'cpu', False
+        cfg.network_ref = cfg.network
+        sd = SRNet(cfg).eval().state_dict()
+        out[name] = [[k, list(v.shape), str(v.dtype).replace('torch.', '')] for k, v in sd.items()]
+    path = os.path.join(GOLD, 'plugin_state_dict.json')
+    with open(path, 'w') as f:                                     # one state-dict entry per line
+        f.write('{\n' + ',\n'.join('%s: [\n%s\n]' % (json.dumps(name), ',\n'.join(json.dumps(e) for e in ents))
+                                   for name, ents in out.items()) + '\n}\n')
+    print('  wrote %-34s %7.1f KB' % ('plugin_state_dict.json', os.path.getsize(path) / 1024.0))
 
 
 if __name__ == '__main__':
