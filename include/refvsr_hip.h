@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define REFVSR_ABI_VERSION 14  /* 2: K-block order of packed conv weights (refvsr_amd/packing.py:kslot);
+#define REFVSR_ABI_VERSION 15  /* 2: K-block order of packed conv weights (refvsr_amd/packing.py:kslot);
                                   3: exact matching (match_refine flagging, match_exact), lean ResBlock;
                                   4: hi + lo patch rows (match_patches rows_lo), split-fp16 match_exact;
                                   5: compile-time-specialised 24-channel ResBlock (resblock24 blob);
@@ -43,7 +43,9 @@ extern "C" {
                                   13: CU partitions: refvsr_stream_create_cu_range / refvsr_stream_set_cu_budget /
                                       refvsr_stream_destroy / refvsr_num_cus;
                                   14: result formats of the output head (REFVSR_RESULT_*): refvsr_conv_last_fmt,
-                                      refvsr_conv_hr_last_fmt, refvsr_convert_result */
+                                      refvsr_conv_hr_last_fmt, refvsr_convert_result;
+                                  15: the fp16 weight format (config.weight_precision = 'fp16'): *_f16w twins of the specialised
+                                      entry points of the mid_channels = 24 family and their blob-size queries */
 
 int refvsr_abi_version(void);
 /* REFVSR_MAX_MAPS of the built library (a value, not a status): bindings check their own copy against it at load time. */
@@ -164,6 +166,19 @@ int refvsr_resblock24_chain_batch(const void* const* src, int batch, int h, int 
                                   float act_slope, void* scratch0, void* scratch1, void* const* out, void* stream);
 /* (ty << 16 | tx << 8 | cg) of K-block (K-step s = 0..6, quarter q = 0..3) of the blob's K order, -1 for the zero block. */
 int refvsr_resblock24_kblock(int s, int q);
+/* The fp16 weight format (ABI 15; config.weight_precision = 'fp16').  Every _f16w function below has the
+ * signature of the function it is named after and takes blobs with plain fp16 weights in ONE fragment per 16 output rows -- no lo
+ * halves, no fold: resblock24 [conv1: 7 K-steps x 2 fragments (rows 0-15, rows 16-23 + 8 zero rows) x 64 lanes x 8 halfs][conv2: same]
+ * [b1: 32 floats][b2: 32 floats] = REFVSR_RESBLOCK24_F16W_BLOB_BYTES (refvsr_amd/packing.py:pack_resblock24_f16w); conv24 / conv32 /
+ * conv_shuffle2: 2 / 2 / 3 fragments per K-step with the bias tails of the hi + lo layout (refvsr_*_f16w_blob_bytes).  Same K order,
+ * accumulator initial values and fold order as the hi + lo kernels: on weights w with fp16(w) == w the results are bit-identical to
+ * the hi + lo entry points (whose lo MFMAs then add exact zeros), with two thirds (24 outputs) or half (32 | 48) of the MFMAs. */
+#define REFVSR_RESBLOCK24_F16W_BLOB_BYTES 28928
+int refvsr_resblock24_f16w_blob_bytes(void);
+int refvsr_resblock24_chain_f16w(const void* src, int h, int w, int n, const void* blobs, size_t blob_stride, float act_slope,
+                                 void* scratch0, void* scratch1, void* out, void* stream);
+int refvsr_resblock24_chain_batch_f16w(const void* const* src, int batch, int h, int w, int n, const void* blobs, size_t blob_stride,
+                                       float act_slope, void* scratch0, void* scratch1, void* const* out, void* stream);
 /* Tuning knob: workgroup shape of the 24-channel kernel.  0 (default): by map size -- 8 waves on 8 x 32-pixel tiles, or 16
  * waves on 16 x 32 tiles (one workgroup per CU) when the map has at least four 8 x 32 tiles per CU; 4 | 8 | 16 force a
  * shape.  Results do not depend on it (bit-identical). */
@@ -289,6 +304,26 @@ int refvsr_conv_shuffle2(const void* src, int c, int h, int w, const void* blobs
 /* refvsr_conv_shuffle2 over `batch` maps (ABI 11, c = 24): src / out host arrays of `batch` device pointers. */
 int refvsr_conv_shuffle2_batch(const void* const* src, int batch, int c, int h, int w, const void* blobs, float act_slope,
                                void* const* out, void* stream);
+/* fp16-weight twins of the conv24 family (ABI 15, see refvsr_resblock24_chain_f16w): the shapes of the mid_channels = 24 models --
+ * conv_shuffle2 c = 24 only, conf_alpha cout = 24 only (-1 / an error otherwise). */
+int refvsr_conv24_f16w_blob_bytes(int c0, int c1);
+int refvsr_conv32_f16w_blob_bytes(int c0, int c1);
+int refvsr_conv_shuffle2_f16w_blob_bytes(int c);
+int refvsr_conv24_f16w(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
+                       const void* mul, const void* res, float post_slope, void* out, void* stream);
+int refvsr_conv24_batch_f16w(const void* const* src0, int c0, const void* const* src1, int c1, int batch, int h, int w, const void* blob,
+                             float act_slope, const void* const* mul, const void* const* res, float post_slope, void* const* out,
+                             void* stream);
+int refvsr_conv32_f16w(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
+                       const void* mul, const void* res, float post_slope, void* out, void* stream);
+int refvsr_conv_shuffle2_f16w(const void* src, int c, int h, int w, const void* blobs, float act_slope, void* out, void* stream);
+int refvsr_conv_shuffle2_batch_f16w(const void* const* src, int batch, int c, int h, int w, const void* blobs, float act_slope,
+                                    void* const* out, void* stream);
+int refvsr_conf_alpha_f16w(const float* conf_a, const float* conf_b, int h, int w, int up, const float* w0, const float* b0,
+                           float slope0, const void* blob, int cout, float slope1, void* alpha, float* conf_max, void* stream);
+int refvsr_conf_alpha_batch_f16w(const float* const* conf_a, const float* const* conf_b, int batch, int h, int w, int up, const float* w0,
+                                 const float* b0, float slope0, const void* blob, int cout, float slope1, void* const* alpha,
+                                 float* const* conf_max, void* stream);
 /* Debug knob (no reference counterpart): when buf != NULL every workgroup of the PROBE instantiations of the fused-block kernels records s_memtime
  * stamps (entry, loads issued, loads landed, conv1 K loop, conv1 epilogue, barrier, conv2 K loop, stores issued) of its
  * iter-th tile at buf[12 * workgroup + i] (uint64; [8], [9] = 100 MHz s_memrealtime at entry / exit, [10] = s_memtime at exit) -- tools/probe_resblock.py.  NULL switches it off (default). */

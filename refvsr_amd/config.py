@@ -91,6 +91,7 @@ def base_config(project='', mode='', config_='', data='', LRS='', batch_size=8):
     c.overlap_streams = True    # forward-branch step on a side HIP stream, concurrent with the new frame's preparation
     c.fuse_resblocks = True     # conv-act-conv+residual pairs in one launch where the LDS budget allows
     c.result_dtype = 'float32'  # 'float16' | 'uint8': the output head stores rint(255 v) itself (extension; host consumers quantise anyway)
+    c.weight_precision = 'hi_lo'  # 'fp16' | 'amp': plain fp16 conv weights, the reference's AMP arithmetic (resolve_weight_precision)
     return c
 
 
@@ -119,6 +120,28 @@ def get_config(project='', mode='', config='', data='', LRS='', batch_size=8):
     c.mid_channels = m['mid_channels']
     c.reset_branch = c.frame_itr_num if m['reset'] == 'itr' else None
     return c
+
+
+WEIGHT_PRECISIONS = ('hi_lo', 'fp16', 'amp')
+
+
+def resolve_weight_precision(c):
+    """config.weight_precision -> 'hi_lo' | 'fp16' (extension).
+      'hi_lo' (default): every fp16-operand conv carries hi + lo weights (~22 bits).
+      'fp16' : plain fp16 conv weights -- what the reference computes under fp16 autocast (is_amp, trainers/trainer.py:237-239);
+               the engine's output equals, bit for bit, the default engine's output on round16(sd) (weights.round16).
+      'amp'  : 'fp16' when config.is_amp, else 'hi_lo'.
+    A resolved 'fp16' exists for the mid_channels = 24 family only (RefVSR_small*); ValueError elsewhere.  Read once, when the
+    engine's weights are packed: torch.autocast does not switch it."""
+    mode = c.get('weight_precision') or 'hi_lo'
+    if mode not in WEIGHT_PRECISIONS:
+        raise ValueError('weight_precision must be one of %s, got %r' % (', '.join(WEIGHT_PRECISIONS), mode))
+    if mode == 'amp':
+        mode = 'fp16' if c.get('is_amp') else 'hi_lo'
+    if mode == 'fp16' and (c.get('mid_channels') != 24 or c.get('network') == 'RefVSR_IR'):
+        raise ValueError("weight_precision 'fp16' is supported for the mid_channels = 24 RefVSR models only "
+                         "(config %r: network %r, mid_channels %r)" % (c.get('config'), c.get('network'), c.get('mid_channels')))
+    return mode
 
 
 def set_scale(c, scale):

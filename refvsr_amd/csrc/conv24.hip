@@ -62,6 +62,11 @@ struct C24Args {
     const float* bconf_a[REFVSR_MAX_MAPS]; const float* bconf_b[REFVSR_MAX_MAPS]; float* bconf_max[REFVSR_MAX_MAPS];
 };
 
+// Fragments per K-step.  Weight format WF = 0: hi + lo (COUT = 24: [hi 0-15] [lo 0-15] [hi 16-23 | lo 16-23]; 32 | 48: [hi | lo] per
+// 16 channels; 3: rows 0-2 hi, rows 8-10 lo).  WF = 1 (ABI 15, config.weight_precision = 'fp16'): plain fp16 weights, one fragment
+// per 16 output channels -- 24: [rows 0-15] [rows 16-23 + 8 zero rows]; 32 | 48: [rows 16 m ..] -- no lo term, no fold.
+constexpr int c24_nf(int cout, int wf) { return wf ? (cout == 24 ? 2 : cout / 16) : cout == 24 ? 3 : cout == 3 ? 1 : cout / 8; }
+
 __device__ __forceinline__ float c24_fold1(const float a) {       // lane l: a[l] + a[l ^ 32] (see resblock24.hip:rb_fold1)
     const unsigned u = __float_as_uint(a);
     const auto pr = __builtin_amdgcn_permlane32_swap(u, u, false, false);
@@ -82,15 +87,18 @@ __device__ __forceinline__ float c24_fold1(const float a) {       // lane l: a[l
 // plan, 70 KB tile: one sixteen-wave workgroup per CU) and stores them into the 48-channel maps at byte offset 48 z.
 // MM = 1 (ABI 11): multi-map launch -- p.batch maps behind one weight fill (the batched entry points; the single-map instantiations
 // are untouched by it).
-template <int COUT, int NCG0, int NCG1, int NWV, int TH, int WPS, int SHUF = 0, int CONF = 0, int HALF = 0, int MM = 0>
+// WF: weight format (c24_nf); WF = 1 issues the hi MFMAs of WF = 0 in the same order on the same accumulators and drops the lo ones
+// (which add exact zeros for fp16-representable weights): bit-identical results on such weights.
+template <int COUT, int NCG0, int NCG1, int NWV, int TH, int WPS, int SHUF = 0, int CONF = 0, int HALF = 0, int MM = 0, int WF = 0>
 __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(WPS, WPS))) void conv24_kernel(C24Args p) {
+    static_assert(WF == 0 || COUT != 3, "output head: one fragment in either format");
     static_assert(HALF == 0 || (COUT == 24 && SHUF == 0 && CONF == 0), "channel-half variant: 24 computed channels per workgroup");
     static_assert(MM == 0 || (HALF == 0 && COUT != 3), "multi-map variant");
     static_assert(SHUF == 0 || (COUT == 48 && (SHUF == 24 || SHUF == 48) && NCG0 * 8 == SHUF && NCG1 == 0), "pixel-shuffle variant");
     static_assert(CONF == 0 || (NCG0 == 2 && NCG1 == 0 && SHUF == 0), "confidence variant: 16-channel single source");
     constexpr int NCG = NCG0 + NCG1, PS = NCG | 1, PXB = PS * 16, ROWB = C24_XW * PXB;
     constexpr int S = c24_steps(NCG), NPAT = c24_npat(NCG);
-    constexpr int NF = COUT == 24 ? 3 : COUT == 3 ? 1 : COUT / 8;   // fragments per K-step (COUT = 32 | 48: [hi | lo] per 16 channels)
+    constexpr int NF = c24_nf(COUT, WF);                             // fragments per K-step
     constexpr int NM = COUT == 24 ? 2 : COUT == 3 ? 1 : COUT / 16;  // accumulator tiles per pixel group
     constexpr int BIASB = COUT == 48 ? 256 : 128;
     constexpr int WB = S * NF * 1024, BIAS = WB, XT = WB + BIASB;
@@ -380,7 +388,15 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(WPS, W
                 }
             };
             auto mfma = [&](const uint4 (&af)[NF], const uint4 (&bf)[T]) {
-                if constexpr (COUT == 24) {                          // [hi 0-15] [lo 0-15] [hi 16-23 | lo 16-23]
+                if constexpr (WF == 1) {                             // [rows 16 m ..] per accumulator tile
+#pragma unroll
+                    for (int m = 0; m < NM; ++m) {
+                        const f16x8 av = *reinterpret_cast<const f16x8*>(&af[m]);
+#pragma unroll
+                        for (int t = 0; t < T; ++t)
+                            acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, *reinterpret_cast<const f16x8*>(&bf[t]), acc[m][t], 0, 0, 0);
+                    }
+                } else if constexpr (COUT == 24) {                   // [hi 0-15] [lo 0-15] [hi 16-23 | lo 16-23]
                     const f16x8 a_hi = *reinterpret_cast<const f16x8*>(&af[0]);
                     const f16x8 a_lo = *reinterpret_cast<const f16x8*>(&af[1]);
                     const f16x8 a_mx = *reinterpret_cast<const f16x8*>(&af[2]);
@@ -407,7 +423,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(WPS, W
                 }
             };
             if constexpr (NF <= 4) {
-                // two fragment sets: the reads of step s + 1 are issued above the MFMAs of step s
+                // two fragment sets: the reads of step s + 1 are issued above the MFMAs of step s (WF = 1: every shape, COUT = 48 too)
                 load(std::integral_constant<int, 0>{}, fa[0], fb[0]);
                 c24_static_for([&](auto sc) {
                     constexpr int s = decltype(sc)::value;
@@ -490,7 +506,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(WPS, W
                 for (int m = 0; m < NM; ++m) {
                     f32x4 y = acc[m][t];
                     if constexpr (COUT == 24) {
-                        if (m == 1) y = (f32x4){c24_fold1(y[0]), c24_fold1(y[1]), c24_fold1(y[2]), c24_fold1(y[3])};
+                        if (WF == 0 && m == 1) y = (f32x4){c24_fold1(y[0]), c24_fold1(y[1]), c24_fold1(y[2]), c24_fold1(y[3])};
                     } else {
                         const unsigned eo = (unsigned)(RW(t) * rowb_o) + oo + CG(t) * 16 * OPX;
                         if (p.mul && okt[t]) mv[m][t] = *reinterpret_cast<const f16x4*>(mulp + oorg + eo + 32 * m);
@@ -523,21 +539,21 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(WPS, W
 #undef CG
 }
 
-template <int COUT, int NCG0, int NCG1, int NWV, int TH, int WPS, int SHUF = 0, int CONF = 0, int HALF = 0, int MM = 0>
+template <int COUT, int NCG0, int NCG1, int NWV, int TH, int WPS, int SHUF = 0, int CONF = 0, int HALF = 0, int MM = 0, int WF = 0>
 static int launch_c24(C24Args& a, hipStream_t st) {
     constexpr int NZ = HALF ? 2 : SHUF == 0 ? 1 : SHUF == 24 ? 2 : 4;   // row groups of the pixel-shuffle / channel-half variants (blockIdx.y)
     constexpr int NCG = NCG0 + NCG1, PS = NCG | 1;
-    constexpr int LDS = c24_steps(NCG) * (COUT == 24 ? 3 : COUT == 3 ? 1 : COUT / 8) * 1024 + (COUT == 48 ? 256 : 128) + (TH + 2) * C24_XW * PS * 16 +
+    constexpr int LDS = c24_steps(NCG) * c24_nf(COUT, WF) * 1024 + (COUT == 48 ? 256 : 128) + (TH + 2) * C24_XW * PS * 16 +
                         (CONF ? 2 * (TH + 4) * (C24_XW + 2) * 4 + 18 * 16 * 4 + 64 : 0);
     static_assert(LDS <= 160 * 1024, "LDS budget");
     static bool attr_done[RV_MAX_DEVICES] = {};
     static int occ_dev[RV_MAX_DEVICES] = {};
     const int dev = rv_device();
     if (!attr_done[dev]) {
-        RV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv24_kernel<COUT, NCG0, NCG1, NWV, TH, WPS, SHUF, CONF, HALF, MM>),
+        RV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv24_kernel<COUT, NCG0, NCG1, NWV, TH, WPS, SHUF, CONF, HALF, MM, WF>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
         int occ = 0;
-        RV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv24_kernel<COUT, NCG0, NCG1, NWV, TH, WPS, SHUF, CONF, HALF, MM>, NWV * 64, LDS));
+        RV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv24_kernel<COUT, NCG0, NCG1, NWV, TH, WPS, SHUF, CONF, HALF, MM, WF>, NWV * 64, LDS));
         occ_dev[dev] = occ < 1 ? 1 : occ;
         attr_done[dev] = true;
     }
@@ -547,7 +563,7 @@ static int launch_c24(C24Args& a, hipStream_t st) {
     int cap = (rv_stream_cus(st) * occ_dev[dev] / NZ) & ~7;
     if (cap < 8) cap = 8;
     a.grid = a.n_tiles < cap ? a.n_tiles : cap;
-    hipLaunchKernelGGL((conv24_kernel<COUT, NCG0, NCG1, NWV, TH, WPS, SHUF, CONF, HALF, MM>), dim3(a.grid, NZ), dim3(NWV * 64), LDS, st, a);
+    hipLaunchKernelGGL((conv24_kernel<COUT, NCG0, NCG1, NWV, TH, WPS, SHUF, CONF, HALF, MM, WF>), dim3(a.grid, NZ), dim3(NWV * 64), LDS, st, a);
     RV_LAUNCH_CHECK();
     return 0;
 }
@@ -580,6 +596,21 @@ extern "C" int refvsr_conv_shuffle2_blob_bytes(int c) {
     return (c == 24 ? 2 : 4) * (c24_steps(c / 8) * 6 * 1024 + 256);
 }
 
+// Blob sizes of the fp16 weight format (ABI 15, refvsr_*_f16w; packing.py:pack_conv24 / pack_conv_shuffle2 with wfmt='fp16'):
+// c24_nf(cout, 1) fragments per K-step, same bias tail.  The twins exist for the shapes the mid_channels = 24 family launches.
+extern "C" int refvsr_conv24_f16w_blob_bytes(int c0, int c1) {
+    if (!refvsr_conv24_supported(c0, c1)) return -1;
+    return c24_steps((c0 + c1) / 8) * c24_nf(24, 1) * 1024 + 128;
+}
+extern "C" int refvsr_conv32_f16w_blob_bytes(int c0, int c1) {
+    if (!refvsr_conv32_supported(c0, c1)) return -1;
+    return c24_steps((c0 + c1) / 8) * c24_nf(32, 1) * 1024 + 128;
+}
+extern "C" int refvsr_conv_shuffle2_f16w_blob_bytes(int c) {
+    if (c != 24) return -1;
+    return 2 * (c24_steps(c / 8) * c24_nf(48, 1) * 1024 + 256);
+}
+
 extern "C" int refvsr_conv24_kblock(int ncg, int s, int q) {
     if (c24_steps(ncg) == 0 || s < 0 || s >= c24_steps(ncg) || q < 0 || q > 3) return -2;
     return c24_kblock(ncg, s, q);
@@ -601,22 +632,32 @@ static int c24_fill(C24Args& a, const char* who, int cout, const void* src0, con
     return 0;
 }
 
-extern "C" int refvsr_conv24(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
-                             const void* mul, const void* res, float post_slope, void* out, void* stream) {
+template <int WF>
+static int c24i_conv24(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
+                       const void* mul, const void* res, float post_slope, void* out, void* stream) {
     RV_CHECK(refvsr_conv24_supported(c0, c1), "conv24: %d + %d input channels not supported", c0, c1);
     C24Args a;
     if (c24_fill(a, "conv24", 24, src0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    if (c0 == 24 && c1 == 0) return launch_c24<24, 3, 0, 8, 8, 4>(a, st);
-    if (c0 == 16 && c1 == 0) return launch_c24<24, 2, 0, 8, 8, 4>(a, st);
-    if (c0 == 8 && c1 == 24) return launch_c24<24, 1, 3, 8, 8, 4>(a, st);
-    return launch_c24<24, 3, 3, 8, 8, 4>(a, st);
+    if (c0 == 24 && c1 == 0) return launch_c24<24, 3, 0, 8, 8, 4, 0, 0, 0, 0, WF>(a, st);
+    if (c0 == 16 && c1 == 0) return launch_c24<24, 2, 0, 8, 8, 4, 0, 0, 0, 0, WF>(a, st);
+    if (c0 == 8 && c1 == 24) return launch_c24<24, 1, 3, 8, 8, 4, 0, 0, 0, 0, WF>(a, st);
+    return launch_c24<24, 3, 3, 8, 8, 4, 0, 0, 0, 0, WF>(a, st);
+}
+extern "C" int refvsr_conv24(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
+                             const void* mul, const void* res, float post_slope, void* out, void* stream) {
+    return c24i_conv24<0>(src0, c0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out, stream);
+}
+extern "C" int refvsr_conv24_f16w(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
+                                  const void* mul, const void* res, float post_slope, void* out, void* stream) {
+    return c24i_conv24<1>(src0, c0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out, stream);
 }
 
 // The same conv over `batch` maps of one geometry in ONE launch (ABI 11): the per-map operands are host arrays of device pointers.
-extern "C" int refvsr_conv24_batch(const void* const* src0, int c0, const void* const* src1, int c1, int batch, int h, int w, const void* blob,
-                                   float act_slope, const void* const* mul, const void* const* res, float post_slope, void* const* out,
-                                   void* stream) {
+template <int WF>
+static int c24i_conv24_batch(const void* const* src0, int c0, const void* const* src1, int c1, int batch, int h, int w, const void* blob,
+                             float act_slope, const void* const* mul, const void* const* res, float post_slope, void* const* out,
+                             void* stream) {
     RV_CHECK(refvsr_conv24_supported(c0, c1), "conv24_batch: %d + %d input channels not supported", c0, c1);
     RV_CHECK(src0 && out && batch >= 1 && batch <= REFVSR_MAX_MAPS, "conv24_batch: 1..%d maps per launch", REFVSR_MAX_MAPS);
     RV_CHECK((c1 == 0) == (src1 == nullptr), "conv24_batch: src1 / c1 mismatch");
@@ -633,21 +674,40 @@ extern "C" int refvsr_conv24_batch(const void* const* src0, int c0, const void* 
         a.bmul[b] = mul ? (const unsigned char*)mul[b] : nullptr; a.bres[b] = res ? (const unsigned char*)res[b] : nullptr;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (c0 == 24 && c1 == 0) return launch_c24<24, 3, 0, 8, 8, 4, 0, 0, 0, 1>(a, st);
-    if (c0 == 16 && c1 == 0) return launch_c24<24, 2, 0, 8, 8, 4, 0, 0, 0, 1>(a, st);
-    if (c0 == 8 && c1 == 24) return launch_c24<24, 1, 3, 8, 8, 4, 0, 0, 0, 1>(a, st);
-    return launch_c24<24, 3, 3, 8, 8, 4, 0, 0, 0, 1>(a, st);
+    if (c0 == 24 && c1 == 0) return launch_c24<24, 3, 0, 8, 8, 4, 0, 0, 0, 1, WF>(a, st);
+    if (c0 == 16 && c1 == 0) return launch_c24<24, 2, 0, 8, 8, 4, 0, 0, 0, 1, WF>(a, st);
+    if (c0 == 8 && c1 == 24) return launch_c24<24, 1, 3, 8, 8, 4, 0, 0, 0, 1, WF>(a, st);
+    return launch_c24<24, 3, 3, 8, 8, 4, 0, 0, 0, 1, WF>(a, st);
+}
+extern "C" int refvsr_conv24_batch(const void* const* src0, int c0, const void* const* src1, int c1, int batch, int h, int w, const void* blob,
+                                   float act_slope, const void* const* mul, const void* const* res, float post_slope, void* const* out,
+                                   void* stream) {
+    return c24i_conv24_batch<0>(src0, c0, src1, c1, batch, h, w, blob, act_slope, mul, res, post_slope, out, stream);
+}
+extern "C" int refvsr_conv24_batch_f16w(const void* const* src0, int c0, const void* const* src1, int c1, int batch, int h, int w, const void* blob,
+                                        float act_slope, const void* const* mul, const void* const* res, float post_slope, void* const* out,
+                                        void* stream) {
+    return c24i_conv24_batch<1>(src0, c0, src1, c1, batch, h, w, blob, act_slope, mul, res, post_slope, out, stream);
 }
 
 // 32 output channels (AlignedConv2d, RefVSR_/alignment.py:18-24,53-100: the 3 -> 32 stem and the 32 -> 32 convs of its ResBlocks)
-extern "C" int refvsr_conv32(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
-                             const void* mul, const void* res, float post_slope, void* out, void* stream) {
+template <int WF>
+static int c24i_conv32(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
+                       const void* mul, const void* res, float post_slope, void* out, void* stream) {
     RV_CHECK(refvsr_conv32_supported(c0, c1), "conv32: %d + %d input channels not supported", c0, c1);
     C24Args a;
     if (c24_fill(a, "conv32", 32, src0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    if (c0 == 32) return launch_c24<32, 4, 0, 8, 8, 4>(a, st);
-    return launch_c24<32, 1, 0, 8, 8, 4>(a, st);
+    if (c0 == 32) return launch_c24<32, 4, 0, 8, 8, 4, 0, 0, 0, 0, WF>(a, st);
+    return launch_c24<32, 1, 0, 8, 8, 4, 0, 0, 0, 0, WF>(a, st);
+}
+extern "C" int refvsr_conv32(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
+                             const void* mul, const void* res, float post_slope, void* out, void* stream) {
+    return c24i_conv32<0>(src0, c0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out, stream);
+}
+extern "C" int refvsr_conv32_f16w(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
+                                  const void* mul, const void* res, float post_slope, void* out, void* stream) {
+    return c24i_conv32<1>(src0, c0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out, stream);
 }
 
 extern "C" int refvsr_conv48(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
@@ -669,18 +729,28 @@ extern "C" int refvsr_conv48(const void* src0, int c0, const void* src1, int c1,
 
 // act(C -> 4 C 3x3 conv + bias) through F.pixel_shuffle(2) on fp16 HWC maps: src [h][w][C] -> out [2h][2w][C].  blobs: the 2 (C = 24) or
 // 4 (C = 48) row-group blobs of refvsr_amd/packing.py:pack_conv_shuffle2, back to back.
-extern "C" int refvsr_conv_shuffle2(const void* src, int c, int h, int w, const void* blobs, float act_slope, void* out, void* stream) {
+template <int WF>
+static int c24i_conv_shuffle2(const void* src, int c, int h, int w, const void* blobs, float act_slope, void* out, void* stream) {
     RV_CHECK(refvsr_conv_shuffle2_supported(c), "conv_shuffle2: %d channels not supported", c);
     C24Args a;
     if (c24_fill(a, "conv_shuffle2", 4 * c, src, nullptr, 0, h, w, blobs, act_slope, nullptr, nullptr, 1.0f, out)) return 1;   // (4 c: the 2h x 2w x c output map)
     hipStream_t st = (hipStream_t)stream;
-    if (c == 24) return launch_c24<48, 3, 0, 8, 8, 4, 24>(a, st);
-    return launch_c24<48, 6, 0, 16, 16, 4, 48>(a, st);
+    if (c == 24) return launch_c24<48, 3, 0, 8, 8, 4, 24, 0, 0, 0, WF>(a, st);
+    if constexpr (WF == 0) return launch_c24<48, 6, 0, 16, 16, 4, 48>(a, st);
+    RV_CHECK(false, "conv_shuffle2_f16w: 24 channels only (the mid_channels = 24 family)");
+    return 1;
+}
+extern "C" int refvsr_conv_shuffle2(const void* src, int c, int h, int w, const void* blobs, float act_slope, void* out, void* stream) {
+    return c24i_conv_shuffle2<0>(src, c, h, w, blobs, act_slope, out, stream);
+}
+extern "C" int refvsr_conv_shuffle2_f16w(const void* src, int c, int h, int w, const void* blobs, float act_slope, void* out, void* stream) {
+    return c24i_conv_shuffle2<1>(src, c, h, w, blobs, act_slope, out, stream);
 }
 
 // PixelShufflePack over `batch` maps in ONE launch (ABI 11, C = 24: upsample1 of the RAP steps, RefVSR.py:138)
-extern "C" int refvsr_conv_shuffle2_batch(const void* const* src, int batch, int c, int h, int w, const void* blobs, float act_slope,
-                                          void* const* out, void* stream) {
+template <int WF>
+static int c24i_conv_shuffle2_batch(const void* const* src, int batch, int c, int h, int w, const void* blobs, float act_slope,
+                                    void* const* out, void* stream) {
     RV_CHECK(c == 24, "conv_shuffle2_batch: %d channels not supported (24)", c);
     RV_CHECK(src && out && batch >= 1 && batch <= REFVSR_MAX_MAPS, "conv_shuffle2_batch: 1..%d maps per launch", REFVSR_MAX_MAPS);
     C24Args a;
@@ -691,7 +761,15 @@ extern "C" int refvsr_conv_shuffle2_batch(const void* const* src, int batch, int
         for (int c2 = 0; c2 < batch; ++c2) RV_CHECK(src[c2] != out[b] && (c2 == b || out[c2] != out[b]), "conv_shuffle2_batch: in-place operation is not supported");
         a.bsrc0[b] = (const unsigned char*)src[b]; a.bout[b] = (unsigned char*)out[b];
     }
-    return launch_c24<48, 3, 0, 8, 8, 4, 24, 0, 0, 1>(a, (hipStream_t)stream);
+    return launch_c24<48, 3, 0, 8, 8, 4, 24, 0, 0, 1, WF>(a, (hipStream_t)stream);
+}
+extern "C" int refvsr_conv_shuffle2_batch(const void* const* src, int batch, int c, int h, int w, const void* blobs, float act_slope,
+                                          void* const* out, void* stream) {
+    return c24i_conv_shuffle2_batch<0>(src, batch, c, h, w, blobs, act_slope, out, stream);
+}
+extern "C" int refvsr_conv_shuffle2_batch_f16w(const void* const* src, int batch, int c, int h, int w, const void* blobs, float act_slope,
+                                               void* const* out, void* stream) {
+    return c24i_conv_shuffle2_batch<1>(src, batch, c, h, w, blobs, act_slope, out, stream);
 }
 
 // The confidence fusions of AA_AF_conf_prop / compute_up in ONE launch (RefVSR.py:47-52 conf_fusion / conf_fusion2 /
@@ -702,8 +780,9 @@ extern "C" int refvsr_conv_shuffle2_batch(const void* const* src, int batch, int
 // blob of refvsr_conv24 / refvsr_conv48 (cout = 24 | 48); alpha: fp16 HWC [up h][up w][cout]; conf_max (optional, up = 1):
 // max(conf_a, conf_b) [h][w] (RefVSR.py:147).  Bit-identical to torch.cat + [refvsr_resize +] refvsr_conv_direct_f32 +
 // refvsr_conv24 / 48 [+ refvsr_max2].
-extern "C" int refvsr_conf_alpha(const float* conf_a, const float* conf_b, int h, int w, int up, const float* w0, const float* b0,
-                                 float slope0, const void* blob, int cout, float slope1, void* alpha, float* conf_max, void* stream) {
+template <int WF>
+static int c24i_conf_alpha(const float* conf_a, const float* conf_b, int h, int w, int up, const float* w0, const float* b0,
+                           float slope0, const void* blob, int cout, float slope1, void* alpha, float* conf_max, void* stream) {
     RV_CHECK(conf_a && conf_b && w0 && b0 && alpha, "conf_alpha: null argument");
     RV_CHECK(up == 1 || up == 2, "conf_alpha: up must be 1 or 2");
     RV_CHECK(cout == 24 || cout == 48, "conf_alpha: %d output channels not supported (24 | 48)", cout);
@@ -714,14 +793,25 @@ extern "C" int refvsr_conf_alpha(const float* conf_a, const float* conf_b, int h
     a.src0 = nullptr;
     a.conf_a = conf_a; a.conf_b = conf_b; a.cw0 = w0; a.cb0 = b0; a.conf_max = conf_max; a.ch = h; a.cw = w; a.slope0 = slope0;
     hipStream_t st = (hipStream_t)stream;
-    if (cout == 24) return up == 1 ? launch_c24<24, 2, 0, 8, 8, 4, 0, 1>(a, st) : launch_c24<24, 2, 0, 8, 8, 4, 0, 2>(a, st);
-    return up == 1 ? launch_c24<48, 2, 0, 8, 8, 4, 0, 1>(a, st) : launch_c24<48, 2, 0, 8, 8, 4, 0, 2>(a, st);
+    if (cout == 24) return up == 1 ? launch_c24<24, 2, 0, 8, 8, 4, 0, 1, 0, 0, WF>(a, st) : launch_c24<24, 2, 0, 8, 8, 4, 0, 2, 0, 0, WF>(a, st);
+    if constexpr (WF == 0) return up == 1 ? launch_c24<48, 2, 0, 8, 8, 4, 0, 1>(a, st) : launch_c24<48, 2, 0, 8, 8, 4, 0, 2>(a, st);
+    RV_CHECK(false, "conf_alpha_f16w: 24 output channels only (the mid_channels = 24 family)");
+    return 1;
+}
+extern "C" int refvsr_conf_alpha(const float* conf_a, const float* conf_b, int h, int w, int up, const float* w0, const float* b0,
+                                 float slope0, const void* blob, int cout, float slope1, void* alpha, float* conf_max, void* stream) {
+    return c24i_conf_alpha<0>(conf_a, conf_b, h, w, up, w0, b0, slope0, blob, cout, slope1, alpha, conf_max, stream);
+}
+extern "C" int refvsr_conf_alpha_f16w(const float* conf_a, const float* conf_b, int h, int w, int up, const float* w0, const float* b0,
+                                      float slope0, const void* blob, int cout, float slope1, void* alpha, float* conf_max, void* stream) {
+    return c24i_conf_alpha<1>(conf_a, conf_b, h, w, up, w0, b0, slope0, blob, cout, slope1, alpha, conf_max, stream);
 }
 
 // The confidence fusion over `batch` pairs of maps in ONE launch (ABI 11, cout = 24)
-extern "C" int refvsr_conf_alpha_batch(const float* const* conf_a, const float* const* conf_b, int batch, int h, int w, int up, const float* w0,
-                                       const float* b0, float slope0, const void* blob, int cout, float slope1, void* const* alpha,
-                                       float* const* conf_max, void* stream) {
+template <int WF>
+static int c24i_conf_alpha_batch(const float* const* conf_a, const float* const* conf_b, int batch, int h, int w, int up, const float* w0,
+                                 const float* b0, float slope0, const void* blob, int cout, float slope1, void* const* alpha,
+                                 float* const* conf_max, void* stream) {
     RV_CHECK(conf_a && conf_b && w0 && b0 && alpha && batch >= 1 && batch <= REFVSR_MAX_MAPS, "conf_alpha_batch: bad args (1..%d maps)", REFVSR_MAX_MAPS);
     RV_CHECK(up == 1 || up == 2, "conf_alpha_batch: up must be 1 or 2");
     RV_CHECK(cout == 24, "conf_alpha_batch: %d output channels not supported (24)", cout);
@@ -738,7 +828,17 @@ extern "C" int refvsr_conf_alpha_batch(const float* const* conf_a, const float* 
         a.bout[b] = (unsigned char*)alpha[b];
     }
     hipStream_t st = (hipStream_t)stream;
-    return up == 1 ? launch_c24<24, 2, 0, 8, 8, 4, 0, 1, 0, 1>(a, st) : launch_c24<24, 2, 0, 8, 8, 4, 0, 2, 0, 1>(a, st);
+    return up == 1 ? launch_c24<24, 2, 0, 8, 8, 4, 0, 1, 0, 1, WF>(a, st) : launch_c24<24, 2, 0, 8, 8, 4, 0, 2, 0, 1, WF>(a, st);
+}
+extern "C" int refvsr_conf_alpha_batch(const float* const* conf_a, const float* const* conf_b, int batch, int h, int w, int up, const float* w0,
+                                       const float* b0, float slope0, const void* blob, int cout, float slope1, void* const* alpha,
+                                       float* const* conf_max, void* stream) {
+    return c24i_conf_alpha_batch<0>(conf_a, conf_b, batch, h, w, up, w0, b0, slope0, blob, cout, slope1, alpha, conf_max, stream);
+}
+extern "C" int refvsr_conf_alpha_batch_f16w(const float* const* conf_a, const float* const* conf_b, int batch, int h, int w, int up, const float* w0,
+                                            const float* b0, float slope0, const void* blob, int cout, float slope1, void* const* alpha,
+                                            float* const* conf_max, void* stream) {
+    return c24i_conf_alpha_batch<1>(conf_a, conf_b, batch, h, w, up, w0, b0, slope0, blob, cout, slope1, alpha, conf_max, stream);
 }
 
 // The output head in ONE launch (RefVSR.py:92,118,288,297: conv_last 3x3 C -> 3, + F.interpolate(lr_centre, scale, bicubic).clamp(0, 1),

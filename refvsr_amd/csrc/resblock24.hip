@@ -54,6 +54,14 @@ constexpr int RB_BLOB = RB_BIAS + 256;                    // 43264
 constexpr int RB_XT = RB_BLOB;                            // LDS offset of the x tile
 constexpr int rb_lds(int th) { return RB_XT + rb_xbytes(th); }         // 64000 -> two workgroups per CU | 77824 -> one
 static_assert(RB_BLOB == REFVSR_RESBLOCK24_BLOB_BYTES, "blob size is part of the C-ABI");
+// Weight format WF (ABI 15): 0 = hi + lo in three fragments per K-step (above); 1 = plain fp16 weights in TWO fragments per K-step,
+// [rows 0-15] [rows 16-23 + 8 zero rows] -- no lo term, no fold (config.weight_precision = 'fp16', packing.py:pack_resblock24_f16w)
+constexpr int rb_nf(int wf) { return wf ? 2 : RB_NF; }
+constexpr int rb_wb(int wf) { return RB_S * rb_nf(wf) * 1024; }      // 21504 | 14336
+constexpr int rb_bias(int wf) { return 2 * rb_wb(wf); }
+constexpr int rb_blob(int wf) { return rb_bias(wf) + 256; }          // 43264 | 28928
+constexpr int rb_lds_wf(int th, int wf) { return rb_blob(wf) + rb_xbytes(th); }   // WF = 1: 49664 (TH = 8) | 63488 (TH = 16)
+static_assert(rb_blob(1) == REFVSR_RESBLOCK24_F16W_BLOB_BYTES, "blob size is part of the C-ABI");
 }  // namespace
 
 struct RB24Args {
@@ -87,31 +95,43 @@ __device__ __forceinline__ f32x4 rb_fold_halves(const f32x4 a) {
 
 // K loop of one conv: T pixel groups of this wave, fragments at smem + wofs, B windows at smem + pb[t] (+ immediates).
 // Software pipelined over two fragment sets (the reads of step s+1 are issued above the MFMAs of step s).
-template <int T, int TA>
+// WF = 1: two fragments per K-step, acc0 += [rows 0-15], acc1 += [rows 16-23 | zero rows] -- the hi MFMAs of WF = 0 in the same
+// order on the same accumulators, without the lo MFMAs (which add exact zeros for fp16-representable weights).
+template <int T, int TA, int WF = 0>
 __device__ __forceinline__ void rb_kloop(f32x4 (&acc0)[TA], f32x4 (&acc1)[TA], const unsigned char* smem, const int wofs,
                                          const int la, const int (&pb)[TA], const int delta6) {
     static_assert(T <= TA, "group count");
-    uint4 a[2][RB_NF], b[2][T];
-    auto load = [&](auto sc, uint4 (&af)[RB_NF], uint4 (&bf)[T]) {
+    constexpr int NF = rb_nf(WF);
+    uint4 a[2][NF], b[2][T];
+    auto load = [&](auto sc, uint4 (&af)[NF], uint4 (&bf)[T]) {
         constexpr int s = decltype(sc)::value;
 #pragma unroll
-        for (int f = 0; f < RB_NF; ++f) af[f] = *reinterpret_cast<const uint4*>(smem + wofs + (s * RB_NF + f) * 1024 + la);
+        for (int f = 0; f < NF; ++f) af[f] = *reinterpret_cast<const uint4*>(smem + wofs + (s * NF + f) * 1024 + la);
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             if constexpr (s < 6) bf[t] = *reinterpret_cast<const uint4*>(smem + pb[t] + (s >> 1) * RB_ROWB + (s & 1) * 64);
             else bf[t] = *reinterpret_cast<const uint4*>(smem + pb[t] + delta6);
         }
     };
-    auto mfma = [&](const uint4 (&af)[RB_NF], const uint4 (&bf)[T]) {
-        const f16x8 a_hi = *reinterpret_cast<const f16x8*>(&af[0]);
-        const f16x8 a_lo = *reinterpret_cast<const f16x8*>(&af[1]);
-        const f16x8 a_mx = *reinterpret_cast<const f16x8*>(&af[2]);
+    auto mfma = [&](const uint4 (&af)[NF], const uint4 (&bf)[T]) {
+        if constexpr (WF == 0) {
+            const f16x8 a_hi = *reinterpret_cast<const f16x8*>(&af[0]);
+            const f16x8 a_lo = *reinterpret_cast<const f16x8*>(&af[1]);
+            const f16x8 a_mx = *reinterpret_cast<const f16x8*>(&af[2]);
 #pragma unroll
-        for (int t = 0; t < T; ++t) acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, *reinterpret_cast<const f16x8*>(&bf[t]), acc0[t], 0, 0, 0);
+            for (int t = 0; t < T; ++t) acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, *reinterpret_cast<const f16x8*>(&bf[t]), acc0[t], 0, 0, 0);
 #pragma unroll
-        for (int t = 0; t < T; ++t) acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_mx, *reinterpret_cast<const f16x8*>(&bf[t]), acc1[t], 0, 0, 0);
+            for (int t = 0; t < T; ++t) acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_mx, *reinterpret_cast<const f16x8*>(&bf[t]), acc1[t], 0, 0, 0);
 #pragma unroll
-        for (int t = 0; t < T; ++t) acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_lo, *reinterpret_cast<const f16x8*>(&bf[t]), acc0[t], 0, 0, 0);
+            for (int t = 0; t < T; ++t) acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_lo, *reinterpret_cast<const f16x8*>(&bf[t]), acc0[t], 0, 0, 0);
+        } else {
+            const f16x8 a_0 = *reinterpret_cast<const f16x8*>(&af[0]);
+            const f16x8 a_1 = *reinterpret_cast<const f16x8*>(&af[1]);
+#pragma unroll
+            for (int t = 0; t < T; ++t) acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_0, *reinterpret_cast<const f16x8*>(&bf[t]), acc0[t], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < T; ++t) acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_1, *reinterpret_cast<const f16x8*>(&bf[t]), acc1[t], 0, 0, 0);
+        }
     };
     load(std::integral_constant<int, 0>{}, a[0], b[0]);
     load(std::integral_constant<int, 1>{}, a[1], b[1]);
@@ -215,10 +235,13 @@ __device__ __forceinline__ uint2 rb_pack(const f32x4 y) {
 // two-conv skeleton: conv1 = conv_hr, the intermediate tile stays in LDS (the 100 MB HR map between the two convs never exists),
 // conv2 = ONE fragment per K-step (rows 0-2 hi, rows 8-10 lo), no residual, the epilogue of refvsr_conv_last (fold, one lane per
 // channel, rv_bicubic_at, planar fp32 stores).  The blob keeps the block layout (conv2's fragment slots 1 and 2 unused).
-template <bool RELU, int NWV, bool PROBE = false, int TH = 8, int STORE = 0, int HEAD = 0>
+// WF: weight format (see rb_nf); 1 only for the plain blocks (no PROBE, no HEAD).
+template <bool RELU, int NWV, bool PROBE = false, int TH = 8, int STORE = 0, int HEAD = 0, int WF = 0>
 __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV == 4 ? 2 : 4, NWV == 4 ? 2 : 4))) void resblock24_kernel(RB24Args p) {
     static_assert((TH == 8 && (NWV == 4 || NWV == 8)) || (TH == 16 && NWV == 16), "tile height / waves");
     static_assert(HEAD == 0 || (!RELU && !PROBE && NWV != 4), "output-head variant");
+    static_assert(WF == 0 || (HEAD == 0 && !PROBE), "fp16 weight format: plain blocks only");
+    constexpr int RB_WB = rb_wb(WF), RB_BIAS = rb_bias(WF), RB_XT = rb_blob(WF);   // (shadow the WF = 0 layout's constants)
     constexpr int RB_TH = TH, RB_XH = TH + 4, RB_IH = TH + 2;    // TH = 8: x tile 12 x 36, intermediate 10 x 34 (22 sixteen-pixel groups)
     constexpr int RB_NI = RB_IH * RB_IW;                         // TH = 16: 20 x 36, 18 x 34 (39 groups), 16 waves, ONE workgroup per CU
     constexpr int RB_G1 = (RB_NI + 15) / 16;                     //   (the large maps, see refvsr_resblock24_chain)
@@ -243,7 +266,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV ==
 
     // ---- weights + biases: global -> LDS, 1 KiB per wave instruction, issued before anything else --------------------------
     {
-        constexpr int NCH = RB_BIAS / 1024;                      // 42 full chunks + the 256-byte bias tail
+        constexpr int NCH = RB_BIAS / 1024;                      // 42 (WF = 1: 28) full chunks + the 256-byte bias tail
         const unsigned char* g = p.blob + lane * 16;
 #pragma unroll
         for (int j = 0; j < (NCH + NWV - 1) / NWV; ++j) {
@@ -371,8 +394,8 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV ==
 #pragma unroll
             for (int t = 0; t < T1; ++t) { a0[t] = bv0; a1[t] = bv1; }
         }
-        if (full1) rb_kloop<T1, T1>(a0, a1, smem, 0, la, pb1, delta6);
-        else rb_kloop<T1 - 1, T1>(a0, a1, smem, 0, la, pb1, delta6);
+        if (full1) rb_kloop<T1, T1, WF>(a0, a1, smem, 0, la, pb1, delta6);
+        else rb_kloop<T1 - 1, T1, WF>(a0, a1, smem, 0, la, pb1, delta6);
         if (stamp) RB_STAMP(3);
         if (has_next) x_fetch(tl + 1);                           // next tile: in flight from here to the end of conv2
         // residual x values of this lane's outputs: the x tile is about to be overwritten by t
@@ -385,8 +408,10 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV ==
                 xr1[t] = *reinterpret_cast<const f16x4*>(smem + (q < 2 ? pb2[t] + dq + 32 : RB_BIAS + 96));
             }
         }
+        if constexpr (WF == 0) {
 #pragma unroll
-        for (int t = 0; t < T1; ++t) a1[t] = rb_fold_halves(a1[t]);
+            for (int t = 0; t < T1; ++t) a1[t] = rb_fold_halves(a1[t]);
+        }
         __syncthreads();                                         // A: every wave is done reading the x tile
         if (stamp) RB_STAMP(4);
         // t = act(acc), zero outside the frame (conv2's zero padding), written over the x tile at (+1, +1)
@@ -433,7 +458,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV ==
             }
         }
         if constexpr (HEAD != 0) rb_kloop_head<T2>(c0, smem, RB_WB, la, pb2, delta6);
-        else rb_kloop<T2, T2>(c0, c1, smem, RB_WB, la, pb2, delta6);
+        else rb_kloop<T2, T2, WF>(c0, c1, smem, RB_WB, la, pb2, delta6);
         if (stamp) RB_STAMP(7);
         if (has_next) {
             __syncthreads();                                     // C: every wave is done reading t
@@ -463,7 +488,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV ==
             unsigned char* ob = outp + ((long long)ty0 * p.w + tx0) * RB_PXB;
 #pragma unroll
             for (int t = 0; t < T2; ++t) {
-                const f32x4 m = rb_fold_halves(c1[t]);
+                const f32x4 m = WF == 0 ? rb_fold_halves(c1[t]) : c1[t];
                 const uint2 v0 = rb_pack(c0[t]), v1 = rb_pack(m);
                 bool ok = true;
                 if (!interior) {
@@ -484,7 +509,8 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV ==
 #pragma unroll
             for (int tp = 0; tp < T2 / 2; ++tp) {
                 const uint2 a0 = rb_pack(c0[2 * tp]), b0 = rb_pack(c0[2 * tp + 1]);
-                const uint2 a1 = rb_pack(rb_fold_halves(c1[2 * tp])), b1 = rb_pack(rb_fold_halves(c1[2 * tp + 1]));
+                const uint2 a1 = rb_pack(WF == 0 ? rb_fold_halves(c1[2 * tp]) : c1[2 * tp]);
+                const uint2 b1 = rb_pack(WF == 0 ? rb_fold_halves(c1[2 * tp + 1]) : c1[2 * tp + 1]);
                 // odd 16-lane rows of the left group's registers <-> even rows of the right group's: lane (q, pixel) ends up with
                 // channels 8 (q >> 1) .. + 8 of its pixel in group q & 1 (and, for q < 2, channels 16-23 from the folded tile)
                 const auto sx = __builtin_amdgcn_permlane16_swap(a0.x, b0.x, false, false);
@@ -531,9 +557,9 @@ extern "C" int refvsr_set_resblock24_waves(int waves) {
     return 0;
 }
 
-template <bool RELU, int NWV, bool PROBE = false, int TH = 8, int STORE = 0, int HEAD = 0>
+template <bool RELU, int NWV, bool PROBE = false, int TH = 8, int STORE = 0, int HEAD = 0, int WF = 0>
 static int launch_rb24(RB24Args& a, hipStream_t st) {
-    constexpr int RB_LDS = rb_lds(TH);
+    constexpr int RB_LDS = rb_lds_wf(TH, WF);
     a.tiles_x = rv_cdiv(a.w, RB_TW);
     a.tpm = a.tiles_x * rv_cdiv(a.h, TH);
     a.n_tiles = a.tpm * (a.batch > 1 ? a.batch : 1);
@@ -541,17 +567,17 @@ static int launch_rb24(RB24Args& a, hipStream_t st) {
     static int occ_dev[RV_MAX_DEVICES] = {};
     const int dev = rv_device();
     if (!attr_done[dev]) {
-        RV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&resblock24_kernel<RELU, NWV, PROBE, TH, STORE, HEAD>),
+        RV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&resblock24_kernel<RELU, NWV, PROBE, TH, STORE, HEAD, WF>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, RB_LDS));
         int occ = 0;
-        RV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, resblock24_kernel<RELU, NWV, PROBE, TH, STORE, HEAD>, NWV * 64, RB_LDS));
+        RV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, resblock24_kernel<RELU, NWV, PROBE, TH, STORE, HEAD, WF>, NWV * 64, RB_LDS));
         occ_dev[dev] = occ < 1 ? 1 : occ;
         attr_done[dev] = true;
     }
     int cap = (rv_stream_cus(st) * occ_dev[dev]) & ~7;
     if (cap < 8) cap = 8;
     a.grid = a.n_tiles < cap ? a.n_tiles : cap;
-    hipLaunchKernelGGL((resblock24_kernel<RELU, NWV, PROBE, TH, STORE, HEAD>), dim3(a.grid), dim3(NWV * 64), RB_LDS, st, a);
+    hipLaunchKernelGGL((resblock24_kernel<RELU, NWV, PROBE, TH, STORE, HEAD, WF>), dim3(a.grid), dim3(NWV * 64), RB_LDS, st, a);
     RV_LAUNCH_CHECK();
     return 0;
 }
@@ -561,11 +587,14 @@ static int launch_rb24(RB24Args& a, hipStream_t st) {
 // over ALL maps (one weight fill per workgroup, batch x the tiles: an LR launch of RefVSR_small is one 8 x 32 tile per workgroup --
 // 4 100 of its 13 000 cycles are the 43 KB fill -- two maps per launch are two tiles per fill); intermediates ping-pong between
 // scratch0 / scratch1 ([batch] maps each, contiguous; blocks cannot run in place: neighbouring tiles read the input halo).
+// WF = 1: the blobs are in the fp16 weight format (REFVSR_RESBLOCK24_F16W_BLOB_BYTES each, refvsr_resblock24_chain_f16w).
+template <int WF>
 static int rb24_chain_impl(const void* const* src, int batch, int h, int w, int n, const void* blobs, size_t blob_stride,
                            float act_slope, void* scratch0, void* scratch1, void* const* out, void* stream) {
+    constexpr int BLOB = rb_blob(WF);
     RV_CHECK(src && out && blobs && h > 0 && w > 0 && n >= 1 && batch >= 1 && batch <= REFVSR_MAX_MAPS, "resblock24_chain: bad args");
-    RV_CHECK(blob_stride >= (size_t)RB_BLOB && blob_stride % 16 == 0 && ((uintptr_t)blobs & 15) == 0,
-             "resblock24_chain: blobs must be 16-byte aligned, stride >= %d", RB_BLOB);
+    RV_CHECK(blob_stride >= (size_t)BLOB && blob_stride % 16 == 0 && ((uintptr_t)blobs & 15) == 0,
+             "resblock24_chain: blobs must be 16-byte aligned, stride >= %d", BLOB);
     RV_CHECK(act_slope >= 0.f && act_slope <= 1.f, "resblock24_chain: activation slope must lie in [0, 1]");
     RV_CHECK(n == 1 || scratch0, "resblock24_chain: n >= 2 needs scratch0");
     RV_CHECK(n <= 2 || scratch1, "resblock24_chain: n >= 3 needs scratch1");
@@ -603,12 +632,12 @@ static int rb24_chain_impl(const void* const* src, int batch, int h, int w, int 
         // and sixteen waves wait longer at the barriers), below that the 8 x 32 tiles fill more CUs (135 x 240: 6.2 vs 8.2 us)
         const int nt8 = rv_cdiv(w, RB_TW) * rv_cdiv(h, 8) * batch;
         const int waves = g_rb24_waves ? g_rb24_waves : (nt8 >= 4 * rv_stream_cus(st) ? 16 : 8);
-        if (g_rb_probe && act_slope == 0.f && waves == 8) rc = launch_rb24<true, 8, true>(a, st);          // tools/probe_resblock24.py
-        else if (g_rb_probe && act_slope == 0.f && waves == 16) rc = launch_rb24<true, 16, true, 16>(a, st);
-        else if (waves == 4) rc = act_slope == 0.f ? launch_rb24<true, 4>(a, st) : launch_rb24<false, 4>(a, st);
+        if (WF == 0 && g_rb_probe && act_slope == 0.f && waves == 8) rc = launch_rb24<true, 8, true>(a, st);          // tools/probe_resblock24.py
+        else if (WF == 0 && g_rb_probe && act_slope == 0.f && waves == 16) rc = launch_rb24<true, 16, true, 16>(a, st);
+        else if (waves == 4) rc = act_slope == 0.f ? launch_rb24<true, 4, false, 8, 0, 0, WF>(a, st) : launch_rb24<false, 4, false, 8, 0, 0, WF>(a, st);
 #define RB24_PICK(R_)                                                                                                              \
-        (waves == 16 ? (g_rb24_store == 1 ? launch_rb24<R_, 16, false, 16, 1>(a, st) : launch_rb24<R_, 16, false, 16, 0>(a, st)) \
-                     : (g_rb24_store == 1 ? launch_rb24<R_, 8, false, 8, 1>(a, st) : launch_rb24<R_, 8, false, 8, 0>(a, st)))
+        (waves == 16 ? (g_rb24_store == 1 ? launch_rb24<R_, 16, false, 16, 1, 0, WF>(a, st) : launch_rb24<R_, 16, false, 16, 0, 0, WF>(a, st)) \
+                     : (g_rb24_store == 1 ? launch_rb24<R_, 8, false, 8, 1, 0, WF>(a, st) : launch_rb24<R_, 8, false, 8, 0, 0, WF>(a, st)))
         else rc = act_slope == 0.f ? RB24_PICK(true) : RB24_PICK(false);
 #undef RB24_PICK
         if (rc) return rc;
@@ -620,12 +649,25 @@ static int rb24_chain_impl(const void* const* src, int batch, int h, int w, int 
 extern "C" int refvsr_resblock24_chain(const void* src, int h, int w, int n, const void* blobs, size_t blob_stride,
                                        float act_slope, void* scratch0, void* scratch1, void* out, void* stream) {
     RV_CHECK(src && out, "resblock24_chain: bad args");
-    return rb24_chain_impl(&src, 1, h, w, n, blobs, blob_stride, act_slope, scratch0, scratch1, &out, stream);
+    return rb24_chain_impl<0>(&src, 1, h, w, n, blobs, blob_stride, act_slope, scratch0, scratch1, &out, stream);
 }
 
 extern "C" int refvsr_resblock24_chain_batch(const void* const* src, int batch, int h, int w, int n, const void* blobs, size_t blob_stride,
                                              float act_slope, void* scratch0, void* scratch1, void* const* out, void* stream) {
-    return rb24_chain_impl(src, batch, h, w, n, blobs, blob_stride, act_slope, scratch0, scratch1, out, stream);
+    return rb24_chain_impl<0>(src, batch, h, w, n, blobs, blob_stride, act_slope, scratch0, scratch1, out, stream);
+}
+
+// The same two entry points on fp16-format blobs (ABI 15, packing.py:pack_resblock24_f16w): two MFMAs per pixel group and K-step
+// instead of three, 28 928-byte blobs.  Bit-identical to the two above on blobs packed from the same fp16-representable weights.
+extern "C" int refvsr_resblock24_f16w_blob_bytes(void) { return rb_blob(1); }
+extern "C" int refvsr_resblock24_chain_f16w(const void* src, int h, int w, int n, const void* blobs, size_t blob_stride,
+                                            float act_slope, void* scratch0, void* scratch1, void* out, void* stream) {
+    RV_CHECK(src && out, "resblock24_chain: bad args");
+    return rb24_chain_impl<1>(&src, 1, h, w, n, blobs, blob_stride, act_slope, scratch0, scratch1, &out, stream);
+}
+extern "C" int refvsr_resblock24_chain_batch_f16w(const void* const* src, int batch, int h, int w, int n, const void* blobs, size_t blob_stride,
+                                                  float act_slope, void* scratch0, void* scratch1, void* const* out, void* stream) {
+    return rb24_chain_impl<1>(src, batch, h, w, n, blobs, blob_stride, act_slope, scratch0, scratch1, out, stream);
 }
 
 // The last two convs of the upsampler in ONE launch (RefVSR.py:91-92,116-118,288,297, mid_channels = 24):

@@ -22,9 +22,10 @@ import os
 import torch
 
 from . import ops
+from .config import resolve_weight_precision
 from .knobs import env_flag
 from .packing import pack_conv
-from .weights import VGG_MEAN, VGG_STD
+from .weights import VGG_MEAN, VGG_STD, round16
 
 _uid = itertools.count()
 
@@ -64,12 +65,18 @@ class Weights(object):
         self.conv = {}
         self.raw = {}
         self.chains = {}            # runs of fused blocks -> ops.ResblockChain pointer tables (Engine._block_chain)
+        # weight format, resolved once per packing (config.resolve_weight_precision): 'fp16' packs round16(sd) -- every packer below
+        # then sees fp16-representable weights (lo halves = 0) -- and the specialised C = 24 kernels take their fp16-format blobs
+        # (no lo fragments), which every launch picks from the ConvWeights / chain it is handed
+        self.wfmt = resolve_weight_precision(config)
+        if self.wfmt == 'fp16':
+            sd = round16(sd)
         C = self.C
         g = lambda n: (sd['Network.' + n + '.weight'], sd['Network.' + n + '.bias'])
 
         def mf(name, srcs, shuffle=False, mt=None):
             w, b = g(name)
-            self.conv[name] = ops.ConvWeights(pack_conv(w, b, srcs, shuffle, mt=mt), device)
+            self.conv[name] = ops.ConvWeights(pack_conv(w, b, srcs, shuffle, mt=mt), device, wfmt=self.wfmt)
 
         def dr(name):
             w, b = g(name)

@@ -293,9 +293,13 @@ def build_config(argv=None):
     ap.add_argument('--result_dtype', default='float32', choices=['float32', 'float16', 'uint8'],
                     help="extension: what the output head stores ('uint8' = rint(255 x), the bytes of the written PNG; the scores are then "
                          "those of the quantised frame)")
+    ap.add_argument('--weight_precision', default='hi_lo', choices=['hi_lo', 'fp16', 'amp'],
+                    help="extension: conv weights of the engine ('fp16' = the reference's fp16-autocast arithmetic, mid_channels = 24 "
+                         "models only; 'amp' = 'fp16' where the config sets is_amp)")
     args, _ = ap.parse_known_args(argv)
     cfg = get_config(args.project, args.mode, args.config, args.data)
     cfg.result_dtype = args.result_dtype
+    cfg.weight_precision = args.weight_precision
     if args.network:
         cfg.network = args.network
     if args.frame_num:

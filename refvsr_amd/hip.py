@@ -13,9 +13,10 @@ OUT_NHWC16, OUT_NHWC16_SHUFFLE2, OUT_PLANAR32 = 0, 1, 2
 RS_BICUBIC, RS_BILINEAR, RS_BILINEAR_AC, RS_NEAREST = 0, 1, 2, 3
 RESULT_F32, RESULT_F16, RESULT_U8 = 0, 1, 2
 MATCH_KP, MATCH_ROWCHUNK, MATCH_COLBLOCK = 152, 256, 512
-ABI_VERSION = 14
+ABI_VERSION = 15
 MAX_MAPS = 4
 RESBLOCK24_BLOB_BYTES = 43264
+RESBLOCK24_F16W_BLOB_BYTES = 28928          # the fp16 weight format (ABI 15)
 RESBLOCK48_BLOB_BYTES = 172544
 
 
@@ -124,6 +125,20 @@ SIGNATURES = {
     'refvsr_pool3s2_nhwc16': [_P, _I, _I, _I, _P, _I, _I, _I, _P],
     'refvsr_up2_bilinear_nhwc16': [_P, _I, _I, _I, _F, _P, _P],
     'refvsr_tsa_blend': [_P, _P, _P, _Z, _P, _P],
+    # fp16 weight format (ABI 15): twins with the signature of the function they are named after
+    'refvsr_resblock24_f16w_blob_bytes': [],     # returns the size
+    'refvsr_conv24_f16w_blob_bytes': [_I, _I],   # returns the size
+    'refvsr_conv32_f16w_blob_bytes': [_I, _I],   # returns the size
+    'refvsr_conv_shuffle2_f16w_blob_bytes': [_I],   # returns the size
+    'refvsr_resblock24_chain_f16w': [_P, _I, _I, _I, _P, _Z, _F, _P, _P, _P, _P],
+    'refvsr_resblock24_chain_batch_f16w': [_P, _I, _I, _I, _I, _P, _Z, _F, _P, _P, _P, _P],
+    'refvsr_conv24_f16w': [_P, _I, _P, _I, _I, _I, _P, _F, _P, _P, _F, _P, _P],
+    'refvsr_conv24_batch_f16w': [_P, _I, _P, _I, _I, _I, _I, _P, _F, _P, _P, _F, _P, _P],
+    'refvsr_conv32_f16w': [_P, _I, _P, _I, _I, _I, _P, _F, _P, _P, _F, _P, _P],
+    'refvsr_conv_shuffle2_f16w': [_P, _I, _I, _I, _P, _F, _P, _P],
+    'refvsr_conv_shuffle2_batch_f16w': [_P, _I, _I, _I, _I, _P, _F, _P, _P],
+    'refvsr_conf_alpha_f16w': [_P, _P, _I, _I, _I, _P, _P, _F, _P, _I, _F, _P, _P, _P],
+    'refvsr_conf_alpha_batch_f16w': [_P, _P, _I, _I, _I, _I, _P, _P, _F, _P, _I, _F, _P, _P, _P],
 }
 _SPECIAL = {'refvsr_abi_version': (C.c_int, []), 'refvsr_last_error': (C.c_char_p, [])}
 EXPORTS = tuple(sorted(list(SIGNATURES) + list(_SPECIAL)))

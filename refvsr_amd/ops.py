@@ -103,9 +103,10 @@ CONV24 = not env_flag('REFVSR_NO_CONV24')      # A/B knob: the generic conv kern
 
 class ConvWeights(object):
     """Packed weights of one conv on the device (see packing.pack_conv)."""
-    __slots__ = ('wpack', 'bias', 'cout', 'ksteps', 'mt', 'ksize', 'cpads', 'shuffle', 'f32', 'hi_only', 'desc', 'odtype', 'raw', 'blob24')
+    __slots__ = ('wpack', 'bias', 'cout', 'ksteps', 'mt', 'ksize', 'cpads', 'shuffle', 'f32', 'hi_only', 'desc', 'odtype', 'raw', 'blob24',
+                 'wfmt', 'blob_wfmt')
 
-    def __init__(self, pk, device):
+    def __init__(self, pk, device, wfmt='hi_lo'):
         self.wpack = pk['wpack'].to(device).contiguous()
         self.bias = pk['bias'].to(device).contiguous()
         self.cout, self.ksteps, self.mt, self.ksize = pk['cout'], pk['ksteps'], pk['mt'], pk['ksize']
@@ -120,15 +121,29 @@ class ConvWeights(object):
         self.raw = pk.get('raw')      # (weight, bias) fp32 cpu tensors when the packer kept them (repacking for specialised kernels)
         # 3x3 convs with 24 / 48 output channels of the supported input shapes also carry the blob of the specialised kernel
         # (conv24.hip; the attribute keeps its first name)
+        # wfmt: the engine's weight format (Weights.wfmt; 'fp16': the packer was handed fp16-representable weights).  blob_wfmt: the
+        # format of blob24 -- 'fp16' where the shape has a refvsr_*_f16w twin (24 | 32 outputs, the C = 24 pixel-shuffle conv), which
+        # every launch of this conv then calls; other shapes keep the hi + lo layout (lo halves = 0 on such weights)
+        self.wfmt = wfmt
+        self.blob_wfmt = 'hi_lo'
         self.blob24 = None
         if self.raw is not None and pk.get('src_channels') is not None and CONV24 and not self.hi_only:
             from .packing import conv24_ok, conv_shuffle2_ok, pack_conv24, pack_conv_shuffle2
             two48 = self.cout == 48 and len(pk['src_channels']) == 2     # 48 + 48 -> 48 as two channel halves (A/B knob)
             if (conv24_ok(tuple(self.raw[0].shape), pk['src_channels'], self.shuffle, self.f32) and not (self.cout == 32 and env_flag('REFVSR_NO_CONV32'))
                     and not (two48 and env_flag('REFVSR_NO_CONV48X2'))):
-                self.blob24 = pack_conv24(self.raw[0], self.raw[1], pk['src_channels']).to(device).contiguous()
+                if wfmt == 'fp16' and self.cout in (24, 32):
+                    self.blob_wfmt = 'fp16'
+                self.blob24 = pack_conv24(self.raw[0], self.raw[1], pk['src_channels'], wfmt=self.blob_wfmt).to(device).contiguous()
             elif self.shuffle and conv_shuffle2_ok(tuple(self.raw[0].shape), pk['src_channels'], self.f32) and not env_flag('REFVSR_NO_CONV_SHUFFLE2'):
-                self.blob24 = pack_conv_shuffle2(self.raw[0], self.raw[1]).to(device).contiguous()     # refvsr_conv_shuffle2
+                if wfmt == 'fp16' and self.raw[0].shape[1] == 24:
+                    self.blob_wfmt = 'fp16'
+                self.blob24 = pack_conv_shuffle2(self.raw[0], self.raw[1], wfmt=self.blob_wfmt).to(device).contiguous()     # refvsr_conv_shuffle2
+
+
+def _c24(cw, name):
+    """Entry point `name` of the conv24 family, or its _f16w twin when cw's blob is in the fp16 weight format (ABI 15)."""
+    return getattr(hip.lib(), name + '_f16w' if cw.blob_wfmt == 'fp16' else name)
 
 
 def conv(cw, src0, src1=None, stride=1, pad=None, act=1.0, mul=None, res=None, post=1.0,
@@ -158,7 +173,7 @@ def conv(cw, src0, src1=None, stride=1, pad=None, act=1.0, mul=None, res=None, p
             src1 is None and mul is None and res is None and 0.0 <= act <= 1.0 and post == 1.0 and h * w * co_ * 2 < 2 ** 31):
         # C -> 4 C conv + pixel shuffle on the compile-time-specialised kernel (csrc/conv24.hip, SHUF variant)
         out = torch.empty((2 * h, 2 * w, c0), dtype=torch.float16, device=src0.device)
-        hip.check(hip.lib().refvsr_conv_shuffle2(_ptr(src0), c0, h, w, _ptr(cw.blob24), act, _ptr(out), _stream()), 'conv_shuffle2')
+        hip.check(_c24(cw, 'refvsr_conv_shuffle2')(_ptr(src0), c0, h, w, _ptr(cw.blob24), act, _ptr(out), _stream()), 'conv_shuffle2')
         return out
     if (cw.blob24 is not None and not cw.shuffle and stride == 1 and pad == 1 and not planar_out and res_planar is None and
             0.0 <= act <= 1.0 and 0.0 <= post <= 1.0 and (mul is None or mul.shape[2] == co_) and (res is None or res.shape[2] == co_) and
@@ -169,7 +184,7 @@ def conv(cw, src0, src1=None, stride=1, pad=None, act=1.0, mul=None, res=None, p
                 _nhwc(m_)
                 assert tuple(m_.shape[:2]) == (h, w)
         out = torch.empty((h, w, co_), dtype=torch.float16, device=src0.device)
-        fn = {24: hip.lib().refvsr_conv24, 32: hip.lib().refvsr_conv32, 48: hip.lib().refvsr_conv48}[co_]
+        fn = _c24(cw, 'refvsr_conv%d' % co_)
         hip.check(fn(_ptr(src0), c0, _ptr(src1), c1, h, w, _ptr(cw.blob24), act, _ptr(mul), _ptr(res), post, _ptr(out), _stream()), 'conv%d' % co_)
         return out
     ho = (h + 2 * pad - k) // stride + 1
@@ -325,18 +340,33 @@ def resblock_chain(chain, x, act, post=1.0):
 class Resblock24Chain(object):
     """A run of 24-channel fused blocks for refvsr_resblock24_chain: one device buffer [n, 43264] of per-block blobs
     (packing.pack_resblock24).  pairs: [(conv1, conv2)] ConvWeights whose packer kept the raw fp32 weights, or
-    [((w1, b1), (w2, b2))] raw tensors."""
+    [((w1, b1), (w2, b2))] raw tensors.  wfmt: 'hi_lo' | 'fp16' (blobs [n, 28928] of packing.pack_resblock24_f16w for
+    refvsr_resblock24_chain_f16w); None = the weight format of the ConvWeights (raw tensors: 'hi_lo')."""
 
-    def __init__(self, pairs, device):
-        from .packing import pack_resblock24
+    def __init__(self, pairs, device, wfmt=None):
+        from .packing import pack_resblock24, pack_resblock24_f16w
+        pairs = list(pairs)
+        if wfmt is None:
+            fmts = set(c.wfmt if isinstance(c, ConvWeights) else 'hi_lo' for p in pairs for c in p)
+            assert len(fmts) == 1, 'one weight format per chain: %s' % sorted(fmts)
+            wfmt = fmts.pop()
+        assert wfmt in ('hi_lo', 'fp16'), wfmt
+        self.wfmt = wfmt
+        pack = pack_resblock24_f16w if wfmt == 'fp16' else pack_resblock24
         blobs = []
         for a, b in pairs:
             (w1, b1), (w2, b2) = (a.raw if isinstance(a, ConvWeights) else a), (b.raw if isinstance(b, ConvWeights) else b)
-            blobs.append(pack_resblock24(w1, b1, w2, b2))
+            blobs.append(pack(w1, b1, w2, b2))
         self.n = len(blobs)
         self.blobs = torch.stack(blobs, 0).to(device).contiguous()
         self.stride = self.blobs.shape[1]
-        assert self.stride == hip.RESBLOCK24_BLOB_BYTES and self.blobs.data_ptr() % 16 == 0
+        assert self.stride == (hip.RESBLOCK24_F16W_BLOB_BYTES if wfmt == 'fp16' else hip.RESBLOCK24_BLOB_BYTES) and self.blobs.data_ptr() % 16 == 0
+
+
+def _rb24(chain, name):
+    """refvsr_resblock24_chain[_batch], or its _f16w twin for a chain of fp16-format blobs (chain-like objects without a weight
+    format -- torch_ops' blob tables -- are hi + lo)."""
+    return getattr(hip.lib(), name + '_f16w' if getattr(chain, 'wfmt', 'hi_lo') == 'fp16' else name)
 
 
 _RB24_WAVES_SET = False
@@ -357,7 +387,7 @@ def resblock24_chain(chain, x, act):
     out = torch.empty_like(x)
     s0 = torch.empty_like(x) if chain.n >= 2 else None
     s1 = torch.empty_like(x) if chain.n >= 3 else None
-    hip.check(hip.lib().refvsr_resblock24_chain(_ptr(x), h, w, chain.n, _ptr(chain.blobs), chain.stride, act, _ptr(s0), _ptr(s1),
+    hip.check(_rb24(chain, 'refvsr_resblock24_chain')(_ptr(x), h, w, chain.n, _ptr(chain.blobs), chain.stride, act, _ptr(s0), _ptr(s1),
                                                 _ptr(out), _stream()), 'resblock24_chain')
     return out
 
@@ -428,7 +458,7 @@ def conf_alpha(conf_a, conf_b, up, w0, b0, cw, slope0=0.2, slope1=0.2, want_max=
     h, w = conf_a.shape[1:]
     alpha = torch.empty((up * h, up * w, cw.cout), dtype=torch.float16, device=conf_a.device)
     cmax = torch.empty_like(conf_a) if want_max else None
-    hip.check(hip.lib().refvsr_conf_alpha(_ptr(conf_a), _ptr(conf_b), h, w, up, _ptr(w0), _ptr(b0), slope0, _ptr(cw.blob24), cw.cout,
+    hip.check(_c24(cw, 'refvsr_conf_alpha')(_ptr(conf_a), _ptr(conf_b), h, w, up, _ptr(w0), _ptr(b0), slope0, _ptr(cw.blob24), cw.cout,
                                           slope1, _ptr(alpha), _ptr(cmax), _stream()), 'conf_alpha')
     return (alpha, cmax) if want_max else alpha
 
@@ -818,14 +848,14 @@ def conv_b(cw, src0s, src1s=None, act=1.0, muls=None, ress=None, post=1.0, stack
     if (multimap_ok(B) and cw.shuffle and cw.blob24 is not None and c0 == 24 and src1s is None and muls is None and ress is None and
             0.0 <= act <= 1.0 and post == 1.0 and h * w * cw.cout * 2 < 2 ** 31):
         out = torch.empty((B, 2 * h, 2 * w, c0), dtype=torch.float16, device=dev)
-        hip.check(hip.lib().refvsr_conv_shuffle2_batch(_parr(src0s), B, c0, h, w, _ptr(cw.blob24), act, _parr(list(out)), _stream()),
+        hip.check(_c24(cw, 'refvsr_conv_shuffle2_batch')(_parr(src0s), B, c0, h, w, _ptr(cw.blob24), act, _parr(list(out)), _stream()),
                   'conv_shuffle2_batch')
         return out
     if (multimap_ok(B) and cw.blob24 is not None and not cw.shuffle and cw.cout == 24 and 0.0 <= act <= 1.0 and 0.0 <= post <= 1.0 and
             [c0] + ([c1] if src1s is not None else []) == list(cw.cpads) and hip.lib().refvsr_conv24_supported(c0, c1) and
             (muls is None or muls[0].shape[2] == 24) and (ress is None or ress[0].shape[2] == 24) and h * w * max(24, c0, c1) * 2 < 2 ** 31):
         out = torch.empty((B, h, w, 24), dtype=torch.float16, device=dev)
-        hip.check(hip.lib().refvsr_conv24_batch(_parr(src0s), c0, _parr(src1s) if src1s is not None else None, c1, B, h, w, _ptr(cw.blob24),
+        hip.check(_c24(cw, 'refvsr_conv24_batch')(_parr(src0s), c0, _parr(src1s) if src1s is not None else None, c1, B, h, w, _ptr(cw.blob24),
                                                 act, _parr(muls) if muls is not None else None, _parr(ress) if ress is not None else None,
                                                 post, _parr(list(out)), _stream()), 'conv24_batch')
         return out
@@ -846,7 +876,7 @@ def resblock24_chain_b(chain, xs, act, stack=True):
     out = torch.empty((B, h, w, 24), dtype=torch.float16, device=dev)
     s0 = torch.empty_like(out) if chain.n >= 2 else None
     s1 = torch.empty_like(out) if chain.n >= 3 else None
-    hip.check(hip.lib().refvsr_resblock24_chain_batch(_parr(xs), B, h, w, chain.n, _ptr(chain.blobs), chain.stride, act, _ptr(s0), _ptr(s1),
+    hip.check(_rb24(chain, 'refvsr_resblock24_chain_batch')(_parr(xs), B, h, w, chain.n, _ptr(chain.blobs), chain.stride, act, _ptr(s0), _ptr(s1),
                                                       _parr(list(out)), _stream()), 'resblock24_chain_batch')
     return out
 
@@ -885,7 +915,7 @@ def conf_alpha_b(conf_as, conf_bs, up, w0, b0, cw, slope0=0.2, slope1=0.2, want_
     dev = conf_as[0].device
     alpha = torch.empty((B, up * h, up * w, 24), dtype=torch.float16, device=dev)
     cmax = torch.empty((B, 1, h, w), dtype=torch.float32, device=dev) if want_max else None
-    hip.check(hip.lib().refvsr_conf_alpha_batch(_parr(conf_as), _parr(conf_bs), B, h, w, up, _ptr(w0), _ptr(b0), slope0, _ptr(cw.blob24), 24,
+    hip.check(_c24(cw, 'refvsr_conf_alpha_batch')(_parr(conf_as), _parr(conf_bs), B, h, w, up, _ptr(w0), _ptr(b0), slope0, _ptr(cw.blob24), 24,
                                                 slope1, _parr(list(alpha)), _parr(list(cmax)) if want_max else None, _stream()),
               'conf_alpha_batch')
     return (alpha, cmax) if want_max else alpha

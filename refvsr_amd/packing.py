@@ -187,6 +187,44 @@ def pack_resblock24(w1, b1, w2, b2):
     return torch.from_numpy(out)
 
 
+RB24_NF_F16W, RB24_F16W_BLOB = 2, 28928     # fp16 weight format (REFVSR_RESBLOCK24_F16W_BLOB_BYTES, ABI 15)
+
+
+def pack_resblock24_f16w(w1, b1, w2, b2):
+    """One fused block in the fp16 weight format -> uint8 [28928] for refvsr_resblock24_chain_f16w (config.weight_precision = 'fp16'):
+    [conv1: 7 K-steps x 2 fragments x 64 lanes x 8 halfs][conv2: same][b1: 32 floats][b2: 32 floats].  Lane l = (q, r) of K-step s
+    holds the 8 input channels of K-block rb24_kblock(s, q) for row r of   f = 0: fp16(W[r])   f = 1: fp16(W[16 + r]) if r < 8, else 0.
+    No lo halves: the kernel computes with fp16(W), bit for bit what refvsr_resblock24_chain computes on pack_resblock24(fp16(W))."""
+    out = np.zeros(RB24_F16W_BLOB, np.uint8)
+    o = 0
+    for w in (w1, w2):
+        w = w.detach().cpu().float().numpy() if isinstance(w, torch.Tensor) else np.asarray(w, np.float32)
+        assert w.shape == (24, 24, 3, 3), w.shape
+        hi = w.astype(np.float16)
+        frag = np.zeros((RB24_S, RB24_NF_F16W, 4, 16, 8), np.float16)  # [s][f][q][r][8]
+        for s_ in range(RB24_S):
+            for q in range(4):
+                kb = rb24_kblock(s_, q)
+                if kb is None:
+                    continue
+                ty, tx, cg = kb
+                ch = slice(cg * 8, cg * 8 + 8)
+                frag[s_, 0, q] = hi[0:16, ch, ty, tx]
+                frag[s_, 1, q, 0:8] = hi[16:24, ch, ty, tx]
+        raw = frag.reshape(-1).view(np.uint8)
+        out[o:o + raw.size] = raw
+        o += raw.size
+    assert o == 2 * RB24_S * RB24_NF_F16W * 1024
+    for b in (b1, b2):
+        b = b.detach().cpu().float().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, np.float32)
+        bb = np.zeros(32, np.float32)
+        bb[:24] = b
+        out[o:o + 128] = bb.view(np.uint8)
+        o += 128
+    assert o == RB24_F16W_BLOB
+    return torch.from_numpy(out)
+
+
 # ---- 24-output-channel 3x3 convs (csrc/conv24.hip) -----------------------------------------------------------------------
 def c24_steps(ncg):
     return {1: 3, 2: 5, 3: 7, 4: 9, 6: 14, 7: 18, 12: 27}[ncg]
@@ -331,22 +369,27 @@ def conv_shuffle2_ok(w_shape, src_channels, f32=False):
     return ks == 3 and not f32 and list(src_channels) in ([24], [48]) and cin == src_channels[0] and cout == 4 * cin
 
 
-def pack_conv24(w, b, src_channels, shuffle_group=False, half_group=False):
+def pack_conv24(w, b, src_channels, shuffle_group=False, half_group=False, wfmt='hi_lo'):
     """uint8 blob of one conv for refvsr_conv24 / refvsr_conv48: fp16 [S][NF][64 lanes][8] + bias floats (32 | 64).  Lane
     l = (q = l >> 4, r = l & 15) of K-step s holds the 8 (padded) input channels of K-block c24_kblock(ncg, s, q) for row r of
     fragment f (hi = fp16(w), lo = fp16(w - hi)):
       24 outputs (NF = 3): f = 0: hi(W[r])   f = 1: lo(W[r])   f = 2: hi(W[16 + r]) if r < 8 else lo(W[8 + r])
-      32 | 48 outputs (NF = 4 | 6): f = 2 m: hi(W[16 m + r])   f = 2 m + 1: lo(W[16 m + r])"""
+      32 | 48 outputs (NF = 4 | 6): f = 2 m: hi(W[16 m + r])   f = 2 m + 1: lo(W[16 m + r])
+    wfmt='fp16' (the refvsr_*_f16w twins, ABI 15): plain fp16 weights, one fragment per 16 output rows, f = m: fp16(W[16 m + r]) (rows
+    past the output channels zero): NF = 2 | 2 | 3 for 24 | 32 | 48 outputs, same bias tail."""
+    assert wfmt in ('hi_lo', 'fp16'), wfmt
     w = w.detach().cpu().float().numpy() if isinstance(w, torch.Tensor) else np.asarray(w, np.float32)
     b = b.detach().cpu().float().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, np.float32)
     assert conv24_ok(w.shape, src_channels, shuffle_group=shuffle_group, half_group=half_group), (w.shape, src_channels)
     cout = w.shape[0]
     if cout == 48 and [_pad8(c) for c in src_channels] == [48, 48]:
         # 48 + 48 -> 48 (refvsr_conv48's two-source form): two channel-half blobs of the 24-output layout (NCG = 12 plan), back to back
-        return torch.cat([pack_conv24(w[0:24], b[0:24], src_channels, half_group=True), pack_conv24(w[24:48], b[24:48], src_channels, half_group=True)])
+        return torch.cat([pack_conv24(w[0:24], b[0:24], src_channels, half_group=True, wfmt=wfmt),
+                          pack_conv24(w[24:48], b[24:48], src_channels, half_group=True, wfmt=wfmt)])
     Wk, _, ncg = kmatrix(w, src_channels)                       # [cout, 9 * ncg * 8], K-block g = tap * ncg + cg
     S = c24_steps(ncg)
-    nf = 3 if cout == 24 else cout // 8
+    f16w = wfmt == 'fp16'
+    nf = (cout + 15) // 16 if f16w else 3 if cout == 24 else cout // 8
     hi = Wk.astype(np.float16)
     lo = (Wk - hi.astype(np.float32)).astype(np.float16)
     frag = np.zeros((S, nf, 4, 16, 8), np.float16)
@@ -358,7 +401,11 @@ def pack_conv24(w, b, src_channels, shuffle_group=False, half_group=False):
             ty, tx, cg = kb
             g = (ty * 3 + tx) * ncg + cg
             cols = slice(g * 8, g * 8 + 8)
-            if cout == 24:
+            if f16w:
+                for m in range(nf):
+                    rows = hi[16 * m:min(16 * m + 16, cout), cols]
+                    frag[s_, m, q, 0:rows.shape[0]] = rows
+            elif cout == 24:
                 frag[s_, 0, q] = hi[0:16, cols]
                 frag[s_, 1, q] = lo[0:16, cols]
                 frag[s_, 2, q, 0:8] = hi[16:24, cols]
@@ -377,11 +424,12 @@ def pack_conv24(w, b, src_channels, shuffle_group=False, half_group=False):
     return torch.from_numpy(out)
 
 
-def pack_conv_shuffle2(w, b):
+def pack_conv_shuffle2(w, b, wfmt='hi_lo'):
     """uint8 blobs of the C -> 4 C pixel-shuffle conv for refvsr_conv_shuffle2 (C = 24 | 48): 2 | 4 conv48-style blobs of 48 output
     rows, back to back.  F.pixel_shuffle(2) puts conv channel 4 c + 2 dy + dx at channel c of sub-pixel (dy, dx); the kernel wants
     a lane's four consecutive accumulator rows to be four consecutive channels of one sub-pixel:
-      C = 24: blob z = dy, row R -> sub-pixel dx = R // 24, channel R % 24;   C = 48: blob z = 2 dy + dx, row R = channel R."""
+      C = 24: blob z = dy, row R -> sub-pixel dx = R // 24, channel R % 24;   C = 48: blob z = 2 dy + dx, row R = channel R.
+    wfmt='fp16': the blobs in pack_conv24's fp16 weight format (refvsr_conv_shuffle2_f16w, C = 24)."""
     w = w.detach().cpu().float() if isinstance(w, torch.Tensor) else torch.from_numpy(np.asarray(w, np.float32))
     b = b.detach().cpu().float() if isinstance(b, torch.Tensor) else torch.from_numpy(np.asarray(b, np.float32))
     c = w.shape[1]
@@ -390,5 +438,5 @@ def pack_conv_shuffle2(w, b):
     for z in range(2 if c == 24 else 4):
         R = np.arange(48)
         rows = 4 * (R % 24) + 2 * z + R // 24 if c == 24 else 4 * R + z
-        blobs.append(pack_conv24(w[rows], b[rows], [c], shuffle_group=True))
+        blobs.append(pack_conv24(w[rows], b[rows], [c], shuffle_group=True, wfmt=wfmt))
     return torch.cat(blobs)

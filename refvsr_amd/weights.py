@@ -249,3 +249,23 @@ def spec_checksum(config):
     for k, v in state_spec(config).items():
         h = zlib.crc32(('%s:%s;' % (k, 'x'.join(map(str, v)))).encode(), h)
     return h
+
+
+def round16_excluded(name):
+    """Conv weights that stay fp32 under config.weight_precision = 'fp16' (DESIGN.md section 2): the matching's MeanShift and VGG
+    extractor (feature_match.*: the arg-max is decided at fp32 accuracy) and the 2 -> 16 confidence convs on refvsr_conv_direct_f32
+    (conf_fusion*.0.0)."""
+    n = name[len('Network.'):] if name.startswith('Network.') else name
+    return n.startswith('feature_match.') or (n.startswith('conf_fusion') and '.0.0.' in n)
+
+
+def round16(sd):
+    """The state dict whose default ('hi_lo') engine computes what the 'fp16' engine computes on sd, bit for bit: every conv weight
+    (4-d `*.weight`) replaced by w.half().float(), except round16_excluded() ones; biases stay fp32.  (No packer transforms weights
+    arithmetically; one that does must round after its transform.)"""
+    out = collections.OrderedDict()
+    for k, v in sd.items():
+        if k.endswith('.weight') and v.dim() == 4 and not round16_excluded(k):
+            v = v.detach().half().to(v.dtype)
+        out[k] = v
+    return out
