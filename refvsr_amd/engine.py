@@ -36,6 +36,17 @@ def _timed_event(stream):
     return e
 
 
+def _flow_pairs(fr, restart):
+    """The flows one window consumes (RefVSR.py:182-191): the backward flows from the centre on and the forward flow of the carried
+    state (forward_flows[:, ctr], :279-283); a window whose forward branch restarts also walks its first frames."""
+    t = len(fr)
+    ctr = t // 2
+    need = [(fr[i], fr[i + 1]) for i in range(ctr, t - 1)] + [(fr[ctr + 1], fr[ctr])]
+    if restart:
+        need += [(fr[i], fr[i - 1]) for i in range(1, ctr + 1)]
+    return need
+
+
 class FrameCtx(object):
     """Per-frame data (functions of one (lr, ref) frame pair only)."""
 
@@ -937,43 +948,51 @@ class Engine(object):
             return self._pipe
         layout = str(getattr(self.cfg, 'pipe_layout', None) or os.environ.get('REFVSR_PIPE_LAYOUT') or self._layout_default or
                      ('pfm' if (self.C == 24 and self.group_ok()) else 'pf_m'))
-        if True:
-            if layout not in ('pf_m', 'pfm', 'one'):                 # ('p_fm', F on M's stream, measured slower in rounds 4-5: removed in round 6)
-                raise ValueError('REFVSR_PIPE_LAYOUT must be pf_m | pfm | one, got %r' % layout)
-            two = self.C != 24
-            split = str(getattr(self.cfg, 'cu_split', None) or os.environ.get('REFVSR_CU_SPLIT') or '')
-            if split and layout in ('pfm', 'pf_m'):
-                # CU partitions (round 6, ABI 13; measurement knob, off by default -- DESIGN 5 "CU partitions"): 'p,f,m' CUs for the
-                # three streams as disjoint ranges (multiples of 8 = an equal share of every XCD); f = 0 with layout pf_m
-                cp, cf, cm = (int(v) for v in split.split(','))
-                p_ = ops.CuStream(0, cp, dev)
-                f_ = ops.CuStream(cp, cf, dev) if (layout == 'pfm' and cf > 0) else p_
-                m = ops.CuStream(cp + (cf if f_ is not p_ else 0), cm, dev)
-                self._pipe = [m, m, f_, p_]
-                self.pipe_layout = layout
-                self._pipe_calls = 0
-                return self._pipe
-            m = torch.cuda.Stream(device=dev)
-            if layout == 'one':                       # measurement aid (bench.py): every section on ONE internal stream -- HIP events
-                two = False                           # around a run of launches then bracket nothing but that run
-            m2 = torch.cuda.Stream(device=dev) if two else m
-            p_ = m if layout == 'one' else torch.cuda.Stream(device=dev)
-            f_ = p_ if layout in ('pf_m', 'one') else torch.cuda.Stream(device=dev)
-            self._pipe = [m, m2, f_, p_]
+        if layout not in ('pf_m', 'pfm', 'one'):                 # ('p_fm', F on M's stream, measured slower in rounds 4-5: removed in round 6)
+            raise ValueError('REFVSR_PIPE_LAYOUT must be pf_m | pfm | one, got %r' % layout)
+        two = self.C != 24
+        split = str(getattr(self.cfg, 'cu_split', None) or os.environ.get('REFVSR_CU_SPLIT') or '')
+        if split and layout in ('pfm', 'pf_m'):
+            # CU partitions (round 6, ABI 13; measurement knob, off by default -- DESIGN 5 "CU partitions"): 'p,f,m' CUs for the
+            # three streams as disjoint ranges (multiples of 8 = an equal share of every XCD); f = 0 with layout pf_m
+            cp, cf, cm = (int(v) for v in split.split(','))
+            p_ = ops.CuStream(0, cp, dev)
+            f_ = ops.CuStream(cp, cf, dev) if (layout == 'pfm' and cf > 0) else p_
+            m = ops.CuStream(cp + (cf if f_ is not p_ else 0), cm, dev)
+            self._pipe = [m, m, f_, p_]
             self.pipe_layout = layout
             self._pipe_calls = 0
+            return self._pipe
+        m = torch.cuda.Stream(device=dev)
+        if layout == 'one':                       # measurement aid (bench.py): every section on ONE internal stream -- HIP events
+            two = False                           # around a run of launches then bracket nothing but that run
+        m2 = torch.cuda.Stream(device=dev) if two else m
+        p_ = m if layout == 'one' else torch.cuda.Stream(device=dev)
+        f_ = p_ if layout in ('pf_m', 'one') else torch.cuda.Stream(device=dev)
+        self._pipe = [m, m2, f_, p_]
+        self.pipe_layout = layout
+        self._pipe_calls = 0
         return self._pipe
 
-    def _pipe_inputs(self, tensors, input_ready, streams, caller):
-        """When the internal streams may read the inputs of a pipelined call.  input_ready = 'materialised' (the caller asserts the
-        tensors are final, e.g. a pre-loaded clip): no wait.  An event / stream: the internal streams wait for it (a producer on a copy
-        stream keeps the calls pipelined).  None: wait for the caller's stream as it stands -- always safe, but the caller's stream also
-        carries the wait for the previous call's result, so consecutive calls then overlap only inside a call."""
+    def _pipe_begin(self, tensors, input_ready, depth, streams):
+        """Start of a pipelined call, after _pipe_streams.  The host waits until fewer than `depth` calls are in flight (each call
+        holds its intermediates until its `done` event), then lets the internal `streams` read the inputs `tensors`:
+        input_ready = 'materialised' (the caller asserts the tensors are final, e.g. a pre-loaded clip): no wait.  An event / stream:
+        the internal streams wait for it (a producer on a copy stream keeps the calls pipelined).  None: wait for the caller's stream
+        as it stands -- always safe, but the caller's stream also carries the wait for the previous call's result, so consecutive
+        calls then overlap only inside a call.  Returns the caller's stream."""
+        while len(self._inflight) >= depth:
+            self._inflight.popleft().synchronize()
+        caller = torch.cuda.current_stream()
+        uniq = []
+        for st in streams:
+            if all(st is not s_ for s_ in uniq):
+                uniq.append(st)
         if input_ready is None:
             input_ready = torch.cuda.Event()
             input_ready.record(caller)
         if not isinstance(input_ready, str):
-            for st in streams:
+            for st in uniq:
                 if isinstance(input_ready, torch.cuda.Stream):
                     st.wait_stream(input_ready)
                 else:
@@ -981,8 +1000,68 @@ class Engine(object):
         elif input_ready != 'materialised':
             raise ValueError("input_ready must be None, 'materialised', a torch.cuda.Event or a torch.cuda.Stream")
         for x in tensors:
-            for st in streams:
+            for st in uniq:
                 x.record_stream(st)
+        return caller
+
+    def _pipe_end(self, caller, M, outs, vis=None, timing=False):
+        """End of a pipelined call whose last section ran on M: the caller's stream waits for the results and owns them from here
+        on, and the call counts as in flight until its `done` event (returned)."""
+        done = torch.cuda.Event(enable_timing=timing)
+        done.record(M)
+        caller.wait_event(done)
+        for o in outs:
+            o.record_stream(caller)
+        if vis:
+            for v in vis.values():
+                v.record_stream(caller)
+        self._inflight.append(done)
+        return done
+
+    @staticmethod
+    def _await_inputs(input_ready):
+        """Sequential path: the current stream waits for an input_ready event / stream (None, 'materialised': nothing to wait for)."""
+        if isinstance(input_ready, torch.cuda.Stream):
+            torch.cuda.current_stream().wait_stream(input_ready)
+        elif isinstance(input_ready, torch.cuda.Event):
+            torch.cuda.current_stream().wait_event(input_ready)
+
+    def _publish(self, f, share):
+        """Make a prepared frame context safe to free while any of the `share` streams may still read it (allocator)."""
+        for x in [f.lr, f.ref, f.lr8, f.conf, f.idx, f.aligned, f.aligned_up] + list(f.pyr or ()):
+            for st in share:
+                x.record_stream(st)
+
+    def _prepare_window(self, fr, start, share, n_ctx, head=False):
+        """P section of a pipelined call for one window, on the current stream: prepares fr[start:] and publishes each frame for
+        `share`; a frame prepared here carries `ready`, the event its consumers on the other streams wait for.  Frames newer than
+        n_ctx were cloned by this call.  head: the frame at the window's end also runs the first `bw_head_blocks` layers of its
+        backward step (a function of that frame alone: load balance between the streams)."""
+        for f in fr:
+            if f.uid > n_ctx:
+                for st in share:
+                    f.lr.record_stream(st)
+                    f.ref.record_stream(st)
+        t = len(fr)
+        for i in range(start, t):          # (a restarting forward branch walks the first frames too: cached)
+            f = fr[i]
+            if f.conf is None:
+                self.pyramid(f)
+                self.prepare_frame(f)
+                if head and i == t - 1 and self.bw_head_blocks >= 0:
+                    h, w = f.lr.shape[1:]
+                    zf = self._zeros((h, w, self._state_cs()), torch.float16, f.lr.device)
+                    f.bw_head = (self.bw_head_blocks, self.resblocks(f.lr8, zf, 'backward_resblocks', stop=self.bw_head_blocks))
+                    for st in share:
+                        f.bw_head[1].record_stream(st)
+                self._publish(f, share)
+                f.ready = torch.cuda.Event()
+                f.ready.record()
+            else:
+                if f.pyr is None:
+                    self.pyramid(f)
+                if f.ready is None:          # prepared on M by a first-frame call: make it safe on the other streams too
+                    self._publish(f, share)
 
     @torch.no_grad()
     def _forward_pipelined(self, lrs, refs, is_first_frame, want_vis, frame_ids, input_ready=None):
@@ -1000,17 +1079,10 @@ class Engine(object):
         if not bool(self.cfg.EVAL.is_gradio) and (is_first_frame or self.fw_feat is not None):
             outs, vis = self._forward_group_pipelined([(lrs, refs, frame_ids)], input_ready, want_vis, first=bool(is_first_frame))
             return outs[0], vis
-        caller = torch.cuda.current_stream()
         M0, M1, F_, P = self._pipe_streams(dev)
         M, Mo = (M0, M1) if (self._pipe_calls & 1) == 0 else (M1, M0)
         self._pipe_calls += 1
-        while len(self._inflight) >= self.pipe_depth:
-            self._inflight.popleft().synchronize()
-        streams = []
-        for st in (M0, M1, F_, P):
-            if all(st is not s_ for s_ in streams):
-                streams.append(st)
-        self._pipe_inputs((lrs, refs), input_ready, streams, caller)
+        caller = self._pipe_begin((lrs, refs), input_ready, self.pipe_depth, (M0, M1, F_, P))
         # restart of the forward branch: run the reference order on M, after everything in flight
         for st in (P, F_, Mo):
             M.wait_stream(st)
@@ -1019,14 +1091,7 @@ class Engine(object):
                                          else is_first_frame, want_vis, frame_ids)
         for st in (F_, P, Mo):
             st.wait_stream(M)
-        done = torch.cuda.Event()
-        done.record(M)
-        caller.wait_event(done)
-        out.record_stream(caller)
-        if vis:
-            for v in vis.values():
-                v.record_stream(caller)
-        self._inflight.append(done)
+        self._pipe_end(caller, M, [out], vis)
         return out, vis
 
     # ------------------------------------------------------------------ frame groups: multi-map launches (opt-in extension)
@@ -1214,8 +1279,8 @@ class Engine(object):
         rst = [bool(self.max_frame_itr_num is not None and self._itr_after(b) == self.max_frame_itr_num) for b in range(B)]
         if first:
             rst[0] = True
-        caller = torch.cuda.current_stream()
-        M0, M1, F_, P = self._pipe_streams(dev)
+        share = tuple(self._pipe_streams(dev))
+        M0, M1, F_, P = share
         # B = 1: the backward branch + upsampler of consecutive calls are independent of each other (only the forward branch carries
         # state): calls alternate between the two M streams of the wider models (mid_channels = 24: M0 is M1, see _pipe_streams).
         # Groups stay on one (two M streams alternating between groups: 210.5 vs 220.4 frames/s, profiles/r05_group_knobs_ab.txt)
@@ -1225,60 +1290,22 @@ class Engine(object):
         # the host may run at most pipe_depth calls ahead of the GPU (each call in flight holds its intermediates: ~0.3 GB at 270p; a
         # group holds B calls' worth).  Depth 3 since round 4: with 2 the host had ~2.4 ms of slack when it issued a call and a 6 ms
         # hiccup of the host reached the GPU as a gap (profiles/r04_stream_layout_ab.txt)
-        while len(self._inflight) >= (self.pipe_depth if B == 1 else max(1, self.pipe_depth - 1)):
-            self._inflight.popleft().synchronize()
-        streams = []
-        for st in (M0, M1, F_, P):
-            if all(st is not s_ for s_ in streams):
-                streams.append(st)
-        self._pipe_inputs([x for lrs, refs, _ in wins for x in (lrs, refs)], input_ready, streams, caller)
+        caller = self._pipe_begin([x for lrs, refs, _ in wins for x in (lrs, refs)], input_ready,
+                                  self.pipe_depth if B == 1 else max(1, self.pipe_depth - 1), share)
         sev = self.stream_events                     # bench.py: per-call (start, end) HIP events of the P / F / M sections
         mark = (lambda st: None) if sev is None else _timed_event
         tev = {'n': B}
-        share = (M0, M1, F_, P)
-
-        def publish(f):
-            for x in [f.lr, f.ref, f.lr8, f.conf, f.idx, f.aligned, f.aligned_up] + list(f.pyr):
-                for st in share:
-                    x.record_stream(st)
         # ---- P: everything that is a function of single frames / frame pairs, for all windows of the call
         with ops.on_stream(P):
             tev['P0'] = mark(P)
             n_ctx = next(_uid)
             frs = self._frames_group(wins)                        # new frames are cloned here, on P
-            for fr in frs:
-                for f in fr:
-                    if f.uid > n_ctx:
-                        for st in share:
-                            f.lr.record_stream(st)
-                            f.ref.record_stream(st)
             for b, fr in enumerate(frs):
-                for i in range(0 if rst[b] else ctr, t):          # (a roll-over window's forward branch walks its first frames too: cached)
-                    f = fr[i]
-                    if f.conf is None:
-                        self.pyramid(f)
-                        self.prepare_frame(f)
-                        if B == 1 and i == t - 1 and self.bw_head_blocks >= 0:
-                            # (a group's own preparation computes no backward head: its whole first step is cheaper as multi-map launches)
-                            zf = self._zeros((h, w, self._state_cs()), torch.float16, dev)
-                            f.bw_head = (self.bw_head_blocks, self.resblocks(f.lr8, zf, 'backward_resblocks', stop=self.bw_head_blocks))
-                            for st in share:
-                                f.bw_head[1].record_stream(st)
-                        publish(f)
-                        f.ready = torch.cuda.Event()
-                        f.ready.record()
-                    else:
-                        if f.pyr is None:
-                            self.pyramid(f)
-                        if f.ready is None:          # prepared on M by a first-frame call: make it safe on the other streams too
-                            publish(f)
-            # the call's new flows in batched SPyNet passes: the backward flows and the forward flow of every window
-            need = []
-            for b, fr in enumerate(frs):
-                need += [(fr[i], fr[i + 1]) for i in range(ctr, t - 1)] + [(fr[ctr + 1], fr[ctr])]
-                if rst[b]:
-                    need += [(fr[i], fr[i - 1]) for i in range(1, ctr + 1)]           # forward flows of the first frames (cached pairs cost nothing)
-            held = self.flows(need, share)                        # (kept until the end of the issue: the cache may trim them)
+                # (a group's own preparation computes no backward head: its whole first step is cheaper as multi-map launches)
+                self._prepare_window(fr, 0 if rst[b] else ctr, share, n_ctx, head=B == 1)
+            # the call's new flows in batched SPyNet passes: the backward flows and the forward flow of every window (`held`: kept
+            # until the end of the issue, the cache may trim them)
+            held = self.flows([pr for b, fr in enumerate(frs) for pr in _flow_pairs(fr, rst[b])], share)
             tev['P1'] = mark(P)
         # ---- F: the forward-branch steps, one frame after the other (the carried state)
         fws, ev_fw = [], []
@@ -1304,46 +1331,18 @@ class Engine(object):
         outs, vis = [], None
         with ops.on_stream(M):
             tev['M0'] = mark(M)
-            cs_ = self._state_cs()
-            feats = [self._zeros((h, w, cs_), torch.float16, dev)] * B
-            feat_ups = [self._zeros((2 * h, 2 * w, cs_), torch.float16, dev)] * B
-            confs = [self._zeros((1, h, w), torch.float32, dev)] * B
-            for i in range(t - 1, ctr - 1, -1):
-                fs = [fr[i] for fr in frs]
-                for f in fs:
-                    if f.ready is not None:
-                        M.wait_event(f.ready)
-                fls = None
-                if i < t - 1:
-                    fls = [self.flow(fr[i], fr[i + 1], share) for fr in frs]         # cached by P above: waits on its event
-                if B == 1:
-                    f1, u1, c1 = self._prop_step(fs[0], 'backward_resblocks', feats[0], feat_ups[0], confs[0], None if fls is None else fls[0])
-                    feats, feat_ups, confs = [f1], [u1], [c1]
-                else:
-                    feats, feat_ups, confs = self._prop_step_b(fs, 'backward_resblocks', feats, feat_ups, confs, fls)
+            bw_ups, bw_confs = self._backward_chains(frs, lambda b, i: self.flow(frs[b][i], frs[b][i + 1], share), wait=True)
             for b, fr in enumerate(frs):
                 M.wait_event(ev_fw[b])
-                outs.append(self.compute_up(feat_ups[b], fws[b][1], confs[b], fws[b][2], fr[ctr].lr))
+                outs.append(self.compute_up(bw_ups[b], fws[b][1], bw_confs[b], fws[b][2], fr[ctr].lr))
             if want_vis and B == 1:
-                vis = collections.OrderedDict()
-                vis['conf_map'] = frs[0][ctr].conf
-                vis['conf_map_prop'] = ops.max2(confs[0], fws[0][2])
-                vis['conf_map_prop_backward'] = confs[0]
-                vis['conf_map_prop_forward'] = fws[0][2]
+                vis = self._conf_vis(frs[0][ctr], bw_confs[0], fws[0][2])
         del held
         self.frame_itr_num = self._itr_after(B)                       # (+ B, through the roll-overs inside the group; RefVSR.py:292-295)
-        done = torch.cuda.Event(enable_timing=sev is not None)
-        done.record(M)
+        done = self._pipe_end(caller, M, outs, vis, timing=sev is not None)
         if sev is not None:
             tev['M1'] = done
             sev.append(tev)
-        caller.wait_event(done)
-        for o in outs:
-            o.record_stream(caller)
-        if vis:
-            for v in vis.values():
-                v.record_stream(caller)
-        self._inflight.append(done)
         return outs, vis
 
     # ------------------------------------------------------------------ n > 1: the samples of a batch as multi-map launches (round 5)
@@ -1384,43 +1383,17 @@ class Engine(object):
             return lead._forward_multi_pipelined(engines, lrs, refs, frame_ids, input_ready)
 
     def _forward_multi_pipelined(self, engines, lrs, refs, frame_ids, input_ready):
-        n, t, _, h, w = lrs.shape
+        n, t = lrs.shape[:2]
         ctr, dev = t // 2, lrs.device
         for b in range(n):
             self._check_window(lrs[b], refs[b])
-        caller = torch.cuda.current_stream()
-        M0, M1, F_, P = self._pipe_streams(dev)
-        M = M0
+        share = tuple(self._pipe_streams(dev))
+        M0, M1, F_, P = share
         self._pipe_calls += 1
         for e in engines:
             e._pipe, e.pipe_layout, e._pipe_calls = self._pipe, self.pipe_layout, self._pipe_calls
             e._await_fw_up(e.fw_feat_up)
-        while len(self._inflight) >= self.pipe_depth:
-            self._inflight.popleft().synchronize()
-        streams = []
-        for st in (M0, M1, F_, P):
-            if all(st is not s_ for s_ in streams):
-                streams.append(st)
-        if input_ready is None:
-            input_ready = torch.cuda.Event()
-            input_ready.record(caller)
-        if not isinstance(input_ready, str):
-            for st in streams:
-                if isinstance(input_ready, torch.cuda.Stream):
-                    st.wait_stream(input_ready)
-                else:
-                    st.wait_event(input_ready)
-        elif input_ready != 'materialised':
-            raise ValueError("input_ready must be None, 'materialised', a torch.cuda.Event or a torch.cuda.Stream")
-        for st in streams:
-            lrs.record_stream(st)
-            refs.record_stream(st)
-        share = (M0, M1, F_, P)
-
-        def publish(f):
-            for x in [f.lr, f.ref, f.lr8, f.conf, f.idx, f.aligned, f.aligned_up] + list(f.pyr):
-                for st in share:
-                    x.record_stream(st)
+        caller = self._pipe_begin((lrs, refs), input_ready, self.pipe_depth, share)
         # ---- P: per-sample preparation of the new frames and flows
         frs = []
         with ops.on_stream(P):
@@ -1428,25 +1401,8 @@ class Engine(object):
                 n_ctx = next(_uid)
                 fr = e._frames(lrs[b], refs[b], frame_ids[b])
                 frs.append(fr)
-                for f in fr:
-                    if f.uid > n_ctx:
-                        for st in share:
-                            f.lr.record_stream(st)
-                            f.ref.record_stream(st)
-                for i in range(ctr, t):
-                    f = fr[i]
-                    if f.conf is None:
-                        e.pyramid(f)
-                        e.prepare_frame(f)
-                        publish(f)
-                        f.ready = torch.cuda.Event()
-                        f.ready.record()
-                    else:
-                        if f.pyr is None:
-                            e.pyramid(f)
-                        if f.ready is None:
-                            publish(f)
-                e.flows([(fr[i], fr[i + 1]) for i in range(ctr, t - 1)] + [(fr[ctr + 1], fr[ctr])], share)
+                e._prepare_window(fr, ctr, share, n_ctx)
+                e.flows(_flow_pairs(fr, False), share)
         # ---- F: the forward-branch step of all samples as multi-map launches
         with ops.on_stream(F_):
             for e, fr in zip(engines, frs):
@@ -1467,32 +1423,13 @@ class Engine(object):
             ev_fw = torch.cuda.Event()
             ev_fw.record()
         # ---- M: the backward branches of all samples step by step as multi-map launches, then the upsamplers
-        outs = []
-        with ops.on_stream(M):
-            cs_ = self._state_cs()
-            feats = [self._zeros((h, w, cs_), torch.float16, dev)] * n
-            feat_ups = [self._zeros((2 * h, 2 * w, cs_), torch.float16, dev)] * n
-            confs = [self._zeros((1, h, w), torch.float32, dev)] * n
-            for i in range(t - 1, ctr - 1, -1):
-                fs = [fr[i] for fr in frs]
-                for f in fs:
-                    if f.ready is not None:
-                        M.wait_event(f.ready)
-                fls = None
-                if i < t - 1:
-                    fls = [e.flow(fr[i], fr[i + 1], share) for e, fr in zip(engines, frs)]
-                feats, feat_ups, confs = self._prop_step_b(fs, 'backward_resblocks', feats, feat_ups, confs, fls)
-            M.wait_event(ev_fw)
-            for b, fr in enumerate(frs):
-                outs.append(self.compute_up(feat_ups[b], fw_up[b], confs[b], fw_conf[b], fr[ctr].lr))
+        with ops.on_stream(M0):
+            bw_ups, bw_confs = self._backward_chains(frs, lambda b, i: engines[b].flow(frs[b][i], frs[b][i + 1], share), wait=True)
+            M0.wait_event(ev_fw)
+            outs = [self.compute_up(bw_ups[b], fw_up[b], bw_confs[b], fw_conf[b], fr[ctr].lr) for b, fr in enumerate(frs)]
         for e in engines:
             e.frame_itr_num += 1
-        done = torch.cuda.Event()
-        done.record(M)
-        caller.wait_event(done)
-        for o in outs:
-            o.record_stream(caller)
-        self._inflight.append(done)
+        self._pipe_end(caller, M0, outs)
         return outs
 
     def _side_stream(self, dev):
@@ -1521,16 +1458,31 @@ class Engine(object):
         self._await_fw_up(feat_up)                        # (split hand-off: the 2x state may still be arriving -- first read here)
         return self.rap(f, conf, x, warp2(feat_up, fl))
 
-    def _backward_branch(self, fr, flow, t, h, w):
-        """Backward propagation branch (RefVSR.py:211-238): restarts from zeros in every window."""
-        ctr, dev, cs_ = t // 2, fr[0].lr.device, self._state_cs()
-        feat = self._zeros((h, w, cs_), torch.float16, dev)
-        feat_up = self._zeros((2 * h, 2 * w, cs_), torch.float16, dev)
-        conf = self._zeros((1, h, w), torch.float32, dev)
+    def _backward_chains(self, frs, flow, wait=False):
+        """Backward propagation branches (RefVSR.py:211-238) of B >= 1 windows: each restarts from zeros and walks from its last
+        frame down to the centre.  B = 1 runs the single-map launch list (_prop_step), B >= 2 one multi-map launch per layer over
+        the B chains (_prop_step_b).  flow(b, i): window b's flow from frame i to i + 1 (backward_flows[:, i] = FlowNet(lrs[i],
+        lrs[i+1])).  wait: the frames were prepared on another stream, each step first waits for its frames' `ready`.  Returns the
+        B 2x maps and the B confidence maps, on the current stream."""
+        B, t = len(frs), len(frs[0])
+        ctr, dev, cs_ = t // 2, frs[0][0].lr.device, self._state_cs()
+        h, w = frs[0][0].lr.shape[1:]
+        feats = [self._zeros((h, w, cs_), torch.float16, dev)] * B
+        feat_ups = [self._zeros((2 * h, 2 * w, cs_), torch.float16, dev)] * B
+        confs = [self._zeros((1, h, w), torch.float32, dev)] * B
         for i in range(t - 1, ctr - 1, -1):
-            fl = flow(i, i + 1) if i < t - 1 else None    # backward_flows[:, i] = FlowNet(lrs[i], lrs[i+1])
-            feat, feat_up, conf = self._prop_step(fr[i], 'backward_resblocks', feat, feat_up, conf, fl)
-        return feat_up, conf
+            fs = [fr[i] for fr in frs]
+            if wait:
+                for f in fs:
+                    if f.ready is not None:
+                        torch.cuda.current_stream().wait_event(f.ready)
+            fls = None if i == t - 1 else [flow(b, i) for b in range(B)]
+            if B == 1:
+                f1, u1, c1 = self._prop_step(fs[0], 'backward_resblocks', feats[0], feat_ups[0], confs[0], None if fls is None else fls[0])
+                feats, feat_ups, confs = [f1], [u1], [c1]
+            else:
+                feats, feat_ups, confs = self._prop_step_b(fs, 'backward_resblocks', feats, feat_ups, confs, fls)
+        return feat_ups, confs
 
     def _forward_branch(self, fr, flow, t, h, w, is_first_frame):
         """Forward propagation branch (RefVSR.py:240-283); updates the carried state.  Runs on the current stream."""
@@ -1569,12 +1521,8 @@ class Engine(object):
         with torch.cuda.device(lrs.device):          # launches go to the tensors' device, whatever the current device is
             if self.takes_pipelined_path(frame_ids, want_log):
                 return self._forward_pipelined(lrs, refs, is_first_frame, want_vis, frame_ids, input_ready)
-            cur = torch.cuda.current_stream()
-            if isinstance(input_ready, torch.cuda.Stream):
-                cur.wait_stream(input_ready)
-            elif isinstance(input_ready, torch.cuda.Event):
-                cur.wait_event(input_ready)
-            with ops.on_stream(cur):
+            self._await_inputs(input_ready)
+            with ops.on_stream(torch.cuda.current_stream()):
                 return self._forward_seq(lrs, refs, is_first_frame, want_vis, frame_ids, want_log)
 
     def takes_pipelined_path(self, frame_ids, want_log=False):
@@ -1606,11 +1554,10 @@ class Engine(object):
             fr = self._frames(lrs, refs, frame_ids)
             flow = (lambda a, b: zero_flow) if zero_flow is not None else (lambda a, b: self.flow(fr[a], fr[b]))
             if zero_flow is None:
-                self.flows([(fr[i], fr[i + 1]) for i in range(ctr, t - 1)] + [(fr[ctr + 1], fr[ctr])] +
-                           ([(fr[i], fr[i - 1]) for i in range(1, ctr + 1)] if first_hint else []))
+                self.flows(_flow_pairs(fr, first_hint))
             for i in range(0 if first_hint else ctr, t):
                 self.prepare_frame(fr[i])
-            bw_up, conf_bw = self._backward_branch(fr, flow, t, h, w)
+            [bw_up], [conf_bw] = self._backward_chains([fr], lambda b, i: flow(i, i + 1))
             # the flows the forward branch will ask for, computed here (parallel phase) and pinned in the handle: the
             # flow cache only keeps pairs of the current window
             flows = {(ctr + 1, ctr): flow(ctr + 1, ctr)}
@@ -1645,18 +1592,9 @@ class Engine(object):
         if streams is not None:
             M = streams[0]
             share = [P, M] + [st for st in streams[1] if st is not P and st is not M]
-
-        def publish(f):
-            for x in [f.lr, f.ref, f.lr8, f.conf, f.idx, f.aligned, f.aligned_up] + list(f.pyr):
-                for st in share:
-                    x.record_stream(st)
         with torch.cuda.device(dev), ops.on_stream(P):
             frs = self._frames_group(wins)
-            need = []
-            for b, fr in enumerate(frs):
-                need += [(fr[i], fr[i + 1]) for i in range(ctr, t - 1)] + [(fr[ctr + 1], fr[ctr])]
-                if hints[b]:
-                    need += [(fr[i], fr[i - 1]) for i in range(1, ctr + 1)]
+            need = [pr for b, fr in enumerate(frs) for pr in _flow_pairs(fr, hints[b])]
             for b, fr in enumerate(frs):
                 for i in range(0 if hints[b] else ctr, t):
                     self.prepare_frame(fr[i])
@@ -1664,7 +1602,7 @@ class Engine(object):
                         # (also contexts prepared / imported ahead on this stream: safe on the other streams from here on)
                         if fr[i].pyr is None:
                             self.pyramid(fr[i])
-                        publish(fr[i])
+                        self._publish(fr[i], share)
                         fr[i].ready = torch.cuda.Event()
                         fr[i].ready.record()
             fl_all = self.flows(need, share)
@@ -1681,18 +1619,7 @@ class Engine(object):
                 M.wait_event(done_p)                               # (everything this group reads was produced on P before this point)
                 for fl in fl_all:
                     fl.record_stream(M)
-            cs_ = self._state_cs()
-            feats = [self._zeros((h, w, cs_), torch.float16, dev)] * B
-            feat_ups = [self._zeros((2 * h, 2 * w, cs_), torch.float16, dev)] * B
-            confs = [self._zeros((1, h, w), torch.float32, dev)] * B
-            if B == 1:
-                fr = frs[0]
-                bw_up, conf_bw = self._backward_branch(fr, (lambda a, b_: self.flow(fr[a], fr[b_], share)), t, h, w)
-                feat_ups, confs = [bw_up], [conf_bw]
-            else:
-                for i in range(t - 1, ctr - 1, -1):
-                    fls = None if i == t - 1 else [self.flow(fr[i], fr[i + 1], share) for fr in frs]
-                    feats, feat_ups, confs = self._prop_step_b([fr[i] for fr in frs], 'backward_resblocks', feats, feat_ups, confs, fls)
+            feat_ups, confs = self._backward_chains(frs, lambda b, i: self.flow(frs[b][i], frs[b][i + 1], share))
             ready = None
             if share is not None:
                 ready = torch.cuda.Event()
@@ -1715,14 +1642,7 @@ class Engine(object):
         that the serial chain over the ranks carries nothing but the forward-branch steps."""
         fr, t, h, w = pa['fr'], pa['t'], pa['h'], pa['w']
         ctr = t // 2
-        if self.max_frame_itr_num is not None and self.frame_itr_num == self.max_frame_itr_num:
-            is_first_frame = True                                                   # :168-170
-        if not is_first_frame and self.fw_feat is None:
-            raise RuntimeError('is_first_frame=False but no forward state is held (first call of a stream '
-                               'must pass is_first_frame=True, cf. RefVSR.py:257-258)')
-        if not is_first_frame and tuple(self.fw_feat.shape[:2]) != (h, w):
-            raise RuntimeError('frame size changed from %s to %s without is_first_frame=True'
-                               % (tuple(self.fw_feat.shape[:2]), (h, w)))
+        is_first_frame = self._branch_restarts(is_first_frame, h, w)
         with ops.on_stream(torch.cuda.current_stream()):
             def flow(a, b):
                 if pa['zero_flow'] is not None:
@@ -1746,13 +1666,7 @@ class Engine(object):
         fr, ctr = pa['fr'], pa['t'] // 2
         with ops.on_stream(torch.cuda.current_stream()):
             out = self.compute_up(pa['bw_up'], pa['fw_up'], pa['conf_bw'], pa['conf_fw'], fr[ctr].lr)
-            vis = None
-            if want_vis:
-                vis = collections.OrderedDict()
-                vis['conf_map'] = fr[ctr].conf
-                vis['conf_map_prop'] = ops.max2(pa['conf_bw'], pa['conf_fw'])
-                vis['conf_map_prop_backward'] = pa['conf_bw']
-                vis['conf_map_prop_forward'] = pa['conf_fw']
+            vis = self._conf_vis(fr[ctr], pa['conf_bw'], pa['conf_fw']) if want_vis else None
         return out, vis
 
     @torch.no_grad()
@@ -1764,6 +1678,29 @@ class Engine(object):
         if after_state is not None:
             after_state()
         return self.phase_b2(pa, want_vis)
+
+    def _branch_restarts(self, is_first_frame, h, w):
+        """Whether a call restarts the forward branch (a caller's first frame or a reset_branch roll-over, RefVSR.py:168-170); a call
+        that does not must find a carried state of its frame size."""
+        if self.max_frame_itr_num is not None and self.frame_itr_num == self.max_frame_itr_num:
+            is_first_frame = True
+        if not is_first_frame and self.fw_feat is None:
+            raise RuntimeError('is_first_frame=False but no forward state is held (first call of a stream '
+                               'must pass is_first_frame=True, cf. RefVSR.py:257-258)')
+        if not is_first_frame and tuple(self.fw_feat.shape[:2]) != (h, w):
+            raise RuntimeError('frame size changed from %s to %s without is_first_frame=True'
+                               % (tuple(self.fw_feat.shape[:2]), (h, w)))
+        return is_first_frame
+
+    @staticmethod
+    def _conf_vis(f, conf_bw, conf_fw):
+        """The eval `vis` maps of centre frame f (RefVSR.py:318-322)."""
+        vis = collections.OrderedDict()
+        vis['conf_map'] = f.conf
+        vis['conf_map_prop'] = ops.max2(conf_bw, conf_fw)
+        vis['conf_map_prop_backward'] = conf_bw
+        vis['conf_map_prop_forward'] = conf_fw
+        return vis
 
     def _sample_vis(self, f, conf_bw, conf_fw):
         """The save_sample block of the `vis` samples (RefVSR.py:301-316; identical in RefVSR_IR.py:367-384) for centre frame f."""
@@ -1811,14 +1748,7 @@ class Engine(object):
         t, h, w = self._check_window(lrs, refs)
         ctr = t // 2
         dev = lrs.device
-        if self.max_frame_itr_num is not None and self.frame_itr_num == self.max_frame_itr_num:
-            is_first_frame = True                                                   # :168-170
-        if not is_first_frame and self.fw_feat is None:
-            raise RuntimeError('is_first_frame=False but no forward state is held (first call of a stream '
-                               'must pass is_first_frame=True, cf. RefVSR.py:257-258)')
-        if not is_first_frame and tuple(self.fw_feat.shape[:2]) != (h, w):
-            raise RuntimeError('frame size changed from %s to %s without is_first_frame=True'
-                               % (tuple(self.fw_feat.shape[:2]), (h, w)))
+        is_first_frame = self._branch_restarts(is_first_frame, h, w)
         gradio = bool(self.cfg.EVAL.is_gradio)
         zero_flow = torch.zeros((2, h, w), dtype=torch.float32, device=dev) if gradio else None
         fr = self._frames(lrs, refs, frame_ids)
@@ -1836,10 +1766,7 @@ class Engine(object):
         fw_flow_in = self.fw_flow
         if not gradio and t > 1:
             # every flow this call consumes, in one batched SPyNet pass before the streams fork (cached pairs cost nothing)
-            need = [(fr[i], fr[i + 1]) for i in range(ctr, t - 1)] + [(fr[ctr + 1], fr[ctr])]
-            if is_first_frame:
-                need += [(fr[i], fr[i - 1]) for i in range(1, ctr + 1)]
-            self.flows(need, share)
+            self.flows(_flow_pairs(fr, is_first_frame), share)
         if overlap:
             for i in range(ctr, t):
                 self.pyramid(fr[i])                        # shared by both streams: build on main before the fork
@@ -1852,7 +1779,7 @@ class Engine(object):
         for i in range(range_start, t):                                             # :196-204 (+ per-frame RAP parts)
             self.prepare_frame(fr[i])
 
-        bw_up, conf_bw = self._backward_branch(fr, flow, t, h, w)
+        [bw_up], [conf_bw] = self._backward_chains([fr], lambda b, i: flow(i, i + 1))
 
         # ---- forward branch (:240-283)
         if overlap:
@@ -1866,13 +1793,7 @@ class Engine(object):
         if is_first_frame:                                                          # :292-295
             self.frame_itr_num = 0
         self.frame_itr_num += 1
-        vis = None
-        if want_vis:                                                                # :318-322
-            vis = collections.OrderedDict()
-            vis['conf_map'] = fr[ctr].conf
-            vis['conf_map_prop'] = ops.max2(conf_bw, conf)
-            vis['conf_map_prop_backward'] = conf_bw
-            vis['conf_map_prop_forward'] = conf
+        vis = self._conf_vis(fr[ctr], conf_bw, conf) if want_vis else None
         if want_log:
             dbg = self._debug_vis(fr, t, is_first_frame, range_start, fw_flow_in, flow, conf_bw, conf, want_vis)
             return out, (vis, dbg)

@@ -99,6 +99,13 @@ class EngineIR(Engine):
         walking the previous call's two propagation branches."""
         self.pipelined = bool(on)
 
+    def _publish(self, f, share):
+        """Engine._publish, and the frame's EDVR feature pyramid."""
+        Engine._publish(self, f, share)
+        for x in getattr(f, 'edvr', None) or ():
+            for st in share:
+                x.record_stream(st)
+
     # ------------------------------------------------------------------ EDVR-M feature extractor
     def _pyramid_feats(self, fr, ph, pw):
         """L1 / L2 / L3 features of one frame (RefVSR_IR.py:514-520), cached on the frame context."""
@@ -185,10 +192,7 @@ class EngineIR(Engine):
             with torch.cuda.device(lrs.device):
                 return self._forward_ir_pipelined(lrs, refs, is_first_frame, frame_ids, input_ready), None
         with torch.cuda.device(lrs.device), ops.on_stream(torch.cuda.current_stream()):
-            if isinstance(input_ready, torch.cuda.Stream):
-                torch.cuda.current_stream().wait_stream(input_ready)
-            elif isinstance(input_ready, torch.cuda.Event):
-                torch.cuda.current_stream().wait_event(input_ready)
+            self._await_inputs(input_ready)
             out, dbg = self._forward_ir(lrs, refs, is_first_frame, frame_ids, bool(want_log and want_vis))
             if self._pipe is not None:           # a sequential call (is_log) between pipelined ones: the internal streams see its state
                 for st in set(self._pipe):
@@ -198,29 +202,12 @@ class EngineIR(Engine):
 
     @torch.no_grad()
     def _forward_ir_pipelined(self, lrs, refs, is_first_frame, frame_ids, input_ready=None):
-        """_forward_ir over two internal streams (Engine._forward_pipelined's rules: dependencies by HIP events, every tensor that
-        crosses streams recorded on its consumers, the host at most pipe_depth calls ahead): P = _ir_part_a of this call, M = the
-        previous call's _ir_part_b, then this one's.  Restarts of the forward branch run both parts on M, after everything in
-        flight.  Results are bit-identical to the sequential call."""
-        dev = lrs.device
-        caller = torch.cuda.current_stream()
-        M, _, _, P = self._pipe_streams(dev)
-        while len(self._inflight) >= self.pipe_depth:
-            self._inflight.popleft().synchronize()
-        if input_ready is None:
-            input_ready = torch.cuda.Event()
-            input_ready.record(caller)
-        if not isinstance(input_ready, str):
-            for st in (M, P):
-                if isinstance(input_ready, torch.cuda.Stream):
-                    st.wait_stream(input_ready)
-                else:
-                    st.wait_event(input_ready)
-        elif input_ready != 'materialised':
-            raise ValueError("input_ready must be None, 'materialised', a torch.cuda.Event or a torch.cuda.Stream")
-        for st in (M, P):
-            lrs.record_stream(st)
-            refs.record_stream(st)
+        """_forward_ir over two internal streams, by the rules of Engine's pipelined calls (Engine._pipe_begin / _pipe_end: dependencies
+        by HIP events, every tensor that crosses streams recorded on its consumers, the host at most pipe_depth calls ahead):
+        P = _ir_part_a of this call, M = the previous call's _ir_part_b, then this one's.  Restarts of the forward branch run both
+        parts on M, after everything in flight.  Results are bit-identical to the sequential call."""
+        M, _, _, P = self._pipe_streams(lrs.device)
+        caller = self._pipe_begin((lrs, refs), input_ready, self.pipe_depth, (M, P))
         restart = is_first_frame or self.fw_feat is None or (self.max_frame_itr_num is not None and self.frame_itr_num == self.max_frame_itr_num)
         if restart:
             M.wait_stream(P)
@@ -235,11 +222,7 @@ class EngineIR(Engine):
             with ops.on_stream(M):
                 M.wait_event(ev_p)
                 out, _ = self._ir_part_b(pa)
-        done = torch.cuda.Event()
-        done.record(M)
-        caller.wait_event(done)
-        out.record_stream(caller)
-        self._inflight.append(done)
+        self._pipe_end(caller, M, [out])
         return out
 
     def _forward_ir(self, lrs, refs, is_first_frame, frame_ids, sample=False):
@@ -277,9 +260,7 @@ class EngineIR(Engine):
             # the flows of both branches in batched SPyNet passes, each carrying an event for its consumers
             self.flows([(fr[i], fr[i + 1]) for i in range(t - 1)] + [(fr[i], fr[i - 1]) for i in range(1, ctr + 1)], share)
             for f in fr:
-                for x in [f.lr, f.ref, f.lr8, f.conf, f.idx, f.aligned, f.aligned_up] + list(f.pyr or []) + list(getattr(f, 'edvr', None) or []):
-                    for st in share:
-                        x.record_stream(st)
+                self._publish(f, share)
             for x in refill.values():
                 for st in share:
                     x.record_stream(st)
