@@ -370,8 +370,31 @@ int refvsr_maxpool2(const float* src, int c, int h, int w, float* dst, void* str
  * Keys the per-frame cache (frames of consecutive sliding windows are recognised by content). */
 int refvsr_buffers_equal(const void* const* a, const void* const* b, int n_pairs, size_t n_bytes,
                          int32_t* flags, void* stream);
+/* Byte-granular form of refvsr_buffers_equal (extension, no ABI bump: added symbols only): flags[i] &= (a[i][0..n_bytes) ==
+ * b[i][0..n_bytes)) for i < n_pairs (<= 32) in one launch, the caller presets flags to 1.  Any n_bytes > 0, any alignment of
+ * either buffer.  Keys the per-frame cache for 8-bit input frames (their byte copies, see refvsr_ingest_u8). */
+int refvsr_bytes_equal(const void* const* a, const void* const* b, int n_pairs, size_t n_bytes,
+                       int32_t* flags, void* stream);
 /* out = max(a, b) elementwise on n floats (confidence accumulation, RefVSR.py:147). */
 int refvsr_max2(const float* a, const float* b, float* out, size_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * 8-bit input frames (extension, no ABI bump: added symbols only).  Replaces the loader's conversion of decoded PNG bytes,
+ * data_loader/utils.py:12-41 (`img / 255.` in float64, then float32 tensors in [0, 1] reach models/archs/RefVSR.py:151).
+ * refvsr_ingest_u8 converts nframes <= REFVSR_INGEST_MAX_FRAMES byte frames of one h x w (h, w even) in one launch:
+ *   src[i]: HOST array of device pointers, 4-byte aligned, to 3 h w bytes laid out as
+ *           REFVSR_INGEST_PLANAR  [3][h][w]   (a contiguous [n, t, 3, h, w] uint8 tensor), or
+ *           REFVSR_INGEST_HWC     [h][w][3]   (the decoders' interleaved layout: [n, t, h, w, 3] passed as its permute(0, 1, 4, 2, 3)),
+ *   dst[i]: HOST array of device pointers, 16-byte aligned, to planar float32 [3][h][w];
+ *   dst = T[src] with T[u] = (float)((double)u / 255.0), bit for bit the reference loader's value of every byte.
+ * refvsr_ingest_table copies T (256 floats) to host memory `out` (no device work).  refvsr_ingest_max_frames returns
+ * REFVSR_INGEST_MAX_FRAMES of the built library (a value, not a status).
+ * ------------------------------------------------------------------------------------------ */
+#define REFVSR_INGEST_MAX_FRAMES 16
+enum { REFVSR_INGEST_PLANAR = 0, REFVSR_INGEST_HWC = 1 };
+int refvsr_ingest_u8(const void* const* src, float* const* dst, int nframes, int h, int w, int layout, void* stream);
+int refvsr_ingest_table(float* out);
+int refvsr_ingest_max_frames(void);
 
 /* ------------------------------------------------------------------------------------------
  * Inter-frame alignment

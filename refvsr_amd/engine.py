@@ -47,15 +47,36 @@ def _flow_pairs(fr, restart):
     return need
 
 
+def _input_kind(lrs, refs):
+    """What a window's frames were made from: None for float32 frames, else the byte layouts (ops.u8_layout) of lr and ref.  Contexts
+    of another kind never match by content (a float frame is not compared with a byte frame)."""
+    return None if lrs.dtype != torch.uint8 else (ops.u8_layout(lrs), ops.u8_layout(refs))
+
+
 class FrameCtx(object):
     """Per-frame data (functions of one (lr, ref) frame pair only)."""
 
-    def __init__(self, lr, ref):
+    def __init__(self, lr, ref, ingest=None):
         self.uid = next(_uid)
         # the context OWNS its frames (clones): it outlives the call in the window cache, and a caller that refills one
         # static input buffer in place must neither change cached data nor make the content compare see "equal" frames
-        self.lr = lr.clone()    # planar fp32 [3,h,w]
-        self.ref = ref.clone()
+        self.kind = _input_kind(lr, ref)
+        if self.kind is None:
+            self.src = None
+            self.lr = lr.clone()    # planar fp32 [3,h,w]
+            self.ref = ref.clone()
+        else:
+            # 8-bit frames: the byte copies (a quarter of the fp32 size, in the caller's layout) key the content compare; the
+            # fp32 frames are filled by refvsr_ingest_u8 -- now, or in the one launch over a call's new frames when the caller
+            # collects them in `ingest` (ops.ingest_u8)
+            self.src = (lr.clone(), ref.clone())
+            self.lr = torch.empty(lr.shape, dtype=torch.float32, device=lr.device)
+            self.ref = torch.empty(ref.shape, dtype=torch.float32, device=ref.device)
+            pairs = [(self.src[0], self.lr), (self.src[1], self.ref)]
+            if ingest is None:
+                ops.ingest_u8(pairs)
+            else:
+                ingest.extend(pairs)
         self.lr8 = None         # nhwc16 [h,w,8]
         self.pyr = None         # SPyNet pyramid of lr, coarse -> fine
         self.conf = None        # planar [1,h,w]
@@ -862,10 +883,18 @@ class Engine(object):
         return ops.convert_result(ops.conv(self.cw('conv_last'), out, planar_out=True, res_planar=base, clamp=(0.0, 1.0)), self.result_dtype)
 
     # ------------------------------------------------------------------ window bookkeeping
-    def _frames(self, lrs, refs, frame_ids=None):
+    def _frames(self, lrs, refs, frame_ids=None, ingest=None):
         """Wrap the t frames of this window, reusing per-frame contexts of the previous window (or of
         earlier positions in this window) whose content is identical -- or, when the caller supplies frame ids,
-        whose id matches (no device work, no synchronisation)."""
+        whose id matches (no device work, no synchronisation).  8-bit frames: the new contexts' conversions run as one
+        ingest launch at the end, or are left in the caller's `ingest` list (one launch over several windows)."""
+        pend = [] if ingest is None else ingest
+        frames = self._window_frames(lrs, refs, frame_ids, pend)
+        if ingest is None:
+            ops.ingest_u8(pend)
+        return frames
+
+    def _window_frames(self, lrs, refs, frame_ids, pend):
         t = lrs.shape[0]
         frames = [None] * t
         if frame_ids is not None and self.cache:
@@ -877,7 +906,7 @@ class Engine(object):
                 if fr is None:
                     fr = self.ctx_pinned.pop(fid, None)            # prepared / imported ahead of its first window (prepare_context)
                     if fr is None:
-                        fr = FrameCtx(lrs[i], refs[i])
+                        fr = FrameCtx(lrs[i], refs[i], pend)
                     self.id_cache[fid] = fr
                 frames[i] = fr
             keep = set(frame_ids)
@@ -888,16 +917,21 @@ class Engine(object):
             return frames
         if not self.cache:
             self.flow_cache = {}
-            return [FrameCtx(lrs[i], refs[i]) for i in range(t)]
+            return [FrameCtx(lrs[i], refs[i], pend) for i in range(t)]
         prev = self.prev_window
         if prev and prev[0].lr.shape != lrs.shape[1:]:          # new clip geometry: nothing to reuse
             prev = []
             self.flow_cache = {}
+        kind = _input_kind(lrs, refs)
+        if kind is None:
+            same, own = ops.buffers_equal, (lambda f: (f.lr, f.ref))
+        else:                                                    # 8-bit frames: compared with the contexts' byte copies
+            same, own = ops.bytes_equal, (lambda f: f.src)
         if prev:
             # candidates in order of likelihood: the window slid by one (i+1), did not move (i), slid back (i-1);
             # all candidate pairs are compared by ONE kernel launch + one D2H sync
-            cand = [(i, i + sh) for sh in (1, 0, -1) for i in range(t) if 0 <= i + sh < len(prev)]
-            flags = ops.buffers_equal([x for i, j in cand for x in ((lrs[i], prev[j].lr), (refs[i], prev[j].ref))])
+            cand = [(i, i + sh) for sh in (1, 0, -1) for i in range(t) if 0 <= i + sh < len(prev) and prev[i + sh].kind == kind]
+            flags = same([x for i, j in cand for x in ((lrs[i], own(prev[j])[0]), (refs[i], own(prev[j])[1]))])
             for n_, (i, j) in enumerate(cand):
                 if frames[i] is None and flags[2 * n_] and flags[2 * n_ + 1]:
                     frames[i] = prev[j]
@@ -905,16 +939,16 @@ class Engine(object):
         fresh = [i for i in range(t) if frames[i] is None]
         if len(fresh) > 1:
             pp = [(a, b) for ai, a in enumerate(fresh) for b in fresh[ai + 1:]]
-            eq = ops.buffers_equal([x for a, b in pp for x in ((lrs[a], lrs[b]), (refs[a], refs[b]))])
+            eq = same([x for a, b in pp for x in ((lrs[a], lrs[b]), (refs[a], refs[b]))])
             for n_, (a, b) in enumerate(pp):
                 if eq[2 * n_] and eq[2 * n_ + 1]:
                     if frames[a] is None:
-                        frames[a] = FrameCtx(lrs[a], refs[a])
+                        frames[a] = FrameCtx(lrs[a], refs[a], pend)
                     if frames[b] is None:
                         frames[b] = frames[a]
         for i in range(t):
             if frames[i] is None:
-                frames[i] = FrameCtx(lrs[i], refs[i])
+                frames[i] = FrameCtx(lrs[i], refs[i], pend)
         live = set(f.uid for f in frames)
         self.flow_cache = {k2: v for k2, v in self.flow_cache.items() if k2[0] in live and k2[1] in live}
         self.prev_window = frames
@@ -1183,14 +1217,15 @@ class Engine(object):
         return self.rap_b(fs, confs, xs, list(ops.warp_nhwc16_up2_b(feat_ups, fls, stack=False)))
 
     def _frames_group(self, wins):
-        """_frames (id-keyed form) for the B windows of a group: the cache keeps the union of their frames."""
+        """_frames (id-keyed form) for the B windows of a group: the cache keeps the union of their frames (8-bit frames: converted
+        by one ingest launch)."""
         keep = set()
         for _, _, ids in wins:
             keep.update(ids)
         lr0 = wins[0][0]
         if self.id_cache and next(iter(self.id_cache.values())).lr.shape != lr0.shape[1:]:
             self.id_cache, self.flow_cache = {}, {}
-        out = []
+        out, pend = [], []
         for lrs, refs, ids in wins:
             assert len(ids) == lrs.shape[0]
             frames = []
@@ -1199,10 +1234,11 @@ class Engine(object):
                 if fr is None:
                     fr = self.ctx_pinned.pop(fid, None)
                     if fr is None:
-                        fr = FrameCtx(lrs[i], refs[i])
+                        fr = FrameCtx(lrs[i], refs[i], pend)
                     self.id_cache[fid] = fr
                 frames.append(fr)
             out.append(frames)
+        ops.ingest_u8(pend)                                      # (8-bit frames: the group's new frames in one launch)
         self.id_cache = {k: v for k, v in self.id_cache.items() if k in keep}
         live = set(f.uid for fr in out for f in fr)
         self.flow_cache = {k2: v for k2, v in self.flow_cache.items() if k2[0] in live and k2[1] in live}
@@ -1397,12 +1433,17 @@ class Engine(object):
         # ---- P: per-sample preparation of the new frames and flows
         frs = []
         with ops.on_stream(P):
+            n_ctx = next(_uid)
+            if lrs.dtype == torch.uint8:
+                # 8-bit frames: every sample's new frames in one ingest launch before any preparation
+                pend = []
+                frs = [e._frames(lrs[b], refs[b], frame_ids[b], pend) for b, e in enumerate(engines)]
+                ops.ingest_u8(pend)
             for b, e in enumerate(engines):
-                n_ctx = next(_uid)
-                fr = e._frames(lrs[b], refs[b], frame_ids[b])
-                frs.append(fr)
-                e._prepare_window(fr, ctr, share, n_ctx)
-                e.flows(_flow_pairs(fr, False), share)
+                if len(frs) == b:
+                    frs.append(e._frames(lrs[b], refs[b], frame_ids[b]))
+                e._prepare_window(frs[b], ctr, share, n_ctx)
+                e.flows(_flow_pairs(frs[b], False), share)
         # ---- F: the forward-branch step of all samples as multi-map launches
         with ops.on_stream(F_):
             for e, fr in zip(engines, frs):
@@ -1510,7 +1551,8 @@ class Engine(object):
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
     def forward(self, lrs, refs, is_first_frame, want_vis=False, frame_ids=None, want_log=False, input_ready=None):
-        """lrs, refs: cuda float32 [t,3,h,w].  Returns (result planar [3,4h,4w], vis dict or None).
+        """lrs, refs: cuda float32 [t,3,h,w] in [0,1], or uint8 [t,3,h,w] (value = byte / 255; contiguous or the channels-last view of
+        [t,h,w,3] bytes).  Returns (result planar [3,4h,4w], vis dict or None).
         frame_ids (optional): one hashable id per window frame -> the window cache is keyed by id instead of by
         content comparison; together with set_pipelined(True) it enables cross-call stream pipelining."""
         if is_first_frame and frame_ids is not None:
@@ -1532,7 +1574,11 @@ class Engine(object):
 
     # ------------------------------------------------------------------ two-phase forward (multi-GPU wavefront)
     def _check_window(self, lrs, refs):
-        assert lrs.is_cuda and lrs.dtype == torch.float32 and lrs.dim() == 4 and lrs.shape == refs.shape
+        assert lrs.is_cuda and lrs.dim() == 4 and lrs.shape == refs.shape
+        if lrs.dtype != refs.dtype or lrs.dtype not in (torch.float32, torch.uint8):
+            raise RuntimeError('lrs and refs must both be float32 or both uint8 (got %s, %s)' % (lrs.dtype, refs.dtype))
+        if lrs.dtype == torch.uint8 and None in _input_kind(lrs, refs):
+            raise RuntimeError('uint8 windows must be contiguous [t,3,h,w] or the channels-last view of [t,h,w,3] bytes')
         t, _, h, w = lrs.shape
         assert t >= 3 and t % 2 == 1 and h % 2 == 0 and w % 2 == 0, 'need odd t >= 3 and even h, w'
         assert not self.hd or (h % 8 == 0 and w % 8 == 0), 'flag_HD_in needs h, w divisible by 8'

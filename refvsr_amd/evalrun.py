@@ -42,11 +42,22 @@ def load_file_list(root_path):
     return [folders[i] for i in order], [files[i] for i in order]
 
 
-def read_frame(path):
-    """PIL image -> float32 [3,H,W] in [0,1] (data_loader/utils.py:12-41)."""
+def read_frame(path, dtype='float32'):
+    """PIL image -> float32 [3,H,W] in [0,1] (data_loader/utils.py:12-41), or (dtype 'uint8', extension) the decoded bytes as a uint8
+    [3,H,W] channels-last view of the [H,W,3] array: the network converts them on the device, bit-identical to the float32 frame."""
     from PIL import Image
+    if dtype == 'uint8':
+        return torch.from_numpy(np.array(Image.open(path).convert('RGB'), dtype=np.uint8)).permute(2, 0, 1)
     a = np.asarray(Image.open(path).convert('RGB'), dtype=np.float32) / 255.0
     return torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1)))
+
+
+def stack_frames(frames):
+    """torch.stack for the loader's frames: uint8 channels-last frames stay channels-last ([.., h, w, 3] bytes underneath), the layout
+    the network takes without a copy."""
+    if frames[0].dtype == torch.uint8:
+        return torch.stack([f.movedim(-3, -1) for f in frames]).movedim(-1, -3)
+    return torch.stack(frames)
 
 
 def write_frame(path, img, quality=None):
@@ -75,17 +86,19 @@ class ClipSet(object):
         assert len(self.lr_uw) == len(self.lr_w) == len(self.hr_uw) and self.lr_uw, \
             'no clips found under %s' % E.LR_data_path
         self.items = [(v, f) for v in range(len(self.lr_uw)) for f in range(len(self.lr_uw[v]))]
+        self.input_dtype = str(getattr(config, 'input_dtype', None) or 'float32')
         self._cache = {}
 
     def __len__(self):
         return len(self.items)
 
-    def _frame(self, path):
-        if path not in self._cache:
+    def _frame(self, path, dtype=None):
+        dtype = dtype or self.input_dtype
+        if (path, dtype) not in self._cache:
             if len(self._cache) > 64:
                 self._cache.clear()
-            self._cache[path] = read_frame(path)
-        return self._cache[path]
+            self._cache[(path, dtype)] = read_frame(path, dtype)
+        return self._cache[(path, dtype)]
 
     def __getitem__(self, index):
         v, f = self.items[index]
@@ -97,9 +110,9 @@ class ClipSet(object):
         if vid_filter is not None and name not in vid_filter:
             return {'is_continue': True, 'is_first': True, 'video_name': name, 'frame_len': n}
         return {
-            'LR_UW': torch.stack([self._frame(self.lr_uw[v][i]) for i in win]),
-            'LR_REF_W': torch.stack([self._frame(self.lr_w[v][i]) for i in win]),
-            'HR_UW': self._frame(self.hr_uw[v][f]),
+            'LR_UW': stack_frames([self._frame(self.lr_uw[v][i]) for i in win]),
+            'LR_REF_W': stack_frames([self._frame(self.lr_w[v][i]) for i in win]),
+            'HR_UW': self._frame(self.hr_uw[v][f], 'float32'),          # (the scores' ground truth stays float)
             'is_first': f == 0, 'video_name': name, 'video_idx': v, 'video_len': len(self.lr_uw),
             'frame_idx': f, 'frame_len': n, 'frame_name': os.path.basename(self.lr_uw[v][f]),
             'frame_ids': [(v, int(i)) for i in win],     # names the window's frames for the cross-window cache
@@ -200,8 +213,9 @@ def evaluate(config, net=None, log=print):
         if not pending:
             return
         t0 = time.time()
-        lrs = torch.stack([it['LR_UW'] for it in pending], 0).to(dev).float().contiguous()
-        rfs = torch.stack([it['LR_REF_W'] for it in pending], 0).to(dev).float().contiguous()
+        lrs, rfs = (stack_frames([it[k] for it in pending]).to(dev) for k in ('LR_UW', 'LR_REF_W'))
+        if lrs.dtype != torch.uint8:
+            lrs, rfs = lrs.float().contiguous(), rfs.float().contiguous()
         outs = net.forward_group(lrs, rfs, [it['frame_ids'] for it in pending])['result']
         torch.cuda.synchronize()
         dt = (time.time() - t0) / len(pending)
@@ -293,6 +307,9 @@ def build_config(argv=None):
     ap.add_argument('--result_dtype', default='float32', choices=['float32', 'float16', 'uint8'],
                     help="extension: what the output head stores ('uint8' = rint(255 x), the bytes of the written PNG; the scores are then "
                          "those of the quantised frame)")
+    ap.add_argument('--input_dtype', default='float32', choices=['float32', 'uint8'],
+                    help="extension: what the loader hands the network ('uint8' = the decoded bytes, converted exactly on the device: "
+                         "a quarter of the bytes in host memory and across PCIe; same scores and PNG bytes)")
     ap.add_argument('--weight_precision', default='hi_lo', choices=['hi_lo', 'fp16', 'amp'],
                     help="extension: conv weights of the engine ('fp16' = the reference's fp16-autocast arithmetic, mid_channels = 24 "
                          "models only; 'amp' = 'fp16' where the config sets is_amp)")
@@ -300,6 +317,7 @@ def build_config(argv=None):
     cfg = get_config(args.project, args.mode, args.config, args.data)
     cfg.result_dtype = args.result_dtype
     cfg.weight_precision = args.weight_precision
+    cfg.input_dtype = args.input_dtype
     if args.network:
         cfg.network = args.network
     if args.frame_num:

@@ -12,9 +12,11 @@ LIB_PATH = os.path.join(_HERE, 'librefvsr_hip.so')
 OUT_NHWC16, OUT_NHWC16_SHUFFLE2, OUT_PLANAR32 = 0, 1, 2
 RS_BICUBIC, RS_BILINEAR, RS_BILINEAR_AC, RS_NEAREST = 0, 1, 2, 3
 RESULT_F32, RESULT_F16, RESULT_U8 = 0, 1, 2
+INGEST_PLANAR, INGEST_HWC = 0, 1
 MATCH_KP, MATCH_ROWCHUNK, MATCH_COLBLOCK = 152, 256, 512
 ABI_VERSION = 15
 MAX_MAPS = 4
+INGEST_MAX_FRAMES = 16                      # REFVSR_INGEST_MAX_FRAMES: byte frames per refvsr_ingest_u8 launch
 RESBLOCK24_BLOB_BYTES = 43264
 RESBLOCK24_F16W_BLOB_BYTES = 28928          # the fp16 weight format (ABI 15)
 RESBLOCK48_BLOB_BYTES = 172544
@@ -139,6 +141,11 @@ SIGNATURES = {
     'refvsr_conv_shuffle2_batch_f16w': [_P, _I, _I, _I, _I, _P, _F, _P, _P],
     'refvsr_conf_alpha_f16w': [_P, _P, _I, _I, _I, _P, _P, _F, _P, _I, _F, _P, _P, _P],
     'refvsr_conf_alpha_batch_f16w': [_P, _P, _I, _I, _I, _I, _P, _P, _F, _P, _I, _F, _P, _P, _P],
+    # 8-bit input frames (added symbols, ABI 15 unchanged)
+    'refvsr_ingest_u8': [_P, _P, _I, _I, _I, _I, _P],
+    'refvsr_ingest_table': [_P],                 # copies the 256-entry byte -> float table to host memory
+    'refvsr_ingest_max_frames': [],              # returns REFVSR_INGEST_MAX_FRAMES
+    'refvsr_bytes_equal': [_P, _P, _I, _Z, _P, _P],
 }
 _SPECIAL = {'refvsr_abi_version': (C.c_int, []), 'refvsr_last_error': (C.c_char_p, [])}
 EXPORTS = tuple(sorted(list(SIGNATURES) + list(_SPECIAL)))
@@ -168,6 +175,9 @@ def lib():
             raise RuntimeError('refvsr_amd: ABI mismatch (library %d, binding %d)' % (h.refvsr_abi_version(), ABI_VERSION))
         if h.refvsr_max_maps() != MAX_MAPS:
             raise RuntimeError('refvsr_amd: REFVSR_MAX_MAPS mismatch (library %d, binding %d)' % (h.refvsr_max_maps(), MAX_MAPS))
+        if h.refvsr_ingest_max_frames() != INGEST_MAX_FRAMES:
+            raise RuntimeError('refvsr_amd: REFVSR_INGEST_MAX_FRAMES mismatch (library %d, binding %d)'
+                               % (h.refvsr_ingest_max_frames(), INGEST_MAX_FRAMES))
         _lib = h
     return _lib
 

@@ -18,7 +18,7 @@ import importlib
 import torch
 import torch.nn as nn
 
-from . import hip
+from . import hip, ops
 from .engine import Engine, Weights
 from .weights import state_spec, strip_module_prefix
 
@@ -31,6 +31,29 @@ def _register(root, dotted, param):
             mod.add_module(p, nn.Module())
         mod = getattr(mod, p)
     mod.register_parameter(parts[-1], param)
+
+
+def _inputs(lrs, refs, what, strict=False):
+    """The network's input contract: float frames in [0, 1] (float16 / float64 are converted to float32, as in the reference), or uint8
+    frames meaning byte / 255 -- contiguous [.., 3, h, w] or the channels-last view of [.., h, w, 3] bytes, converted exactly on the
+    device (refvsr_ingest_u8).  lrs and refs are both uint8 or both not.  strict: inputs the engine reads off the caller's stream order
+    (input_ready= on the pipelined path) are refused instead of converted."""
+    if (lrs.dtype == torch.uint8) != (refs.dtype == torch.uint8):
+        raise RuntimeError('%s: lrs and refs must both be uint8 or both float (got %s and %s)' % (what, lrs.dtype, refs.dtype))
+    if lrs.dtype == torch.uint8:
+        if strict:
+            for t_ in (lrs, refs):
+                if ops.u8_layout(t_) is None:
+                    raise RuntimeError('%s: pipelined mode with input_ready= needs uint8 inputs that are contiguous or the channels-last '
+                                       'view of [.., h, w, 3] bytes (got strides %s): convert before the producer signals, or pass '
+                                       'input_ready=None' % (what, tuple(t_.stride())))
+        return tuple(t_ if ops.u8_layout(t_) is not None else t_.contiguous() for t_ in (lrs, refs))
+    if strict:
+        for t_ in (lrs, refs):
+            if t_.dtype != torch.float32 or not t_.is_contiguous():
+                raise RuntimeError('pipelined mode with input_ready= needs contiguous float32 inputs (got %s, contiguous=%s): '
+                                   'convert before the producer signals, or pass input_ready=None' % (t_.dtype, t_.is_contiguous()))
+    return lrs.float().contiguous(), refs.float().contiguous()
 
 
 class _FlowNetHandle(nn.Module):
@@ -121,7 +144,7 @@ class Network(nn.Module):
         return self._engines
 
     def forward(self, lrs, refs, is_first_frame, is_log=False, is_train=False, frame_ids=None, input_ready=None):
-        """Same contract as RefVSR.py:151: lrs, refs [n,t,3,h,w] in [0,1]; returns OrderedDict with
+        """Same contract as RefVSR.py:151: lrs, refs [n,t,3,h,w] in [0,1] (or uint8: byte / 255, see _inputs); returns OrderedDict with
         'result' [n,3,4h,4w] (+ 'eval_vis' when is_log and config.save_sample).
         frame_ids / input_ready: extensions (window cache keyed by ids; when the inputs are final -- Engine.set_pipelined)."""
         if is_train:
@@ -132,17 +155,12 @@ class Network(nn.Module):
                                % lrs.device)
         n = lrs.shape[0]
         self.ensure_engines(n, lrs.device)
-        if input_ready is not None and any(e.takes_pipelined_path(frame_ids, bool(is_log)) for e in self._engines[:n]):
-            # the engine's internal streams will read the inputs when `input_ready` says so, not in the caller's stream order: a
-            # dtype / layout conversion here would be pending work on the caller's stream that nothing waits for -- refused
-            # instead of raced against.  (input_ready=None waits for the caller's stream, conversions included; calls that take
-            # the sequential path -- is_log, cache or overlap off -- run in the caller's stream order anyway.)
-            for t_ in (lrs, refs):
-                if t_.dtype != torch.float32 or not t_.is_contiguous():
-                    raise RuntimeError('pipelined mode with input_ready= needs contiguous float32 inputs (got %s, contiguous=%s): '
-                                       'convert before the producer signals, or pass input_ready=None' % (t_.dtype, t_.is_contiguous()))
-        lrs = lrs.float().contiguous()
-        refs = refs.float().contiguous()
+        # the engine's internal streams will read the inputs when `input_ready` says so, not in the caller's stream order: a
+        # dtype / layout conversion here would be pending work on the caller's stream that nothing waits for -- refused
+        # instead of raced against.  (input_ready=None waits for the caller's stream, conversions included; calls that take
+        # the sequential path -- is_log, cache or overlap off -- run in the caller's stream order anyway.)
+        strict = input_ready is not None and any(e.takes_pipelined_path(frame_ids, bool(is_log)) for e in self._engines[:n])
+        lrs, refs = _inputs(lrs, refs, 'forward', strict)
         want_vis = bool(is_log and self.config.save_sample)
         results, vis_all = [], []
         dbg_all = []
@@ -184,8 +202,12 @@ class Network(nn.Module):
         if not lrs.is_cuda:
             raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path' % lrs.device)
         for t_ in (lrs, refs):
-            if t_.dtype != torch.float32 or not t_.is_contiguous() or t_.dim() != 5:
-                raise RuntimeError('forward_group needs contiguous float32 [B,t,3,h,w] inputs (got %s, contiguous=%s)' % (t_.dtype, t_.is_contiguous()))
+            ok = t_.dtype == torch.uint8 and ops.u8_layout(t_) is not None or t_.dtype == torch.float32 and t_.is_contiguous()
+            if not ok or t_.dim() != 5:
+                raise RuntimeError('forward_group needs contiguous float32 or uint8 [B,t,3,h,w] inputs, or the channels-last view of uint8 '
+                                   '[B,t,h,w,3] (got %s, contiguous=%s)' % (t_.dtype, t_.is_contiguous()))
+        if lrs.dtype != refs.dtype:
+            raise RuntimeError('forward_group: lrs and refs must both be uint8 or both float32 (got %s and %s)' % (lrs.dtype, refs.dtype))
         assert len(frame_ids) == lrs.shape[0] and lrs.shape == refs.shape
         eng = self.ensure_engines(1, lrs.device)[0]
         wins = [(lrs[b], refs[b], [(0, f) for f in frame_ids[b]]) for b in range(lrs.shape[0])]
@@ -200,7 +222,7 @@ class Network(nn.Module):
         hip.lib()
         if not lrs.is_cuda:
             raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path' % lrs.device)
-        lrs, refs = lrs.float().contiguous(), refs.float().contiguous()
+        lrs, refs = _inputs(lrs, refs, 'phase_a')
         self.ensure_engines(lrs.shape[0], lrs.device)
         return [self._engines[b].phase_a(lrs[b], refs[b], None if frame_ids is None else [(b, f) for f in frame_ids],
                                          first_hint) for b in range(lrs.shape[0])]
@@ -214,7 +236,7 @@ class Network(nn.Module):
             raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path' % lrs[0].device)
         assert len(lrs) == len(refs) == len(frame_ids)
         eng = self.ensure_engines(1, lrs[0].device)[0]
-        wins = [(lrs[b].float().contiguous(), refs[b].float().contiguous(), [(0, f) for f in frame_ids[b]]) for b in range(len(lrs))]
+        wins = [_inputs(lrs[b], refs[b], 'phase_a_group') + ([(0, f) for f in frame_ids[b]],) for b in range(len(lrs))]
         return [[h] for h in eng.phase_a_group(wins, first_hints, streams)]
 
     def phase_b1(self, handles, is_first_frame):

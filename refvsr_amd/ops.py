@@ -631,6 +631,84 @@ def buffers_equal(pairs):
     return [bool(v) for v in flags.cpu().tolist()]
 
 
+def bytes_equal(pairs):
+    """pairs: list of (a, b) uint8 tensors of one size whose bytes are dense (contiguous, or a channels-last frame: u8_layout; a and b
+    may differ in alignment).  Returns a python list of bools -- True where the raw bytes are equal (one launch per 32 pairs, one D2H
+    sync).  The caller compares frames of one layout only."""
+    if not pairs:
+        return []
+    nbytes = pairs[0][0].numel()
+    flags = torch.ones(len(pairs), dtype=torch.int32, device=pairs[0][0].device)
+    for s0 in range(0, len(pairs), 32):
+        chunk = pairs[s0:s0 + 32]
+        for a, b in chunk:
+            assert a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.numel() == b.numel() == nbytes
+            assert all(x.is_contiguous() or u8_layout(x) is not None for x in (a, b))
+        pa = (C.c_void_p * len(chunk))(*[a.data_ptr() for a, _ in chunk])
+        pb = (C.c_void_p * len(chunk))(*[b.data_ptr() for _, b in chunk])
+        hip.check(hip.lib().refvsr_bytes_equal(pa, pb, len(chunk), nbytes, C.c_void_p(flags.data_ptr() + 4 * s0),
+                                               _stream()), 'bytes_equal')
+    return [bool(v) for v in flags.cpu().tolist()]
+
+
+def u8_layout(x):
+    """Layout code of a uint8 frame [3,h,w] or window [t,3,h,w] whose frames are dense: INGEST_PLANAR (contiguous) or INGEST_HWC
+    (the channels-last view of [.., h, w, 3] bytes, e.g. x.permute(0, 3, 1, 2) of a decoded window); None for any other strides."""
+    if x.dtype != torch.uint8 or x.shape[-3] != 3:
+        return None
+    if x.is_contiguous():
+        return hip.INGEST_PLANAR
+    if x.movedim(-3, -1).is_contiguous():
+        return hip.INGEST_HWC
+    return None
+
+
+def ingest_table():
+    """The library's byte -> float table (256 floats, host query, no device work): T[u] = (float)((double)u / 255.0)."""
+    t = (C.c_float * 256)()
+    hip.check(hip.lib().refvsr_ingest_table(t), 'ingest_table')
+    return list(t)
+
+
+def ingest_u8(pairs):
+    """pairs: [(src uint8 [3,h,w] (u8_layout not None), dst float32 [3,h,w] contiguous)] of one h x w: dst = src / 255 exactly as the
+    reference loader computes it (refvsr_ingest_u8).  One launch per layout and REFVSR_INGEST_MAX_FRAMES frames."""
+    if not pairs:
+        return
+    h, w = pairs[0][1].shape[1:]
+    by_layout = {}
+    for src, dst in pairs:
+        lay = u8_layout(src)
+        assert lay is not None and src.shape == (3, h, w), 'ingest_u8: uint8 [3,h,w] planar or channels-last frames of one size'
+        _planar(dst, 3)
+        assert dst.shape[1:] == (h, w)
+        by_layout.setdefault(lay, []).append((src, dst))
+    for lay, pp in sorted(by_layout.items()):
+        for s0 in range(0, len(pp), hip.INGEST_MAX_FRAMES):
+            chunk = pp[s0:s0 + hip.INGEST_MAX_FRAMES]
+            ps = (C.c_void_p * len(chunk))(*[s.data_ptr() for s, _ in chunk])
+            pd = (C.c_void_p * len(chunk))(*[d.data_ptr() for _, d in chunk])
+            hip.check(hip.lib().refvsr_ingest_u8(ps, pd, len(chunk), h, w, lay, _stream()), 'ingest_u8')
+
+
+def ingest_frames(x):
+    """uint8 [..., 3, h, w] (planar or channels-last; other strides and unaligned storage are copied first) -> a new contiguous
+    float32 tensor of the same shape, x / 255 as the reference loader computes it, frame by frame through refvsr_ingest_u8."""
+    assert x.is_cuda and x.dtype == torch.uint8 and x.dim() >= 3 and x.shape[-3] == 3, 'ingest_frames: cuda uint8 [..., 3, h, w]'
+    h, w = x.shape[-2:]
+    if u8_layout(x) is None:
+        x = x.contiguous()
+    if x.data_ptr() % 4:
+        x = x.clone()                            # (keeps the strides of a dense tensor, in fresh aligned storage)
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    if x.is_contiguous():
+        frames = x.reshape(-1, 3, h, w)
+    else:
+        frames = x.movedim(-3, -1).reshape(-1, h, w, 3).permute(0, 3, 1, 2)
+    ingest_u8(list(zip(frames, out.view(-1, 3, h, w))))
+    return out
+
+
 def warp_nhwc16(x, flow):
     _nhwc(x)
     _planar(flow, 2)

@@ -25,6 +25,7 @@ Op set (argument conventions of ops.py: `planar` = float32 [C,H,W], `nhwc16` = f
   block_gather(value_nhwc16, idx, gh, gw, s) / block_gather_rgb(value, idx, gh, gw, s)
   aligned_sample(x_nhwc16, affine, ks)
   resize(x, oh, ow, mode, sy, sx, clamp01) ; pack_nhwc16(x, cs) ; unpack_nhwc16(x, c)
+  ingest_u8(x)                                           uint8 [..., 3, h, w] (planar or channels-last) -> float32 x / 255, exact
 """
 from typing import List, Optional, Tuple
 
@@ -263,8 +264,17 @@ def register():
     def _(x, c):
         return x.new_empty((c, x.shape[0], x.shape[1]), dtype=torch.float32)
 
+    @op('ingest_u8')
+    def ingest_u8(x: torch.Tensor) -> torch.Tensor:
+        return ops.ingest_frames(x)
+
+    @ingest_u8.register_fake
+    def _(x):
+        torch._check(x.dtype == torch.uint8, lambda: 'ingest_u8 takes uint8 frames')
+        return torch.empty(x.shape, dtype=torch.float32, device=x.device)
+
 
 OP_NAMES = ('conv_mfma', 'conv24', 'resblock', 'resblock24_chain', 'resblock24_chain_batch', 'conv24_batch', 'warp_batch', 'match_argmax', 'warp', 'warp_planar', 'spynet_level_input', 'block_gather',
-            'block_gather_rgb', 'aligned_sample', 'resize', 'pack_nhwc16', 'unpack_nhwc16')
+            'block_gather_rgb', 'aligned_sample', 'resize', 'pack_nhwc16', 'unpack_nhwc16', 'ingest_u8')
 
 register()
