@@ -15,8 +15,14 @@ over the ranks with the forward-state hand-off and the context exchange over RCC
 barrier + synchronize on both sides, max over ranks, frames verified against a single-rank run; the exchange-free figure (every
 rank K steps on its own reset-aligned shard, per-GPU work fixed) sits beside it as `weak_scaling_shards`.
 
+A plain run does what `value` needs and nothing else: set-up, the untimed warm passes, the --repeats timed passes of the headline
+mode, --dump-outputs, the line (contract fields, the timed passes' samples and per-stream section times, whole_path).  `--full` adds
+every other leg below -- the other call modes interleaved with the timed passes, the rooflines, the per-kernel rates, the PCIe,
+wavefront-model and other-config legs, the CPU baseline.  The timed passes are the same in both.  N > 1: the sharded-clip leg IS the
+headline and runs in both.
+
 The stdout line is the COMPACT form of the record (< 6 KB: the driver keeps 8 KB); the complete record goes to --full-json.
-What the line carries beside the contract fields:
+What the line carries beside the contract fields (with --full):
   value              -- the build's fastest supported call mode: FRAME GROUPS (`forward_group`: --group consecutive output frames per
                         call, named by frame ids, on the engine's internal streams, inputs 'materialised') -- documented EXTENSIONS of
                         the reference's call surface, bit-identical to it; the backward branches of a group run as multi-map launches
@@ -102,6 +108,19 @@ def cpu_baseline_child(config, h, w, t):
                       % (2 * (t - 1), t // 2 + 1, t - t // 2, h, w, t, total)),
            'seconds_per_frame': total, 'host_cpu_count': os.cpu_count(), 'usable_cores': usable_cores()}
     print('CPU_BASELINE ' + json.dumps(out), flush=True)
+
+
+def make_clip_parallel(nfr, h, w, start=0, world=1):
+    """(lr, ref) of synth.make_clip(nfr, h, w, seed=0, start=start, want_gt=False), bit for bit: frame k is global frame start + k of
+    one endless clip and is computed on its own, so the frames are made on a thread pool (numpy releases the GIL inside its array
+    operations; one 270 x 480 frame is ~0.4 s of single-threaded numpy).  At most 16 threads per process, fewer for large frames: one
+    frame in flight holds ~12 fp32 planes of the HR size (768 h w bytes), kept under 4 GB in all."""
+    from concurrent.futures import ThreadPoolExecutor
+    from refvsr_amd.synth import make_clip
+    n = max(1, min(16, usable_cores() // max(1, world), nfr, int(4e9 // (768 * h * w))))
+    with ThreadPoolExecutor(n) as ex:
+        frames = list(ex.map(lambda k: make_clip(1, h, w, seed=0, start=start + k, want_gt=False), range(nfr)))
+    return torch.cat([f[0] for f in frames]), torch.cat([f[1] for f in frames])
 
 
 def queued_launch_us(fn, iters, blocker):
@@ -1008,14 +1027,16 @@ def dump_outputs(outs, out_dir, limit=DUMP_LIMIT_BYTES, seed=0):
 
 
 def emit(line, args):
-    """Complete record -> --full-json (best effort), compact line -> stdout."""
-    try:
-        os.makedirs(os.path.dirname(os.path.abspath(args.full_json)), exist_ok=True)
-        with open(args.full_json, 'w') as f:
-            json.dump(line, f)
-        line['full_record'] = os.path.relpath(args.full_json, ROOT)
-    except OSError:
-        line['full_record'] = None
+    """Complete record -> args.record (best effort; None: no file), compact line -> stdout."""
+    line['full_record'] = None
+    if args.record:
+        try:
+            os.makedirs(os.path.dirname(os.path.abspath(args.record)), exist_ok=True)
+            with open(args.record, 'w') as f:
+                json.dump(line, f)
+            line['full_record'] = os.path.relpath(args.record, ROOT)
+        except OSError:
+            pass
     print(json.dumps(line if args.verbose_line else compact_line(line)), flush=True)
 
 
@@ -1062,7 +1083,10 @@ def main():
     ap.add_argument('--group', type=int, default=4, help='output frames per forward_group call of the headline mode (multi-map launches of '
                                                          'the backward branches, 2..4); 1 = one forward() per frame, the round-4 headline')
     ap.add_argument('--full-json', default=os.path.join(ROOT, 'gpurun_out', 'bench_full.json'),
-                    help='where the complete record goes (the stdout line is the compact form of it)')
+                    help='where the complete record goes (the stdout line is the compact form of it); a plain run writes it only when '
+                         'this option is given')
+    ap.add_argument('--full', action='store_true', help='run every leg beside the headline: the other call modes interleaved with the timed '
+                                                        'passes, rooflines, kernels, pcie_inclusive, wavefront_model, other_configs, cpu_baseline')
     ap.add_argument('--verbose-line', action='store_true', help='print the complete record on stdout instead of the compact line')
     ap.add_argument('--no-dropin', action='store_true', help='skip the second timed pass through the unmodified call surface')
     ap.add_argument('--no-kernels', action='store_true', help='skip the per-kernel roofline measurements')
@@ -1082,6 +1106,7 @@ def main():
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last call of the last timed pass returned to DIR/<name>.npy (rank 0; at most 64 MB in all)')
     args = ap.parse_args()
+    args.record = args.full_json if (args.full or args.full_json != ap.get_default('full_json')) else None
     H, W_ = [int(v) for v in args.size.lower().split('x')]
     T = args.frames
     if args.cpu_baseline_only:
@@ -1134,7 +1159,7 @@ def main():
 
     from refvsr_amd import SRNet, get_config, make_state_dict
     from refvsr_amd.flops import tflop_per_frame
-    from refvsr_amd.synth import make_clip, window_indices
+    from refvsr_amd.synth import window_indices
     cfg = get_config('bench', 'bench', args.config)
     cfg.frame_num = T
     cfg.cache_windows = not args.no_cache
@@ -1149,7 +1174,7 @@ def main():
         raise SystemExit('bench.py keeps the whole synthetic clip and its sliding windows resident (host + HBM): --warmup + --steps <= 600')
     R = cfg.reset_branch or nfr
     start = rank * int(math.ceil(nfr / float(R))) * R          # reset-aligned shard start (exchange-free)
-    lr, rf, _ = make_clip(nfr, H, W_, seed=0, start=start, want_gt=False)
+    lr, rf = make_clip_parallel(nfr, H, W_, start=start, world=world)
     lr, rf = lr.to(dev), rf.to(dev)                             # inputs resident in HBM
     # the sliding windows are materialised before the timed region (inputs resident in HBM)
     wins = [window_indices(f, nfr, T) for f in range(nfr)]
@@ -1250,16 +1275,16 @@ def main():
 
     use_ids = not args.no_frame_ids
     pipelined = use_ids and not args.no_pipeline and cfg.cache_windows
-    want_dropin = not args.no_dropin and (use_ids or pipelined)
+    want_dropin = args.full and not args.no_dropin and (use_ids or pipelined)
     # headline call mode: frame groups (forward_group: the backward branches of G consecutive output frames as multi-map launches)
     # where the engine has the multi-map launch list (mid_channels = 24), else one forward() per frame
     G = max(1, min(4, args.group)) if (pipelined and eng.group_ok()) else 1
     if H * W_ > 4 * 270 * 480 and '--group' not in sys.argv:
         G = 1                                       # (1080p -> 8K: four frames' 8K intermediates; one frame per call unless asked for)
-    want_percall = G > 1 and not args.no_dropin
+    want_percall = args.full and G > 1 and not args.no_dropin
     # ---- warm-up proper (the first timed pass used to be the first 36 ms of GPU work of the process): untimed
-    # passes of both call modes until >= args.warm_seconds of real work have run -- kernels loaded, allocator pools grown for
-    # BOTH modes, clocks and power state settled
+    # passes of every call mode the run times until >= args.warm_seconds of real work have run -- kernels loaded, allocator pools
+    # grown for each mode, clocks and power state settled
     tw = time.perf_counter()
     nwarm = 0
     while True:
@@ -1283,8 +1308,9 @@ def main():
     gc.collect()
     if not args.no_gc_freeze:
         gc.freeze()
-    # ---- R timed repetitions, the two call modes interleaved (fast / reference surface / fast / ...): every sample is printed,
-    # `value` is the MEDIAN of the fast mode's samples
+    # ---- R timed repetitions, with --full the other call modes interleaved (fast / one frame per call / reference surface / fast / ...):
+    # every sample is printed, `value` is the MEDIAN of the fast mode's samples.  The timed passes record the same HIP events in a
+    # plain run as with --full (the rooflines read them only there): the K timed steps are the same in both.
     samples, samples_dropin, samples_percall, sums, ev = [], [], [], [], None
     nrep = max(1, args.repeats)
     for rep in range(nrep):
@@ -1307,7 +1333,7 @@ def main():
     fps_samples = [world * args.steps / x for x in samples]
     # (round 6, ADVICE r5: the mode is fixed BEFORE the measurement -- frame groups wherever the engine has the multi-map launch list;
     #  rounds 4-5 reported the faster of the two modes measured, a max-of-medians with a small upward bias.  The other mode's rate stays
-    #  in the line as `one_frame_per_call`.)
+    #  in the line as `one_frame_per_call` (--full).)
     headline_mode = 'frame groups' if G > 1 else 'one frame per call'
     # The fused-ResBlock launches are ~10 us each: with the internal streams feeding the GPU concurrently the HIP events around a
     # run of them also bracket the other stream's kernels that get scheduled in between (measured 18.6 us per launch where
@@ -1316,7 +1342,7 @@ def main():
     # Group mode (round 5): the launches of record are the MULTI-MAP launches of the backward branches (G maps behind one launch);
     # they are timed in one more pass of the same group calls with every internal section on ONE stream (pipe layout 'one').
     ev_rb = None
-    if eng.rb24 and cfg.mid_channels == 24:            # (every rank: timed_pass holds barriers)
+    if args.full and eng.rb24 and cfg.mid_channels == 24:   # (every rank: timed_pass holds barriers)
         if G > 1:
             lay = getattr(cfg, 'pipe_layout', None)
             cfg.pipe_layout, eng._pipe = 'one', None
@@ -1355,7 +1381,7 @@ def main():
     # first-frame latency (SURVEY 8(d) asks for it beside the steady-state rate): a new clip on a cold window cache,
     # measured AFTER the timed region, host clock around one synchronised call; never part of `value`
     first_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             net.Network.reset()
             torch.cuda.synchronize()
@@ -1371,7 +1397,7 @@ def main():
     # waits for them through input_ready=<event>; every result goes device -> host behind the call), host clock to the last
     # result in host memory.  One untimed + three timed passes after the timed region.
     pcie = None
-    if rank == 0 and world == 1 and pipelined and not args.no_dropin:
+    if args.full and rank == 0 and world == 1 and pipelined and not args.no_dropin:
         try:
             pcie = pcie_inclusive_pass(net, args, all_lr, all_rf, wins, start, G, dev)
             # ... and with config.result_dtype = 'uint8' (round 6): the output head stores the 8-bit frame itself
@@ -1388,7 +1414,7 @@ def main():
     # `traffic` of the two roofline kernels measured in THIS run (round 6): two rocprofv3 --pmc child passes (counters only, the GPU is
     # idle meanwhile); any failure -- no rocprofv3, a refused counter, a timeout -- falls back to the committed profiles/pmc_*.json
     live_pmc, live_pmc_err = None, None
-    if rank == 0 and world == 1 and not args.no_live_pmc and (H, W_) == (270, 480) and args.config == 'config_RefVSR_small_L1':
+    if args.full and rank == 0 and world == 1 and not args.no_live_pmc and (H, W_) == (270, 480) and args.config == 'config_RefVSR_small_L1':
         try:
             torch.cuda.synchronize()
             live_pmc = live_pmc_traffic()
@@ -1416,12 +1442,13 @@ def main():
                        'dropin_frames_per_s': round(dropin['value'], 2) if dropin else None,
                        'one_frame_per_call_frames_per_s': round(percall['value'], 2) if percall else None,
                        'pipe_layout': getattr(eng, 'pipe_layout', None) if pipelined else None,
+                       'full': bool(args.full),
                        'precision': 'fp16 HWC feature maps + fp16 hi+lo MFMA weights, fp32 accumulate; fp32 matching features / flows / '
                                     'output; arg-max decided at fp32 accuracy (fp16 GEMM top-2 + fp32 re-rank + split-fp16 search of ambiguous columns)'},
             'dropin_surface': dropin,
             'one_frame_per_call': percall,
-            # every timed repetition of the fast mode (frames/s); `value` = their median.  The K steps are timed `repeats` times,
-            # interleaved with the reference-surface passes, after `warm_seconds` of untimed passes of both modes.
+            # every timed repetition of the fast mode (frames/s); `value` = their median.  The K steps are timed `repeats` times
+            # (with --full interleaved with the other call modes' passes), after `warm_seconds` of untimed passes of every mode timed.
             'samples': [round(v, 2) for v in fps_samples], 'min': min(fps_samples), 'median': fps, 'max': max(fps_samples),
             'repeats': len(fps_samples), 'untimed_warm_passes': nwarm, 'untimed_warm_seconds': round(warm_s, 3),
             # per-stream section times of the median-nearest and of the slowest pass (HIP events around the P / F / M sections of
@@ -1431,97 +1458,98 @@ def main():
                         'slow_passes': [{'rep': i, 'frames_per_s': round(fps_samples[i], 2), 'sections': sums[i]}
                                         for i in range(len(samples)) if fps_samples[i] < 0.9 * max(fps_samples)]},
         }
-        # ---- rooflines from HIP events.  `roofline` = the time-dominant kernel: the fused 24-channel ResBlock
-        # (resblock24_kernel, 156 launches per frame, ~28 % of the device time; events bracket every run of >= 8 blocks on the
-        # LR map in the single-stream pass above, duration / blocks = per-launch time incl. the gaps between the launches);
-        # `roofline_match_top2` = the matching GEMM (one launch per frame, ~14 %).  Configurations whose blocks do not run on
-        # that kernel (C = 48) report the matching kernel as `roofline`.
-        ev, cev = ev if ev else (None, None)
-        rb_line = None
-        # chain events: (start, end, blocks, h, w[, maps per launch]); group mode: the multi-map launches only
-        cev5 = [(c[0], c[1], c[2], c[3], c[4], (c[5] if len(c) > 5 else 1)) for c in (cev or [])]
-        maps_per_launch = G if any(c[5] == G for c in cev5) else 1
-        runs = [(a.elapsed_time(b), n) for a, b, n, hh, ww, bb in cev5 if (hh, ww) == (H, W_) and n >= 8 and bb == maps_per_launch]
-        if runs:
-            per_launch_ms = sum(m for m, _ in runs) / sum(n for _, n in runs)
-            C_ = cfg.mid_channels
-            flops = maps_per_launch * 2 * 2.0 * 9 * C_ * C_ * H * W_
-            ach = flops / (per_launch_ms * 1e-3) / 1e12
-            traffic, tsrc = None, None
-            pj = os.path.join(ROOT, 'profiles', 'pmc_kernels.json')
-            if live_pmc is not None and (H, W_) == (270, 480):
-                tj = live_pmc[0].get('traffic_bytes_per_launch', {})
-                traffic = tj.get('resblock LR x%d maps' % maps_per_launch) if maps_per_launch > 1 else tj.get('resblock LR')
-                tsrc = ('LIVE: two rocprofv3 --pmc child passes of this run (FETCH_SIZE, WRITE_SIZE: separate processes, counters only) on '
-                        'tools/pmc_kernels.py; FETCH_SIZE x 2 (gfx950, 16-byte coalesced reads) + WRITE_SIZE, KiB units')
-            if traffic is None and os.path.exists(pj) and (H, W_) == (270, 480):
-                try:
-                    tj = json.load(open(pj)).get('traffic_bytes_per_launch', {})
+        if args.full:
+            # ---- rooflines from HIP events.  `roofline` = the time-dominant kernel: the fused 24-channel ResBlock
+            # (resblock24_kernel, 156 launches per frame, ~28 % of the device time; events bracket every run of >= 8 blocks on the
+            # LR map in the single-stream pass above, duration / blocks = per-launch time incl. the gaps between the launches);
+            # `roofline_match_top2` = the matching GEMM (one launch per frame, ~14 %).  Configurations whose blocks do not run on
+            # that kernel (C = 48) report the matching kernel as `roofline`.
+            ev, cev = ev if ev else (None, None)
+            rb_line = None
+            # chain events: (start, end, blocks, h, w[, maps per launch]); group mode: the multi-map launches only
+            cev5 = [(c[0], c[1], c[2], c[3], c[4], (c[5] if len(c) > 5 else 1)) for c in (cev or [])]
+            maps_per_launch = G if any(c[5] == G for c in cev5) else 1
+            runs = [(a.elapsed_time(b), n) for a, b, n, hh, ww, bb in cev5 if (hh, ww) == (H, W_) and n >= 8 and bb == maps_per_launch]
+            if runs:
+                per_launch_ms = sum(m for m, _ in runs) / sum(n for _, n in runs)
+                C_ = cfg.mid_channels
+                flops = maps_per_launch * 2 * 2.0 * 9 * C_ * C_ * H * W_
+                ach = flops / (per_launch_ms * 1e-3) / 1e12
+                traffic, tsrc = None, None
+                pj = os.path.join(ROOT, 'profiles', 'pmc_kernels.json')
+                if live_pmc is not None and (H, W_) == (270, 480):
+                    tj = live_pmc[0].get('traffic_bytes_per_launch', {})
                     traffic = tj.get('resblock LR x%d maps' % maps_per_launch) if maps_per_launch > 1 else tj.get('resblock LR')
-                    if traffic is None and maps_per_launch > 1 and tj.get('resblock LR'):
-                        traffic = tj['resblock LR'] * maps_per_launch
-                    tsrc = 'STATIC: profiles/pmc_kernels.json (rocprofv3 --pmc FETCH_SIZE x2 gfx950 correction + WRITE_SIZE in separate passes on tools/pmc_kernels.py; re-measured on the round-6 tree, tools/gpu_runs/r6_call8.sh, raw counters profiles/r06_pmc_kernels_*.csv), not measured in this run'
-                except Exception:  # noqa: BLE001
-                    traffic = None
-            # Both roofs.  Algorithmic bytes per launch = every map read once + written once (fp16 HWC, 48 bytes per
-            # pixel each way) + one weight blob; arithmetic intensity = useful FLOPs / those bytes; the roof that GOVERNS is the HBM one
-            # when the intensity lies below the ridge (peak FLOP/s / peak bytes/s = 312 FLOP/byte), else the MFMA one.  `achieved` /
-            # `peak` / `frac` are those of the governing roof, the other roof's fraction is beside it.
-            abytes = maps_per_launch * 2.0 * H * W_ * 48 + 43264
-            ai = flops / abytes
-            ridge = PEAK_F16_TFLOPS * 1e12 / (PEAK_HBM_GBS * 1e9)
-            hbm_gbs = abytes / (per_launch_ms * 1e-3) / 1e9
-            governing = 'hbm' if ai < ridge else 'mfma'
-            issued = 798.0 * 16384 / (2 * 2.0 * 9 * C_ * C_ * 256)
-            rb_line = {'kernel': 'resblock24_kernel (fused conv3x3-ReLU-conv3x3+residual, 24 channels, LR map %dx%d%s)' %
-                                 (H, W_, ', %d maps per launch' % maps_per_launch if maps_per_launch > 1 else ''), 'bound': governing,
-                       'maps_per_launch': maps_per_launch,
-                       'achieved': hbm_gbs if governing == 'hbm' else ach, 'peak': PEAK_HBM_GBS if governing == 'hbm' else PEAK_F16_TFLOPS,
-                       'unit': 'GB/s' if governing == 'hbm' else 'TFLOP/s',
-                       'frac': (hbm_gbs / PEAK_HBM_GBS) if governing == 'hbm' else ach / PEAK_F16_TFLOPS,
-                       'governing': '%s (arithmetic intensity %.0f FLOP/byte %s the ridge %.0f)' % (governing, ai, '<' if ai < ridge else '>=', ridge),
-                       'mfma_frac': ach / PEAK_F16_TFLOPS, 'mfma_tflops': ach, 'mfma_issued_frac': issued * ach / PEAK_F16_TFLOPS,
-                       'hbm_frac': hbm_gbs / PEAK_HBM_GBS, 'hbm_gbs': hbm_gbs, 'algorithmic_bytes_per_launch': abytes, 'arithmetic_intensity': ai,
-                       'traffic': traffic, 'traffic_source': tsrc, 'traffic_static': None if traffic is None else not str(tsrc).startswith('LIVE'),
-                       'traffic_over_algorithmic': None if traffic is None else traffic / abytes,
-                       'launches_timed': sum(n for _, n in runs),
-                       'launches_timed_in': 'one more pass of the SAME calls with every internal section on one stream (in the timed passes the '
-                                            'events around a run also bracket the other streams\' kernels)',
-                       'mean_launch_ms': per_launch_ms, 'flops_per_launch': flops,
-                       'issued_over_useful_flops': 798.0 * 16384 / (2 * 2.0 * 9 * C_ * C_ * 256),
-                       'note': 'useful FLOPs (2 x 9 x 24 x 24 x 2 convs per pixel); the kernel issues 2.46x that on the matrix pipe: x2 hi + lo '
-                               'weight halves (48 rows in 3 fragments), x1.19 the 10 x 34 halo region of conv1, x1.04 K = 216 padded to 224'}
-        ms = [a.elapsed_time(b) for a, b in (ev or [])]
-        if ms:
-            mean_ms = sum(ms) / len(ms)
-            hm, wm = (H // (cfg.scale // 2), W_ // (cfg.scale // 2)) if cfg.flag_HD_in else (H, W_)
-            n_lr, n_ref = ((hm // 2) * (wm // 2), (hm // 4) * (wm // 4)) if cfg.flag_HD_in else (hm * wm, (hm // 2) * (wm // 2))
-            flops = 2.0 * n_lr * n_ref * 144
-            ach = flops / (mean_ms * 1e-3) / 1e12
-            traffic, tsrc = None, None
-            pj = os.path.join(ROOT, 'profiles', 'pmc_match_top2.json')
-            if live_pmc is not None and (n_lr, n_ref) == (129600, 32400):
-                traffic = live_pmc[1].get('traffic_bytes_per_launch')
-                tsrc = 'LIVE: two rocprofv3 --pmc child passes of this run (FETCH_SIZE x 2 gfx950 correction + WRITE_SIZE)'
-            if traffic is None and os.path.exists(pj) and (n_lr, n_ref) == (129600, 32400):   # HBM bytes per launch from the committed PMC passes
-                try:
-                    traffic = json.load(open(pj))['traffic_bytes_per_launch']
-                    tsrc = 'STATIC: profiles/pmc_match_top2.json (rocprofv3 --pmc FETCH_SIZE x2 gfx950 correction + WRITE_SIZE; re-measured on the round-6 tree, tools/gpu_runs/r6_call8.sh), not measured in this run'
-                except Exception:  # noqa: BLE001
-                    traffic = None
-            mbytes = (n_lr + n_ref) * 304.0 + n_lr * 16.0            # fp16 rows of 152 halfs, read once; top-2 (index, value) written
-            line['roofline_match_top2'] = {'kernel': 'match_top2_kernel (fused cosine GEMM + column top-2)', 'bound': 'mfma',
-                                           'achieved': ach, 'peak': PEAK_F16_TFLOPS, 'unit': 'TFLOP/s', 'frac': ach / PEAK_F16_TFLOPS,
-                                           'governing': 'mfma (arithmetic intensity %.0f FLOP/byte >> the ridge %.0f)' % (flops / mbytes, PEAK_F16_TFLOPS * 1e3 / PEAK_HBM_GBS),
-                                           'mfma_frac': ach / PEAK_F16_TFLOPS, 'hbm_frac': mbytes / (mean_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
-                                           'traffic': traffic, 'traffic_source': tsrc, 'traffic_static': None if traffic is None else not str(tsrc).startswith('LIVE'),
-                                           'launches_timed': len(ms), 'launches_timed_in': 'the timed passes themselves (one launch per frame, events around it)',
-                                           'mean_launch_ms': mean_ms, 'flops_per_launch': flops}
-        else:
-            line['roofline_match_top2'] = None
-        line['roofline'] = rb_line if rb_line is not None else line['roofline_match_top2']
-        if live_pmc_err and isinstance(line['roofline'], dict):
-            line['roofline']['live_pmc_error'] = live_pmc_err
+                    tsrc = ('LIVE: two rocprofv3 --pmc child passes of this run (FETCH_SIZE, WRITE_SIZE: separate processes, counters only) on '
+                            'tools/pmc_kernels.py; FETCH_SIZE x 2 (gfx950, 16-byte coalesced reads) + WRITE_SIZE, KiB units')
+                if traffic is None and os.path.exists(pj) and (H, W_) == (270, 480):
+                    try:
+                        tj = json.load(open(pj)).get('traffic_bytes_per_launch', {})
+                        traffic = tj.get('resblock LR x%d maps' % maps_per_launch) if maps_per_launch > 1 else tj.get('resblock LR')
+                        if traffic is None and maps_per_launch > 1 and tj.get('resblock LR'):
+                            traffic = tj['resblock LR'] * maps_per_launch
+                        tsrc = 'STATIC: profiles/pmc_kernels.json (rocprofv3 --pmc FETCH_SIZE x2 gfx950 correction + WRITE_SIZE in separate passes on tools/pmc_kernels.py; re-measured on the round-6 tree, tools/gpu_runs/r6_call8.sh, raw counters profiles/r06_pmc_kernels_*.csv), not measured in this run'
+                    except Exception:  # noqa: BLE001
+                        traffic = None
+                # Both roofs.  Algorithmic bytes per launch = every map read once + written once (fp16 HWC, 48 bytes per
+                # pixel each way) + one weight blob; arithmetic intensity = useful FLOPs / those bytes; the roof that GOVERNS is the HBM one
+                # when the intensity lies below the ridge (peak FLOP/s / peak bytes/s = 312 FLOP/byte), else the MFMA one.  `achieved` /
+                # `peak` / `frac` are those of the governing roof, the other roof's fraction is beside it.
+                abytes = maps_per_launch * 2.0 * H * W_ * 48 + 43264
+                ai = flops / abytes
+                ridge = PEAK_F16_TFLOPS * 1e12 / (PEAK_HBM_GBS * 1e9)
+                hbm_gbs = abytes / (per_launch_ms * 1e-3) / 1e9
+                governing = 'hbm' if ai < ridge else 'mfma'
+                issued = 798.0 * 16384 / (2 * 2.0 * 9 * C_ * C_ * 256)
+                rb_line = {'kernel': 'resblock24_kernel (fused conv3x3-ReLU-conv3x3+residual, 24 channels, LR map %dx%d%s)' %
+                                     (H, W_, ', %d maps per launch' % maps_per_launch if maps_per_launch > 1 else ''), 'bound': governing,
+                           'maps_per_launch': maps_per_launch,
+                           'achieved': hbm_gbs if governing == 'hbm' else ach, 'peak': PEAK_HBM_GBS if governing == 'hbm' else PEAK_F16_TFLOPS,
+                           'unit': 'GB/s' if governing == 'hbm' else 'TFLOP/s',
+                           'frac': (hbm_gbs / PEAK_HBM_GBS) if governing == 'hbm' else ach / PEAK_F16_TFLOPS,
+                           'governing': '%s (arithmetic intensity %.0f FLOP/byte %s the ridge %.0f)' % (governing, ai, '<' if ai < ridge else '>=', ridge),
+                           'mfma_frac': ach / PEAK_F16_TFLOPS, 'mfma_tflops': ach, 'mfma_issued_frac': issued * ach / PEAK_F16_TFLOPS,
+                           'hbm_frac': hbm_gbs / PEAK_HBM_GBS, 'hbm_gbs': hbm_gbs, 'algorithmic_bytes_per_launch': abytes, 'arithmetic_intensity': ai,
+                           'traffic': traffic, 'traffic_source': tsrc, 'traffic_static': None if traffic is None else not str(tsrc).startswith('LIVE'),
+                           'traffic_over_algorithmic': None if traffic is None else traffic / abytes,
+                           'launches_timed': sum(n for _, n in runs),
+                           'launches_timed_in': 'one more pass of the SAME calls with every internal section on one stream (in the timed passes the '
+                                                'events around a run also bracket the other streams\' kernels)',
+                           'mean_launch_ms': per_launch_ms, 'flops_per_launch': flops,
+                           'issued_over_useful_flops': 798.0 * 16384 / (2 * 2.0 * 9 * C_ * C_ * 256),
+                           'note': 'useful FLOPs (2 x 9 x 24 x 24 x 2 convs per pixel); the kernel issues 2.46x that on the matrix pipe: x2 hi + lo '
+                                   'weight halves (48 rows in 3 fragments), x1.19 the 10 x 34 halo region of conv1, x1.04 K = 216 padded to 224'}
+            ms = [a.elapsed_time(b) for a, b in (ev or [])]
+            if ms:
+                mean_ms = sum(ms) / len(ms)
+                hm, wm = (H // (cfg.scale // 2), W_ // (cfg.scale // 2)) if cfg.flag_HD_in else (H, W_)
+                n_lr, n_ref = ((hm // 2) * (wm // 2), (hm // 4) * (wm // 4)) if cfg.flag_HD_in else (hm * wm, (hm // 2) * (wm // 2))
+                flops = 2.0 * n_lr * n_ref * 144
+                ach = flops / (mean_ms * 1e-3) / 1e12
+                traffic, tsrc = None, None
+                pj = os.path.join(ROOT, 'profiles', 'pmc_match_top2.json')
+                if live_pmc is not None and (n_lr, n_ref) == (129600, 32400):
+                    traffic = live_pmc[1].get('traffic_bytes_per_launch')
+                    tsrc = 'LIVE: two rocprofv3 --pmc child passes of this run (FETCH_SIZE x 2 gfx950 correction + WRITE_SIZE)'
+                if traffic is None and os.path.exists(pj) and (n_lr, n_ref) == (129600, 32400):   # HBM bytes per launch from the committed PMC passes
+                    try:
+                        traffic = json.load(open(pj))['traffic_bytes_per_launch']
+                        tsrc = 'STATIC: profiles/pmc_match_top2.json (rocprofv3 --pmc FETCH_SIZE x2 gfx950 correction + WRITE_SIZE; re-measured on the round-6 tree, tools/gpu_runs/r6_call8.sh), not measured in this run'
+                    except Exception:  # noqa: BLE001
+                        traffic = None
+                mbytes = (n_lr + n_ref) * 304.0 + n_lr * 16.0            # fp16 rows of 152 halfs, read once; top-2 (index, value) written
+                line['roofline_match_top2'] = {'kernel': 'match_top2_kernel (fused cosine GEMM + column top-2)', 'bound': 'mfma',
+                                               'achieved': ach, 'peak': PEAK_F16_TFLOPS, 'unit': 'TFLOP/s', 'frac': ach / PEAK_F16_TFLOPS,
+                                               'governing': 'mfma (arithmetic intensity %.0f FLOP/byte >> the ridge %.0f)' % (flops / mbytes, PEAK_F16_TFLOPS * 1e3 / PEAK_HBM_GBS),
+                                               'mfma_frac': ach / PEAK_F16_TFLOPS, 'hbm_frac': mbytes / (mean_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
+                                               'traffic': traffic, 'traffic_source': tsrc, 'traffic_static': None if traffic is None else not str(tsrc).startswith('LIVE'),
+                                               'launches_timed': len(ms), 'launches_timed_in': 'the timed passes themselves (one launch per frame, events around it)',
+                                               'mean_launch_ms': mean_ms, 'flops_per_launch': flops}
+            else:
+                line['roofline_match_top2'] = None
+            line['roofline'] = rb_line if rb_line is not None else line['roofline_match_top2']
+            if live_pmc_err and isinstance(line['roofline'], dict):
+                line['roofline']['live_pmc_error'] = live_pmc_err
         line['first_frame_ms'] = first_ms
         line['pcie_inclusive'] = pcie
         if dumped is not None:
@@ -1534,17 +1562,17 @@ def main():
             'achieved_tflops_per_gpu': alg * fps / world, 'frac_of_f16_mfma_peak': alg * fps / world / PEAK_F16_TFLOPS,
             'survey_8d_tflop_per_frame': sv,
             'frac_of_f16_mfma_peak_on_survey_figure': (sv * fps / world / PEAK_F16_TFLOPS) if sv else None}
-        if not args.no_kernels:
+        if args.full and not args.no_kernels:
             try:
                 line['kernels'] = kernel_rooflines(cfg, eng, H, W_, dev, None if live_pmc is None else live_pmc[0].get('traffic_bytes_per_launch'))
             except Exception as e:  # noqa: BLE001
                 line['kernels'] = {'error': repr(e)[:300]}
-        if world == 1 and not args.no_wavefront and (H, W_) == (270, 480):
+        if args.full and world == 1 and not args.no_wavefront and (H, W_) == (270, 480):
             try:
                 line['wavefront_model'] = wavefront_model_single_gpu(args, dev, H, W_)
             except Exception as e:  # noqa: BLE001
                 line['wavefront_model'] = {'error': repr(e)[:300]}
-        if world == 1 and not args.no_other_configs and args.config == 'config_RefVSR_small_L1' and (H, W_) == (270, 480):
+        if args.full and world == 1 and not args.no_other_configs and args.config == 'config_RefVSR_small_L1' and (H, W_) == (270, 480):
             # BASELINE configs[2] and configs[4] on this GPU, after the headline: never in `value`
             del win_lr, win_rf, lr, rf
             net.Network.reset()
@@ -1584,7 +1612,7 @@ def main():
         if rank == 0:
             promote_wavefront(line, wf, args, world)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             import subprocess
             try:                     # child process + timeout: the baseline leg must never take the GPU number down
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), '--cpu-baseline-only', '--config', args.config,

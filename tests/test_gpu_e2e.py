@@ -1269,7 +1269,7 @@ def test_bench_n1_prints_exactly_one_stdout_line(dev, tmp_path):
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '8', '--warmup', '3', '--repeats', '1', '--warm-seconds', '0.05',
-                        '--no-other-configs', '--no-cpu-baseline', '--no-kernels', '--full-json', str(tmp_path / 'bench_n1_full.json')],
+                        '--full', '--no-other-configs', '--no-cpu-baseline', '--no-kernels', '--full-json', str(tmp_path / 'bench_n1_full.json')],
                        capture_output=True, text=True, timeout=420, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     out_lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -1279,6 +1279,34 @@ def test_bench_n1_prints_exactly_one_stdout_line(dev, tmp_path):
     assert {'mfma_frac', 'hbm_frac', 'governing', 'traffic_static'} <= set(d['roofline'])
     assert 'restarts_vs_n1_fast_path' in d['wavefront_model_predicted_speedup']['8']
     assert d['pcie_inclusive']['result_uint8']['value'] > 0
+
+
+def test_bench_plain_run_times_the_headline_only(dev):
+    """A plain `python bench.py` (no --full) runs set-up, warm-up and the timed passes of the headline mode and prints the line: no
+    other call mode, roofline, kernel, PCIe, wavefront-model, other-config or CPU-baseline leg, and no record file unless asked for."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '8', '--warmup', '3', '--repeats', '2'],
+                       capture_output=True, text=True, timeout=300, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out_lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(out_lines) == 1 and out_lines[0].startswith('{'), r.stdout[:600]
+    d = json.loads(out_lines[0])
+    assert d['n_gpus'] == 1 and d['steps'] == 8 and d['warmup'] == 3 and d['unit'] == 'frames/s' and d['higher_is_better'] is True
+    assert d['dtype'] == 'f16' and d['metric'].startswith('4x SR frames/sec') and d['value'] > 0
+    assert abs(d['ms_per_step'] - 1e3 / d['value']) < 1e-6 * d['ms_per_step'] and len(d['samples']) == 2
+    assert d['config']['full'] is False and d['config']['headline_mode'] == 'frame groups'
+    for k in ('roofline', 'roofline_match_top2', 'cpu_baseline', 'dropin_surface', 'one_frame_per_call', 'pcie_inclusive', 'first_frame_ms',
+              'full_record'):
+        assert d.get(k) is None, k
+    for k in ('kernels', 'wavefront_model_predicted_speedup', 'other_configs'):
+        assert k not in d, k
+    assert d['streams_ms_per_frame']['wall_ms_per_call'] > 0
 
 
 def test_bench_dump_outputs_hold_the_last_timed_call(dev, tmp_path):

@@ -1128,6 +1128,22 @@ def test_bench_compact_line_keeps_the_judged_fields_under_6_kb():
     assert line_bad['value'] == 1700.0 and line_bad['scaling'] == 'weak'
 
 
+def test_bench_parallel_clip_equals_make_clip():
+    """bench.make_clip_parallel (the timed passes' inputs, frames made on a thread pool) returns synth.make_clip's tensors bit for bit,
+    from the first frame of the clip and from a shard start."""
+    import importlib.util
+    import os
+    from refvsr_amd.synth import make_clip
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_mod4', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    for start in (0, 27):
+        lr, rf, _ = make_clip(7, 36, 60, seed=0, start=start, want_gt=False)
+        lr_p, rf_p = bench.make_clip_parallel(7, 36, 60, start=start)
+        assert lr_p.dtype == lr.dtype and torch.equal(lr_p, lr) and torch.equal(rf_p, rf)
+
+
 def test_bench_dump_outputs_names_budget_and_fixed_sample(tmp_path):
     """bench.dump_outputs (pure host code, --dump-outputs): one float32 .npy per returned tensor, named after the returned structure;
     small outputs whole, large ones as the same seeded sample in every run, all files together under the 64 MB limit."""
