@@ -397,6 +397,34 @@ int refvsr_ingest_table(float* out);
 int refvsr_ingest_max_frames(void);
 
 /* ------------------------------------------------------------------------------------------
+ * Frame scores on the device (extension, no ABI bump: added symbols only).  Replaces the host-side scoring of the evaluation loop:
+ * trainers/trainer.py:252-254 (PSNR = 10 log10(1 / mse)) and evaluation/metrics.py:17-18 (skimage structural_similarity defaults:
+ * 7 x 7 uniform window over the valid positions, sample covariance, K1 = 0.01, K2 = 0.03, data range 1, mean over the channels),
+ * which evaluation/eval_qual_quan.py:86-101 calls on a frame it first copies to the host.
+ * refvsr_score_frames scores nframes <= REFVSR_SCORE_MAX_FRAMES (result, ground truth) pairs of one 3 x h x w geometry (h, w >= 7,
+ * any parity) in one launch plus one tiny reduction launch and leaves scores[i] = {mse, ssim} (float64) on the device:
+ *   mse  = mean over the 3 h w samples of (a - b)^2                      (the PSNR's log stays on the host)
+ *   ssim = mean over the 3 (h - 6)(w - 6) windows of ((2 ua ub + c1)(2 vab + c2)) / ((ua^2 + ub^2 + c1)(va + vb + c2)), box means u,
+ *          v = 49/48 (E[xy] - ux uy), c1 = 1e-4, c2 = 9e-4;  win = 7.  win = 0: mse only, the ssim field is 0.
+ *   out[i]: HOST array of device pointers to planar [3][h][w] results as the output head stores them, out_fmt = REFVSR_RESULT_F32 |
+ *           _F16 | _U8; a byte u means T[u] = (float)((double)u / 255.0), the table of refvsr_ingest_u8;
+ *   gt[i]:  HOST array of device pointers, gt_fmt = REFVSR_RESULT_F32 (planar) | REFVSR_RESULT_U8 with gt_layout =
+ *           REFVSR_INGEST_PLANAR [3][h][w] | REFVSR_INGEST_HWC [h][w][3] (the decoders' layout: the ground truth uploaded as bytes);
+ *   pointers need the natural alignment of their samples only (fp32 4, fp16 2 bytes, bytes none);
+ *   workspace: device, 16-byte aligned, workspace_bytes >= refvsr_score_workspace_bytes(nframes, h, w) (host only; 0 for a geometry
+ *           that refvsr_score_frames rejects); scores: device, 16-byte aligned, [nframes][2].
+ * Exactness: float64 arithmetic on the float32 value of every sample, direct 7-term window sums, fixed-order reduction without
+ * floating-point atomics: a pair's two numbers are the same bits on every run, on every stream and at every position of a launch;
+ * they agree with the float64 host definition (refvsr_amd/evalrun.py:ssim) to ~1e-13 (summation order).
+ * refvsr_score_max_frames returns REFVSR_SCORE_MAX_FRAMES of the built library (a value, not a status).
+ * ------------------------------------------------------------------------------------------ */
+#define REFVSR_SCORE_MAX_FRAMES 16
+size_t refvsr_score_workspace_bytes(int nframes, int h, int w);
+int refvsr_score_max_frames(void);
+int refvsr_score_frames(const void* const* out, int out_fmt, const void* const* gt, int gt_fmt, int gt_layout, int nframes, int h, int w,
+                        int win, void* workspace, size_t workspace_bytes, double* scores, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Inter-frame alignment
  * ------------------------------------------------------------------------------------------ */
 /* models/utils.py:35-43 `warp`: linspace(-1,1) base grid + flow/((Win-1)/2), grid_sample(bilinear,

@@ -7,13 +7,8 @@
 // correctly rounded quotient, and float64 -> float32 rounding of the float64 quotient gives the same value for all 256 bytes,
 // tests/test_input_u8.py).  u * (1 / 255.f) is NOT the same function (it differs on 126 of the 256 values).
 #include "common.h"
+#include "ingest_table.h"
 
-struct IngestTable { float v[256]; };
-static constexpr IngestTable ingest_table() {
-    IngestTable t{};
-    for (int u = 0; u < 256; ++u) t.v[u] = (float)((double)u / 255.0);
-    return t;
-}
 static constexpr IngestTable kIngestHost = ingest_table();
 __constant__ IngestTable kIngestDev = ingest_table();
 

@@ -87,6 +87,8 @@ class ClipSet(object):
             'no clips found under %s' % E.LR_data_path
         self.items = [(v, f) for v in range(len(self.lr_uw)) for f in range(len(self.lr_uw[v]))]
         self.input_dtype = str(getattr(config, 'input_dtype', None) or 'float32')
+        # --metrics device: the ground truth stays the decoded bytes (the device scorer looks them up: T[u] == the float32 frame)
+        self.gt_dtype = 'uint8' if getattr(E, 'metrics', 'host') == 'device' else 'float32'
         self._cache = {}
 
     def __len__(self):
@@ -112,7 +114,7 @@ class ClipSet(object):
         return {
             'LR_UW': stack_frames([self._frame(self.lr_uw[v][i]) for i in win]),
             'LR_REF_W': stack_frames([self._frame(self.lr_w[v][i]) for i in win]),
-            'HR_UW': self._frame(self.hr_uw[v][f], 'float32'),          # (the scores' ground truth stays float)
+            'HR_UW': self._frame(self.hr_uw[v][f], self.gt_dtype),      # (the scores' ground truth stays float on the host path)
             'is_first': f == 0, 'video_name': name, 'video_idx': v, 'video_len': len(self.lr_uw),
             'frame_idx': f, 'frame_len': n, 'frame_name': os.path.basename(self.lr_uw[v][f]),
             'frame_ids': [(v, int(i)) for i in win],     # names the window's frames for the cross-window cache
@@ -167,17 +169,41 @@ def evaluate(config, net=None, log=print):
     # (SRNet.forward_group: the backward branches of the G frames as multi-map launches; results bit-identical); the per-frame time in
     # the score lines is then the group's time / G
     G = max(1, int(getattr(E, 'frame_group', 1) or 1))
-    was_pipelined = bool(getattr(config, 'pipelined', False))
+    # (the state to restore is the net's own: a caller's net may have been switched on without config.pipelined saying so)
+    engines = getattr(net.Network, '_engines', None)
+    was_pipelined = bool(engines[0].pipelined) if engines else bool(getattr(config, 'pipelined', False))
     if G > 1:
         net.Network.set_pipelined(True)          # (restored at the end: the caller's plain net(...) calls keep their stream contract)
     st = {'clip_p': 0.0, 'clip_s': 0.0, 'clip_t': 0.0, 'clip_n': 0, 'first_line': True, 'prev': None}
+    # --metrics device (extension, default 'host' = the loop below as it always was): the scores come from ONE refvsr_score_frames launch
+    # per network call, on the caller's current stream (which already waits for the results, pipelined mode included: INTEGRATION.md),
+    # and cross to the host as 16 bytes per frame; the frame itself is only copied when an image is written
+    on_device = getattr(E, 'metrics', 'host') == 'device' and not getattr(E, 'qualitative_only', False)
 
-    def emit(it, out, lr_c, dt):
-        out_raw = out[0].cpu()
-        # (result_dtype 'uint8' / 'float16', extensions: the scores are then those of the quantised frame; the PNG bytes are the same)
-        out_cpu = out_raw.float() / 255.0 if out_raw.dtype == torch.uint8 else out_raw.float()
+    def score_device(outs, items):
+        from . import ops
+        from .metrics import psnr_from_mse
+        gts = [it['HR_UW'].to(dev) for it in items]              # (decoded bytes, channels-last: a quarter of the float frame)
+        for o, g in zip(outs, gts):
+            if o[0].shape != g.shape:
+                raise RuntimeError('--metrics device: result %s and ground truth %s differ in shape' % (tuple(o[0].shape), tuple(g.shape)))
+        # flag_HD_in: the host path's SSIM compares a down-scaled result with the full-size ground truth and is 0.0: mse only
+        sc = ops.score_frames([o[0] for o in outs], gts, win=0 if config.flag_HD_in else 7).cpu().tolist()
+        return [(psnr_from_mse(m), s) for m, s in sc]
+
+    def emit(it, out, lr_c, dt, scored=None):
+        if on_device and scored is None:
+            scored = score_device([out], [it])[0]
+        if scored is not None and getattr(E, 'quantitative_only', False):
+            out_raw = out_cpu = None                 # (nothing reads the frame: it stays on the device)
+        else:
+            out_raw = out[0].cpu()
+            # (result_dtype 'uint8' / 'float16', extensions: the scores are then those of the quantised frame; the PNG bytes are the same)
+            out_cpu = out_raw.float() / 255.0 if out_raw.dtype == torch.uint8 else out_raw.float()
         p = s = 0.0
-        if not getattr(E, 'qualitative_only', False):
+        if scored is not None:
+            p, s = scored
+        elif not getattr(E, 'qualitative_only', False):
             gt = it['HR_UW']
             p = psnr(out_cpu, gt)
             cmp_out = out_cpu
@@ -220,8 +246,9 @@ def evaluate(config, net=None, log=print):
         torch.cuda.synchronize()
         dt = (time.time() - t0) / len(pending)
         c = lrs.shape[1] // 2
+        scored = score_device(outs, pending) if on_device else [None] * len(pending)
         for b, it in enumerate(pending):
-            emit(it, outs[b], lrs[b, c], dt)
+            emit(it, outs[b], lrs[b, c], dt, scored[b])
         del pending[:]
 
     try:
@@ -313,6 +340,10 @@ def build_config(argv=None):
     ap.add_argument('--weight_precision', default='hi_lo', choices=['hi_lo', 'fp16', 'amp'],
                     help="extension: conv weights of the engine ('fp16' = the reference's fp16-autocast arithmetic, mid_channels = 24 "
                          "models only; 'amp' = 'fp16' where the config sets is_amp)")
+    ap.add_argument('--metrics', default='host', choices=['host', 'device'],
+                    help="extension: where PSNR / SSIM are computed ('device' = one refvsr_score_frames launch per network call in float64, "
+                         "16 bytes per frame cross to the host and with --quantitative_only the frame never does; SSIM agrees with the host "
+                         "to 1e-10, PSNR to 2e-5 dB -- the host's mean is float32 -- so a score line may differ in the fifth decimal of PSNR)")
     args, _ = ap.parse_known_args(argv)
     cfg = get_config(args.project, args.mode, args.config, args.data)
     cfg.result_dtype = args.result_dtype
@@ -329,6 +360,7 @@ def build_config(argv=None):
     E.is_gradio, E.vid_name = args.is_gradio, args.vid_name
     E.eval_mode, E.test_set, E.data = args.eval_mode, args.test_set, args.data
     E.frame_group = args.frame_group
+    E.metrics = args.metrics
     cfg.save_sample = args.save_sample
     cfg.device = 'cpu' if args.cpu else 'cuda'
     cfg.cuda = not args.cpu

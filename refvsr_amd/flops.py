@@ -74,6 +74,14 @@ def upsampler(cfg, h, w):
     return f
 
 
+def score_frames_flop(h, w):
+    """float64 operations (add, multiply, divide = 1 each) refvsr_score_frames needs for one 3 x h x w pair, counted from the definition
+    with separable direct sums and no redundancy between tiles: per sample 3 products (a a, b b, a b) and 3 for the squared error;
+    per row position 5 x 6 horizontal adds; per window 5 x 6 vertical adds, 27 for the SSIM expression (5 divisions by 49, 6 products
+    and differences of the moments, 3 scalings, 6 + 5 for numerator and denominator, the division, the running sum)."""
+    return 3.0 * (6.0 * h * w + 30.0 * h * (w - 6) + (30.0 + 27.0) * (h - 6) * (w - 6))
+
+
 def tflop_per_frame(cfg, h, w, t=5, dedup=True):
     """Algorithmic TFLOP per steady-state output frame; returns (total, breakdown dict)."""
     gemm, vgg = matching(cfg, h, w)

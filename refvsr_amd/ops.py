@@ -709,6 +709,48 @@ def ingest_frames(x):
     return out
 
 
+_SCORE_WS = {}        # (device, stream handle, h, w) -> workspace of one full refvsr_score_frames launch
+
+
+def score_frames(outs, gts, win=7):
+    """{mse, ssim} of B (result, ground truth) pairs of one 3 x h x w geometry, computed on the device (refvsr_score_frames): a
+    torch.float64 [B, 2] tensor on the current stream, no synchronisation.  outs: [B,3,h,w] tensor or B tensors [3,h,w], contiguous
+    float32 / float16 / uint8 (what the output head stores; a byte means byte / 255); gts: the same shapes, contiguous float32, or
+    uint8 planar or channels-last (u8_layout).  win = 7: both numbers; win = 0: the mse alone (ssim field 0).  One launch per
+    REFVSR_SCORE_MAX_FRAMES pairs.  PSNR = metrics.psnr_from_mse(mse) on the host."""
+    outs, gts = list(outs), list(gts)
+    assert outs and len(outs) == len(gts), 'score_frames: as many results as ground truths'
+    a0, g0 = outs[0], gts[0]
+    _, h, w = a0.shape
+    fmts = {torch.float32: hip.RESULT_F32, torch.float16: hip.RESULT_F16, torch.uint8: hip.RESULT_U8}
+    assert a0.dtype in fmts and g0.dtype in (torch.float32, torch.uint8), 'score_frames: float32 | float16 | uint8 results, float32 | uint8 ground truth'
+    lay = u8_layout(g0) if g0.dtype == torch.uint8 else hip.INGEST_PLANAR
+    for a, g in zip(outs, gts):
+        if a.shape != (3, h, w) or g.shape != (3, h, w):
+            raise RuntimeError('score_frames: result %s and ground truth %s must both be [3, %d, %d]' % (tuple(a.shape), tuple(g.shape), h, w))
+        assert a.is_cuda and g.is_cuda and a.dtype == a0.dtype and g.dtype == g0.dtype and a.is_contiguous()
+        assert (u8_layout(g) if g.dtype == torch.uint8 else (hip.INGEST_PLANAR if g.is_contiguous() else None)) == lay and lay is not None, \
+            'score_frames: ground-truth frames must be dense and of one layout'
+    st = _stream()
+    key = (a0.device, st.value, h, w)
+    ws = _SCORE_WS.get(key)
+    if ws is None:
+        if len(_SCORE_WS) > 16:
+            _SCORE_WS.clear()
+        nbytes = hip.lib().refvsr_score_workspace_bytes(hip.SCORE_MAX_FRAMES, h, w)
+        if nbytes == 0:
+            raise RuntimeError('score_frames: frames must be at least 7 x 7 (got %d x %d)' % (h, w))
+        ws = _SCORE_WS[key] = torch.empty(nbytes // 8, dtype=torch.float64, device=a0.device)
+    scores = torch.empty((len(outs), 2), dtype=torch.float64, device=a0.device)
+    for s0 in range(0, len(outs), hip.SCORE_MAX_FRAMES):
+        n = min(hip.SCORE_MAX_FRAMES, len(outs) - s0)
+        pa = (C.c_void_p * n)(*[a.data_ptr() for a in outs[s0:s0 + n]])
+        pg = (C.c_void_p * n)(*[g.data_ptr() for g in gts[s0:s0 + n]])
+        hip.check(hip.lib().refvsr_score_frames(pa, fmts[a0.dtype], pg, fmts[g0.dtype], lay, n, h, w, int(win), _ptr(ws), ws.numel() * 8,
+                                                C.c_void_p(scores.data_ptr() + 16 * s0), st), 'score_frames')
+    return scores
+
+
 def warp_nhwc16(x, flow):
     _nhwc(x)
     _planar(flow, 2)

@@ -26,6 +26,7 @@ Op set (argument conventions of ops.py: `planar` = float32 [C,H,W], `nhwc16` = f
   aligned_sample(x_nhwc16, affine, ks)
   resize(x, oh, ow, mode, sy, sx, clamp01) ; pack_nhwc16(x, cs) ; unpack_nhwc16(x, c)
   ingest_u8(x)                                           uint8 [..., 3, h, w] (planar or channels-last) -> float32 x / 255, exact
+  score_frames(outs, gts, win)                           [B,3,h,w] results / ground truths -> float64 [B,2] = {mse, ssim} on the device
 """
 from typing import List, Optional, Tuple
 
@@ -273,8 +274,17 @@ def register():
         torch._check(x.dtype == torch.uint8, lambda: 'ingest_u8 takes uint8 frames')
         return torch.empty(x.shape, dtype=torch.float32, device=x.device)
 
+    @op('score_frames')
+    def score_frames(outs: torch.Tensor, gts: torch.Tensor, win: int) -> torch.Tensor:
+        return ops.score_frames(outs, gts, win)
+
+    @score_frames.register_fake
+    def _(outs, gts, win):
+        torch._check(outs.dim() == 4 and outs.shape == gts.shape and outs.shape[1] == 3, lambda: 'score_frames takes [B,3,h,w] results and ground truths')
+        return torch.empty((outs.shape[0], 2), dtype=torch.float64, device=outs.device)
+
 
 OP_NAMES = ('conv_mfma', 'conv24', 'resblock', 'resblock24_chain', 'resblock24_chain_batch', 'conv24_batch', 'warp_batch', 'match_argmax', 'warp', 'warp_planar', 'spynet_level_input', 'block_gather',
-            'block_gather_rgb', 'aligned_sample', 'resize', 'pack_nhwc16', 'unpack_nhwc16', 'ingest_u8')
+            'block_gather_rgb', 'aligned_sample', 'resize', 'pack_nhwc16', 'unpack_nhwc16', 'ingest_u8', 'score_frames')
 
 register()
