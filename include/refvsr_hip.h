@@ -425,6 +425,32 @@ int refvsr_score_frames(const void* const* out, int out_fmt, const void* const* 
                         int win, void* workspace, size_t workspace_bytes, double* scores, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Rectangle sums for the field-of-view evaluation (extension, no ABI bump: added symbols only).  Replaces the host-side masked
+ * scoring of evaluation/eval_quan_FOV.py:155-192, which calls evaluation/metrics.py:18-30 (psnr_masked = 10 log10(sum mask /
+ * sum (a - b)^2 mask); ssim_masked = sum S mask / sum mask with S the FULL map of skimage structural_similarity: a value at every
+ * pixel, the 3-pixel border through scipy.ndimage.uniform_filter's default 'reflect' = the symmetric extension d c b a | a b c d |
+ * d c b a) 16 times per frame on a frame it first copies to the host.  Every one of those masks is a rectangle or the difference of
+ * two, so refvsr_score_regions leaves RAW sums over rectangles on the device and the host forms the 16 means
+ * (refvsr_amd/metrics.py:fov_rects / fov_table):
+ *   sums[f][r] = { sum (a - b)^2, sum S } over the three channels and the pixels y0 <= y < y1, x0 <= x < x1 of rectangle r (float64);
+ *   rects: HOST array [nrects][4] = y0, y1, x0, x1 (half-open), 1 <= nrects <= REFVSR_SCORE_MAX_RECTS, every rectangle non-empty
+ *          and inside the frame; rectangles may overlap or nest in any way;
+ *   out / gt / formats / layouts / alignment / nframes <= REFVSR_SCORE_MAX_FRAMES / h, w >= 7: exactly as refvsr_score_frames;
+ *   workspace: device, 16-byte aligned, workspace_bytes >= refvsr_score_regions_workspace_bytes(nframes, h, w, nrects) (host only; 0
+ *          for arguments that refvsr_score_regions rejects); sums: device, 16-byte aligned, [nframes][nrects][2].
+ * Exactness: the arithmetic of refvsr_score_frames (float64 on the float32 value of every sample, direct 7-term window sums) at every
+ * pixel centre, fixed-order reduction without floating-point atomics: a frame's sums are the same bits on every run, on every stream
+ * and at every position of a launch.  The window sums of the valid crop [3, h - 3) x [3, w - 3) are those of refvsr_score_frames; the
+ * tiles, hence the last bits of their total, differ.
+ * refvsr_score_max_rects returns REFVSR_SCORE_MAX_RECTS of the built library (a value, not a status).
+ * ------------------------------------------------------------------------------------------ */
+#define REFVSR_SCORE_MAX_RECTS 8
+size_t refvsr_score_regions_workspace_bytes(int nframes, int h, int w, int nrects);
+int refvsr_score_max_rects(void);
+int refvsr_score_regions(const void* const* out, int out_fmt, const void* const* gt, int gt_fmt, int gt_layout, int nframes, int h, int w,
+                         const int* rects, int nrects, void* workspace, size_t workspace_bytes, double* sums, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Inter-frame alignment
  * ------------------------------------------------------------------------------------------ */
 /* models/utils.py:35-43 `warp`: linspace(-1,1) base grid + flow/((Win-1)/2), grid_sample(bilinear,

@@ -233,3 +233,261 @@ extern "C" int refvsr_score_frames(const void* const* out, int out_fmt, const vo
     RV_LAUNCH_CHECK();
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------ rectangle sums (FOV evaluation)
+// refvsr_score_regions: per frame and per axis-aligned rectangle r (at most REFVSR_SCORE_MAX_RECTS) the RAW sums { sum (a - b)^2,
+// sum S } over the three channels and the pixels of r, where S is the FULL SSIM map of evaluation/metrics.py:18-30 (ssim_masked:
+// structural_similarity(full=True), a value at every pixel, the 3-pixel border through scipy's uniform_filter 'reflect' = the
+// symmetric extension d c b a | a b c d | d c b a).  The masked scores of evaluation/eval_quan_FOV.py:155-192 are sums and differences
+// of such sums (refvsr_amd/metrics.py:fov_table).
+//
+// Same arithmetic as score_tile_kernel (float64 on the float32 value of every sample, direct 7-term sums left to right, then top to
+// bottom, the same five moments and formula).  What differs: a tile is 32 x 64 PIXEL CENTRES (ceil(h / 32) x ceil(w / 64) tiles), its
+// 38 x 70 input tile starts 3 rows / columns before the first centre and is staged through the symmetric-reflect index (i < 0 ->
+// -i - 1, i >= n -> 2 n - 1 - i; rows that only out-of-frame centres read are clamped into the frame and never used).  The thread of
+// centre (y, x) adds S(y, x) and the centre's own (a - b)^2 (read back from the staged tile: every sample is the centre of exactly one
+// thread of one tile) to the accumulators of the rectangles that hold (y, x): the column test once per thread, the row test on the
+// wave-uniform row (scalar compares), and a rectangle that does not meet the tile -- decided from blockIdx and the arguments alone --
+// is skipped by the whole workgroup, so the order of summation never depends on data.
+// Reduction (deterministic, no floating-point atomics): per sum a fixed-order __shfl_down tree inside each wave (offsets 32 .. 1), the
+// four wave results through LDS as ((w0 + w1) + w2) + w3, one barrier for all 16 sums; plain vector stores to
+// workspace[frame][channel][tile][rect][2]; regions_finish_kernel (one workgroup per frame) gives partial sum i to slice i mod 64,
+// sums a slice in order and the 64 slices in order.  refvsr_amd/metrics.py:score_regions_model restates all of it in numpy.
+//
+// Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): the figures next to regions_tile_kernel;
+// regions_finish_kernel: 34 VGPRs, 8 KB LDS, no scratch.
+struct RegionArgs {
+    const void* a[REFVSR_SCORE_MAX_FRAMES];
+    const void* b[REFVSR_SCORE_MAX_FRAMES];
+    double* part;                      // [nframes][3][nty * ntx][nrects][2] partial sums {sum (a - b)^2, sum S}
+    int h, w, ntx, nty;
+    int afmt;                          // REFVSR_RESULT_*
+    int bkind;                         // SC_GT_*
+    int nrects;
+    int rect[REFVSR_SCORE_MAX_RECTS][4];   // y0, y1, x0, x1 (half-open); entries past nrects are empty
+};
+
+static inline int rg_tiles(int n, int t) { return (n + t - 1) / t; }        // tiles over n pixel centres
+
+__device__ __forceinline__ int rg_reflect(int i, const int n) {             // scipy.ndimage 'reflect' (numpy 'symmetric'), then clamped
+    i = i < 0 ? -i - 1 : i;
+    i = i >= n ? 2 * n - 1 - i : i;
+    return i < 0 ? 0 : i;
+}
+
+// fixed-order sum over the 64 lanes of a wave; the result is valid in lane 0
+__device__ __forceinline__ double rg_wave_sum(double v) {
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) v = v + __shfl_down(v, s, 64);
+    return v;
+}
+
+// regions_tile_kernel: 132 VGPRs, 61 SGPRs, no scratch, no spills, 22 816 B LDS, 3 waves per SIMD by registers (figures of the build
+// this file was written against -- re-check with -Rpass-analysis=kernel-resource-usage after a change).  The 16 accumulators (32
+// VGPRs) on top of the 35 doubles of the row ring put it past 128 VGPRs, one wave per SIMD fewer than score_tile_kernel: a stated
+// choice -- the kernel streams LDS into float64 adds, three workgroups per CU keep the float64 pipe fed, and a sixteen-sum spill to
+// LDS per output row would cost more than the fourth wave brings.
+__global__ void __launch_bounds__(SC_THREADS) regions_tile_kernel(RegionArgs s) {
+    __shared__ float tbl[256];
+    __shared__ float ta[SC_IH * SC_IW], tb[SC_IH * SC_IW];
+    __shared__ double red[4][2 * REFVSR_SCORE_MAX_RECTS];
+    const int tid = (int)threadIdx.x;
+    const int tile = (int)blockIdx.x, c = (int)blockIdx.y, f = (int)blockIdx.z;
+    const int ty = tile / s.ntx, tx = tile - ty * s.ntx;
+    const int y0 = ty * SC_TH, x0 = tx * SC_TW;                  // first pixel centre of the tile
+    const int h = s.h, w = s.w;
+    tbl[tid] = kScoreTable.v[tid];
+    __syncthreads();
+
+    // ---- stage the 38 x 70 input tile around the centres, symmetric-reflect at the frame's border
+    const unsigned char* __restrict__ pa = (const unsigned char*)s.a[f];
+    const unsigned char* __restrict__ pb = (const unsigned char*)s.b[f];
+    for (int e = tid; e < SC_IH * SC_IW; e += SC_THREADS) {
+        const int r = e / SC_IW, q = e - r * SC_IW;
+        const int y = rg_reflect(y0 - 3 + r, h), x = rg_reflect(x0 - 3 + q, w);      // 0 <= y < h, 0 <= x < w
+        const size_t ip = ((size_t)c * h + y) * w + x;           // planar [3][h][w]
+        float va, vb;
+        if (s.afmt == REFVSR_RESULT_F32) va = reinterpret_cast<const float*>(pa)[ip];
+        else if (s.afmt == REFVSR_RESULT_F16) va = (float)reinterpret_cast<const f16*>(pa)[ip];
+        else va = tbl[pa[ip]];
+        if (s.bkind == SC_GT_F32) vb = reinterpret_cast<const float*>(pb)[ip];
+        else if (s.bkind == SC_GT_U8_PLANAR) vb = tbl[pb[ip]];
+        else vb = tbl[pb[((size_t)y * w + x) * 3 + c]];          // interleaved [h][w][3]
+        ta[e] = va;
+        tb[e] = vb;
+    }
+    __syncthreads();
+
+    // ---- S and (a - b)^2 of the pixel centres (y0 + 8 wave + o, x0 + lane), added to the rectangles that hold them
+    const int col = tid & 63, rg = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ox = x0 + col;
+    bool touch[REFVSR_SCORE_MAX_RECTS], col_in[REFVSR_SCORE_MAX_RECTS];
+    double acc[REFVSR_SCORE_MAX_RECTS][2];
+#pragma unroll
+    for (int r = 0; r < REFVSR_SCORE_MAX_RECTS; ++r) {
+        // (blockIdx and arguments only: workgroup-uniform)
+        touch[r] = s.rect[r][0] < y0 + SC_TH && s.rect[r][1] > y0 && s.rect[r][2] < x0 + SC_TW && s.rect[r][3] > x0;
+        col_in[r] = ox >= s.rect[r][2] && ox < s.rect[r][3];
+        acc[r][0] = 0.0;
+        acc[r][1] = 0.0;
+    }
+    constexpr double c1 = 0.01 * 0.01, c2 = 0.03 * 0.03;
+    constexpr double norm = 49.0 / 48.0;
+    double hs[7][5];                                              // horizontal sums of the last seven input rows (static indices)
+#pragma unroll
+    for (int i = 0; i < SC_ROWS + 6; ++i) {
+        const float* ra = ta + (rg * SC_ROWS + i) * SC_IW + col;
+        const float* rb = tb + (rg * SC_ROWS + i) * SC_IW + col;
+        double sa = 0.0, sb = 0.0, saa = 0.0, sbb = 0.0, sab = 0.0;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+            const double a = (double)ra[k], b = (double)rb[k];
+            sa = sa + a;
+            sb = sb + b;
+            saa = saa + a * a;
+            sbb = sbb + b * b;
+            sab = sab + a * b;
+        }
+        double* hrow = hs[i % 7];
+        hrow[0] = sa; hrow[1] = sb; hrow[2] = saa; hrow[3] = sbb; hrow[4] = sab;
+        if (i >= 6) {
+            double t[5];
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {
+                double a5 = hs[(i - 6) % 7][j];
+#pragma unroll
+                for (int k = 5; k >= 0; --k) a5 = a5 + hs[(i - k) % 7][j];
+                t[j] = a5;
+            }
+            const double ua = t[0] / 49.0, ub = t[1] / 49.0;
+            const double va = norm * (t[2] / 49.0 - ua * ua);
+            const double vb = norm * (t[3] / 49.0 - ub * ub);
+            const double vab = norm * (t[4] / 49.0 - ua * ub);
+            const double num = (2.0 * ua * ub + c1) * (2.0 * vab + c2);
+            const double den = (ua * ua + ub * ub + c1) * (va + vb + c2);
+            const double ss = num / den;
+            // the centre's own sample: input row i - 3 of this thread's rows, column + 3
+            const double d = (double)ta[(rg * SC_ROWS + i - 3) * SC_IW + col + 3] - (double)tb[(rg * SC_ROWS + i - 3) * SC_IW + col + 3];
+            const double d2 = d * d;
+            const int oy = y0 + rg * SC_ROWS + (i - 6);
+#pragma unroll
+            for (int r = 0; r < REFVSR_SCORE_MAX_RECTS; ++r) {
+                if (touch[r]) {
+                    const bool in = col_in[r] && oy >= s.rect[r][0] && oy < s.rect[r][1];      // (inside the frame: rectangles are)
+                    acc[r][0] = acc[r][0] + (in ? d2 : 0.0);
+                    acc[r][1] = acc[r][1] + (in ? ss : 0.0);
+                }
+            }
+        }
+    }
+
+    // ---- 16 sums: wave trees, then the four waves through LDS
+#pragma unroll
+    for (int r = 0; r < REFVSR_SCORE_MAX_RECTS; ++r) {
+        double m = 0.0, q = 0.0;
+        if (touch[r]) {
+            m = rg_wave_sum(acc[r][0]);
+            q = rg_wave_sum(acc[r][1]);
+        }
+        if (col == 0) {
+            red[rg][2 * r] = m;
+            red[rg][2 * r + 1] = q;
+        }
+    }
+    __syncthreads();
+    if (tid < 2 * s.nrects) {
+        const double v = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+        const size_t nt = (size_t)s.ntx * s.nty;
+        s.part[(((size_t)f * 3 + c) * nt + tile) * (2 * s.nrects) + tid] = v;
+    }
+}
+
+// one workgroup per frame: the frame's n = 3 nty ntx partial sums of each of the m = 2 nrects sums -> sums[frame][rect][2].  64 slices per
+// sum (1024 threads) and four loads in flight per thread: the walk over a 1080p frame's 3 060 partial sums is bound by load latency
+#define RG_SLICES 64
+__global__ void __launch_bounds__(16 * RG_SLICES) regions_finish_kernel(const double* __restrict__ part, int n, int m, double* __restrict__ sums) {
+    __shared__ double red[RG_SLICES][2 * REFVSR_SCORE_MAX_RECTS];
+    const int tid = (int)threadIdx.x, f = (int)blockIdx.x;
+    const int j = tid & 15, g = tid >> 4;                         // sum j, slice g: partial sums g, g + 64, .. in order
+    const double* p = part + (size_t)f * n * m;
+    double v = 0.0;
+    if (j < m) {
+        int i = g;
+        for (; i + 3 * RG_SLICES < n; i += 4 * RG_SLICES) {
+            const double q0 = p[(size_t)i * m + j], q1 = p[(size_t)(i + RG_SLICES) * m + j];
+            const double q2 = p[(size_t)(i + 2 * RG_SLICES) * m + j], q3 = p[(size_t)(i + 3 * RG_SLICES) * m + j];
+            v = v + q0;
+            v = v + q1;
+            v = v + q2;
+            v = v + q3;
+        }
+        for (; i < n; i += RG_SLICES) v = v + p[(size_t)i * m + j];
+    }
+    red[g][j] = v;
+    __syncthreads();
+    if (tid < m) {
+        double t = red[0][tid];
+#pragma unroll 8
+        for (int k = 1; k < RG_SLICES; ++k) t = t + red[k][tid];
+        sums[(size_t)f * m + tid] = t;
+    }
+}
+
+extern "C" int refvsr_score_max_rects(void) { return REFVSR_SCORE_MAX_RECTS; }
+
+extern "C" size_t refvsr_score_regions_workspace_bytes(int nframes, int h, int w, int nrects) {
+    if (nframes < 1 || !sc_geometry_ok(h, w) || nrects < 1 || nrects > REFVSR_SCORE_MAX_RECTS) return 0;
+    return (size_t)nframes * 3 * rg_tiles(h, SC_TH) * rg_tiles(w, SC_TW) * nrects * 2 * sizeof(double);
+}
+
+extern "C" int refvsr_score_regions(const void* const* out, int out_fmt, const void* const* gt, int gt_fmt, int gt_layout, int nframes,
+                                    int h, int w, const int* rects, int nrects, void* workspace, size_t workspace_bytes, double* sums,
+                                    void* stream) {
+    RV_CHECK(out && gt, "score_regions: null frame table");
+    RV_CHECK(nframes >= 1 && nframes <= REFVSR_SCORE_MAX_FRAMES, "score_regions: 1..%d frames per launch", REFVSR_SCORE_MAX_FRAMES);
+    RV_CHECK(sc_geometry_ok(h, w), "score_regions: h, w must be at least 7 (the SSIM window) and h * w at most 2^29");
+    RV_CHECK(nrects >= 1 && nrects <= REFVSR_SCORE_MAX_RECTS, "score_regions: 1..%d rectangles", REFVSR_SCORE_MAX_RECTS);
+    RV_CHECK(rects, "score_regions: null rectangle table");
+    for (int r = 0; r < nrects; ++r) {
+        const int* q = rects + 4 * r;
+        RV_CHECK(q[0] < q[1] && q[2] < q[3], "score_regions: rectangle %d is empty", r);
+        RV_CHECK(q[0] >= 0 && q[1] <= h && q[2] >= 0 && q[3] <= w, "score_regions: rectangle %d leaves the frame", r);
+    }
+    RV_CHECK(out_fmt == REFVSR_RESULT_F32 || out_fmt == REFVSR_RESULT_F16 || out_fmt == REFVSR_RESULT_U8,
+             "score_regions: result format must be REFVSR_RESULT_F32 | _F16 | _U8");
+    RV_CHECK(gt_fmt == REFVSR_RESULT_F32 || gt_fmt == REFVSR_RESULT_U8, "score_regions: ground-truth format must be REFVSR_RESULT_F32 | _U8");
+    RV_CHECK(gt_layout == REFVSR_INGEST_PLANAR || gt_layout == REFVSR_INGEST_HWC,
+             "score_regions: ground-truth layout must be REFVSR_INGEST_PLANAR | REFVSR_INGEST_HWC");
+    RV_CHECK(!(gt_fmt == REFVSR_RESULT_F32 && gt_layout == REFVSR_INGEST_HWC), "score_regions: the interleaved layout is for uint8 ground truth");
+    RV_CHECK(workspace && sums, "score_regions: null workspace / sums");
+    RV_CHECK(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)sums & 15) == 0, "score_regions: workspace and sums must be 16-byte aligned");
+    RV_CHECK(workspace_bytes >= refvsr_score_regions_workspace_bytes(nframes, h, w, nrects),
+             "score_regions: workspace too small (%zu bytes, %zu needed)", workspace_bytes,
+             refvsr_score_regions_workspace_bytes(nframes, h, w, nrects));
+    RegionArgs a;
+    memset(&a, 0, sizeof(a));                                    // (rectangles past nrects: empty, met by no tile)
+    const uintptr_t amask = out_fmt == REFVSR_RESULT_F32 ? 3 : out_fmt == REFVSR_RESULT_F16 ? 1 : 0;
+    const uintptr_t bmask = gt_fmt == REFVSR_RESULT_F32 ? 3 : 0;
+    for (int i = 0; i < nframes; ++i) {
+        RV_CHECK(out[i] && gt[i], "score_regions: null pointer (frame %d)", i);
+        RV_CHECK(((uintptr_t)out[i] & amask) == 0 && ((uintptr_t)gt[i] & bmask) == 0,
+                 "score_regions: fp32 frames must be 4-byte, fp16 frames 2-byte aligned (frame %d)", i);
+        a.a[i] = out[i];
+        a.b[i] = gt[i];
+    }
+    a.part = (double*)workspace;
+    a.h = h; a.w = w;
+    a.ntx = rg_tiles(w, SC_TW); a.nty = rg_tiles(h, SC_TH);
+    a.afmt = out_fmt;
+    a.bkind = gt_fmt == REFVSR_RESULT_F32 ? SC_GT_F32 : gt_layout == REFVSR_INGEST_PLANAR ? SC_GT_U8_PLANAR : SC_GT_U8_HWC;
+    a.nrects = nrects;
+    for (int r = 0; r < nrects; ++r)
+        for (int k = 0; k < 4; ++k) a.rect[r][k] = rects[4 * r + k];
+    const int nt = a.ntx * a.nty;
+    hipLaunchKernelGGL(regions_tile_kernel, dim3(nt, 3, nframes), dim3(SC_THREADS), 0, (hipStream_t)stream, a);
+    RV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(regions_finish_kernel, dim3(nframes), dim3(16 * RG_SLICES), 0, (hipStream_t)stream, (const double*)workspace, 3 * nt,
+                       2 * nrects, sums);
+    RV_LAUNCH_CHECK();
+    return 0;
+}

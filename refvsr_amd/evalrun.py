@@ -9,6 +9,8 @@ Counterpart of the reference's eval stack, restated from its behaviour:
   * SSIM = skimage.structural_similarity defaults  -- evaluation/metrics.py:17-18 (7x7 uniform window, sample
     covariance, K1=0.01, K2=0.03, mean over channels) re-implemented (skimage is not in this image)
   * score file lines / output tree                 -- evaluation/eval_qual_quan.py:98-101,106-124,140-143
+  * `--eval_mode quan_FOV` (eval.py:16-21): PSNR / SSIM inside, outside and in rings around the overlapped field of view
+    -- evaluation/eval_quan_FOV.py:155-192 (the 16 masked scores per frame), :93-111, :196, :245-264 (its lines and blocks)
   * checkpoint loading (flat state dict, optional `module.` prefix) -- ckpt_manager.py:50-60
 
     python -m refvsr_amd.evalrun --mode amp_RefVSR_small_L1 --config config_RefVSR_small_L1 --data RealMCVSR \
@@ -147,9 +149,15 @@ def load_checkpoint(net, path):
 
 
 def evaluate(config, net=None, log=print):
-    """eval_qual_quan counterpart.  Returns dict(psnr=[..], ssim=[..], frames=N, seconds=[..])."""
+    """eval_qual_quan counterpart.  Returns dict(psnr=[..], ssim=[..], frames=N, seconds=[..]).
+    'FOV' in EVAL.eval_mode: eval_quan_FOV counterpart -- the same loop; a frame's score is its FOV table (metrics.fov_table,
+    [6 keys][fi, fo, fr][psnr, ssim]), whose key 1 fi pair is the per-frame line; the summaries are the reference's six-row blocks; no
+    image is written (the reference has that part commented out); the tables are returned as res['fov']."""
     from . import SRNet
     E = config.EVAL
+    fov = 'FOV' in str(E.eval_mode)
+    if fov and config.flag_HD_in:
+        raise RuntimeError('--eval_mode %s: flag_HD_in configs are not supported (the reference scores a cv2.resize(INTER_CUBIC) of the result)' % E.eval_mode)
     if net is None:
         if config.device != 'cuda':
             raise RuntimeError('refvsr_amd has no CPU path; run on the GPU (drop --cpu)')
@@ -165,6 +173,8 @@ def evaluate(config, net=None, log=print):
     ds = ClipSet(config)
     dev = next(net.parameters()).device
     res = {'psnr': [], 'ssim': [], 'seconds': [], 'frames': 0}
+    if fov:
+        res['fov'] = []
     # --frame_group G (extension, default 1 = the reference's loop): G consecutive windows of a clip per network call
     # (SRNet.forward_group: the backward branches of the G frames as multi-map launches; results bit-identical); the per-frame time in
     # the score lines is then the group's time / G
@@ -174,7 +184,7 @@ def evaluate(config, net=None, log=print):
     was_pipelined = bool(engines[0].pipelined) if engines else bool(getattr(config, 'pipelined', False))
     if G > 1:
         net.Network.set_pipelined(True)          # (restored at the end: the caller's plain net(...) calls keep their stream contract)
-    st = {'clip_p': 0.0, 'clip_s': 0.0, 'clip_t': 0.0, 'clip_n': 0, 'first_line': True, 'prev': None}
+    st = {'clip_p': 0.0, 'clip_s': 0.0, 'clip_t': 0.0, 'clip_n': 0, 'first_line': True, 'prev': None, 'clip_fov': 0.0}
     # --metrics device (extension, default 'host' = the loop below as it always was): the scores come from ONE refvsr_score_frames launch
     # per network call, on the caller's current stream (which already waits for the results, pipelined mode included: INTEGRATION.md),
     # and cross to the host as 16 bytes per frame; the frame itself is only copied when an image is written
@@ -187,6 +197,13 @@ def evaluate(config, net=None, log=print):
         for o, g in zip(outs, gts):
             if o[0].shape != g.shape:
                 raise RuntimeError('--metrics device: result %s and ground truth %s differ in shape' % (tuple(o[0].shape), tuple(g.shape)))
+        if fov:
+            # one refvsr_score_regions launch: 7 rectangles x 16 bytes per frame cross to the host
+            from .metrics import fov_rects, fov_table
+            h, w = gts[0].shape[-2:]
+            sums = ops.score_regions([o[0] for o in outs], gts, fov_rects(h, w)).cpu().numpy()
+            tables = [fov_table(sm, h, w) for sm in sums]
+            return [(float(t[0, 0, 0]), float(t[0, 0, 1]), t) for t in tables]
         # flag_HD_in: the host path's SSIM compares a down-scaled result with the full-size ground truth and is 0.0: mse only
         sc = ops.score_frames([o[0] for o in outs], gts, win=0 if config.flag_HD_in else 7).cpu().tolist()
         return [(psnr_from_mse(m), s) for m, s in sc]
@@ -194,15 +211,24 @@ def evaluate(config, net=None, log=print):
     def emit(it, out, lr_c, dt, scored=None):
         if on_device and scored is None:
             scored = score_device([out], [it])[0]
-        if scored is not None and getattr(E, 'quantitative_only', False):
+        if scored is not None and (fov or getattr(E, 'quantitative_only', False)):
             out_raw = out_cpu = None                 # (nothing reads the frame: it stays on the device)
         else:
             out_raw = out[0].cpu()
             # (result_dtype 'uint8' / 'float16', extensions: the scores are then those of the quantised frame; the PNG bytes are the same)
             out_cpu = out_raw.float() / 255.0 if out_raw.dtype == torch.uint8 else out_raw.float()
         p = s = 0.0
+        table = None
         if scored is not None:
-            p, s = scored
+            p, s = scored[:2]
+            table = scored[2] if fov else None
+        elif fov:
+            from .metrics import fov_scores_host
+            gt = it['HR_UW']
+            if out_cpu.shape != gt.shape:
+                raise RuntimeError('--eval_mode %s: result %s and ground truth %s differ in shape' % (E.eval_mode, tuple(out_cpu.shape), tuple(gt.shape)))
+            table = fov_scores_host(out_cpu, gt)
+            p, s = float(table[0, 0, 0]), float(table[0, 0, 1])
         elif not getattr(E, 'qualitative_only', False):
             gt = it['HR_UW']
             p = psnr(out_cpu, gt)
@@ -219,7 +245,7 @@ def evaluate(config, net=None, log=print):
         with open(score_path, 'w' if st['first_line'] else 'a') as fh:
             fh.write(line + '\n')
         st['first_line'] = False
-        if not getattr(E, 'quantitative_only', False):
+        if not fov and not getattr(E, 'quantitative_only', False):
             stem = it['frame_name'].split('.')[0]
             for fmt in ('png', 'jpg'):
                 base = os.path.join(out_root, fmt)
@@ -230,6 +256,9 @@ def evaluate(config, net=None, log=print):
         st['clip_t'] += dt
         st['clip_n'] += 1
         st['prev'] = it
+        if fov:
+            st['clip_fov'] = st['clip_fov'] + table
+            res['fov'].append(table)
         res['psnr'].append(p)
         res['ssim'].append(s)
         res['seconds'].append(dt)
@@ -251,27 +280,44 @@ def evaluate(config, net=None, log=print):
             emit(it, outs[b], lrs[b, c], dt, scored[b])
         del pending[:]
 
+    def clip_summary():
+        """The clip's MEAN line / block, named for the clip it summarises; resets the clip's sums."""
+        if st['clip_n']:
+            n = st['clip_n']
+            if fov:
+                _fov_clip_summary(config, score_path, st['prev'], st['clip_fov'] / n, st['clip_t'] / n, log)
+            else:
+                _clip_summary(config, score_path, st['prev'], st['clip_p'], st['clip_s'], st['clip_t'], n, log)
+        st['clip_p'] = st['clip_s'] = st['clip_t'] = st['clip_fov'] = 0.0
+        st['clip_n'] = 0
+
     try:
-        _evaluate_loop(net, ds, dev, E, G, st, emit, flush, config, score_path, log)
+        _evaluate_loop(net, ds, dev, E, G, st, emit, flush, clip_summary)
     finally:
         if G > 1 and not was_pipelined:
             torch.cuda.synchronize()
             net.Network.set_pipelined(False)
-    clip_p, clip_s, clip_t, clip_n, prev = st['clip_p'], st['clip_s'], st['clip_t'], st['clip_n'], st['prev']
-    if clip_n:
-        _clip_summary(config, score_path, prev, clip_p, clip_s, clip_t, clip_n, log)
+    clip_summary()
     n = max(res['frames'], 1)
-    total = '\n[TOTAL {}|{}] PSNR: {:.5f} SSIM: {:.5f} ({:.5f}sec)'.format(
-        ckpt_name, E.data, sum(res['psnr']) / n, sum(res['ssim']) / n, sum(res['seconds']) / n)
-    log(total)
-    with open(score_path, 'a') as fh:
-        fh.write(total + '\n')
+    if fov:
+        total = fov_block('\n[TOTAL {}|{}] \n'.format(ckpt_name, E.data), sum(res['fov']) / n if res['fov'] else np.zeros((6, 3, 2)),
+                          ') ({:.5f}sec)\n\n'.format(sum(res['seconds']) / n))
+        log(total)
+        with open(score_path, 'a') as fh:
+            fh.write(total)
+    else:
+        total = '\n[TOTAL {}|{}] PSNR: {:.5f} SSIM: {:.5f} ({:.5f}sec)'.format(
+            ckpt_name, E.data, sum(res['psnr']) / n, sum(res['ssim']) / n, sum(res['seconds']) / n)
+        log(total)
+        with open(score_path, 'a') as fh:
+            fh.write(total + '\n')
     res['score_file'], res['output_root'] = score_path, out_root
     return res
 
 
-def _evaluate_loop(net, ds, dev, E, G, st, emit, flush, config, score_path, log):
-    """The per-frame loop of evaluate() (eval_qual_quan.py:39-128)."""
+def _evaluate_loop(net, ds, dev, E, G, st, emit, flush, clip_summary):
+    """The per-frame loop of evaluate() (eval_qual_quan.py:39-128, eval_quan_FOV.py:55-232): emit scores and logs a frame,
+    clip_summary closes a clip."""
     with torch.no_grad():
         pending = []
         for i in range(len(ds)):
@@ -280,10 +326,7 @@ def _evaluate_loop(net, ds, dev, E, G, st, emit, flush, config, score_path, log)
                 continue
             if it['is_first']:
                 flush(pending)
-                if st['clip_n']:
-                    _clip_summary(config, score_path, st['prev'], st['clip_p'], st['clip_s'], st['clip_t'], st['clip_n'], log)
-                    st['clip_p'] = st['clip_s'] = st['clip_t'] = 0.0
-                    st['clip_n'] = 0
+                clip_summary()
                 net.Network.reset()
             use_ids = getattr(E, 'use_frame_ids', True) and 'frame_ids' in it
             if G > 1 and use_ids and not it['is_first']:
@@ -308,6 +351,32 @@ def _clip_summary(config, score_path, it, p, s, t, n, log):
         fh.write(line + '\n')
 
 
+def fov_block(head, table, tail):
+    """The six labelled rows of a FOV summary (eval_quan_FOV.py:93-111 / :245-264, its format strings) between `head` and `tail`;
+    table: [6 keys][fi, fo, fr][psnr, ssim]."""
+    from .metrics import FOV_KEYS as keys
+    out = head
+    for m, name in enumerate(('PSNR', 'SSIM')):
+        out += (')\n' if m else '') + '[%s-FOV_in  ] (' % name
+        for k, v in zip(keys, table[:, 0, m]):
+            out += '0-{:3.1f}%: {:.5f}, '.format(k * 100, v)
+        out += ')\n[%s-FOV_out ] (' % name
+        for k, v in zip(keys, table[:, 1, m]):
+            out += '{:3.1f}-100%: {:.5f}, '.format(k * 100, v)
+        out += ')\n[%s-FOV_ring] (' % name
+        for k, v in zip(keys, table[:, 2, m]):
+            out += '{:3.1f}-{:3.1f}%: {:.5f}, '.format(keys[-1] * 100, k * 100, v)
+    return out + tail
+
+
+def _fov_clip_summary(config, score_path, it, table, t, log):
+    block = fov_block('[MEAN EVAL {}|{}|{}][{}/{}] ({:.5f}sec) \n'.format(config.mode, config.EVAL.data, it['video_name'], it['video_idx'],
+                                                                         it['video_len'], t), table, ') \n\n')
+    log(block)
+    with open(score_path, 'a') as fh:
+        fh.write(block)
+
+
 # ------------------------------------------------------------------------------------------------ CLI
 def build_config(argv=None):
     """run.py:218-417 flag surface (evaluation subset)."""
@@ -321,7 +390,10 @@ def build_config(argv=None):
     ap.add_argument('-output_offset', '--output_offset', type=str, default='./result')
     ap.add_argument('-ckpt_abs_name', '--ckpt_abs_name', type=str, default=None)
     ap.add_argument('-cpu', '--cpu', action='store_true')
-    ap.add_argument('-eval_mode', '--eval_mode', type=str, default='qual_quan')
+    ap.add_argument('-eval_mode', '--eval_mode', type=str, default='qual_quan',
+                    help="'qual_quan' (whole-frame PSNR / SSIM and result images) | a name with 'FOV' in it, e.g. 'quan_FOV': PSNR / SSIM "
+                         "inside, outside and in rings around the overlapped field of view, no images (with --metrics device one "
+                         "refvsr_score_regions launch per network call)")
     ap.add_argument('-test_set', '--test_set', type=str, default='test')
     ap.add_argument('-qualitative_only', '--qualitative_only', action='store_true')
     ap.add_argument('-quantitative_only', '--quantitative_only', action='store_true')

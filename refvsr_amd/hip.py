@@ -18,6 +18,7 @@ ABI_VERSION = 15
 MAX_MAPS = 4
 INGEST_MAX_FRAMES = 16                      # REFVSR_INGEST_MAX_FRAMES: byte frames per refvsr_ingest_u8 launch
 SCORE_MAX_FRAMES = 16                       # REFVSR_SCORE_MAX_FRAMES: frame pairs per refvsr_score_frames launch
+SCORE_MAX_RECTS = 8                         # REFVSR_SCORE_MAX_RECTS: rectangles per refvsr_score_regions launch
 RESBLOCK24_BLOB_BYTES = 43264
 RESBLOCK24_F16W_BLOB_BYTES = 28928          # the fp16 weight format (ABI 15)
 RESBLOCK48_BLOB_BYTES = 172544
@@ -150,9 +151,13 @@ SIGNATURES = {
     # frame scores on the device (added symbols, ABI 15 unchanged)
     'refvsr_score_frames': [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P],
     'refvsr_score_max_frames': [],               # returns REFVSR_SCORE_MAX_FRAMES
+    # rectangle sums for the field-of-view evaluation (added symbols, ABI 15 unchanged)
+    'refvsr_score_regions': [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _Z, _P, _P],
+    'refvsr_score_max_rects': [],                # returns REFVSR_SCORE_MAX_RECTS
 }
 _SPECIAL = {'refvsr_abi_version': (C.c_int, []), 'refvsr_last_error': (C.c_char_p, []),
-            'refvsr_score_workspace_bytes': (C.c_size_t, [_I, _I, _I])}
+            'refvsr_score_workspace_bytes': (C.c_size_t, [_I, _I, _I]),
+            'refvsr_score_regions_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I])}
 EXPORTS = tuple(sorted(list(SIGNATURES) + list(_SPECIAL)))
 
 _lib = None
@@ -186,6 +191,9 @@ def lib():
         if h.refvsr_score_max_frames() != SCORE_MAX_FRAMES:
             raise RuntimeError('refvsr_amd: REFVSR_SCORE_MAX_FRAMES mismatch (library %d, binding %d)'
                                % (h.refvsr_score_max_frames(), SCORE_MAX_FRAMES))
+        if h.refvsr_score_max_rects() != SCORE_MAX_RECTS:
+            raise RuntimeError('refvsr_amd: REFVSR_SCORE_MAX_RECTS mismatch (library %d, binding %d)'
+                               % (h.refvsr_score_max_rects(), SCORE_MAX_RECTS))
         _lib = h
     return _lib
 

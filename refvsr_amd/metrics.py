@@ -1,6 +1,10 @@
 """Host side of the device scorer (refvsr_score_frames, csrc/score.hip): the PSNR of a device-computed mse, and a numpy float64 model of
 the kernel -- its tile decomposition, its direct 7-term window sums and its fixed reduction order -- that the CPU suite can run against
-evalrun.psnr / evalrun.ssim (trainers/trainer.py:252-254, evaluation/metrics.py:17-18)."""
+evalrun.psnr / evalrun.ssim (trainers/trainer.py:252-254, evaluation/metrics.py:17-18).
+
+The field-of-view evaluation (evaluation/eval_quan_FOV.py:155-192 on evaluation/metrics.py:18-30) lives here too: the seven rectangles
+its 16 masked scores are made of (fov_rects), the table those scores form from rectangle sums (fov_table), a numpy model of
+refvsr_score_regions (score_regions_model) and the whole-array float64 host path (fov_scores_host)."""
 import math
 
 import numpy as np
@@ -97,3 +101,142 @@ def score_frames_model(a, b, tile=TILE, win=7):
     mse = _strided_sum(part_m) / (3.0 * h * w)
     ssim = _strided_sum(part_s) / (3.0 * (h - 6) * (w - 6)) if win else 0.0
     return float(mse), float(ssim)
+
+
+# ------------------------------------------------------------------------------------------------ field-of-view evaluation
+FOV_KEYS = (1, 0.9, 0.8, 0.7, 0.6, 0.5)        # eval_quan_FOV.py:26
+MAX_RECTS = 8                                   # REFVSR_SCORE_MAX_RECTS
+
+
+def fov_crop_ratio(key):
+    """eval_quan_FOV.py:167, evaluated as the reference evaluates it (Python floats): 20, 10, 6, 5, 4 for 0.9 .. 0.5."""
+    return int(1 / ((1 - key) / 2))
+
+
+def fov_rects(h, w):
+    """The seven rectangles (y0, y1, x0, x1), half-open, that every mask of eval_quan_FOV.py:155-192 is one of or a difference of
+    two of: the whole frame, the valid crop of the plain SSIM, and R(key) = [h // cr : h - h // cr, w // cr : w - w // cr] for
+    key = 0.9 .. 0.5.  Below 20 rows or columns h // 20 == 0: R(0.9) is the whole frame and the reference divides by an empty mask."""
+    h, w = int(h), int(w)
+    if h < 20 or w < 20:
+        raise ValueError('fov_rects: the FOV masks need frames of at least 20 x 20 (got %d x %d)' % (h, w))
+    rects = [(0, h, 0, w), (3, h - 3, 3, w - 3)]
+    for key in FOV_KEYS[1:]:
+        cr = fov_crop_ratio(key)
+        rects.append((h // cr, h - h // cr, w // cr, w - w // cr))
+    return rects
+
+
+def _area3(r):
+    return 3.0 * (r[1] - r[0]) * (r[3] - r[2])
+
+
+def fov_table(sums, h, w):
+    """float64 [6 keys][fi, fo, fr][psnr, ssim] of one frame from sums [7][2] = {sum (a - b)^2, sum S} over fov_rects(h, w)
+    (refvsr_score_regions / score_regions_model / host_region_sums): fi = R(key), fo = frame - R(key), fr = R(key) - R(0.5); key 1:
+    fi = the plain psnr / ssim (whole-frame mse, S over the valid crop), fo = 0, fr = frame - R(0.5); key 0.5: fr = 0 -- exact 0.0
+    where the reference reports 0, inf PSNR where a region's error is zero."""
+    sums = np.asarray(sums, dtype=np.float64)
+    rects = fov_rects(h, w)
+    assert sums.shape == (len(rects), 2)
+    cnt = [_area3(r) for r in rects]
+    mean = lambda se, ss, n: (psnr_from_mse(se / n), ss / n)
+    full, inner = 0, len(rects) - 1
+    table = np.zeros((len(FOV_KEYS), 3, 2), dtype=np.float64)
+    for k in range(len(FOV_KEYS)):
+        r = k + 1                                               # R(key)'s rectangle (key 1: the valid crop)
+        if k == 0:
+            table[k, 0] = (psnr_from_mse(sums[full, 0] / cnt[full]), sums[r, 1] / cnt[r])
+            r = full
+        else:
+            table[k, 0] = mean(sums[r, 0], sums[r, 1], cnt[r])
+            table[k, 1] = mean(sums[full, 0] - sums[r, 0], sums[full, 1] - sums[r, 1], cnt[full] - cnt[r])
+        if r != inner:
+            table[k, 2] = mean(sums[r, 0] - sums[inner, 0], sums[r, 1] - sums[inner, 1], cnt[r] - cnt[inner])
+    return table
+
+
+def _as64(x):
+    if hasattr(x, 'detach'):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x, dtype=np.float32).astype(np.float64)
+
+
+def _ssim_map(ta, tb):
+    """S at the (rows - 6) x (cols - 6) centres of ta, tb: direct 7-term sums left to right, then top to bottom."""
+    t = [_seq7(_seq7(x, -1), -2) for x in (ta, tb, ta * ta, tb * tb, ta * tb)]
+    ua, ub = t[0] / 49.0, t[1] / 49.0
+    va, vb, vab = NORM * (t[2] / 49.0 - ua * ua), NORM * (t[3] / 49.0 - ub * ub), NORM * (t[4] / 49.0 - ua * ub)
+    return ((2.0 * ua * ub + C1) * (2.0 * vab + C2)) / ((ua * ua + ub * ub + C1) * (va + vb + C2))
+
+
+def _reflect(i, n):
+    """scipy.ndimage 'reflect' = numpy 'symmetric' (d c b a | a b c d | d c b a), then clamped (rg_reflect of csrc/score.hip)."""
+    i = np.where(i < 0, -i - 1, i)
+    i = np.where(i >= n, 2 * n - 1 - i, i)
+    return np.maximum(i, 0)
+
+
+def score_regions_model(a, b, rects, tile=TILE):
+    """sums [R][2] = {sum (a - b)^2, sum S} over rects (y0, y1, x0, x1) of one pair a, b [3,h,w] exactly as refvsr_score_regions
+    computes them: per (channel, tile of 32 x 64 pixel centres) workgroup the 38 x 70 input tile staged through the symmetric-reflect
+    index, S and the centre's (a - b)^2 per (column, 8-row group) thread added top to bottom to the rectangles that hold the centre, a
+    64-lane tree per wave, ((w0 + w1) + w2) + w3, and in the finishing kernel partial sum i in slice i mod 64, a slice in order, the
+    slices in order.  (A rectangle that misses a tile is skipped by the kernel; its partial sum is the 0.0 computed here.)"""
+    a, b = _as64(a), _as64(b)
+    assert a.shape == b.shape and a.ndim == 3 and a.shape[0] == 3
+    _, h, w = a.shape
+    th, tw = tile
+    rects = [tuple(int(v) for v in r) for r in rects]
+    assert h >= 7 and w >= 7 and 1 <= len(rects) <= MAX_RECTS and th % 4 == 0 and tw * 4 == THREADS
+    for y0, y1, x0, x1 in rects:
+        assert 0 <= y0 < y1 <= h and 0 <= x0 < x1 <= w
+    rows = th // 4
+    nty, ntx = -(-h // th), -(-w // tw)
+    part = []                                                   # [3 nty ntx][R][2]
+    for c in range(3):
+        for ty in range(nty):
+            for tx in range(ntx):
+                cy, cx = ty * th, tx * tw
+                iy, ix = _reflect(cy - 3 + np.arange(th + 6), h), _reflect(cx - 3 + np.arange(tw + 6), w)
+                ta, tb = a[c][iy][:, ix], b[c][iy][:, ix]
+                s = _ssim_map(ta, tb)                           # [th, tw]
+                d = ta[3:-3, 3:-3] - tb[3:-3, 3:-3]
+                d2 = d * d
+                oy, ox = (cy + np.arange(th))[:, None], (cx + np.arange(tw))[None, :]
+                out = np.zeros((len(rects), 2))
+                for r, (y0, y1, x0, x1) in enumerate(rects):
+                    inside = (oy >= y0) & (oy < y1) & (ox >= x0) & (ox < x1)
+                    for k, v in enumerate((d2, s)):
+                        v = np.where(inside, v, 0.0).reshape(4, rows, tw)       # [wave, row of the wave, lane]
+                        acc = np.zeros((4, tw))
+                        for o in range(rows):
+                            acc = acc + v[:, o]
+                        wv = [_tree(acc[g]) for g in range(4)]
+                        out[r, k] = ((wv[0] + wv[1]) + wv[2]) + wv[3]
+                part.append(out)
+    part = np.array(part)
+    sl = np.zeros((64,) + part.shape[1:])
+    for i in range(part.shape[0]):
+        sl[i % 64] = sl[i % 64] + part[i]
+    total = sl[0]
+    for g in range(1, 64):
+        total = total + sl[g]
+    return total
+
+
+def host_region_sums(a, b, rects):
+    """sums [R][2] over rects from whole-array float64 numpy: (a - b)^2 and the full SSIM map (symmetric padding by 3, direct 7-term
+    sums), each rectangle a plain slice sum."""
+    a, b = _as64(a), _as64(b)
+    assert a.shape == b.shape and a.ndim == 3 and a.shape[0] == 3 and a.shape[1] >= 7 and a.shape[2] >= 7
+    d2 = (a - b) ** 2
+    pad = lambda x: np.pad(x, ((0, 0), (3, 3), (3, 3)), mode='symmetric')
+    s = _ssim_map(pad(a), pad(b))
+    return np.array([[d2[:, y0:y1, x0:x1].sum(), s[:, y0:y1, x0:x1].sum()] for y0, y1, x0, x1 in rects], dtype=np.float64)
+
+
+def fov_scores_host(a, b):
+    """The FOV table [6][3][2] of one pair a, b [3,h,w] on the host in float64 (`--eval_mode quan_FOV --metrics host`)."""
+    h, w = a.shape[-2:]
+    return fov_table(host_region_sums(a, b, fov_rects(h, w)), h, w)

@@ -712,43 +712,82 @@ def ingest_frames(x):
 _SCORE_WS = {}        # (device, stream handle, h, w) -> workspace of one full refvsr_score_frames launch
 
 
+def _score_inputs(outs, gts, what):
+    """The frame pairs of a scorer call, checked: (results, ground truths, h, w, result format, ground-truth format, layout)."""
+    outs, gts = list(outs), list(gts)
+    assert outs and len(outs) == len(gts), '%s: as many results as ground truths' % what
+    a0, g0 = outs[0], gts[0]
+    _, h, w = a0.shape
+    fmts = {torch.float32: hip.RESULT_F32, torch.float16: hip.RESULT_F16, torch.uint8: hip.RESULT_U8}
+    assert a0.dtype in fmts and g0.dtype in (torch.float32, torch.uint8), '%s: float32 | float16 | uint8 results, float32 | uint8 ground truth' % what
+    lay = u8_layout(g0) if g0.dtype == torch.uint8 else hip.INGEST_PLANAR
+    for a, g in zip(outs, gts):
+        if a.shape != (3, h, w) or g.shape != (3, h, w):
+            raise RuntimeError('%s: result %s and ground truth %s must both be [3, %d, %d]' % (what, tuple(a.shape), tuple(g.shape), h, w))
+        assert a.is_cuda and g.is_cuda and a.dtype == a0.dtype and g.dtype == g0.dtype and a.is_contiguous()
+        assert (u8_layout(g) if g.dtype == torch.uint8 else (hip.INGEST_PLANAR if g.is_contiguous() else None)) == lay and lay is not None, \
+            '%s: ground-truth frames must be dense and of one layout' % what
+    return outs, gts, h, w, fmts[a0.dtype], fmts[g0.dtype], lay
+
+
+def _score_workspace(cache, dev, st, h, w, nbytes, what):
+    """The cached float64 workspace of one full launch per (device, stream, h, w)."""
+    key = (dev, st.value, h, w)
+    ws = cache.get(key)
+    if ws is None:
+        if len(cache) > 16:
+            cache.clear()
+        if nbytes == 0:
+            raise RuntimeError('%s: frames must be at least 7 x 7 (got %d x %d)' % (what, h, w))
+        ws = cache[key] = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    return ws
+
+
 def score_frames(outs, gts, win=7):
     """{mse, ssim} of B (result, ground truth) pairs of one 3 x h x w geometry, computed on the device (refvsr_score_frames): a
     torch.float64 [B, 2] tensor on the current stream, no synchronisation.  outs: [B,3,h,w] tensor or B tensors [3,h,w], contiguous
     float32 / float16 / uint8 (what the output head stores; a byte means byte / 255); gts: the same shapes, contiguous float32, or
     uint8 planar or channels-last (u8_layout).  win = 7: both numbers; win = 0: the mse alone (ssim field 0).  One launch per
     REFVSR_SCORE_MAX_FRAMES pairs.  PSNR = metrics.psnr_from_mse(mse) on the host."""
-    outs, gts = list(outs), list(gts)
-    assert outs and len(outs) == len(gts), 'score_frames: as many results as ground truths'
-    a0, g0 = outs[0], gts[0]
-    _, h, w = a0.shape
-    fmts = {torch.float32: hip.RESULT_F32, torch.float16: hip.RESULT_F16, torch.uint8: hip.RESULT_U8}
-    assert a0.dtype in fmts and g0.dtype in (torch.float32, torch.uint8), 'score_frames: float32 | float16 | uint8 results, float32 | uint8 ground truth'
-    lay = u8_layout(g0) if g0.dtype == torch.uint8 else hip.INGEST_PLANAR
-    for a, g in zip(outs, gts):
-        if a.shape != (3, h, w) or g.shape != (3, h, w):
-            raise RuntimeError('score_frames: result %s and ground truth %s must both be [3, %d, %d]' % (tuple(a.shape), tuple(g.shape), h, w))
-        assert a.is_cuda and g.is_cuda and a.dtype == a0.dtype and g.dtype == g0.dtype and a.is_contiguous()
-        assert (u8_layout(g) if g.dtype == torch.uint8 else (hip.INGEST_PLANAR if g.is_contiguous() else None)) == lay and lay is not None, \
-            'score_frames: ground-truth frames must be dense and of one layout'
+    outs, gts, h, w, afmt, gfmt, lay = _score_inputs(outs, gts, 'score_frames')
     st = _stream()
-    key = (a0.device, st.value, h, w)
-    ws = _SCORE_WS.get(key)
-    if ws is None:
-        if len(_SCORE_WS) > 16:
-            _SCORE_WS.clear()
-        nbytes = hip.lib().refvsr_score_workspace_bytes(hip.SCORE_MAX_FRAMES, h, w)
-        if nbytes == 0:
-            raise RuntimeError('score_frames: frames must be at least 7 x 7 (got %d x %d)' % (h, w))
-        ws = _SCORE_WS[key] = torch.empty(nbytes // 8, dtype=torch.float64, device=a0.device)
-    scores = torch.empty((len(outs), 2), dtype=torch.float64, device=a0.device)
+    dev = outs[0].device
+    ws = _score_workspace(_SCORE_WS, dev, st, h, w, hip.lib().refvsr_score_workspace_bytes(hip.SCORE_MAX_FRAMES, h, w), 'score_frames')
+    scores = torch.empty((len(outs), 2), dtype=torch.float64, device=dev)
     for s0 in range(0, len(outs), hip.SCORE_MAX_FRAMES):
         n = min(hip.SCORE_MAX_FRAMES, len(outs) - s0)
         pa = (C.c_void_p * n)(*[a.data_ptr() for a in outs[s0:s0 + n]])
         pg = (C.c_void_p * n)(*[g.data_ptr() for g in gts[s0:s0 + n]])
-        hip.check(hip.lib().refvsr_score_frames(pa, fmts[a0.dtype], pg, fmts[g0.dtype], lay, n, h, w, int(win), _ptr(ws), ws.numel() * 8,
+        hip.check(hip.lib().refvsr_score_frames(pa, afmt, pg, gfmt, lay, n, h, w, int(win), _ptr(ws), ws.numel() * 8,
                                                 C.c_void_p(scores.data_ptr() + 16 * s0), st), 'score_frames')
     return scores
+
+
+_REGION_WS = {}       # (device, stream handle, h, w) -> workspace of one full refvsr_score_regions launch
+
+
+def score_regions(outs, gts, rects):
+    """{sum (a - b)^2, sum S} of B (result, ground truth) pairs of one 3 x h x w geometry over R <= REFVSR_SCORE_MAX_RECTS rectangles
+    (y0, y1, x0, x1), half-open, computed on the device (refvsr_score_regions; S = the full SSIM map with the symmetric border): a
+    torch.float64 [B, R, 2] tensor of raw sums on the current stream, no synchronisation.  Inputs as score_frames takes them.  One
+    launch per REFVSR_SCORE_MAX_FRAMES pairs.  The FOV table: metrics.fov_table(sums of metrics.fov_rects(h, w), h, w) on the host."""
+    outs, gts, h, w, afmt, gfmt, lay = _score_inputs(outs, gts, 'score_regions')
+    rects = [tuple(int(v) for v in r) for r in rects]
+    assert all(len(r) == 4 for r in rects), 'score_regions: rectangles are (y0, y1, x0, x1)'
+    nr = len(rects)
+    crects = (C.c_int * max(4 * nr, 1))(*[v for r in rects for v in r])
+    st = _stream()
+    dev = outs[0].device
+    ws = _score_workspace(_REGION_WS, dev, st, h, w, hip.lib().refvsr_score_regions_workspace_bytes(hip.SCORE_MAX_FRAMES, h, w, hip.SCORE_MAX_RECTS),
+                          'score_regions')
+    sums = torch.empty((len(outs), nr, 2), dtype=torch.float64, device=dev)
+    for s0 in range(0, len(outs), hip.SCORE_MAX_FRAMES):
+        n = min(hip.SCORE_MAX_FRAMES, len(outs) - s0)
+        pa = (C.c_void_p * n)(*[a.data_ptr() for a in outs[s0:s0 + n]])
+        pg = (C.c_void_p * n)(*[g.data_ptr() for g in gts[s0:s0 + n]])
+        hip.check(hip.lib().refvsr_score_regions(pa, afmt, pg, gfmt, lay, n, h, w, crects, nr, _ptr(ws), ws.numel() * 8,
+                                                 C.c_void_p(sums.data_ptr() + 16 * nr * s0), st), 'score_regions')
+    return sums
 
 
 def warp_nhwc16(x, flow):

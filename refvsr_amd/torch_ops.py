@@ -27,6 +27,7 @@ Op set (argument conventions of ops.py: `planar` = float32 [C,H,W], `nhwc16` = f
   resize(x, oh, ow, mode, sy, sx, clamp01) ; pack_nhwc16(x, cs) ; unpack_nhwc16(x, c)
   ingest_u8(x)                                           uint8 [..., 3, h, w] (planar or channels-last) -> float32 x / 255, exact
   score_frames(outs, gts, win)                           [B,3,h,w] results / ground truths -> float64 [B,2] = {mse, ssim} on the device
+  score_regions(outs, gts, rects)                        the same pairs, rects = flat [4 R] ints -> float64 [B,R,2] = {sum (a-b)^2, sum S}
 """
 from typing import List, Optional, Tuple
 
@@ -283,8 +284,19 @@ def register():
         torch._check(outs.dim() == 4 and outs.shape == gts.shape and outs.shape[1] == 3, lambda: 'score_frames takes [B,3,h,w] results and ground truths')
         return torch.empty((outs.shape[0], 2), dtype=torch.float64, device=outs.device)
 
+    @op('score_regions')
+    def score_regions(outs: torch.Tensor, gts: torch.Tensor, rects: List[int]) -> torch.Tensor:
+        return ops.score_regions(outs, gts, [rects[i:i + 4] for i in range(0, len(rects), 4)])
+
+    @score_regions.register_fake
+    def _(outs, gts, rects):
+        torch._check(outs.dim() == 4 and outs.shape == gts.shape and outs.shape[1] == 3, lambda: 'score_regions takes [B,3,h,w] results and ground truths')
+        torch._check(len(rects) % 4 == 0 and 1 <= len(rects) // 4 <= hip.SCORE_MAX_RECTS,
+                     lambda: 'score_regions takes 1..%d rectangles as a flat list of y0, y1, x0, x1' % hip.SCORE_MAX_RECTS)
+        return torch.empty((outs.shape[0], len(rects) // 4, 2), dtype=torch.float64, device=outs.device)
+
 
 OP_NAMES = ('conv_mfma', 'conv24', 'resblock', 'resblock24_chain', 'resblock24_chain_batch', 'conv24_batch', 'warp_batch', 'match_argmax', 'warp', 'warp_planar', 'spynet_level_input', 'block_gather',
-            'block_gather_rgb', 'aligned_sample', 'resize', 'pack_nhwc16', 'unpack_nhwc16', 'ingest_u8', 'score_frames')
+            'block_gather_rgb', 'aligned_sample', 'resize', 'pack_nhwc16', 'unpack_nhwc16', 'ingest_u8', 'score_frames', 'score_regions')
 
 register()
