@@ -365,6 +365,16 @@ int refvsr_resize(const float* src, int c, int h, int w, void* dst, int oh, int 
                   const float* chan_mul, int clamp01, int out_nhwc16, int out_c, void* stream);
 int refvsr_avgpool2(const float* src, int c, int h, int w, float* dst, void* stream);
 int refvsr_maxpool2(const float* src, int c, int h, int w, float* dst, void* stream);
+/* Five refvsr_avgpool2 calls in one launch (added symbol, ABI 15 unchanged): src planar fp32 [c][h][w] with h, w multiples of 32;
+ * dst: host array of five device pointers, dst[k] = planar [c][h >> (k + 1)][w >> (k + 1)], each level pooled from the stored
+ * values of the one before.  The same bits as the five calls. */
+int refvsr_avgpool_pyramid(const float* src, int c, int h, int w, float* const* dst, void* stream);
+/* Everything the per-frame preparation derives from the two planar fp32 frames lr [3][h][w] and ref [3][hr][wr] alone, in one
+ * launch (added symbol, ABI 15 unchanged): lr8 [h][w][8], ref8 [hr][wr][8] = refvsr_pack_nhwc16(., cs = 8); lr_n [h][w][4] =
+ * refvsr_pack_nhwc32(MeanShift(lr), cs = 4); ref_n [hr/2][wr/2][4] = refvsr_pack_nhwc32(refvsr_avgpool2(MeanShift(ref)), cs = 4),
+ * MeanShift = refvsr_conv_direct_f32 with the 1x1 filter wgt [3][3] / bias [3] (device, fp32).  The same bits as those launches. */
+int refvsr_frame_prep(const float* lr, int h, int w, const float* ref, int hr, int wr, const float* wgt, const float* bias,
+                      void* lr8, void* ref8, float* lr_n, float* ref_n, void* stream);
 /* flags[i] &= (a[i][0..n_bytes) == b[i][0..n_bytes)) for i < n_pairs (<= 32) in one launch; the caller presets
  * flags to 1.  a, b: HOST arrays of device pointers (16-byte aligned buffers, n_bytes % 16 == 0).
  * Keys the per-frame cache (frames of consecutive sliding windows are recognised by content). */
@@ -497,6 +507,15 @@ int refvsr_spynet_level_input_batch(const float* const* ref, const float* const*
  * the low halves of the fp16 hi + lo split of the same normalised patches, rows_lo [h*w][KP] fp16 =
  * fp16((p - rows) * 2^11) (second operand of refvsr_match_exact; allocate it padded like rows). */
 int refvsr_match_patches(const float* feat, int h, int w, void* rows, float* inv_norm, void* rows_lo, void* stream);
+/* Tuning knob (added symbol, ABI 15 unchanged): which kernel refvsr_match_patches launches.  0: one pixel per thread with global
+ * gathers; 1: a 256-pixel strip staged in LDS (default).  Results do not depend on it (bit-identical). */
+int refvsr_set_match_patches_kernel(int mode);
+/* rows_lo of the columns in the flagged list of refvsr_match_refine only (added symbol, ABI 15 unchanged): the values
+ * refvsr_match_patches writes with rows_lo != NULL, at the same offsets of the [h*w][KP] buffer; every other row is left
+ * untouched.  refvsr_match_exact reads lr_rows_lo at the flagged columns alone, so this stands in for the full LR array.
+ * inv_norm: as written by refvsr_match_patches for feat.  The count is read on the device. */
+int refvsr_match_lo_rows(const float* feat, int h, int w, const float* inv_norm, const int32_t* flagged, void* rows_lo,
+                         void* stream);
 /* Fused cosine GEMM + column top-2 (never materialises the [n_ref x n_lr] matrix).
  * ref_rows: [n_ref_pad][KP], lr_rows: [n_lr_pad][KP] (pads zero).  row_splits >= 1 partitions the
  * reference rows over blockIdx.y.  cand_idx / cand_val: [n_lr][2*row_splits] (first-max-wins order). */

@@ -85,11 +85,151 @@ __global__ __launch_bounds__(128) void match_patches_kernel(const float* __restr
     }
 }
 
+// The same rows through an LDS tile.  The kernel above fetches every feature value ~18 times from global memory with scalar
+// gathers (9 in phase 1, 9 in phase 2, each with its own reflect arithmetic; 61 us for the 270 x 480 LR map = 1.4 TB/s of
+// stores).  Here a workgroup of 256 threads owns a strip of MP_S = 256 consecutive pixels and stages, per channel c and tap row
+// ky, the LINEAR pixel run [p0 - 1, p0 + MP_S] of row reflect(y + ky - 1): s_f[c * 3 + ky][j] = feat[c][reflect(y_q + ky - 1)][x_q]
+// with q = p0 - 1 + j.  The horizontal neighbours of strip pixel pl are then s_f[.][pl + 1 +- 1]; at the map's left / right
+// edge the reflected neighbour is the pixel on the OTHER side (x = -1 -> 1, x = w -> w - 2), so the two halo entries are only
+// ever read for a neighbour in the pixel's own row.  One division per staged pixel, none per element; every feature value is
+// fetched 3 times (once per tap row) with coalesced loads.  Both phases use the expressions of the kernel above in its
+// order, so rows, inv_norm and rows_lo are the same bits (tests/test_gpu_match_prep.py).
+#define MP_S 256
+#define MP_LD (MP_S + 2)
+__global__ __launch_bounds__(256) void match_patches_lds_kernel(const float* __restrict__ feat, int h, int w,
+                                                                f16* __restrict__ rows, float* __restrict__ inv_norm,
+                                                                f16* __restrict__ rows_lo) {
+    __shared__ float s_f[48 * MP_LD];
+    __shared__ float s_inv[MP_S];
+    __shared__ int s_edge[MP_S];                       // bit 0: x == 0, bit 1: x == w - 1
+    const int tid = threadIdx.x, p0 = blockIdx.x * MP_S, n = h * w;
+    const size_t plane = (size_t)h * w;
+    for (int j = tid; j < MP_LD; j += 256) {
+        const int q = min(max(p0 - 1 + j, 0), n - 1);
+        const int y = q / w, x = q - y * w;
+        int ro[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ro[k] = rv_reflect(y + k - 1, h) * w + x;
+#pragma unroll 4
+        for (int c = 0; c < 16; ++c) {
+            const float* f = feat + c * plane;
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky) s_f[(c * 3 + ky) * MP_LD + j] = f[ro[ky]];
+        }
+    }
+    __syncthreads();
+    {   // phase 1: one pixel per thread, 1 / |patch|
+        const int p = min(p0 + tid, n - 1);
+        const int x = p % w;
+        const int edge = (x == 0 ? 1 : 0) | (x == w - 1 ? 2 : 0);
+        const float* sp = s_f + (p - p0) + 1;
+        const int d0 = (edge & 1) ? 1 : -1, d2 = (edge & 2) ? -1 : 1;
+        float ss = 0.0f;
+#pragma unroll 4
+        for (int r = 0; r < 48; ++r) {                  // r = c * 3 + ky: c outer, ky, kx inner
+            const float v0 = sp[r * MP_LD + d0], v1 = sp[r * MP_LD], v2 = sp[r * MP_LD + d2];
+            ss = fmaf(v0, v0, ss);
+            ss = fmaf(v1, v1, ss);
+            ss = fmaf(v2, v2, ss);
+        }
+        const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+        s_inv[tid] = inv;
+        s_edge[tid] = edge;
+        if (p0 + tid < n) inv_norm[p0 + tid] = inv;
+    }
+    __syncthreads();
+    // phase 2: the strip's rows = MP_S x 19 sixteen-byte slots, consecutive threads -> consecutive slots; element e = 8 g + k of a
+    // row is tap kx = e % 3 of staged row r = e / 3 (= c * 3 + ky); slot 18 is the zero pad
+    const int n_slots = min(MP_S, n - p0) * 19;
+    for (int i = tid; i < n_slots; i += 256) {
+        const int pl = i / 19, g = i - pl * 19;
+        const float inv = s_inv[pl];
+        const int edge = s_edge[pl];
+        int r = (g * 8) / 3, kx = g * 8 - r * 3;
+        const float* sp = s_f + r * MP_LD + pl + 1;
+        f16x8 o, lo;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            float v = 0.0f;
+            if (g < 18) {
+                const int d = kx == 0 ? ((edge & 1) ? 1 : -1) : kx == 1 ? 0 : ((edge & 2) ? -1 : 1);
+                v = sp[d];
+            }
+            if (++kx == 3) { kx = 0; sp += MP_LD; }
+            float vn = v * inv;
+            asm volatile("" : "+v"(vn));               // (see match_patches_kernel)
+            o[k] = (f16)vn;
+            lo[k] = (f16)((vn - (float)o[k]) * LO_SCALE);
+        }
+        const size_t off = (size_t)p0 * KP + (size_t)i * 8;
+        *reinterpret_cast<f16x8*>(rows + off) = o;
+        if (rows_lo) *reinterpret_cast<f16x8*>(rows_lo + off) = lo;
+    }
+}
+
+static int g_match_patches_kernel = 1;       // A/B knob (refvsr_set_match_patches_kernel): 0 = global gathers, 1 = LDS tile
+extern "C" int refvsr_set_match_patches_kernel(int mode) {
+    if (mode < 0 || mode > 1) return 1;
+    g_match_patches_kernel = mode;
+    return 0;
+}
+
 extern "C" int refvsr_match_patches(const float* feat, int h, int w, void* rows, float* inv_norm, void* rows_lo,
                                     void* stream) {
     RV_CHECK(feat && rows && inv_norm && h >= 2 && w >= 2, "match_patches: bad args");
-    hipLaunchKernelGGL(match_patches_kernel, dim3(rv_cdiv(h * w, 128)), dim3(128), 0, (hipStream_t)stream,
-                       feat, h, w, (f16*)rows, inv_norm, (f16*)rows_lo);
+    RV_CHECK((long long)h * w <= (1ll << 26), "match_patches: map too large");
+    if (g_match_patches_kernel == 1)
+        hipLaunchKernelGGL(match_patches_lds_kernel, dim3(rv_cdiv(h * w, MP_S)), dim3(256), 0, (hipStream_t)stream,
+                           feat, h, w, (f16*)rows, inv_norm, (f16*)rows_lo);
+    else
+        hipLaunchKernelGGL(match_patches_kernel, dim3(rv_cdiv(h * w, 128)), dim3(128), 0, (hipStream_t)stream,
+                           feat, h, w, (f16*)rows, inv_norm, (f16*)rows_lo);
+    RV_LAUNCH_CHECK();
+    return 0;
+}
+
+// The low halves of the FLAGGED columns' rows only: refvsr_match_exact reads lr_rows_lo at the columns of the flagged list and
+// nowhere else (B operand: flagged[1 + min(fi, count - 1)]), which is a per cent or so of the map (1 673 of 129 600 columns on
+// the benchmark clip) -- writing all of them was a 39 MB pass.  One thread per sixteen-byte slot of a flagged row, at the
+// row's usual offset of the [h*w][KP] buffer; phase 2 of match_patches_kernel with its expressions (the hi half is re-derived
+// from the same v * inv, inv read back from inv_norm).  The count is read on the device; the grid is sized on the host.
+__global__ __launch_bounds__(256) void match_lo_rows_kernel(const float* __restrict__ feat, int h, int w,
+                                                            const float* __restrict__ inv_norm,
+                                                            const int32_t* __restrict__ flagged, f16* __restrict__ rows_lo) {
+    const int total = flagged[0] * 19;
+    const size_t plane = (size_t)h * w;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+        const int f = i / 19, g = i - f * 19;
+        const int p = flagged[1 + f];
+        const int y = p / w, x = p - y * w;
+        const float inv = inv_norm[p];
+        f16x8 lo;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int e = g * 8 + k;
+            float v = 0.0f;
+            if (e < 144) {
+                const int c = e / 9, t = e - c * 9;
+                const int ky = t / 3, kx = t - ky * 3;
+                v = feat[c * plane + (size_t)rv_reflect(y + ky - 1, h) * w + rv_reflect(x + kx - 1, w)];
+            }
+            float vn = v * inv;
+            asm volatile("" : "+v"(vn));               // (see match_patches_kernel)
+            const f16 hi = (f16)vn;
+            lo[k] = (f16)((vn - (float)hi) * LO_SCALE);
+        }
+        *reinterpret_cast<f16x8*>(rows_lo + (size_t)p * KP + g * 8) = lo;
+    }
+}
+
+extern "C" int refvsr_match_lo_rows(const float* feat, int h, int w, const float* inv_norm, const int32_t* flagged,
+                                    void* rows_lo, void* stream) {
+    RV_CHECK(feat && inv_norm && flagged && rows_lo && h >= 2 && w >= 2, "match_lo_rows: bad args");
+    RV_CHECK((long long)h * w <= (1ll << 26), "match_lo_rows: map too large");
+    const int slots = rv_cdiv(h * w * 19, 256);
+    const int grid = slots < 1024 ? slots : 1024;
+    hipLaunchKernelGGL(match_lo_rows_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, feat, h, w, inv_norm, flagged,
+                       (f16*)rows_lo);
     RV_LAUNCH_CHECK();
     return 0;
 }

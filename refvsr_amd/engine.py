@@ -253,6 +253,10 @@ class Engine(object):
         # the 1x1 map that ends the matching's feature extractor on its own HBM-bound kernel (refvsr_conv1x1_f32) instead of the
         # generic conv's fp32 mode (118 us at 270 x 480 for 33 MB of reads); A/B knob REFVSR_NO_MAP1X1=1
         self.map1x1 = not env_flag('REFVSR_NO_MAP1X1')
+        # A/B knob REFVSR_LEGACY_PREP=1: the per-frame preparation's launch list before the one-launch pyramid / frame preparation, the
+        # LDS-tile patch-row kernel and the flagged-only LR lo rows (bit-identical results, profiles/match_prep_ab.txt)
+        self.legacy_prep = env_flag('REFVSR_LEGACY_PREP')
+        self.last_flagged = None                            # flagged list of the last feature_match (int32 [1 + n], [0] = count; tests)
         self.spynet_batch = not env_flag('REFVSR_NO_SPYNET_BATCH')   # A/B knob: one SPyNet pass per flow, as in round 3
         self.overlap = bool(getattr(config, 'overlap_streams', True)) and not env_flag('REFVSR_NO_OVERLAP')
         self._side = None
@@ -626,8 +630,11 @@ class Engine(object):
             w_up = w if w % 32 == 0 else 32 * (w // 32 + 1)
             h_up = h if h % 32 == 0 else 32 * (h // 32 + 1)
             lv = [ops.resize(fr.lr, (h_up, w_up), ops.RS_BILINEAR, mean=VGG_MEAN, std=VGG_STD)]
-            for _ in range(5):
-                lv.append(ops.avgpool2(lv[-1]))
+            if self.legacy_prep:
+                for _ in range(5):
+                    lv.append(ops.avgpool2(lv[-1]))
+            else:
+                lv += ops.avgpool_pyramid(lv[0])
             fr.pyr = lv[::-1]
         return fr.pyr
 
@@ -718,15 +725,21 @@ class Engine(object):
         for i, (a, b) in enumerate(todo):
             self.flow_cache[(a.uid, b.uid)] = (out[i], ev)
 
-    def feature_match(self, fr):
-        """FeatureMatching.forward (RefVSR_/attention.py:58-100), fused GEMM+argmax."""
+    def frame_prep(self, fr):
+        """(lr8, ref8, packed MeanShift(lr), packed avg_pool2(MeanShift(ref))) of a frame in one launch; None where the matching
+        resizes the normalised frames first (HD) or the legacy launch list is asked for."""
+        if self.hd or self.legacy_prep:
+            return None
+        return ops.frame_prep(fr.lr, fr.ref, *self.W.raw['feature_match.sub_mean'])
+
+    def feature_match(self, fr, prep=None):
+        """FeatureMatching.forward (RefVSR_/attention.py:58-100), fused GEMM+argmax.  prep: self.frame_prep(fr) if the caller has it."""
         R = self.W.raw
         h, w = fr.lr.shape[1:]
 
         fe = 'feature_match.feature_extract.'
 
-        def extract(x):       # VGG19 head + 1x1 map in exact fp32 on v_mfma_f32_16x16x4_f32 (attention.py:31-42)
-            x = ops.pack_nhwc32(x, 4)
+        def extract(x):       # VGG19 head + 1x1 map in exact fp32 on v_mfma_f32_16x16x4_f32 (attention.py:31-42); x: packed fp32 [h,w,4]
             x = ops.conv(self.cw(fe + '0'), x, act=0.0)
             if not self.vgg7:
                 x = ops.conv(self.cw(fe + '2'), x, act=0.0)
@@ -739,16 +752,26 @@ class Engine(object):
             if self.map1x1:
                 return ops.conv1x1_f32(x, *R[fe + 'map128.0'], act=0.2)
             return ops.conv(self.cw(fe + 'map128.0'), x, act=0.2, planar_out=True)
-        lr_n = ops.conv_direct(fr.lr, *R['feature_match.sub_mean'])
-        ref_n = ops.conv_direct(fr.ref, *R['feature_match.sub_mean'])
-        if self.hd:                                                                # attention.py:65-67
-            f = 1.0 / (self.cfg.scale // 2)
-            oh, ow = int(h * f), int(w * f)
-            lr_n = ops.resize(lr_n, (oh, ow), ops.RS_NEAREST, (1.0 / f, 1.0 / f))
-            ref_n = ops.resize(ref_n, (oh, ow), ops.RS_NEAREST, (1.0 / f, 1.0 / f))
+        if prep is None:
+            prep = self.frame_prep(fr)
+        if prep is not None:
+            lr_n, ref_n = prep[2], prep[3]
+        else:
+            lr_n = ops.conv_direct(fr.lr, *R['feature_match.sub_mean'])
+            ref_n = ops.conv_direct(fr.ref, *R['feature_match.sub_mean'])
+            if self.hd:                                                            # attention.py:65-67
+                f = 1.0 / (self.cfg.scale // 2)
+                oh, ow = int(h * f), int(w * f)
+                lr_n = ops.resize(lr_n, (oh, ow), ops.RS_NEAREST, (1.0 / f, 1.0 / f))
+                ref_n = ops.resize(ref_n, (oh, ow), ops.RS_NEAREST, (1.0 / f, 1.0 / f))
+            lr_n, ref_n = ops.pack_nhwc32(lr_n, 4), ops.pack_nhwc32(ops.avgpool2(ref_n), 4)
         lr_f = extract(lr_n)
-        ref_f = extract(ops.avgpool2(ref_n))
-        lr_rows, inv_lr, lr_lo = ops.match_patches(lr_f, ops.hip.MATCH_COLBLOCK, want_lo=True)
+        ref_f = extract(ref_n)
+        ops.set_match_patches_kernel(0 if self.legacy_prep else 1)
+        if self.legacy_prep:
+            lr_rows, inv_lr, lr_lo = ops.match_patches(lr_f, ops.hip.MATCH_COLBLOCK, want_lo=True)
+        else:       # the search reads the LR lo rows of the flagged columns only: match_refine writes those after the flagging
+            (lr_rows, inv_lr), lr_lo = ops.match_patches(lr_f, ops.hip.MATCH_COLBLOCK), None
         ref_rows, inv_ref, ref_lo = ops.match_patches(ref_f, ops.hip.MATCH_ROWCHUNK, want_lo=True)
         n_lr = lr_f.shape[1] * lr_f.shape[2]
         n_ref = ref_f.shape[1] * ref_f.shape[2]
@@ -760,8 +783,8 @@ class Engine(object):
             e1.record()
             self.kernel_events.append((e0, e1))
         # exact fp32 re-rank of the top-2 + exhaustive fp32-grade (split-fp16) search of the columns the fp16 GEMM cannot decide
-        conf, idx, _ = ops.match_refine(lr_f, ref_f, inv_lr, inv_ref, cand, cand_val, self.match_margin, (lr_rows, lr_lo),
-                                        (ref_rows, ref_lo))
+        conf, idx, self.last_flagged = ops.match_refine(lr_f, ref_f, inv_lr, inv_ref, cand, cand_val, self.match_margin, (lr_rows, lr_lo),
+                                                        (ref_rows, ref_lo))
         conf = conf.view(1, lr_f.shape[1], lr_f.shape[2])
         grid = (lr_f.shape[1], lr_f.shape[2])
         if grid[0] != h:                                                           # attention.py:96-98 (HD)
@@ -782,9 +805,10 @@ class Engine(object):
         affine = ops.conv(self.cw(prefix + '.p_conv.4'), a, planar_out=True, add_const=1.0, clamp=(-3.0, 3.0))
         return ops.aligned_sample(feats, affine, ks)
 
-    def _ref_encoders(self, fr):
+    def _ref_encoders(self, fr, ref8=None):
         """ref_feat = res1(ref_encoder1(ref)), ref_feat_down = res2(ref_encoder2(ref_feat))  (RefVSR.py:233-234)."""
-        ref8 = ops.pack_nhwc16(fr.ref, 8)
+        if ref8 is None:
+            ref8 = ops.pack_nhwc16(fr.ref, 8)
         x = ops.conv(self.cw('ref_encoder1.0.0'), ref8, act=0.2)
         x = ops.conv(self.cw('ref_encoder1.1.0'), x, act=0.2)
         ref_feat = self.res_list(x, 'res1', 4)
@@ -802,10 +826,11 @@ class Engine(object):
             # received (import_context); preparing one here would silently redo another rank's work
             raise RuntimeError('a window needs a per-frame context that was neither prepared ahead nor imported (strict mode)')
         h, w = fr.lr.shape[1:]
-        fr.lr8 = ops.pack_nhwc16(fr.lr, 8)
+        prep = self.frame_prep(fr)
+        fr.lr8 = prep[0] if prep is not None else ops.pack_nhwc16(fr.lr, 8)
         # (running the reference encoders on a side stream underneath the matching kernel measured neutral, +0..1 %: removed in round 5)
-        fr.conf, fr.idx, (gh, gw) = self.feature_match(fr)
-        ref_feat, ref_feat_down = self._ref_encoders(fr)
+        fr.conf, fr.idx, (gh, gw) = self.feature_match(fr, prep)
+        ref_feat, ref_feat_down = self._ref_encoders(fr, prep[1] if prep is not None else None)
         s1, s2 = self.ks // 2, self.ks
         # aa1 (RefVSR.py:127, attention.py:142-157): gather of LR/2 reference features; with a patch > 1 px (HD)
         # also the affine AlignedConv2d, queried by bicubic x0.5 of the LR frame (RefVSR.py:125)

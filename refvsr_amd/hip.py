@@ -154,6 +154,11 @@ SIGNATURES = {
     # rectangle sums for the field-of-view evaluation (added symbols, ABI 15 unchanged)
     'refvsr_score_regions': [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _Z, _P, _P],
     'refvsr_score_max_rects': [],                # returns REFVSR_SCORE_MAX_RECTS
+    # matching rows through LDS, flagged lo rows, one-launch pyramid and frame preparation (added symbols, ABI 15 unchanged)
+    'refvsr_set_match_patches_kernel': [_I],
+    'refvsr_match_lo_rows': [_P, _I, _I, _P, _P, _P, _P],
+    'refvsr_avgpool_pyramid': [_P, _I, _I, _I, _P, _P],
+    'refvsr_frame_prep': [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
 }
 _SPECIAL = {'refvsr_abi_version': (C.c_int, []), 'refvsr_last_error': (C.c_char_p, []),
             'refvsr_score_workspace_bytes': (C.c_size_t, [_I, _I, _I]),

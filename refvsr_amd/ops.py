@@ -597,6 +597,42 @@ def avgpool2(x):
     return out
 
 
+def avgpool_pyramid(x):
+    """Five avgpool2 calls in one launch (refvsr_avgpool_pyramid): x planar [c,h,w] with h, w multiples of 32 -> the list of the five
+    coarser levels, finest first (views of one allocation).  The same bits as the five calls."""
+    _planar(x)
+    c, h, w = x.shape
+    assert h % 32 == 0 and w % 32 == 0
+    sizes = [c * (h >> k) * (w >> k) for k in range(1, 6)]
+    offs = [0]
+    for n in sizes:
+        offs.append(offs[-1] + (n + 63) // 64 * 64)
+    buf = torch.empty((offs[-1],), dtype=torch.float32, device=x.device)
+    lv = [buf[offs[k]:offs[k] + sizes[k]].view(c, h >> (k + 1), w >> (k + 1)) for k in range(5)]
+    dst = (C.c_void_p * 5)(*[t_.data_ptr() for t_ in lv])
+    hip.check(hip.lib().refvsr_avgpool_pyramid(_ptr(x), c, h, w, dst, _stream()), 'avgpool_pyramid')
+    return lv
+
+
+def frame_prep(lr, ref, w, b):
+    """refvsr_frame_prep: what pack_nhwc16 x 2, the 1x1 MeanShift conv_direct x 2, avgpool2 of the reference map and pack_nhwc32 x 2
+    make of the planar fp32 frames lr [3,h,w] / ref [3,hr,wr], in one launch and the same bits.  w [3,3,1,1] / b [3]: the MeanShift.
+    Returns (lr8 [h,w,8] fp16, ref8 [hr,wr,8] fp16, lr_n [h,w,4] fp32, ref_n [hr//2,wr//2,4] fp32)."""
+    _planar(lr, 3)
+    _planar(ref, 3)
+    assert tuple(w.shape) == (3, 3, 1, 1) and w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
+    assert tuple(b.shape) == (3,) and b.is_cuda and b.dtype == torch.float32 and b.is_contiguous()
+    h, wd = lr.shape[1:]
+    hr, wr = ref.shape[1:]
+    lr8 = torch.empty((h, wd, 8), dtype=torch.float16, device=lr.device)
+    ref8 = torch.empty((hr, wr, 8), dtype=torch.float16, device=lr.device)
+    lr_n = torch.empty((h, wd, 4), dtype=torch.float32, device=lr.device)
+    ref_n = torch.empty((hr // 2, wr // 2, 4), dtype=torch.float32, device=lr.device)
+    hip.check(hip.lib().refvsr_frame_prep(_ptr(lr), h, wd, _ptr(ref), hr, wr, _ptr(w), _ptr(b), _ptr(lr8), _ptr(ref8), _ptr(lr_n),
+                                          _ptr(ref_n), _stream()), 'frame_prep')
+    return lr8, ref8, lr_n, ref_n
+
+
 def maxpool2(x):
     _planar(x)
     c, h, w = x.shape
@@ -855,6 +891,11 @@ def spynet_level_input_batch(refs, supps, flow_prev):
     return out8, fup
 
 
+def set_match_patches_kernel(mode):
+    """A/B knob of refvsr_match_patches (process-wide): 0 = one pixel per thread with global gathers, 1 = LDS tile (default)."""
+    hip.check(hip.lib().refvsr_set_match_patches_kernel(int(mode)), 'set_match_patches_kernel')
+
+
 def match_patches(feat, row_pad, want_lo=False):
     """feat planar [16,h,w] -> (rows fp16 [pad(h*w), KP] zero padded, inv_norm fp32 [h*w][, rows_lo fp16 like rows: the
     low halves of the hi + lo operand split, scaled by 2^11 -- the exact search's second operand])."""
@@ -892,6 +933,8 @@ MATCH_EXACT_MARGIN = 2.5e-4
 def match_refine(lr_feat, ref_feat, inv_lr, inv_ref, cand, cand_val=None, margin=None, lr_split=None, ref_split=None):
     """Exact re-rank of the candidates; with cand_val / margin / lr_split = (lr_rows, lr_rows_lo) / ref_split = (ref_rows, ref_rows_lo) also the exhaustive
     search of the columns the fp16 GEMM cannot decide.  margin = inf searches EVERY column exhaustively (test aid).
+    lr_rows_lo = None: the low halves of the flagged columns' rows -- the only ones the search reads -- are written here, after the
+    flagging, by refvsr_match_lo_rows (the reference rows' low halves are streamed whole and must be complete).
     Returns (conf, idx) or (conf, idx, flagged int32 [1 + n], [0] = count) when flagging is on."""
     _planar(lr_feat, 16)
     _planar(ref_feat, 16)
@@ -908,6 +951,9 @@ def match_refine(lr_feat, ref_feat, inv_lr, inv_ref, cand, cand_val=None, margin
     assert cand_val is not None and ref_split is not None and lr_split is not None
     assert cand_val.shape == cand.shape and cand_val.is_contiguous()
     (lr_rows, lr_lo), (ref_rows, ref_lo) = lr_split, ref_split
+    sparse_lo = lr_lo is None
+    if sparse_lo:
+        lr_lo = torch.empty_like(lr_rows)
     for r, n_, pad in ((lr_rows, h * w, 1), (lr_lo, h * w, 1), (ref_rows, hr * wr, hip.MATCH_ROWCHUNK), (ref_lo, hr * wr, hip.MATCH_ROWCHUNK)):
         assert r.dtype == torch.float16 and r.is_contiguous() and r.shape[1] == hip.MATCH_KP
         assert r.shape[0] >= n_ and r.shape[0] % pad == 0
@@ -919,6 +965,8 @@ def match_refine(lr_feat, ref_feat, inv_lr, inv_ref, cand, cand_val=None, margin
     hip.check(hip.lib().refvsr_match_refine(_ptr(lr_feat), h, w, _ptr(ref_feat), hr, wr, _ptr(inv_lr), _ptr(inv_ref),
                                             _ptr(cand), _ptr(cand_val), cand.shape[1], float(margin), _ptr(flagged), _ptr(conf),
                                             _ptr(idx), _stream()), 'match_refine')
+    if sparse_lo:
+        hip.check(hip.lib().refvsr_match_lo_rows(_ptr(lr_feat), h, w, _ptr(inv_lr), _ptr(flagged), _ptr(lr_lo), _stream()), 'match_lo_rows')
     hip.check(hip.lib().refvsr_match_exact(_ptr(lr_feat), h, w, _ptr(ref_feat), hr, wr, _ptr(lr_rows), _ptr(lr_lo), _ptr(ref_rows), _ptr(ref_lo),
                                            _ptr(inv_lr), _ptr(inv_ref), _ptr(flagged), _ptr(keys), _ptr(conf), _ptr(idx),
                                            _stream()), 'match_exact')
