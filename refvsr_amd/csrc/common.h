@@ -61,6 +61,83 @@ static inline int rv_num_cus() {
 // (refvsr_stream_create_cu_range / refvsr_stream_set_cu_budget, runtime.hip), otherwise the whole device.
 int rv_stream_cus(hipStream_t st);
 
+// Grid cap of a persistent launcher on `st`, with the launcher's per-device one-time set-up (a process may drive several GPUs): the
+// kernel's dynamic-LDS attribute (attr_lds bytes) and its occupancy with `lds` bytes (asked again when lds changes; block = 0: one
+// workgroup per CU by construction, nothing is asked).  *cap = CUs of the stream x occupancy, a multiple of 8 (XCDs), at least 8.
+// One RvLaunchCap per kernel instantiation (a function-local static of its launcher).
+struct RvLaunchCap {
+    bool attr_done[RV_MAX_DEVICES];
+    int occ[RV_MAX_DEVICES];
+    size_t occ_lds[RV_MAX_DEVICES];
+};
+template <typename Kernel>
+static int rv_launch_cap(RvLaunchCap& c, Kernel kernel, int block, size_t attr_lds, size_t lds, hipStream_t st, int* cap) {
+    const int dev = rv_device();
+    if (!c.attr_done[dev]) {
+        RV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)attr_lds));
+        c.attr_done[dev] = true;
+    }
+    if (block == 0) {
+        c.occ[dev] = 1;
+    } else if (c.occ[dev] == 0 || c.occ_lds[dev] != lds) {
+        int occ = 0;
+        RV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, block, lds));
+        c.occ[dev] = occ < 1 ? 1 : occ;
+        c.occ_lds[dev] = lds;
+    }
+    *cap = (rv_stream_cus(st) * c.occ[dev]) & ~7;
+    if (*cap < 8) *cap = 8;
+    return 0;
+}
+
+// Host driver of a chain of fused blocks (resblock24.hip, resblock48.hip): n blocks x <- x + conv2(act(conv1 x)) on `batch` fp16 HWC
+// maps of one geometry, pxb bytes per pixel (batch = 1: the plain chain); block i's parameters are the blob at blobs + i * blob_stride
+// (>= min_blob bytes).  n launches on the caller's stream, each over ALL maps: launch(a, st) with a.bsrc / a.bout / a.src / a.out /
+// a.blob of block i; intermediates ping-pong between scratch0 / scratch1 ([batch] maps each, contiguous; blocks cannot run in
+// place: neighbouring tiles read the input halo).  name: the entry point, as the error messages call it.
+template <typename Args, typename Launch>
+static int rv_resblock_chain(const char* name, int pxb, int min_blob, const void* const* src, int batch, int h, int w, int n,
+                             const void* blobs, size_t blob_stride, float act_slope, void* scratch0, void* scratch1, void* const* out,
+                             void* stream, Launch launch) {
+    RV_CHECK(src && out && blobs && h > 0 && w > 0 && n >= 1 && batch >= 1 && batch <= REFVSR_MAX_MAPS, "%s: bad args", name);
+    RV_CHECK(blob_stride >= (size_t)min_blob && blob_stride % 16 == 0 && ((uintptr_t)blobs & 15) == 0,
+             "%s: blobs must be 16-byte aligned, stride >= %d", name, min_blob);
+    RV_CHECK(act_slope >= 0.f && act_slope <= 1.f, "%s: activation slope must lie in [0, 1]", name);
+    RV_CHECK(n == 1 || scratch0, "%s: n >= 2 needs scratch0", name);
+    RV_CHECK(n <= 2 || scratch1, "%s: n >= 3 needs scratch1", name);
+    const size_t mapb = (size_t)h * w * pxb;
+    for (int b = 0; b < batch; ++b) {
+        RV_CHECK(src[b] && out[b], "%s: null map pointer (map %d)", name, b);
+        for (int c = 0; c < batch; ++c) {
+            const unsigned char* s0 = scratch0 ? (const unsigned char*)scratch0 + c * mapb : nullptr;
+            const unsigned char* s1 = scratch1 ? (const unsigned char*)scratch1 + c * mapb : nullptr;
+            RV_CHECK(src[b] != out[c] && s0 != out[b] && s1 != out[b] && (n < 2 || s0 != src[b]) && (n < 3 || s1 != src[b]) &&
+                     (c == b || out[b] != out[c]), "%s: buffers must be distinct", name);
+        }
+    }
+    RV_CHECK(n < 3 || scratch0 != scratch1, "%s: buffers must be distinct", name);
+    RV_CHECK((long long)h * w * pxb < (1ll << 31), "%s: map too large for 32-bit offsets", name);
+    RV_CHECK(refvsr_init() == 0, "init failed");
+    Args a;
+    memset(&a, 0, sizeof(a));
+    a.h = h; a.w = w; a.act_slope = act_slope; a.batch = batch;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned char* cur[REFVSR_MAX_MAPS];
+    for (int b = 0; b < batch; ++b) cur[b] = (const unsigned char*)src[b];
+    for (int i = 0; i < n; ++i) {
+        unsigned char* sc = (unsigned char*)((i & 1) ? scratch1 : scratch0);
+        for (int b = 0; b < batch; ++b) {
+            a.bsrc[b] = cur[b];
+            a.bout[b] = (i == n - 1) ? (unsigned char*)out[b] : sc + b * mapb;
+        }
+        a.src = a.bsrc[0]; a.out = a.bout[0]; a.blob = (const unsigned char*)blobs + (size_t)i * blob_stride;
+        const int rc = launch(a, st);
+        if (rc) return rc;
+        for (int b = 0; b < batch; ++b) cur[b] = a.bout[b];
+    }
+    return 0;
+}
+
 // Persistent tile walk, XCD-aware and balanced.  Workgroup b runs on XCD b % 8 (observed placement, used for speed only):
 // the workgroups of one XCD get consecutive ranks, rank r walks the CONTIGUOUS tile range [r*n/g, (r+1)*n/g), so every
 // workgroup has floor or ceil(n/g) tiles (a strided walk inside fixed eighths of the frame left single workgroups with

@@ -563,68 +563,24 @@ static int launch_rb24(RB24Args& a, hipStream_t st) {
     a.tiles_x = rv_cdiv(a.w, RB_TW);
     a.tpm = a.tiles_x * rv_cdiv(a.h, TH);
     a.n_tiles = a.tpm * (a.batch > 1 ? a.batch : 1);
-    static bool attr_done[RV_MAX_DEVICES] = {};
-    static int occ_dev[RV_MAX_DEVICES] = {};
-    const int dev = rv_device();
-    if (!attr_done[dev]) {
-        RV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&resblock24_kernel<RELU, NWV, PROBE, TH, STORE, HEAD, WF>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, RB_LDS));
-        int occ = 0;
-        RV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, resblock24_kernel<RELU, NWV, PROBE, TH, STORE, HEAD, WF>, NWV * 64, RB_LDS));
-        occ_dev[dev] = occ < 1 ? 1 : occ;
-        attr_done[dev] = true;
-    }
-    int cap = (rv_stream_cus(st) * occ_dev[dev]) & ~7;
-    if (cap < 8) cap = 8;
+    static RvLaunchCap lc = {};
+    int cap;
+    if (int rc = rv_launch_cap(lc, &resblock24_kernel<RELU, NWV, PROBE, TH, STORE, HEAD, WF>, NWV * 64, RB_LDS, RB_LDS, st, &cap)) return rc;
     a.grid = a.n_tiles < cap ? a.n_tiles : cap;
     hipLaunchKernelGGL((resblock24_kernel<RELU, NWV, PROBE, TH, STORE, HEAD, WF>), dim3(a.grid), dim3(NWV * 64), RB_LDS, st, a);
     RV_LAUNCH_CHECK();
     return 0;
 }
 
-// n fused blocks x <- x + conv2(act(conv1 x)) on `batch` 24-channel fp16 HWC maps of one geometry (batch = 1: the plain chain); block
-// i's weights are the blob at blobs + i * blob_stride (refvsr_amd/packing.py:pack_resblock24).  n launches on the caller's stream, each
-// over ALL maps (one weight fill per workgroup, batch x the tiles: an LR launch of RefVSR_small is one 8 x 32 tile per workgroup --
-// 4 100 of its 13 000 cycles are the 43 KB fill -- two maps per launch are two tiles per fill); intermediates ping-pong between
-// scratch0 / scratch1 ([batch] maps each, contiguous; blocks cannot run in place: neighbouring tiles read the input halo).
+// n fused blocks x <- x + conv2(act(conv1 x)) on `batch` 24-channel fp16 HWC maps of one geometry (rv_resblock_chain, common.h); block
+// i's weights are the blob at blobs + i * blob_stride (refvsr_amd/packing.py:pack_resblock24).  Each launch runs over ALL maps (one
+// weight fill per workgroup, batch x the tiles: an LR launch of RefVSR_small is one 8 x 32 tile per workgroup -- 4 100 of its 13 000
+// cycles are the 43 KB fill -- two maps per launch are two tiles per fill).
 // WF = 1: the blobs are in the fp16 weight format (REFVSR_RESBLOCK24_F16W_BLOB_BYTES each, refvsr_resblock24_chain_f16w).
 template <int WF>
 static int rb24_chain_impl(const void* const* src, int batch, int h, int w, int n, const void* blobs, size_t blob_stride,
                            float act_slope, void* scratch0, void* scratch1, void* const* out, void* stream) {
-    constexpr int BLOB = rb_blob(WF);
-    RV_CHECK(src && out && blobs && h > 0 && w > 0 && n >= 1 && batch >= 1 && batch <= REFVSR_MAX_MAPS, "resblock24_chain: bad args");
-    RV_CHECK(blob_stride >= (size_t)BLOB && blob_stride % 16 == 0 && ((uintptr_t)blobs & 15) == 0,
-             "resblock24_chain: blobs must be 16-byte aligned, stride >= %d", BLOB);
-    RV_CHECK(act_slope >= 0.f && act_slope <= 1.f, "resblock24_chain: activation slope must lie in [0, 1]");
-    RV_CHECK(n == 1 || scratch0, "resblock24_chain: n >= 2 needs scratch0");
-    RV_CHECK(n <= 2 || scratch1, "resblock24_chain: n >= 3 needs scratch1");
-    const size_t mapb = (size_t)h * w * RB_PXB;
-    for (int b = 0; b < batch; ++b) {
-        RV_CHECK(src[b] && out[b], "resblock24_chain: null map pointer (map %d)", b);
-        for (int c = 0; c < batch; ++c) {
-            const unsigned char* s0 = scratch0 ? (const unsigned char*)scratch0 + c * mapb : nullptr;
-            const unsigned char* s1 = scratch1 ? (const unsigned char*)scratch1 + c * mapb : nullptr;
-            RV_CHECK(src[b] != out[c] && s0 != out[b] && s1 != out[b] && (n < 2 || s0 != src[b]) && (n < 3 || s1 != src[b]) &&
-                     (c == b || out[b] != out[c]), "resblock24_chain: buffers must be distinct");
-        }
-    }
-    RV_CHECK(n < 3 || scratch0 != scratch1, "resblock24_chain: buffers must be distinct");
-    RV_CHECK((long long)h * w * RB_PXB < (1ll << 31), "resblock24_chain: map too large for 32-bit offsets");
-    RV_CHECK(refvsr_init() == 0, "init failed");
-    RB24Args a;
-    memset(&a, 0, sizeof(a));
-    a.h = h; a.w = w; a.act_slope = act_slope; a.batch = batch;
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned char* cur[REFVSR_MAX_MAPS];
-    for (int b = 0; b < batch; ++b) cur[b] = (const unsigned char*)src[b];
-    for (int i = 0; i < n; ++i) {
-        unsigned char* sc = (unsigned char*)((i & 1) ? scratch1 : scratch0);
-        for (int b = 0; b < batch; ++b) {
-            a.bsrc[b] = cur[b];
-            a.bout[b] = (i == n - 1) ? (unsigned char*)out[b] : sc + b * mapb;
-        }
-        a.src = a.bsrc[0]; a.out = a.bout[0]; a.blob = (const unsigned char*)blobs + (size_t)i * blob_stride;
-        int rc;
+    const auto launch = [=](RB24Args& a, hipStream_t st) -> int {
         a.probe = g_rb_probe; a.probe_iter = g_rb_probe_iter;
         // 16 x 32 tiles on sixteen waves (one workgroup per CU: half the weight fill per CU, 10 % less halo work in conv1, 17 % less
         // tile staging) pay on maps of many tiles per workgroup -- 540 x 960: 27.3 -> 26.3 us, 1080 x 1920: 100.1 -> 95.9 us; at
@@ -632,18 +588,17 @@ static int rb24_chain_impl(const void* const* src, int batch, int h, int w, int 
         // and sixteen waves wait longer at the barriers), below that the 8 x 32 tiles fill more CUs (135 x 240: 6.2 vs 8.2 us)
         const int nt8 = rv_cdiv(w, RB_TW) * rv_cdiv(h, 8) * batch;
         const int waves = g_rb24_waves ? g_rb24_waves : (nt8 >= 4 * rv_stream_cus(st) ? 16 : 8);
-        if (WF == 0 && g_rb_probe && act_slope == 0.f && waves == 8) rc = launch_rb24<true, 8, true>(a, st);          // tools/probe_resblock24.py
-        else if (WF == 0 && g_rb_probe && act_slope == 0.f && waves == 16) rc = launch_rb24<true, 16, true, 16>(a, st);
-        else if (waves == 4) rc = act_slope == 0.f ? launch_rb24<true, 4, false, 8, 0, 0, WF>(a, st) : launch_rb24<false, 4, false, 8, 0, 0, WF>(a, st);
+        if (WF == 0 && g_rb_probe && act_slope == 0.f && waves == 8) return launch_rb24<true, 8, true>(a, st);         // tools/probe_resblock24.py
+        if (WF == 0 && g_rb_probe && act_slope == 0.f && waves == 16) return launch_rb24<true, 16, true, 16>(a, st);
+        if (waves == 4) return act_slope == 0.f ? launch_rb24<true, 4, false, 8, 0, 0, WF>(a, st) : launch_rb24<false, 4, false, 8, 0, 0, WF>(a, st);
 #define RB24_PICK(R_)                                                                                                              \
         (waves == 16 ? (g_rb24_store == 1 ? launch_rb24<R_, 16, false, 16, 1, 0, WF>(a, st) : launch_rb24<R_, 16, false, 16, 0, 0, WF>(a, st)) \
                      : (g_rb24_store == 1 ? launch_rb24<R_, 8, false, 8, 1, 0, WF>(a, st) : launch_rb24<R_, 8, false, 8, 0, 0, WF>(a, st)))
-        else rc = act_slope == 0.f ? RB24_PICK(true) : RB24_PICK(false);
+        return act_slope == 0.f ? RB24_PICK(true) : RB24_PICK(false);
 #undef RB24_PICK
-        if (rc) return rc;
-        for (int b = 0; b < batch; ++b) cur[b] = a.bout[b];
-    }
-    return 0;
+    };
+    return rv_resblock_chain<RB24Args>("resblock24_chain", RB_PXB, rb_blob(WF), src, batch, h, w, n, blobs, blob_stride, act_slope, scratch0,
+                                       scratch1, out, stream, launch);
 }
 
 extern "C" int refvsr_resblock24_chain(const void* src, int h, int w, int n, const void* blobs, size_t blob_stride,

@@ -380,67 +380,29 @@ extern int g_rb_probe_iter;
 
 template <bool RELU, bool PROBE = false>
 static int launch_rb48(RB48Args& a, hipStream_t st) {
-    static bool attr_done[RV_MAX_DEVICES] = {};
-    const int dev = rv_device();
-    if (!attr_done[dev]) {
-        RV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&resblock48_kernel<RELU, PROBE>), hipFuncAttributeMaxDynamicSharedMemorySize, R48_LDS));
-        attr_done[dev] = true;
-    }
+    static RvLaunchCap lc = {};
+    int cap;                                                              // one 135 KB workgroup per CU
+    if (int rc = rv_launch_cap(lc, &resblock48_kernel<RELU, PROBE>, 0, R48_LDS, R48_LDS, st, &cap)) return rc;
     a.tiles_x = rv_cdiv(a.w, R48_TW);
     a.tpm = a.tiles_x * rv_cdiv(a.h, R48_TH);
     a.n_tiles = a.tpm * (a.batch > 1 ? a.batch : 1);
-    int cap = rv_stream_cus(st) & ~7;                                     // one 135 KB workgroup per CU
-    if (cap < 8) cap = 8;
     a.grid = a.n_tiles < cap ? a.n_tiles : cap;
     hipLaunchKernelGGL((resblock48_kernel<RELU, PROBE>), dim3(a.grid), dim3(R48_NT), R48_LDS, st, a);
     RV_LAUNCH_CHECK();
     return 0;
 }
 
-// n fused blocks x <- x + conv2(act(conv1 x)) on `batch` 48-channel fp16 HWC maps of one geometry (batch = 1: the plain chain); block i's
-// parameters are the blob at blobs + i * blob_stride (refvsr_amd/packing.py:pack_resblock48).  n launches on the caller's stream, each over
-// ALL maps; intermediates ping-pong between scratch0 / scratch1 ([batch] maps each, contiguous) like refvsr_resblock24_chain.
+// n fused blocks x <- x + conv2(act(conv1 x)) on `batch` 48-channel fp16 HWC maps of one geometry (rv_resblock_chain, common.h); block i's
+// parameters are the blob at blobs + i * blob_stride (refvsr_amd/packing.py:pack_resblock48).
 static int rb48_chain_impl(const void* const* src, int batch, int h, int w, int n, const void* blobs, size_t blob_stride, float act_slope,
                            void* scratch0, void* scratch1, void* const* out, void* stream) {
-    RV_CHECK(src && out && blobs && h > 0 && w > 0 && n >= 1 && batch >= 1 && batch <= REFVSR_MAX_MAPS, "resblock48_chain: bad args");
-    RV_CHECK(blob_stride >= (size_t)R48_BLOB && blob_stride % 16 == 0 && ((uintptr_t)blobs & 15) == 0,
-             "resblock48_chain: blobs must be 16-byte aligned, stride >= %d", R48_BLOB);
-    RV_CHECK(act_slope >= 0.f && act_slope <= 1.f, "resblock48_chain: activation slope must lie in [0, 1]");
-    RV_CHECK(n == 1 || scratch0, "resblock48_chain: n >= 2 needs scratch0");
-    RV_CHECK(n <= 2 || scratch1, "resblock48_chain: n >= 3 needs scratch1");
-    const size_t mapb = (size_t)h * w * R48_GPX;
-    for (int b = 0; b < batch; ++b) {
-        RV_CHECK(src[b] && out[b], "resblock48_chain: null map pointer (map %d)", b);
-        for (int c = 0; c < batch; ++c) {
-            const unsigned char* s0 = scratch0 ? (const unsigned char*)scratch0 + c * mapb : nullptr;
-            const unsigned char* s1 = scratch1 ? (const unsigned char*)scratch1 + c * mapb : nullptr;
-            RV_CHECK(src[b] != out[c] && s0 != out[b] && s1 != out[b] && (n < 2 || s0 != src[b]) && (n < 3 || s1 != src[b]) &&
-                     (c == b || out[b] != out[c]), "resblock48_chain: buffers must be distinct");
-        }
-    }
-    RV_CHECK(n < 3 || scratch0 != scratch1, "resblock48_chain: buffers must be distinct");
-    RV_CHECK((long long)h * w * R48_GPX < (1ll << 31), "resblock48_chain: map too large for 32-bit offsets");
-    RV_CHECK(refvsr_init() == 0, "init failed");
-    RB48Args a;
-    memset(&a, 0, sizeof(a));
-    a.h = h; a.w = w; a.act_slope = act_slope; a.batch = batch;
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned char* cur[REFVSR_MAX_MAPS];
-    for (int b = 0; b < batch; ++b) cur[b] = (const unsigned char*)src[b];
-    for (int i = 0; i < n; ++i) {
-        unsigned char* sc = (unsigned char*)((i & 1) ? scratch1 : scratch0);
-        for (int b = 0; b < batch; ++b) {
-            a.bsrc[b] = cur[b];
-            a.bout[b] = (i == n - 1) ? (unsigned char*)out[b] : sc + b * mapb;
-        }
-        a.src = a.bsrc[0]; a.out = a.bout[0]; a.blob = (const unsigned char*)blobs + (size_t)i * blob_stride;
+    const auto launch = [=](RB48Args& a, hipStream_t st) -> int {
         a.probe = g_rb_probe; a.probe_iter = g_rb_probe_iter;
-        const int rc = (g_rb_probe && act_slope == 0.f) ? launch_rb48<true, true>(a, st)       // tools/probe_resblock48.py
-                       : act_slope == 0.f ? launch_rb48<true>(a, st) : launch_rb48<false>(a, st);
-        if (rc) return rc;
-        for (int b = 0; b < batch; ++b) cur[b] = a.bout[b];
-    }
-    return 0;
+        return (g_rb_probe && act_slope == 0.f) ? launch_rb48<true, true>(a, st)       // tools/probe_resblock48.py
+               : act_slope == 0.f ? launch_rb48<true>(a, st) : launch_rb48<false>(a, st);
+    };
+    return rv_resblock_chain<RB48Args>("resblock48_chain", R48_GPX, R48_BLOB, src, batch, h, w, n, blobs, blob_stride, act_slope, scratch0,
+                                       scratch1, out, stream, launch);
 }
 
 extern "C" int refvsr_resblock48_chain(const void* src, int h, int w, int n, const void* blobs, size_t blob_stride, float act_slope,

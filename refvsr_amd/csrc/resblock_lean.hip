@@ -365,24 +365,9 @@ extern "C" int refvsr_set_resblock_waves(int waves) {
 
 template <int MT, bool WIDE, int NWV>
 static int launch_lean(ResLeanArgs& a, size_t lds, hipStream_t st) {
-    // per device: the dynamic-LDS attribute and the occupancy (a process may drive several GPUs)
-    static bool attr_done[RV_MAX_DEVICES] = {};
-    static int occ_dev[RV_MAX_DEVICES] = {};
-    static size_t occ_lds[RV_MAX_DEVICES] = {};
-    const int dev = rv_device();
-    if (!attr_done[dev]) {
-        RV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&resblock_lean_kernel<MT, WIDE, NWV>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done[dev] = true;
-    }
-    if (occ_dev[dev] == 0 || occ_lds[dev] != lds) {
-        int occ = 0;
-        RV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, resblock_lean_kernel<MT, WIDE, NWV>, NWV * 64, lds));
-        occ_dev[dev] = occ < 1 ? 1 : occ;
-        occ_lds[dev] = lds;
-    }
-    int cap = (rv_stream_cus(st) * occ_dev[dev]) & ~7;
-    if (cap < 8) cap = 8;
+    static RvLaunchCap lc = {};
+    int cap;
+    if (int rc = rv_launch_cap(lc, &resblock_lean_kernel<MT, WIDE, NWV>, NWV * 64, 160 * 1024, lds, st, &cap)) return rc;
     const int gx = a.n_tiles < cap ? a.n_tiles : cap;
     a.grid = gx;
     hipLaunchKernelGGL((resblock_lean_kernel<MT, WIDE, NWV>), dim3(gx), dim3(NWV * 64), lds, st, a);

@@ -553,75 +553,94 @@ class Engine(object):
             torch.cuda.current_stream(dev).synchronize()
         return z
 
+    def _chain(self, kind, pairs, dev):
+        """The table of a run of fused blocks for one kernel family (kind: 'rb24' | 'rb48' | 'generic'), built once per run and kept
+        with the packed weights it points into."""
+        chains = self.W.chains
+        key = tuple(id(c1) for c1, _ in pairs)
+        if kind != 'generic':
+            key = (kind,) + key
+        ch = chains.get(key)
+        if ch is None:
+            ch = chains[key] = (ops.ResblockChain(pairs) if kind == 'generic' else
+                                (ops.Resblock24Chain if kind == 'rb24' else ops.Resblock48Chain)(pairs, dev))
+        return ch
+
     def _block_chain(self, x, pairs, act):
-        """A run of residual blocks x <- x + conv2(act(conv1 x)); pairs = [(conv1, conv2), ...] packed weights.
-        One launch per block (fused kernel) or two launches per block (fuse_resblocks off / unsupported channel count).
+        return self._block_chain_b([x], pairs, act)[0]
+
+    def _block_chain_b(self, xs, pairs, act):
+        """A run of residual blocks x <- x + conv2(act(conv1 x)) over the B >= 1 maps xs (list in, list out); pairs = [(conv1,
+        conv2), ...] packed weights.  One launch per block over all maps (the 24- and 48-channel fused kernels), else map by map:
+        one launch per block (generic fused kernel) or two (fuse_resblocks off / unsupported channel count).
         (A kernel chaining TWO blocks per launch with halo recomputation was built in round 1 and measured in round 2:
         29.3 us vs 2 x 14.7 us on the LR maps, slower on the 2x maps and 4 % slower end to end -- removed.)"""
-        if self.fuse_resblocks and self.rb24 and x.shape[2] == 24 and pairs[0][0].raw is not None:
+        h, w, c = xs[0].shape
+        if self.fuse_resblocks and self.rb24 and c == 24 and pairs[0][0].raw is not None:
             # mid_channels = 24 (the RefVSR_small family): the compile-time-specialised kernel, one blob per block
-            chains = self.W.chains                                  # lives and dies with the packed weights it points into
-            key = ('rb24',) + tuple(id(c1) for c1, _ in pairs)
-            ch = chains.get(key)
-            if ch is None:
-                ch = chains[key] = ops.Resblock24Chain(pairs, x.device)
+            ch = self._chain('rb24', pairs, xs[0].device)
             if self.chain_events is None:
-                return ops.resblock24_chain(ch, x, act)
+                return list(ops.resblock24_chain_b(ch, xs, act, stack=False))
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            out = ops.resblock24_chain(ch, x, act)
+            out = list(ops.resblock24_chain_b(ch, xs, act, stack=False))
             e1.record()
-            self.chain_events.append((e0, e1, len(pairs), x.shape[0], x.shape[1]))
+            self.chain_events.append((e0, e1, len(pairs), h, w) + ((len(xs),) if len(xs) > 1 else ()))
             return out
-        if (self.rb48 and x.shape[2] == 48 and pairs[0][0].raw is not None and 0.0 <= act <= 1.0 and
-                x.shape[0] * x.shape[1] <= self.rb48_max_pixels):
+        if self.rb48 and c == 48 and pairs[0][0].raw is not None and 0.0 <= act <= 1.0 and h * w <= self.rb48_max_pixels:
             # mid_channels = 48 (RefVSR / RefVSR_MFID / RefVSR_MFID_8K): one launch per block, the two 84 KB weight sets swap
             # per tile through LDS-DMA (csrc/resblock48.hip); the intermediate map never reaches HBM.  Maps up to 540 x 960:
             # per block 12.9 vs 23.5 us at 135 x 240, 26.7 vs 30.2 us at 270 x 480 (RefVSR_MFID 85.0 vs 83.2 frames/s); at
             # 1080 x 1920 the two forms are equal stand-alone (396 vs 405 us: 32 tiles per workgroup, each swapping 168 KB of
             # weights, against conv48's 16 x 32 tiles on sixteen waves) and the 1080p -> 8K frame is 0.7 % slower with the fused
             # block (6.76 vs 6.81 frames/s) -> the large maps keep the two launches (profiles/r04_resblock48.txt)
-            chains = self.W.chains
-            key = ('rb48',) + tuple(id(c1) for c1, _ in pairs)
-            ch = chains.get(key)
-            if ch is None:
-                ch = chains[key] = ops.Resblock48Chain(pairs, x.device)
-            return ops.resblock48_chain(ch, x, act)
-        if self.fuse_resblocks and self.chain_calls and ops.resblock_chain_ok(x.shape[2]):
+            ch = self._chain('rb48', pairs, xs[0].device)
+            if len(xs) == 1 or self.rb48_multimap:
+                return list(ops.resblock48_chain_b(ch, xs, act, stack=False))
+            return [ops.resblock48_chain(ch, x, act) for x in xs]
+        if self.fuse_resblocks and self.chain_calls and ops.resblock_chain_ok(c):
             # one library call per run (same launches, same results): 156 of the ~330 launches of a frame
-            chains = self.W.chains
-            key = tuple(id(c1) for c1, _ in pairs)
-            ch = chains.get(key)
-            if ch is None:
-                ch = chains[key] = ops.ResblockChain(pairs)
-            return ops.resblock_chain(ch, x, act)
-        for c1, c2 in pairs:
-            if self.fuse_resblocks:
-                x = ops.resblock(c1, c2, x, act=act)
-            else:
-                t = ops.conv(c1, x, act=act)
-                x = ops.conv(c2, t, res=x)
-        return x
+            ch = self._chain('generic', pairs, None)
+            return [ops.resblock_chain(ch, x, act) for x in xs]
+        out = []
+        for x in xs:
+            for c1, c2 in pairs:
+                if self.fuse_resblocks:
+                    x = ops.resblock(c1, c2, x, act=act)
+                else:
+                    t = ops.conv(c1, x, act=act)
+                    x = ops.conv(c2, t, res=x)
+            out.append(x)
+        return out
 
-    def res_list(self, x, name, n):
+    # The layers below are written ONCE, over lists of B >= 1 maps (`_b`: lists in, lists out): the ops.*_b wrappers issue one
+    # multi-map launch per layer for B >= 2 and hand a list of one map straight to the single-map op.  The unsuffixed names are the
+    # same layers for callers that hold single maps.
+    def res_list_b(self, xs, name, n):
         """ResList (RefVSR_/common.py:64-82) with ResBlocks (:25-39)."""
         pairs = [(self.cw('%s.RBs.%d.conv1' % (name, i)), self.cw('%s.RBs.%d.conv2' % (name, i))) for i in range(n)]
-        y = self._block_chain(x, pairs, 0.2)
-        return ops.conv(self.cw(name + '.conv_tail'), y, res=x)
+        ys = self._block_chain_b(xs, pairs, 0.2)
+        return list(ops.conv_b(self.cw(name + '.conv_tail'), ys, ress=xs, stack=False))
 
-    def resblocks(self, lr8, feat, name, stop=None, resume=None):
+    def res_list(self, x, name, n):
+        return self.res_list_b([x], name, n)[0]
+
+    def resblocks_b(self, lr8s, feats, name, stop=None, resume=None):
         """ResidualBlocksWithInputConv (RefVSR.py:327-360); torch.cat([lr, feat]) fused as two sources.
-        stop = n: only the input conv and the first n blocks (returns the intermediate map); resume = (n, map): the blocks from n
+        stop = n: only the input conv and the first n blocks (returns the intermediate maps); resume = (n, maps): the blocks from n
         on -- the two halves of one call, for running them on different streams (same launches, same results)."""
         pairs = [(self.cw('%s.main.2.%d.conv1' % (name, i)), self.cw('%s.main.2.%d.conv2' % (name, i)))
                  for i in range(self.nb)]
         if resume is not None:
-            n, x = resume
-            return self._block_chain(x, pairs[n:], 0.0) if n < self.nb else x
-        x = ops.conv(self.cw(name + '.main.0'), lr8, feat, act=0.1)
+            n, xs = resume
+            return self._block_chain_b(xs, pairs[n:], 0.0) if n < self.nb else xs
+        xs = list(ops.conv_b(self.cw(name + '.main.0'), lr8s, feats, act=0.1, stack=False))
         if stop is not None:
-            return self._block_chain(x, pairs[:stop], 0.0) if stop > 0 else x
-        return self._block_chain(x, pairs, 0.0)
+            return self._block_chain_b(xs, pairs[:stop], 0.0) if stop > 0 else xs
+        return self._block_chain_b(xs, pairs, 0.0)
+
+    def resblocks(self, lr8, feat, name, stop=None):
+        return self.resblocks_b([lr8], [feat], name, stop)[0]
 
     def pyramid(self, fr):
         """SPyNet.forward resize-to-/32 + normalise + 5x avg_pool2d (SPyNet.py:62-81,117-126)."""
@@ -845,34 +864,45 @@ class Engine(object):
         rgb2 = ops.block_gather_rgb(fr.ref, fr.idx, gh, gw, s2)                          # attention.py:152-154
         fr.aligned_up = self.aligned_conv(feats2, fr.lr, rgb2, 'aa2.align', s2)
 
-    def rap(self, fr, conf_prop, feat, feat_up):
-        """AA_AF_conf_prop (RefVSR.py:123-149)."""
-        R = self.W.raw
+    def _conf_alpha(self, fused, name, up, conf_props, confs, pairs):
+        """The alpha maps of the confidence fusion `name` (RefVSR.py:130, :140-142) for B maps.  fused: cat + both convs (+ the bicubic
+        x2 for up = 2, + the torch.max of :147 for up = 1: returns (alphas, maxima)) in one launch.  Else the separate launches, map
+        by map, on pairs[b] = cat[conf_prop, conf] [2,h,w] (REFVSR_NO_FUSE_CONF, blobs without the fused kernel)."""
+        w0, cw = self.W.raw[name + '.0.0'], self.cw(name + '.1.0')
+        if fused:
+            return ops.conf_alpha_b(conf_props, confs, up, *w0, cw, want_max=up == 1, stack=False)
+        alphas = []
+        for p in pairs:
+            if up == 2:
+                p = ops.bicubic_scale(p, 2, clamp01=True)                                # :140-141
+            a = ops.conv_direct(p, *w0, act=0.2, nhwc16_out=True)
+            alphas.append(ops.conv(cw, a, act=0.2))
+        return alphas
+
+    def rap_b(self, fs, conf_props, feats, feat_ups):
+        """AA_AF_conf_prop (RefVSR.py:123-149) of B independent (frame, carried maps) tuples."""
+        confs = [f.conf for f in fs]
         fused = self.fuse_conf and ops.conf_alpha_ok(self.cw('conf_fusion.1.0')) and ops.conf_alpha_ok(self.cw('conf_fusion2.1.0'))
+        pairs = None if fused else [torch.cat([p, c], 0) for p, c in zip(conf_props, confs)]     # [2,h,w] (:130)
+        alpha = self._conf_alpha(fused, 'conf_fusion', 1, conf_props, confs, pairs)
         if fused:
-            # cat + conf_fusion.0 + conf_fusion.1 (+ the torch.max of :147) in one launch, likewise bicubic x2 + conf_fusion2
-            alpha, conf_next = ops.conf_alpha(conf_prop, fr.conf, 1, *R['conf_fusion.0.0'], self.cw('conf_fusion.1.0'), want_max=True)
-        else:
-            pair = torch.cat([conf_prop, fr.conf], 0)                                    # [2,h,w] (:130)
-            a = ops.conv_direct(pair, *R['conf_fusion.0.0'], act=0.2, nhwc16_out=True)
-            alpha = ops.conv(self.cw('conf_fusion.1.0'), a, act=0.2)
-        t = ops.conv(self.cw('feat_fusion.0.0'), feat, fr.aligned, act=0.2)
-        feat = ops.conv(self.cw('feat_fusion.1.0'), t, act=0.2, mul=alpha, res=feat)     # :131
-        feat = self.res_list(feat, 'feat_decoder', 8)
-        up1 = ops.conv(self.cw('upsample1.upsample_conv'), feat)                         # :138 (pixel shuffle fused)
-        feat_up = ops.conv(self.cw('feat_fusion2_1.0.0'), feat_up, up1, act=0.2)
-        if fused:
-            alpha2 = ops.conf_alpha(conf_prop, fr.conf, 2, *R['conf_fusion2.0.0'], self.cw('conf_fusion2.1.0'))   # :140-142
-        else:
-            pair_up = ops.bicubic_scale(pair, 2, clamp01=True)                           # :140-141
-            a = ops.conv_direct(pair_up, *R['conf_fusion2.0.0'], act=0.2, nhwc16_out=True)
-            alpha2 = ops.conv(self.cw('conf_fusion2.1.0'), a, act=0.2)
-        t = ops.conv(self.cw('feat_fusion2.0.0'), feat_up, fr.aligned_up, act=0.2)
-        feat_up = ops.conv(self.cw('feat_fusion2.1.0'), t, act=0.2, mul=alpha2, res=feat_up)   # :143
-        feat_up = self.res_list(feat_up, 'feat_decoder2', 4)
+            alpha, conf_next = alpha
+        t = ops.conv_b(self.cw('feat_fusion.0.0'), feats, [f.aligned for f in fs], act=0.2, stack=False)
+        feat = list(ops.conv_b(self.cw('feat_fusion.1.0'), list(t), act=0.2, muls=list(alpha), ress=feats, stack=False))     # :131
+        feat = self.res_list_b(feat, 'feat_decoder', 8)
+        up1 = ops.conv_b(self.cw('upsample1.upsample_conv'), feat, stack=False)          # :138 (pixel shuffle fused)
+        feat_up = list(ops.conv_b(self.cw('feat_fusion2_1.0.0'), feat_ups, list(up1), act=0.2, stack=False))
+        alpha2 = self._conf_alpha(fused, 'conf_fusion2', 2, conf_props, confs, pairs)    # :140-142
+        t = ops.conv_b(self.cw('feat_fusion2.0.0'), feat_up, [f.aligned_up for f in fs], act=0.2, stack=False)
+        feat_up = list(ops.conv_b(self.cw('feat_fusion2.1.0'), list(t), act=0.2, muls=list(alpha2), ress=feat_up, stack=False))   # :143
+        feat_up = self.res_list_b(feat_up, 'feat_decoder2', 4)
         if not fused:
-            conf_next = ops.max2(conf_prop, fr.conf)                                     # :147
-        return feat, feat_up, conf_next
+            conf_next = [ops.max2(p, c) for p, c in zip(conf_props, confs)]              # :147
+        return feat, feat_up, list(conf_next)
+
+    def rap(self, fr, conf_prop, feat, feat_up):
+        feat, feat_up, conf_next = self.rap_b([fr], [conf_prop], [feat], [feat_up])
+        return feat[0], feat_up[0], conf_next[0]
 
     def compute_up(self, bw_up, fw_up, conf_bw, conf_fw, lr_center):
         """compute_up + base (RefVSR.py:104-119,288) + final clamp (:297)."""
@@ -1161,85 +1191,13 @@ class Engine(object):
     # forward-branch step (which carries the state from frame to frame) stays one frame per launch.  Results are bit-identical to
     # B forward() calls (tests/test_gpu_e2e.py::test_frame_groups_are_bit_identical).
     def group_ok(self):
-        """Frame groups run on the default kernels of the mid_channels = 24 family (every launch of the backward branches multi-map)
-        and of the mid_channels = 48 family (multi-map warps; its blocks and convs have no multi-map kernels and run map by map inside
-        the group's schedule -- same results)."""
+        """Whether B windows per call are SCHEDULED as a group.  The propagation layers take any configuration for any B (what has no
+        multi-map kernel runs map by map -- same results); a group pays where its launches are multi-map: the default kernels of the
+        mid_channels = 24 family (every launch of the backward branches) and of the mid_channels = 48 family (warps and fused blocks;
+        its convs run map by map inside the group's schedule).  Other configurations keep one window per call."""
         return bool(((self.C == 24 and self.rb24 and self.fuse_resblocks) or (self.C == 48 and self.rb48)) and self.fuse_conf and self.warp_up2 and
                     ops.CONV24 and self.cache and self.overlap and not bool(self.cfg.EVAL.is_gradio) and
                     ops.conf_alpha_ok(self.cw('conf_fusion.1.0')) and ops.conf_alpha_ok(self.cw('conf_fusion2.1.0')))
-
-    def _block_chain_b(self, xs, pairs, act):
-        """_block_chain over B maps (lists in, list out): one multi-map launch per block (the 24- and 48-channel fused blocks; anything
-        else map by map)."""
-        if (self.rb48 and xs[0].shape[2] == 48 and pairs[0][0].raw is not None and 0.0 <= act <= 1.0 and
-                xs[0].shape[0] * xs[0].shape[1] <= self.rb48_max_pixels and self.rb48_multimap):
-            chains = self.W.chains
-            key = ('rb48',) + tuple(id(c1) for c1, _ in pairs)
-            ch = chains.get(key)
-            if ch is None:
-                ch = chains[key] = ops.Resblock48Chain(pairs, xs[0].device)
-            return list(ops.resblock48_chain_b(ch, xs, act, stack=False))
-        if not (self.rb24 and xs[0].shape[2] == 24 and pairs[0][0].raw is not None):
-            return [self._block_chain(x, pairs, act) for x in xs]
-        chains = self.W.chains
-        key = ('rb24',) + tuple(id(c1) for c1, _ in pairs)
-        ch = chains.get(key)
-        if ch is None:
-            ch = chains[key] = ops.Resblock24Chain(pairs, xs[0].device)
-        if self.chain_events is None:
-            return list(ops.resblock24_chain_b(ch, xs, act, stack=False))
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = list(ops.resblock24_chain_b(ch, xs, act, stack=False))
-        e1.record()
-        self.chain_events.append((e0, e1, len(pairs), xs[0].shape[0], xs[0].shape[1], len(xs)))
-        return out
-
-    def res_list_b(self, xs, name, n):
-        pairs = [(self.cw('%s.RBs.%d.conv1' % (name, i)), self.cw('%s.RBs.%d.conv2' % (name, i))) for i in range(n)]
-        ys = self._block_chain_b(xs, pairs, 0.2)
-        return list(ops.conv_b(self.cw(name + '.conv_tail'), ys, ress=xs, stack=False))
-
-    def resblocks_b(self, lr8s, feats, name, resume=None):
-        pairs = [(self.cw('%s.main.2.%d.conv1' % (name, i)), self.cw('%s.main.2.%d.conv2' % (name, i)))
-                 for i in range(self.nb)]
-        if resume is not None:
-            n, xs = resume
-            return self._block_chain_b(xs, pairs[n:], 0.0) if n < self.nb else xs
-        xs = list(ops.conv_b(self.cw(name + '.main.0'), lr8s, feats, act=0.1, stack=False))
-        return self._block_chain_b(xs, pairs, 0.0)
-
-    def rap_b(self, fs, conf_props, feats, feat_ups):
-        """rap() of B independent (frame, carried maps) tuples as multi-map launches (the fused-confidence launch list)."""
-        R = self.W.raw
-        confs = [f.conf for f in fs]
-        alpha, conf_next = ops.conf_alpha_b(conf_props, confs, 1, *R['conf_fusion.0.0'], self.cw('conf_fusion.1.0'), want_max=True, stack=False)
-        t = ops.conv_b(self.cw('feat_fusion.0.0'), feats, [f.aligned for f in fs], act=0.2, stack=False)
-        feat = list(ops.conv_b(self.cw('feat_fusion.1.0'), list(t), act=0.2, muls=list(alpha), ress=feats, stack=False))     # :131
-        feat = self.res_list_b(feat, 'feat_decoder', 8)
-        up1 = ops.conv_b(self.cw('upsample1.upsample_conv'), feat, stack=False)                                                # :138
-        feat_up = list(ops.conv_b(self.cw('feat_fusion2_1.0.0'), feat_ups, list(up1), act=0.2, stack=False))
-        alpha2 = ops.conf_alpha_b(conf_props, confs, 2, *R['conf_fusion2.0.0'], self.cw('conf_fusion2.1.0'), stack=False)      # :140-142
-        t = ops.conv_b(self.cw('feat_fusion2.0.0'), feat_up, [f.aligned_up for f in fs], act=0.2, stack=False)
-        feat_up = list(ops.conv_b(self.cw('feat_fusion2.1.0'), list(t), act=0.2, muls=list(alpha2), ress=feat_up, stack=False))   # :143
-        feat_up = self.res_list_b(feat_up, 'feat_decoder2', 4)
-        return feat, feat_up, list(conf_next)
-
-    def _prop_step_b(self, fs, branch, feats, feat_ups, confs, fls):
-        """_prop_step for B independent chains (lists of B maps / frames / flows; fls None: the first step of the branches)."""
-        if fls is None:
-            # (frames that a one-frame-per-call window prepared carry the head of this step -- input conv + bw_head_blocks blocks, run
-            #  with their preparation: used when every frame of the group has one; a group's own preparation computes none: the whole
-            #  first step is cheaper as multi-map launches here)
-            heads = [f.bw_head for f in fs] if branch == 'backward_resblocks' else [None]
-            if all(hd is not None and hd[0] == heads[0][0] for hd in heads):
-                xs = self.resblocks_b(None, None, branch, resume=(heads[0][0], [hd[1] for hd in heads]))
-            else:
-                xs = self.resblocks_b([f.lr8 for f in fs], feats, branch)
-            return self.rap_b(fs, confs, xs, feat_ups)
-        confs = list(ops.warp_planar_b(confs, fls, stack=False))
-        xs = self.resblocks_b([f.lr8 for f in fs], list(ops.warp_nhwc16_b(feats, fls, stack=False)), branch)
-        return self.rap_b(fs, confs, xs, list(ops.warp_nhwc16_up2_b(feat_ups, fls, stack=False)))
 
     def _frames_group(self, wins):
         """_frames (id-keyed form) for the B windows of a group: the cache keeps the union of their frames (8-bit frames: converted
@@ -1477,7 +1435,7 @@ class Engine(object):
                         F_.wait_event(f.ready)
                 for x in (e.fw_feat, e.fw_feat_up, e.fw_conf, e.fw_flow):
                     x.record_stream(F_)
-            fw_feat, fw_up, fw_conf = self._prop_step_b([fr[ctr] for fr in frs], 'forward_resblocks', [e.fw_feat for e in engines],
+            fw_feat, fw_up, fw_conf = self._prop_step([fr[ctr] for fr in frs], 'forward_resblocks', [e.fw_feat for e in engines],
                                                         [e.fw_feat_up for e in engines], [e.fw_conf for e in engines],
                                                         [e.fw_flow for e in engines])
             for b, (e, fr) in enumerate(zip(engines, frs)):                               # RefVSR.py:279-283
@@ -1504,30 +1462,41 @@ class Engine(object):
             self._side = torch.cuda.Stream(device=dev)
         return self._side
 
-    def _prop_step(self, f, branch, feat, feat_up, conf, fl, up_from_lr=False):
-        """One propagation step (RefVSR.py:216-230 backward, :251-277 forward): warp the carried maps with `fl` (None: first
-        step of a branch, nothing to warp), ResidualBlocksWithInputConv, AA_AF_conf_prop.  up_from_lr: the 2x state is warp(warp(feat, fl), flow_up2(fl)) -- the reference's :254 quirk."""
-        if fl is None:
-            if branch == 'backward_resblocks' and f.bw_head is not None:
-                feat = self.resblocks(f.lr8, feat, branch, resume=f.bw_head)      # its head ran with the frame's preparation
+    def _prop_step(self, fs, branch, feats, feat_ups, confs, fls, up_from_lr=False):
+        """One propagation step (RefVSR.py:216-230 backward, :251-277 forward) of B >= 1 independent chains (lists of B frames / maps /
+        flows in, lists out): warp the carried maps with `fls` (None: first step of a branch, nothing to warp),
+        ResidualBlocksWithInputConv, AA_AF_conf_prop.  up_from_lr: the 2x state is warp(warp(feat, fl), flow_up2(fl)) -- the
+        reference's :254 quirk (feat_ups is not read)."""
+        lr8s = [f.lr8 for f in fs]
+        if fls is None:
+            # (frames that a one-frame-per-call window prepared carry the head of this step -- input conv + bw_head_blocks blocks, run
+            #  with their preparation: used when every frame has one, of the same length; a group's own preparation computes none:
+            #  the whole first step is cheaper as multi-map launches here)
+            heads = [f.bw_head for f in fs] if branch == 'backward_resblocks' else [None]
+            if all(hd is not None and hd[0] == heads[0][0] for hd in heads):
+                xs = self.resblocks_b(None, None, branch, resume=(heads[0][0], [hd[1] for hd in heads]))
             else:
-                feat = self.resblocks(f.lr8, feat, branch)
-            return self.rap(f, conf, feat, feat_up)
-        conf = ops.warp_planar(conf, fl)
-        # the 2x state is warped by flow_up2(fl): evaluated inside the warp kernel (no 2x flow map) unless REFVSR_NO_WARP_UP2=1
-        warp2 = ops.warp_nhwc16_up2 if self.warp_up2 else (lambda m, fl_: ops.warp_nhwc16(m, ops.flow_up2(fl_)))
+                xs = self.resblocks_b(lr8s, feats, branch)
+            return self.rap_b(fs, confs, xs, feat_ups)
+        confs = list(ops.warp_planar_b(confs, fls, stack=False))
+        feats = list(ops.warp_nhwc16_b(feats, fls, stack=False))
+        xs = self.resblocks_b(lr8s, feats, branch)
         if up_from_lr:
-            feat = ops.warp_nhwc16(feat, fl)              # the reference's :254 quirk: the ALREADY WARPED LR state, on the 2x grid
-            x = self.resblocks(f.lr8, feat, branch)
-            return self.rap(f, conf, x, warp2(feat, fl))
-        x = self.resblocks(f.lr8, ops.warp_nhwc16(feat, fl), branch)
-        self._await_fw_up(feat_up)                        # (split hand-off: the 2x state may still be arriving -- first read here)
-        return self.rap(f, conf, x, warp2(feat_up, fl))
+            feat_ups = feats                              # the reference's :254 quirk: the ALREADY WARPED LR state, on the 2x grid
+        else:
+            for u in feat_ups:
+                self._await_fw_up(u)                      # (split hand-off: the 2x state may still be arriving -- first read here)
+        # the 2x state is warped by flow_up2(fl): evaluated inside the warp kernel (no 2x flow map) unless REFVSR_NO_WARP_UP2=1
+        if self.warp_up2:
+            feat_ups = ops.warp_nhwc16_up2_b(feat_ups, fls, stack=False)
+        else:
+            feat_ups = ops.warp_nhwc16_b(feat_ups, [ops.flow_up2(fl) for fl in fls], stack=False)
+        return self.rap_b(fs, confs, xs, list(feat_ups))
 
     def _backward_chains(self, frs, flow, wait=False):
         """Backward propagation branches (RefVSR.py:211-238) of B >= 1 windows: each restarts from zeros and walks from its last
-        frame down to the centre.  B = 1 runs the single-map launch list (_prop_step), B >= 2 one multi-map launch per layer over
-        the B chains (_prop_step_b).  flow(b, i): window b's flow from frame i to i + 1 (backward_flows[:, i] = FlowNet(lrs[i],
+        frame down to the centre, step by step over all B chains (_prop_step: one multi-map launch per layer for B >= 2, the
+        single-map launches for B = 1).  flow(b, i): window b's flow from frame i to i + 1 (backward_flows[:, i] = FlowNet(lrs[i],
         lrs[i+1])).  wait: the frames were prepared on another stream, each step first waits for its frames' `ready`.  Returns the
         B 2x maps and the B confidence maps, on the current stream."""
         B, t = len(frs), len(frs[0])
@@ -1543,11 +1512,7 @@ class Engine(object):
                     if f.ready is not None:
                         torch.cuda.current_stream().wait_event(f.ready)
             fls = None if i == t - 1 else [flow(b, i) for b in range(B)]
-            if B == 1:
-                f1, u1, c1 = self._prop_step(fs[0], 'backward_resblocks', feats[0], feat_ups[0], confs[0], None if fls is None else fls[0])
-                feats, feat_ups, confs = [f1], [u1], [c1]
-            else:
-                feats, feat_ups, confs = self._prop_step_b(fs, 'backward_resblocks', feats, feat_ups, confs, fls)
+            feats, feat_ups, confs = self._prop_step(fs, 'backward_resblocks', feats, feat_ups, confs, fls)
         return feat_ups, confs
 
     def _forward_branch(self, fr, flow, t, h, w, is_first_frame):
@@ -1560,14 +1525,17 @@ class Engine(object):
             range_start = 0
         else:
             range_start = ctr
+
+        def step(f, feat, feat_up, conf, fl, **kw):               # one chain through the list form
+            return [m[0] for m in self._prop_step([f], 'forward_resblocks', [feat], [feat_up], [conf], None if fl is None else [fl], **kw)]
         for i in range(range_start, ctr + 1):
             if i > range_start:
                 # forward_flows[:, i-1] = FlowNet(lrs[i], lrs[i-1]); :253-255 warps the ALREADY WARPED LR state onto the 2x grid
-                feat, feat_up, conf = self._prop_step(fr[i], 'forward_resblocks', feat, None, conf, flow(i, i - 1), up_from_lr=True)
+                feat, feat_up, conf = step(fr[i], feat, None, conf, flow(i, i - 1), up_from_lr=True)
             elif not is_first_frame:                                                # :257-260
-                feat, feat_up, conf = self._prop_step(fr[i], 'forward_resblocks', self.fw_feat, self.fw_feat_up, self.fw_conf, self.fw_flow)
+                feat, feat_up, conf = step(fr[i], self.fw_feat, self.fw_feat_up, self.fw_conf, self.fw_flow)
             else:
-                feat, feat_up, conf = self._prop_step(fr[i], 'forward_resblocks', feat, feat_up, conf, None)
+                feat, feat_up, conf = step(fr[i], feat, feat_up, conf, None)
             if i == ctr:                                                            # :279-283
                 self.fw_feat, self.fw_feat_up, self.fw_conf = feat, feat_up, conf
                 self.fw_flow = flow(ctr + 1, ctr)         # forward_flows[:, ctr]
@@ -1642,7 +1610,7 @@ class Engine(object):
         """phase_a of B <= REFVSR_MAX_MAPS windows of one clip in ONE pass (round 6): wins = [(lrs [t,3,h,w], refs, frame_ids)] -- any
         windows of the clip, consecutive or not (a rank's frames of a block-cyclic partition are not): their backward branches are B
         independent chains over identical weights (RefVSR.py:211-238 restarts from zeros in every window) and run as multi-map launches
-        (_prop_step_b: one launch per layer over B maps, the launch list of a frame group's M section), every flow the B windows ask for
+        (_prop_step: one launch per layer over B maps, the launch list of a frame group's M section), every flow the B windows ask for
         comes out of batched SPyNet passes.  Returns the B handles phase_a would return, bit for bit
         (tests/test_gpu_e2e.py::test_phase_a_group_equals_phase_a); engines without the multi-map launch list run phase_a per window.
         streams=None: everything on the current stream, like phase_a.

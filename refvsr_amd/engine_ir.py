@@ -88,7 +88,7 @@ class EngineIR(Engine):
         self.keyframe_idx = None
 
     def group_ok(self):
-        """Frame groups, phase-A groups and the n > 1 multi-map path are schedules of RefVSR's propagation (Engine._prop_step_b / rap_b):
+        """Frame groups, phase-A groups and the n > 1 multi-map path are schedules of RefVSR's propagation (Engine._prop_step / rap_b):
         an IR engine never takes them, whatever its mid_channels."""
         return False
 

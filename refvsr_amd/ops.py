@@ -337,11 +337,25 @@ def resblock_chain(chain, x, act, post=1.0):
     return out
 
 
-class Resblock24Chain(object):
-    """A run of 24-channel fused blocks for refvsr_resblock24_chain: one device buffer [n, 43264] of per-block blobs
-    (packing.pack_resblock24).  pairs: [(conv1, conv2)] ConvWeights whose packer kept the raw fp32 weights, or
-    [((w1, b1), (w2, b2))] raw tensors.  wfmt: 'hi_lo' | 'fp16' (blobs [n, 28928] of packing.pack_resblock24_f16w for
-    refvsr_resblock24_chain_f16w); None = the weight format of the ConvWeights (raw tensors: 'hi_lo')."""
+class _BlobChain(object):
+    """A run of fused blocks as one device buffer [n, stride] of per-block blobs.  pairs: [(conv1, conv2)] ConvWeights whose packer
+    kept the raw fp32 weights, or [((w1, b1), (w2, b2))] raw tensors; pack(w1, b1, w2, b2): the blob of one block, `stride` bytes."""
+
+    def __init__(self, pairs, device, pack, stride):
+        blobs = []
+        for a, b in pairs:
+            (w1, b1), (w2, b2) = (a.raw if isinstance(a, ConvWeights) else a), (b.raw if isinstance(b, ConvWeights) else b)
+            blobs.append(pack(w1, b1, w2, b2))
+        self.n = len(blobs)
+        self.blobs = torch.stack(blobs, 0).to(device).contiguous()
+        self.stride = self.blobs.shape[1]
+        assert self.stride == stride and self.blobs.data_ptr() % 16 == 0
+
+
+class Resblock24Chain(_BlobChain):
+    """A run of 24-channel fused blocks for refvsr_resblock24_chain: blobs [n, 43264] (packing.pack_resblock24).
+    wfmt: 'hi_lo' | 'fp16' (blobs [n, 28928] of packing.pack_resblock24_f16w for refvsr_resblock24_chain_f16w); None = the weight
+    format of the ConvWeights (raw tensors: 'hi_lo')."""
 
     def __init__(self, pairs, device, wfmt=None):
         from .packing import pack_resblock24, pack_resblock24_f16w
@@ -352,73 +366,57 @@ class Resblock24Chain(object):
             wfmt = fmts.pop()
         assert wfmt in ('hi_lo', 'fp16'), wfmt
         self.wfmt = wfmt
-        pack = pack_resblock24_f16w if wfmt == 'fp16' else pack_resblock24
-        blobs = []
-        for a, b in pairs:
-            (w1, b1), (w2, b2) = (a.raw if isinstance(a, ConvWeights) else a), (b.raw if isinstance(b, ConvWeights) else b)
-            blobs.append(pack(w1, b1, w2, b2))
-        self.n = len(blobs)
-        self.blobs = torch.stack(blobs, 0).to(device).contiguous()
-        self.stride = self.blobs.shape[1]
-        assert self.stride == (hip.RESBLOCK24_F16W_BLOB_BYTES if wfmt == 'fp16' else hip.RESBLOCK24_BLOB_BYTES) and self.blobs.data_ptr() % 16 == 0
+        if wfmt == 'fp16':
+            _BlobChain.__init__(self, pairs, device, pack_resblock24_f16w, hip.RESBLOCK24_F16W_BLOB_BYTES)
+        else:
+            _BlobChain.__init__(self, pairs, device, pack_resblock24, hip.RESBLOCK24_BLOB_BYTES)
 
 
-def _rb24(chain, name):
-    """refvsr_resblock24_chain[_batch], or its _f16w twin for a chain of fp16-format blobs (chain-like objects without a weight
-    format -- torch_ops' blob tables -- are hi + lo)."""
-    return getattr(hip.lib(), name + '_f16w' if getattr(chain, 'wfmt', 'hi_lo') == 'fp16' else name)
+class Resblock48Chain(_BlobChain):
+    """A run of 48-channel fused blocks for refvsr_resblock48_chain: blobs [n, 172544] (packing.pack_resblock48)."""
+
+    def __init__(self, pairs, device):
+        from .packing import pack_resblock48
+        _BlobChain.__init__(self, pairs, device, pack_resblock48, hip.RESBLOCK48_BLOB_BYTES)
 
 
-_RB24_WAVES_SET = False
+_RB24_KNOBS_SET = False
+
+
+def _rb_entry(c, chain, name):
+    """Entry point `name` of the c-channel fused block ('resblock24_chain' ...): for c = 24 the A/B knobs of its workgroup shape
+    (default 8 waves) and output store path (0 | 1, refvsr_set_resblock24_store) are applied before the first call, and a chain of
+    fp16-format blobs goes to the _f16w twin (chain-like objects without a weight format -- torch_ops' blob tables -- are hi + lo)."""
+    global _RB24_KNOBS_SET
+    if c == 24 and not _RB24_KNOBS_SET:
+        _RB24_KNOBS_SET = True
+        if os.environ.get('REFVSR_RESBLOCK24_WAVES'):
+            hip.check(hip.lib().refvsr_set_resblock24_waves(int(os.environ['REFVSR_RESBLOCK24_WAVES'])), 'set_resblock24_waves')
+        if os.environ.get('REFVSR_RB24_STORE'):
+            hip.check(hip.lib().refvsr_set_resblock24_store(int(os.environ['REFVSR_RB24_STORE'])), 'set_resblock24_store')
+    return getattr(hip.lib(), 'refvsr_' + name + ('_f16w' if c == 24 and getattr(chain, 'wfmt', 'hi_lo') == 'fp16' else ''))
+
+
+def _rb_chain(c, chain, x, act):
+    _nhwc(x)
+    h, w, cx = x.shape
+    assert cx == c
+    out = torch.empty_like(x)
+    s0 = torch.empty_like(x) if chain.n >= 2 else None
+    s1 = torch.empty_like(x) if chain.n >= 3 else None
+    name = 'resblock%d_chain' % c
+    hip.check(_rb_entry(c, chain, name)(_ptr(x), h, w, chain.n, _ptr(chain.blobs), chain.stride, act, _ptr(s0), _ptr(s1), _ptr(out), _stream()), name)
+    return out
 
 
 def resblock24_chain(chain, x, act):
     """refvsr_resblock24_chain: chain.n fused 24-channel blocks x <- x + conv2(act(conv1 x)) behind one library call."""
-    global _RB24_WAVES_SET
-    if not _RB24_WAVES_SET:                # A/B knob of the workgroup shape (default 8 waves)
-        _RB24_WAVES_SET = True
-        if os.environ.get('REFVSR_RESBLOCK24_WAVES'):
-            hip.check(hip.lib().refvsr_set_resblock24_waves(int(os.environ['REFVSR_RESBLOCK24_WAVES'])), 'set_resblock24_waves')
-        if os.environ.get('REFVSR_RB24_STORE'):           # A/B knob of the output store path (0 | 1, refvsr_set_resblock24_store)
-            hip.check(hip.lib().refvsr_set_resblock24_store(int(os.environ['REFVSR_RB24_STORE'])), 'set_resblock24_store')
-    _nhwc(x)
-    h, w, c = x.shape
-    assert c == 24
-    out = torch.empty_like(x)
-    s0 = torch.empty_like(x) if chain.n >= 2 else None
-    s1 = torch.empty_like(x) if chain.n >= 3 else None
-    hip.check(_rb24(chain, 'refvsr_resblock24_chain')(_ptr(x), h, w, chain.n, _ptr(chain.blobs), chain.stride, act, _ptr(s0), _ptr(s1),
-                                                _ptr(out), _stream()), 'resblock24_chain')
-    return out
-
-
-class Resblock48Chain(object):
-    """A run of 48-channel fused blocks for refvsr_resblock48_chain: one device buffer [n, 172544] of per-block blobs
-    (packing.pack_resblock48).  pairs: [(conv1, conv2)] ConvWeights whose packer kept the raw fp32 weights, or raw tensors."""
-
-    def __init__(self, pairs, device):
-        from .packing import pack_resblock48
-        blobs = []
-        for a, b in pairs:
-            (w1, b1), (w2, b2) = (a.raw if isinstance(a, ConvWeights) else a), (b.raw if isinstance(b, ConvWeights) else b)
-            blobs.append(pack_resblock48(w1, b1, w2, b2))
-        self.n = len(blobs)
-        self.blobs = torch.stack(blobs, 0).to(device).contiguous()
-        self.stride = self.blobs.shape[1]
-        assert self.stride == hip.RESBLOCK48_BLOB_BYTES and self.blobs.data_ptr() % 16 == 0
+    return _rb_chain(24, chain, x, act)
 
 
 def resblock48_chain(chain, x, act):
     """refvsr_resblock48_chain: chain.n fused 48-channel blocks x <- x + conv2(act(conv1 x)), one launch per block."""
-    _nhwc(x)
-    h, w, c = x.shape
-    assert c == 48
-    out = torch.empty_like(x)
-    s0 = torch.empty_like(x) if chain.n >= 2 else None
-    s1 = torch.empty_like(x) if chain.n >= 3 else None
-    hip.check(hip.lib().refvsr_resblock48_chain(_ptr(x), h, w, chain.n, _ptr(chain.blobs), chain.stride, act, _ptr(s0), _ptr(s1),
-                                                _ptr(out), _stream()), 'resblock48_chain')
-    return out
+    return _rb_chain(48, chain, x, act)
 
 
 def resblock_chain_ok(c):
@@ -1036,13 +1034,16 @@ def multimap_ok(B):
 def _maps(ts, stack):
     """Result of a map-by-map fallback: one [B, ...] tensor like the multi-map launches return (stack: one more copy per map), or
     the list of the B maps as they are (the engine only ever indexes / iterates the result)."""
-    return torch.stack(ts, 0) if stack else list(ts)
+    return torch.stack(ts, 0) if stack else ts
 
 
 def conv_b(cw, src0s, src1s=None, act=1.0, muls=None, ress=None, post=1.0, stack=True):
     """refvsr_conv24_batch / refvsr_conv_shuffle2_batch: conv() over B maps (24 output channels, 3x3, or the C = 24 pixel-shuffle
     conv).  Shapes without a multi-map kernel run map by map (same results; stack=False: returned as a list, no copy)."""
     B = len(src0s)
+    if B == 1:                                       # the single-map op, before anything is spent on the list
+        return _maps([conv(cw, src0s[0], None if src1s is None else src1s[0], act=act, mul=None if muls is None else muls[0],
+                           res=None if ress is None else ress[0], post=post)], stack)
     h, w, c0 = src0s[0].shape
     c1 = src1s[0].shape[2] if src1s is not None else 0
     for l_ in (src0s, src1s, muls, ress):
@@ -1070,39 +1071,31 @@ def conv_b(cw, src0s, src1s=None, act=1.0, muls=None, ress=None, post=1.0, stack
                        res=None if ress is None else ress[b], post=post) for b in range(B)], stack)
 
 
-def resblock24_chain_b(chain, xs, act, stack=True):
-    """refvsr_resblock24_chain_batch: chain.n fused 24-channel blocks over B maps, one launch per block."""
+def _rb_chain_b(c, single, chain, xs, act, stack):
     B = len(xs)
+    if not multimap_ok(B):
+        return _maps([single(chain, x, act) for x in xs], stack)
     for t_ in xs:
         _nhwc(t_)
-        assert tuple(t_.shape) == tuple(xs[0].shape) and t_.shape[2] == 24
-    if not multimap_ok(B):
-        return _maps([resblock24_chain(chain, x, act) for x in xs], stack)
+        assert tuple(t_.shape) == tuple(xs[0].shape) and t_.shape[2] == c
     h, w, _ = xs[0].shape
-    dev = xs[0].device
-    out = torch.empty((B, h, w, 24), dtype=torch.float16, device=dev)
+    out = torch.empty((B, h, w, c), dtype=torch.float16, device=xs[0].device)
     s0 = torch.empty_like(out) if chain.n >= 2 else None
     s1 = torch.empty_like(out) if chain.n >= 3 else None
-    hip.check(_rb24(chain, 'refvsr_resblock24_chain_batch')(_parr(xs), B, h, w, chain.n, _ptr(chain.blobs), chain.stride, act, _ptr(s0), _ptr(s1),
-                                                      _parr(list(out)), _stream()), 'resblock24_chain_batch')
+    name = 'resblock%d_chain_batch' % c
+    hip.check(_rb_entry(c, chain, name)(_parr(xs), B, h, w, chain.n, _ptr(chain.blobs), chain.stride, act, _ptr(s0), _ptr(s1),
+                                        _parr(list(out)), _stream()), name)
     return out
+
+
+def resblock24_chain_b(chain, xs, act, stack=True):
+    """refvsr_resblock24_chain_batch: chain.n fused 24-channel blocks over B maps, one launch per block."""
+    return _rb_chain_b(24, resblock24_chain, chain, xs, act, stack)
 
 
 def resblock48_chain_b(chain, xs, act, stack=True):
     """refvsr_resblock48_chain_batch (ABI 12): chain.n fused 48-channel blocks over B maps, one launch per block."""
-    B = len(xs)
-    for t_ in xs:
-        _nhwc(t_)
-        assert tuple(t_.shape) == tuple(xs[0].shape) and t_.shape[2] == 48
-    if not multimap_ok(B):
-        return _maps([resblock48_chain(chain, x, act) for x in xs], stack)
-    h, w, _ = xs[0].shape
-    out = torch.empty((B, h, w, 48), dtype=torch.float16, device=xs[0].device)
-    s0 = torch.empty_like(out) if chain.n >= 2 else None
-    s1 = torch.empty_like(out) if chain.n >= 3 else None
-    hip.check(hip.lib().refvsr_resblock48_chain_batch(_parr(xs), B, h, w, chain.n, _ptr(chain.blobs), chain.stride, act, _ptr(s0), _ptr(s1),
-                                                      _parr(list(out)), _stream()), 'resblock48_chain_batch')
-    return out
+    return _rb_chain_b(48, resblock48_chain, chain, xs, act, stack)
 
 
 def conf_alpha_b(conf_as, conf_bs, up, w0, b0, cw, slope0=0.2, slope1=0.2, want_max=False, stack=True):
@@ -1128,51 +1121,33 @@ def conf_alpha_b(conf_as, conf_bs, up, w0, b0, cw, slope0=0.2, slope1=0.2, want_
     return (alpha, cmax) if want_max else alpha
 
 
-def _warp_b(fn, name, xs, flows, out, dims):
-    hip.check(fn(_parr(xs), len(xs), *dims[0], _parr(flows), *dims[1], _parr(list(out)), _stream()), name)
+def _warp_b(single, name, check, out_shape, xs, flows, stack):
+    """refvsr_<name>_batch: the warp `single` over B maps.  check: the maps' layout check; out_shape(map shape, hf, wf): one result."""
+    B = len(xs)
+    if not multimap_ok(B):
+        return _maps([single(x, f) for x, f in zip(xs, flows)], stack)
+    for x, f in zip(xs, flows):
+        check(x)
+        _planar(f, 2)
+        assert x.shape == xs[0].shape and f.shape == flows[0].shape
+    hf, wf = flows[0].shape[1:]
+    out = torch.empty((B,) + out_shape(xs[0].shape, hf, wf), dtype=xs[0].dtype, device=xs[0].device)
+    # (the maps' three extents go as they lie: hin, win, cs of an nhwc16 map, c, hin, win of a planar one)
+    hip.check(getattr(hip.lib(), 'refvsr_%s_batch' % name)(_parr(xs), B, *xs[0].shape, _parr(flows), hf, wf, _parr(list(out)), _stream()),
+              name + '_batch')
     return out
 
 
 def warp_nhwc16_b(xs, flows, stack=True):
-    B = len(xs)
-    if not multimap_ok(B):
-        return _maps([warp_nhwc16(x, f) for x, f in zip(xs, flows)], stack)
-    for x, f in zip(xs, flows):
-        _nhwc(x)
-        _planar(f, 2)
-        assert x.shape == xs[0].shape and f.shape == flows[0].shape
-    hin, win, cs = xs[0].shape
-    hf, wf = flows[0].shape[1:]
-    out = torch.empty((B, hf, wf, cs), dtype=torch.float16, device=xs[0].device)
-    return _warp_b(hip.lib().refvsr_warp_nhwc16_batch, 'warp_nhwc16_batch', xs, flows, out, ((hin, win, cs), (hf, wf)))
+    return _warp_b(warp_nhwc16, 'warp_nhwc16', _nhwc, lambda s, hf, wf: (hf, wf, s[2]), xs, flows, stack)
 
 
 def warp_nhwc16_up2_b(xs, flows_lr, stack=True):
-    B = len(xs)
-    if not multimap_ok(B):
-        return _maps([warp_nhwc16_up2(x, f) for x, f in zip(xs, flows_lr)], stack)
-    for x, f in zip(xs, flows_lr):
-        _nhwc(x)
-        _planar(f, 2)
-        assert x.shape == xs[0].shape and f.shape == flows_lr[0].shape
-    hin, win, cs = xs[0].shape
-    hl, wl = flows_lr[0].shape[1:]
-    out = torch.empty((B, 2 * hl, 2 * wl, cs), dtype=torch.float16, device=xs[0].device)
-    return _warp_b(hip.lib().refvsr_warp_nhwc16_up2_batch, 'warp_nhwc16_up2_batch', xs, flows_lr, out, ((hin, win, cs), (hl, wl)))
+    return _warp_b(warp_nhwc16_up2, 'warp_nhwc16_up2', _nhwc, lambda s, hl, wl: (2 * hl, 2 * wl, s[2]), xs, flows_lr, stack)
 
 
 def warp_planar_b(xs, flows, stack=True):
-    B = len(xs)
-    if not multimap_ok(B):
-        return _maps([warp_planar(x, f) for x, f in zip(xs, flows)], stack)
-    for x, f in zip(xs, flows):
-        _planar(x)
-        _planar(f, 2)
-        assert x.shape == xs[0].shape and f.shape == flows[0].shape
-    c, hin, win = xs[0].shape
-    hf, wf = flows[0].shape[1:]
-    out = torch.empty((B, c, hf, wf), dtype=torch.float32, device=xs[0].device)
-    return _warp_b(hip.lib().refvsr_warp_planar_batch, 'warp_planar_batch', xs, flows, out, ((c, hin, win), (hf, wf)))
+    return _warp_b(warp_planar, 'warp_planar', _planar, lambda s, hf, wf: (s[0], hf, wf), xs, flows, stack)
 
 
 # ---- RefVSR_IR / EDVR-M pieces (csrc/edvr.hip) -------------------------------------------------------------------------

@@ -331,7 +331,7 @@ def test_block_chain_applies_blocks_in_order(monkeypatch):
     monkeypatch.setattr(ops, 'conv', lambda cw, x, act=1.0, res=None: X(x.shape, x.hist + ((cw, act, res is not None),)))
 
     class E(object):
-        _block_chain = engine.Engine._block_chain
+        _block_chain, _block_chain_b, _chain = engine.Engine._block_chain, engine.Engine._block_chain_b, engine.Engine._chain
         fuse_resblocks = True
         rb24 = False                             # the generic kernels (the 24-channel kernel is dispatched below)
         rb48, rb48_max_pixels = False, 0         # (the fused 48-channel block has its own dispatch test on the GPU)
@@ -367,6 +367,335 @@ def test_block_chain_applies_blocks_in_order(monkeypatch):
     e.fuse_resblocks = False
     want = tuple(x for a, b in pairs for x in ((a, 0.0, False), (b, 1.0, True)))
     assert e._block_chain(X((270, 480, 24)), pairs, 0.0).hist == want
+
+
+def _prop_trace(monkeypatch, case):
+    """The launches of Engine._prop_step / Engine._backward_chains in one configuration, on stand-in maps: one line
+    'op weight scalars <- input maps' per ops call.  A map is named after the line that produced it (m<line>), so the trace also
+    pins which map goes where; [a|b]: the B maps of one multi-map launch."""
+    from refvsr_amd import engine, ops
+    trace = []
+    h, w = 4, 6
+
+    class M(object):                               # a stand-in map: a name and a shape
+        device = 'dev'
+
+        def __init__(self, name, shape):
+            self.name, self.shape = name, tuple(shape)
+
+    CW = collections.namedtuple('CW', 'name raw')
+
+    def one(x):
+        return x[0] if isinstance(x, list) else x
+
+    def rec(op, weight, maps, shapes, **scalars):
+        """One launch over `maps` (lists: a multi-map launch); returns one stand-in (or list of B) per entry of `shapes`."""
+        k, B = len(trace), max([len(m) for m in maps if isinstance(m, list)] or [0])
+        names = ['-' if m is None else '[%s]' % '|'.join(x.name for x in m) if B else m.name for m in maps]
+        trace.append(' '.join([op, weight] + ['%s=%s' % kv for kv in sorted(scalars.items())] + ['<-'] + names))
+        tags = ['m%d%s' % (k, 'ab'[j] if len(shapes) > 1 else '') for j in range(len(shapes))]
+        outs = [[M('%s.%d' % (t, b), s) for b in range(B)] if B else M(t, s) for t, s in zip(tags, shapes)]
+        return outs if len(outs) > 1 else outs[0]
+
+    def conv_shape(cw, s0):
+        return ((2, 2, 1) if cw.name.endswith('upsample_conv') else (1, 1, 1), one(s0).shape[:2] + (24,))
+
+    def scaled(f, s):
+        return tuple(a * b for a, b in zip(f, s))
+
+    def conv(cw, src0, src1=None, act=1.0, mul=None, res=None, post=1.0):
+        return rec('conv', cw.name, [src0, src1, mul, res], [scaled(*conv_shape(cw, src0))], act=act, post=post)
+
+    def conv_b(cw, src0s, src1s=None, act=1.0, muls=None, ress=None, post=1.0, stack=True):
+        return rec('conv_b', cw.name, [src0s, src1s, muls, ress], [scaled(*conv_shape(cw, src0s))], act=act, post=post, stack=stack)
+
+    def conf_shapes(a, up, want_max):
+        _, h_, w_ = one(a).shape
+        return [(up * h_, up * w_, 24)] + ([one(a).shape] if want_max else [])
+
+    def conf_alpha(a, b, up, w0, b0, cw, slope0=0.2, slope1=0.2, want_max=False):
+        return rec('conf_alpha', w0 + '+' + cw.name, [a, b], conf_shapes(a, up, want_max), up=up, want_max=want_max)
+
+    def conf_alpha_b(a, b, up, w0, b0, cw, slope0=0.2, slope1=0.2, want_max=False, stack=True):
+        return rec('conf_alpha_b', w0 + '+' + cw.name, [a, b], conf_shapes(a, up, want_max), up=up, want_max=want_max, stack=stack)
+
+    def warp_shape(x, fl, up):
+        s, (_, hf, wf) = one(x).shape, one(fl).shape
+        return (s[0], up * hf, up * wf) if s[0] <= 2 else (up * hf, up * wf, s[2])       # planar [c,h,w] | nhwc16 [h,w,cs]
+
+    stubs = dict(
+        conv=conv, conv_b=conv_b, conf_alpha=conf_alpha, conf_alpha_b=conf_alpha_b, conf_alpha_ok=lambda cw: True,
+        conv_direct=lambda x, w_, b, act=1.0, nhwc16_out=False: rec('conv_direct', w_, [x], [x.shape[1:] + (16,)], act=act, nhwc16_out=nhwc16_out),
+        bicubic_scale=lambda x, f, clamp01=True: rec('bicubic_scale', '-', [x], [scaled((1, f, f), x.shape)], clamp01=clamp01, factor=f),
+        max2=lambda a, b: rec('max2', '-', [a, b], [a.shape]),
+        flow_up2=lambda fl: rec('flow_up2', '-', [fl], [scaled((1, 2, 2), fl.shape)]),
+        Resblock24Chain=lambda pairs, dev: CW('%s..%s' % (pairs[0][0].name, pairs[-1][1].name), None),
+        resblock24_chain=lambda ch, x, act: rec('resblock24_chain', ch.name, [x], [x.shape], act=act),
+        resblock24_chain_b=lambda ch, xs, act, stack=True: rec('resblock24_chain_b', ch.name, [xs], [xs[0].shape], act=act, stack=stack))
+    for name, up in (('warp_planar', 1), ('warp_nhwc16', 1), ('warp_nhwc16_up2', 2)):
+        stubs[name] = lambda x, fl, name=name, up=up: rec(name, '-', [x, fl], [warp_shape(x, fl, up)])
+        stubs[name + '_b'] = lambda xs, fls, stack=True, name=name, up=up: rec(name + '_b', '-', [xs, fls], [warp_shape(xs, fls, up)], stack=stack)
+
+    def list_op(real, stub):
+        # a list of ONE map goes through the real wrapper, which has to hand the map to the single-map op (the stub of that name)
+        # before it looks at anything else: the B = 1 trace is the single-map launch list
+        return lambda *a, **k: (real if len(next(x for x in a if isinstance(x, list))) == 1 else stub)(*a, **k)
+    for name, stub in stubs.items():
+        monkeypatch.setattr(ops, name, list_op(getattr(ops, name), stub) if name.endswith('_b') else stub)
+    cat = torch.cat
+    monkeypatch.setattr(torch, 'cat', lambda ts, dim=0: rec('cat', '-', list(ts), [(len(ts),) + ts[0].shape[1:]]) if isinstance(ts[0], M)
+                        else cat(ts, dim))
+
+    class Named(dict):                             # weights by name: whatever is asked for exists
+        def __init__(self, make):
+            self.make = make
+
+        def __missing__(self, name):
+            return self.make(name)
+
+    e = engine.Engine.__new__(engine.Engine)
+    e.W = type('W', (), dict(chains={}, conv=Named(lambda n: CW(n, ('w', 'b'))), raw=Named(lambda n: (n, n + '.bias'))))()
+    e.C, e.nb = 24, 2
+    e.fuse_resblocks, e.rb24, e.rb48, e.rb48_max_pixels, e.rb48_multimap, e.chain_calls, e.chain_events = True, True, False, 0, True, False, None
+    e.fuse_conf, e.warp_up2 = case != 'fuse_conf off', case != 'warp_up2 off'
+    e._zeros = lambda shape, dtype, dev: M('zeros%d' % shape[-2], shape)
+    e.fw_feat_up = e._fw_up_wait = None
+
+    def frame(tag):
+        f = type('F', (), dict(bw_head=None, ready=None))()
+        f.lr, f.lr8, f.conf = M('lr' + tag, (3, h, w)), M('lr8' + tag, (h, w, 8)), M('conf' + tag, (1, h, w))
+        f.aligned, f.aligned_up = M('aligned' + tag, (h, w, 24)), M('aligned_up' + tag, (2 * h, 2 * w, 24))
+        return f
+    B = 2 if case.startswith('B=2') else 1
+    fs = [frame('.%d' % b) for b in range(B)]
+    feats, ups = [M('feat.%d' % b, (h, w, 24)) for b in range(B)], [M('feat_up.%d' % b, (2 * h, 2 * w, 24)) for b in range(B)]
+    confs, fls = [M('conf_prop.%d' % b, (1, h, w)) for b in range(B)], [M('flow.%d' % b, (2, h, w)) for b in range(B)]
+    if case in ('fused', 'B=2 fused'):             # the backward walk of a window of three frames: the first step and one warped step
+        frs = [[frame('.%d.%d' % (b, i)) for i in range(3)] for b in range(B)]
+        outs = e._backward_chains(frs, lambda b, i: M('flow.%d.%d' % (b, i), (2, h, w)))
+    elif case == 'up_from_lr':
+        outs = e._prop_step(fs, 'forward_resblocks', feats, None, confs, fls, up_from_lr=True)
+    elif case in ('first step', 'bw_head', 'B=2 bw_head', 'B=2 one bw_head'):
+        for f in fs[:1 if case == 'B=2 one bw_head' else B if 'bw_head' in case else 0]:
+            f.bw_head = (1, M(f.lr.name.replace('lr', 'head'), (h, w, 24)))
+        outs = e._prop_step(fs, 'backward_resblocks', feats, ups, confs, None)
+    else:                                          # one warped step; 'steady': the carried 2x state of a split hand-off is awaited
+        if case == 'steady':
+            e.fw_feat_up, e._fw_up_wait = ups[0], lambda: trace.append('await fw_feat_up')
+        outs = e._prop_step(fs, 'forward_resblocks', feats, ups, confs, fls)
+    assert all(isinstance(o, list) and len(o) == B and all(isinstance(m, M) for m in o) for o in outs)
+    return trace + ['-> ' + ' '.join('[%s]' % '|'.join(m.name for m in o) for o in outs)]
+
+
+# recorded with the stubs above from the single-map (B = 1) and the B-map (B = 2) copy of the layers that this form replaced
+_PROP_TRACES = {'fused': ['conv backward_resblocks.main.0 act=0.1 post=1.0 <- lr8.0.2 zeros6 - -',
+           'resblock24_chain backward_resblocks.main.2.0.conv1..backward_resblocks.main.2.1.conv2 act=0.0 <- m0',
+           'conf_alpha conf_fusion.0.0+conf_fusion.1.0 up=1 want_max=True <- zeros4 conf.0.2',
+           'conv feat_fusion.0.0 act=0.2 post=1.0 <- m1 aligned.0.2 - -',
+           'conv feat_fusion.1.0 act=0.2 post=1.0 <- m3 - m2a m1',
+           'resblock24_chain feat_decoder.RBs.0.conv1..feat_decoder.RBs.7.conv2 act=0.2 <- m4',
+           'conv feat_decoder.conv_tail act=1.0 post=1.0 <- m5 - - m4',
+           'conv upsample1.upsample_conv act=1.0 post=1.0 <- m6 - - -',
+           'conv feat_fusion2_1.0.0 act=0.2 post=1.0 <- zeros12 m7 - -',
+           'conf_alpha conf_fusion2.0.0+conf_fusion2.1.0 up=2 want_max=False <- zeros4 conf.0.2',
+           'conv feat_fusion2.0.0 act=0.2 post=1.0 <- m8 aligned_up.0.2 - -',
+           'conv feat_fusion2.1.0 act=0.2 post=1.0 <- m10 - m9 m8',
+           'resblock24_chain feat_decoder2.RBs.0.conv1..feat_decoder2.RBs.3.conv2 act=0.2 <- m11',
+           'conv feat_decoder2.conv_tail act=1.0 post=1.0 <- m12 - - m11',
+           'warp_planar - <- m2b flow.0.1',
+           'warp_nhwc16 - <- m6 flow.0.1',
+           'conv backward_resblocks.main.0 act=0.1 post=1.0 <- lr8.0.1 m15 - -',
+           'resblock24_chain backward_resblocks.main.2.0.conv1..backward_resblocks.main.2.1.conv2 act=0.0 <- m16',
+           'warp_nhwc16_up2 - <- m13 flow.0.1',
+           'conf_alpha conf_fusion.0.0+conf_fusion.1.0 up=1 want_max=True <- m14 conf.0.1',
+           'conv feat_fusion.0.0 act=0.2 post=1.0 <- m17 aligned.0.1 - -',
+           'conv feat_fusion.1.0 act=0.2 post=1.0 <- m20 - m19a m17',
+           'resblock24_chain feat_decoder.RBs.0.conv1..feat_decoder.RBs.7.conv2 act=0.2 <- m21',
+           'conv feat_decoder.conv_tail act=1.0 post=1.0 <- m22 - - m21',
+           'conv upsample1.upsample_conv act=1.0 post=1.0 <- m23 - - -',
+           'conv feat_fusion2_1.0.0 act=0.2 post=1.0 <- m18 m24 - -',
+           'conf_alpha conf_fusion2.0.0+conf_fusion2.1.0 up=2 want_max=False <- m14 conf.0.1',
+           'conv feat_fusion2.0.0 act=0.2 post=1.0 <- m25 aligned_up.0.1 - -',
+           'conv feat_fusion2.1.0 act=0.2 post=1.0 <- m27 - m26 m25',
+           'resblock24_chain feat_decoder2.RBs.0.conv1..feat_decoder2.RBs.3.conv2 act=0.2 <- m28',
+           'conv feat_decoder2.conv_tail act=1.0 post=1.0 <- m29 - - m28',
+           '-> [m30] [m19b]'],
+ 'fuse_conf off': ['warp_planar - <- conf_prop.0 flow.0',
+                   'warp_nhwc16 - <- feat.0 flow.0',
+                   'conv forward_resblocks.main.0 act=0.1 post=1.0 <- lr8.0 m1 - -',
+                   'resblock24_chain forward_resblocks.main.2.0.conv1..forward_resblocks.main.2.1.conv2 act=0.0 <- m2',
+                   'warp_nhwc16_up2 - <- feat_up.0 flow.0',
+                   'cat - <- m0 conf.0',
+                   'conv_direct conf_fusion.0.0 act=0.2 nhwc16_out=True <- m5',
+                   'conv conf_fusion.1.0 act=0.2 post=1.0 <- m6 - - -',
+                   'conv feat_fusion.0.0 act=0.2 post=1.0 <- m3 aligned.0 - -',
+                   'conv feat_fusion.1.0 act=0.2 post=1.0 <- m8 - m7 m3',
+                   'resblock24_chain feat_decoder.RBs.0.conv1..feat_decoder.RBs.7.conv2 act=0.2 <- m9',
+                   'conv feat_decoder.conv_tail act=1.0 post=1.0 <- m10 - - m9',
+                   'conv upsample1.upsample_conv act=1.0 post=1.0 <- m11 - - -',
+                   'conv feat_fusion2_1.0.0 act=0.2 post=1.0 <- m4 m12 - -',
+                   'bicubic_scale - clamp01=True factor=2 <- m5',
+                   'conv_direct conf_fusion2.0.0 act=0.2 nhwc16_out=True <- m14',
+                   'conv conf_fusion2.1.0 act=0.2 post=1.0 <- m15 - - -',
+                   'conv feat_fusion2.0.0 act=0.2 post=1.0 <- m13 aligned_up.0 - -',
+                   'conv feat_fusion2.1.0 act=0.2 post=1.0 <- m17 - m16 m13',
+                   'resblock24_chain feat_decoder2.RBs.0.conv1..feat_decoder2.RBs.3.conv2 act=0.2 <- m18',
+                   'conv feat_decoder2.conv_tail act=1.0 post=1.0 <- m19 - - m18',
+                   'max2 - <- m0 conf.0',
+                   '-> [m11] [m20] [m21]'],
+ 'warp_up2 off': ['warp_planar - <- conf_prop.0 flow.0',
+                  'warp_nhwc16 - <- feat.0 flow.0',
+                  'conv forward_resblocks.main.0 act=0.1 post=1.0 <- lr8.0 m1 - -',
+                  'resblock24_chain forward_resblocks.main.2.0.conv1..forward_resblocks.main.2.1.conv2 act=0.0 <- m2',
+                  'flow_up2 - <- flow.0',
+                  'warp_nhwc16 - <- feat_up.0 m4',
+                  'conf_alpha conf_fusion.0.0+conf_fusion.1.0 up=1 want_max=True <- m0 conf.0',
+                  'conv feat_fusion.0.0 act=0.2 post=1.0 <- m3 aligned.0 - -',
+                  'conv feat_fusion.1.0 act=0.2 post=1.0 <- m7 - m6a m3',
+                  'resblock24_chain feat_decoder.RBs.0.conv1..feat_decoder.RBs.7.conv2 act=0.2 <- m8',
+                  'conv feat_decoder.conv_tail act=1.0 post=1.0 <- m9 - - m8',
+                  'conv upsample1.upsample_conv act=1.0 post=1.0 <- m10 - - -',
+                  'conv feat_fusion2_1.0.0 act=0.2 post=1.0 <- m5 m11 - -',
+                  'conf_alpha conf_fusion2.0.0+conf_fusion2.1.0 up=2 want_max=False <- m0 conf.0',
+                  'conv feat_fusion2.0.0 act=0.2 post=1.0 <- m12 aligned_up.0 - -',
+                  'conv feat_fusion2.1.0 act=0.2 post=1.0 <- m14 - m13 m12',
+                  'resblock24_chain feat_decoder2.RBs.0.conv1..feat_decoder2.RBs.3.conv2 act=0.2 <- m15',
+                  'conv feat_decoder2.conv_tail act=1.0 post=1.0 <- m16 - - m15',
+                  '-> [m10] [m17] [m6b]'],
+ 'up_from_lr': ['warp_planar - <- conf_prop.0 flow.0',
+                'warp_nhwc16 - <- feat.0 flow.0',
+                'conv forward_resblocks.main.0 act=0.1 post=1.0 <- lr8.0 m1 - -',
+                'resblock24_chain forward_resblocks.main.2.0.conv1..forward_resblocks.main.2.1.conv2 act=0.0 <- m2',
+                'warp_nhwc16_up2 - <- m1 flow.0',
+                'conf_alpha conf_fusion.0.0+conf_fusion.1.0 up=1 want_max=True <- m0 conf.0',
+                'conv feat_fusion.0.0 act=0.2 post=1.0 <- m3 aligned.0 - -',
+                'conv feat_fusion.1.0 act=0.2 post=1.0 <- m6 - m5a m3',
+                'resblock24_chain feat_decoder.RBs.0.conv1..feat_decoder.RBs.7.conv2 act=0.2 <- m7',
+                'conv feat_decoder.conv_tail act=1.0 post=1.0 <- m8 - - m7',
+                'conv upsample1.upsample_conv act=1.0 post=1.0 <- m9 - - -',
+                'conv feat_fusion2_1.0.0 act=0.2 post=1.0 <- m4 m10 - -',
+                'conf_alpha conf_fusion2.0.0+conf_fusion2.1.0 up=2 want_max=False <- m0 conf.0',
+                'conv feat_fusion2.0.0 act=0.2 post=1.0 <- m11 aligned_up.0 - -',
+                'conv feat_fusion2.1.0 act=0.2 post=1.0 <- m13 - m12 m11',
+                'resblock24_chain feat_decoder2.RBs.0.conv1..feat_decoder2.RBs.3.conv2 act=0.2 <- m14',
+                'conv feat_decoder2.conv_tail act=1.0 post=1.0 <- m15 - - m14',
+                '-> [m9] [m16] [m5b]'],
+ 'bw_head': ['resblock24_chain backward_resblocks.main.2.1.conv1..backward_resblocks.main.2.1.conv2 act=0.0 <- head.0',
+             'conf_alpha conf_fusion.0.0+conf_fusion.1.0 up=1 want_max=True <- conf_prop.0 conf.0',
+             'conv feat_fusion.0.0 act=0.2 post=1.0 <- m0 aligned.0 - -',
+             'conv feat_fusion.1.0 act=0.2 post=1.0 <- m2 - m1a m0',
+             'resblock24_chain feat_decoder.RBs.0.conv1..feat_decoder.RBs.7.conv2 act=0.2 <- m3',
+             'conv feat_decoder.conv_tail act=1.0 post=1.0 <- m4 - - m3',
+             'conv upsample1.upsample_conv act=1.0 post=1.0 <- m5 - - -',
+             'conv feat_fusion2_1.0.0 act=0.2 post=1.0 <- feat_up.0 m6 - -',
+             'conf_alpha conf_fusion2.0.0+conf_fusion2.1.0 up=2 want_max=False <- conf_prop.0 conf.0',
+             'conv feat_fusion2.0.0 act=0.2 post=1.0 <- m7 aligned_up.0 - -',
+             'conv feat_fusion2.1.0 act=0.2 post=1.0 <- m9 - m8 m7',
+             'resblock24_chain feat_decoder2.RBs.0.conv1..feat_decoder2.RBs.3.conv2 act=0.2 <- m10',
+             'conv feat_decoder2.conv_tail act=1.0 post=1.0 <- m11 - - m10',
+             '-> [m5] [m12] [m1b]'],
+ 'first step': ['conv backward_resblocks.main.0 act=0.1 post=1.0 <- lr8.0 feat.0 - -',
+                'resblock24_chain backward_resblocks.main.2.0.conv1..backward_resblocks.main.2.1.conv2 act=0.0 <- m0',
+                'conf_alpha conf_fusion.0.0+conf_fusion.1.0 up=1 want_max=True <- conf_prop.0 conf.0',
+                'conv feat_fusion.0.0 act=0.2 post=1.0 <- m1 aligned.0 - -',
+                'conv feat_fusion.1.0 act=0.2 post=1.0 <- m3 - m2a m1',
+                'resblock24_chain feat_decoder.RBs.0.conv1..feat_decoder.RBs.7.conv2 act=0.2 <- m4',
+                'conv feat_decoder.conv_tail act=1.0 post=1.0 <- m5 - - m4',
+                'conv upsample1.upsample_conv act=1.0 post=1.0 <- m6 - - -',
+                'conv feat_fusion2_1.0.0 act=0.2 post=1.0 <- feat_up.0 m7 - -',
+                'conf_alpha conf_fusion2.0.0+conf_fusion2.1.0 up=2 want_max=False <- conf_prop.0 conf.0',
+                'conv feat_fusion2.0.0 act=0.2 post=1.0 <- m8 aligned_up.0 - -',
+                'conv feat_fusion2.1.0 act=0.2 post=1.0 <- m10 - m9 m8',
+                'resblock24_chain feat_decoder2.RBs.0.conv1..feat_decoder2.RBs.3.conv2 act=0.2 <- m11',
+                'conv feat_decoder2.conv_tail act=1.0 post=1.0 <- m12 - - m11',
+                '-> [m6] [m13] [m2b]'],
+ 'steady': ['warp_planar - <- conf_prop.0 flow.0',
+            'warp_nhwc16 - <- feat.0 flow.0',
+            'conv forward_resblocks.main.0 act=0.1 post=1.0 <- lr8.0 m1 - -',
+            'resblock24_chain forward_resblocks.main.2.0.conv1..forward_resblocks.main.2.1.conv2 act=0.0 <- m2',
+            'await fw_feat_up',
+            'warp_nhwc16_up2 - <- feat_up.0 flow.0',
+            'conf_alpha conf_fusion.0.0+conf_fusion.1.0 up=1 want_max=True <- m0 conf.0',
+            'conv feat_fusion.0.0 act=0.2 post=1.0 <- m3 aligned.0 - -',
+            'conv feat_fusion.1.0 act=0.2 post=1.0 <- m7 - m6a m3',
+            'resblock24_chain feat_decoder.RBs.0.conv1..feat_decoder.RBs.7.conv2 act=0.2 <- m8',
+            'conv feat_decoder.conv_tail act=1.0 post=1.0 <- m9 - - m8',
+            'conv upsample1.upsample_conv act=1.0 post=1.0 <- m10 - - -',
+            'conv feat_fusion2_1.0.0 act=0.2 post=1.0 <- m5 m11 - -',
+            'conf_alpha conf_fusion2.0.0+conf_fusion2.1.0 up=2 want_max=False <- m0 conf.0',
+            'conv feat_fusion2.0.0 act=0.2 post=1.0 <- m12 aligned_up.0 - -',
+            'conv feat_fusion2.1.0 act=0.2 post=1.0 <- m14 - m13 m12',
+            'resblock24_chain feat_decoder2.RBs.0.conv1..feat_decoder2.RBs.3.conv2 act=0.2 <- m15',
+            'conv feat_decoder2.conv_tail act=1.0 post=1.0 <- m16 - - m15',
+            '-> [m10] [m17] [m6b]'],
+ 'B=2 fused': ['conv_b backward_resblocks.main.0 act=0.1 post=1.0 stack=False <- [lr8.0.2|lr8.1.2] [zeros6|zeros6] - -',
+               'resblock24_chain_b backward_resblocks.main.2.0.conv1..backward_resblocks.main.2.1.conv2 act=0.0 stack=False <- [m0.0|m0.1]',
+               'conf_alpha_b conf_fusion.0.0+conf_fusion.1.0 stack=False up=1 want_max=True <- [zeros4|zeros4] [conf.0.2|conf.1.2]',
+               'conv_b feat_fusion.0.0 act=0.2 post=1.0 stack=False <- [m1.0|m1.1] [aligned.0.2|aligned.1.2] - -',
+               'conv_b feat_fusion.1.0 act=0.2 post=1.0 stack=False <- [m3.0|m3.1] - [m2a.0|m2a.1] [m1.0|m1.1]',
+               'resblock24_chain_b feat_decoder.RBs.0.conv1..feat_decoder.RBs.7.conv2 act=0.2 stack=False <- [m4.0|m4.1]',
+               'conv_b feat_decoder.conv_tail act=1.0 post=1.0 stack=False <- [m5.0|m5.1] - - [m4.0|m4.1]',
+               'conv_b upsample1.upsample_conv act=1.0 post=1.0 stack=False <- [m6.0|m6.1] - - -',
+               'conv_b feat_fusion2_1.0.0 act=0.2 post=1.0 stack=False <- [zeros12|zeros12] [m7.0|m7.1] - -',
+               'conf_alpha_b conf_fusion2.0.0+conf_fusion2.1.0 stack=False up=2 want_max=False <- [zeros4|zeros4] [conf.0.2|conf.1.2]',
+               'conv_b feat_fusion2.0.0 act=0.2 post=1.0 stack=False <- [m8.0|m8.1] [aligned_up.0.2|aligned_up.1.2] - -',
+               'conv_b feat_fusion2.1.0 act=0.2 post=1.0 stack=False <- [m10.0|m10.1] - [m9.0|m9.1] [m8.0|m8.1]',
+               'resblock24_chain_b feat_decoder2.RBs.0.conv1..feat_decoder2.RBs.3.conv2 act=0.2 stack=False <- [m11.0|m11.1]',
+               'conv_b feat_decoder2.conv_tail act=1.0 post=1.0 stack=False <- [m12.0|m12.1] - - [m11.0|m11.1]',
+               'warp_planar_b - stack=False <- [m2b.0|m2b.1] [flow.0.1|flow.1.1]',
+               'warp_nhwc16_b - stack=False <- [m6.0|m6.1] [flow.0.1|flow.1.1]',
+               'conv_b backward_resblocks.main.0 act=0.1 post=1.0 stack=False <- [lr8.0.1|lr8.1.1] [m15.0|m15.1] - -',
+               'resblock24_chain_b backward_resblocks.main.2.0.conv1..backward_resblocks.main.2.1.conv2 act=0.0 stack=False <- [m16.0|m16.1]',
+               'warp_nhwc16_up2_b - stack=False <- [m13.0|m13.1] [flow.0.1|flow.1.1]',
+               'conf_alpha_b conf_fusion.0.0+conf_fusion.1.0 stack=False up=1 want_max=True <- [m14.0|m14.1] [conf.0.1|conf.1.1]',
+               'conv_b feat_fusion.0.0 act=0.2 post=1.0 stack=False <- [m17.0|m17.1] [aligned.0.1|aligned.1.1] - -',
+               'conv_b feat_fusion.1.0 act=0.2 post=1.0 stack=False <- [m20.0|m20.1] - [m19a.0|m19a.1] [m17.0|m17.1]',
+               'resblock24_chain_b feat_decoder.RBs.0.conv1..feat_decoder.RBs.7.conv2 act=0.2 stack=False <- [m21.0|m21.1]',
+               'conv_b feat_decoder.conv_tail act=1.0 post=1.0 stack=False <- [m22.0|m22.1] - - [m21.0|m21.1]',
+               'conv_b upsample1.upsample_conv act=1.0 post=1.0 stack=False <- [m23.0|m23.1] - - -',
+               'conv_b feat_fusion2_1.0.0 act=0.2 post=1.0 stack=False <- [m18.0|m18.1] [m24.0|m24.1] - -',
+               'conf_alpha_b conf_fusion2.0.0+conf_fusion2.1.0 stack=False up=2 want_max=False <- [m14.0|m14.1] [conf.0.1|conf.1.1]',
+               'conv_b feat_fusion2.0.0 act=0.2 post=1.0 stack=False <- [m25.0|m25.1] [aligned_up.0.1|aligned_up.1.1] - -',
+               'conv_b feat_fusion2.1.0 act=0.2 post=1.0 stack=False <- [m27.0|m27.1] - [m26.0|m26.1] [m25.0|m25.1]',
+               'resblock24_chain_b feat_decoder2.RBs.0.conv1..feat_decoder2.RBs.3.conv2 act=0.2 stack=False <- [m28.0|m28.1]',
+               'conv_b feat_decoder2.conv_tail act=1.0 post=1.0 stack=False <- [m29.0|m29.1] - - [m28.0|m28.1]',
+               '-> [m30.0|m30.1] [m19b.0|m19b.1]'],
+ 'B=2 bw_head': ['resblock24_chain_b backward_resblocks.main.2.1.conv1..backward_resblocks.main.2.1.conv2 act=0.0 stack=False <- [head.0|head.1]',
+                 'conf_alpha_b conf_fusion.0.0+conf_fusion.1.0 stack=False up=1 want_max=True <- [conf_prop.0|conf_prop.1] [conf.0|conf.1]',
+                 'conv_b feat_fusion.0.0 act=0.2 post=1.0 stack=False <- [m0.0|m0.1] [aligned.0|aligned.1] - -',
+                 'conv_b feat_fusion.1.0 act=0.2 post=1.0 stack=False <- [m2.0|m2.1] - [m1a.0|m1a.1] [m0.0|m0.1]',
+                 'resblock24_chain_b feat_decoder.RBs.0.conv1..feat_decoder.RBs.7.conv2 act=0.2 stack=False <- [m3.0|m3.1]',
+                 'conv_b feat_decoder.conv_tail act=1.0 post=1.0 stack=False <- [m4.0|m4.1] - - [m3.0|m3.1]',
+                 'conv_b upsample1.upsample_conv act=1.0 post=1.0 stack=False <- [m5.0|m5.1] - - -',
+                 'conv_b feat_fusion2_1.0.0 act=0.2 post=1.0 stack=False <- [feat_up.0|feat_up.1] [m6.0|m6.1] - -',
+                 'conf_alpha_b conf_fusion2.0.0+conf_fusion2.1.0 stack=False up=2 want_max=False <- [conf_prop.0|conf_prop.1] [conf.0|conf.1]',
+                 'conv_b feat_fusion2.0.0 act=0.2 post=1.0 stack=False <- [m7.0|m7.1] [aligned_up.0|aligned_up.1] - -',
+                 'conv_b feat_fusion2.1.0 act=0.2 post=1.0 stack=False <- [m9.0|m9.1] - [m8.0|m8.1] [m7.0|m7.1]',
+                 'resblock24_chain_b feat_decoder2.RBs.0.conv1..feat_decoder2.RBs.3.conv2 act=0.2 stack=False <- [m10.0|m10.1]',
+                 'conv_b feat_decoder2.conv_tail act=1.0 post=1.0 stack=False <- [m11.0|m11.1] - - [m10.0|m10.1]',
+                 '-> [m5.0|m5.1] [m12.0|m12.1] [m1b.0|m1b.1]'],
+ 'B=2 one bw_head': ['conv_b backward_resblocks.main.0 act=0.1 post=1.0 stack=False <- [lr8.0|lr8.1] [feat.0|feat.1] - -',
+                     'resblock24_chain_b backward_resblocks.main.2.0.conv1..backward_resblocks.main.2.1.conv2 act=0.0 stack=False <- [m0.0|m0.1]',
+                     'conf_alpha_b conf_fusion.0.0+conf_fusion.1.0 stack=False up=1 want_max=True <- [conf_prop.0|conf_prop.1] [conf.0|conf.1]',
+                     'conv_b feat_fusion.0.0 act=0.2 post=1.0 stack=False <- [m1.0|m1.1] [aligned.0|aligned.1] - -',
+                     'conv_b feat_fusion.1.0 act=0.2 post=1.0 stack=False <- [m3.0|m3.1] - [m2a.0|m2a.1] [m1.0|m1.1]',
+                     'resblock24_chain_b feat_decoder.RBs.0.conv1..feat_decoder.RBs.7.conv2 act=0.2 stack=False <- [m4.0|m4.1]',
+                     'conv_b feat_decoder.conv_tail act=1.0 post=1.0 stack=False <- [m5.0|m5.1] - - [m4.0|m4.1]',
+                     'conv_b upsample1.upsample_conv act=1.0 post=1.0 stack=False <- [m6.0|m6.1] - - -',
+                     'conv_b feat_fusion2_1.0.0 act=0.2 post=1.0 stack=False <- [feat_up.0|feat_up.1] [m7.0|m7.1] - -',
+                     'conf_alpha_b conf_fusion2.0.0+conf_fusion2.1.0 stack=False up=2 want_max=False <- [conf_prop.0|conf_prop.1] [conf.0|conf.1]',
+                     'conv_b feat_fusion2.0.0 act=0.2 post=1.0 stack=False <- [m8.0|m8.1] [aligned_up.0|aligned_up.1] - -',
+                     'conv_b feat_fusion2.1.0 act=0.2 post=1.0 stack=False <- [m10.0|m10.1] - [m9.0|m9.1] [m8.0|m8.1]',
+                     'resblock24_chain_b feat_decoder2.RBs.0.conv1..feat_decoder2.RBs.3.conv2 act=0.2 stack=False <- [m11.0|m11.1]',
+                     'conv_b feat_decoder2.conv_tail act=1.0 post=1.0 stack=False <- [m12.0|m12.1] - - [m11.0|m11.1]',
+                     '-> [m6.0|m6.1] [m13.0|m13.1] [m2b.0|m2b.1]']}
+
+
+@pytest.mark.parametrize('case', sorted(_PROP_TRACES))
+def test_propagation_launch_list(monkeypatch, case):
+    """The propagation layers exist once, over lists of B >= 1 maps: their launch list in every configuration is the one recorded
+    from the former single-map (B = 1) and multi-map (B = 2) copies -- op for op, weight for weight, map for map."""
+    assert _prop_trace(monkeypatch, case) == _PROP_TRACES[case]
 
 
 def test_split_fp16_dot_product_is_fp32_grade():
