@@ -461,6 +461,27 @@ int refvsr_score_regions(const void* const* out, int out_fmt, const void* const*
                          const int* rects, int nrects, void* workspace, size_t workspace_bytes, double* sums, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Confidence maps as images (extension, no ABI bump: added symbols only).  Replaces the host-side normalisation and colouring of
+ * evaluation/eval_quan_conf_map.py:64-100 (x - x.min(), / x.max(), matplotlib's colormap(x)[:, :, :3] with `inferno`) and
+ * :126,148-165 (x * 255 in float32 through cv2.imwrite's round-to-nearest cast), which it runs on maps it first copies to the host.
+ * refvsr_conf_colormap colours n <= REFVSR_COLORMAP_MAX_MAPS maps of one h x w geometry (h, w >= 1, h * w < 2^31) in two launches:
+ *   maps[k]: HOST array of device pointers, 4-byte aligned, to contiguous fp32 [h][w];
+ *   rgb[k]:  HOST array of device pointers (any alignment) to contiguous uint8 [h][w][3], RGB order;
+ *   per map, all fp32: lo = min x, a = x - lo, span = max a, y = a / span (the correctly rounded quotient),
+ *           idx = min((int)(y * 256), 255), rgb = T[idx]; a constant map (span = 0, y = NaN) is matplotlib's "bad" colour: zero bytes;
+ *   T[i][c] = rint(float32(float32(lut64[i][c]) * 255)) with lut64 matplotlib's 256-entry inferno table (csrc/colormap_table.h);
+ *   ws: device, 8-byte aligned, ws_bytes >= refvsr_conf_colormap_workspace_bytes(n, h, w) (host only; 0 for arguments that
+ *           refvsr_conf_colormap rejects).
+ * Exactness: bit for bit the reference's bytes for finite maps; min / max are exact, so a map's bytes are the same on every run, on
+ * every stream and at every position of a launch.  refvsr_colormap_table copies T (768 bytes, row-major RGB) to host memory `out768`
+ * (no device work).
+ * ------------------------------------------------------------------------------------------ */
+#define REFVSR_COLORMAP_MAX_MAPS 16
+int refvsr_conf_colormap(const void* const* maps, int n, int h, int w, void* const* rgb, void* ws, size_t ws_bytes, void* stream);
+size_t refvsr_conf_colormap_workspace_bytes(int n, int h, int w);
+int refvsr_colormap_table(unsigned char* out768);
+
+/* ------------------------------------------------------------------------------------------
  * Inter-frame alignment
  * ------------------------------------------------------------------------------------------ */
 /* models/utils.py:35-43 `warp`: linspace(-1,1) base grid + flow/((Win-1)/2), grid_sample(bilinear,

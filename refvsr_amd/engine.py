@@ -1094,15 +1094,15 @@ class Engine(object):
         return caller
 
     def _pipe_end(self, caller, M, outs, vis=None, timing=False):
-        """End of a pipelined call whose last section ran on M: the caller's stream waits for the results and owns them from here
-        on, and the call counts as in flight until its `done` event (returned)."""
+        """End of a pipelined call whose last section ran on M: the caller's stream waits for the results (and the vis dicts' maps:
+        one dict or one per window) and owns them from here on, and the call counts as in flight until its `done` event (returned)."""
         done = torch.cuda.Event(enable_timing=timing)
         done.record(M)
         caller.wait_event(done)
         for o in outs:
             o.record_stream(caller)
-        if vis:
-            for v in vis.values():
+        for d in ([vis] if isinstance(vis, dict) else vis or ()):
+            for v in d.values():
                 v.record_stream(caller)
         self._inflight.append(done)
         return done
@@ -1167,7 +1167,7 @@ class Engine(object):
         # serial launches on M at 270p; a clip's first call now overlaps like any other).
         if not bool(self.cfg.EVAL.is_gradio) and (is_first_frame or self.fw_feat is not None):
             outs, vis = self._forward_group_pipelined([(lrs, refs, frame_ids)], input_ready, want_vis, first=bool(is_first_frame))
-            return outs[0], vis
+            return outs[0], (vis[0] if vis else None)
         M0, M1, F_, P = self._pipe_streams(dev)
         M, Mo = (M0, M1) if (self._pipe_calls & 1) == 0 else (M1, M0)
         self._pipe_calls += 1
@@ -1238,15 +1238,17 @@ class Engine(object):
         return itr
 
     @torch.no_grad()
-    def forward_group(self, wins, is_first_frame=False, input_ready=None):
+    def forward_group(self, wins, is_first_frame=False, input_ready=None, want_vis=False):
         """B consecutive windows of this stream in one call: wins = [(lrs [t,3,h,w], refs, frame_ids)] in stream order, every window
         as forward(lrs, refs, is_first, frame_ids=ids) would get it (is_first_frame applies to wins[0]).  Returns [result planar
         [3,s h,s w]] per window -- bit-identical to the B forward() calls.  Runs of >= 2 windows execute as a group (multi-map launches
         on the internal streams: needs set_pipelined(True); a reset_branch roll-over window and -- round 6 -- a caller's first frame stay
         in their group, only their forward branch is the long one); a stream without a carried state, the gradio mode and engines
         without the group schedule run one forward() each.
-        input_ready: as in forward() (None | 'materialised' | event | stream), for all windows of the call."""
-        outs = [None] * len(wins)
+        input_ready: as in forward() (None | 'materialised' | event | stream), for all windows of the call.
+        want_vis: returns (results, [the eval `vis` maps of every window, _conf_vis]) instead -- the maps forward(want_vis=True) gives
+        for that window, bit for bit; off, the launch list is the one without it."""
+        outs, vis = [None] * len(wins), [None] * len(wins)
         i = 0
         if is_first_frame:
             self.id_cache, self.flow_cache = {}, {}               # a new clip: ids of the previous one must not match (as in forward())
@@ -1266,14 +1268,17 @@ class Engine(object):
                     while j < len(wins) and j - i < ops.hip.MAX_MAPS:
                         j += 1
                 if j - i >= 2:
-                    res, _ = self._forward_group_pipelined(wins[i:j], input_ready, first=head)
+                    res, vs = self._forward_group_pipelined(wins[i:j], input_ready, want_vis, first=head)
                     outs[i:j] = res
+                    if want_vis:
+                        vis[i:j] = vs
                     i = j
                 else:
                     lrs, refs, ids = wins[i]
-                    outs[i] = self.forward(lrs, refs, bool(is_first_frame) and i == 0, frame_ids=ids, input_ready=input_ready)[0]
+                    outs[i], vis[i] = self.forward(lrs, refs, bool(is_first_frame) and i == 0, want_vis=want_vis, frame_ids=ids,
+                                                   input_ready=input_ready)
                     i += 1
-        return outs
+        return (outs, vis) if want_vis else outs
 
     def _forward_group_pipelined(self, wins, input_ready, want_vis=False, first=False):
         """B >= 1 steady windows of this stream on the internal streams (the ONE implementation of the P | F | M schedule, round 6):
@@ -1281,7 +1286,7 @@ class Engine(object):
         multi-map launches for B >= 2, the single-map launch list for B = 1 (one forward() per frame: the first layers of its backward
         branch, a function of the new frame alone, run with the frame's preparation on P: `bw_head_blocks`) -- then the upsamplers.
         first: wins[0] is a caller's first frame (RefVSR.py:257-258,292-295): its forward branch starts from zeros like a roll-over's, the
-        iteration counter restarts.  Returns (results, vis of the single window or None)."""
+        iteration counter restarts.  Returns (results, the windows' vis dicts -- None unless want_vis)."""
         B = len(wins)
         t, _, h, w = wins[0][0].shape
         ctr, dev = t // 2, wins[0][0].device
@@ -1354,8 +1359,9 @@ class Engine(object):
             for b, fr in enumerate(frs):
                 M.wait_event(ev_fw[b])
                 outs.append(self.compute_up(bw_ups[b], fws[b][1], bw_confs[b], fws[b][2], fr[ctr].lr))
-            if want_vis and B == 1:
-                vis = self._conf_vis(frs[0][ctr], bw_confs[0], fws[0][2])
+            if want_vis:
+                # (after the window's compute_up, on M: f.conf is `ready`, fws[b] was waited for above)
+                vis = [self._conf_vis(fr[ctr], bw_confs[b], fws[b][2]) for b, fr in enumerate(frs)]
         del held
         self.frame_itr_num = self._itr_after(B)                       # (+ B, through the roll-overs inside the group; RefVSR.py:292-295)
         done = self._pipe_end(caller, M, outs, vis, timing=sev is not None)

@@ -11,6 +11,9 @@ Counterpart of the reference's eval stack, restated from its behaviour:
   * score file lines / output tree                 -- evaluation/eval_qual_quan.py:98-101,106-124,140-143
   * `--eval_mode quan_FOV` (eval.py:16-21): PSNR / SSIM inside, outside and in rings around the overlapped field of view
     -- evaluation/eval_quan_FOV.py:155-192 (the 16 masked scores per frame), :93-111, :196, :245-264 (its lines and blocks)
+  * `--eval_mode quan_conf_map` (eval.py:16-21): the four confidence maps that steer the fusion, min/max-normalised and coloured with
+    matplotlib's inferno, as images next to the input and the result -- evaluation/eval_quan_conf_map.py:64-100,148-165 (the maps, on
+    the device here: ops.conf_colormap), :47,115,179 (its lines)
   * checkpoint loading (flat state dict, optional `module.` prefix) -- ckpt_manager.py:50-60
 
     python -m refvsr_amd.evalrun --mode amp_RefVSR_small_L1 --config config_RefVSR_small_L1 --data RealMCVSR \
@@ -152,10 +155,19 @@ def evaluate(config, net=None, log=print):
     """eval_qual_quan counterpart.  Returns dict(psnr=[..], ssim=[..], frames=N, seconds=[..]).
     'FOV' in EVAL.eval_mode: eval_quan_FOV counterpart -- the same loop; a frame's score is its FOV table (metrics.fov_table,
     [6 keys][fi, fo, fr][psnr, ssim]), whose key 1 fi pair is the per-frame line; the summaries are the reference's six-row blocks; no
-    image is written (the reference has that part commented out); the tables are returned as res['fov']."""
+    image is written (the reference has that part commented out); the tables are returned as res['fov'].
+    'conf_map' in EVAL.eval_mode: eval_quan_conf_map counterpart -- the same loop without scores (psnr / ssim stay empty; --metrics,
+    -qualitative_only and -quantitative_only have no effect, as in the reference's loop): per frame the input, the result and the four
+    maps of 'eval_vis' coloured by ONE ops.conf_colormap launch per network call (CONF_MAP_DIRS names the folders); with --frame_group
+    G > 1 the maps come from forward_group(want_conf=True).  RefVSR_IR has no such maps (the reference fails on None['conf_map'])."""
+    if 'conf_map' in str(config.EVAL.eval_mode) and config.network == 'RefVSR_IR':
+        raise RuntimeError('--eval_mode %s: RefVSR_IR returns no confidence maps (config %s)' % (config.EVAL.eval_mode, config.get('config')))
     from . import SRNet
     E = config.EVAL
     fov = 'FOV' in str(E.eval_mode)
+    conf = 'conf_map' in str(E.eval_mode)
+    if conf:
+        config.save_sample = True            # eval_quan_conf_map.py:23: Network.forward(is_log=True) then returns 'eval_vis'
     if fov and config.flag_HD_in:
         raise RuntimeError('--eval_mode %s: flag_HD_in configs are not supported (the reference scores a cv2.resize(INTER_CUBIC) of the result)' % E.eval_mode)
     if net is None:
@@ -164,6 +176,8 @@ def evaluate(config, net=None, log=print):
         net = SRNet(config).to('cuda').eval()
         if E.ckpt_abs_name:
             log('Loading checkpoint %s: %s' % (E.ckpt_abs_name, load_checkpoint(net, E.ckpt_abs_name)))
+    if conf:
+        net.Network.config.save_sample = True            # (a caller's net may carry a config of its own)
     ckpt_name = os.path.basename(E.ckpt_abs_name) if E.ckpt_abs_name else 'seeded'
     date = datetime.datetime.now().strftime('%Y_%m_%d_%H%M')
     root = os.path.join(E.LOG_DIR.save, E.eval_mode, ckpt_name.split('.')[0])
@@ -188,7 +202,7 @@ def evaluate(config, net=None, log=print):
     # --metrics device (extension, default 'host' = the loop below as it always was): the scores come from ONE refvsr_score_frames launch
     # per network call, on the caller's current stream (which already waits for the results, pipelined mode included: INTEGRATION.md),
     # and cross to the host as 16 bytes per frame; the frame itself is only copied when an image is written
-    on_device = getattr(E, 'metrics', 'host') == 'device' and not getattr(E, 'qualitative_only', False)
+    on_device = getattr(E, 'metrics', 'host') == 'device' and not getattr(E, 'qualitative_only', False) and not conf
 
     def score_device(outs, items):
         from . import ops
@@ -208,7 +222,40 @@ def evaluate(config, net=None, log=print):
         sc = ops.score_frames([o[0] for o in outs], gts, win=0 if config.flag_HD_in else 7).cpu().tolist()
         return [(psnr_from_mse(m), s) for m, s in sc]
 
-    def emit(it, out, lr_c, dt, scored=None):
+    def colour(vis_list):
+        """The windows' 'eval_vis' dicts -> per window {folder: uint8 [h, w, 3] on the host}: one conf_colormap launch for all maps."""
+        from . import ops
+        maps = [v[src] for v in vis_list for _, src in CONF_MAP_DIRS]
+        imgs = [x.cpu() for x in ops.conf_colormap(maps)]
+        k = len(CONF_MAP_DIRS)
+        return [dict((CONF_MAP_DIRS[j][0], imgs[b * k + j]) for j in range(k)) for b in range(len(vis_list))]
+
+    def emit_conf(it, out, lr_c, dt, imgs):
+        out_raw = out[0].cpu()
+        out_cpu = out_raw.float() / 255.0 if out_raw.dtype == torch.uint8 else out_raw.float()
+        line = '[EVAL {}|{}|{}][{}/{}][{}/{}] {} ({:.5f}sec)'.format(
+            config.mode, E.data, it['video_name'], it['video_idx'] + 1, it['video_len'], it['frame_idx'] + 1, it['frame_len'],
+            it['frame_name'], dt)
+        log(line)
+        with open(score_path, 'w' if st['first_line'] else 'a') as fh:
+            fh.write(line + '\n')
+        st['first_line'] = False
+        stem = it['frame_name'].split('.')[0]
+        for fmt in ('png', 'jpg'):
+            base = os.path.join(out_root, fmt)
+            write_frame(os.path.join(base, 'input', it['video_name'], '%s.%s' % (stem, fmt)), lr_c)
+            write_frame(os.path.join(base, 'output', it['video_name'], '%s.%s' % (stem, fmt)), out_raw if out_raw.dtype == torch.uint8 else out_cpu)
+            for folder, _ in CONF_MAP_DIRS:
+                write_frame(os.path.join(base, folder, it['video_name'], '%s.%s' % (stem, fmt)), imgs[folder].permute(2, 0, 1))
+        st['clip_t'] += dt
+        st['clip_n'] += 1
+        st['prev'] = it
+        res['seconds'].append(dt)
+        res['frames'] += 1
+
+    def emit(it, out, lr_c, dt, scored=None, vis=None):
+        if conf:
+            return emit_conf(it, out, lr_c, dt, scored if scored is not None else colour([vis])[0])
         if on_device and scored is None:
             scored = score_device([out], [it])[0]
         if scored is not None and (fov or getattr(E, 'quantitative_only', False)):
@@ -264,18 +311,23 @@ def evaluate(config, net=None, log=print):
         res['seconds'].append(dt)
         res['frames'] += 1
 
-    def flush(pending):
+    def flush(pending, first=False):
         if not pending:
             return
         t0 = time.time()
         lrs, rfs = (stack_frames([it[k] for it in pending]).to(dev) for k in ('LR_UW', 'LR_REF_W'))
         if lrs.dtype != torch.uint8:
             lrs, rfs = lrs.float().contiguous(), rfs.float().contiguous()
-        outs = net.forward_group(lrs, rfs, [it['frame_ids'] for it in pending])['result']
+        kw = {'want_conf': True} if conf else {}
+        got = net.forward_group(lrs, rfs, [it['frame_ids'] for it in pending], is_first_frame=first, **kw)
+        outs = got['result']
         torch.cuda.synchronize()
         dt = (time.time() - t0) / len(pending)
         c = lrs.shape[1] // 2
-        scored = score_device(outs, pending) if on_device else [None] * len(pending)
+        if conf:
+            scored = colour(got['eval_vis'])         # (the windows' images, in the place of their scores)
+        else:
+            scored = score_device(outs, pending) if on_device else [None] * len(pending)
         for b, it in enumerate(pending):
             emit(it, outs[b], lrs[b, c], dt, scored[b])
         del pending[:]
@@ -286,13 +338,15 @@ def evaluate(config, net=None, log=print):
             n = st['clip_n']
             if fov:
                 _fov_clip_summary(config, score_path, st['prev'], st['clip_fov'] / n, st['clip_t'] / n, log)
+            elif conf:
+                _conf_clip_summary(config, score_path, st['prev'], st['clip_t'] / n, log)
             else:
                 _clip_summary(config, score_path, st['prev'], st['clip_p'], st['clip_s'], st['clip_t'], n, log)
         st['clip_p'] = st['clip_s'] = st['clip_t'] = st['clip_fov'] = 0.0
         st['clip_n'] = 0
 
     try:
-        _evaluate_loop(net, ds, dev, E, G, st, emit, flush, clip_summary)
+        _evaluate_loop(net, ds, dev, E, G, st, emit, flush, clip_summary, conf)
     finally:
         if G > 1 and not was_pipelined:
             torch.cuda.synchronize()
@@ -305,6 +359,11 @@ def evaluate(config, net=None, log=print):
         log(total)
         with open(score_path, 'a') as fh:
             fh.write(total)
+    elif conf:
+        total = '\n[TOTAL {}|{}] ({:.5f}sec)'.format(ckpt_name, E.data, sum(res['seconds']) / n)
+        log(total)
+        with open(score_path, 'a') as fh:
+            fh.write(total + '\n')
     else:
         total = '\n[TOTAL {}|{}] PSNR: {:.5f} SSIM: {:.5f} ({:.5f}sec)'.format(
             ckpt_name, E.data, sum(res['psnr']) / n, sum(res['ssim']) / n, sum(res['seconds']) / n)
@@ -315,9 +374,10 @@ def evaluate(config, net=None, log=print):
     return res
 
 
-def _evaluate_loop(net, ds, dev, E, G, st, emit, flush, clip_summary):
-    """The per-frame loop of evaluate() (eval_qual_quan.py:39-128, eval_quan_FOV.py:55-232): emit scores and logs a frame,
-    clip_summary closes a clip."""
+def _evaluate_loop(net, ds, dev, E, G, st, emit, flush, clip_summary, conf=False):
+    """The per-frame loop of evaluate() (eval_qual_quan.py:39-128, eval_quan_FOV.py:55-232, eval_quan_conf_map.py:32-174): emit scores
+    and logs a frame, clip_summary closes a clip.  conf: a one-window call is the reference's own, net(.., is_log=True), whose
+    'eval_vis' goes to emit; in a grouped run every call is a forward_group, a clip's first frame one of a single window."""
     with torch.no_grad():
         pending = []
         for i in range(len(ds)):
@@ -329,6 +389,9 @@ def _evaluate_loop(net, ds, dev, E, G, st, emit, flush, clip_summary):
                 clip_summary()
                 net.Network.reset()
             use_ids = getattr(E, 'use_frame_ids', True) and 'frame_ids' in it
+            if G > 1 and use_ids and conf and it['is_first']:
+                flush([it], first=True)
+                continue
             if G > 1 and use_ids and not it['is_first']:
                 pending.append(it)
                 if len(pending) == G:
@@ -337,15 +400,27 @@ def _evaluate_loop(net, ds, dev, E, G, st, emit, flush, clip_summary):
             t0 = time.time()
             lr, rf = it['LR_UW'][None].to(dev), it['LR_REF_W'][None].to(dev)
             kw = {'frame_ids': it['frame_ids']} if use_ids else {}
-            out = net(lr, rf, it['is_first'], is_log=False, is_train=False, **kw)['result']
+            got = net(lr, rf, it['is_first'], is_log=conf, is_train=False, **kw)
             torch.cuda.synchronize()
-            emit(it, out, lr[0, lr.shape[1] // 2], time.time() - t0)
+            emit(it, got['result'], lr[0, lr.shape[1] // 2], time.time() - t0, vis=got['eval_vis'] if conf else None)
         flush(pending)
 
 
 def _clip_summary(config, score_path, it, p, s, t, n, log):
     line = '[MEAN EVAL {}|{}|{}][{}/{}] PSNR: {:.5f} SSIM: {:.5f} ({:.5f}sec)\n'.format(
         config.mode, config.EVAL.data, it['video_name'], it['video_idx'], it['video_len'], p / n, s / n, t / n)
+    log(line)
+    with open(score_path, 'a') as fh:
+        fh.write(line + '\n')
+
+
+# folder of the reference's output tree <- key of 'eval_vis' (eval_quan_conf_map.py:64-77,148-165)
+CONF_MAP_DIRS = (('conf_map_norm', 'conf_map'), ('conf_map_prop_norm', 'conf_map_prop'),
+                 ('conf_map_prop_b_norm', 'conf_map_prop_backward'), ('conf_map_prop_f_norm', 'conf_map_prop_forward'))
+
+
+def _conf_clip_summary(config, score_path, it, t, log):
+    line = '[MEAN EVAL {}|{}|{}][{}/{}] ({:.5f}sec)\n'.format(config.mode, config.EVAL.data, it['video_name'], it['video_idx'], it['video_len'], t)
     log(line)
     with open(score_path, 'a') as fh:
         fh.write(line + '\n')
@@ -393,7 +468,9 @@ def build_config(argv=None):
     ap.add_argument('-eval_mode', '--eval_mode', type=str, default='qual_quan',
                     help="'qual_quan' (whole-frame PSNR / SSIM and result images) | a name with 'FOV' in it, e.g. 'quan_FOV': PSNR / SSIM "
                          "inside, outside and in rings around the overlapped field of view, no images (with --metrics device one "
-                         "refvsr_score_regions launch per network call)")
+                         "refvsr_score_regions launch per network call) | a name with 'conf_map' in it, e.g. 'quan_conf_map': no "
+                         "scores; the input, the result and the four confidence maps of the fusion as inferno-coloured images (one "
+                         "refvsr_conf_colormap launch per network call; not for RefVSR_IR)")
     ap.add_argument('-test_set', '--test_set', type=str, default='test')
     ap.add_argument('-qualitative_only', '--qualitative_only', action='store_true')
     ap.add_argument('-quantitative_only', '--quantitative_only', action='store_true')
@@ -433,7 +510,7 @@ def build_config(argv=None):
     E.eval_mode, E.test_set, E.data = args.eval_mode, args.test_set, args.data
     E.frame_group = args.frame_group
     E.metrics = args.metrics
-    cfg.save_sample = args.save_sample
+    cfg.save_sample = args.save_sample or 'conf_map' in str(args.eval_mode)      # (eval_quan_conf_map.py:23)
     cfg.device = 'cpu' if args.cpu else 'cuda'
     cfg.cuda = not args.cpu
     if args.data_offset:

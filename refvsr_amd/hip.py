@@ -19,6 +19,7 @@ MAX_MAPS = 4
 INGEST_MAX_FRAMES = 16                      # REFVSR_INGEST_MAX_FRAMES: byte frames per refvsr_ingest_u8 launch
 SCORE_MAX_FRAMES = 16                       # REFVSR_SCORE_MAX_FRAMES: frame pairs per refvsr_score_frames launch
 SCORE_MAX_RECTS = 8                         # REFVSR_SCORE_MAX_RECTS: rectangles per refvsr_score_regions launch
+COLORMAP_MAX_MAPS = 16                      # REFVSR_COLORMAP_MAX_MAPS: maps per refvsr_conf_colormap launch
 RESBLOCK24_BLOB_BYTES = 43264
 RESBLOCK24_F16W_BLOB_BYTES = 28928          # the fp16 weight format (ABI 15)
 RESBLOCK48_BLOB_BYTES = 172544
@@ -159,10 +160,14 @@ SIGNATURES = {
     'refvsr_match_lo_rows': [_P, _I, _I, _P, _P, _P, _P],
     'refvsr_avgpool_pyramid': [_P, _I, _I, _I, _P, _P],
     'refvsr_frame_prep': [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    # confidence maps as images (added symbols, ABI 15 unchanged)
+    'refvsr_conf_colormap': [_P, _I, _I, _I, _P, _P, _Z, _P],
+    'refvsr_colormap_table': [_P],               # copies the 256 x 3 byte colour table to host memory
 }
 _SPECIAL = {'refvsr_abi_version': (C.c_int, []), 'refvsr_last_error': (C.c_char_p, []),
             'refvsr_score_workspace_bytes': (C.c_size_t, [_I, _I, _I]),
-            'refvsr_score_regions_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I])}
+            'refvsr_score_regions_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I]),
+            'refvsr_conf_colormap_workspace_bytes': (C.c_size_t, [_I, _I, _I])}
 EXPORTS = tuple(sorted(list(SIGNATURES) + list(_SPECIAL)))
 
 _lib = None

@@ -4,7 +4,10 @@ evalrun.psnr / evalrun.ssim (trainers/trainer.py:252-254, evaluation/metrics.py:
 
 The field-of-view evaluation (evaluation/eval_quan_FOV.py:155-192 on evaluation/metrics.py:18-30) lives here too: the seven rectangles
 its 16 masked scores are made of (fov_rects), the table those scores form from rectangle sums (fov_table), a numpy model of
-refvsr_score_regions (score_regions_model) and the whole-array float64 host path (fov_scores_host)."""
+refvsr_score_regions (score_regions_model) and the whole-array float64 host path (fov_scores_host).
+
+The confidence-map evaluation (evaluation/eval_quan_conf_map.py:64-100,148-165) has its numpy model here as well: conf_colormap_model,
+the steps of refvsr_conf_colormap (csrc/colormap.hip) one by one."""
 import math
 
 import numpy as np
@@ -240,3 +243,32 @@ def fov_scores_host(a, b):
     """The FOV table [6][3][2] of one pair a, b [3,h,w] on the host in float64 (`--eval_mode quan_FOV --metrics host`)."""
     h, w = a.shape[-2:]
     return fov_table(host_region_sums(a, b, fov_rects(h, w)), h, w)
+
+
+# ------------------------------------------------------------------------------------------------ confidence maps as images
+def conf_colormap_model(x):
+    """uint8 [h, w, 3] (RGB): one confidence map [.., h, w] (numpy or torch, numel == h * w, finite) min/max-normalised and coloured
+    with matplotlib's inferno exactly as csrc/colormap.hip computes it, all float32: lo = min x, a = x - lo, span = max a, y = a / span
+    (the IEEE quotient), idx = min((int)(y * 256), 255), out = T[idx] with T the library's table (refvsr_colormap_table; no matplotlib
+    here).  A constant map (span = 0, y = NaN) is matplotlib's "bad" colour: zero bytes.  Bit for bit what
+    evaluation/eval_quan_conf_map.py:79-84,126,150 writes (x - x.min(), / x.max(), colormap(x)[:, :, :3], torch.Tensor, * 255, the
+    rounding cast of cv2.imwrite)."""
+    from . import ops
+    if hasattr(x, 'detach'):
+        x = x.detach().cpu().numpy()
+    x = np.asarray(x, dtype=np.float32)
+    h, w = x.shape[-2:]
+    assert x.size == h * w, 'conf_colormap_model: one [.., h, w] map'
+    x = x.reshape(h, w)
+    table = np.array(ops.colormap_table(), dtype=np.uint8)
+    lo = x.min()
+    a = x - lo
+    span = a.max()
+    with np.errstate(invalid='ignore', divide='ignore'):
+        y = a / span
+    assert y.dtype == np.float32
+    bad = np.isnan(y)
+    idx = np.minimum(np.where(bad, np.float32(0), y * np.float32(256)).astype(np.int64), 255)
+    out = table[idx]
+    out[bad] = 0
+    return out

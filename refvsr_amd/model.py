@@ -193,11 +193,14 @@ class Network(nn.Module):
             outs['eval_vis'] = ev
         return outs
 
-    def forward_group(self, lrs, refs, frame_ids, is_first_frame=False, input_ready=None):
+    def forward_group(self, lrs, refs, frame_ids, is_first_frame=False, input_ready=None, want_conf=False):
         """B CONSECUTIVE windows of one stream in one call (extension; see Engine.forward_group): lrs, refs [B,t,3,h,w] -- window b
         is what the b-th of B consecutive forward() calls would get as its n = 1 input -- frame_ids: B lists of t ids.  Returns
         OrderedDict{'result': tuple of B tensors [1,3,sh,sw]}, bit-identical to the B calls; the backward branches and the
-        upsamplers' inputs of the B frames run as multi-map launches, the forward-branch steps frame by frame."""
+        upsamplers' inputs of the B frames run as multi-map launches, the forward-branch steps frame by frame.
+        want_conf: the dict also carries 'eval_vis', a tuple of B OrderedDicts of [1,1,h,w] float32 maps -- what forward(window b, ..,
+        is_log=True) returns as 'eval_vis' under config.save_sample (RefVSR.py:318-322), bit for bit.  (RefVSR_IR has no such maps:
+        no 'eval_vis' key, as in forward().)  Off (the default), no launch is added."""
         hip.lib()
         if not lrs.is_cuda:
             raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path' % lrs.device)
@@ -211,9 +214,14 @@ class Network(nn.Module):
         assert len(frame_ids) == lrs.shape[0] and lrs.shape == refs.shape
         eng = self.ensure_engines(1, lrs.device)[0]
         wins = [(lrs[b], refs[b], [(0, f) for f in frame_ids[b]]) for b in range(lrs.shape[0])]
-        res = eng.forward_group(wins, bool(is_first_frame), input_ready)
+        res = eng.forward_group(wins, bool(is_first_frame), input_ready, want_vis=bool(want_conf))
+        vis = None
+        if want_conf:
+            res, vis = res
         outs = collections.OrderedDict()
         outs['result'] = tuple(r.unsqueeze(0) for r in res)
+        if vis is not None and all(v is not None for v in vis):
+            outs['eval_vis'] = tuple(collections.OrderedDict((k, x.unsqueeze(0)) for k, x in v.items()) for v in vis)
         return outs
 
     # ---- two-phase forward for the multi-GPU wavefront (refvsr_amd/shard.py:run_wavefront; not in the reference) ----
@@ -308,6 +316,6 @@ class SRNet(nn.Module):
         final -- see Engine.forward and Engine.set_pipelined."""
         return self.Network.forward(x, ref, is_first_frame, is_log=is_log, is_train=is_train, frame_ids=frame_ids, input_ready=input_ready)
 
-    def forward_group(self, x, ref, frame_ids, is_first_frame=False, input_ready=None):
+    def forward_group(self, x, ref, frame_ids, is_first_frame=False, input_ready=None, want_conf=False):
         """B consecutive windows of one stream in one call (extension, not in the reference): see Network.forward_group."""
-        return self.Network.forward_group(x, ref, frame_ids, is_first_frame=is_first_frame, input_ready=input_ready)
+        return self.Network.forward_group(x, ref, frame_ids, is_first_frame=is_first_frame, input_ready=input_ready, want_conf=want_conf)

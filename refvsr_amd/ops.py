@@ -824,6 +824,51 @@ def score_regions(outs, gts, rects):
     return sums
 
 
+_COLORMAP_WS = {}     # (device, stream handle, h, w) -> workspace of one full refvsr_conf_colormap launch
+
+
+def colormap_table():
+    """The library's colour table (host query, no device work): 256 [r, g, b] byte triples, matplotlib's inferno as the reference's
+    images hold it (csrc/colormap_table.h)."""
+    t = (C.c_ubyte * 768)()
+    hip.check(hip.lib().refvsr_colormap_table(t), 'colormap_table')
+    return [list(t[3 * i:3 * i + 3]) for i in range(256)]
+
+
+def conf_colormap(maps):
+    """The confidence-map images of evaluation/eval_quan_conf_map.py:64-100,148-165, computed on the device (refvsr_conf_colormap):
+    maps: cuda float32 tensors of one [.., h, w] geometry with numel == h * w (e.g. the [1, h, w] or [1, 1, h, w] maps of 'eval_vis'),
+    contiguous.  Returns one uint8 [h, w, 3] tensor (RGB) per map -- the map min/max-normalised and coloured with matplotlib's
+    inferno, bit for bit the reference's bytes (metrics.conf_colormap_model) -- on the current stream, no synchronisation.  One launch
+    per REFVSR_COLORMAP_MAX_MAPS maps."""
+    maps = list(maps)
+    assert maps, 'conf_colormap: no maps'
+    h, w = maps[0].shape[-2:]
+    for m in maps:
+        assert m.is_cuda and m.dtype == torch.float32 and m.is_contiguous() and m.dim() >= 2, \
+            'conf_colormap: contiguous cuda float32 maps, got %s %s' % (m.dtype, tuple(m.shape))
+        if tuple(m.shape[-2:]) != (h, w) or m.numel() != h * w:
+            raise RuntimeError('conf_colormap: maps must be single [.., %d, %d] maps of one geometry (got %s)' % (h, w, tuple(m.shape)))
+    st = _stream()
+    dev = maps[0].device
+    key = (dev, st.value, h, w)
+    ws = _COLORMAP_WS.get(key)
+    if ws is None:
+        if len(_COLORMAP_WS) > 16:
+            _COLORMAP_WS.clear()
+        nbytes = hip.lib().refvsr_conf_colormap_workspace_bytes(hip.COLORMAP_MAX_MAPS, h, w)
+        if nbytes == 0:
+            raise RuntimeError('conf_colormap: maps must hold 1 .. 2^31 - 1 samples (got %d x %d)' % (h, w))
+        ws = _COLORMAP_WS[key] = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    outs = [torch.empty((h, w, 3), dtype=torch.uint8, device=dev) for _ in maps]
+    for s0 in range(0, len(maps), hip.COLORMAP_MAX_MAPS):
+        n = min(hip.COLORMAP_MAX_MAPS, len(maps) - s0)
+        pm = (C.c_void_p * n)(*[m.data_ptr() for m in maps[s0:s0 + n]])
+        po = (C.c_void_p * n)(*[o.data_ptr() for o in outs[s0:s0 + n]])
+        hip.check(hip.lib().refvsr_conf_colormap(pm, n, h, w, po, _ptr(ws), ws.numel() * 4, st), 'conf_colormap')
+    return outs
+
+
 def warp_nhwc16(x, flow):
     _nhwc(x)
     _planar(flow, 2)
