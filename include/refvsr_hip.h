@@ -435,6 +435,26 @@ int refvsr_score_frames(const void* const* out, int out_fmt, const void* const* 
                         int win, void* workspace, size_t workspace_bytes, double* scores, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Frame scores of the flag_HD_in configurations (extension, no ABI bump: an added symbol only), whose result is `down` = scale times
+ * the size of the ground truth.  Replaces models/loss/Loss.py:91-92,141 (sr_down = F.interpolate(sr, scale_factor = 1 / scale, mode =
+ * 'bicubic', align_corners = False).clamp(0, 1), then get_psnr(sr_down, hr)) and evaluation/eval_qual_quan.py:85-92 (ssim of
+ * cv2.resize(output, fx = fy = 1 / scale, INTER_CUBIC), not clamped, against the ground truth), both computed on a frame first copied
+ * to the host.  refvsr_score_frames_down is refvsr_score_frames with the bicubic down-scale fused into the kernel's tile staging:
+ *   out[i]: planar [3][down h][down w] results; gt[i]: [3][h][w] ground truths -- h, w name the GROUND TRUTH, and the workspace is
+ *           refvsr_score_workspace_bytes(nframes, h, w) as for refvsr_score_frames; down = 2 | 4;
+ *   D(y, x) = sum_j W[j] (sum_k W[k] out[clamp(down y + down / 2 - 2 + j)][clamp(down x + down / 2 - 2 + k)]), W = (-3, 19, 19, -3) / 32
+ *           (Keys' cubic, A = -0.75, half-pixel centres, no anti-aliasing: what both reference lines compute at an exact integer
+ *           factor), float64 on the float32 value of every tap, k left to right, j top to bottom, rounded once to float32;
+ *   mse  = mean of (clamp(D, 0, 1) - gt)^2;  ssim = the SSIM of refvsr_score_frames on the unclamped D.
+ *   Every other argument, check and alignment rule is that of refvsr_score_frames (results aligned to four samples are read with
+ *   wider loads at down = 4; the scores do not depend on it).
+ * Exactness: the scores are bit for bit those of refvsr_score_frames on D (ssim) and on clamp(D, 0, 1) with win = 0 (mse), with D as
+ * refvsr_amd/metrics.py:down_bicubic_model computes it; the same determinism.
+ * ------------------------------------------------------------------------------------------ */
+int refvsr_score_frames_down(const void* const* out, int out_fmt, const void* const* gt, int gt_fmt, int gt_layout, int nframes, int h,
+                             int w, int down, int win, void* workspace, size_t workspace_bytes, double* scores, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Rectangle sums for the field-of-view evaluation (extension, no ABI bump: added symbols only).  Replaces the host-side masked
  * scoring of evaluation/eval_quan_FOV.py:155-192, which calls evaluation/metrics.py:18-30 (psnr_masked = 10 log10(sum mask /
  * sum (a - b)^2 mask); ssim_masked = sum S mask / sum mask with S the FULL map of skimage structural_similarity: a value at every

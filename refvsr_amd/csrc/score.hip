@@ -25,6 +25,23 @@
 // in a fixed strided order + the same tree and divides by the counts.  A frame's bits therefore do not depend on the other frames of
 // the launch, on the stream or on the run.  refvsr_amd/metrics.py:score_frames_model restates the decomposition and the order in numpy.
 //
+//
+// Down-scaled scoring (refvsr_score_frames_down, the flag_HD_in configs whose result is `down` = 2 | 4 times the ground truth): the
+// kernel is a template on DOWN.  DOWN = 1 is the kernel described above, statement for statement.  DOWN > 1 differs in the staging
+// alone: the thread that stages element (y, x) of the 38 x 70 tile forms D(y, x), the bicubic down-scale of the big result frame
+// [3][DOWN h][DOWN w] that models/loss/Loss.py:91-92 (F.interpolate(sr, scale_factor = 1 / scale, mode = 'bicubic', align_corners =
+// False)) and evaluation/eval_qual_quan.py:85-92 (cv2.resize(.., fx = fy = 1 / scale, INTER_CUBIC)) compute: at an exact integer factor
+// both are Keys' cubic with A = -0.75 at half-pixel centres without anti-aliasing, whose source coordinate DOWN x + DOWN / 2 - 1 / 2
+// has the fraction 1 / 2 -- four taps i0 .. i0 + 3, i0 = DOWN x + DOWN / 2 - 2, clamped into the frame, with the weights (-3, 19, 19,
+// -3) / 32, exact in binary.  float64 on the float32 value of every tap: the products are exact, a row's four are added left to right,
+// the four row sums weighted and added top to bottom, and D is rounded ONCE to float32 (the reference's float32 image, correctly
+// rounded; refvsr_amd/metrics.py:down_bicubic_model).  ta holds (float)D -- the SSIM is that of the unclamped image (eval_qual_quan.py
+// does not clamp) -- and the owned samples add (clamp01(D) - b)^2 (Loss.py:92 clamps before get_psnr, :141).  Everything after the
+// staging is the same code, so the summation order and the determinism are the ones above, and the scores are bit for bit those of
+// DOWN = 1 on the uploaded D / clamp01(D).  Every index into the big frame is size_t.  Taps are loaded element by element (natural
+// alignment); for DOWN = 4, where a row's four taps 4 x .. 4 x + 3 are one aligned group of four, as ONE 16- / 8- / 4-byte load when
+// the entry point has seen every result pointer aligned to four samples (ScoreArgs::avec; the same values, hence the same bits).
+//
 // Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): the figures next to score_tile_kernel;
 // score_finish_kernel: 14 VGPRs, 2 KB LDS, no scratch.
 #include "common.h"
@@ -51,6 +68,7 @@ struct ScoreArgs {
     int afmt;                          // REFVSR_RESULT_*
     int bkind;                         // SC_GT_*
     int win;                           // 7 | 0
+    int avec;                          // DOWN = 4: every result pointer is aligned to four samples (one load per tap row)
 };
 
 static inline int sc_tiles(int n, int t) { return (n - 6 + t - 1) / t; }    // tiles over n - 6 window origins
@@ -67,8 +85,61 @@ __device__ __forceinline__ double sc_block_sum(double* red, const int tid, const
     return red[0];
 }
 
-// score_tile_kernel: 104 VGPRs, 43 SGPRs, no scratch, no spills, 24 352 B LDS, 4 waves per SIMD by registers (figures of the build
-// this file was written against -- re-check with -Rpass-analysis=kernel-resource-usage after a change)
+// D(y, x) of result plane c, rounded once to float32: the bicubic down-scale by DOWN = 2 | 4 of the big frame [3][DOWN h][DOWN w] at
+// ground-truth position (y, x) (the file header).  avec (DOWN = 4 only): one load per tap row
+template <int DOWN>
+__device__ __forceinline__ float sc_down_sample(const unsigned char* __restrict__ pa, const float* tbl, const int afmt, const int avec,
+                                                const int c, const int y, const int x, const int h, const int w) {
+    static_assert(DOWN == 2 || DOWN == 4, "integer factors whose source coordinate has the fraction 1 / 2");
+    constexpr double W0 = -3.0 / 32.0, W1 = 19.0 / 32.0;
+    const int bh = DOWN * h, bw = DOWN * w;                       // (h w <= 2^29 and h, w >= 7: both fit an int)
+    const int i0y = DOWN * y + DOWN / 2 - 2, i0x = DOWN * x + DOWN / 2 - 2;
+    int xi[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) xi[k] = DOWN == 4 ? i0x + k : min(max(i0x + k, 0), bw - 1);      // DOWN = 4: 4 x .. 4 x + 3, inside
+    double rs[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int yy = DOWN == 4 ? i0y + j : min(max(i0y + j, 0), bh - 1);
+        const size_t row = ((size_t)c * bh + yy) * (size_t)bw;   // planar [3][bh][bw]
+        float t[4];
+        if (DOWN == 4 && avec) {                                  // row + xi[0] is a multiple of 4 samples, the pointer of 4 samples
+            const size_t i4 = (row + (size_t)xi[0]) >> 2;
+            if (afmt == REFVSR_RESULT_F32) {
+                const f32x4 v = reinterpret_cast<const f32x4*>(pa)[i4];
+                t[0] = v[0]; t[1] = v[1]; t[2] = v[2]; t[3] = v[3];
+            } else if (afmt == REFVSR_RESULT_F16) {
+                const f16x4 v = reinterpret_cast<const f16x4*>(pa)[i4];
+                t[0] = (float)v[0]; t[1] = (float)v[1]; t[2] = (float)v[2]; t[3] = (float)v[3];
+            } else {
+                const unsigned v = reinterpret_cast<const unsigned*>(pa)[i4];
+                t[0] = tbl[v & 255u]; t[1] = tbl[(v >> 8) & 255u]; t[2] = tbl[(v >> 16) & 255u]; t[3] = tbl[v >> 24];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const size_t ip = row + (size_t)xi[k];
+                if (afmt == REFVSR_RESULT_F32) t[k] = reinterpret_cast<const float*>(pa)[ip];
+                else if (afmt == REFVSR_RESULT_F16) t[k] = (float)reinterpret_cast<const f16*>(pa)[ip];
+                else t[k] = tbl[pa[ip]];
+            }
+        }
+        double acc = W0 * (double)t[0] + W1 * (double)t[1];       // exact products, added left to right
+        acc = acc + W1 * (double)t[2];
+        acc = acc + W0 * (double)t[3];
+        rs[j] = acc;
+    }
+    double d = W0 * rs[0] + W1 * rs[1];                           // the four row sums, top to bottom
+    d = d + W1 * rs[2];
+    d = d + W0 * rs[3];
+    return (float)d;
+}
+
+// score_tile_kernel<1>: 104 VGPRs, 43 SGPRs, no scratch, no spills, 24 352 B LDS, 4 waves per SIMD by registers (figures of the build
+// this file was written against -- re-check with -Rpass-analysis=kernel-resource-usage after a change; re-checked when the kernel
+// became a template: the same figures as before it).  score_tile_kernel<2>: 104 VGPRs, 53 SGPRs; score_tile_kernel<4>: 104 VGPRs,
+// 55 SGPRs; both no scratch, 24 352 B LDS, 4 waves per SIMD -- the sixteen taps live only in the staging loop, before the row ring
+template <int DOWN>
 __global__ void __launch_bounds__(SC_THREADS) score_tile_kernel(ScoreArgs s) {
     __shared__ float tbl[256];
     __shared__ float ta[SC_IH * SC_IW], tb[SC_IH * SC_IW];
@@ -93,14 +164,18 @@ __global__ void __launch_bounds__(SC_THREADS) score_tile_kernel(ScoreArgs s) {
         float va = 0.0f, vb = 0.0f;
         if (y < h && x < w) {
             const size_t ip = ((size_t)c * h + y) * w + x;       // planar [3][h][w]
-            if (s.afmt == REFVSR_RESULT_F32) va = reinterpret_cast<const float*>(pa)[ip];
-            else if (s.afmt == REFVSR_RESULT_F16) va = (float)reinterpret_cast<const f16*>(pa)[ip];
-            else va = tbl[pa[ip]];
+            if constexpr (DOWN == 1) {
+                if (s.afmt == REFVSR_RESULT_F32) va = reinterpret_cast<const float*>(pa)[ip];
+                else if (s.afmt == REFVSR_RESULT_F16) va = (float)reinterpret_cast<const f16*>(pa)[ip];
+                else va = tbl[pa[ip]];
+            } else {
+                va = sc_down_sample<DOWN>(pa, tbl, s.afmt, s.avec, c, y, x, h, w);
+            }
             if (s.bkind == SC_GT_F32) vb = reinterpret_cast<const float*>(pb)[ip];
             else if (s.bkind == SC_GT_U8_PLANAR) vb = tbl[pb[ip]];
             else vb = tbl[pb[((size_t)y * w + x) * 3 + c]];      // interleaved [h][w][3]
             if (r < own_h && q < own_w) {
-                const double d = (double)va - (double)vb;
+                const double d = (double)(DOWN == 1 ? va : fminf(fmaxf(va, 0.0f), 1.0f)) - (double)vb;
                 mse = mse + d * d;
             }
         }
@@ -192,30 +267,33 @@ extern "C" size_t refvsr_score_workspace_bytes(int nframes, int h, int w) {
     return (size_t)nframes * 3 * sc_tiles(h, SC_TH) * sc_tiles(w, SC_TW) * 2 * sizeof(double);
 }
 
-extern "C" int refvsr_score_frames(const void* const* out, int out_fmt, const void* const* gt, int gt_fmt, int gt_layout, int nframes,
-                                   int h, int w, int win, void* workspace, size_t workspace_bytes, double* scores, void* stream) {
-    RV_CHECK(out && gt, "score_frames: null frame table");
-    RV_CHECK(nframes >= 1 && nframes <= REFVSR_SCORE_MAX_FRAMES, "score_frames: 1..%d frames per launch", REFVSR_SCORE_MAX_FRAMES);
-    RV_CHECK(sc_geometry_ok(h, w), "score_frames: h, w must be at least 7 (the SSIM window) and h * w at most 2^29");
-    RV_CHECK(win == 7 || win == 0, "score_frames: win must be 7, or 0 for the mse alone");
+// the two entry points' checks and launches; `who` names the caller in the messages, down = 1 | 2 | 4
+static int sc_run(const char* who, const void* const* out, int out_fmt, const void* const* gt, int gt_fmt, int gt_layout, int nframes, int h, int w,
+                  int down, int win, void* workspace, size_t workspace_bytes, double* scores, void* stream) {
+    RV_CHECK(out && gt, "%s: null frame table", who);
+    RV_CHECK(nframes >= 1 && nframes <= REFVSR_SCORE_MAX_FRAMES, "%s: 1..%d frames per launch", who, REFVSR_SCORE_MAX_FRAMES);
+    RV_CHECK(sc_geometry_ok(h, w), "%s: h, w must be at least 7 (the SSIM window) and h * w at most 2^29", who);
+    RV_CHECK(win == 7 || win == 0, "%s: win must be 7, or 0 for the mse alone", who);
     RV_CHECK(out_fmt == REFVSR_RESULT_F32 || out_fmt == REFVSR_RESULT_F16 || out_fmt == REFVSR_RESULT_U8,
-             "score_frames: result format must be REFVSR_RESULT_F32 | _F16 | _U8");
-    RV_CHECK(gt_fmt == REFVSR_RESULT_F32 || gt_fmt == REFVSR_RESULT_U8, "score_frames: ground-truth format must be REFVSR_RESULT_F32 | _U8");
+             "%s: result format must be REFVSR_RESULT_F32 | _F16 | _U8", who);
+    RV_CHECK(gt_fmt == REFVSR_RESULT_F32 || gt_fmt == REFVSR_RESULT_U8, "%s: ground-truth format must be REFVSR_RESULT_F32 | _U8", who);
     RV_CHECK(gt_layout == REFVSR_INGEST_PLANAR || gt_layout == REFVSR_INGEST_HWC,
-             "score_frames: ground-truth layout must be REFVSR_INGEST_PLANAR | REFVSR_INGEST_HWC");
-    RV_CHECK(!(gt_fmt == REFVSR_RESULT_F32 && gt_layout == REFVSR_INGEST_HWC), "score_frames: the interleaved layout is for uint8 ground truth");
-    RV_CHECK(workspace && scores, "score_frames: null workspace / scores");
-    RV_CHECK(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)scores & 15) == 0, "score_frames: workspace and scores must be 16-byte aligned");
-    RV_CHECK(workspace_bytes >= refvsr_score_workspace_bytes(nframes, h, w), "score_frames: workspace too small (%zu bytes, %zu needed)",
+             "%s: ground-truth layout must be REFVSR_INGEST_PLANAR | REFVSR_INGEST_HWC", who);
+    RV_CHECK(!(gt_fmt == REFVSR_RESULT_F32 && gt_layout == REFVSR_INGEST_HWC), "%s: the interleaved layout is for uint8 ground truth", who);
+    RV_CHECK(workspace && scores, "%s: null workspace / scores", who);
+    RV_CHECK(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)scores & 15) == 0, "%s: workspace and scores must be 16-byte aligned", who);
+    RV_CHECK(workspace_bytes >= refvsr_score_workspace_bytes(nframes, h, w), "%s: workspace too small (%zu bytes, %zu needed)", who,
              workspace_bytes, refvsr_score_workspace_bytes(nframes, h, w));
     ScoreArgs a;
     memset(&a, 0, sizeof(a));
     const uintptr_t amask = out_fmt == REFVSR_RESULT_F32 ? 3 : out_fmt == REFVSR_RESULT_F16 ? 1 : 0;
     const uintptr_t bmask = gt_fmt == REFVSR_RESULT_F32 ? 3 : 0;
+    a.avec = down == 4;
     for (int i = 0; i < nframes; ++i) {
-        RV_CHECK(out[i] && gt[i], "score_frames: null pointer (frame %d)", i);
+        RV_CHECK(out[i] && gt[i], "%s: null pointer (frame %d)", who, i);
         RV_CHECK(((uintptr_t)out[i] & amask) == 0 && ((uintptr_t)gt[i] & bmask) == 0,
-                 "score_frames: fp32 frames must be 4-byte, fp16 frames 2-byte aligned (frame %d)", i);
+                 "%s: fp32 frames must be 4-byte, fp16 frames 2-byte aligned (frame %d)", who, i);
+        if ((uintptr_t)out[i] & (4 * (amask + 1) - 1)) a.avec = 0;      // a frame not aligned to four samples: element loads for all
         a.a[i] = out[i];
         a.b[i] = gt[i];
     }
@@ -226,12 +304,28 @@ extern "C" int refvsr_score_frames(const void* const* out, int out_fmt, const vo
     a.bkind = gt_fmt == REFVSR_RESULT_F32 ? SC_GT_F32 : gt_layout == REFVSR_INGEST_PLANAR ? SC_GT_U8_PLANAR : SC_GT_U8_HWC;
     a.win = win;
     const int nt = a.ntx * a.nty;
-    hipLaunchKernelGGL(score_tile_kernel, dim3(nt, 3, nframes), dim3(SC_THREADS), 0, (hipStream_t)stream, a);
+    const dim3 grid(nt, 3, nframes);
+    if (down == 1) hipLaunchKernelGGL(score_tile_kernel<1>, grid, dim3(SC_THREADS), 0, (hipStream_t)stream, a);
+    else if (down == 2) hipLaunchKernelGGL(score_tile_kernel<2>, grid, dim3(SC_THREADS), 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(score_tile_kernel<4>, grid, dim3(SC_THREADS), 0, (hipStream_t)stream, a);
     RV_LAUNCH_CHECK();
     hipLaunchKernelGGL(score_finish_kernel, dim3(nframes), dim3(SC_THREADS), 0, (hipStream_t)stream, (const double*)workspace, 3 * nt, h, w, win,
                        scores);
     RV_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int refvsr_score_frames(const void* const* out, int out_fmt, const void* const* gt, int gt_fmt, int gt_layout, int nframes,
+                                   int h, int w, int win, void* workspace, size_t workspace_bytes, double* scores, void* stream) {
+    return sc_run("score_frames", out, out_fmt, gt, gt_fmt, gt_layout, nframes, h, w, 1, win, workspace, workspace_bytes, scores, stream);
+}
+
+// results [3][down h][down w], ground truths [3][h][w] (h, w name the ground truth: the tiling, the workspace and the counts are its)
+extern "C" int refvsr_score_frames_down(const void* const* out, int out_fmt, const void* const* gt, int gt_fmt, int gt_layout, int nframes,
+                                        int h, int w, int down, int win, void* workspace, size_t workspace_bytes, double* scores,
+                                        void* stream) {
+    RV_CHECK(down == 2 || down == 4, "score_frames_down: down must be 2 or 4 (the result must be `down` times the ground truth)");
+    return sc_run("score_frames_down", out, out_fmt, gt, gt_fmt, gt_layout, nframes, h, w, down, win, workspace, workspace_bytes, scores, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ rectangle sums (FOV evaluation)

@@ -6,6 +6,8 @@ Counterpart of the reference's eval stack, restated from its behaviour:
   * `is_first` per clip                            -- datasets.py:286-288 (the reference yields False for frame 0
     of a single-clip dataset and then crashes, RefVSR.py:257-258; here the first frame of every clip is True)
   * PSNR = 10 log10(1/mse)                         -- trainers/trainer.py:252-254
+  * flag_HD_in configs (result = scale x the ground truth): both scores on the bicubic down-scale of the result -- PSNR of the
+    clamped image (models/loss/Loss.py:91-92,141), SSIM of the unclamped one (evaluation/eval_qual_quan.py:85-92)
   * SSIM = skimage.structural_similarity defaults  -- evaluation/metrics.py:17-18 (7x7 uniform window, sample
     covariance, K1=0.01, K2=0.03, mean over channels) re-implemented (skimage is not in this image)
   * score file lines / output tree                 -- evaluation/eval_qual_quan.py:98-101,106-124,140-143
@@ -208,8 +210,11 @@ def evaluate(config, net=None, log=print):
         from . import ops
         from .metrics import psnr_from_mse
         gts = [it['HR_UW'].to(dev) for it in items]              # (decoded bytes, channels-last: a quarter of the float frame)
+        # flag_HD_in: the result is `scale` times the ground truth and the scores are those of its bicubic down-scale, which the
+        # kernel forms while it stages its tiles (refvsr_score_frames_down): the big frame is read once where it lies
+        down = int(config.scale) if config.flag_HD_in else 1     # (no FOV mode here: evaluate() refuses it for these configs)
         for o, g in zip(outs, gts):
-            if o[0].shape != g.shape:
+            if tuple(o[0].shape) != (3, down * g.shape[-2], down * g.shape[-1]):
                 raise RuntimeError('--metrics device: result %s and ground truth %s differ in shape' % (tuple(o[0].shape), tuple(g.shape)))
         if fov:
             # one refvsr_score_regions launch: 7 rectangles x 16 bytes per frame cross to the host
@@ -218,8 +223,10 @@ def evaluate(config, net=None, log=print):
             sums = ops.score_regions([o[0] for o in outs], gts, fov_rects(h, w)).cpu().numpy()
             tables = [fov_table(sm, h, w) for sm in sums]
             return [(float(t[0, 0, 0]), float(t[0, 0, 1]), t) for t in tables]
-        # flag_HD_in: the host path's SSIM compares a down-scaled result with the full-size ground truth and is 0.0: mse only
-        sc = ops.score_frames([o[0] for o in outs], gts, win=0 if config.flag_HD_in else 7).cpu().tolist()
+        if down == 1:
+            sc = ops.score_frames([o[0] for o in outs], gts, win=7).cpu().tolist()
+        else:
+            sc = ops.score_frames([o[0] for o in outs], gts, win=7, down=down).cpu().tolist()
         return [(psnr_from_mse(m), s) for m, s in sc]
 
     def colour(vis_list):
@@ -278,13 +285,16 @@ def evaluate(config, net=None, log=print):
             p, s = float(table[0, 0, 0]), float(table[0, 0, 1])
         elif not getattr(E, 'qualitative_only', False):
             gt = it['HR_UW']
-            p = psnr(out_cpu, gt)
-            cmp_out = out_cpu
-            if config.flag_HD_in:          # eval_qual_quan.py:86-87: SSIM against the LR-size GT
-                cmp_out = F.interpolate(out_cpu[None], scale_factor=1.0 / config.scale, mode='bicubic',
-                                        align_corners=False)[0]
-            if cmp_out.shape == gt.shape:
-                s = ssim(cmp_out, gt)
+            if config.flag_HD_in:
+                # the result is `scale` times the ground truth; both scores are those of its bicubic down-scale: the PSNR of the
+                # clamped image (models/loss/Loss.py:91-92,141), the SSIM of the unclamped one (eval_qual_quan.py:85-92, whose
+                # cv2.resize(INTER_CUBIC) is this filter at an exact integer factor)
+                d = F.interpolate(out_cpu[None], scale_factor=1.0 / config.scale, mode='bicubic', align_corners=False)[0]
+                p = psnr(d.clamp(0, 1), gt)
+                s = ssim(d, gt)
+            else:
+                p = psnr(out_cpu, gt)
+                s = ssim(out_cpu, gt)
         line = '[EVAL {}|{}|{}][{}/{}][{}/{}] {} PSNR: {:.5f} SSIM: {:.5f} ({:.5f}sec)'.format(
             config.mode, E.data, it['video_name'], it['video_idx'] + 1, it['video_len'], it['frame_idx'] + 1,
             it['frame_len'], it['frame_name'], p, s, dt)
@@ -492,7 +502,10 @@ def build_config(argv=None):
     ap.add_argument('--metrics', default='host', choices=['host', 'device'],
                     help="extension: where PSNR / SSIM are computed ('device' = one refvsr_score_frames launch per network call in float64, "
                          "16 bytes per frame cross to the host and with --quantitative_only the frame never does; SSIM agrees with the host "
-                         "to 1e-10, PSNR to 2e-5 dB -- the host's mean is float32 -- so a score line may differ in the fifth decimal of PSNR)")
+                         "to 1e-10, PSNR to 2e-5 dB -- the host's mean is float32 -- so a score line may differ in the fifth decimal of PSNR; "
+                         "the flag_HD_in configs (.._8K), whose result is `scale` times the ground truth, are scored on the result's bicubic "
+                         "down-scale -- PSNR of the clamped, SSIM of the unclamped image -- which 'device' fuses into the same launch "
+                         "(refvsr_score_frames_down, float64 taps) and 'host' takes from F.interpolate in float32: SSIM then agrees to ~1e-9)")
     args, _ = ap.parse_known_args(argv)
     cfg = get_config(args.project, args.mode, args.config, args.data)
     cfg.result_dtype = args.result_dtype

@@ -152,6 +152,8 @@ SIGNATURES = {
     # frame scores on the device (added symbols, ABI 15 unchanged)
     'refvsr_score_frames': [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P],
     'refvsr_score_max_frames': [],               # returns REFVSR_SCORE_MAX_FRAMES
+    # the same with the bicubic down-scale of a `down` times larger result fused in (added symbol, ABI 15 unchanged)
+    'refvsr_score_frames_down': [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P],
     # rectangle sums for the field-of-view evaluation (added symbols, ABI 15 unchanged)
     'refvsr_score_regions': [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _Z, _P, _P],
     'refvsr_score_max_rects': [],                # returns REFVSR_SCORE_MAX_RECTS

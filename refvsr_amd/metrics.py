@@ -106,6 +106,49 @@ def score_frames_model(a, b, tile=TILE, win=7):
     return float(mse), float(ssim)
 
 
+# ------------------------------------------------------------------------------------------------ down-scaled scoring (flag_HD_in)
+DOWN_W = (-3.0 / 32.0, 19.0 / 32.0, 19.0 / 32.0, -3.0 / 32.0)      # Keys' cubic, A = -0.75, at the fraction 1 / 2: exact in binary
+
+
+def _down_taps(n, s):
+    """[4][n] source indices of the n output positions along an axis of s n samples: i0 = s x + s / 2 - 2, clamped into the axis."""
+    i0 = s * np.arange(n) + s // 2 - 2
+    return [np.clip(i0 + k, 0, s * n - 1) for k in range(4)]
+
+
+def _down_axis(x, s, axis, weights, taps):
+    """One pass of the down-scale along `axis`: the four weighted taps added first to last."""
+    t = taps(x.shape[axis] // s, s)
+    sl = lambda k: np.float64(weights[k]) * np.take(x, t[k], axis=axis)
+    acc = sl(0) + sl(1)
+    acc = acc + sl(2)
+    return acc + sl(3)
+
+
+def down_bicubic_model(a, s, weights=DOWN_W, taps=_down_taps):
+    """float32 [3, h, w]: the bicubic down-scale by s = 2 | 4 of a float32 [3, s h, s w] frame (numpy or torch), the image both
+    reference definitions score at an exact integer factor --
+      models/loss/Loss.py:91-92   F.interpolate(sr, scale_factor=1 / scale, mode='bicubic', align_corners=False) (.clamp(0, 1), PSNR :141)
+      evaluation/eval_qual_quan.py:85-92   cv2.resize(output, fx=1 / scale, fy=1 / scale, INTER_CUBIC) (not clamped, SSIM)
+    -- as refvsr_score_frames_down computes it (csrc/score.hip): float64 on the float32 value of every sample; horizontal pass
+    W0 a[i0] + W1 a[i0 + 1] + W2 a[i0 + 2] + W3 a[i0 + 3] added left to right, i0 = s x + s / 2 - 2, indices clamped to [0, n - 1];
+    vertical pass the same over the four row sums, top to bottom; rounded once to float32.
+    (weights, taps: the definition's two ingredients, which the tests replace by wrong ones to show that their bars can tell.)"""
+    a = _as64(a)
+    assert s in (2, 4) and a.ndim == 3 and a.shape[0] == 3 and a.shape[1] % s == 0 and a.shape[2] % s == 0
+    return _down_axis(_down_axis(a, s, 2, weights, taps), s, 1, weights, taps).astype(np.float32)
+
+
+def score_frames_down_model(a, g, s, win=7):
+    """(mse, ssim) of one result a [3, s h, s w] against the ground truth g [3, h, w] as refvsr_score_frames_down computes them: with
+    D = down_bicubic_model(a, s), the mse of score_frames_model on clip(D, 0, 1) (Loss.py:92,141 clamps before the PSNR) and its ssim
+    on the unclamped D (eval_qual_quan.py:85-92 does not clamp)."""
+    d = down_bicubic_model(a, s)
+    mse, _ = score_frames_model(np.clip(d, np.float32(0), np.float32(1)), g, win=0)
+    _, ssim = score_frames_model(d, g, win=win) if win else (0.0, 0.0)
+    return mse, ssim
+
+
 # ------------------------------------------------------------------------------------------------ field-of-view evaluation
 FOV_KEYS = (1, 0.9, 0.8, 0.7, 0.6, 0.5)        # eval_quan_FOV.py:26
 MAX_RECTS = 8                                   # REFVSR_SCORE_MAX_RECTS

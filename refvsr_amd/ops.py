@@ -746,18 +746,22 @@ def ingest_frames(x):
 _SCORE_WS = {}        # (device, stream handle, h, w) -> workspace of one full refvsr_score_frames launch
 
 
-def _score_inputs(outs, gts, what):
-    """The frame pairs of a scorer call, checked: (results, ground truths, h, w, result format, ground-truth format, layout)."""
+def _score_inputs(outs, gts, what, down=1):
+    """The frame pairs of a scorer call, checked: (results, ground truths, h, w, result format, ground-truth format, layout); h, w are
+    the ground truth's, the results are [3, down h, down w]."""
     outs, gts = list(outs), list(gts)
     assert outs and len(outs) == len(gts), '%s: as many results as ground truths' % what
     a0, g0 = outs[0], gts[0]
-    _, h, w = a0.shape
+    _, h, w = a0.shape if down == 1 else g0.shape
     fmts = {torch.float32: hip.RESULT_F32, torch.float16: hip.RESULT_F16, torch.uint8: hip.RESULT_U8}
     assert a0.dtype in fmts and g0.dtype in (torch.float32, torch.uint8), '%s: float32 | float16 | uint8 results, float32 | uint8 ground truth' % what
     lay = u8_layout(g0) if g0.dtype == torch.uint8 else hip.INGEST_PLANAR
     for a, g in zip(outs, gts):
-        if a.shape != (3, h, w) or g.shape != (3, h, w):
+        if down == 1 and (a.shape != (3, h, w) or g.shape != (3, h, w)):
             raise RuntimeError('%s: result %s and ground truth %s must both be [3, %d, %d]' % (what, tuple(a.shape), tuple(g.shape), h, w))
+        if down != 1 and (a.shape != (3, down * h, down * w) or g.shape != (3, h, w)):
+            raise RuntimeError('%s: result %s and ground truth %s must both be [3, %d, %d] after the down-scale by %d (the result %d times that)'
+                               % (what, tuple(a.shape), tuple(g.shape), h, w, down, down))
         assert a.is_cuda and g.is_cuda and a.dtype == a0.dtype and g.dtype == g0.dtype and a.is_contiguous()
         assert (u8_layout(g) if g.dtype == torch.uint8 else (hip.INGEST_PLANAR if g.is_contiguous() else None)) == lay and lay is not None, \
             '%s: ground-truth frames must be dense and of one layout' % what
@@ -777,13 +781,18 @@ def _score_workspace(cache, dev, st, h, w, nbytes, what):
     return ws
 
 
-def score_frames(outs, gts, win=7):
+def score_frames(outs, gts, win=7, down=1):
     """{mse, ssim} of B (result, ground truth) pairs of one 3 x h x w geometry, computed on the device (refvsr_score_frames): a
     torch.float64 [B, 2] tensor on the current stream, no synchronisation.  outs: [B,3,h,w] tensor or B tensors [3,h,w], contiguous
     float32 / float16 / uint8 (what the output head stores; a byte means byte / 255); gts: the same shapes, contiguous float32, or
     uint8 planar or channels-last (u8_layout).  win = 7: both numbers; win = 0: the mse alone (ssim field 0).  One launch per
-    REFVSR_SCORE_MAX_FRAMES pairs.  PSNR = metrics.psnr_from_mse(mse) on the host."""
-    outs, gts, h, w, afmt, gfmt, lay = _score_inputs(outs, gts, 'score_frames')
+    REFVSR_SCORE_MAX_FRAMES pairs.  PSNR = metrics.psnr_from_mse(mse) on the host.
+    down = 2 | 4 (the flag_HD_in configs; refvsr_score_frames_down): outs are [3, down h, down w] against gts [3, h, w]; the kernel
+    forms the bicubic down-scale D of the result while it stages its tiles (metrics.down_bicubic_model) and returns the mse of
+    clamp(D, 0, 1) and the ssim of D."""
+    if down not in (1, 2, 4):
+        raise RuntimeError('score_frames: down must be 1, 2 or 4 (got %r)' % (down,))
+    outs, gts, h, w, afmt, gfmt, lay = _score_inputs(outs, gts, 'score_frames', down)
     st = _stream()
     dev = outs[0].device
     ws = _score_workspace(_SCORE_WS, dev, st, h, w, hip.lib().refvsr_score_workspace_bytes(hip.SCORE_MAX_FRAMES, h, w), 'score_frames')
@@ -792,8 +801,11 @@ def score_frames(outs, gts, win=7):
         n = min(hip.SCORE_MAX_FRAMES, len(outs) - s0)
         pa = (C.c_void_p * n)(*[a.data_ptr() for a in outs[s0:s0 + n]])
         pg = (C.c_void_p * n)(*[g.data_ptr() for g in gts[s0:s0 + n]])
-        hip.check(hip.lib().refvsr_score_frames(pa, afmt, pg, gfmt, lay, n, h, w, int(win), _ptr(ws), ws.numel() * 8,
-                                                C.c_void_p(scores.data_ptr() + 16 * s0), st), 'score_frames')
+        tail = (int(win), _ptr(ws), ws.numel() * 8, C.c_void_p(scores.data_ptr() + 16 * s0), st)
+        if down == 1:
+            hip.check(hip.lib().refvsr_score_frames(pa, afmt, pg, gfmt, lay, n, h, w, *tail), 'score_frames')
+        else:
+            hip.check(hip.lib().refvsr_score_frames_down(pa, afmt, pg, gfmt, lay, n, h, w, int(down), *tail), 'score_frames_down')
     return scores
 
 
