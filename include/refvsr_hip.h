@@ -249,6 +249,24 @@ int refvsr_conv_hr_last(const void* src, int h, int w, const void* blob, float a
  * rint(255 v) of the clamped fp32 value -- the bytes the reference's PNG writer produces -- so that 1/2 or 1/4 of the bytes cross
  * PCIe; refvsr_convert_result does the same conversion on an fp32 result (the generic head of configurations without a fused one). */
 enum { REFVSR_RESULT_F32 = 0, REFVSR_RESULT_F16 = 1, REFVSR_RESULT_U8 = 2 };
+/* Channels-last results (extension, no ABI bump: an added flag bit and an added symbol; without the bit every entry point behaves as
+ * before).  REFVSR_RESULT_HWC is OR-ed into an `out_fmt` argument: the 3 x h x w result is then the dense interleaved array
+ * [h][w][3] -- element (y w + x) 3 + c instead of c h w + y w + x -- which is what image writers, encoders and raw-video pipes
+ * consume (the layout REFVSR_INGEST_HWC names on the way in).  The layout decides the address alone: every value and its rounding
+ * are those of the planar result, bit for bit.
+ *   refvsr_conv_last_fmt / refvsr_conv_hr_last_fmt: `out` is [h][w][3] of the format's samples; one element per lane, the three
+ *     channels of a pixel from neighbouring lane quarters (48 contiguous bytes per 16-pixel group at uint8).  Only element stores:
+ *     `out` needs the natural alignment of its samples, for any w;
+ *   refvsr_convert_result_hwc(src, h, w, out_fmt, out, stream): the generic head -- planar fp32 [3][h][w] `src` -> interleaved
+ *     [h][w][3] fp32 | fp16 | uint8 with the fused heads' clamp and rounding (refvsr_convert_result has no geometry argument);
+ *     out_fmt with or without the bit, src 4-byte aligned, out naturally aligned, src != out, 3 h w < 2^31;
+ *   refvsr_score_frames / refvsr_score_frames_down / refvsr_score_regions: out_fmt | REFVSR_RESULT_HWC reads interleaved results (at
+ *     down = 2 | 4: [down h][down w][3]).  Only the staging index changes; the order of summation depends on position alone, so the
+ *     scores and sums are the float64 bits of the planar frame of the same values.
+ * Any other bit in an out_fmt is refused ("unknown result format"). */
+#define REFVSR_RESULT_FMT_MASK 0x0f
+#define REFVSR_RESULT_HWC 0x10
+int refvsr_convert_result_hwc(const float* src, int h, int w, int out_fmt, void* out, void* stream);
 int refvsr_conv_last_fmt(const void* src, int c, int h, int w, const void* blob, const float* base_lr, int bh, int bw,
                          void* out, int out_fmt, void* stream);
 int refvsr_conv_hr_last_fmt(const void* src, int h, int w, const void* blob, float act_slope, const float* base_lr, int bh, int bw,

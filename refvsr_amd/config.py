@@ -91,6 +91,7 @@ def base_config(project='', mode='', config_='', data='', LRS='', batch_size=8):
     c.overlap_streams = True    # forward-branch step on a side HIP stream, concurrent with the new frame's preparation
     c.fuse_resblocks = True     # conv-act-conv+residual pairs in one launch where the LDS budget allows
     c.result_dtype = 'float32'  # 'float16' | 'uint8': the output head stores rint(255 v) itself (extension; host consumers quantise anyway)
+    c.result_layout = 'chw'     # 'hwc': the result is the [.., 3, sh, sw] view of dense [.., sh, sw, 3] memory (extension; what image writers consume)
     c.weight_precision = 'hi_lo'  # 'fp16' | 'amp': plain fp16 conv weights, the reference's AMP arithmetic (resolve_weight_precision)
     return c
 

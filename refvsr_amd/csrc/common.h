@@ -292,10 +292,20 @@ __device__ __forceinline__ float rv_bicubic_at(const float* __restrict__ s, int 
 // ---- result formats of the output head (ABI 14, REFVSR_RESULT_*): one value v in [0, 1] of the planar [3][h][w] result at element e.
 // U8 = what the reference's consumers make of the fp32 frame on the CPU (evaluation/eval_qual_quan.py:117-119: cv2.imwrite of
 // output * 255 = saturate_cast<uchar>, round to nearest even): rint(v * 255) in fp32, the same two roundings.
+// `fmt` may carry REFVSR_RESULT_HWC: the layout decides the element (rv_result_index), never the value or its rounding.
 __device__ __forceinline__ void rv_store_result(void* out, const size_t e, const float v, const int fmt) {
-    if (fmt == REFVSR_RESULT_F32) reinterpret_cast<float*>(out)[e] = v;
-    else if (fmt == REFVSR_RESULT_F16) reinterpret_cast<f16*>(out)[e] = (f16)v;
+    const int f = fmt & REFVSR_RESULT_FMT_MASK;
+    if (f == REFVSR_RESULT_F32) reinterpret_cast<float*>(out)[e] = v;
+    else if (f == REFVSR_RESULT_F16) reinterpret_cast<f16*>(out)[e] = (f16)v;
     else reinterpret_cast<unsigned char*>(out)[e] = (unsigned char)__float2int_rn(v * 255.0f);
+}
+// element of channel c at (y, x) of a 3 x h x w result: planar [3][h][w], or interleaved [h][w][3] with REFVSR_RESULT_HWC
+__host__ __device__ __forceinline__ size_t rv_result_index(const int fmt, const int c, const int y, const int x, const int h, const int w) {
+    return (fmt & REFVSR_RESULT_HWC) ? ((size_t)y * w + x) * 3 + c : ((size_t)c * h + y) * w + x;
+}
+// host-side check of an out_fmt argument: a known sample format, optionally | REFVSR_RESULT_HWC
+static inline bool rv_result_fmt_ok(const int fmt) {
+    return fmt >= 0 && (fmt & ~(REFVSR_RESULT_FMT_MASK | REFVSR_RESULT_HWC)) == 0 && (fmt & REFVSR_RESULT_FMT_MASK) <= REFVSR_RESULT_U8;
 }
 
 // ---- K-block order of the MFMA convolutions (shared with refvsr_amd/packing.py:kslot) --------------------------

@@ -52,7 +52,7 @@ struct C24Args {
     // COUT = 3 (refvsr_conv_last): `out` is planar fp32 [3][h][w]; base_lr: the LR centre frame, planar fp32 [3][bh][bw], whose
     // bicubic up-sampling (clamped to [0, 1]) is added before the final clamp
     const float* base_lr; int bh, bw; float base_step;
-    int out_fmt;                                 // COUT = 3: REFVSR_RESULT_* of `out`
+    int out_fmt;                                 // COUT = 3: REFVSR_RESULT_* of `out` (| REFVSR_RESULT_HWC)
     // Multi-map launches (refvsr_*_batch, ABI 11): batch > 1 maps of one geometry share the launch and the weight fill; flat tile
     // index t = b * tpm + (tile of map b); map b's operands come from the tables (entry 0 == the scalar fields above, which stay
     // the "operand present" flags).  Not for the HALF variant.
@@ -453,8 +453,12 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(WPS, W
             // ---------------- output head (RefVSR.py:118,288,297): clamp( conv + bias + clamp01(bicubic(lr_centre)), 0, 1 ) -> planar fp32.
             // After the fold lane (0, n) holds the three channel sums of pixel n of the group; lane (q, n), q < 3, takes channel q
             // (ds_bpermute), evaluates ITS channel's bicubic sample (rv_bicubic_at: resize_kernel<BICUBIC>'s FMA chains) and stores one
-            // value: 48 lanes x 4 bytes = three 64-byte row segments per group
-            const size_t plane_o = (size_t)p.h * p.w, plane_b = (size_t)p.bh * p.bw;
+            // value: 48 lanes x 4 bytes = three 64-byte row segments per group (planar), or with REFVSR_RESULT_HWC one 192-byte segment
+            // [16 pixels][3], lane (q, n) on element 3 lp + q (rv_result_index: the layout moves the address, never the value; a variant
+            // with lane e on element e -- one contiguous run per wave -- scatters the lanes' bicubic taps over the three base planes
+            // and measured 2 - 2.7 x slower, profiles/result_layout_timing.txt).  Resource usage with the layout select
+            // (-Rpass-analysis=kernel-resource-usage): C = 24 88 VGPRs (78 before it), C = 48 104 (94); no scratch, 4 waves per SIMD as before
+            const size_t plane_b = (size_t)p.bh * p.bw;
 #pragma unroll
             for (int t = 0; t < T; ++t) {
                 const f32x4 y = acc[0][t];
@@ -467,7 +471,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(WPS, W
                 const int oy = ty0 + RW(t), ox = tx0 + CG(t) * 16 + lpe;
                 if (q < 3 && oy < p.h && ox < p.w) {
                     const float b = fminf(fmaxf(rv_bicubic_at(p.base_lr + q * plane_b, p.bh, p.bw, oy, ox, p.base_step, p.base_step), 0.0f), 1.0f);
-                    rv_store_result(outp, q * plane_o + (size_t)oy * p.w + ox, fminf(fmaxf(v + b, 0.0f), 1.0f), p.out_fmt);
+                    rv_store_result(outp, rv_result_index(p.out_fmt, q, oy, ox, p.h, p.w), fminf(fmaxf(v + b, 0.0f), 1.0f), p.out_fmt);
                 }
             }
         } else if constexpr (SHUF != 0) {
@@ -857,7 +861,7 @@ extern "C" int refvsr_conv_last(const void* src, int c, int h, int w, const void
 }
 extern "C" int refvsr_conv_last_fmt(const void* src, int c, int h, int w, const void* blob, const float* base_lr, int bh, int bw,
                                     void* out, int out_fmt, void* stream) {
-    RV_CHECK(out_fmt >= REFVSR_RESULT_F32 && out_fmt <= REFVSR_RESULT_U8, "conv_last: unknown result format %d", out_fmt);
+    RV_CHECK(rv_result_fmt_ok(out_fmt), "conv_last: unknown result format %d", out_fmt);
     RV_CHECK(refvsr_conv_last_supported(c), "conv_last: %d input channels not supported (24 | 48)", c);
     RV_CHECK(base_lr && bh > 0 && bw > 0 && h % bh == 0 && w % bw == 0 && h / bh == w / bw, "conv_last: base frame %dx%d does not divide the output %dx%d", bh, bw, h, w);
     C24Args a;

@@ -519,3 +519,28 @@ extern "C" int refvsr_convert_result(const float* src, size_t n, int out_fmt, vo
     RV_LAUNCH_CHECK();
     return 0;
 }
+
+// ... into the interleaved layout (REFVSR_RESULT_HWC; extension, no ABI bump): planar fp32 [3][h][w] -> [h][w][3] fp32 | fp16 | uint8 with
+// the same clamp and rounding (rv_store_result).  One thread per pixel: a wave reads 64 consecutive floats of each plane (three
+// coalesced 256-byte reads) and writes the 192 consecutive elements of its 64 pixels, three per lane.  Element stores only: `out`
+// needs the natural alignment of its samples, for any w.
+__global__ void __launch_bounds__(256) convert_result_hwc_kernel(const float* __restrict__ src, int npix, int fmt, void* __restrict__ out) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= npix) return;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        rv_store_result(out, (size_t)i * 3 + c, fminf(fmaxf(src[(size_t)c * npix + i], 0.f), 1.f), fmt);
+}
+
+extern "C" int refvsr_convert_result_hwc(const float* src, int h, int w, int out_fmt, void* out, void* stream) {
+    RV_CHECK(src && out && h > 0 && w > 0 && (const void*)src != out, "convert_result_hwc: bad args");
+    RV_CHECK(rv_result_fmt_ok(out_fmt), "convert_result_hwc: unknown result format %d", out_fmt);
+    RV_CHECK((long long)h * w * 3 < (1ll << 31), "convert_result_hwc: frame too large (3 h w must stay below 2^31)");
+    const int f = out_fmt & REFVSR_RESULT_FMT_MASK;
+    RV_CHECK(((uintptr_t)src & 3) == 0 && ((uintptr_t)out & (f == REFVSR_RESULT_F32 ? 3 : f == REFVSR_RESULT_F16 ? 1 : 0)) == 0,
+             "convert_result_hwc: src must be 4-byte aligned, out aligned to its samples");
+    const int npix = h * w;
+    hipLaunchKernelGGL(convert_result_hwc_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, npix, out_fmt, out);
+    RV_LAUNCH_CHECK();
+    return 0;
+}

@@ -72,7 +72,7 @@ struct RB24Args {
     int probe_iter;                      // which tile iteration of the workgroup is stamped
     // HEAD kernels (refvsr_conv_hr_last): `out` is planar fp32 [3][h][w]; base_lr = the LR centre frame, planar fp32 [3][bh][bw]
     const float* base_lr; int bh, bw; float base_step;
-    int out_fmt;                         // HEAD kernels: REFVSR_RESULT_* of `out` (planar [3][h][w])
+    int out_fmt;                         // HEAD kernels: REFVSR_RESULT_* of `out` (planar [3][h][w]; | REFVSR_RESULT_HWC: [h][w][3])
     // Multi-map launches (refvsr_resblock24_chain_batch): batch > 1 maps of one geometry share the launch and the weight fill; the
     // flat tile index t = b * tpm + (tile of map b), map b reads bsrc[b] and writes bout[b].  batch <= 1: src / out above.
     int batch, tpm;
@@ -468,7 +468,8 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV ==
         if constexpr (HEAD != 0) {
             // clamp( conv_last + bias + clamp01(bicubic(lr_centre)), 0, 1 ) -> planar fp32: after the fold lane (0, n) holds the
             // three channel sums of pixel n, lane (q, n), q < 3, takes channel q and evaluates ITS channel's bicubic sample
-            const size_t plane_o = (size_t)p.h * p.w, plane_b = (size_t)p.bh * p.bw;
+            const size_t plane_b = (size_t)p.bh * p.bw;                 // (REFVSR_RESULT_HWC: rv_result_index moves the address alone;
+            // the 16-wave HEAD kernel 126 VGPRs with it, 124 before, the 8-wave one unchanged; no scratch, 4 waves per SIMD)
 #pragma unroll
             for (int t = 0; t < T2; ++t) {
                 const f32x4 y = c0[t];
@@ -481,7 +482,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV ==
                 const int oy = ty0 + oy0 + (t >> 1), ox = tx0 + (t & 1) * 16 + lpe;
                 if (q < 3 && oy < p.h && ox < p.w) {
                     const float b = fminf(fmaxf(rv_bicubic_at(p.base_lr + q * plane_b, p.bh, p.bw, oy, ox, p.base_step, p.base_step), 0.0f), 1.0f);
-                    rv_store_result(outp, q * plane_o + (size_t)oy * p.w + ox, fminf(fmaxf(v + b, 0.0f), 1.0f), p.out_fmt);
+                    rv_store_result(outp, rv_result_index(p.out_fmt, q, oy, ox, p.h, p.w), fminf(fmaxf(v + b, 0.0f), 1.0f), p.out_fmt);
                 }
             }
         } else if constexpr (STORE == 0) {
@@ -641,7 +642,7 @@ extern "C" int refvsr_conv_hr_last(const void* src, int h, int w, const void* bl
 extern "C" int refvsr_conv_hr_last_fmt(const void* src, int h, int w, const void* blob, float act_slope, const float* base_lr, int bh, int bw,
                                        void* out, int out_fmt, void* stream) {
     RV_CHECK(src && out && blob && base_lr && h > 0 && w > 0, "conv_hr_last: bad args");
-    RV_CHECK(out_fmt >= REFVSR_RESULT_F32 && out_fmt <= REFVSR_RESULT_U8, "conv_hr_last: unknown result format %d", out_fmt);
+    RV_CHECK(rv_result_fmt_ok(out_fmt), "conv_hr_last: unknown result format %d", out_fmt);
     RV_CHECK(((uintptr_t)blob & 15) == 0, "conv_hr_last: blob must be 16-byte aligned");
     RV_CHECK(act_slope > 0.f && act_slope <= 1.f, "conv_hr_last: activation slope must lie in (0, 1]");
     RV_CHECK(bh > 0 && bw > 0 && h % bh == 0 && w % bw == 0 && h / bh == w / bw, "conv_hr_last: base frame %dx%d does not divide the output %dx%d", bh, bw, h, w);

@@ -16,7 +16,8 @@
 // anywhere, so the rounding error of a window does not depend on the image size.  Wave-wide LDS reads are 64 consecutive floats
 // (ds_read_b32, conflict free for any row pitch).
 // Loads are one element per lane (4-, 2- or 1-byte, consecutive lanes on consecutive samples of a tile row; an interleaved ground truth
-// at a 3-byte stride), so pointers only need the natural alignment of their element type: fp32 4 bytes, fp16 2 bytes, bytes none.
+// at a 3-byte stride, an interleaved result -- out_fmt | REFVSR_RESULT_HWC -- at a stride of three samples: the staging index alone
+// differs, so the scores are the planar frame's bits), so pointers only need the natural alignment of their element type: fp32 4 bytes, fp16 2 bytes, bytes none.
 //
 // MSE: every sample belongs to exactly one tile (the last tile of a row / column of tiles owns its 6 halo columns / rows); the thread
 // that stages it adds (a - b)^2 to its own float64 sum.
@@ -65,7 +66,8 @@ struct ScoreArgs {
     const void* b[REFVSR_SCORE_MAX_FRAMES];
     double* part;                      // [nframes][3][nty * ntx][2] partial sums {sum (a - b)^2, sum ssim}
     int h, w, ntx, nty;
-    int afmt;                          // REFVSR_RESULT_*
+    int afmt;                          // REFVSR_RESULT_* (the sample format alone)
+    int ahwc;                          // results are interleaved [h][w][3] (REFVSR_RESULT_HWC)
     int bkind;                         // SC_GT_*
     int win;                           // 7 | 0
     int avec;                          // DOWN = 4: every result pointer is aligned to four samples (one load per tap row)
@@ -88,7 +90,7 @@ __device__ __forceinline__ double sc_block_sum(double* red, const int tid, const
 // D(y, x) of result plane c, rounded once to float32: the bicubic down-scale by DOWN = 2 | 4 of the big frame [3][DOWN h][DOWN w] at
 // ground-truth position (y, x) (the file header).  avec (DOWN = 4 only): one load per tap row
 template <int DOWN>
-__device__ __forceinline__ float sc_down_sample(const unsigned char* __restrict__ pa, const float* tbl, const int afmt, const int avec,
+__device__ __forceinline__ float sc_down_sample(const unsigned char* __restrict__ pa, const float* tbl, const int afmt, const int avec, const int ahwc,
                                                 const int c, const int y, const int x, const int h, const int w) {
     static_assert(DOWN == 2 || DOWN == 4, "integer factors whose source coordinate has the fraction 1 / 2");
     constexpr double W0 = -3.0 / 32.0, W1 = 19.0 / 32.0;
@@ -101,7 +103,9 @@ __device__ __forceinline__ float sc_down_sample(const unsigned char* __restrict_
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int yy = DOWN == 4 ? i0y + j : min(max(i0y + j, 0), bh - 1);
-        const size_t row = ((size_t)c * bh + yy) * (size_t)bw;   // planar [3][bh][bw]
+        // planar [3][bh][bw]: element row + x; interleaved [bh][bw][3]: element row + 3 x (avec is off: a tap row is not one group)
+        const size_t row = ahwc ? (size_t)yy * (size_t)bw * 3 + (size_t)c : ((size_t)c * bh + yy) * (size_t)bw;
+        const size_t xs = ahwc ? 3 : 1;
         float t[4];
         if (DOWN == 4 && avec) {                                  // row + xi[0] is a multiple of 4 samples, the pointer of 4 samples
             const size_t i4 = (row + (size_t)xi[0]) >> 2;
@@ -118,7 +122,7 @@ __device__ __forceinline__ float sc_down_sample(const unsigned char* __restrict_
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const size_t ip = row + (size_t)xi[k];
+                const size_t ip = row + xs * (size_t)xi[k];
                 if (afmt == REFVSR_RESULT_F32) t[k] = reinterpret_cast<const float*>(pa)[ip];
                 else if (afmt == REFVSR_RESULT_F16) t[k] = (float)reinterpret_cast<const f16*>(pa)[ip];
                 else t[k] = tbl[pa[ip]];
@@ -135,10 +139,10 @@ __device__ __forceinline__ float sc_down_sample(const unsigned char* __restrict_
     return (float)d;
 }
 
-// score_tile_kernel<1>: 104 VGPRs, 43 SGPRs, no scratch, no spills, 24 352 B LDS, 4 waves per SIMD by registers (figures of the build
+// score_tile_kernel<1>: 104 VGPRs, 47 SGPRs, no scratch, no spills, 24 352 B LDS, 4 waves per SIMD by registers (figures of the build
 // this file was written against -- re-check with -Rpass-analysis=kernel-resource-usage after a change; re-checked when the kernel
-// became a template: the same figures as before it).  score_tile_kernel<2>: 104 VGPRs, 53 SGPRs; score_tile_kernel<4>: 104 VGPRs,
-// 55 SGPRs; both no scratch, 24 352 B LDS, 4 waves per SIMD -- the sixteen taps live only in the staging loop, before the row ring
+// became a template: the same figures as before it).  score_tile_kernel<2>: 104 VGPRs, 59 SGPRs; score_tile_kernel<4>: 104 VGPRs,
+// 61 SGPRs (re-checked with the interleaved result layout: 4-6 SGPRs more, nothing else moved); both no scratch, 24 352 B LDS, 4 waves per SIMD -- the sixteen taps live only in the staging loop, before the row ring
 template <int DOWN>
 __global__ void __launch_bounds__(SC_THREADS) score_tile_kernel(ScoreArgs s) {
     __shared__ float tbl[256];
@@ -165,11 +169,12 @@ __global__ void __launch_bounds__(SC_THREADS) score_tile_kernel(ScoreArgs s) {
         if (y < h && x < w) {
             const size_t ip = ((size_t)c * h + y) * w + x;       // planar [3][h][w]
             if constexpr (DOWN == 1) {
-                if (s.afmt == REFVSR_RESULT_F32) va = reinterpret_cast<const float*>(pa)[ip];
-                else if (s.afmt == REFVSR_RESULT_F16) va = (float)reinterpret_cast<const f16*>(pa)[ip];
-                else va = tbl[pa[ip]];
+                const size_t ia = s.ahwc ? ((size_t)y * w + x) * 3 + c : ip;     // interleaved [h][w][3] result
+                if (s.afmt == REFVSR_RESULT_F32) va = reinterpret_cast<const float*>(pa)[ia];
+                else if (s.afmt == REFVSR_RESULT_F16) va = (float)reinterpret_cast<const f16*>(pa)[ia];
+                else va = tbl[pa[ia]];
             } else {
-                va = sc_down_sample<DOWN>(pa, tbl, s.afmt, s.avec, c, y, x, h, w);
+                va = sc_down_sample<DOWN>(pa, tbl, s.afmt, s.avec, s.ahwc, c, y, x, h, w);
             }
             if (s.bkind == SC_GT_F32) vb = reinterpret_cast<const float*>(pb)[ip];
             else if (s.bkind == SC_GT_U8_PLANAR) vb = tbl[pb[ip]];
@@ -274,8 +279,9 @@ static int sc_run(const char* who, const void* const* out, int out_fmt, const vo
     RV_CHECK(nframes >= 1 && nframes <= REFVSR_SCORE_MAX_FRAMES, "%s: 1..%d frames per launch", who, REFVSR_SCORE_MAX_FRAMES);
     RV_CHECK(sc_geometry_ok(h, w), "%s: h, w must be at least 7 (the SSIM window) and h * w at most 2^29", who);
     RV_CHECK(win == 7 || win == 0, "%s: win must be 7, or 0 for the mse alone", who);
-    RV_CHECK(out_fmt == REFVSR_RESULT_F32 || out_fmt == REFVSR_RESULT_F16 || out_fmt == REFVSR_RESULT_U8,
-             "%s: result format must be REFVSR_RESULT_F32 | _F16 | _U8", who);
+    RV_CHECK(rv_result_fmt_ok(out_fmt), "%s: unknown result format %d (REFVSR_RESULT_F32 | _F16 | _U8, optionally | REFVSR_RESULT_HWC)", who, out_fmt);
+    const int ahwc = (out_fmt & REFVSR_RESULT_HWC) != 0;
+    out_fmt &= REFVSR_RESULT_FMT_MASK;
     RV_CHECK(gt_fmt == REFVSR_RESULT_F32 || gt_fmt == REFVSR_RESULT_U8, "%s: ground-truth format must be REFVSR_RESULT_F32 | _U8", who);
     RV_CHECK(gt_layout == REFVSR_INGEST_PLANAR || gt_layout == REFVSR_INGEST_HWC,
              "%s: ground-truth layout must be REFVSR_INGEST_PLANAR | REFVSR_INGEST_HWC", who);
@@ -288,7 +294,7 @@ static int sc_run(const char* who, const void* const* out, int out_fmt, const vo
     memset(&a, 0, sizeof(a));
     const uintptr_t amask = out_fmt == REFVSR_RESULT_F32 ? 3 : out_fmt == REFVSR_RESULT_F16 ? 1 : 0;
     const uintptr_t bmask = gt_fmt == REFVSR_RESULT_F32 ? 3 : 0;
-    a.avec = down == 4;
+    a.avec = down == 4 && !ahwc;                                 // (an interleaved tap row is not one aligned group of four)
     for (int i = 0; i < nframes; ++i) {
         RV_CHECK(out[i] && gt[i], "%s: null pointer (frame %d)", who, i);
         RV_CHECK(((uintptr_t)out[i] & amask) == 0 && ((uintptr_t)gt[i] & bmask) == 0,
@@ -300,7 +306,7 @@ static int sc_run(const char* who, const void* const* out, int out_fmt, const vo
     a.part = (double*)workspace;
     a.h = h; a.w = w;
     a.ntx = sc_tiles(w, SC_TW); a.nty = sc_tiles(h, SC_TH);
-    a.afmt = out_fmt;
+    a.afmt = out_fmt; a.ahwc = ahwc;
     a.bkind = gt_fmt == REFVSR_RESULT_F32 ? SC_GT_F32 : gt_layout == REFVSR_INGEST_PLANAR ? SC_GT_U8_PLANAR : SC_GT_U8_HWC;
     a.win = win;
     const int nt = a.ntx * a.nty;
@@ -355,7 +361,8 @@ struct RegionArgs {
     const void* b[REFVSR_SCORE_MAX_FRAMES];
     double* part;                      // [nframes][3][nty * ntx][nrects][2] partial sums {sum (a - b)^2, sum S}
     int h, w, ntx, nty;
-    int afmt;                          // REFVSR_RESULT_*
+    int afmt;                          // REFVSR_RESULT_* (the sample format alone)
+    int ahwc;                          // results are interleaved [h][w][3] (REFVSR_RESULT_HWC)
     int bkind;                         // SC_GT_*
     int nrects;
     int rect[REFVSR_SCORE_MAX_RECTS][4];   // y0, y1, x0, x1 (half-open); entries past nrects are empty
@@ -376,7 +383,7 @@ __device__ __forceinline__ double rg_wave_sum(double v) {
     return v;
 }
 
-// regions_tile_kernel: 132 VGPRs, 61 SGPRs, no scratch, no spills, 22 816 B LDS, 3 waves per SIMD by registers (figures of the build
+// regions_tile_kernel: 132 VGPRs, 64 SGPRs, no scratch, no spills, 22 816 B LDS, 3 waves per SIMD by registers (figures of the build
 // this file was written against -- re-check with -Rpass-analysis=kernel-resource-usage after a change).  The 16 accumulators (32
 // VGPRs) on top of the 35 doubles of the row ring put it past 128 VGPRs, one wave per SIMD fewer than score_tile_kernel: a stated
 // choice -- the kernel streams LDS into float64 adds, three workgroups per CU keep the float64 pipe fed, and a sixteen-sum spill to
@@ -400,10 +407,11 @@ __global__ void __launch_bounds__(SC_THREADS) regions_tile_kernel(RegionArgs s) 
         const int r = e / SC_IW, q = e - r * SC_IW;
         const int y = rg_reflect(y0 - 3 + r, h), x = rg_reflect(x0 - 3 + q, w);      // 0 <= y < h, 0 <= x < w
         const size_t ip = ((size_t)c * h + y) * w + x;           // planar [3][h][w]
+        const size_t ia = s.ahwc ? ((size_t)y * w + x) * 3 + c : ip;             // interleaved [h][w][3] result
         float va, vb;
-        if (s.afmt == REFVSR_RESULT_F32) va = reinterpret_cast<const float*>(pa)[ip];
-        else if (s.afmt == REFVSR_RESULT_F16) va = (float)reinterpret_cast<const f16*>(pa)[ip];
-        else va = tbl[pa[ip]];
+        if (s.afmt == REFVSR_RESULT_F32) va = reinterpret_cast<const float*>(pa)[ia];
+        else if (s.afmt == REFVSR_RESULT_F16) va = (float)reinterpret_cast<const f16*>(pa)[ia];
+        else va = tbl[pa[ia]];
         if (s.bkind == SC_GT_F32) vb = reinterpret_cast<const float*>(pb)[ip];
         else if (s.bkind == SC_GT_U8_PLANAR) vb = tbl[pb[ip]];
         else vb = tbl[pb[((size_t)y * w + x) * 3 + c]];          // interleaved [h][w][3]
@@ -547,8 +555,9 @@ extern "C" int refvsr_score_regions(const void* const* out, int out_fmt, const v
         RV_CHECK(q[0] < q[1] && q[2] < q[3], "score_regions: rectangle %d is empty", r);
         RV_CHECK(q[0] >= 0 && q[1] <= h && q[2] >= 0 && q[3] <= w, "score_regions: rectangle %d leaves the frame", r);
     }
-    RV_CHECK(out_fmt == REFVSR_RESULT_F32 || out_fmt == REFVSR_RESULT_F16 || out_fmt == REFVSR_RESULT_U8,
-             "score_regions: result format must be REFVSR_RESULT_F32 | _F16 | _U8");
+    RV_CHECK(rv_result_fmt_ok(out_fmt), "score_regions: unknown result format %d (REFVSR_RESULT_F32 | _F16 | _U8, optionally | REFVSR_RESULT_HWC)", out_fmt);
+    const int ahwc = (out_fmt & REFVSR_RESULT_HWC) != 0;
+    out_fmt &= REFVSR_RESULT_FMT_MASK;
     RV_CHECK(gt_fmt == REFVSR_RESULT_F32 || gt_fmt == REFVSR_RESULT_U8, "score_regions: ground-truth format must be REFVSR_RESULT_F32 | _U8");
     RV_CHECK(gt_layout == REFVSR_INGEST_PLANAR || gt_layout == REFVSR_INGEST_HWC,
              "score_regions: ground-truth layout must be REFVSR_INGEST_PLANAR | REFVSR_INGEST_HWC");
@@ -572,7 +581,7 @@ extern "C" int refvsr_score_regions(const void* const* out, int out_fmt, const v
     a.part = (double*)workspace;
     a.h = h; a.w = w;
     a.ntx = rg_tiles(w, SC_TW); a.nty = rg_tiles(h, SC_TH);
-    a.afmt = out_fmt;
+    a.afmt = out_fmt; a.ahwc = ahwc;
     a.bkind = gt_fmt == REFVSR_RESULT_F32 ? SC_GT_F32 : gt_layout == REFVSR_INGEST_PLANAR ? SC_GT_U8_PLANAR : SC_GT_U8_HWC;
     a.nrects = nrects;
     for (int r = 0; r < nrects; ++r)

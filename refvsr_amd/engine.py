@@ -268,6 +268,9 @@ class Engine(object):
         # rint(255 v) itself (REFVSR_RESULT_U8: the bytes eval_qual_quan.py:117-119 writes to the PNG), a quarter of the bytes to copy
         self.result_dtype = str(getattr(config, 'result_dtype', None) or 'float32').replace('torch.', '')
         ops.result_format(self.result_dtype)
+        # result layout (extension; default 'chw' = planar): 'hwc' -- the output head stores the frame interleaved (REFVSR_RESULT_HWC),
+        # the result is the [3, sh, sw] view of dense [sh, sw, 3] memory: what image writers and encoders consume, the same values
+        self.result_layout = ops.check_result_layout(getattr(config, 'result_layout', None))
         self._pipe = None
         # stream layout of the pipelined mode when nothing is configured: 'pf_m' for one forward() per frame (round 4); an engine that
         # is driven through forward_group switches to 'pfm' (P | F | M) at its first group: with the backward branches batched the
@@ -925,7 +928,7 @@ class Engine(object):
             if blob is None:
                 from .packing import pack_conv_hr_last
                 blob = self.W.chains['conv_hr_last_blob'] = pack_conv_hr_last(*self.cw('conv_hr').raw, *self.cw('conv_last').raw).to(out.device).contiguous()
-            return ops.conv_hr_last(blob, out, lr_center, act=0.1, result_dtype=self.result_dtype)
+            return ops.conv_hr_last(blob, out, lr_center, act=0.1, result_dtype=self.result_dtype, result_layout=self.result_layout)
         out = ops.conv(self.cw('conv_hr'), out, act=0.1)
         if self.fuse_head and ops.conv_last_ok(self.C, out.shape[0], out.shape[1]):
             # conv_last + the bicubic base + the clamps in one launch: the base map is evaluated per output value
@@ -933,9 +936,10 @@ class Engine(object):
             if blob is None:
                 from .packing import pack_conv_last
                 blob = self.W.chains['conv_last_blob'] = pack_conv_last(*self.cw('conv_last').raw).to(out.device).contiguous()
-            return ops.conv_last(blob, out, lr_center, result_dtype=self.result_dtype)
+            return ops.conv_last(blob, out, lr_center, result_dtype=self.result_dtype, result_layout=self.result_layout)
         base = ops.bicubic_scale(lr_center, self.cfg.scale, clamp01=True)
-        return ops.convert_result(ops.conv(self.cw('conv_last'), out, planar_out=True, res_planar=base, clamp=(0.0, 1.0)), self.result_dtype)
+        return ops.convert_result(ops.conv(self.cw('conv_last'), out, planar_out=True, res_planar=base, clamp=(0.0, 1.0)), self.result_dtype,
+                                  self.result_layout)
 
     # ------------------------------------------------------------------ window bookkeeping
     def _frames(self, lrs, refs, frame_ids=None, ingest=None):

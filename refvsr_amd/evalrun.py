@@ -71,6 +71,7 @@ def write_frame(path, img, quality=None):
     from PIL import Image
     if img.dtype == torch.uint8:
         # config.result_dtype = 'uint8': the output head stored rint(255 x) itself (REFVSR_RESULT_U8) -- the bytes computed below
+        # (config.result_layout = 'hwc': the transposed view is the dense array itself, no strided copy in fromarray)
         im = Image.fromarray(img.detach().cpu().numpy().transpose(1, 2, 0))
     else:
         a = (img.detach().float().cpu().clamp(0, 1).numpy().transpose(1, 2, 0) * 255.0)
@@ -279,22 +280,24 @@ def evaluate(config, net=None, log=print):
         elif fov:
             from .metrics import fov_scores_host
             gt = it['HR_UW']
+            out_cpu = out_cpu.contiguous()           # (host scores are taken on the planar frame whatever --result_layout says)
             if out_cpu.shape != gt.shape:
                 raise RuntimeError('--eval_mode %s: result %s and ground truth %s differ in shape' % (E.eval_mode, tuple(out_cpu.shape), tuple(gt.shape)))
             table = fov_scores_host(out_cpu, gt)
             p, s = float(table[0, 0, 0]), float(table[0, 0, 1])
         elif not getattr(E, 'qualitative_only', False):
             gt = it['HR_UW']
+            sc_cpu = out_cpu.contiguous()            # (host scores are taken on the planar frame whatever --result_layout says)
             if config.flag_HD_in:
                 # the result is `scale` times the ground truth; both scores are those of its bicubic down-scale: the PSNR of the
                 # clamped image (models/loss/Loss.py:91-92,141), the SSIM of the unclamped one (eval_qual_quan.py:85-92, whose
                 # cv2.resize(INTER_CUBIC) is this filter at an exact integer factor)
-                d = F.interpolate(out_cpu[None], scale_factor=1.0 / config.scale, mode='bicubic', align_corners=False)[0]
+                d = F.interpolate(sc_cpu[None], scale_factor=1.0 / config.scale, mode='bicubic', align_corners=False)[0]
                 p = psnr(d.clamp(0, 1), gt)
                 s = ssim(d, gt)
             else:
-                p = psnr(out_cpu, gt)
-                s = ssim(out_cpu, gt)
+                p = psnr(sc_cpu, gt)
+                s = ssim(sc_cpu, gt)
         line = '[EVAL {}|{}|{}][{}/{}][{}/{}] {} PSNR: {:.5f} SSIM: {:.5f} ({:.5f}sec)'.format(
             config.mode, E.data, it['video_name'], it['video_idx'] + 1, it['video_len'], it['frame_idx'] + 1,
             it['frame_len'], it['frame_name'], p, s, dt)
@@ -493,6 +496,10 @@ def build_config(argv=None):
     ap.add_argument('--result_dtype', default='float32', choices=['float32', 'float16', 'uint8'],
                     help="extension: what the output head stores ('uint8' = rint(255 x), the bytes of the written PNG; the scores are then "
                          "those of the quantised frame)")
+    ap.add_argument('--result_layout', default='chw', choices=['chw', 'hwc'],
+                    help="extension: memory layout of the result frames ('hwc' = the output head stores them interleaved, dense [h, w, 3] "
+                         "under the unchanged [3, h, w] shape: the image writer gets its array without a host-side transposition; same "
+                         "scores and image bytes)")
     ap.add_argument('--input_dtype', default='float32', choices=['float32', 'uint8'],
                     help="extension: what the loader hands the network ('uint8' = the decoded bytes, converted exactly on the device: "
                          "a quarter of the bytes in host memory and across PCIe; same scores and PNG bytes)")
@@ -509,6 +516,7 @@ def build_config(argv=None):
     args, _ = ap.parse_known_args(argv)
     cfg = get_config(args.project, args.mode, args.config, args.data)
     cfg.result_dtype = args.result_dtype
+    cfg.result_layout = args.result_layout
     cfg.weight_precision = args.weight_precision
     cfg.input_dtype = args.input_dtype
     if args.network:

@@ -143,6 +143,10 @@ class Network(nn.Module):
             self._engines.append(self._engine_cls(self.config, W))
         return self._engines
 
+    def _stack(self, results):
+        """n results [3,sh,sw] -> [n,3,sh,sw] in the engines' result layout (config.result_layout = 'hwc': dense [n,sh,sw,3] memory)."""
+        return ops.stack_results(results, self._engines[0].result_layout)
+
     def forward(self, lrs, refs, is_first_frame, is_log=False, is_train=False, frame_ids=None, input_ready=None):
         """Same contract as RefVSR.py:151: lrs, refs [n,t,3,h,w] in [0,1] (or uint8: byte / 255, see _inputs); returns OrderedDict with
         'result' [n,3,4h,4w] (+ 'eval_vis' when is_log and config.save_sample).
@@ -171,7 +175,7 @@ class Network(nn.Module):
             res = self._engine_cls.forward_multi(self._engines[:n], lrs, refs, bool(is_first_frame),
                                                  [[(b, f) for f in frame_ids] for b in range(n)], input_ready)
             outs = collections.OrderedDict()
-            outs['result'] = torch.stack(res, 0)
+            outs['result'] = self._stack(res)
             return outs
         for b in range(n):
             out, vis = self._engines[b].forward(lrs[b], refs[b], bool(is_first_frame), want_vis,
@@ -185,7 +189,7 @@ class Network(nn.Module):
         outs = collections.OrderedDict()
         if is_log:                                             # RefVSR.py:162-164,219-221,262-263,301-316
             outs['vis'] = collections.OrderedDict((k, torch.stack([d[k] for d in dbg_all], 0)) for k in dbg_all[0])
-        outs['result'] = results[0].unsqueeze(0) if n == 1 else torch.stack(results, 0)     # (n == 1: a view, no 25 MB copy)
+        outs['result'] = results[0].unsqueeze(0) if n == 1 else self._stack(results)        # (n == 1: a view, no 25 MB copy)
         if want_vis and vis_all[0] is not None:                # (RefVSR_IR has no 'eval_vis')
             ev = collections.OrderedDict()
             for k in vis_all[0]:
@@ -260,7 +264,7 @@ class Network(nn.Module):
         outs = collections.OrderedDict()
         if is_log:
             outs['vis'] = collections.OrderedDict()
-        outs['result'] = res[0][0].unsqueeze(0) if len(res) == 1 else torch.stack([r[0] for r in res], 0)
+        outs['result'] = res[0][0].unsqueeze(0) if len(res) == 1 else self._stack([r[0] for r in res])
         if want_vis:
             ev = collections.OrderedDict()
             for k in res[0][1]:
@@ -277,7 +281,7 @@ class Network(nn.Module):
         outs = collections.OrderedDict()
         if is_log:
             outs['vis'] = collections.OrderedDict()
-        outs['result'] = res[0][0].unsqueeze(0) if len(res) == 1 else torch.stack([r[0] for r in res], 0)
+        outs['result'] = res[0][0].unsqueeze(0) if len(res) == 1 else self._stack([r[0] for r in res])
         if want_vis:
             ev = collections.OrderedDict()
             for k in res[0][1]:

@@ -472,9 +472,55 @@ def result_format(name):
     return RESULT_DTYPES[key]
 
 
-def convert_result(x, result_dtype):
-    """fp32 result in [0, 1] -> fp16 | uint8 = rint(255 x) (refvsr_convert_result: what the fused heads store directly)."""
+RESULT_LAYOUTS = ('chw', 'hwc')
+
+
+def check_result_layout(name):
+    """config.result_layout resolved: 'chw' (planar [3, h, w] memory; None = 'chw') | 'hwc' (the channels-last view of dense [h, w, 3]
+    memory, REFVSR_RESULT_HWC: what image writers and encoders consume; the logical shape and the values do not change)."""
+    key = str(name or 'chw')
+    if key not in RESULT_LAYOUTS:
+        raise ValueError("result_layout must be 'chw' or 'hwc', got %r" % (name,))
+    return key
+
+
+def _result_empty(h, w, dt, device, layout):
+    """An uninitialised [3, h, w] result of the layout (hwc: the view of a dense [h, w, 3] array) and the flag for its out_fmt."""
+    if check_result_layout(layout) == 'hwc':
+        return torch.empty((h, w, 3), dtype=dt, device=device).permute(2, 0, 1), hip.RESULT_HWC
+    return torch.empty((3, h, w), dtype=dt, device=device), 0
+
+
+def stack_results(frames, layout=None):
+    """[3, h, w] results -> [n, 3, h, w]; with 'hwc' the dense [n, h, w, 3] array viewed channels-first (a plain torch.stack would
+    re-planarise the frames)."""
+    if check_result_layout(layout) == 'hwc':
+        return torch.stack([f.permute(1, 2, 0) for f in frames]).permute(0, 3, 1, 2)
+    return torch.stack(frames)
+
+
+def result_layout_of(x):
+    """'chw' | 'hwc' of a result [..., 3, h, w] by its strides (any dtype): contiguous, or the channels-last view of dense
+    [..., h, w, 3] memory; None for any other strides.  (A frame both describe, e.g. h = w = 1, counts as 'chw'.)"""
+    if x.dim() < 3 or x.shape[-3] != 3:
+        return None
+    if x.is_contiguous():
+        return 'chw'
+    if x.movedim(-3, -1).is_contiguous():
+        return 'hwc'
+    return None
+
+
+def convert_result(x, result_dtype, result_layout=None):
+    """fp32 planar result in [0, 1] -> fp16 | uint8 = rint(255 x) (refvsr_convert_result: what the fused heads store directly);
+    result_layout = 'hwc': the same values as the channels-last view of dense [h, w, 3] memory (refvsr_convert_result_hwc; x [3, h, w])."""
     dt, fmt = result_format(result_dtype)
+    if check_result_layout(result_layout) == 'hwc':
+        _planar(x, 3)
+        h, w = x.shape[1:]
+        out, flag = _result_empty(h, w, dt, x.device, 'hwc')
+        hip.check(hip.lib().refvsr_convert_result_hwc(_ptr(x), h, w, fmt | flag, _ptr(out), _stream()), 'convert_result_hwc')
+        return out
     if fmt == hip.RESULT_F32:
         return x
     assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
@@ -483,31 +529,31 @@ def convert_result(x, result_dtype):
     return out
 
 
-def conv_last(blob, src, base_lr, result_dtype=None):
+def conv_last(blob, src, base_lr, result_dtype=None, result_layout=None):
     """refvsr_conv_last: clamp(conv3x3_{C->3}(src) + bias + clamp01(bicubic(base_lr)), 0, 1) -> planar [3, h, w] in one launch (fp32, or
-    result_dtype = 'float16' | 'uint8': REFVSR_RESULT_*).
+    result_dtype = 'float16' | 'uint8': REFVSR_RESULT_*; result_layout = 'hwc': the same [3, h, w] tensor over dense [h, w, 3] memory).
     blob: packing.pack_conv_last on the device; src nhwc16 [h, w, C]; base_lr planar fp32 [3, h / s, w / s]."""
     _nhwc(src)
     _planar(base_lr, 3)
     h, w, c = src.shape
     bh, bw = base_lr.shape[1:]
     dt, fmt = result_format(result_dtype)
-    out = torch.empty((3, h, w), dtype=dt, device=src.device)
-    hip.check(hip.lib().refvsr_conv_last_fmt(_ptr(src), c, h, w, _ptr(blob), _ptr(base_lr), bh, bw, _ptr(out), fmt, _stream()), 'conv_last')
+    out, flag = _result_empty(h, w, dt, src.device, result_layout)
+    hip.check(hip.lib().refvsr_conv_last_fmt(_ptr(src), c, h, w, _ptr(blob), _ptr(base_lr), bh, bw, _ptr(out), fmt | flag, _stream()), 'conv_last')
     return out
 
 
-def conv_hr_last(blob, src, base_lr, act=0.1, result_dtype=None):
+def conv_hr_last(blob, src, base_lr, act=0.1, result_dtype=None, result_layout=None):
     """refvsr_conv_hr_last: clamp(conv_last(lrelu(conv_hr(src))) + clamp01(bicubic(base_lr)), 0, 1) -> planar [3, h, w], one launch
-    (mid_channels = 24; fp32, or result_dtype = 'float16' | 'uint8').  blob: packing.pack_conv_hr_last on the device."""
+    (mid_channels = 24; fp32, or result_dtype = 'float16' | 'uint8'; result_layout as conv_last).  blob: packing.pack_conv_hr_last on the device."""
     _nhwc(src)
     _planar(base_lr, 3)
     h, w, c = src.shape
     assert c == 24 and blob.numel() == hip.RESBLOCK24_BLOB_BYTES
     bh, bw = base_lr.shape[1:]
     dt, fmt = result_format(result_dtype)
-    out = torch.empty((3, h, w), dtype=dt, device=src.device)
-    hip.check(hip.lib().refvsr_conv_hr_last_fmt(_ptr(src), h, w, _ptr(blob), act, _ptr(base_lr), bh, bw, _ptr(out), fmt, _stream()), 'conv_hr_last')
+    out, flag = _result_empty(h, w, dt, src.device, result_layout)
+    hip.check(hip.lib().refvsr_conv_hr_last_fmt(_ptr(src), h, w, _ptr(blob), act, _ptr(base_lr), bh, bw, _ptr(out), fmt | flag, _stream()), 'conv_hr_last')
     return out
 
 
@@ -756,16 +802,20 @@ def _score_inputs(outs, gts, what, down=1):
     fmts = {torch.float32: hip.RESULT_F32, torch.float16: hip.RESULT_F16, torch.uint8: hip.RESULT_U8}
     assert a0.dtype in fmts and g0.dtype in (torch.float32, torch.uint8), '%s: float32 | float16 | uint8 results, float32 | uint8 ground truth' % what
     lay = u8_layout(g0) if g0.dtype == torch.uint8 else hip.INGEST_PLANAR
+    alay = result_layout_of(a0)
     for a, g in zip(outs, gts):
         if down == 1 and (a.shape != (3, h, w) or g.shape != (3, h, w)):
             raise RuntimeError('%s: result %s and ground truth %s must both be [3, %d, %d]' % (what, tuple(a.shape), tuple(g.shape), h, w))
         if down != 1 and (a.shape != (3, down * h, down * w) or g.shape != (3, h, w)):
             raise RuntimeError('%s: result %s and ground truth %s must both be [3, %d, %d] after the down-scale by %d (the result %d times that)'
                                % (what, tuple(a.shape), tuple(g.shape), h, w, down, down))
-        assert a.is_cuda and g.is_cuda and a.dtype == a0.dtype and g.dtype == g0.dtype and a.is_contiguous()
+        assert a.is_cuda and g.is_cuda and a.dtype == a0.dtype and g.dtype == g0.dtype
+        if alay is None or result_layout_of(a) != alay:
+            raise RuntimeError('%s: results must be dense and of one layout, contiguous [3, h, w] or the channels-last view of [h, w, 3] '
+                               '(config.result_layout), got strides %s' % (what, tuple(a.stride())))
         assert (u8_layout(g) if g.dtype == torch.uint8 else (hip.INGEST_PLANAR if g.is_contiguous() else None)) == lay and lay is not None, \
             '%s: ground-truth frames must be dense and of one layout' % what
-    return outs, gts, h, w, fmts[a0.dtype], fmts[g0.dtype], lay
+    return outs, gts, h, w, fmts[a0.dtype] | (hip.RESULT_HWC if alay == 'hwc' else 0), fmts[g0.dtype], lay
 
 
 def _score_workspace(cache, dev, st, h, w, nbytes, what):
@@ -784,6 +834,7 @@ def _score_workspace(cache, dev, st, h, w, nbytes, what):
 def score_frames(outs, gts, win=7, down=1):
     """{mse, ssim} of B (result, ground truth) pairs of one 3 x h x w geometry, computed on the device (refvsr_score_frames): a
     torch.float64 [B, 2] tensor on the current stream, no synchronisation.  outs: [B,3,h,w] tensor or B tensors [3,h,w], contiguous
+    or channels-last (config.result_layout = 'hwc': the same scores, bit for bit),
     float32 / float16 / uint8 (what the output head stores; a byte means byte / 255); gts: the same shapes, contiguous float32, or
     uint8 planar or channels-last (u8_layout).  win = 7: both numbers; win = 0: the mse alone (ssim field 0).  One launch per
     REFVSR_SCORE_MAX_FRAMES pairs.  PSNR = metrics.psnr_from_mse(mse) on the host.

@@ -972,6 +972,8 @@ class EngineExecutor(object):
         return [min(max(f - self.t // 2 + k, 0), self.nframes - 1) for k in range(self.t)]
 
     def _out(self, r):
+        # results never travel between ranks (only the carried state does); a channels-last result (config.result_layout = 'hwc')
+        # keeps its layout here: indexing a frame and .cpu() both preserve the strides of a dense tensor
         return r if self.keep else r.cpu()
 
     def __call__(self, lrs, refs, first, f=None):
