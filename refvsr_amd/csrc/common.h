@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
+#include <utility>
 
 #include "../../include/refvsr_hip.h"
 
@@ -38,6 +40,10 @@ void refvsr_set_error(const char* fmt, ...);
 #define RV_LAUNCH_CHECK() RV_HIP(hipGetLastError())
 
 static inline int rv_cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// f(std::integral_constant<int, I>{}) for every I of the sequence, in order: a loop whose index is a compile-time constant
+template <class F, int... I>
+__device__ __forceinline__ void rv_static_for(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
 
 // Per-device caches (function attributes, occupancy, CU count): one process may drive several GPUs.
 #define RV_MAX_DEVICES 16

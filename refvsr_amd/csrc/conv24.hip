@@ -425,7 +425,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(WPS, W
             if constexpr (NF <= 4) {
                 // two fragment sets: the reads of step s + 1 are issued above the MFMAs of step s (WF = 1: every shape, COUT = 48 too)
                 load(std::integral_constant<int, 0>{}, fa[0], fb[0]);
-                c24_static_for([&](auto sc) {
+                rv_static_for([&](auto sc) {
                     constexpr int s = decltype(sc)::value;
                     if constexpr (s + 1 < S) load(std::integral_constant<int, s + 1>{}, fa[(s + 1) & 1], fb[(s + 1) & 1]);
                     __builtin_amdgcn_sched_barrier(0);
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(WPS, W
                 // right behind the 6 T MFMAs of step s -- those have latched their operands by then and occupy the matrix pipe for
                 // 96 T cycles, longer than the reads take
                 load(std::integral_constant<int, 0>{}, fa[0], fb[0]);
-                c24_static_for([&](auto sc) {
+                rv_static_for([&](auto sc) {
                     constexpr int s = decltype(sc)::value;
                     __builtin_amdgcn_sched_barrier(0);
                     mfma(fa[0], fb[0]);
@@ -636,68 +636,59 @@ static int c24_fill(C24Args& a, const char* who, int cout, const void* src0, con
     return 0;
 }
 
-template <int WF>
-static int c24i_conv24(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
-                       const void* mul, const void* res, float post_slope, void* out, void* stream) {
-    RV_CHECK(refvsr_conv24_supported(c0, c1), "conv24: %d + %d input channels not supported", c0, c1);
-    C24Args a;
-    if (c24_fill(a, "conv24", 24, src0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out)) return 1;
-    hipStream_t st = (hipStream_t)stream;
-    if (c0 == 24 && c1 == 0) return launch_c24<24, 3, 0, 8, 8, 4, 0, 0, 0, 0, WF>(a, st);
-    if (c0 == 16 && c1 == 0) return launch_c24<24, 2, 0, 8, 8, 4, 0, 0, 0, 0, WF>(a, st);
-    if (c0 == 8 && c1 == 24) return launch_c24<24, 1, 3, 8, 8, 4, 0, 0, 0, 0, WF>(a, st);
-    return launch_c24<24, 3, 3, 8, 8, 4, 0, 0, 0, 0, WF>(a, st);
-}
-extern "C" int refvsr_conv24(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
-                             const void* mul, const void* res, float post_slope, void* out, void* stream) {
-    return c24i_conv24<0>(src0, c0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out, stream);
-}
-extern "C" int refvsr_conv24_f16w(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
-                                  const void* mul, const void* res, float post_slope, void* out, void* stream) {
-    return c24i_conv24<1>(src0, c0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out, stream);
-}
-
-// The same conv over `batch` maps of one geometry in ONE launch (ABI 11): the per-map operands are host arrays of device pointers.
-template <int WF>
-static int c24i_conv24_batch(const void* const* src0, int c0, const void* const* src1, int c1, int batch, int h, int w, const void* blob,
-                             float act_slope, const void* const* mul, const void* const* res, float post_slope, void* const* out,
-                             void* stream) {
-    RV_CHECK(refvsr_conv24_supported(c0, c1), "conv24_batch: %d + %d input channels not supported", c0, c1);
-    RV_CHECK(src0 && out && batch >= 1 && batch <= REFVSR_MAX_MAPS, "conv24_batch: 1..%d maps per launch", REFVSR_MAX_MAPS);
-    RV_CHECK((c1 == 0) == (src1 == nullptr), "conv24_batch: src1 / c1 mismatch");
-    C24Args a;
-    if (c24_fill(a, "conv24_batch", 24, src0[0], src1 ? src1[0] : nullptr, c1, h, w, blob, act_slope, mul ? mul[0] : nullptr,
+// Per-map operands of an entry point (ABI 11): `batch` device pointers per operand in host arrays; a single-map entry passes the
+// addresses of its own arguments and batch = 1.  The checks of c24_fill on map 0, then every map's null / alias checks and the
+// per-map tables the MM = 1 kernels read.
+static int c24_fill_maps(C24Args& a, const char* who, int cout, const void* const* src0, const void* const* src1, int c1, int batch,
+                         int h, int w, const void* blob, float act_slope, const void* const* mul, const void* const* res,
+                         float post_slope, void* const* out) {
+    if (c24_fill(a, who, cout, src0[0], src1 ? src1[0] : nullptr, c1, h, w, blob, act_slope, mul ? mul[0] : nullptr,
                  res ? res[0] : nullptr, post_slope, out[0])) return 1;
     a.batch = batch;
     for (int b = 0; b < batch; ++b) {
-        RV_CHECK(src0[b] && out[b] && (!src1 || src1[b]) && (!mul || mul[b]) && (!res || res[b]), "conv24_batch: null map pointer (map %d)", b);
+        RV_CHECK(src0[b] && out[b] && (!src1 || src1[b]) && (!mul || mul[b]) && (!res || res[b]), "%s: null map pointer (map %d)", who, b);
         for (int c = 0; c < batch; ++c)
-            RV_CHECK(src0[c] != out[b] && (!src1 || src1[c] != out[b]) && (c == b || out[c] != out[b]), "conv24_batch: in-place operation is not supported");
+            RV_CHECK(src0[c] != out[b] && (!src1 || src1[c] != out[b]) && (c == b || out[c] != out[b]), "%s: in-place operation is not supported", who);
         a.bsrc0[b] = (const unsigned char*)src0[b]; a.bsrc1[b] = src1 ? (const unsigned char*)src1[b] : nullptr;
         a.bout[b] = (unsigned char*)out[b];
         a.bmul[b] = mul ? (const unsigned char*)mul[b] : nullptr; a.bres[b] = res ? (const unsigned char*)res[b] : nullptr;
     }
+    return 0;
+}
+// a single-map entry's optional operand as a one-entry table
+#define C24_OPT(p) ((p) ? &(p) : nullptr)
+
+// Each op below: ONE implementation <WF, MM> over per-map tables.  MM = 0: the single-map entry (its own arguments, batch = 1);
+// MM = 1: the `_batch` entry (ABI 11), `batch` maps of one geometry in ONE launch of the multi-map kernel.  WF = 1: the `_f16w` twin.
+template <int WF, int MM>
+static int c24_conv24(const void* const* src0, int c0, const void* const* src1, int c1, int batch, int h, int w, const void* blob,
+                      float act_slope, const void* const* mul, const void* const* res, float post_slope, void* const* out, void* stream) {
+    const char* who = MM ? "conv24_batch" : "conv24";
+    RV_CHECK(refvsr_conv24_supported(c0, c1), "%s: %d + %d input channels not supported", who, c0, c1);
+    RV_CHECK(src0 && out && batch >= 1 && batch <= REFVSR_MAX_MAPS, "%s: 1..%d maps per launch", who, REFVSR_MAX_MAPS);
+    RV_CHECK(!MM || (c1 == 0) == (src1 == nullptr), "%s: src1 / c1 mismatch", who);
+    C24Args a;
+    if (c24_fill_maps(a, who, 24, src0, src1, c1, batch, h, w, blob, act_slope, mul, res, post_slope, out)) return 1;
     hipStream_t st = (hipStream_t)stream;
-    if (c0 == 24 && c1 == 0) return launch_c24<24, 3, 0, 8, 8, 4, 0, 0, 0, 1, WF>(a, st);
-    if (c0 == 16 && c1 == 0) return launch_c24<24, 2, 0, 8, 8, 4, 0, 0, 0, 1, WF>(a, st);
-    if (c0 == 8 && c1 == 24) return launch_c24<24, 1, 3, 8, 8, 4, 0, 0, 0, 1, WF>(a, st);
-    return launch_c24<24, 3, 3, 8, 8, 4, 0, 0, 0, 1, WF>(a, st);
+    if (c0 == 24 && c1 == 0) return launch_c24<24, 3, 0, 8, 8, 4, 0, 0, 0, MM, WF>(a, st);
+    if (c0 == 16 && c1 == 0) return launch_c24<24, 2, 0, 8, 8, 4, 0, 0, 0, MM, WF>(a, st);
+    if (c0 == 8 && c1 == 24) return launch_c24<24, 1, 3, 8, 8, 4, 0, 0, 0, MM, WF>(a, st);
+    return launch_c24<24, 3, 3, 8, 8, 4, 0, 0, 0, MM, WF>(a, st);
 }
-extern "C" int refvsr_conv24_batch(const void* const* src0, int c0, const void* const* src1, int c1, int batch, int h, int w, const void* blob,
-                                   float act_slope, const void* const* mul, const void* const* res, float post_slope, void* const* out,
-                                   void* stream) {
-    return c24i_conv24_batch<0>(src0, c0, src1, c1, batch, h, w, blob, act_slope, mul, res, post_slope, out, stream);
-}
-extern "C" int refvsr_conv24_batch_f16w(const void* const* src0, int c0, const void* const* src1, int c1, int batch, int h, int w, const void* blob,
-                                        float act_slope, const void* const* mul, const void* const* res, float post_slope, void* const* out,
-                                        void* stream) {
-    return c24i_conv24_batch<1>(src0, c0, src1, c1, batch, h, w, blob, act_slope, mul, res, post_slope, out, stream);
-}
+#define C24_CONV_ARGS const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope, \
+                      const void* mul, const void* res, float post_slope, void* out, void* stream
+#define C24_CONV_BATCH_ARGS const void* const* src0, int c0, const void* const* src1, int c1, int batch, int h, int w, const void* blob, \
+                            float act_slope, const void* const* mul, const void* const* res, float post_slope, void* const* out, void* stream
+#define C24_CONV_PASS(MM, WF) c24_conv24<WF, MM>(&src0, c0, C24_OPT(src1), c1, 1, h, w, blob, act_slope, C24_OPT(mul), C24_OPT(res), post_slope, &out, stream)
+#define C24_CONV_BATCH_PASS(WF) c24_conv24<WF, 1>(src0, c0, src1, c1, batch, h, w, blob, act_slope, mul, res, post_slope, out, stream)
+extern "C" int refvsr_conv24(C24_CONV_ARGS) { return C24_CONV_PASS(0, 0); }
+extern "C" int refvsr_conv24_f16w(C24_CONV_ARGS) { return C24_CONV_PASS(0, 1); }
+extern "C" int refvsr_conv24_batch(C24_CONV_BATCH_ARGS) { return C24_CONV_BATCH_PASS(0); }
+extern "C" int refvsr_conv24_batch_f16w(C24_CONV_BATCH_ARGS) { return C24_CONV_BATCH_PASS(1); }
 
 // 32 output channels (AlignedConv2d, RefVSR_/alignment.py:18-24,53-100: the 3 -> 32 stem and the 32 -> 32 convs of its ResBlocks)
 template <int WF>
-static int c24i_conv32(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
-                       const void* mul, const void* res, float post_slope, void* out, void* stream) {
+static int c24i_conv32(C24_CONV_ARGS) {
     RV_CHECK(refvsr_conv32_supported(c0, c1), "conv32: %d + %d input channels not supported", c0, c1);
     C24Args a;
     if (c24_fill(a, "conv32", 32, src0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out)) return 1;
@@ -705,17 +696,10 @@ static int c24i_conv32(const void* src0, int c0, const void* src1, int c1, int h
     if (c0 == 32) return launch_c24<32, 4, 0, 8, 8, 4, 0, 0, 0, 0, WF>(a, st);
     return launch_c24<32, 1, 0, 8, 8, 4, 0, 0, 0, 0, WF>(a, st);
 }
-extern "C" int refvsr_conv32(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
-                             const void* mul, const void* res, float post_slope, void* out, void* stream) {
-    return c24i_conv32<0>(src0, c0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out, stream);
-}
-extern "C" int refvsr_conv32_f16w(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
-                                  const void* mul, const void* res, float post_slope, void* out, void* stream) {
-    return c24i_conv32<1>(src0, c0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out, stream);
-}
+extern "C" int refvsr_conv32(C24_CONV_ARGS) { return c24i_conv32<0>(src0, c0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out, stream); }
+extern "C" int refvsr_conv32_f16w(C24_CONV_ARGS) { return c24i_conv32<1>(src0, c0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out, stream); }
 
-extern "C" int refvsr_conv48(const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope,
-                             const void* mul, const void* res, float post_slope, void* out, void* stream) {
+extern "C" int refvsr_conv48(C24_CONV_ARGS) {
     RV_CHECK(refvsr_conv48_supported(c0, c1), "conv48: %d + %d input channels not supported", c0, c1);
     C24Args a;
     if (c24_fill(a, "conv48", 48, src0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out)) return 1;
@@ -732,49 +716,29 @@ extern "C" int refvsr_conv48(const void* src0, int c0, const void* src1, int c1,
 }
 
 // act(C -> 4 C 3x3 conv + bias) through F.pixel_shuffle(2) on fp16 HWC maps: src [h][w][C] -> out [2h][2w][C].  blobs: the 2 (C = 24) or
-// 4 (C = 48) row-group blobs of refvsr_amd/packing.py:pack_conv_shuffle2, back to back.
-template <int WF>
-static int c24i_conv_shuffle2(const void* src, int c, int h, int w, const void* blobs, float act_slope, void* out, void* stream) {
+// 4 (C = 48) row-group blobs of refvsr_amd/packing.py:pack_conv_shuffle2, back to back.  The `_batch` entries (PixelShufflePack over
+// `batch` maps: upsample1 of the RAP steps, RefVSR.py:138) and the `_f16w` twins take C = 24 only.
+template <int WF, int MM>
+static int c24_conv_shuffle2(const void* const* src, int batch, int c, int h, int w, const void* blobs, float act_slope, void* const* out,
+                             void* stream) {
+    const char* who = MM ? "conv_shuffle2_batch" : "conv_shuffle2";
+    if (MM) RV_CHECK(c == 24, "conv_shuffle2_batch: %d channels not supported (24)", c);
     RV_CHECK(refvsr_conv_shuffle2_supported(c), "conv_shuffle2: %d channels not supported", c);
+    RV_CHECK(src && out && batch >= 1 && batch <= REFVSR_MAX_MAPS, "%s: 1..%d maps per launch", who, REFVSR_MAX_MAPS);
     C24Args a;
-    if (c24_fill(a, "conv_shuffle2", 4 * c, src, nullptr, 0, h, w, blobs, act_slope, nullptr, nullptr, 1.0f, out)) return 1;   // (4 c: the 2h x 2w x c output map)
+    if (c24_fill_maps(a, who, 4 * c, src, nullptr, 0, batch, h, w, blobs, act_slope, nullptr, nullptr, 1.0f, out)) return 1;   // (4 c: the 2h x 2w x c output map)
     hipStream_t st = (hipStream_t)stream;
-    if (c == 24) return launch_c24<48, 3, 0, 8, 8, 4, 24, 0, 0, 0, WF>(a, st);
-    if constexpr (WF == 0) return launch_c24<48, 6, 0, 16, 16, 4, 48>(a, st);
+    if (c == 24) return launch_c24<48, 3, 0, 8, 8, 4, 24, 0, 0, MM, WF>(a, st);
+    if constexpr (WF == 0 && MM == 0) return launch_c24<48, 6, 0, 16, 16, 4, 48>(a, st);
     RV_CHECK(false, "conv_shuffle2_f16w: 24 channels only (the mid_channels = 24 family)");
     return 1;
 }
-extern "C" int refvsr_conv_shuffle2(const void* src, int c, int h, int w, const void* blobs, float act_slope, void* out, void* stream) {
-    return c24i_conv_shuffle2<0>(src, c, h, w, blobs, act_slope, out, stream);
-}
-extern "C" int refvsr_conv_shuffle2_f16w(const void* src, int c, int h, int w, const void* blobs, float act_slope, void* out, void* stream) {
-    return c24i_conv_shuffle2<1>(src, c, h, w, blobs, act_slope, out, stream);
-}
-
-// PixelShufflePack over `batch` maps in ONE launch (ABI 11, C = 24: upsample1 of the RAP steps, RefVSR.py:138)
-template <int WF>
-static int c24i_conv_shuffle2_batch(const void* const* src, int batch, int c, int h, int w, const void* blobs, float act_slope,
-                                    void* const* out, void* stream) {
-    RV_CHECK(c == 24, "conv_shuffle2_batch: %d channels not supported (24)", c);
-    RV_CHECK(src && out && batch >= 1 && batch <= REFVSR_MAX_MAPS, "conv_shuffle2_batch: 1..%d maps per launch", REFVSR_MAX_MAPS);
-    C24Args a;
-    if (c24_fill(a, "conv_shuffle2_batch", 4 * c, src[0], nullptr, 0, h, w, blobs, act_slope, nullptr, nullptr, 1.0f, out[0])) return 1;
-    a.batch = batch;
-    for (int b = 0; b < batch; ++b) {
-        RV_CHECK(src[b] && out[b], "conv_shuffle2_batch: null map pointer (map %d)", b);
-        for (int c2 = 0; c2 < batch; ++c2) RV_CHECK(src[c2] != out[b] && (c2 == b || out[c2] != out[b]), "conv_shuffle2_batch: in-place operation is not supported");
-        a.bsrc0[b] = (const unsigned char*)src[b]; a.bout[b] = (unsigned char*)out[b];
-    }
-    return launch_c24<48, 3, 0, 8, 8, 4, 24, 0, 0, 1, WF>(a, (hipStream_t)stream);
-}
-extern "C" int refvsr_conv_shuffle2_batch(const void* const* src, int batch, int c, int h, int w, const void* blobs, float act_slope,
-                                          void* const* out, void* stream) {
-    return c24i_conv_shuffle2_batch<0>(src, batch, c, h, w, blobs, act_slope, out, stream);
-}
-extern "C" int refvsr_conv_shuffle2_batch_f16w(const void* const* src, int batch, int c, int h, int w, const void* blobs, float act_slope,
-                                               void* const* out, void* stream) {
-    return c24i_conv_shuffle2_batch<1>(src, batch, c, h, w, blobs, act_slope, out, stream);
-}
+#define C24_SHUF_ARGS const void* src, int c, int h, int w, const void* blobs, float act_slope, void* out, void* stream
+#define C24_SHUF_BATCH_ARGS const void* const* src, int batch, int c, int h, int w, const void* blobs, float act_slope, void* const* out, void* stream
+extern "C" int refvsr_conv_shuffle2(C24_SHUF_ARGS) { return c24_conv_shuffle2<0, 0>(&src, 1, c, h, w, blobs, act_slope, &out, stream); }
+extern "C" int refvsr_conv_shuffle2_f16w(C24_SHUF_ARGS) { return c24_conv_shuffle2<1, 0>(&src, 1, c, h, w, blobs, act_slope, &out, stream); }
+extern "C" int refvsr_conv_shuffle2_batch(C24_SHUF_BATCH_ARGS) { return c24_conv_shuffle2<0, 1>(src, batch, c, h, w, blobs, act_slope, out, stream); }
+extern "C" int refvsr_conv_shuffle2_batch_f16w(C24_SHUF_BATCH_ARGS) { return c24_conv_shuffle2<1, 1>(src, batch, c, h, w, blobs, act_slope, out, stream); }
 
 // The confidence fusions of AA_AF_conf_prop / compute_up in ONE launch (RefVSR.py:47-52 conf_fusion / conf_fusion2 /
 // conf_fusion_BWFW, called at :130, :141-142, :107-109):
@@ -783,67 +747,45 @@ extern "C" int refvsr_conv_shuffle2_batch_f16w(const void* const* src, int batch
 // both convs zero padded.  conf_a / conf_b: planar fp32 [h][w]; w0 / b0: fp32 [16][2][3][3] / [16] (device); blob: the 16 -> cout
 // blob of refvsr_conv24 / refvsr_conv48 (cout = 24 | 48); alpha: fp16 HWC [up h][up w][cout]; conf_max (optional, up = 1):
 // max(conf_a, conf_b) [h][w] (RefVSR.py:147).  Bit-identical to torch.cat + [refvsr_resize +] refvsr_conv_direct_f32 +
-// refvsr_conv24 / 48 [+ refvsr_max2].
-template <int WF>
-static int c24i_conf_alpha(const float* conf_a, const float* conf_b, int h, int w, int up, const float* w0, const float* b0,
-                           float slope0, const void* blob, int cout, float slope1, void* alpha, float* conf_max, void* stream) {
-    RV_CHECK(conf_a && conf_b && w0 && b0 && alpha, "conf_alpha: null argument");
-    RV_CHECK(up == 1 || up == 2, "conf_alpha: up must be 1 or 2");
-    RV_CHECK(cout == 24 || cout == 48, "conf_alpha: %d output channels not supported (24 | 48)", cout);
-    RV_CHECK(conf_max == nullptr || up == 1, "conf_alpha: the max by-product exists at up = 1 only");
-    RV_CHECK(slope0 >= 0.f && slope0 <= 1.f, "conf_alpha: activation slopes must lie in [0, 1]");
+// refvsr_conv24 / 48 [+ refvsr_max2].  The `_batch` entries (`batch` pairs of maps) and the `_f16w` twins take cout = 24 only.
+template <int WF, int MM>
+static int c24_conf_alpha(const float* const* conf_a, const float* const* conf_b, int batch, int h, int w, int up, const float* w0,
+                          const float* b0, float slope0, const void* blob, int cout, float slope1, void* const* alpha,
+                          float* const* conf_max, void* stream) {
+    const char* who = MM ? "conf_alpha_batch" : "conf_alpha";
+    if (MM) RV_CHECK(conf_a && conf_b && w0 && b0 && alpha && batch >= 1 && batch <= REFVSR_MAX_MAPS, "conf_alpha_batch: bad args (1..%d maps)", REFVSR_MAX_MAPS);
+    else RV_CHECK(conf_a[0] && conf_b[0] && w0 && b0 && alpha[0], "conf_alpha: null argument");
+    RV_CHECK(up == 1 || up == 2, "%s: up must be 1 or 2", who);
+    if (MM) RV_CHECK(cout == 24, "conf_alpha_batch: %d output channels not supported (24)", cout);
+    else RV_CHECK(cout == 24 || cout == 48, "conf_alpha: %d output channels not supported (24 | 48)", cout);
+    RV_CHECK(conf_max == nullptr || up == 1, "%s: the max by-product exists at up = 1 only", who);
+    RV_CHECK(slope0 >= 0.f && slope0 <= 1.f, "%s: activation slopes must lie in [0, 1]", who);
     C24Args a;
-    if (c24_fill(a, "conf_alpha", cout, conf_a, nullptr, 0, up * h, up * w, blob, slope1, nullptr, nullptr, 1.0f, alpha)) return 1;
-    a.src0 = nullptr;
-    a.conf_a = conf_a; a.conf_b = conf_b; a.cw0 = w0; a.cb0 = b0; a.conf_max = conf_max; a.ch = h; a.cw = w; a.slope0 = slope0;
-    hipStream_t st = (hipStream_t)stream;
-    if (cout == 24) return up == 1 ? launch_c24<24, 2, 0, 8, 8, 4, 0, 1, 0, 0, WF>(a, st) : launch_c24<24, 2, 0, 8, 8, 4, 0, 2, 0, 0, WF>(a, st);
-    if constexpr (WF == 0) return up == 1 ? launch_c24<48, 2, 0, 8, 8, 4, 0, 1>(a, st) : launch_c24<48, 2, 0, 8, 8, 4, 0, 2>(a, st);
-    RV_CHECK(false, "conf_alpha_f16w: 24 output channels only (the mid_channels = 24 family)");
-    return 1;
-}
-extern "C" int refvsr_conf_alpha(const float* conf_a, const float* conf_b, int h, int w, int up, const float* w0, const float* b0,
-                                 float slope0, const void* blob, int cout, float slope1, void* alpha, float* conf_max, void* stream) {
-    return c24i_conf_alpha<0>(conf_a, conf_b, h, w, up, w0, b0, slope0, blob, cout, slope1, alpha, conf_max, stream);
-}
-extern "C" int refvsr_conf_alpha_f16w(const float* conf_a, const float* conf_b, int h, int w, int up, const float* w0, const float* b0,
-                                      float slope0, const void* blob, int cout, float slope1, void* alpha, float* conf_max, void* stream) {
-    return c24i_conf_alpha<1>(conf_a, conf_b, h, w, up, w0, b0, slope0, blob, cout, slope1, alpha, conf_max, stream);
-}
-
-// The confidence fusion over `batch` pairs of maps in ONE launch (ABI 11, cout = 24)
-template <int WF>
-static int c24i_conf_alpha_batch(const float* const* conf_a, const float* const* conf_b, int batch, int h, int w, int up, const float* w0,
-                                 const float* b0, float slope0, const void* blob, int cout, float slope1, void* const* alpha,
-                                 float* const* conf_max, void* stream) {
-    RV_CHECK(conf_a && conf_b && w0 && b0 && alpha && batch >= 1 && batch <= REFVSR_MAX_MAPS, "conf_alpha_batch: bad args (1..%d maps)", REFVSR_MAX_MAPS);
-    RV_CHECK(up == 1 || up == 2, "conf_alpha_batch: up must be 1 or 2");
-    RV_CHECK(cout == 24, "conf_alpha_batch: %d output channels not supported (24)", cout);
-    RV_CHECK(conf_max == nullptr || up == 1, "conf_alpha_batch: the max by-product exists at up = 1 only");
-    RV_CHECK(slope0 >= 0.f && slope0 <= 1.f, "conf_alpha_batch: activation slopes must lie in [0, 1]");
-    C24Args a;
-    if (c24_fill(a, "conf_alpha_batch", cout, conf_a[0], nullptr, 0, up * h, up * w, blob, slope1, nullptr, nullptr, 1.0f, alpha[0])) return 1;
+    if (c24_fill(a, who, cout, conf_a[0], nullptr, 0, up * h, up * w, blob, slope1, nullptr, nullptr, 1.0f, alpha[0])) return 1;
     a.src0 = nullptr;
     a.conf_a = conf_a[0]; a.conf_b = conf_b[0]; a.cw0 = w0; a.cb0 = b0; a.conf_max = conf_max ? conf_max[0] : nullptr; a.ch = h; a.cw = w; a.slope0 = slope0;
     a.batch = batch;
     for (int b = 0; b < batch; ++b) {
-        RV_CHECK(conf_a[b] && conf_b[b] && alpha[b] && (!conf_max || conf_max[b]), "conf_alpha_batch: null map pointer (map %d)", b);
+        RV_CHECK(conf_a[b] && conf_b[b] && alpha[b] && (!conf_max || conf_max[b]), "%s: null map pointer (map %d)", who, b);
         a.bconf_a[b] = conf_a[b]; a.bconf_b[b] = conf_b[b]; a.bconf_max[b] = conf_max ? conf_max[b] : nullptr;
         a.bout[b] = (unsigned char*)alpha[b];
     }
     hipStream_t st = (hipStream_t)stream;
-    return up == 1 ? launch_c24<24, 2, 0, 8, 8, 4, 0, 1, 0, 1, WF>(a, st) : launch_c24<24, 2, 0, 8, 8, 4, 0, 2, 0, 1, WF>(a, st);
+    if (cout == 24) return up == 1 ? launch_c24<24, 2, 0, 8, 8, 4, 0, 1, 0, MM, WF>(a, st) : launch_c24<24, 2, 0, 8, 8, 4, 0, 2, 0, MM, WF>(a, st);
+    if constexpr (WF == 0 && MM == 0) return up == 1 ? launch_c24<48, 2, 0, 8, 8, 4, 0, 1>(a, st) : launch_c24<48, 2, 0, 8, 8, 4, 0, 2>(a, st);
+    RV_CHECK(false, "conf_alpha_f16w: 24 output channels only (the mid_channels = 24 family)");
+    return 1;
 }
-extern "C" int refvsr_conf_alpha_batch(const float* const* conf_a, const float* const* conf_b, int batch, int h, int w, int up, const float* w0,
-                                       const float* b0, float slope0, const void* blob, int cout, float slope1, void* const* alpha,
-                                       float* const* conf_max, void* stream) {
-    return c24i_conf_alpha_batch<0>(conf_a, conf_b, batch, h, w, up, w0, b0, slope0, blob, cout, slope1, alpha, conf_max, stream);
-}
-extern "C" int refvsr_conf_alpha_batch_f16w(const float* const* conf_a, const float* const* conf_b, int batch, int h, int w, int up, const float* w0,
-                                            const float* b0, float slope0, const void* blob, int cout, float slope1, void* const* alpha,
-                                            float* const* conf_max, void* stream) {
-    return c24i_conf_alpha_batch<1>(conf_a, conf_b, batch, h, w, up, w0, b0, slope0, blob, cout, slope1, alpha, conf_max, stream);
-}
+#define C24_CONF_ARGS const float* conf_a, const float* conf_b, int h, int w, int up, const float* w0, const float* b0, float slope0, \
+                      const void* blob, int cout, float slope1, void* alpha, float* conf_max, void* stream
+#define C24_CONF_BATCH_ARGS const float* const* conf_a, const float* const* conf_b, int batch, int h, int w, int up, const float* w0, const float* b0, \
+                            float slope0, const void* blob, int cout, float slope1, void* const* alpha, float* const* conf_max, void* stream
+#define C24_CONF_PASS(WF) c24_conf_alpha<WF, 0>(&conf_a, &conf_b, 1, h, w, up, w0, b0, slope0, blob, cout, slope1, &alpha, C24_OPT(conf_max), stream)
+#define C24_CONF_BATCH_PASS(WF) c24_conf_alpha<WF, 1>(conf_a, conf_b, batch, h, w, up, w0, b0, slope0, blob, cout, slope1, alpha, conf_max, stream)
+extern "C" int refvsr_conf_alpha(C24_CONF_ARGS) { return C24_CONF_PASS(0); }
+extern "C" int refvsr_conf_alpha_f16w(C24_CONF_ARGS) { return C24_CONF_PASS(1); }
+extern "C" int refvsr_conf_alpha_batch(C24_CONF_BATCH_ARGS) { return C24_CONF_BATCH_PASS(0); }
+extern "C" int refvsr_conf_alpha_batch_f16w(C24_CONF_BATCH_ARGS) { return C24_CONF_BATCH_PASS(1); }
 
 // The output head in ONE launch (RefVSR.py:92,118,288,297: conv_last 3x3 C -> 3, + F.interpolate(lr_centre, scale, bicubic).clamp(0, 1),
 // final clamp): out planar fp32 [3][h][w] = clamp( conv(src) + bias + clamp01(bicubic(base_lr)), 0, 1 ).  src: fp16 HWC [h][w][c],

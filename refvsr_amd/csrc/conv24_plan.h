@@ -3,8 +3,6 @@
 // one pixel in PS = ncg | 1 sixteen-byte slots (odd stride: bank-conflict-free B reads with the pixel permutation of common.h);
 // XW = pixels per staged row (34 for a 1-pixel halo, 36 for the 2-pixel halo of a fused block).
 #pragma once
-#include <type_traits>
-#include <utility>
 
 namespace {
 constexpr int C24_TW = 32, C24_XW = 34;                       // tile width; staged row of the single convs = 34 pixels
@@ -88,8 +86,5 @@ __host__ __device__ constexpr bool c24_plan_ok(int ncg, int xw = C24_XW) {
     return true;
 }
 static_assert(c24_plan_ok(1) && c24_plan_ok(2) && c24_plan_ok(3) && c24_plan_ok(4) && c24_plan_ok(6) && c24_plan_ok(7) && c24_plan_ok(12), "conv24 K plan");
-
-template <class F, int... I>
-__device__ __forceinline__ void c24_static_for(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
 }  // namespace
 

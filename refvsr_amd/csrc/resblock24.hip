@@ -94,19 +94,21 @@ __device__ __forceinline__ f32x4 rb_fold_halves(const f32x4 a) {
 }
 
 // K loop of one conv: T pixel groups of this wave, fragments at smem + wofs, B windows at smem + pb[t] (+ immediates).
-// Software pipelined over two fragment sets (the reads of step s+1 are issued above the MFMAs of step s).
+// Software pipelined over two fragment sets (the reads of step s+2 are issued below the MFMAs of step s, above those of step s+1).
 // WF = 1: two fragments per K-step, acc0 += [rows 0-15], acc1 += [rows 16-23 | zero rows] -- the hi MFMAs of WF = 0 in the same
 // order on the same accumulators, without the lo MFMAs (which add exact zeros for fp16-representable weights).
-template <int T, int TA, int WF = 0>
+// HEAD = 1 (the output head's conv): ONE fragment per K-step -- rows 0-2 = hi, rows 8-10 = lo of the three output channels -- at
+// the blob's fragment slot (s, 0) of the 3-fragment layout; the other two slots are not read and acc1 is not touched.
+template <int T, int TA, int WF = 0, int HEAD = 0>
 __device__ __forceinline__ void rb_kloop(f32x4 (&acc0)[TA], f32x4 (&acc1)[TA], const unsigned char* smem, const int wofs,
                                          const int la, const int (&pb)[TA], const int delta6) {
     static_assert(T <= TA, "group count");
-    constexpr int NF = rb_nf(WF);
+    constexpr int NF = HEAD ? 1 : rb_nf(WF), SLOTS = HEAD ? RB_NF : NF;   // fragments read per K-step, fragment slots per K-step
     uint4 a[2][NF], b[2][T];
     auto load = [&](auto sc, uint4 (&af)[NF], uint4 (&bf)[T]) {
         constexpr int s = decltype(sc)::value;
 #pragma unroll
-        for (int f = 0; f < NF; ++f) af[f] = *reinterpret_cast<const uint4*>(smem + wofs + (s * NF + f) * 1024 + la);
+        for (int f = 0; f < NF; ++f) af[f] = *reinterpret_cast<const uint4*>(smem + wofs + (s * SLOTS + f) * 1024 + la);
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             if constexpr (s < 6) bf[t] = *reinterpret_cast<const uint4*>(smem + pb[t] + (s >> 1) * RB_ROWB + (s & 1) * 64);
@@ -114,89 +116,24 @@ __device__ __forceinline__ void rb_kloop(f32x4 (&acc0)[TA], f32x4 (&acc1)[TA], c
         }
     };
     auto mfma = [&](const uint4 (&af)[NF], const uint4 (&bf)[T]) {
-        if constexpr (WF == 0) {
-            const f16x8 a_hi = *reinterpret_cast<const f16x8*>(&af[0]);
-            const f16x8 a_lo = *reinterpret_cast<const f16x8*>(&af[1]);
-            const f16x8 a_mx = *reinterpret_cast<const f16x8*>(&af[2]);
+        // fragment f of the set into accumulator `acc`, every pixel group
+        auto fma = [&](f32x4 (&acc)[TA], const int f) {
+            const f16x8 a_f = *reinterpret_cast<const f16x8*>(&af[f]);
 #pragma unroll
-            for (int t = 0; t < T; ++t) acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, *reinterpret_cast<const f16x8*>(&bf[t]), acc0[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < T; ++t) acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_mx, *reinterpret_cast<const f16x8*>(&bf[t]), acc1[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < T; ++t) acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_lo, *reinterpret_cast<const f16x8*>(&bf[t]), acc0[t], 0, 0, 0);
-        } else {
-            const f16x8 a_0 = *reinterpret_cast<const f16x8*>(&af[0]);
-            const f16x8 a_1 = *reinterpret_cast<const f16x8*>(&af[1]);
-#pragma unroll
-            for (int t = 0; t < T; ++t) acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_0, *reinterpret_cast<const f16x8*>(&bf[t]), acc0[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < T; ++t) acc1[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_1, *reinterpret_cast<const f16x8*>(&bf[t]), acc1[t], 0, 0, 0);
-        }
+            for (int t = 0; t < T; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_f, *reinterpret_cast<const f16x8*>(&bf[t]), acc[t], 0, 0, 0);
+        };
+        if constexpr (HEAD != 0) { fma(acc0, 0); }
+        else if constexpr (WF == 0) { fma(acc0, 0); fma(acc1, 2); fma(acc0, 1); }      // hi, mixed, lo
+        else { fma(acc0, 0); fma(acc1, 1); }
     };
     load(std::integral_constant<int, 0>{}, a[0], b[0]);
     load(std::integral_constant<int, 1>{}, a[1], b[1]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma(a[0], b[0]);
-    load(std::integral_constant<int, 2>{}, a[0], b[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma(a[1], b[1]);
-    load(std::integral_constant<int, 3>{}, a[1], b[1]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma(a[0], b[0]);
-    load(std::integral_constant<int, 4>{}, a[0], b[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma(a[1], b[1]);
-    load(std::integral_constant<int, 5>{}, a[1], b[1]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma(a[0], b[0]);
-    load(std::integral_constant<int, 6>{}, a[0], b[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma(a[1], b[1]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma(a[0], b[0]);
-}
-
-// K loop of the output head's conv (HEAD kernels): ONE fragment per K-step -- rows 0-2 = hi, rows 8-10 = lo of the three output
-// channels -- at the blob's fragment slot (s, 0); the other two slots of the 3-fragment layout are not read.
-template <int T>
-__device__ __forceinline__ void rb_kloop_head(f32x4 (&acc0)[T], const unsigned char* smem, const int wofs, const int la,
-                                              const int (&pb)[T], const int delta6) {
-    uint4 a[2], b[2][T];
-    auto load = [&](auto sc, uint4& af, uint4 (&bf)[T]) {
+    rv_static_for([&](auto sc) {
         constexpr int s = decltype(sc)::value;
-        af = *reinterpret_cast<const uint4*>(smem + wofs + s * RB_NF * 1024 + la);
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            if constexpr (s < 6) bf[t] = *reinterpret_cast<const uint4*>(smem + pb[t] + (s >> 1) * RB_ROWB + (s & 1) * 64);
-            else bf[t] = *reinterpret_cast<const uint4*>(smem + pb[t] + delta6);
-        }
-    };
-    auto mfma = [&](const uint4& af, const uint4 (&bf)[T]) {
-        const f16x8 a_w = *reinterpret_cast<const f16x8*>(&af);
-#pragma unroll
-        for (int t = 0; t < T; ++t) acc0[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_w, *reinterpret_cast<const f16x8*>(&bf[t]), acc0[t], 0, 0, 0);
-    };
-    load(std::integral_constant<int, 0>{}, a[0], b[0]);
-    load(std::integral_constant<int, 1>{}, a[1], b[1]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma(a[0], b[0]);
-    load(std::integral_constant<int, 2>{}, a[0], b[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma(a[1], b[1]);
-    load(std::integral_constant<int, 3>{}, a[1], b[1]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma(a[0], b[0]);
-    load(std::integral_constant<int, 4>{}, a[0], b[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma(a[1], b[1]);
-    load(std::integral_constant<int, 5>{}, a[1], b[1]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma(a[0], b[0]);
-    load(std::integral_constant<int, 6>{}, a[0], b[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma(a[1], b[1]);
-    __builtin_amdgcn_sched_barrier(0);
-    mfma(a[0], b[0]);
+        __builtin_amdgcn_sched_barrier(0);
+        mfma(a[s & 1], b[s & 1]);
+        if constexpr (s + 2 < RB_S) load(std::integral_constant<int, s + 2>{}, a[s & 1], b[s & 1]);
+    }, std::make_integer_sequence<int, RB_S>{});
 }
 
 // act(y) of four fp32 values -> two packed fp16 pairs.  RELU: conversion first, v_pk_max_f16 on the pairs (ReLU commutes with
@@ -457,8 +394,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV ==
                 }
             }
         }
-        if constexpr (HEAD != 0) rb_kloop_head<T2>(c0, smem, RB_WB, la, pb2, delta6);
-        else rb_kloop<T2, T2, WF>(c0, c1, smem, RB_WB, la, pb2, delta6);
+        rb_kloop<T2, T2, WF, HEAD != 0>(c0, c1, smem, RB_WB, la, pb2, delta6);
         if (stamp) RB_STAMP(7);
         if (has_next) {
             __syncthreads();                                     // C: every wave is done reading t

@@ -104,7 +104,7 @@ __device__ __forceinline__ void r48_kloop(f32x4 (&acc)[R48_NM][TA], const unsign
             }
     };
     load(std::integral_constant<int, 0>{}, fa[0], fb[0]);
-    c24_static_for([&](auto sc) {
+    rv_static_for([&](auto sc) {
         constexpr int s = decltype(sc)::value;
         if constexpr (s + 1 < R48_S) load(std::integral_constant<int, s + 1>{}, fa[(s + 1) & 1], fb[(s + 1) & 1]);
         __builtin_amdgcn_sched_barrier(0);

@@ -132,20 +132,11 @@ SIGNATURES = {
     'refvsr_pool3s2_nhwc16': [_P, _I, _I, _I, _P, _I, _I, _I, _P],
     'refvsr_up2_bilinear_nhwc16': [_P, _I, _I, _I, _F, _P, _P],
     'refvsr_tsa_blend': [_P, _P, _P, _Z, _P, _P],
-    # fp16 weight format (ABI 15): twins with the signature of the function they are named after
+    # fp16 weight format (ABI 15): blob sizes; the _f16w twins of _F16W_TWINS follow the dict
     'refvsr_resblock24_f16w_blob_bytes': [],     # returns the size
     'refvsr_conv24_f16w_blob_bytes': [_I, _I],   # returns the size
     'refvsr_conv32_f16w_blob_bytes': [_I, _I],   # returns the size
     'refvsr_conv_shuffle2_f16w_blob_bytes': [_I],   # returns the size
-    'refvsr_resblock24_chain_f16w': [_P, _I, _I, _I, _P, _Z, _F, _P, _P, _P, _P],
-    'refvsr_resblock24_chain_batch_f16w': [_P, _I, _I, _I, _I, _P, _Z, _F, _P, _P, _P, _P],
-    'refvsr_conv24_f16w': [_P, _I, _P, _I, _I, _I, _P, _F, _P, _P, _F, _P, _P],
-    'refvsr_conv24_batch_f16w': [_P, _I, _P, _I, _I, _I, _I, _P, _F, _P, _P, _F, _P, _P],
-    'refvsr_conv32_f16w': [_P, _I, _P, _I, _I, _I, _P, _F, _P, _P, _F, _P, _P],
-    'refvsr_conv_shuffle2_f16w': [_P, _I, _I, _I, _P, _F, _P, _P],
-    'refvsr_conv_shuffle2_batch_f16w': [_P, _I, _I, _I, _I, _P, _F, _P, _P],
-    'refvsr_conf_alpha_f16w': [_P, _P, _I, _I, _I, _P, _P, _F, _P, _I, _F, _P, _P, _P],
-    'refvsr_conf_alpha_batch_f16w': [_P, _P, _I, _I, _I, _I, _P, _P, _F, _P, _I, _F, _P, _P, _P],
     # 8-bit input frames (added symbols, ABI 15 unchanged)
     'refvsr_ingest_u8': [_P, _P, _I, _I, _I, _I, _P],
     'refvsr_ingest_table': [_P],                 # copies the 256-entry byte -> float table to host memory
@@ -168,6 +159,10 @@ SIGNATURES = {
     'refvsr_conf_colormap': [_P, _I, _I, _I, _P, _P, _Z, _P],
     'refvsr_colormap_table': [_P],               # copies the 256 x 3 byte colour table to host memory
 }
+# fp16 weight format (ABI 15): <name>_f16w twins with the signature of the function they are named after
+_F16W_TWINS = ('refvsr_resblock24_chain', 'refvsr_resblock24_chain_batch', 'refvsr_conv24', 'refvsr_conv24_batch', 'refvsr_conv32',
+               'refvsr_conv_shuffle2', 'refvsr_conv_shuffle2_batch', 'refvsr_conf_alpha', 'refvsr_conf_alpha_batch')
+SIGNATURES.update((name + '_f16w', SIGNATURES[name]) for name in _F16W_TWINS)
 _SPECIAL = {'refvsr_abi_version': (C.c_int, []), 'refvsr_last_error': (C.c_char_p, []),
             'refvsr_score_workspace_bytes': (C.c_size_t, [_I, _I, _I]),
             'refvsr_score_regions_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I]),
@@ -195,19 +190,12 @@ def lib():
             fn = getattr(h, name)
             fn.argtypes = args
             fn.restype = res
-        if h.refvsr_abi_version() != ABI_VERSION:
-            raise RuntimeError('refvsr_amd: ABI mismatch (library %d, binding %d)' % (h.refvsr_abi_version(), ABI_VERSION))
-        if h.refvsr_max_maps() != MAX_MAPS:
-            raise RuntimeError('refvsr_amd: REFVSR_MAX_MAPS mismatch (library %d, binding %d)' % (h.refvsr_max_maps(), MAX_MAPS))
-        if h.refvsr_ingest_max_frames() != INGEST_MAX_FRAMES:
-            raise RuntimeError('refvsr_amd: REFVSR_INGEST_MAX_FRAMES mismatch (library %d, binding %d)'
-                               % (h.refvsr_ingest_max_frames(), INGEST_MAX_FRAMES))
-        if h.refvsr_score_max_frames() != SCORE_MAX_FRAMES:
-            raise RuntimeError('refvsr_amd: REFVSR_SCORE_MAX_FRAMES mismatch (library %d, binding %d)'
-                               % (h.refvsr_score_max_frames(), SCORE_MAX_FRAMES))
-        if h.refvsr_score_max_rects() != SCORE_MAX_RECTS:
-            raise RuntimeError('refvsr_amd: REFVSR_SCORE_MAX_RECTS mismatch (library %d, binding %d)'
-                               % (h.refvsr_score_max_rects(), SCORE_MAX_RECTS))
+        for query, const, name in ((h.refvsr_abi_version, ABI_VERSION, 'ABI'), (h.refvsr_max_maps, MAX_MAPS, 'REFVSR_MAX_MAPS'),
+                                   (h.refvsr_ingest_max_frames, INGEST_MAX_FRAMES, 'REFVSR_INGEST_MAX_FRAMES'),
+                                   (h.refvsr_score_max_frames, SCORE_MAX_FRAMES, 'REFVSR_SCORE_MAX_FRAMES'),
+                                   (h.refvsr_score_max_rects, SCORE_MAX_RECTS, 'REFVSR_SCORE_MAX_RECTS')):
+            if query() != const:
+                raise RuntimeError('refvsr_amd: %s mismatch (library %d, binding %d)' % (name, query(), const))
         _lib = h
     return _lib
 

@@ -141,9 +141,14 @@ class ConvWeights(object):
                 self.blob24 = pack_conv_shuffle2(self.raw[0], self.raw[1], wfmt=self.blob_wfmt).to(device).contiguous()     # refvsr_conv_shuffle2
 
 
+def _entry(name, f16w):
+    """Entry point `name` of the library, or its _f16w twin (ABI 15: the same signature over fp16-format blobs)."""
+    return getattr(hip.lib(), name + '_f16w' if f16w else name)
+
+
 def _c24(cw, name):
-    """Entry point `name` of the conv24 family, or its _f16w twin when cw's blob is in the fp16 weight format (ABI 15)."""
-    return getattr(hip.lib(), name + '_f16w' if cw.blob_wfmt == 'fp16' else name)
+    """Entry point `name` of the conv24 family, or its _f16w twin when cw's blob is in the fp16 weight format."""
+    return _entry(name, cw.blob_wfmt == 'fp16')
 
 
 def conv(cw, src0, src1=None, stride=1, pad=None, act=1.0, mul=None, res=None, post=1.0,
@@ -187,77 +192,49 @@ def conv(cw, src0, src1=None, stride=1, pad=None, act=1.0, mul=None, res=None, p
         fn = _c24(cw, 'refvsr_conv%d' % co_)
         hip.check(fn(_ptr(src0), c0, _ptr(src1), c1, h, w, _ptr(cw.blob24), act, _ptr(mul), _ptr(res), post, _ptr(out), _stream()), 'conv%d' % co_)
         return out
-    ho = (h + 2 * pad - k) // stride + 1
-    wo = (w + 2 * pad - k) // stride + 1
-    d = cw.desc
-    d.src0, d.c0, d.src1, d.c1 = src0.data_ptr(), c0, (src1.data_ptr() if src1 is not None else None), c1
-    d.h_in, d.w_in, d.h_out, d.w_out = h, w, ho, wo
-    d.stride, d.pad = stride, pad
-    d.act_slope, d.post_slope = act, post
-    if mul is not None:
-        _nhwc(mul, f32)
-        assert tuple(mul.shape[:2]) == (ho, wo)
-        d.mul, d.mul_c = mul.data_ptr(), mul.shape[2]
-    else:
-        d.mul, d.mul_c = None, 0
-    if res is not None:
-        _nhwc(res, f32)
-        assert tuple(res.shape[:2]) == (ho, wo)
-        d.res, d.res_c = res.data_ptr(), res.shape[2]
-    else:
-        d.res, d.res_c = None, 0
-    d.res_planar, d.add_const, d.clamp_lo, d.clamp_hi = None, 0.0, 0.0, 0.0
-    if planar_out:
-        out = torch.empty((cw.cout, ho, wo), dtype=torch.float32, device=src0.device)
-        d.out_mode, d.out_c = OUT_PLANAR32, 0
-        if res_planar is not None:
-            _planar(res_planar, cw.cout)
-            assert tuple(res_planar.shape[1:]) == (ho, wo)
-            d.res_planar = res_planar.data_ptr()
-        d.add_const = add_const
-        if clamp is not None:
-            d.clamp_lo, d.clamp_hi = clamp
-    elif cw.shuffle:
-        co = _round_up(cw.cout // 4, 8)             # channel stride of the map (padding channels are written as zeros)
-        out = torch.empty((2 * ho, 2 * wo, co), dtype=torch.float16, device=src0.device)
-        d.out_mode, d.out_c = OUT_NHWC16_SHUFFLE2, co
-    else:
-        co = _round_up(cw.cout, 4 if f32 else 8)
-        out = torch.empty((ho, wo, co), dtype=cw.odtype, device=src0.device)
-        d.out_mode, d.out_c = OUT_NHWC16, co
-    d.out = out.data_ptr()
-    rc = hip.lib().refvsr_conv_mfma(C.byref(d), _stream())
-    hip.check(rc, 'conv_mfma')
-    return out
+    return _conv_mfma(cw, src0, src1, None, stride, pad, act, mul, res, post, planar_out, res_planar, add_const, clamp)
 
 
 def _conv_batch(cw, src0, B, stride, pad, act, post, planar_out, res_planar, add_const, clamp, src1, mul, res):
     assert src1 is None and mul is None and res is None and not cw.shuffle, 'batched conv: single source, no mul / res'
     assert src0.dim() == 4 and src0.shape[0] == B and src0.is_contiguous() and B >= 1
-    f32 = cw.f32
-    _nhwc(src0[0], f32)
-    h, w, c0 = src0.shape[1:]
+    _nhwc(src0[0], cw.f32)
+    c0 = src0.shape[3]
     assert [c0] == list(cw.cpads), 'conv input channels %s do not match packed weights %s' % ([c0], cw.cpads)
+    return _conv_mfma(cw, src0, None, B, stride, cw.ksize // 2 if pad is None else pad, act, None, None, post, planar_out, res_planar,
+                      add_const, clamp)
+
+
+def _conv_mfma(cw, src0, src1, B, stride, pad, act, mul, res, post, planar_out, res_planar, add_const, clamp):
+    """The refvsr_conv_mfma launch of conv() on checked sources: ONE fill of the shared descriptor for one image (B None) or for a
+    contiguous batch (src0 [B,h,w,c], res_planar [B,cout,ho,wo], output [B,...]: RefvsrConv.batch and the bs_* byte strides)."""
+    f32 = cw.f32
+    lead = () if B is None else (B,)
+    h, w, c0 = src0.shape[-3:]
+    c1 = src1.shape[2] if src1 is not None else 0
     k = cw.ksize
-    if pad is None:
-        pad = k // 2
     ho = (h + 2 * pad - k) // stride + 1
     wo = (w + 2 * pad - k) // stride + 1
+    esz = 4 if f32 else 2
     d = cw.desc
-    d.src0, d.c0, d.src1, d.c1 = src0.data_ptr(), c0, None, 0
+    d.src0, d.c0, d.src1, d.c1 = src0.data_ptr(), c0, (src1.data_ptr() if src1 is not None else None), c1
     d.h_in, d.w_in, d.h_out, d.w_out = h, w, ho, wo
     d.stride, d.pad = stride, pad
     d.act_slope, d.post_slope = act, post
-    d.mul, d.mul_c, d.res, d.res_c = None, 0, None, 0
+    for name, m_ in (('mul', mul), ('res', res)):
+        if m_ is not None:
+            _nhwc(m_, f32)
+            assert tuple(m_.shape[:2]) == (ho, wo)
+        setattr(d, name, m_.data_ptr() if m_ is not None else None)
+        setattr(d, name + '_c', m_.shape[2] if m_ is not None else 0)
     d.res_planar, d.add_const, d.clamp_lo, d.clamp_hi = None, 0.0, 0.0, 0.0
-    esz = 4 if f32 else 2
-    d.bs_res_planar = 0
+    d.bs_src0, d.bs_src1, d.bs_res_planar = h * w * c0 * esz, 0, 0
     if planar_out:
-        out = torch.empty((B, cw.cout, ho, wo), dtype=torch.float32, device=src0.device)
+        out = torch.empty(lead + (cw.cout, ho, wo), dtype=torch.float32, device=src0.device)
         d.out_mode, d.out_c = OUT_PLANAR32, 0
         if res_planar is not None:
-            assert res_planar.is_cuda and res_planar.dtype == torch.float32 and res_planar.is_contiguous() and \
-                tuple(res_planar.shape) == (B, cw.cout, ho, wo)
+            _planar(res_planar if B is None else res_planar[0], cw.cout)
+            assert res_planar.is_contiguous() and tuple(res_planar.shape) == lead + (cw.cout, ho, wo)
             d.res_planar = res_planar.data_ptr()
             d.bs_res_planar = cw.cout * ho * wo * 4
         d.add_const = add_const
@@ -265,16 +242,17 @@ def _conv_batch(cw, src0, B, stride, pad, act, post, planar_out, res_planar, add
             d.clamp_lo, d.clamp_hi = clamp
         d.bs_out = cw.cout * ho * wo * 4
     else:
-        co = _round_up(cw.cout, 4 if f32 else 8)
-        out = torch.empty((B, ho, wo, co), dtype=cw.odtype, device=src0.device)
-        d.out_mode, d.out_c = OUT_NHWC16, co
+        up = 2 if cw.shuffle else 1                 # pixel-shuffle weights: [2ho, 2wo, cout / 4]
+        co = _round_up(cw.cout // 4, 8) if cw.shuffle else _round_up(cw.cout, 4 if f32 else 8)    # channel stride of the map (padding channels are written as zeros)
+        out = torch.empty(lead + (up * ho, up * wo, co), dtype=torch.float16 if cw.shuffle else cw.odtype, device=src0.device)
+        d.out_mode, d.out_c = OUT_NHWC16_SHUFFLE2 if cw.shuffle else OUT_NHWC16, co
         d.bs_out = ho * wo * co * esz
     d.out = out.data_ptr()
-    d.batch, d.bs_src0, d.bs_src1 = B, h * w * c0 * esz, 0
+    d.batch = B or 0
     try:
         hip.check(hip.lib().refvsr_conv_mfma(C.byref(d), _stream()), 'conv_mfma')
     finally:
-        d.batch = 0                                  # the descriptor is shared with the single-image calls
+        d.batch = 0                                  # the descriptor is shared between the batched and the single-image calls
     return out
 
 
@@ -394,18 +372,23 @@ def _rb_entry(c, chain, name):
             hip.check(hip.lib().refvsr_set_resblock24_waves(int(os.environ['REFVSR_RESBLOCK24_WAVES'])), 'set_resblock24_waves')
         if os.environ.get('REFVSR_RB24_STORE'):
             hip.check(hip.lib().refvsr_set_resblock24_store(int(os.environ['REFVSR_RB24_STORE'])), 'set_resblock24_store')
-    return getattr(hip.lib(), 'refvsr_' + name + ('_f16w' if c == 24 and getattr(chain, 'wfmt', 'hi_lo') == 'fp16' else ''))
+    return _entry('refvsr_' + name, c == 24 and getattr(chain, 'wfmt', 'hi_lo') == 'fp16')
 
 
-def _rb_chain(c, chain, x, act):
-    _nhwc(x)
-    h, w, cx = x.shape
-    assert cx == c
-    out = torch.empty_like(x)
-    s0 = torch.empty_like(x) if chain.n >= 2 else None
-    s1 = torch.empty_like(x) if chain.n >= 3 else None
-    name = 'resblock%d_chain' % c
-    hip.check(_rb_entry(c, chain, name)(_ptr(x), h, w, chain.n, _ptr(chain.blobs), chain.stride, act, _ptr(s0), _ptr(s1), _ptr(out), _stream()), name)
+def _rb_chain(c, chain, xs, act, B=None):
+    """refvsr_resblock<c>_chain on the map xs (B None), or refvsr_resblock<c>_chain_batch on the list xs of B maps -> [B, h, w, c]."""
+    maps = [xs] if B is None else xs
+    for t_ in maps:
+        _nhwc(t_)
+        assert tuple(t_.shape) == tuple(maps[0].shape) and t_.shape[2] == c
+    h, w, _ = maps[0].shape
+    out = torch.empty(((B,) if B else ()) + (h, w, c), dtype=torch.float16, device=maps[0].device)
+    s0 = torch.empty_like(out) if chain.n >= 2 else None
+    s1 = torch.empty_like(out) if chain.n >= 3 else None
+    name = 'resblock%d_chain' % c + ('_batch' if B else '')
+    src = (_parr(xs), B) if B else (_ptr(xs),)
+    hip.check(_rb_entry(c, chain, name)(*src, h, w, chain.n, _ptr(chain.blobs), chain.stride, act, _ptr(s0), _ptr(s1),
+                                        _parr(list(out)) if B else _ptr(out), _stream()), name)
     return out
 
 
@@ -449,15 +432,26 @@ def conf_alpha(conf_a, conf_b, up, w0, b0, cw, slope0=0.2, slope1=0.2, want_max=
     """refvsr_conf_alpha: conv_{16->C}(lrelu(conv_{2->16}(P))) with P = cat[conf_a, conf_b] (up = 1) or its clamped bicubic x2
     up-sampling (up = 2), one launch.  conf_a / conf_b planar fp32 [1,h,w]; w0 / b0 the 2 -> 16 conv (fp32, device); cw the packed
     16 -> C conv (ConvWeights with a conv24 / conv48 blob).  Returns alpha [up h, up w, C] (and max(conf_a, conf_b) [1,h,w])."""
-    _planar(conf_a, 1)
-    _planar(conf_b, 1)
-    assert conf_a.shape == conf_b.shape and cw.blob24 is not None and cw.cpads == [16] and cw.cout in (24, 48)
+    return _conf_alpha(conf_a, conf_b, up, w0, b0, cw, slope0, slope1, want_max)
+
+
+def _conf_alpha(conf_as, conf_bs, up, w0, b0, cw, slope0, slope1, want_max, B=None):
+    """refvsr_conf_alpha on one pair of maps (B None), or refvsr_conf_alpha_batch on the lists of B maps -> [B, ...] results."""
+    a_s, b_s = ([conf_as], [conf_bs]) if B is None else (conf_as, conf_bs)
+    for t_ in list(a_s) + list(b_s):
+        _planar(t_, 1)
+        assert t_.shape == a_s[0].shape
+    assert cw.blob24 is not None and cw.cpads == [16] and cw.cout in ((24, 48) if B is None else (24,))
     assert tuple(w0.shape) == (16, 2, 3, 3) and w0.is_cuda and w0.dtype == torch.float32 and w0.is_contiguous() and b0.numel() == 16
-    h, w = conf_a.shape[1:]
-    alpha = torch.empty((up * h, up * w, cw.cout), dtype=torch.float16, device=conf_a.device)
-    cmax = torch.empty_like(conf_a) if want_max else None
-    hip.check(_c24(cw, 'refvsr_conf_alpha')(_ptr(conf_a), _ptr(conf_b), h, w, up, _ptr(w0), _ptr(b0), slope0, _ptr(cw.blob24), cw.cout,
-                                          slope1, _ptr(alpha), _ptr(cmax), _stream()), 'conf_alpha')
+    lead = (B,) if B else ()
+    h, w = a_s[0].shape[1:]
+    dev = a_s[0].device
+    alpha = torch.empty(lead + (up * h, up * w, cw.cout), dtype=torch.float16, device=dev)
+    cmax = torch.empty(lead + (1, h, w), dtype=torch.float32, device=dev) if want_max else None
+    tab = (lambda t: None if t is None else _parr(list(t))) if B else _ptr
+    name = 'conf_alpha_batch' if B else 'conf_alpha'
+    hip.check(_c24(cw, 'refvsr_' + name)(tab(conf_as), tab(conf_bs), *lead, h, w, up, _ptr(w0), _ptr(b0), slope0, _ptr(cw.blob24), cw.cout,
+                                         slope1, tab(alpha), tab(cmax), _stream()), name)
     return (alpha, cmax) if want_max else alpha
 
 
@@ -565,13 +559,21 @@ def conf_alpha_ok(cw):
     return cw.blob24 is not None and cw.cpads == [16] and cw.cout in (24, 48) and not cw.shuffle
 
 
-def pack_nhwc16(x, cs=None):
+def _pack_nhwc(x, cs, name, align, dtype):
     _planar(x)
     c, h, w = x.shape
-    cs = cs or (c + 7) // 8 * 8
-    out = torch.empty((h, w, cs), dtype=torch.float16, device=x.device)
-    hip.check(hip.lib().refvsr_pack_nhwc16(_ptr(x), c, h, w, _ptr(out), cs, _stream()), 'pack_nhwc16')
+    cs = cs or _round_up(c, align)
+    out = torch.empty((h, w, cs), dtype=dtype, device=x.device)
+    hip.check(getattr(hip.lib(), 'refvsr_' + name)(_ptr(x), c, h, w, _ptr(out), cs, _stream()), name)
     return out
+
+
+def pack_nhwc16(x, cs=None):
+    return _pack_nhwc(x, cs, 'pack_nhwc16', 8, torch.float16)
+
+
+def pack_nhwc32(x, cs=None):
+    return _pack_nhwc(x, cs, 'pack_nhwc32', 4, torch.float32)
 
 
 def conv1x1_f32(x, w, b, act=0.2):
@@ -581,15 +583,6 @@ def conv1x1_f32(x, w, b, act=0.2):
     assert tuple(w.shape) == (16, cin) and w.dtype == torch.float32 and w.is_contiguous() and tuple(b.shape) == (16,)
     out = torch.empty((16, h, w_), dtype=torch.float32, device=x.device)
     hip.check(hip.lib().refvsr_conv1x1_f32(_ptr(x), cin, h, w_, _ptr(w), _ptr(b), float(act), _ptr(out), _stream()), 'conv1x1_f32')
-    return out
-
-
-def pack_nhwc32(x, cs=None):
-    _planar(x)
-    c, h, w = x.shape
-    cs = cs or (c + 3) // 4 * 4
-    out = torch.empty((h, w, cs), dtype=torch.float32, device=x.device)
-    hip.check(hip.lib().refvsr_pack_nhwc32(_ptr(x), c, h, w, _ptr(out), cs, _stream()), 'pack_nhwc32')
     return out
 
 
@@ -633,12 +626,20 @@ def flow_up2(flow):
     return resize(flow, (2 * h, 2 * w), RS_BILINEAR_AC, (0.0, 0.0), chan_mul=[2.0] * c)
 
 
-def avgpool2(x):
+def _pool2(x, name):
     _planar(x)
     c, h, w = x.shape
     out = torch.empty((c, h // 2, w // 2), dtype=torch.float32, device=x.device)
-    hip.check(hip.lib().refvsr_avgpool2(_ptr(x), c, h, w, _ptr(out), _stream()), 'avgpool2')
+    hip.check(getattr(hip.lib(), 'refvsr_' + name)(_ptr(x), c, h, w, _ptr(out), _stream()), name)
     return out
+
+
+def avgpool2(x):
+    return _pool2(x, 'avgpool2')
+
+
+def maxpool2(x):
+    return _pool2(x, 'maxpool2')
 
 
 def avgpool_pyramid(x):
@@ -677,19 +678,23 @@ def frame_prep(lr, ref, w, b):
     return lr8, ref8, lr_n, ref_n
 
 
-def maxpool2(x):
-    _planar(x)
-    c, h, w = x.shape
-    out = torch.empty((c, h // 2, w // 2), dtype=torch.float32, device=x.device)
-    hip.check(hip.lib().refvsr_maxpool2(_ptr(x), c, h, w, _ptr(out), _stream()), 'maxpool2')
-    return out
-
-
 def max2(a, b):
     assert a.shape == b.shape and a.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
     out = torch.empty_like(a)
     hip.check(hip.lib().refvsr_max2(_ptr(a), _ptr(b), _ptr(out), a.numel(), _stream()), 'max2')
     return out
+
+
+def _pairs_equal(pairs, name, nbytes, check):
+    """refvsr_<name> over (a, b) pairs of nbytes bytes each, check(a, b) asserted per pair: one launch per 32 pairs, one D2H sync."""
+    flags = torch.ones(len(pairs), dtype=torch.int32, device=pairs[0][0].device)
+    for s0 in range(0, len(pairs), 32):
+        chunk = pairs[s0:s0 + 32]
+        for a, b in chunk:
+            check(a, b)
+        hip.check(getattr(hip.lib(), 'refvsr_' + name)(_parr([a for a, _ in chunk]), _parr([b for _, b in chunk]), len(chunk), nbytes,
+                                                       C.c_void_p(flags.data_ptr() + 4 * s0), _stream()), name)
+    return [bool(v) for v in flags.cpu().tolist()]
 
 
 def buffers_equal(pairs):
@@ -698,17 +703,11 @@ def buffers_equal(pairs):
     if not pairs:
         return []
     nbytes = pairs[0][0].numel() * 4
-    flags = torch.ones(len(pairs), dtype=torch.int32, device=pairs[0][0].device)
-    for s0 in range(0, len(pairs), 32):
-        chunk = pairs[s0:s0 + 32]
-        for a, b in chunk:
-            assert a.shape == b.shape and a.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
-            assert a.numel() * 4 == nbytes
-        pa = (C.c_void_p * len(chunk))(*[a.data_ptr() for a, _ in chunk])
-        pb = (C.c_void_p * len(chunk))(*[b.data_ptr() for _, b in chunk])
-        hip.check(hip.lib().refvsr_buffers_equal(pa, pb, len(chunk), nbytes, C.c_void_p(flags.data_ptr() + 4 * s0),
-                                                 _stream()), 'buffers_equal')
-    return [bool(v) for v in flags.cpu().tolist()]
+
+    def check(a, b):
+        assert a.shape == b.shape and a.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
+        assert a.numel() * 4 == nbytes
+    return _pairs_equal(pairs, 'buffers_equal', nbytes, check)
 
 
 def bytes_equal(pairs):
@@ -718,17 +717,11 @@ def bytes_equal(pairs):
     if not pairs:
         return []
     nbytes = pairs[0][0].numel()
-    flags = torch.ones(len(pairs), dtype=torch.int32, device=pairs[0][0].device)
-    for s0 in range(0, len(pairs), 32):
-        chunk = pairs[s0:s0 + 32]
-        for a, b in chunk:
-            assert a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.numel() == b.numel() == nbytes
-            assert all(x.is_contiguous() or u8_layout(x) is not None for x in (a, b))
-        pa = (C.c_void_p * len(chunk))(*[a.data_ptr() for a, _ in chunk])
-        pb = (C.c_void_p * len(chunk))(*[b.data_ptr() for _, b in chunk])
-        hip.check(hip.lib().refvsr_bytes_equal(pa, pb, len(chunk), nbytes, C.c_void_p(flags.data_ptr() + 4 * s0),
-                                               _stream()), 'bytes_equal')
-    return [bool(v) for v in flags.cpu().tolist()]
+
+    def check(a, b):
+        assert a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.numel() == b.numel() == nbytes
+        assert all(x.is_contiguous() or u8_layout(x) is not None for x in (a, b))
+    return _pairs_equal(pairs, 'bytes_equal', nbytes, check)
 
 
 def u8_layout(x):
@@ -818,17 +811,25 @@ def _score_inputs(outs, gts, what, down=1):
     return outs, gts, h, w, fmts[a0.dtype] | (hip.RESULT_HWC if alay == 'hwc' else 0), fmts[g0.dtype], lay
 
 
-def _score_workspace(cache, dev, st, h, w, nbytes, what):
-    """The cached float64 workspace of one full launch per (device, stream, h, w)."""
+def _score_workspace(cache, dev, st, h, w, nbytes, what, esize=8, too_small='frames must be at least 7 x 7'):
+    """The cached workspace of one full launch per (device, stream, h, w): nbytes() bytes as floats of esize = 8 | 4 bytes."""
     key = (dev, st.value, h, w)
     ws = cache.get(key)
     if ws is None:
         if len(cache) > 16:
             cache.clear()
+        nbytes = nbytes()
         if nbytes == 0:
-            raise RuntimeError('%s: frames must be at least 7 x 7 (got %d x %d)' % (what, h, w))
-        ws = cache[key] = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+            raise RuntimeError('%s: %s (got %d x %d)' % (what, too_small, h, w))
+        ws = cache[key] = torch.empty(nbytes // esize, dtype={8: torch.float64, 4: torch.float32}[esize], device=dev)
     return ws
+
+
+def _score_launches(outs, gts, launch):
+    """launch(pa, pg, n, s0) per REFVSR_SCORE_MAX_FRAMES pairs: the pointer tables of the n pairs from s0 on."""
+    for s0 in range(0, len(outs), hip.SCORE_MAX_FRAMES):
+        n = min(hip.SCORE_MAX_FRAMES, len(outs) - s0)
+        launch(_parr(outs[s0:s0 + n]), _parr(gts[s0:s0 + n]), n, s0)
 
 
 def score_frames(outs, gts, win=7, down=1):
@@ -846,17 +847,16 @@ def score_frames(outs, gts, win=7, down=1):
     outs, gts, h, w, afmt, gfmt, lay = _score_inputs(outs, gts, 'score_frames', down)
     st = _stream()
     dev = outs[0].device
-    ws = _score_workspace(_SCORE_WS, dev, st, h, w, hip.lib().refvsr_score_workspace_bytes(hip.SCORE_MAX_FRAMES, h, w), 'score_frames')
+    ws = _score_workspace(_SCORE_WS, dev, st, h, w, lambda: hip.lib().refvsr_score_workspace_bytes(hip.SCORE_MAX_FRAMES, h, w), 'score_frames')
     scores = torch.empty((len(outs), 2), dtype=torch.float64, device=dev)
-    for s0 in range(0, len(outs), hip.SCORE_MAX_FRAMES):
-        n = min(hip.SCORE_MAX_FRAMES, len(outs) - s0)
-        pa = (C.c_void_p * n)(*[a.data_ptr() for a in outs[s0:s0 + n]])
-        pg = (C.c_void_p * n)(*[g.data_ptr() for g in gts[s0:s0 + n]])
+
+    def launch(pa, pg, n, s0):
         tail = (int(win), _ptr(ws), ws.numel() * 8, C.c_void_p(scores.data_ptr() + 16 * s0), st)
         if down == 1:
             hip.check(hip.lib().refvsr_score_frames(pa, afmt, pg, gfmt, lay, n, h, w, *tail), 'score_frames')
         else:
             hip.check(hip.lib().refvsr_score_frames_down(pa, afmt, pg, gfmt, lay, n, h, w, int(down), *tail), 'score_frames_down')
+    _score_launches(outs, gts, launch)
     return scores
 
 
@@ -875,15 +875,12 @@ def score_regions(outs, gts, rects):
     crects = (C.c_int * max(4 * nr, 1))(*[v for r in rects for v in r])
     st = _stream()
     dev = outs[0].device
-    ws = _score_workspace(_REGION_WS, dev, st, h, w, hip.lib().refvsr_score_regions_workspace_bytes(hip.SCORE_MAX_FRAMES, h, w, hip.SCORE_MAX_RECTS),
-                          'score_regions')
+    ws = _score_workspace(_REGION_WS, dev, st, h, w,
+                          lambda: hip.lib().refvsr_score_regions_workspace_bytes(hip.SCORE_MAX_FRAMES, h, w, hip.SCORE_MAX_RECTS), 'score_regions')
     sums = torch.empty((len(outs), nr, 2), dtype=torch.float64, device=dev)
-    for s0 in range(0, len(outs), hip.SCORE_MAX_FRAMES):
-        n = min(hip.SCORE_MAX_FRAMES, len(outs) - s0)
-        pa = (C.c_void_p * n)(*[a.data_ptr() for a in outs[s0:s0 + n]])
-        pg = (C.c_void_p * n)(*[g.data_ptr() for g in gts[s0:s0 + n]])
-        hip.check(hip.lib().refvsr_score_regions(pa, afmt, pg, gfmt, lay, n, h, w, crects, nr, _ptr(ws), ws.numel() * 8,
-                                                 C.c_void_p(sums.data_ptr() + 16 * nr * s0), st), 'score_regions')
+    _score_launches(outs, gts, lambda pa, pg, n, s0: hip.check(
+        hip.lib().refvsr_score_regions(pa, afmt, pg, gfmt, lay, n, h, w, crects, nr, _ptr(ws), ws.numel() * 8,
+                                       C.c_void_p(sums.data_ptr() + 16 * nr * s0), st), 'score_regions'))
     return sums
 
 
@@ -914,20 +911,12 @@ def conf_colormap(maps):
             raise RuntimeError('conf_colormap: maps must be single [.., %d, %d] maps of one geometry (got %s)' % (h, w, tuple(m.shape)))
     st = _stream()
     dev = maps[0].device
-    key = (dev, st.value, h, w)
-    ws = _COLORMAP_WS.get(key)
-    if ws is None:
-        if len(_COLORMAP_WS) > 16:
-            _COLORMAP_WS.clear()
-        nbytes = hip.lib().refvsr_conf_colormap_workspace_bytes(hip.COLORMAP_MAX_MAPS, h, w)
-        if nbytes == 0:
-            raise RuntimeError('conf_colormap: maps must hold 1 .. 2^31 - 1 samples (got %d x %d)' % (h, w))
-        ws = _COLORMAP_WS[key] = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    ws = _score_workspace(_COLORMAP_WS, dev, st, h, w, lambda: hip.lib().refvsr_conf_colormap_workspace_bytes(hip.COLORMAP_MAX_MAPS, h, w),
+                          'conf_colormap', 4, 'maps must hold 1 .. 2^31 - 1 samples')
     outs = [torch.empty((h, w, 3), dtype=torch.uint8, device=dev) for _ in maps]
     for s0 in range(0, len(maps), hip.COLORMAP_MAX_MAPS):
         n = min(hip.COLORMAP_MAX_MAPS, len(maps) - s0)
-        pm = (C.c_void_p * n)(*[m.data_ptr() for m in maps[s0:s0 + n]])
-        po = (C.c_void_p * n)(*[o.data_ptr() for o in outs[s0:s0 + n]])
+        pm, po = _parr(maps[s0:s0 + n]), _parr(outs[s0:s0 + n])
         hip.check(hip.lib().refvsr_conf_colormap(pm, n, h, w, po, _ptr(ws), ws.numel() * 4, st), 'conf_colormap')
     return outs
 
@@ -1183,17 +1172,7 @@ def _rb_chain_b(c, single, chain, xs, act, stack):
     B = len(xs)
     if not multimap_ok(B):
         return _maps([single(chain, x, act) for x in xs], stack)
-    for t_ in xs:
-        _nhwc(t_)
-        assert tuple(t_.shape) == tuple(xs[0].shape) and t_.shape[2] == c
-    h, w, _ = xs[0].shape
-    out = torch.empty((B, h, w, c), dtype=torch.float16, device=xs[0].device)
-    s0 = torch.empty_like(out) if chain.n >= 2 else None
-    s1 = torch.empty_like(out) if chain.n >= 3 else None
-    name = 'resblock%d_chain_batch' % c
-    hip.check(_rb_entry(c, chain, name)(_parr(xs), B, h, w, chain.n, _ptr(chain.blobs), chain.stride, act, _ptr(s0), _ptr(s1),
-                                        _parr(list(out)), _stream()), name)
-    return out
+    return _rb_chain(c, chain, xs, act, B)
 
 
 def resblock24_chain_b(chain, xs, act, stack=True):
@@ -1215,18 +1194,7 @@ def conf_alpha_b(conf_as, conf_bs, up, w0, b0, cw, slope0=0.2, slope1=0.2, want_
         if want_max:
             return _maps([a for a, _ in r], stack), _maps([m for _, m in r], stack)
         return _maps(r, stack)
-    for t_ in list(conf_as) + list(conf_bs):
-        _planar(t_, 1)
-        assert t_.shape == conf_as[0].shape
-    assert cw.blob24 is not None and cw.cpads == [16]
-    h, w = conf_as[0].shape[1:]
-    dev = conf_as[0].device
-    alpha = torch.empty((B, up * h, up * w, 24), dtype=torch.float16, device=dev)
-    cmax = torch.empty((B, 1, h, w), dtype=torch.float32, device=dev) if want_max else None
-    hip.check(_c24(cw, 'refvsr_conf_alpha_batch')(_parr(conf_as), _parr(conf_bs), B, h, w, up, _ptr(w0), _ptr(b0), slope0, _ptr(cw.blob24), 24,
-                                                slope1, _parr(list(alpha)), _parr(list(cmax)) if want_max else None, _stream()),
-              'conf_alpha_batch')
-    return (alpha, cmax) if want_max else alpha
+    return _conf_alpha(conf_as, conf_bs, up, w0, b0, cw, slope0, slope1, want_max, B)
 
 
 def _warp_b(single, name, check, out_shape, xs, flows, stack):

@@ -1524,3 +1524,148 @@ def test_roll_over_counter_of_a_frame_group():
             else:
                 assert all(b - a == reset for a, b in zip(restarts, restarts[1:])), (reset, start, restarts)
                 assert restarts and restarts[0] == reset - start
+
+
+# ------------------------------------------------------------------------------------------ device-message layout (engine.py)
+def _msg_engine(C):
+    """An Engine with the state fields of a h x w = 3 x 5 step on the CPU (no weights, no device): what the messages carry."""
+    from refvsr_amd import engine
+    h, w, cs = 3, 5, (C + 7) // 8 * 8
+    g = torch.Generator().manual_seed(C)
+    e = engine.Engine.__new__(engine.Engine)
+    e.C, e._fw_up_wait, e.frame_itr_num = C, None, 9
+    e.fw_feat = torch.randn(h, w, cs, generator=g).half()
+    e.fw_feat_up = torch.randn(2 * h, 2 * w, cs, generator=g).half()
+    e.fw_flow = torch.randn(2, h, w, generator=g)
+    e.fw_conf = torch.rand(1, h, w, generator=g)
+    return e, h, w, cs
+
+
+def _same_storage(t, buf):
+    lo = buf.data_ptr()
+    return lo <= t.data_ptr() < lo + buf.numel()
+
+
+@pytest.mark.parametrize('C,cs_want', [(24, 24), (36, 40)])
+def test_message_layout_sizes_offsets_and_round_trip(C, cs_want):
+    """msg_nbytes / msg_pack / msg_views: the three closed forms of the docstrings, every part bit for bit at offsets computed here by
+    hand, the 16-byte gap behind a context part of 60 bytes, clones against views."""
+    from refvsr_amd import engine
+    e, h, w, cs = _msg_engine(C)
+    hw = h * w
+    assert cs == cs_want
+    # --- sizes
+    assert e.state_nbytes(h, w) == 64 + engine.msg_nbytes(e._state_spec(h, w)) == 64 + hw * (10 * cs + 12)
+    assert e.state_head_nbytes(h, w) == 64 + engine.msg_nbytes(e._state_spec(h, w, head=True)) == 64 + hw * (2 * cs + 12)
+    ctx = dict(conf=torch.rand(1, h, w), idx=torch.arange(hw, dtype=torch.int32).view(h, w) * 7 - 3,
+               aligned=torch.randn(h, w, cs).half(), aligned_up=torch.randn(2 * h, 2 * w, cs).half())
+    spec = [(k, tuple(ctx[k].shape), ctx[k].dtype) for k in engine.Engine.CTX_FIELDS]
+    pad16 = lambda n: (n + 15) // 16 * 16
+    sizes = [4 * hw, 4 * hw, 2 * hw * cs, 8 * hw * cs]
+    assert 4 * hw == 60 and pad16(60) == 64                  # 3 x 5 int32 / float32: a part that needs a 4-byte gap
+    assert engine.Engine.context_nbytes(spec) == engine.msg_nbytes(spec, 16) == sum(pad16(n) for n in sizes)
+    assert engine.msg_nbytes(spec) == sum(sizes)             # align = 1: back to back
+
+    # --- packed state: [64-byte header][feat][feat_up][flow][conf]
+    buf = e.export_state_packed()
+    assert buf.dtype == torch.uint8 and buf.numel() == e.state_nbytes(h, w)
+    assert buf[:64].view(torch.int32).tolist() == [9, h, w, cs, 0] + [0] * 11
+    o_feat, o_up, o_flow, o_conf = 64, 64 + 2 * hw * cs, 64 + 10 * hw * cs, 64 + 10 * hw * cs + 8 * hw
+    for o, t in ((o_feat, e.fw_feat), (o_up, e.fw_feat_up), (o_flow, e.fw_flow), (o_conf, e.fw_conf)):
+        n = t.numel() * t.element_size()
+        assert torch.equal(buf[o:o + n].view(t.dtype).view(t.shape), t)
+    assert o_conf + 4 * hw == buf.numel()
+    r = engine.Engine.__new__(engine.Engine)
+    r.C = C
+    r.import_state_packed(buf)
+    for k in ('fw_feat', 'fw_feat_up', 'fw_flow', 'fw_conf'):
+        got, want = getattr(r, k), getattr(e, k)
+        assert got.dtype == want.dtype and torch.equal(got, want) and not _same_storage(got, buf)      # state imports clone
+    assert r.frame_itr_num == 9
+
+    # --- split state: head = [header][feat][flow][conf], the 2x state travels as it lies
+    head, up = e.export_state_split()
+    assert up is e.fw_feat_up and head.numel() == e.state_head_nbytes(h, w)
+    assert buf[:64].tolist() == head[:64].tolist()
+    for o, t in ((64, e.fw_feat), (64 + 2 * hw * cs, e.fw_flow), (64 + 2 * hw * cs + 8 * hw, e.fw_conf)):
+        n = t.numel() * t.element_size()
+        assert torch.equal(head[o:o + n].view(t.dtype).view(t.shape), t)
+    r = engine.Engine.__new__(engine.Engine)
+    r.C = C
+    waiter = lambda: None
+    r.import_state_head(head, up, waiter)
+    assert r.fw_feat_up is up and r._fw_up_wait is waiter and r.frame_itr_num == 9
+    assert all(torch.equal(getattr(r, k), getattr(e, k)) and not _same_storage(getattr(r, k), head) for k in ('fw_feat', 'fw_flow', 'fw_conf'))
+    with pytest.raises(AssertionError, match='state buffer does not match this model'):
+        r.import_state_head(head[:-4], up, waiter)
+
+    # --- context parts: CTX_FIELDS order, each padded to 16 bytes
+    cbuf = torch.full((engine.msg_nbytes(spec, 16),), 0xAB, dtype=torch.uint8)
+    end = engine.msg_pack(cbuf, 0, [ctx[k] for k in engine.Engine.CTX_FIELDS], 16)
+    assert end == cbuf.numel()
+    offs = [0, 64, 128, 128 + pad16(2 * hw * cs)]
+    for o, k in zip(offs, engine.Engine.CTX_FIELDS):
+        n = ctx[k].numel() * ctx[k].element_size()
+        assert torch.equal(cbuf[o:o + n].view(ctx[k].dtype).view(ctx[k].shape), ctx[k])
+    assert cbuf[60:64].tolist() == [0xAB] * 4 and cbuf[124:128].tolist() == [0xAB] * 4          # the gaps are not written
+    views = engine.msg_views(cbuf, 0, spec, 16)
+    copies = engine.msg_views(cbuf, 0, spec, 16, clone=True)
+    assert list(views) == list(copies) == list(engine.Engine.CTX_FIELDS)
+    for o, k in zip(offs, engine.Engine.CTX_FIELDS):
+        assert views[k].data_ptr() == cbuf.data_ptr() + o and torch.equal(views[k], ctx[k])      # context imports are views into buf
+        assert not _same_storage(copies[k], cbuf) and torch.equal(copies[k], ctx[k])
+    # an offset: the same parts behind a prefix
+    shifted = torch.zeros(32 + cbuf.numel(), dtype=torch.uint8)
+    assert engine.msg_pack(shifted, 32, [ctx[k] for k in engine.Engine.CTX_FIELDS], 16) == shifted.numel()
+    assert torch.equal(shifted[32 + 64:32 + 64 + 60].view(torch.int32).view(h, w), ctx['idx'])
+    assert torch.equal(engine.msg_views(shifted, 32, spec, 16)['aligned_up'], ctx['aligned_up'])
+
+
+def test_conv_descriptor_batch_is_reset_for_the_single_image_calls(monkeypatch):
+    """conv() fills ONE shared descriptor for both forms: a batched call launches with batch = B and the byte strides and leaves
+    batch = 0 behind (also when the launch fails), so the single-image call that follows launches with batch = 0 -- the library then
+    ignores every bs_* field (include/refvsr_hip.h)."""
+    import types
+    from refvsr_amd import hip, ops
+    seen = []
+
+    class Lib(object):
+        rc = 0
+
+        def refvsr_conv_mfma(self, dref, stream):
+            d = dref._obj
+            seen.append({k: getattr(d, k) for k, _ in hip.RefvsrConv._fields_})
+            return self.rc
+
+        def refvsr_last_error(self):
+            return b'recorder says no'
+    lib = Lib()
+    monkeypatch.setattr(hip, 'lib', lambda: lib)
+    monkeypatch.setattr(ops, '_stream', lambda: None)
+    monkeypatch.setattr(ops, '_nhwc', lambda t, f32=False: t)
+    cw = types.SimpleNamespace(desc=hip.RefvsrConv(), f32=False, shuffle=False, ksize=3, cout=20, cpads=[24], odtype=torch.float16, blob24=None)
+    h, w = 4, 6
+    out = ops.conv(cw, torch.zeros(2, h, w, 24, dtype=torch.float16), batch=2)
+    assert tuple(out.shape) == (2, h, w, 24) and out.dtype == torch.float16
+    d = seen[-1]
+    assert (d['batch'], d['bs_src0'], d['bs_src1'], d['bs_out'], d['bs_res_planar']) == (2, h * w * 24 * 2, 0, h * w * 24 * 2, 0)
+    assert (d['h_in'], d['w_in'], d['h_out'], d['w_out'], d['c0'], d['c1'], d['pad'], d['stride'], d['out_c']) == (h, w, h, w, 24, 0, 1, 1, 24)
+    assert cw.desc.batch == 0
+    rp = torch.zeros(2, 20, h, w)
+    monkeypatch.setattr(ops, '_planar', lambda t, c=None: t)
+    out = ops.conv(cw, torch.zeros(2, h, w, 24, dtype=torch.float16), batch=2, planar_out=True, res_planar=rp, clamp=(0.0, 1.0))
+    d = seen[-1]
+    assert tuple(out.shape) == (2, 20, h, w) and (d['batch'], d['bs_out'], d['bs_res_planar']) == (2, 20 * h * w * 4, 20 * h * w * 4)
+    assert d['out_mode'] == hip.OUT_PLANAR32 and (d['clamp_lo'], d['clamp_hi']) == (0.0, 1.0) and cw.desc.batch == 0
+    # the single-image call behind the batched ones
+    mul = torch.zeros(h, w, 24, dtype=torch.float16)
+    out = ops.conv(cw, torch.zeros(h, w, 24, dtype=torch.float16), mul=mul, act=0.1)
+    d = seen[-1]
+    assert tuple(out.shape) == (h, w, 24) and d['batch'] == 0 and cw.desc.batch == 0
+    assert d['mul'] == mul.data_ptr() and d['mul_c'] == 24 and d['res'] is None and d['res_c'] == 0 and d['res_planar'] is None
+    assert d['out_mode'] == hip.OUT_NHWC16 and (d['clamp_lo'], d['clamp_hi']) == (0.0, 0.0)
+    # a failing batched launch still resets the shared descriptor
+    lib.rc = 1
+    with pytest.raises(RuntimeError, match='conv_mfma'):
+        ops.conv(cw, torch.zeros(2, h, w, 24, dtype=torch.float16), batch=2)
+    assert seen[-1]['batch'] == 2 and cw.desc.batch == 0
