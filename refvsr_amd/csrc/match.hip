@@ -288,8 +288,14 @@ __global__ void match_refine_kernel(const float* __restrict__ lf, int h, int w, 
     float top16 = -INFINITY;
     if (cand_val)
         for (int k = 0; k < ncand; ++k) top16 = fmaxf(top16, cand_val[(size_t)p * ncand + k]);
+    // The top candidate itself is always evaluated: where 2 x margin vanishes against top16 (margin = 0, or below half an ulp of
+    // top16) `> top16 - 2 margin` fails for it too, and every column would end as (-inf, INT_MAX) and be flagged
+    // (tests/test_gpu_match_exact.py, family R at margin = 0).  No other margin is affected: top16 > top16 - 2 margin there.
     for (int k = 0; k < ncand; ++k) {
-        if (cand_val && !(cand_val[(size_t)p * ncand + k] > top16 - 2.0f * margin)) continue;
+        if (cand_val) {
+            const float cv = cand_val[(size_t)p * ncand + k];
+            if (cv != top16 && !(cv > top16 - 2.0f * margin)) continue;
+        }
         int r = cand[(size_t)p * ncand + k];
         r = min(max(r, 0), n_ref - 1);
         const int ry = r / wr, rx = r - ry * wr;
