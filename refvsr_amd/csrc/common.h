@@ -10,6 +10,7 @@
 #include <utility>
 
 #include "../../include/refvsr_hip.h"
+#include "plan_common.h"
 
 typedef _Float16 f16;
 typedef f16 f16x2 __attribute__((ext_vector_type(2)));
@@ -17,16 +18,6 @@ typedef f16 f16x4 __attribute__((ext_vector_type(4)));
 typedef f16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-void refvsr_set_error(const char* fmt, ...);
-
-#define RV_CHECK(cond, ...)                        \
-    do {                                           \
-        if (!(cond)) {                             \
-            refvsr_set_error(__VA_ARGS__);         \
-            return 1;                              \
-        }                                          \
-    } while (0)
 
 #define RV_HIP(call)                                                                  \
     do {                                                                              \
@@ -38,8 +29,6 @@ void refvsr_set_error(const char* fmt, ...);
     } while (0)
 
 #define RV_LAUNCH_CHECK() RV_HIP(hipGetLastError())
-
-static inline int rv_cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // f(std::integral_constant<int, I>{}) for every I of the sequence, in order: a loop whose index is a compile-time constant
 template <class F, int... I>
@@ -68,30 +57,37 @@ static inline int rv_num_cus() {
 int rv_stream_cus(hipStream_t st);
 
 // Grid cap of a persistent launcher on `st`, with the launcher's per-device one-time set-up (a process may drive several GPUs): the
-// kernel's dynamic-LDS attribute (attr_lds bytes) and its occupancy with `lds` bytes (asked again when lds changes; block = 0: one
-// workgroup per CU by construction, nothing is asked).  *cap = CUs of the stream x occupancy, a multiple of 8 (XCDs), at least 8.
+// kernel's dynamic-LDS attribute (attr_lds bytes) and its occupancy with `lds` bytes (block = 0: one workgroup per CU by
+// construction, nothing is asked).  *cap = CUs of the stream x occupancy / div, a multiple of 8 (XCDs), at least 8; div = the
+// grid's extent in y and z.  cap = nullptr: the attribute alone (one workgroup per tile, no cap to compute).
+// The occupancies of the last four LDS sizes are kept: the generic conv launches one instantiation with several carves in turn, and
+// the runtime's occupancy query sits on the launch path.
 // One RvLaunchCap per kernel instantiation (a function-local static of its launcher).
 struct RvLaunchCap {
     bool attr_done[RV_MAX_DEVICES];
-    int occ[RV_MAX_DEVICES];
-    size_t occ_lds[RV_MAX_DEVICES];
+    int occ[RV_MAX_DEVICES][4];                    // 0 = empty entry
+    size_t occ_lds[RV_MAX_DEVICES][4];
+    int next[RV_MAX_DEVICES];                      // entries are replaced in turn
 };
 template <typename Kernel>
-static int rv_launch_cap(RvLaunchCap& c, Kernel kernel, int block, size_t attr_lds, size_t lds, hipStream_t st, int* cap) {
+static int rv_launch_cap(RvLaunchCap& c, Kernel kernel, int block, size_t attr_lds, size_t lds, hipStream_t st, int* cap, int div = 1) {
     const int dev = rv_device();
     if (!c.attr_done[dev]) {
         RV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)attr_lds));
         c.attr_done[dev] = true;
     }
-    if (block == 0) {
-        c.occ[dev] = 1;
-    } else if (c.occ[dev] == 0 || c.occ_lds[dev] != lds) {
-        int occ = 0;
+    if (!cap) return 0;
+    int occ = block == 0 ? 1 : 0;
+    for (int i = 0; i < 4 && !occ; ++i)
+        if (c.occ_lds[dev][i] == lds) occ = c.occ[dev][i];
+    if (!occ) {
         RV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, block, lds));
-        c.occ[dev] = occ < 1 ? 1 : occ;
-        c.occ_lds[dev] = lds;
+        if (occ < 1) occ = 1;
+        const int i = c.next[dev]++ & 3;
+        c.occ_lds[dev][i] = lds;
+        c.occ[dev][i] = occ;
     }
-    *cap = (rv_stream_cus(st) * c.occ[dev]) & ~7;
+    *cap = (rv_stream_cus(st) * occ / div) & ~7;
     if (*cap < 8) *cap = 8;
     return 0;
 }
@@ -314,34 +310,6 @@ static inline bool rv_result_fmt_ok(const int fmt) {
     return fmt >= 0 && (fmt & ~(REFVSR_RESULT_FMT_MASK | REFVSR_RESULT_HWC)) == 0 && (fmt & REFVSR_RESULT_FMT_MASK) <= REFVSR_RESULT_U8;
 }
 
-// ---- K-block order of the MFMA convolutions (shared with refvsr_amd/packing.py:kslot) --------------------------
-// A K-block is one 16-byte channel group `cg` of one tap (ty, tx).  A wave's ds_read_b128 of the B operand is
-// served in four groups of 16 lanes, each mixing TWO adjacent K-blocks (q = 0|1 or 2|3, MI355X_MICROARCH.md
-// "LDS": {0-3,12-15,20-27}, {4-11,16-19,28-31}, ...).  With the pixel -> lane permutation rv_pix16 the eight lanes
-// of one K-block in a group sit on even (or odd) pixels, so a group is bank-conflict free iff the two K-blocks'
-// LDS slot offsets have the same parity = (tx + cg) & 1 (tile pitch even, pixel stride odd).  K-blocks are
-// therefore ordered: all even-parity blocks in natural (ty, tx, cg) order, one zero block if their count E is odd,
-// all odd-parity blocks, zero blocks up to a multiple of 4.
-__host__ __device__ inline int rv_keven(int ks, int ncg) {
-    const int ce = (ncg + 1) >> 1, co = ncg >> 1;
-    return ks * (((ks + 1) >> 1) * ce + (ks >> 1) * co);
-}
-__host__ __device__ inline int rv_ksteps(int ks, int ncg) { return (ks * ks * ncg + (rv_keven(ks, ncg) & 1) + 3) / 4; }
-__host__ __device__ inline int rv_kslot(int ty, int tx, int cg, int ks, int ncg) {
-    const int ce = (ncg + 1) >> 1, co = ncg >> 1;
-    const int p = (tx + cg) & 1;
-    const int c0 = p ? co : ce, c1 = p ? ce : co;                 // class-p blocks per tap with even | odd tx
-    const int row = ((ks + 1) >> 1) * c0 + (ks >> 1) * c1;
-    const int rank = ty * row + ((tx + 1) >> 1) * c0 + (tx >> 1) * c1 + (cg >> 1);
-    if (!p) return rank;
-    const int E = rv_keven(ks, ncg);
-    return E + (E & 1) + rank;
-}
-// j-th zero block (j = 0 .. 4*S - G - 1) -> slot
-__host__ __device__ inline int rv_kpad_slot(int j, int ks, int ncg) {
-    const int E = rv_keven(ks, ncg);
-    return ((E & 1) && j == 0) ? E : ks * ks * ncg + j;
-}
 // MFMA column n (= lane & 15) -> pixel of the 16-pixel tile: the lanes a ds_read_b128 group takes from one K-block
 // ({0-3, 12-15} | {4-11}) land on the even | odd pixels.
 __device__ __forceinline__ int rv_pix16(int n) { return (n < 4 || n >= 12) ? ((n & 7) << 1) : (((n - 4) << 1) | 1); }

@@ -38,12 +38,7 @@
 #include <type_traits>
 
 #include "common.h"
-#include <stdlib.h>
-
-#define CONV_CH 8          // K-steps of weights per streamed LDS chunk (chunked convs)
-#define CONV_RES_MAX 16    // K-steps a resident weight set may have (persistent convs)
-#define CONV_XPF 8         // uint4 prefetch registers per thread for the next input tile (persistent convs)
-#define CONV_TW 32         // output tile width in pixels
+#include "conv_plan.h"
 
 struct ConvArgs {
     const unsigned char* src0; const unsigned char* src1;   // HWC maps: f16 (8 ch / 16 B) or f32 (4 ch / 16 B)
@@ -713,75 +708,37 @@ extern "C" int refvsr_ksteps(int ksize, int ncg) { return rv_ksteps(ksize, ncg);
 
 // RESIDENT kernels launch only as many workgroups as the chip holds at once (occupancy x CUs, a multiple of 8 for
 // the XCD banding) and walk the tiles; the others launch one workgroup per tile.
-template <int MT, int TILES, bool F32, bool GATHER, bool RESIDENT, int EPI = 0, int NW = 4, bool HI1 = false>
+template <int MT, int TILES, bool F32, bool GATHER, bool RESIDENT, int EPI, int NW, bool HI1>
 static int launch_conv(ConvArgs& a, int nz, size_t lds, hipStream_t st) {
-    // per device: the dynamic-LDS attribute and the occupancy table (a process may drive several GPUs)
-    static bool attr_done[RV_MAX_DEVICES] = {};
-    const int dev = rv_device();
-    if (!attr_done[dev]) {
-        RV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<MT, TILES, F32, GATHER, RESIDENT, EPI, NW, HI1>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done[dev] = true;
-    }
-    int gx = a.n_xy;
+    static RvLaunchCap lc = {};
+    int gx = a.n_xy, cap = 0;
+    if (int rc = rv_launch_cap(lc, &conv_mfma_kernel<MT, TILES, F32, GATHER, RESIDENT, EPI, NW, HI1>, NW * 64, 160 * 1024, lds, st,
+                               RESIDENT ? &cap : nullptr, nz * a.batch))
+        return rc;
     if (RESIDENT) {
-        static size_t occ_lds[RV_MAX_DEVICES][4] = {};
-        static int occ_val[RV_MAX_DEVICES][4] = {};
-        static int slot[RV_MAX_DEVICES] = {};
-        int occ = 0;
-        for (int i = 0; i < 4; ++i)
-            if (occ_lds[dev][i] == lds && occ_val[dev][i] > 0) occ = occ_val[dev][i];
-        if (occ == 0) {
-            RV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv_mfma_kernel<MT, TILES, F32, GATHER, RESIDENT, EPI, NW, HI1>, NW * 64, lds));
-            if (occ < 1) occ = 1;
-            occ_lds[dev][slot[dev] & 3] = lds; occ_val[dev][slot[dev] & 3] = occ; ++slot[dev];
-        }
-        int cap = (rv_stream_cus(st) * occ / (nz * (a.batch > 1 ? a.batch : 1))) & ~7;
-        if (cap < 8) cap = 8;
         if (g_wg_cap > 0) cap = g_wg_cap;                          // refvsr_set_conv_workgroup_cap
         if (gx > cap) gx = cap;
     }
     a.grid = gx;
-    hipLaunchKernelGGL((conv_mfma_kernel<MT, TILES, F32, GATHER, RESIDENT, EPI, NW, HI1>), dim3(gx, a.batch > 1 ? a.batch : 1, nz), dim3(NW * 64), lds, st, a);
+    hipLaunchKernelGGL((conv_mfma_kernel<MT, TILES, F32, GATHER, RESIDENT, EPI, NW, HI1>), dim3(gx, a.batch, nz), dim3(NW * 64), lds, st, a);
     RV_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int refvsr_conv_mfma(const RefvsrConv* d, void* stream) {
-    RV_CHECK(d != nullptr, "conv: null descriptor");
-    const bool f32 = d->f32 == 1;
-    const bool hi1 = d->f32 == 2;                      // fp16 weights without the lo term (streamed kernels only)
-    RV_CHECK(d->f32 >= 0 && d->f32 <= 2, "conv: weight mode (f32) must be 0, 1 or 2");
-    const int cgrp = f32 ? 4 : 8;                      // channels per 16-byte group
-    const int esz = f32 ? 4 : 2;
-    RV_CHECK(d->src0 && d->c0 > 0 && d->c0 % cgrp == 0, "conv: src0/c0 invalid (c0=%d)", d->c0);
-    RV_CHECK((d->src1 == nullptr) == (d->c1 == 0) && d->c1 % cgrp == 0, "conv: src1/c1 invalid (c1=%d)", d->c1);
-    RV_CHECK(d->ksize >= 1 && d->ksize <= 7 && d->stride >= 1 && d->pad >= 0, "conv: bad geometry");
-    RV_CHECK(d->h_in > 0 && d->w_in > 0 && d->h_out > 0 && d->w_out > 0, "conv: bad sizes");
-    RV_CHECK(d->wpack && d->bias && d->out, "conv: null weights/bias/out");
-    RV_CHECK(d->mt_per_block >= 1 && d->mt_per_block <= 3, "conv: mt_per_block must be 1..3");
-    RV_CHECK(d->cout >= 1, "conv: cout");
-    if (d->out_mode != REFVSR_OUT_PLANAR32) {
-        RV_CHECK(d->cout % 4 == 0 && d->out_c % 4 == 0, "conv: nhwc16 output needs cout %% 4 == 0");
-        RV_CHECK(d->res_planar == nullptr, "conv: res_planar only with planar output");
-    }
-    if (d->out_mode == REFVSR_OUT_NHWC16_SHUFFLE2)
-        RV_CHECK(d->cout % 16 == 0 && !d->mul && !d->res && !f32 && d->out_c >= d->cout / 4 && d->out_c - d->cout / 4 <= 4,
-                 "conv: pixel-shuffle output constraints");
-    RV_CHECK(refvsr_init() == 0, "init failed");
-
+// kernel arguments of a checked descriptor and its plan
+static ConvArgs conv_args(const RefvsrConv* d, const ConvPlan& p) {
+    const int cgrp = p.F32 ? 4 : 8, esz = p.F32 ? 4 : 2;           // channels per 16-byte group, bytes per element
     ConvArgs a;
     memset(&a, 0, sizeof(a));
     a.src0 = (const unsigned char*)d->src0; a.src1 = (const unsigned char*)d->src1;
     a.c0 = d->c0; a.c1 = d->c1;
     a.pixb0 = d->c0 * esz; a.pixb1 = d->c1 * esz;
     a.ncg0 = d->c0 / cgrp; a.ncg = (d->c0 + d->c1) / cgrp;
-    a.ps = a.ncg | 1;
+    a.ps = p.ps;
     a.h_in = d->h_in; a.w_in = d->w_in; a.h_out = d->h_out; a.w_out = d->w_out;
     a.ks = d->ksize; a.stride = d->stride; a.pad = d->pad;
-    a.G = d->ksize * d->ksize * a.ncg;
-    a.S = rv_ksteps(d->ksize, a.ncg);
-    RV_CHECK(a.S == d->ksteps, "conv: ksteps mismatch (descriptor %d, geometry %d)", d->ksteps, a.S);
+    a.LH = p.LH; a.LW = p.LW;
+    a.G = p.G; a.S = p.S;
     a.inv_ncg = 1.0f / (float)a.ncg;
     a.wpack = (const uint4*)d->wpack; a.bias = d->bias; a.cout = d->cout;
     a.act_slope = d->act_slope; a.post_slope = d->post_slope;
@@ -790,168 +747,25 @@ extern "C" int refvsr_conv_mfma(const RefvsrConv* d, void* stream) {
     a.out_mode = d->out_mode; a.out = d->out; a.out_c = d->out_c;
     a.res_planar = d->res_planar; a.add_const = d->add_const;
     a.clamp_lo = d->clamp_lo; a.clamp_hi = d->clamp_hi;
-    RV_CHECK(d->batch >= 0 && d->batch <= 65535, "conv: batch out of range (%d)", d->batch);
+    a.tab_bytes = p.tab_bytes; a.wl_bytes = p.wl_bytes;
+    a.gather = p.gather; a.ring = p.ring; a.prefetch = p.prefetch;
+    a.tiles_x = p.tiles_x; a.n_xy = p.n_xy;
     a.batch = d->batch > 1 ? d->batch : 1;
-    if (a.batch > 1) {
-        RV_CHECK(!d->mul && !d->res, "conv: batch > 1 takes no mul / res operands");
-        RV_CHECK(d->bs_src0 % 16 == 0 && d->bs_src1 % 16 == 0 && d->bs_out % 8 == 0 && d->bs_res_planar % 4 == 0, "conv: batch strides must keep the maps aligned");
-        RV_CHECK(d->bs_src0 > 0 && d->bs_out > 0 && (!d->src1 || d->bs_src1 > 0) && (!d->res_planar || d->bs_res_planar > 0), "conv: batch strides missing");
-        a.bs_src0 = d->bs_src0; a.bs_src1 = d->bs_src1; a.bs_out = d->bs_out; a.bs_res_planar = d->bs_res_planar;
-    }
+    if (a.batch > 1) { a.bs_src0 = d->bs_src0; a.bs_src1 = d->bs_src1; a.bs_out = d->bs_out; a.bs_res_planar = d->bs_res_planar; }
+    return a;
+}
 
-    const int MT = d->mt_per_block;
-    const int n_mt = (d->cout + 15) / 16;
-    const int nz = (n_mt + MT - 1) / MT;
-    a.tab_bytes = ((a.S * 4 * 4 + 15) / 16) * 16;
-    const int wfr_kb = MT * ((f32 || hi1) ? 1 : 2) * 1024;   // bytes of weight fragments per K-step
-    static const bool no_resident = getenv("REFVSR_CONV_NO_PERSIST") != nullptr;   // A/B knob, read once
-    const size_t LDS_MAX = 160 * 1024;
-
-    int tiles = 4;
-    size_t lds = 0;
-    auto tile_bytes = [&](int tl) {
-        a.LH = (tl * 2 - 1) * a.stride + a.ks;
-        a.LW = (CONV_TW - 1) * a.stride + a.ks;
-        return (size_t)a.LH * a.LW * a.ps * 16;
-    };
-    // RESIDENT: whole weight set in LDS, persistent workgroups with a register-prefetched input tile.  Needs few enough
-    // K-steps, a tile that fits the prefetch registers, and LDS for >= 2 workgroups per CU (8 x 32 pixels preferred,
-    // 4 x 32 when that buys a second / third workgroup).
-    bool resident = false, one_wg = false;             // one_wg: LDS admits a single workgroup per CU
-    bool w16 = false;                                  // 16 x 32 tile, 16 waves
-    static const int res_max = getenv("REFVSR_CONV_RES_MAX") ? atoi(getenv("REFVSR_CONV_RES_MAX")) : CONV_RES_MAX;   // A/B knob
-    if (!no_resident && !hi1 && a.S <= res_max && a.S <= CONV_RES_MAX) {
-        int best_wg = 0;
-        static const int force_tiles = getenv("REFVSR_CONV_TILES") ? atoi(getenv("REFVSR_CONV_TILES")) : 0;   // A/B knob: 2 | 4
-        for (int tl = 4; tl >= 2; tl -= 2) {
-            if (force_tiles && tl != force_tiles) continue;
-            const size_t tb = tile_bytes(tl);
-            const size_t need = (size_t)a.tab_bytes + (size_t)a.S * wfr_kb + tb;
-            const int chunks = a.LH * a.LW * a.ncg;
-            const int wg = need <= LDS_MAX ? (int)(LDS_MAX / need) : 0;
-            if (chunks > CONV_XPF * 256 || wg == 0) continue;
-            if (a.LH > 31 || a.LW > 127 || a.ncg > 127) continue;   // packed chunk descriptor of the tile staging (r:5, c:7, cg:7 + 7 bits)
-            if (best_wg == 0 || (best_wg < 2 && wg > best_wg)) { best_wg = wg; tiles = tl; lds = need; resident = true; }
-        }
-        if (resident) { a.wl_bytes = a.S * wfr_kb; tile_bytes(tiles); one_wg = best_wg == 1; }
-        // One workgroup per CU (the C = 48 weight sets): a 16 x 32 tile walked by SIXTEEN waves (two pixel groups each) keeps
-        // four waves per SIMD next to the 84 KB weight set and halves the halo; 8 waves on 8 x 32 where that does not fit.
-        // (same box, frames/s: RefVSR_MFID 60.6 [4 waves] / 68.9 [8 x 2] / 70.1 [8 x 4] / 72.2 [16 x 2]; MFID_8K 1080p 5.04 / 5.80 / 6.24 / 6.25)
-        static const bool no_w16 = getenv("REFVSR_CONV_NO_W16") != nullptr;          // A/B knob, read once
-        if (resident && one_wg && tiles == 4 && !f32 && !no_w16 && (MT == 2 || MT == 3)) {
-            const size_t tb = tile_bytes(8);
-            const size_t need = (size_t)a.tab_bytes + (size_t)a.S * wfr_kb + tb;
-            const int chunks = a.LH * a.LW * a.ncg;
-            if (need <= LDS_MAX && chunks <= 4096 && a.LH <= 31 && a.LW <= 127) { tiles = 8; lds = need; w16 = true; }
-            else tile_bytes(tiles);
-        }
-    }
-    if (!resident) {
-        // streamed weights: a ring of 2..4 LDS slots of CONV_CH K-steps each next to the staged input tile.  Large maps prefer a
-        // footprint that admits two workgroups per CU; 8 x 32 pixels if the staged input fits, else 4 x 32, else gather mode
-        // (one slot, register-prefetched, B fragments from global memory)
-        const size_t slot = (size_t)CONV_CH * wfr_kb;
-        const int n_chunks = (a.S + CONV_CH - 1) / CONV_CH;
-        auto ring_for = [&](int tl, size_t budget) {
-            const size_t fixed = (size_t)a.tab_bytes + tile_bytes(tl);
-            if (fixed + 2 * slot > budget) return 0;
-            int ns = (int)((budget - fixed) / slot);
-            if (ns > 4) ns = 4;
-            if (ns > n_chunks + 1) ns = n_chunks + 1 > 2 ? n_chunks + 1 : 2;
-            return ns;
-        };
-        static const int force_ring = getenv("REFVSR_CONV_RING") ? atoi(getenv("REFVSR_CONV_RING")) : 0;   // A/B knob: 2 | 3 | 4
-        const bool big = (long long)d->h_out * d->w_out > 64 * 1024;
-        int ns = 0;
-        tiles = 4;
-        if (big) ns = ring_for(4, LDS_MAX / 2);
-        if (!ns && big) { tiles = 2; ns = ring_for(2, LDS_MAX / 2); }
-        if (!ns) { tiles = 4; ns = ring_for(4, LDS_MAX); }
-        if (!ns) { tiles = 2; ns = ring_for(2, LDS_MAX); }
-        if (ns) {
-            if (force_ring >= 2 && force_ring < ns) ns = force_ring;
-            a.ring = ns;
-            a.wl_bytes = (int)(ns * slot);
-            lds = (size_t)a.tab_bytes + (size_t)a.wl_bytes + tile_bytes(tiles);
-        } else {                                       // strided predictor convs: gather B fragments from global memory
-            a.gather = 1;
-            a.ring = 1;
-            tiles = 4;
-            a.LH = a.LW = 0;
-            a.wl_bytes = (int)slot;
-            lds = (size_t)a.tab_bytes + (size_t)a.wl_bytes;
-            RV_CHECK(d->h_in < 60000 && d->w_in < 60000, "conv: frame too large for gather-mode coordinates");
-        }
-        one_wg = !a.gather && lds > LDS_MAX / 2;
-    }
-    // one workgroup per CU: eight waves on the same 8 x 32 tile (two pixel groups per wave) keep two waves per SIMD
-    static const bool no_nw8 = getenv("REFVSR_CONV_NO_NW8") != nullptr;             // A/B knob, read once
-    // ... and eight waves (two pixel groups each) on the other 8 x 32 fp16 tiles as well, unless the map is large: 2 workgroups x
-    // 8 waves = 4 waves per SIMD instead of 3 x 4 = 3 hides more latency (24->24 at 270p 9.7 -> 9.2 us, at 540p 24.3 -> 23.0 us,
-    // same box 156.7 -> 159.3 frames/s on RefVSR_small); at 1080p (4080 tiles, 8 per workgroup) the better weight-fragment
-    // reuse of four pixel groups per wave wins (75.5 vs 78.5 us).  (Forcing <= 80 VGPRs for 6 waves per SIMD spills.)
-    const int n_tiles8 = rv_cdiv(d->w_out, CONV_TW) * rv_cdiv(d->h_out, 8);
-    const bool nw8 = tiles == 4 && !f32 && !a.gather && !no_nw8 && (one_wg || n_tiles8 <= 2048);
-    static const bool no_prefetch = getenv("REFVSR_CONV_NO_PREFETCH") != nullptr;   // A/B knob, read once
-    a.prefetch = no_prefetch ? 0 : 1;
-    a.tiles_x = rv_cdiv(d->w_out, CONV_TW);
-    a.n_xy = a.tiles_x * rv_cdiv(d->h_out, tiles * 2);
-    hipStream_t st = (hipStream_t)stream;
-    if (a.gather) {                                // only the fp16 strided predictors need it
-        RV_CHECK(!f32 && !hi1, "conv: gather mode is built for the fp16 hi+lo path only");
-        if (MT == 1) return launch_conv<1, 4, false, true, false>(a, nz, lds, st);
-        if (MT == 2) return launch_conv<2, 4, false, true, false>(a, nz, lds, st);
-        return launch_conv<3, 4, false, true, false>(a, nz, lds, st);
-    }
-    if (hi1) {                                     // SPyNet's streamed 7x7 convs (Engine.flow): half the weight stream, half the MFMAs
-        RV_CHECK(!a.gather && MT <= 2, "conv: single-fp16 weights are built for the streamed stride-1 convs (MT=%d)", MT);
-        const bool nw8h = tiles == 4 && !no_nw8 && (one_wg || n_tiles8 <= 2048);
-        if (nw8h) return MT == 1 ? launch_conv<1, 2, false, false, false, 0, 8, true>(a, nz, lds, st)
-                                 : launch_conv<2, 2, false, false, false, 0, 8, true>(a, nz, lds, st);
-        if (tiles == 4) return MT == 1 ? launch_conv<1, 4, false, false, false, 0, 4, true>(a, nz, lds, st)
-                                       : launch_conv<2, 4, false, false, false, 0, 4, true>(a, nz, lds, st);
-        return MT == 1 ? launch_conv<1, 2, false, false, false, 0, 4, true>(a, nz, lds, st)
-                       : launch_conv<2, 2, false, false, false, 0, 4, true>(a, nz, lds, st);
-    }
-    // lean epilogue: fp16 HWC output, slopes in [0, 1], maps addressable with 32-bit element offsets, tile coordinates in
-    // the packed chunk descriptor's range
-    static const bool no_lean = getenv("REFVSR_CONV_NO_LEAN_EPI") != nullptr;      // A/B knob, read once
-    const bool lean = resident && !f32 && !no_lean && d->out_mode == REFVSR_OUT_NHWC16 && d->act_slope >= 0.f && d->act_slope <= 1.f &&
-                      d->post_slope >= 0.f && d->post_slope <= 1.f &&
-                      (long long)d->h_out * d->w_out * (long long)(d->out_c > d->mul_c ? (d->out_c > d->res_c ? d->out_c : d->res_c)
-                                                                                       : (d->mul_c > d->res_c ? d->mul_c : d->res_c)) < (1ll << 31);
-#define RV_CONV_CASE(M, T)                                                                                \
-    if (MT == M && tiles == T) {                                                                          \
-        if (f32) return resident ? launch_conv<M, T, true, false, true>(a, nz, lds, st)                   \
-                                 : launch_conv<M, T, true, false, false>(a, nz, lds, st);                 \
-        if (lean) return launch_conv<M, T, false, false, true, 1>(a, nz, lds, st);                        \
-        return resident ? launch_conv<M, T, false, false, true>(a, nz, lds, st)                           \
-                        : launch_conv<M, T, false, false, false>(a, nz, lds, st);                         \
-    }
-    if (w16) {
-        if (MT == 3) return lean ? launch_conv<3, 2, false, false, true, 1, 16>(a, nz, lds, st) : launch_conv<3, 2, false, false, true, 0, 16>(a, nz, lds, st);
-        return lean ? launch_conv<2, 2, false, false, true, 1, 16>(a, nz, lds, st) : launch_conv<2, 2, false, false, true, 0, 16>(a, nz, lds, st);
-    }
-    if (nw8) {
-#define RV_CONV_CASE8(M)                                                                                  \
-        if (MT == M) {                                                                                    \
-            if (lean) return launch_conv<M, 2, false, false, true, 1, 8>(a, nz, lds, st);                 \
-            return resident ? launch_conv<M, 2, false, false, true, 0, 8>(a, nz, lds, st)                 \
-                            : launch_conv<M, 2, false, false, false, 0, 8>(a, nz, lds, st);               \
-        }
-        RV_CONV_CASE8(1) RV_CONV_CASE8(2) RV_CONV_CASE8(3)
-#undef RV_CONV_CASE8
-    }
-    // the exact-fp32 convs (VGG head of the matching) on 4 x 32 tiles: eight waves with one pixel group each (fp32 MFMAs are
-    // slow enough that the lost fragment reuse costs nothing: 64->64 at 270p 115 -> 105 us)
-    if (!no_nw8 && f32 && tiles == 2 && !a.gather && (MT == 1 || MT == 2)) {
-        if (MT == 1) return resident ? launch_conv<1, 1, true, false, true, 0, 8>(a, nz, lds, st) : launch_conv<1, 1, true, false, false, 0, 8>(a, nz, lds, st);
-        return resident ? launch_conv<2, 1, true, false, true, 0, 8>(a, nz, lds, st) : launch_conv<2, 1, true, false, false, 0, 8>(a, nz, lds, st);
-    }
-    RV_CONV_CASE(1, 2) RV_CONV_CASE(1, 4)
-    RV_CONV_CASE(2, 2) RV_CONV_CASE(2, 4)
-    RV_CONV_CASE(3, 2) RV_CONV_CASE(3, 4)
+extern "C" int refvsr_conv_mfma(const RefvsrConv* d, void* stream) {
+    static const ConvKnobs knobs = conv_knobs_from_env();          // A/B knobs, read once
+    ConvPlan p;
+    if (int rc = conv_plan(d, knobs, &p)) return rc;
+    RV_CHECK(refvsr_init() == 0, "init failed");
+    ConvArgs a = conv_args(d, p);
+    switch (p.key()) {                                             // key and launcher of a case: the same entry of RV_CONV_VARIANTS (conv_plan.h)
+#define RV_CONV_CASE(...) case conv_variant_key(__VA_ARGS__): return launch_conv<__VA_ARGS__>(a, p.nz, p.lds, (hipStream_t)stream);
+        RV_CONV_VARIANTS(RV_CONV_CASE)
 #undef RV_CONV_CASE
-    refvsr_set_error("conv: no kernel for MT=%d tiles=%d", MT, tiles);
+    }
+    refvsr_set_error("conv: no kernel for MT=%d tiles=%d", p.MT, p.TILES);
     return 1;
 }

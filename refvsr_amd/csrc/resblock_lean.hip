@@ -342,18 +342,24 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV / 
 extern unsigned long long* g_rb_probe;             // runtime.hip: refvsr_set_probe
 extern int g_rb_probe_iter;
 
-static size_t rl_lds_bytes(int c) {
-    const int ncg = c / 8, ps = ncg | 1;
-    const int S = rv_ksteps(3, ncg);
-    const int MT = (c + 15) / 16;
-    return (size_t)((S * 4 * 2 * 4 + 256 + 15) / 16 * 16) + 2 * (size_t)S * MT * 2 * 1024 + (size_t)RL_XH * RL_XW * ps * 16;
+// geometry and LDS carve of the C-channel block: [two K-slot tables + 2 x 32 bias floats][w1][w2][one activation tile]
+struct RlPlan { int ncg, ps, G, S, MT, tab_bytes, w_bytes; size_t lds; bool wide; };
+static RlPlan rl_plan(int c) {
+    RlPlan p;
+    p.ncg = c / 8; p.ps = p.ncg | 1;
+    p.G = 9 * p.ncg; p.S = rv_ksteps(3, p.ncg);
+    p.MT = (c + 15) / 16;
+    p.tab_bytes = (p.S * 4 * 2 * 4 + 256 + 15) / 16 * 16;
+    p.w_bytes = p.S * p.MT * 2 * 1024;
+    p.lds = (size_t)p.tab_bytes + 2 * (size_t)p.w_bytes + (size_t)RL_XH * RL_XW * p.ps * 16;
+    p.wide = RL_XW * p.ncg > 128;
+    return p;
 }
 
 extern "C" int refvsr_resblock_lean_fits(int c) {
     if (c <= 0 || c % 8 != 0) return 0;
-    if ((c + 15) / 16 > 2) return 0;
-    if (RL_XW * (c / 8) > 256) return 0;
-    return rl_lds_bytes(c) <= 160 * 1024 ? 1 : 0;
+    const RlPlan p = rl_plan(c);
+    return p.MT <= 2 && RL_XW * p.ncg <= 256 && p.lds <= 160 * 1024 ? 1 : 0;
 }
 
 static int g_lean_waves = 8;               // A/B knob (refvsr_set_resblock_waves): 4 or 8 waves per workgroup
@@ -375,6 +381,11 @@ static int launch_lean(ResLeanArgs& a, size_t lds, hipStream_t st) {
     return 0;
 }
 
+// every instantiation X(MT, WIDE, NWV), written down once
+#define RL_VARIANTS(X)                                                             \
+    X(1, false, 8) X(2, false, 8) X(1, true, 8) X(2, true, 8) X(1, false, 4) X(2, false, 4) X(1, true, 4) X(2, true, 4)
+constexpr int rl_variant_key(int MT, bool wide, int waves) { return MT | (int)wide << 2 | waves << 3; }
+
 extern "C" int refvsr_resblock_lean(const void* src, int c, int h, int w, const void* w1, const float* b1,
                                     const void* w2, const float* b2, int ksteps, float act_slope, float post_slope,
                                     void* out, void* stream) {
@@ -384,30 +395,26 @@ extern "C" int refvsr_resblock_lean(const void* src, int c, int h, int w, const 
     RV_CHECK(act_slope >= 0.f && act_slope <= 1.f && post_slope >= 0.f && post_slope <= 1.f,
              "resblock_lean: activation slopes must lie in [0, 1]");
     RV_CHECK(refvsr_init() == 0, "init failed");
+    const RlPlan p = rl_plan(c);
+    RV_CHECK(p.S == ksteps, "resblock_lean: ksteps mismatch (%d vs %d)", ksteps, p.S);
     ResLeanArgs a;
     memset(&a, 0, sizeof(a));
     a.src = (const f16*)src; a.out = (f16*)out;
-    a.c = c; a.ncg = c / 8; a.ps = a.ncg | 1; a.h = h; a.w = w;
-    a.G = 9 * a.ncg; a.S = rv_ksteps(3, a.ncg);
-    RV_CHECK(a.S == ksteps, "resblock_lean: ksteps mismatch (%d vs %d)", ksteps, a.S);
+    a.c = c; a.ncg = p.ncg; a.ps = p.ps; a.h = h; a.w = w;
+    a.G = p.G; a.S = p.S;
     a.inv_ncg = 1.0f / (float)a.ncg;
     a.w1 = (const uint4*)w1; a.b1 = b1; a.w2 = (const uint4*)w2; a.b2 = b2;
     a.act_slope = act_slope; a.post_slope = post_slope;
     a.probe = g_rb_probe; a.probe_iter = g_rb_probe_iter;
-    const int MT = (c + 15) / 16;
-    a.tab_bytes = (a.S * 4 * 2 * 4 + 256 + 15) / 16 * 16;         // two K-slot tables + 2 x 32 bias floats
-    a.w_bytes = a.S * MT * 2 * 1024;
+    a.tab_bytes = p.tab_bytes; a.w_bytes = p.w_bytes;
     a.tiles_x = rv_cdiv(w, RL_TW);
     a.n_tiles = a.tiles_x * rv_cdiv(h, RL_TH);
-    const size_t lds = rl_lds_bytes(c);
-    hipStream_t st = (hipStream_t)stream;
-    const bool wide = RL_XW * a.ncg > 128;
-#define RL_CASE(M, WD, NW_)                                                          \
-    if (MT == M && wide == WD && g_lean_waves == NW_) return launch_lean<M, WD, NW_>(a, lds, st);
-    RL_CASE(1, false, 8) RL_CASE(2, false, 8) RL_CASE(1, true, 8) RL_CASE(2, true, 8)
-    RL_CASE(1, false, 4) RL_CASE(2, false, 4) RL_CASE(1, true, 4) RL_CASE(2, true, 4)
+    switch (rl_variant_key(p.MT, p.wide, g_lean_waves)) {         // key and launcher of a case come from the same list entry
+#define RL_CASE(...) case rl_variant_key(__VA_ARGS__): return launch_lean<__VA_ARGS__>(a, p.lds, (hipStream_t)stream);
+        RL_VARIANTS(RL_CASE)
 #undef RL_CASE
-    refvsr_set_error("resblock_lean: no kernel for MT=%d wide=%d waves=%d", MT, (int)wide, g_lean_waves);
+    }
+    refvsr_set_error("resblock_lean: no kernel for MT=%d wide=%d waves=%d", p.MT, (int)p.wide, g_lean_waves);
     return 1;
 }
 

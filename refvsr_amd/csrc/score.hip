@@ -272,13 +272,17 @@ extern "C" size_t refvsr_score_workspace_bytes(int nframes, int h, int w) {
     return (size_t)nframes * 3 * sc_tiles(h, SC_TH) * sc_tiles(w, SC_TW) * 2 * sizeof(double);
 }
 
-// the two entry points' checks and launches; `who` names the caller in the messages, down = 1 | 2 | 4
-static int sc_run(const char* who, const void* const* out, int out_fmt, const void* const* gt, int gt_fmt, int gt_layout, int nframes, int h, int w,
-                  int down, int win, void* workspace, size_t workspace_bytes, double* scores, void* stream) {
+// What every scoring entry point checks of its frames, and the frame table of its argument struct (ScoreArgs | RegionArgs: a, b, afmt,
+// ahwc, bkind).  `who` names the caller in the messages, `res` its result array ("scores" | "sums"), `needed` its workspace size;
+// own_checks() holds the caller's own arguments and runs where they always have: behind the geometry, ahead of the formats.
+template <typename Args, typename OwnChecks>
+static int sc_frames(const char* who, const char* res, Args& a, const void* const* out, int out_fmt, const void* const* gt, int gt_fmt, int gt_layout,
+                     int nframes, int h, int w, OwnChecks own_checks, const void* workspace, size_t workspace_bytes, size_t needed,
+                     const void* results) {
     RV_CHECK(out && gt, "%s: null frame table", who);
     RV_CHECK(nframes >= 1 && nframes <= REFVSR_SCORE_MAX_FRAMES, "%s: 1..%d frames per launch", who, REFVSR_SCORE_MAX_FRAMES);
     RV_CHECK(sc_geometry_ok(h, w), "%s: h, w must be at least 7 (the SSIM window) and h * w at most 2^29", who);
-    RV_CHECK(win == 7 || win == 0, "%s: win must be 7, or 0 for the mse alone", who);
+    if (int rc = own_checks()) return rc;
     RV_CHECK(rv_result_fmt_ok(out_fmt), "%s: unknown result format %d (REFVSR_RESULT_F32 | _F16 | _U8, optionally | REFVSR_RESULT_HWC)", who, out_fmt);
     const int ahwc = (out_fmt & REFVSR_RESULT_HWC) != 0;
     out_fmt &= REFVSR_RESULT_FMT_MASK;
@@ -286,28 +290,42 @@ static int sc_run(const char* who, const void* const* out, int out_fmt, const vo
     RV_CHECK(gt_layout == REFVSR_INGEST_PLANAR || gt_layout == REFVSR_INGEST_HWC,
              "%s: ground-truth layout must be REFVSR_INGEST_PLANAR | REFVSR_INGEST_HWC", who);
     RV_CHECK(!(gt_fmt == REFVSR_RESULT_F32 && gt_layout == REFVSR_INGEST_HWC), "%s: the interleaved layout is for uint8 ground truth", who);
-    RV_CHECK(workspace && scores, "%s: null workspace / scores", who);
-    RV_CHECK(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)scores & 15) == 0, "%s: workspace and scores must be 16-byte aligned", who);
-    RV_CHECK(workspace_bytes >= refvsr_score_workspace_bytes(nframes, h, w), "%s: workspace too small (%zu bytes, %zu needed)", who,
-             workspace_bytes, refvsr_score_workspace_bytes(nframes, h, w));
-    ScoreArgs a;
+    RV_CHECK(workspace && results, "%s: null workspace / %s", who, res);
+    RV_CHECK(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)results & 15) == 0, "%s: workspace and %s must be 16-byte aligned", who, res);
+    RV_CHECK(workspace_bytes >= needed, "%s: workspace too small (%zu bytes, %zu needed)", who, workspace_bytes, needed);
     memset(&a, 0, sizeof(a));
     const uintptr_t amask = out_fmt == REFVSR_RESULT_F32 ? 3 : out_fmt == REFVSR_RESULT_F16 ? 1 : 0;
     const uintptr_t bmask = gt_fmt == REFVSR_RESULT_F32 ? 3 : 0;
-    a.avec = down == 4 && !ahwc;                                 // (an interleaved tap row is not one aligned group of four)
     for (int i = 0; i < nframes; ++i) {
         RV_CHECK(out[i] && gt[i], "%s: null pointer (frame %d)", who, i);
         RV_CHECK(((uintptr_t)out[i] & amask) == 0 && ((uintptr_t)gt[i] & bmask) == 0,
                  "%s: fp32 frames must be 4-byte, fp16 frames 2-byte aligned (frame %d)", who, i);
-        if ((uintptr_t)out[i] & (4 * (amask + 1) - 1)) a.avec = 0;      // a frame not aligned to four samples: element loads for all
         a.a[i] = out[i];
         a.b[i] = gt[i];
     }
+    a.afmt = out_fmt; a.ahwc = ahwc;
+    a.bkind = gt_fmt == REFVSR_RESULT_F32 ? SC_GT_F32 : gt_layout == REFVSR_INGEST_PLANAR ? SC_GT_U8_PLANAR : SC_GT_U8_HWC;
+    return 0;
+}
+
+// the two entry points' launches; `who` names the caller in the messages, down = 1 | 2 | 4
+static int sc_run(const char* who, const void* const* out, int out_fmt, const void* const* gt, int gt_fmt, int gt_layout, int nframes, int h, int w,
+                  int down, int win, void* workspace, size_t workspace_bytes, double* scores, void* stream) {
+    ScoreArgs a;
+    auto own_checks = [&]() {
+        RV_CHECK(win == 7 || win == 0, "%s: win must be 7, or 0 for the mse alone", who);
+        return 0;
+    };
+    if (int rc = sc_frames(who, "scores", a, out, out_fmt, gt, gt_fmt, gt_layout, nframes, h, w, own_checks, workspace, workspace_bytes,
+                           refvsr_score_workspace_bytes(nframes, h, w), scores))
+        return rc;
+    a.avec = down == 4 && !a.ahwc;                               // (an interleaved tap row is not one aligned group of four)
+    const uintptr_t quad = a.afmt == REFVSR_RESULT_F32 ? 15 : a.afmt == REFVSR_RESULT_F16 ? 7 : 3;
+    for (int i = 0; i < nframes; ++i)
+        if ((uintptr_t)out[i] & quad) a.avec = 0;                // a frame not aligned to four samples: element loads for all
     a.part = (double*)workspace;
     a.h = h; a.w = w;
     a.ntx = sc_tiles(w, SC_TW); a.nty = sc_tiles(h, SC_TH);
-    a.afmt = out_fmt; a.ahwc = ahwc;
-    a.bkind = gt_fmt == REFVSR_RESULT_F32 ? SC_GT_F32 : gt_layout == REFVSR_INGEST_PLANAR ? SC_GT_U8_PLANAR : SC_GT_U8_HWC;
     a.win = win;
     const int nt = a.ntx * a.nty;
     const dim3 grid(nt, 3, nframes);
@@ -545,44 +563,23 @@ extern "C" size_t refvsr_score_regions_workspace_bytes(int nframes, int h, int w
 extern "C" int refvsr_score_regions(const void* const* out, int out_fmt, const void* const* gt, int gt_fmt, int gt_layout, int nframes,
                                     int h, int w, const int* rects, int nrects, void* workspace, size_t workspace_bytes, double* sums,
                                     void* stream) {
-    RV_CHECK(out && gt, "score_regions: null frame table");
-    RV_CHECK(nframes >= 1 && nframes <= REFVSR_SCORE_MAX_FRAMES, "score_regions: 1..%d frames per launch", REFVSR_SCORE_MAX_FRAMES);
-    RV_CHECK(sc_geometry_ok(h, w), "score_regions: h, w must be at least 7 (the SSIM window) and h * w at most 2^29");
-    RV_CHECK(nrects >= 1 && nrects <= REFVSR_SCORE_MAX_RECTS, "score_regions: 1..%d rectangles", REFVSR_SCORE_MAX_RECTS);
-    RV_CHECK(rects, "score_regions: null rectangle table");
-    for (int r = 0; r < nrects; ++r) {
-        const int* q = rects + 4 * r;
-        RV_CHECK(q[0] < q[1] && q[2] < q[3], "score_regions: rectangle %d is empty", r);
-        RV_CHECK(q[0] >= 0 && q[1] <= h && q[2] >= 0 && q[3] <= w, "score_regions: rectangle %d leaves the frame", r);
-    }
-    RV_CHECK(rv_result_fmt_ok(out_fmt), "score_regions: unknown result format %d (REFVSR_RESULT_F32 | _F16 | _U8, optionally | REFVSR_RESULT_HWC)", out_fmt);
-    const int ahwc = (out_fmt & REFVSR_RESULT_HWC) != 0;
-    out_fmt &= REFVSR_RESULT_FMT_MASK;
-    RV_CHECK(gt_fmt == REFVSR_RESULT_F32 || gt_fmt == REFVSR_RESULT_U8, "score_regions: ground-truth format must be REFVSR_RESULT_F32 | _U8");
-    RV_CHECK(gt_layout == REFVSR_INGEST_PLANAR || gt_layout == REFVSR_INGEST_HWC,
-             "score_regions: ground-truth layout must be REFVSR_INGEST_PLANAR | REFVSR_INGEST_HWC");
-    RV_CHECK(!(gt_fmt == REFVSR_RESULT_F32 && gt_layout == REFVSR_INGEST_HWC), "score_regions: the interleaved layout is for uint8 ground truth");
-    RV_CHECK(workspace && sums, "score_regions: null workspace / sums");
-    RV_CHECK(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)sums & 15) == 0, "score_regions: workspace and sums must be 16-byte aligned");
-    RV_CHECK(workspace_bytes >= refvsr_score_regions_workspace_bytes(nframes, h, w, nrects),
-             "score_regions: workspace too small (%zu bytes, %zu needed)", workspace_bytes,
-             refvsr_score_regions_workspace_bytes(nframes, h, w, nrects));
-    RegionArgs a;
-    memset(&a, 0, sizeof(a));                                    // (rectangles past nrects: empty, met by no tile)
-    const uintptr_t amask = out_fmt == REFVSR_RESULT_F32 ? 3 : out_fmt == REFVSR_RESULT_F16 ? 1 : 0;
-    const uintptr_t bmask = gt_fmt == REFVSR_RESULT_F32 ? 3 : 0;
-    for (int i = 0; i < nframes; ++i) {
-        RV_CHECK(out[i] && gt[i], "score_regions: null pointer (frame %d)", i);
-        RV_CHECK(((uintptr_t)out[i] & amask) == 0 && ((uintptr_t)gt[i] & bmask) == 0,
-                 "score_regions: fp32 frames must be 4-byte, fp16 frames 2-byte aligned (frame %d)", i);
-        a.a[i] = out[i];
-        a.b[i] = gt[i];
-    }
+    RegionArgs a;                                                // (sc_frames zeroes it: rectangles past nrects are empty, met by no tile)
+    auto own_checks = [&]() {
+        RV_CHECK(nrects >= 1 && nrects <= REFVSR_SCORE_MAX_RECTS, "score_regions: 1..%d rectangles", REFVSR_SCORE_MAX_RECTS);
+        RV_CHECK(rects, "score_regions: null rectangle table");
+        for (int r = 0; r < nrects; ++r) {
+            const int* q = rects + 4 * r;
+            RV_CHECK(q[0] < q[1] && q[2] < q[3], "score_regions: rectangle %d is empty", r);
+            RV_CHECK(q[0] >= 0 && q[1] <= h && q[2] >= 0 && q[3] <= w, "score_regions: rectangle %d leaves the frame", r);
+        }
+        return 0;
+    };
+    if (int rc = sc_frames("score_regions", "sums", a, out, out_fmt, gt, gt_fmt, gt_layout, nframes, h, w, own_checks, workspace, workspace_bytes,
+                           refvsr_score_regions_workspace_bytes(nframes, h, w, nrects), sums))
+        return rc;
     a.part = (double*)workspace;
     a.h = h; a.w = w;
     a.ntx = rg_tiles(w, SC_TW); a.nty = rg_tiles(h, SC_TH);
-    a.afmt = out_fmt; a.ahwc = ahwc;
-    a.bkind = gt_fmt == REFVSR_RESULT_F32 ? SC_GT_F32 : gt_layout == REFVSR_INGEST_PLANAR ? SC_GT_U8_PLANAR : SC_GT_U8_HWC;
     a.nrects = nrects;
     for (int r = 0; r < nrects; ++r)
         for (int k = 0; k < 4; ++k) a.rect[r][k] = rects[4 * r + k];
