@@ -116,6 +116,12 @@ int refvsr_conv_mfma(const RefvsrConv* d, void* stream);
 /* Tuning / test knob (no reference counterpart): upper bound on the workgroups one single-chunk conv launches; each
  * workgroup walks the remaining pixel tiles.  0 = automatic (occupancy x CUs).  Results do not depend on it. */
 int refvsr_set_conv_workgroup_cap(int cap);
+/* Test query (added symbol, ABI 15 unchanged; no reference counterpart): which conv_mfma_kernel instantiation refvsr_conv_mfma
+ * would launch for `d` under this process's REFVSR_CONV_* knobs, as the packed key of refvsr_amd/csrc/conv_plan.h
+ * (conv_variant_key: MT | TILES << 2 | NW << 6 | EPI << 11 | F32 << 12 | GATHER << 13 | RESIDENT << 14 | HI1 << 15).  The same
+ * plan function and the same knob object as the launcher.  Host only: no launch, no device call.  A descriptor the launcher
+ * rejects is rejected here with the same message (returns 1). */
+int refvsr_conv_variant(const RefvsrConv* d, int* key);
 /* Packing contract of `wpack` (host-side helpers, no GPU needed): K-slot of K-block (ty, tx, cg) of a ks x ks conv over
  * ncg 16-byte channel groups, and the number of 4-slot K-steps; refvsr_amd/packing.py:kslot/ksteps are the same closed
  * forms and tests/test_capi.py pins the two against each other.  Return the value (>= 0), not a status. */

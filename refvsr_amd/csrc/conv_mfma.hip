@@ -755,10 +755,24 @@ static ConvArgs conv_args(const RefvsrConv* d, const ConvPlan& p) {
     return a;
 }
 
-extern "C" int refvsr_conv_mfma(const RefvsrConv* d, void* stream) {
-    static const ConvKnobs knobs = conv_knobs_from_env();          // A/B knobs, read once
+// the A/B knobs of this process, read once: the launcher and the query below plan with the same object
+static const ConvKnobs& conv_knobs() {
+    static const ConvKnobs knobs = conv_knobs_from_env();
+    return knobs;
+}
+
+// host only: no launch, no refvsr_init, no HIP call
+extern "C" int refvsr_conv_variant(const RefvsrConv* d, int* key) {
+    RV_CHECK(key != nullptr, "conv_variant: null key");
     ConvPlan p;
-    if (int rc = conv_plan(d, knobs, &p)) return rc;
+    if (int rc = conv_plan(d, conv_knobs(), &p)) return rc;
+    *key = p.key();
+    return 0;
+}
+
+extern "C" int refvsr_conv_mfma(const RefvsrConv* d, void* stream) {
+    ConvPlan p;
+    if (int rc = conv_plan(d, conv_knobs(), &p)) return rc;
     RV_CHECK(refvsr_init() == 0, "init failed");
     ConvArgs a = conv_args(d, p);
     switch (p.key()) {                                             // key and launcher of a case: the same entry of RV_CONV_VARIANTS (conv_plan.h)

@@ -61,6 +61,7 @@ SIGNATURES = {
     'refvsr_stream_destroy': [_P],
     'refvsr_conv_mfma': [C.POINTER(RefvsrConv), _P],
     'refvsr_set_conv_workgroup_cap': [_I],
+    'refvsr_conv_variant': [C.POINTER(RefvsrConv), C.POINTER(C.c_int)],      # the planned kernel variant's key (added symbol, ABI 15 unchanged)
     'refvsr_kslot': [_I, _I, _I, _I, _I],        # returns the slot, not a status
     'refvsr_ksteps': [_I, _I],                   # returns the K-step count
     'refvsr_set_probe': [_P, _I],

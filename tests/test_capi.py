@@ -120,6 +120,30 @@ def test_argument_validation_precedes_device_work(libpath):
     expect(h.refvsr_buffers_equal(flags, flags, 1, 24, q, None), 'multiple of 16 bytes')
 
 
+def test_conv_variant_query_is_the_launchers_plan(libpath):
+    """refvsr_conv_variant (added symbol, ABI 15 unchanged): host only -- it answers here, where no device exists -- with the packed
+    key of the planned conv_mfma_kernel instantiation, and rejects what refvsr_conv_mfma rejects, with the same message."""
+    from refvsr_amd import hip
+    h = hip.lib()
+    buf = (ctypes.c_char * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    key = ctypes.c_int(-1)
+    assert h.refvsr_conv_variant(None, ctypes.byref(key)) != 0 and b'null descriptor' in h.refvsr_last_error()
+    d = hip.RefvsrConv()
+    d.src0, d.c0, d.h_in, d.w_in, d.h_out, d.w_out = p, 24, 19, 45, 19, 45
+    d.ksize, d.stride, d.pad, d.wpack, d.bias, d.out = 3, 1, 1, p, p, p
+    d.cout, d.mt_per_block, d.ksteps, d.out_c, d.act_slope, d.post_slope = 24, 2, h.refvsr_ksteps(3, 3), 24, 1.0, 1.0
+    assert h.refvsr_conv_variant(ctypes.byref(d), None) != 0 and b'null key' in h.refvsr_last_error()
+    if not [k for k in os.environ if k.startswith('REFVSR_CONV_')]:
+        assert h.refvsr_conv_variant(ctypes.byref(d), ctypes.byref(key)) == 0
+        # MT | TILES << 2 | NW << 6 | EPI << 11 | F32 << 12 | GATHER << 13 | RESIDENT << 14 | HI1 << 15: resident, lean, 8 waves, 2 tiles
+        assert key.value == (2 | 2 << 2 | 8 << 6 | 1 << 11 | 1 << 14), key.value
+    d.ksteps += 1
+    key.value = -1
+    assert h.refvsr_conv_variant(ctypes.byref(d), ctypes.byref(key)) != 0 and b'ksteps mismatch' in h.refvsr_last_error() and key.value == -1
+    assert h.refvsr_conv_mfma(ctypes.byref(d), None) != 0 and b'ksteps mismatch' in h.refvsr_last_error()
+
+
 def test_multimap_entry_points_validate_before_device_work(libpath):
     """The ABI 11 entry points (host arrays of per-map device pointers): batch bounds, null table entries, shape support and aliasing are
     rejected with a message before anything touches the device."""

@@ -1,7 +1,8 @@
 """The launch plan of the generic MFMA convolution (refvsr_amd/csrc/conv_plan.h), pinned on the CPU.
 
 Which conv_mfma_kernel instantiation a descriptor runs, and with which LDS carve, decides speed and nothing else: every variant
-computes the same numbers, so no parity test sees a slipped threshold.  tools/conv_plan_dump (plain C++, no HIP) prints the plan of
+computes the same numbers (tests/test_gpu_conv_variants.py runs all 56 bit for bit against one float64 reference), so no parity test
+sees a slipped threshold.  tools/conv_plan_dump (plain C++, no HIP) prints the plan of
 every descriptor row of tests/golden/conv_plan_cases.txt; tests/golden/conv_plan_expected.txt holds the plans the launcher chose
 before the plan was a function of its own (recorded from that launcher's code, not from conv_plan.h)."""
 import os
