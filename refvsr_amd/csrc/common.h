@@ -310,6 +310,16 @@ static inline bool rv_result_fmt_ok(const int fmt) {
     return fmt >= 0 && (fmt & ~(REFVSR_RESULT_FMT_MASK | REFVSR_RESULT_HWC)) == 0 && (fmt & REFVSR_RESULT_FMT_MASK) <= REFVSR_RESULT_U8;
 }
 
+// lane l: a[l] + a[l ^ 32]   (v_mov, v_permlane32_swap, v_add per register): the fold of an accumulator whose lanes 32-63 hold the
+// lo sums (resblock24.hip, conv24.hip).  The two results are taken out of the builtin's vector as plain unsigned values first:
+// __builtin_bit_cast on `pr[1]` directly made hipcc (ROCm 7.2) read element 0 twice.
+__device__ __forceinline__ float rv_fold1(const float a) {
+    const unsigned u = __float_as_uint(a);
+    const auto pr = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    const unsigned x0 = pr[0], x1 = pr[1];
+    return __uint_as_float(x0) + __uint_as_float(x1);
+}
+
 // MFMA column n (= lane & 15) -> pixel of the 16-pixel tile: the lanes a ds_read_b128 group takes from one K-block
 // ({0-3, 12-15} | {4-11}) land on the even | odd pixels.
 __device__ __forceinline__ int rv_pix16(int n) { return (n < 4 || n >= 12) ? ((n & 7) << 1) : (((n - 4) << 1) | 1); }

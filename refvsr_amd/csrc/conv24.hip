@@ -35,8 +35,7 @@
 //   NCG 2: u = {0,4,1,3} per row, then u = 6 | 7 of rows 0,1, then of row 2                                  (5 steps)
 //   NCG 6: one step per tap with cg = {0,2,1,3}; cg 4,5 of taps (tx 0, tx 1) per row; of tx 2 for rows 0,1; for row 2   (14 steps)
 #include "common.h"
-#include "conv24_plan.h"
-#include <stdlib.h>
+#include "fixed_plan.h"
 
 struct C24Args {
     const unsigned char* src0; const unsigned char* src1; unsigned char* out;
@@ -62,18 +61,6 @@ struct C24Args {
     const float* bconf_a[REFVSR_MAX_MAPS]; const float* bconf_b[REFVSR_MAX_MAPS]; float* bconf_max[REFVSR_MAX_MAPS];
 };
 
-// Fragments per K-step.  Weight format WF = 0: hi + lo (COUT = 24: [hi 0-15] [lo 0-15] [hi 16-23 | lo 16-23]; 32 | 48: [hi | lo] per
-// 16 channels; 3: rows 0-2 hi, rows 8-10 lo).  WF = 1 (ABI 15, config.weight_precision = 'fp16'): plain fp16 weights, one fragment
-// per 16 output channels -- 24: [rows 0-15] [rows 16-23 + 8 zero rows]; 32 | 48: [rows 16 m ..] -- no lo term, no fold.
-constexpr int c24_nf(int cout, int wf) { return wf ? (cout == 24 ? 2 : cout / 16) : cout == 24 ? 3 : cout == 3 ? 1 : cout / 8; }
-
-__device__ __forceinline__ float c24_fold1(const float a) {       // lane l: a[l] + a[l ^ 32] (see resblock24.hip:rb_fold1)
-    const unsigned u = __float_as_uint(a);
-    const auto pr = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    const unsigned x0 = pr[0], x1 = pr[1];
-    return __uint_as_float(x0) + __uint_as_float(x1);
-}
-
 // COUT = 24 | 48 output channels; TH = 8 | 16 tile rows; NWV waves walk the TH x 32 tile, T = 2 TH / NWV pixel groups per wave;
 // WPS = waves per SIMD the kernel is built for (register budget).
 // CONF = 1 | 2 (16 -> COUT convs of the confidence fusions, RefVSR.py:47-52,130,141-142,107-109): the kernel's 16-channel
@@ -87,7 +74,7 @@ __device__ __forceinline__ float c24_fold1(const float a) {       // lane l: a[l
 // plan, 70 KB tile: one sixteen-wave workgroup per CU) and stores them into the 48-channel maps at byte offset 48 z.
 // MM = 1 (ABI 11): multi-map launch -- p.batch maps behind one weight fill (the batched entry points; the single-map instantiations
 // are untouched by it).
-// WF: weight format (c24_nf); WF = 1 issues the hi MFMAs of WF = 0 in the same order on the same accumulators and drops the lo ones
+// WF: weight format (fixed_plan.h:c24_nf); WF = 1 issues the hi MFMAs of WF = 0 in the same order on the same accumulators and drops the lo ones
 // (which add exact zeros for fp16-representable weights): bit-identical results on such weights.
 template <int COUT, int NCG0, int NCG1, int NWV, int TH, int WPS, int SHUF = 0, int CONF = 0, int HALF = 0, int MM = 0, int WF = 0>
 __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(WPS, WPS))) void conv24_kernel(C24Args p) {
@@ -462,7 +449,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(WPS, W
 #pragma unroll
             for (int t = 0; t < T; ++t) {
                 const f32x4 y = acc[0][t];
-                const float s0 = c24_fold1(y[0]), s1 = c24_fold1(y[1]), s2 = c24_fold1(y[2]);
+                const float s0 = rv_fold1(y[0]), s1 = rv_fold1(y[1]), s2 = rv_fold1(y[2]);
                 const int srcl = lane & 15;
                 const float v0 = __shfl(s0, srcl), v1 = __shfl(s1, srcl), v2 = __shfl(s2, srcl);
                 const float v = q == 0 ? v0 : q == 1 ? v1 : v2;
@@ -510,7 +497,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(WPS, W
                 for (int m = 0; m < NM; ++m) {
                     f32x4 y = acc[m][t];
                     if constexpr (COUT == 24) {
-                        if (WF == 0 && m == 1) y = (f32x4){c24_fold1(y[0]), c24_fold1(y[1]), c24_fold1(y[2]), c24_fold1(y[3])};
+                        if (WF == 0 && m == 1) y = (f32x4){rv_fold1(y[0]), rv_fold1(y[1]), rv_fold1(y[2]), rv_fold1(y[3])};
                     } else {
                         const unsigned eo = (unsigned)(RW(t) * rowb_o) + oo + CG(t) * 16 * OPX;
                         if (p.mul && okt[t]) mv[m][t] = *reinterpret_cast<const f16x4*>(mulp + oorg + eo + 32 * m);
@@ -543,77 +530,56 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(WPS, W
 #undef CG
 }
 
-template <int COUT, int NCG0, int NCG1, int NWV, int TH, int WPS, int SHUF = 0, int CONF = 0, int HALF = 0, int MM = 0, int WF = 0>
-static int launch_c24(C24Args& a, hipStream_t st) {
-    constexpr int NZ = HALF ? 2 : SHUF == 0 ? 1 : SHUF == 24 ? 2 : 4;   // row groups of the pixel-shuffle / channel-half variants (blockIdx.y)
-    constexpr int NCG = NCG0 + NCG1, PS = NCG | 1;
-    constexpr int LDS = c24_steps(NCG) * c24_nf(COUT, WF) * 1024 + (COUT == 48 ? 256 : 128) + (TH + 2) * C24_XW * PS * 16 +
-                        (CONF ? 2 * (TH + 4) * (C24_XW + 2) * 4 + 18 * 16 * 4 + 64 : 0);
+template <int COUT, int NCG0, int NCG1, int NWV, int TH, int WPS, int SHUF, int CONF, int HALF, int MM, int WF>
+static int launch_c24(C24Args& a, const C24Plan& p, hipStream_t st) {
+    constexpr int NZ = c24_nz(SHUF, HALF), LDS = c24_lds(COUT, NCG0 + NCG1, TH, CONF, WF);
     static_assert(LDS <= 160 * 1024, "LDS budget");
-    static bool attr_done[RV_MAX_DEVICES] = {};
-    static int occ_dev[RV_MAX_DEVICES] = {};
-    const int dev = rv_device();
-    if (!attr_done[dev]) {
-        RV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv24_kernel<COUT, NCG0, NCG1, NWV, TH, WPS, SHUF, CONF, HALF, MM, WF>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        int occ = 0;
-        RV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv24_kernel<COUT, NCG0, NCG1, NWV, TH, WPS, SHUF, CONF, HALF, MM, WF>, NWV * 64, LDS));
-        occ_dev[dev] = occ < 1 ? 1 : occ;
-        attr_done[dev] = true;
-    }
-    a.tiles_x = rv_cdiv(a.w, C24_TW);
-    a.tpm = a.tiles_x * rv_cdiv(a.h, TH);
-    a.n_tiles = a.tpm * (MM ? a.batch : 1);
-    int cap = (rv_stream_cus(st) * occ_dev[dev] / NZ) & ~7;
-    if (cap < 8) cap = 8;
+    static RvLaunchCap lc = {};
+    int cap;
+    if (int rc = rv_launch_cap(lc, &conv24_kernel<COUT, NCG0, NCG1, NWV, TH, WPS, SHUF, CONF, HALF, MM, WF>, NWV * 64, LDS, LDS, st, &cap, NZ)) return rc;
+    a.tiles_x = p.tiles_x; a.tpm = p.tpm; a.n_tiles = p.n_tiles;
     a.grid = a.n_tiles < cap ? a.n_tiles : cap;
     hipLaunchKernelGGL((conv24_kernel<COUT, NCG0, NCG1, NWV, TH, WPS, SHUF, CONF, HALF, MM, WF>), dim3(a.grid, NZ), dim3(NWV * 64), LDS, st, a);
     RV_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int refvsr_conv24_supported(int c0, int c1) {
-    return (c0 == 24 && c1 == 0) || (c0 == 16 && c1 == 0) || (c0 == 8 && c1 == 24) || (c0 == 24 && c1 == 24);
+// the A/B knob of this process, read once
+static const C24Knobs& c24_knobs() {
+    static const C24Knobs knobs = c24_knobs_from_env();
+    return knobs;
 }
-extern "C" int refvsr_conv48_supported(int c0, int c1) {
-    return (c0 == 48 && c1 == 0) || (c0 == 16 && c1 == 0) || (c0 == 48 && c1 == 48) || (c0 == 8 && c1 == 48);
-}
-extern "C" int refvsr_conv32_supported(int c0, int c1) { return (c0 == 32 && c1 == 0) || (c0 == 8 && c1 == 0); }
 
-extern "C" int refvsr_conv24_blob_bytes(int c0, int c1) {
-    if (!refvsr_conv24_supported(c0, c1)) return -1;
-    return c24_steps((c0 + c1) / 8) * 3 * 1024 + 128;
+// the launch of a plan with its filled arguments
+static int c24_dispatch(C24Args& a, const C24Plan& p, void* stream) {
+    switch (p.key()) {                                             // key and launcher of a case: the same entry of RV_C24_VARIANTS (fixed_plan.h)
+#define RV_C24_CASE(...) case c24_variant_key(__VA_ARGS__): return launch_c24<__VA_ARGS__>(a, p, (hipStream_t)stream);
+        RV_C24_VARIANTS(RV_C24_CASE)
+#undef RV_C24_CASE
+    }
+    RV_CHECK(false, "%s", p.no_twin ? p.no_twin : "conv24: no kernel for this plan");
+    return 1;
 }
-extern "C" int refvsr_conv32_blob_bytes(int c0, int c1) {
-    if (!refvsr_conv32_supported(c0, c1)) return -1;
-    return c24_steps((c0 + c1) / 8) * 4 * 1024 + 128;
-}
+
+extern "C" int refvsr_conv24_supported(int c0, int c1) { return c24_supported(C24_CONV24, c0, c1); }
+extern "C" int refvsr_conv48_supported(int c0, int c1) { return c24_supported(C24_CONV48, c0, c1); }
+extern "C" int refvsr_conv32_supported(int c0, int c1) { return c24_supported(C24_CONV32, c0, c1); }
+extern "C" int refvsr_conv_shuffle2_supported(int c) { return c24_supported(C24_SHUFFLE2, c, 0); }
+
+// Blob sizes (fixed_plan.h:c24_blob_bytes).  48 + 48: two channel-half blobs of the 24-output layout, back to back; pixel shuffle: one
+// 48-row blob per row group.  The fp16 weight format (ABI 15, refvsr_*_f16w; packing.py:pack_conv24 / pack_conv_shuffle2 with
+// wfmt='fp16') has c24_nf(cout, 1) fragments per K-step and the same bias tail; the twins exist for the shapes the mid_channels = 24
+// family launches.
+extern "C" int refvsr_conv24_blob_bytes(int c0, int c1) { return refvsr_conv24_supported(c0, c1) ? c24_blob_bytes(24, (c0 + c1) / 8, 0) : -1; }
+extern "C" int refvsr_conv32_blob_bytes(int c0, int c1) { return refvsr_conv32_supported(c0, c1) ? c24_blob_bytes(32, (c0 + c1) / 8, 0) : -1; }
 extern "C" int refvsr_conv48_blob_bytes(int c0, int c1) {
     if (!refvsr_conv48_supported(c0, c1)) return -1;
-    if (c0 == 48 && c1 == 48) return 2 * (c24_steps(12) * 3 * 1024 + 128);   // two channel-half blobs of the 24-output layout, back to back
-    return c24_steps((c0 + c1) / 8) * 6 * 1024 + 256;
+    return c0 == 48 && c1 == 48 ? c24_nz(0, 1) * c24_blob_bytes(24, 12, 0) : c24_blob_bytes(48, (c0 + c1) / 8, 0);
 }
-
-extern "C" int refvsr_conv_shuffle2_supported(int c) { return c == 24 || c == 48; }
-extern "C" int refvsr_conv_shuffle2_blob_bytes(int c) {
-    if (!refvsr_conv_shuffle2_supported(c)) return -1;
-    return (c == 24 ? 2 : 4) * (c24_steps(c / 8) * 6 * 1024 + 256);
-}
-
-// Blob sizes of the fp16 weight format (ABI 15, refvsr_*_f16w; packing.py:pack_conv24 / pack_conv_shuffle2 with wfmt='fp16'):
-// c24_nf(cout, 1) fragments per K-step, same bias tail.  The twins exist for the shapes the mid_channels = 24 family launches.
-extern "C" int refvsr_conv24_f16w_blob_bytes(int c0, int c1) {
-    if (!refvsr_conv24_supported(c0, c1)) return -1;
-    return c24_steps((c0 + c1) / 8) * c24_nf(24, 1) * 1024 + 128;
-}
-extern "C" int refvsr_conv32_f16w_blob_bytes(int c0, int c1) {
-    if (!refvsr_conv32_supported(c0, c1)) return -1;
-    return c24_steps((c0 + c1) / 8) * c24_nf(32, 1) * 1024 + 128;
-}
-extern "C" int refvsr_conv_shuffle2_f16w_blob_bytes(int c) {
-    if (c != 24) return -1;
-    return 2 * (c24_steps(c / 8) * c24_nf(48, 1) * 1024 + 256);
-}
+extern "C" int refvsr_conv_shuffle2_blob_bytes(int c) { return refvsr_conv_shuffle2_supported(c) ? c24_nz(c, 0) * c24_blob_bytes(48, c / 8, 0) : -1; }
+extern "C" int refvsr_conv24_f16w_blob_bytes(int c0, int c1) { return refvsr_conv24_supported(c0, c1) ? c24_blob_bytes(24, (c0 + c1) / 8, 1) : -1; }
+extern "C" int refvsr_conv32_f16w_blob_bytes(int c0, int c1) { return refvsr_conv32_supported(c0, c1) ? c24_blob_bytes(32, (c0 + c1) / 8, 1) : -1; }
+extern "C" int refvsr_conv_shuffle2_f16w_blob_bytes(int c) { return c == 24 ? c24_nz(c, 0) * c24_blob_bytes(48, c / 8, 1) : -1; }
 
 extern "C" int refvsr_conv24_kblock(int ncg, int s, int q) {
     if (c24_steps(ncg) == 0 || s < 0 || s >= c24_steps(ncg) || q < 0 || q > 3) return -2;
@@ -658,87 +624,64 @@ static int c24_fill_maps(C24Args& a, const char* who, int cout, const void* cons
 // a single-map entry's optional operand as a one-entry table
 #define C24_OPT(p) ((p) ? &(p) : nullptr)
 
-// Each op below: ONE implementation <WF, MM> over per-map tables.  MM = 0: the single-map entry (its own arguments, batch = 1);
-// MM = 1: the `_batch` entry (ABI 11), `batch` maps of one geometry in ONE launch of the multi-map kernel.  WF = 1: the `_f16w` twin.
-template <int WF, int MM>
-static int c24_conv24(const void* const* src0, int c0, const void* const* src1, int c1, int batch, int h, int w, const void* blob,
+// Each op below: ONE implementation (wf, mm) over per-map tables -- plan (fixed_plan.h:c24_plan: shape support, kernel variant, tile
+// counts), argument checks and fill, c24_dispatch.  mm = 0: the single-map entry (its own arguments, batch = 1); mm = 1: the `_batch`
+// entry (ABI 11), `batch` maps of one geometry in ONE launch of the multi-map kernel.  wf = 1: the `_f16w` twin.
+static int c24_conv24(int wf, int mm, const void* const* src0, int c0, const void* const* src1, int c1, int batch, int h, int w, const void* blob,
                       float act_slope, const void* const* mul, const void* const* res, float post_slope, void* const* out, void* stream) {
-    const char* who = MM ? "conv24_batch" : "conv24";
-    RV_CHECK(refvsr_conv24_supported(c0, c1), "%s: %d + %d input channels not supported", who, c0, c1);
-    RV_CHECK(src0 && out && batch >= 1 && batch <= REFVSR_MAX_MAPS, "%s: 1..%d maps per launch", who, REFVSR_MAX_MAPS);
-    RV_CHECK(!MM || (c1 == 0) == (src1 == nullptr), "%s: src1 / c1 mismatch", who);
+    const char* who = mm ? "conv24_batch" : "conv24";
+    C24Plan p;
     C24Args a;
+    if (c24_plan(C24_CONV24, c0, c1, mm, wf, batch, h, w, c24_knobs(), &p)) return 1;
+    RV_CHECK(src0 && out, "%s: 1..%d maps per launch", who, REFVSR_MAX_MAPS);
+    RV_CHECK(!mm || (c1 == 0) == (src1 == nullptr), "%s: src1 / c1 mismatch", who);
     if (c24_fill_maps(a, who, 24, src0, src1, c1, batch, h, w, blob, act_slope, mul, res, post_slope, out)) return 1;
-    hipStream_t st = (hipStream_t)stream;
-    if (c0 == 24 && c1 == 0) return launch_c24<24, 3, 0, 8, 8, 4, 0, 0, 0, MM, WF>(a, st);
-    if (c0 == 16 && c1 == 0) return launch_c24<24, 2, 0, 8, 8, 4, 0, 0, 0, MM, WF>(a, st);
-    if (c0 == 8 && c1 == 24) return launch_c24<24, 1, 3, 8, 8, 4, 0, 0, 0, MM, WF>(a, st);
-    return launch_c24<24, 3, 3, 8, 8, 4, 0, 0, 0, MM, WF>(a, st);
+    return c24_dispatch(a, p, stream);
 }
 #define C24_CONV_ARGS const void* src0, int c0, const void* src1, int c1, int h, int w, const void* blob, float act_slope, \
                       const void* mul, const void* res, float post_slope, void* out, void* stream
 #define C24_CONV_BATCH_ARGS const void* const* src0, int c0, const void* const* src1, int c1, int batch, int h, int w, const void* blob, \
                             float act_slope, const void* const* mul, const void* const* res, float post_slope, void* const* out, void* stream
-#define C24_CONV_PASS(MM, WF) c24_conv24<WF, MM>(&src0, c0, C24_OPT(src1), c1, 1, h, w, blob, act_slope, C24_OPT(mul), C24_OPT(res), post_slope, &out, stream)
-#define C24_CONV_BATCH_PASS(WF) c24_conv24<WF, 1>(src0, c0, src1, c1, batch, h, w, blob, act_slope, mul, res, post_slope, out, stream)
-extern "C" int refvsr_conv24(C24_CONV_ARGS) { return C24_CONV_PASS(0, 0); }
-extern "C" int refvsr_conv24_f16w(C24_CONV_ARGS) { return C24_CONV_PASS(0, 1); }
+#define C24_CONV_PASS(WF) c24_conv24(WF, 0, &src0, c0, C24_OPT(src1), c1, 1, h, w, blob, act_slope, C24_OPT(mul), C24_OPT(res), post_slope, &out, stream)
+#define C24_CONV_BATCH_PASS(WF) c24_conv24(WF, 1, src0, c0, src1, c1, batch, h, w, blob, act_slope, mul, res, post_slope, out, stream)
+extern "C" int refvsr_conv24(C24_CONV_ARGS) { return C24_CONV_PASS(0); }
+extern "C" int refvsr_conv24_f16w(C24_CONV_ARGS) { return C24_CONV_PASS(1); }
 extern "C" int refvsr_conv24_batch(C24_CONV_BATCH_ARGS) { return C24_CONV_BATCH_PASS(0); }
 extern "C" int refvsr_conv24_batch_f16w(C24_CONV_BATCH_ARGS) { return C24_CONV_BATCH_PASS(1); }
 
-// 32 output channels (AlignedConv2d, RefVSR_/alignment.py:18-24,53-100: the 3 -> 32 stem and the 32 -> 32 convs of its ResBlocks)
-template <int WF>
-static int c24i_conv32(C24_CONV_ARGS) {
-    RV_CHECK(refvsr_conv32_supported(c0, c1), "conv32: %d + %d input channels not supported", c0, c1);
+// 32 output channels (AlignedConv2d, RefVSR_/alignment.py:18-24,53-100: the 3 -> 32 stem and the 32 -> 32 convs of its ResBlocks) and 48
+// (the mid_channels = 48 family; hi + lo weights only)
+static int c24_conv_single(C24Op op, const char* who, int cout, int wf, C24_CONV_ARGS) {
+    C24Plan p;
     C24Args a;
-    if (c24_fill(a, "conv32", 32, src0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out)) return 1;
-    hipStream_t st = (hipStream_t)stream;
-    if (c0 == 32) return launch_c24<32, 4, 0, 8, 8, 4, 0, 0, 0, 0, WF>(a, st);
-    return launch_c24<32, 1, 0, 8, 8, 4, 0, 0, 0, 0, WF>(a, st);
+    if (c24_plan(op, c0, c1, 0, wf, 1, h, w, c24_knobs(), &p)) return 1;
+    if (c24_fill(a, who, cout, src0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out)) return 1;
+    return c24_dispatch(a, p, stream);
 }
-extern "C" int refvsr_conv32(C24_CONV_ARGS) { return c24i_conv32<0>(src0, c0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out, stream); }
-extern "C" int refvsr_conv32_f16w(C24_CONV_ARGS) { return c24i_conv32<1>(src0, c0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out, stream); }
-
-extern "C" int refvsr_conv48(C24_CONV_ARGS) {
-    RV_CHECK(refvsr_conv48_supported(c0, c1), "conv48: %d + %d input channels not supported", c0, c1);
-    C24Args a;
-    if (c24_fill(a, "conv48", 48, src0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out)) return 1;
-    hipStream_t st = (hipStream_t)stream;
-    // 84 KB of weights + 18 x 34-pixel tile: one workgroup per CU.  Sixteen waves with two pixel groups each (default), or eight
-    // waves with four (A/B knob REFVSR_CONV48_WAVES=8: 37 % fewer LDS fragment reads, half the waves per SIMD)
-    static const bool w8 = getenv("REFVSR_CONV48_WAVES") && atoi(getenv("REFVSR_CONV48_WAVES")) == 8;
-    if (c0 == 48 && c1 == 48) return launch_c24<24, 6, 6, 16, 8, 4, 0, 0, 1>(a, st);      // two channel halves on blockIdx.y
-    // 8 + 48 -> 48: the input conv of ResidualBlocksWithInputConv on cat([lr, feat]) (RefVSR.py:340-343): NCG = 7 plan, 108 KB of
-    // weights resident next to the 38 KB tile, sixteen waves with one pixel group each
-    if (c0 == 8 && c1 == 48) return launch_c24<48, 1, 6, 16, 8, 4>(a, st);
-    if (c0 == 48) return w8 ? launch_c24<48, 6, 0, 8, 16, 2>(a, st) : launch_c24<48, 6, 0, 16, 16, 4>(a, st);
-    return launch_c24<48, 2, 0, 8, 8, 4>(a, st);
-}
+#define C24_CONV_SINGLE(OP, WHO, COUT, WF) c24_conv_single(OP, WHO, COUT, WF, src0, c0, src1, c1, h, w, blob, act_slope, mul, res, post_slope, out, stream)
+extern "C" int refvsr_conv32(C24_CONV_ARGS) { return C24_CONV_SINGLE(C24_CONV32, "conv32", 32, 0); }
+extern "C" int refvsr_conv32_f16w(C24_CONV_ARGS) { return C24_CONV_SINGLE(C24_CONV32, "conv32", 32, 1); }
+extern "C" int refvsr_conv48(C24_CONV_ARGS) { return C24_CONV_SINGLE(C24_CONV48, "conv48", 48, 0); }
 
 // act(C -> 4 C 3x3 conv + bias) through F.pixel_shuffle(2) on fp16 HWC maps: src [h][w][C] -> out [2h][2w][C].  blobs: the 2 (C = 24) or
 // 4 (C = 48) row-group blobs of refvsr_amd/packing.py:pack_conv_shuffle2, back to back.  The `_batch` entries (PixelShufflePack over
 // `batch` maps: upsample1 of the RAP steps, RefVSR.py:138) and the `_f16w` twins take C = 24 only.
-template <int WF, int MM>
-static int c24_conv_shuffle2(const void* const* src, int batch, int c, int h, int w, const void* blobs, float act_slope, void* const* out,
-                             void* stream) {
-    const char* who = MM ? "conv_shuffle2_batch" : "conv_shuffle2";
-    if (MM) RV_CHECK(c == 24, "conv_shuffle2_batch: %d channels not supported (24)", c);
-    RV_CHECK(refvsr_conv_shuffle2_supported(c), "conv_shuffle2: %d channels not supported", c);
-    RV_CHECK(src && out && batch >= 1 && batch <= REFVSR_MAX_MAPS, "%s: 1..%d maps per launch", who, REFVSR_MAX_MAPS);
+static int c24_conv_shuffle2(int wf, int mm, const void* const* src, int batch, int c, int h, int w, const void* blobs, float act_slope,
+                             void* const* out, void* stream) {
+    const char* who = mm ? "conv_shuffle2_batch" : "conv_shuffle2";
+    C24Plan p;
     C24Args a;
+    if (c24_plan(C24_SHUFFLE2, c, 0, mm, wf, batch, h, w, c24_knobs(), &p)) return 1;
+    RV_CHECK(src && out, "%s: 1..%d maps per launch", who, REFVSR_MAX_MAPS);
     if (c24_fill_maps(a, who, 4 * c, src, nullptr, 0, batch, h, w, blobs, act_slope, nullptr, nullptr, 1.0f, out)) return 1;   // (4 c: the 2h x 2w x c output map)
-    hipStream_t st = (hipStream_t)stream;
-    if (c == 24) return launch_c24<48, 3, 0, 8, 8, 4, 24, 0, 0, MM, WF>(a, st);
-    if constexpr (WF == 0 && MM == 0) return launch_c24<48, 6, 0, 16, 16, 4, 48>(a, st);
-    RV_CHECK(false, "conv_shuffle2_f16w: 24 channels only (the mid_channels = 24 family)");
-    return 1;
+    return c24_dispatch(a, p, stream);
 }
 #define C24_SHUF_ARGS const void* src, int c, int h, int w, const void* blobs, float act_slope, void* out, void* stream
 #define C24_SHUF_BATCH_ARGS const void* const* src, int batch, int c, int h, int w, const void* blobs, float act_slope, void* const* out, void* stream
-extern "C" int refvsr_conv_shuffle2(C24_SHUF_ARGS) { return c24_conv_shuffle2<0, 0>(&src, 1, c, h, w, blobs, act_slope, &out, stream); }
-extern "C" int refvsr_conv_shuffle2_f16w(C24_SHUF_ARGS) { return c24_conv_shuffle2<1, 0>(&src, 1, c, h, w, blobs, act_slope, &out, stream); }
-extern "C" int refvsr_conv_shuffle2_batch(C24_SHUF_BATCH_ARGS) { return c24_conv_shuffle2<0, 1>(src, batch, c, h, w, blobs, act_slope, out, stream); }
-extern "C" int refvsr_conv_shuffle2_batch_f16w(C24_SHUF_BATCH_ARGS) { return c24_conv_shuffle2<1, 1>(src, batch, c, h, w, blobs, act_slope, out, stream); }
+extern "C" int refvsr_conv_shuffle2(C24_SHUF_ARGS) { return c24_conv_shuffle2(0, 0, &src, 1, c, h, w, blobs, act_slope, &out, stream); }
+extern "C" int refvsr_conv_shuffle2_f16w(C24_SHUF_ARGS) { return c24_conv_shuffle2(1, 0, &src, 1, c, h, w, blobs, act_slope, &out, stream); }
+extern "C" int refvsr_conv_shuffle2_batch(C24_SHUF_BATCH_ARGS) { return c24_conv_shuffle2(0, 1, src, batch, c, h, w, blobs, act_slope, out, stream); }
+extern "C" int refvsr_conv_shuffle2_batch_f16w(C24_SHUF_BATCH_ARGS) { return c24_conv_shuffle2(1, 1, src, batch, c, h, w, blobs, act_slope, out, stream); }
 
 // The confidence fusions of AA_AF_conf_prop / compute_up in ONE launch (RefVSR.py:47-52 conf_fusion / conf_fusion2 /
 // conf_fusion_BWFW, called at :130, :141-142, :107-109):
@@ -748,19 +691,17 @@ extern "C" int refvsr_conv_shuffle2_batch_f16w(C24_SHUF_BATCH_ARGS) { return c24
 // blob of refvsr_conv24 / refvsr_conv48 (cout = 24 | 48); alpha: fp16 HWC [up h][up w][cout]; conf_max (optional, up = 1):
 // max(conf_a, conf_b) [h][w] (RefVSR.py:147).  Bit-identical to torch.cat + [refvsr_resize +] refvsr_conv_direct_f32 +
 // refvsr_conv24 / 48 [+ refvsr_max2].  The `_batch` entries (`batch` pairs of maps) and the `_f16w` twins take cout = 24 only.
-template <int WF, int MM>
-static int c24_conf_alpha(const float* const* conf_a, const float* const* conf_b, int batch, int h, int w, int up, const float* w0,
+static int c24_conf_alpha(int wf, int mm, const float* const* conf_a, const float* const* conf_b, int batch, int h, int w, int up, const float* w0,
                           const float* b0, float slope0, const void* blob, int cout, float slope1, void* const* alpha,
                           float* const* conf_max, void* stream) {
-    const char* who = MM ? "conf_alpha_batch" : "conf_alpha";
-    if (MM) RV_CHECK(conf_a && conf_b && w0 && b0 && alpha && batch >= 1 && batch <= REFVSR_MAX_MAPS, "conf_alpha_batch: bad args (1..%d maps)", REFVSR_MAX_MAPS);
+    const char* who = mm ? "conf_alpha_batch" : "conf_alpha";
+    if (mm) RV_CHECK(conf_a && conf_b && w0 && b0 && alpha, "conf_alpha_batch: bad args (1..%d maps)", REFVSR_MAX_MAPS);
     else RV_CHECK(conf_a[0] && conf_b[0] && w0 && b0 && alpha[0], "conf_alpha: null argument");
-    RV_CHECK(up == 1 || up == 2, "%s: up must be 1 or 2", who);
-    if (MM) RV_CHECK(cout == 24, "conf_alpha_batch: %d output channels not supported (24)", cout);
-    else RV_CHECK(cout == 24 || cout == 48, "conf_alpha: %d output channels not supported (24 | 48)", cout);
+    C24Plan p;
+    C24Args a;
+    if (c24_plan(C24_CONF_ALPHA, cout, up, mm, wf, batch, h, w, c24_knobs(), &p)) return 1;
     RV_CHECK(conf_max == nullptr || up == 1, "%s: the max by-product exists at up = 1 only", who);
     RV_CHECK(slope0 >= 0.f && slope0 <= 1.f, "%s: activation slopes must lie in [0, 1]", who);
-    C24Args a;
     if (c24_fill(a, who, cout, conf_a[0], nullptr, 0, up * h, up * w, blob, slope1, nullptr, nullptr, 1.0f, alpha[0])) return 1;
     a.src0 = nullptr;
     a.conf_a = conf_a[0]; a.conf_b = conf_b[0]; a.cw0 = w0; a.cb0 = b0; a.conf_max = conf_max ? conf_max[0] : nullptr; a.ch = h; a.cw = w; a.slope0 = slope0;
@@ -770,18 +711,14 @@ static int c24_conf_alpha(const float* const* conf_a, const float* const* conf_b
         a.bconf_a[b] = conf_a[b]; a.bconf_b[b] = conf_b[b]; a.bconf_max[b] = conf_max ? conf_max[b] : nullptr;
         a.bout[b] = (unsigned char*)alpha[b];
     }
-    hipStream_t st = (hipStream_t)stream;
-    if (cout == 24) return up == 1 ? launch_c24<24, 2, 0, 8, 8, 4, 0, 1, 0, MM, WF>(a, st) : launch_c24<24, 2, 0, 8, 8, 4, 0, 2, 0, MM, WF>(a, st);
-    if constexpr (WF == 0 && MM == 0) return up == 1 ? launch_c24<48, 2, 0, 8, 8, 4, 0, 1>(a, st) : launch_c24<48, 2, 0, 8, 8, 4, 0, 2>(a, st);
-    RV_CHECK(false, "conf_alpha_f16w: 24 output channels only (the mid_channels = 24 family)");
-    return 1;
+    return c24_dispatch(a, p, stream);
 }
 #define C24_CONF_ARGS const float* conf_a, const float* conf_b, int h, int w, int up, const float* w0, const float* b0, float slope0, \
                       const void* blob, int cout, float slope1, void* alpha, float* conf_max, void* stream
 #define C24_CONF_BATCH_ARGS const float* const* conf_a, const float* const* conf_b, int batch, int h, int w, int up, const float* w0, const float* b0, \
                             float slope0, const void* blob, int cout, float slope1, void* const* alpha, float* const* conf_max, void* stream
-#define C24_CONF_PASS(WF) c24_conf_alpha<WF, 0>(&conf_a, &conf_b, 1, h, w, up, w0, b0, slope0, blob, cout, slope1, &alpha, C24_OPT(conf_max), stream)
-#define C24_CONF_BATCH_PASS(WF) c24_conf_alpha<WF, 1>(conf_a, conf_b, batch, h, w, up, w0, b0, slope0, blob, cout, slope1, alpha, conf_max, stream)
+#define C24_CONF_PASS(WF) c24_conf_alpha(WF, 0, &conf_a, &conf_b, 1, h, w, up, w0, b0, slope0, blob, cout, slope1, &alpha, C24_OPT(conf_max), stream)
+#define C24_CONF_BATCH_PASS(WF) c24_conf_alpha(WF, 1, conf_a, conf_b, batch, h, w, up, w0, b0, slope0, blob, cout, slope1, alpha, conf_max, stream)
 extern "C" int refvsr_conf_alpha(C24_CONF_ARGS) { return C24_CONF_PASS(0); }
 extern "C" int refvsr_conf_alpha_f16w(C24_CONF_ARGS) { return C24_CONF_PASS(1); }
 extern "C" int refvsr_conf_alpha_batch(C24_CONF_BATCH_ARGS) { return C24_CONF_BATCH_PASS(0); }
@@ -793,8 +730,8 @@ extern "C" int refvsr_conf_alpha_batch_f16w(C24_CONF_BATCH_ARGS) { return C24_CO
 // bytes = [S K-steps x ONE fragment x 64 lanes x 8 halfs][32 bias floats]: fragment rows 0-2 = hi(W[r]), rows 8-10 = lo(W[r - 8]),
 // K-blocks by refvsr_conv24_kblock(c / 8, s, q) (refvsr_amd/packing.py:pack_conv_last).  Replaces refvsr_resize (the x4 base map)
 // + refvsr_conv_mfma's planar mode: the 3-channel base never exists in HBM, one MFMA per K-step instead of two 16-row tiles.
-extern "C" int refvsr_conv_last_supported(int c) { return c == 24 || c == 48; }
-extern "C" int refvsr_conv_last_blob_bytes(int c) { return refvsr_conv_last_supported(c) ? c24_steps(c / 8) * 1024 + 128 : -1; }
+extern "C" int refvsr_conv_last_supported(int c) { return c24_supported(C24_CONV_LAST, c, 0); }
+extern "C" int refvsr_conv_last_blob_bytes(int c) { return refvsr_conv_last_supported(c) ? c24_blob_bytes(3, c / 8, 0) : -1; }
 extern "C" int refvsr_conv_last_fmt(const void* src, int c, int h, int w, const void* blob, const float* base_lr, int bh, int bw,
                                     void* out, int out_fmt, void* stream);
 extern "C" int refvsr_conv_last(const void* src, int c, int h, int w, const void* blob, const float* base_lr, int bh, int bw,
@@ -804,12 +741,11 @@ extern "C" int refvsr_conv_last(const void* src, int c, int h, int w, const void
 extern "C" int refvsr_conv_last_fmt(const void* src, int c, int h, int w, const void* blob, const float* base_lr, int bh, int bw,
                                     void* out, int out_fmt, void* stream) {
     RV_CHECK(rv_result_fmt_ok(out_fmt), "conv_last: unknown result format %d", out_fmt);
-    RV_CHECK(refvsr_conv_last_supported(c), "conv_last: %d input channels not supported (24 | 48)", c);
-    RV_CHECK(base_lr && bh > 0 && bw > 0 && h % bh == 0 && w % bw == 0 && h / bh == w / bw, "conv_last: base frame %dx%d does not divide the output %dx%d", bh, bw, h, w);
+    C24Plan p;
     C24Args a;
+    if (c24_plan(C24_CONV_LAST, c, 0, 0, 0, 1, h, w, c24_knobs(), &p)) return 1;
+    RV_CHECK(base_lr && bh > 0 && bw > 0 && h % bh == 0 && w % bw == 0 && h / bh == w / bw, "conv_last: base frame %dx%d does not divide the output %dx%d", bh, bw, h, w);
     if (c24_fill(a, "conv_last", c, src, nullptr, 0, h, w, blob, 1.0f, nullptr, nullptr, 1.0f, out)) return 1;
     a.base_lr = base_lr; a.bh = bh; a.bw = bw; a.base_step = (float)bh / (float)h; a.out_fmt = out_fmt;
-    hipStream_t st = (hipStream_t)stream;
-    if (c == 24) return launch_c24<3, 3, 0, 8, 8, 4>(a, st);
-    return launch_c24<3, 6, 0, 8, 8, 4>(a, st);
+    return c24_dispatch(a, p, stream);
 }

@@ -33,36 +33,9 @@
 #include <type_traits>
 
 #include "common.h"
+#include "fixed_plan.h"
 
-#ifndef REFVSR_RB24_STORE_DEFAULT
-#define REFVSR_RB24_STORE_DEFAULT 1
-#endif
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-namespace {
-constexpr int RB_TW = 32;                                 // tile width; the tile height TH is a template parameter (8 | 16)
-constexpr int RB_XW = RB_TW + 4;                          // x tile: (TH + 4) x 36 pixels
-constexpr int RB_IW = RB_TW + 2;                          // intermediate: (TH + 2) x 34
-constexpr int RB_PXB = 48;                                // bytes per pixel (24 halfs)
-constexpr int RB_ROWB = RB_XW * RB_PXB;                   // 1728 bytes per tile row
-constexpr int RB_RCH = RB_ROWB / 16;                      // 108 chunks per tile row
-constexpr int rb_xbytes(int th) { return (th + 4) * RB_ROWB; }         // 20736 (TH = 8) | 34560 (TH = 16)
-constexpr int RB_S = 7, RB_NF = 3;
-constexpr int RB_WB = RB_S * RB_NF * 1024;                // 21504 bytes of fragments per conv
-constexpr int RB_BIAS = 2 * RB_WB;                        // 43008
-constexpr int RB_BLOB = RB_BIAS + 256;                    // 43264
-constexpr int RB_XT = RB_BLOB;                            // LDS offset of the x tile
-constexpr int rb_lds(int th) { return RB_XT + rb_xbytes(th); }         // 64000 -> two workgroups per CU | 77824 -> one
-static_assert(RB_BLOB == REFVSR_RESBLOCK24_BLOB_BYTES, "blob size is part of the C-ABI");
-// Weight format WF (ABI 15): 0 = hi + lo in three fragments per K-step (above); 1 = plain fp16 weights in TWO fragments per K-step,
-// [rows 0-15] [rows 16-23 + 8 zero rows] -- no lo term, no fold (config.weight_precision = 'fp16', packing.py:pack_resblock24_f16w)
-constexpr int rb_nf(int wf) { return wf ? 2 : RB_NF; }
-constexpr int rb_wb(int wf) { return RB_S * rb_nf(wf) * 1024; }      // 21504 | 14336
-constexpr int rb_bias(int wf) { return 2 * rb_wb(wf); }
-constexpr int rb_blob(int wf) { return rb_bias(wf) + 256; }          // 43264 | 28928
-constexpr int rb_lds_wf(int th, int wf) { return rb_blob(wf) + rb_xbytes(th); }   // WF = 1: 49664 (TH = 8) | 63488 (TH = 16)
-static_assert(rb_blob(1) == REFVSR_RESBLOCK24_F16W_BLOB_BYTES, "blob size is part of the C-ABI");
-}  // namespace
 
 struct RB24Args {
     const unsigned char* src; unsigned char* out; const unsigned char* blob;
@@ -79,17 +52,9 @@ struct RB24Args {
     const unsigned char* bsrc[REFVSR_MAX_MAPS]; unsigned char* bout[REFVSR_MAX_MAPS];
 };
 
-// lane l: a[l] + a[l ^ 32]   (v_mov, v_permlane32_swap, v_add per register).  The two results are taken out of the builtin's
-// vector as plain unsigned values first: __builtin_bit_cast on `pr[1]` directly made hipcc (ROCm 7.2) read element 0 twice.
-__device__ __forceinline__ float rb_fold1(const float a) {
-    const unsigned u = __float_as_uint(a);
-    const auto pr = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    const unsigned x0 = pr[0], x1 = pr[1];
-    return __uint_as_float(x0) + __uint_as_float(x1);
-}
 __device__ __forceinline__ f32x4 rb_fold_halves(const f32x4 a) {
     f32x4 r;
-    r[0] = rb_fold1(a[0]); r[1] = rb_fold1(a[1]); r[2] = rb_fold1(a[2]); r[3] = rb_fold1(a[3]);
+    r[0] = rv_fold1(a[0]); r[1] = rv_fold1(a[1]); r[2] = rv_fold1(a[2]); r[3] = rv_fold1(a[3]);
     return r;
 }
 
@@ -409,7 +374,7 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV ==
 #pragma unroll
             for (int t = 0; t < T2; ++t) {
                 const f32x4 y = c0[t];
-                const float s0 = rb_fold1(y[0]), s1 = rb_fold1(y[1]), s2 = rb_fold1(y[2]);
+                const float s0 = rv_fold1(y[0]), s1 = rv_fold1(y[1]), s2 = rv_fold1(y[2]);
                 const int srcl = lane & 15;
                 const float v0 = __shfl(s0, srcl), v1 = __shfl(s1, srcl), v2 = __shfl(s2, srcl);
                 const float v = q == 0 ? v0 : q == 1 ? v1 : v2;
@@ -481,25 +446,27 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV ==
 extern unsigned long long* g_rb_probe;             // runtime.hip: refvsr_set_probe
 extern int g_rb_probe_iter;
 
-static int g_rb24_store = REFVSR_RB24_STORE_DEFAULT;   // A/B knob (refvsr_set_resblock24_store): 0 | 1, see the kernel's STORE parameter
+// the A/B knobs of this process (fixed_plan.h:Rb24Knobs): the setters write here, the launchers plan with it.  `probe` follows
+// g_rb_probe at every launch.
+static Rb24Knobs& rb24_knobs() {
+    static Rb24Knobs knobs;
+    return knobs;
+}
 extern "C" int refvsr_set_resblock24_store(int mode) {
     if (mode < 0 || mode > 1) return 1;
-    g_rb24_store = mode;
+    rb24_knobs().store = mode;
     return 0;
 }
-static int g_rb24_waves = 0;                 // A/B knob (refvsr_set_resblock24_waves): 0 = by map size; 4 | 8: 8 x 32 tiles; 16: 16 x 32
 extern "C" int refvsr_set_resblock24_waves(int waves) {
     if (waves != 0 && waves != 4 && waves != 8 && waves != 16) return 1;
-    g_rb24_waves = waves;
+    rb24_knobs().waves = waves;
     return 0;
 }
 
-template <bool RELU, int NWV, bool PROBE = false, int TH = 8, int STORE = 0, int HEAD = 0, int WF = 0>
-static int launch_rb24(RB24Args& a, hipStream_t st) {
+template <bool RELU, int NWV, bool PROBE, int TH, int STORE, int HEAD, int WF>
+static int launch_rb24(RB24Args& a, const Rb24Plan& p, hipStream_t st) {
     constexpr int RB_LDS = rb_lds_wf(TH, WF);
-    a.tiles_x = rv_cdiv(a.w, RB_TW);
-    a.tpm = a.tiles_x * rv_cdiv(a.h, TH);
-    a.n_tiles = a.tpm * (a.batch > 1 ? a.batch : 1);
+    a.tiles_x = p.tiles_x; a.tpm = p.tpm; a.n_tiles = p.n_tiles;
     static RvLaunchCap lc = {};
     int cap;
     if (int rc = rv_launch_cap(lc, &resblock24_kernel<RELU, NWV, PROBE, TH, STORE, HEAD, WF>, NWV * 64, RB_LDS, RB_LDS, st, &cap)) return rc;
@@ -509,44 +476,42 @@ static int launch_rb24(RB24Args& a, hipStream_t st) {
     return 0;
 }
 
+// plan (fixed_plan.h:rb24_plan) and launch of one block (head = 0) or of the output head over the filled arguments
+static int rb24_launch(RB24Args& a, int head, int wf, hipStream_t st) {
+    Rb24Knobs knobs = rb24_knobs();
+    knobs.probe = g_rb_probe != nullptr;
+    Rb24Plan p;
+    if (int rc = rb24_plan(head, wf, a.act_slope == 0.f, a.h, a.w, a.batch, rv_stream_cus(st), knobs, &p)) return rc;
+    a.probe = g_rb_probe; a.probe_iter = g_rb_probe_iter;
+    switch (p.key()) {                                             // key and launcher of a case: the same entry of RV_RB24_VARIANTS (fixed_plan.h)
+#define RV_RB24_CASE(...) case rb24_variant_key(__VA_ARGS__): return launch_rb24<__VA_ARGS__>(a, p, st);
+        RV_RB24_VARIANTS(RV_RB24_CASE)
+#undef RV_RB24_CASE
+    }
+    refvsr_set_error("resblock24: no kernel for waves=%d store=%d", p.NWV, p.STORE);
+    return 1;
+}
+
 // n fused blocks x <- x + conv2(act(conv1 x)) on `batch` 24-channel fp16 HWC maps of one geometry (rv_resblock_chain, common.h); block
 // i's weights are the blob at blobs + i * blob_stride (refvsr_amd/packing.py:pack_resblock24).  Each launch runs over ALL maps (one
 // weight fill per workgroup, batch x the tiles: an LR launch of RefVSR_small is one 8 x 32 tile per workgroup -- 4 100 of its 13 000
 // cycles are the 43 KB fill -- two maps per launch are two tiles per fill).
-// WF = 1: the blobs are in the fp16 weight format (REFVSR_RESBLOCK24_F16W_BLOB_BYTES each, refvsr_resblock24_chain_f16w).
-template <int WF>
-static int rb24_chain_impl(const void* const* src, int batch, int h, int w, int n, const void* blobs, size_t blob_stride,
-                           float act_slope, void* scratch0, void* scratch1, void* const* out, void* stream) {
-    const auto launch = [=](RB24Args& a, hipStream_t st) -> int {
-        a.probe = g_rb_probe; a.probe_iter = g_rb_probe_iter;
-        // 16 x 32 tiles on sixteen waves (one workgroup per CU: half the weight fill per CU, 10 % less halo work in conv1, 17 % less
-        // tile staging) pay on maps of many tiles per workgroup -- 540 x 960: 27.3 -> 26.3 us, 1080 x 1920: 100.1 -> 95.9 us; at
-        // 270 x 480 (one tile per workgroup either way) the two shapes are equal (9.3 vs 9.4 us: the fill is latency, not bandwidth,
-        // and sixteen waves wait longer at the barriers), below that the 8 x 32 tiles fill more CUs (135 x 240: 6.2 vs 8.2 us)
-        const int nt8 = rv_cdiv(w, RB_TW) * rv_cdiv(h, 8) * batch;
-        const int waves = g_rb24_waves ? g_rb24_waves : (nt8 >= 4 * rv_stream_cus(st) ? 16 : 8);
-        if (WF == 0 && g_rb_probe && act_slope == 0.f && waves == 8) return launch_rb24<true, 8, true>(a, st);         // tools/probe_resblock24.py
-        if (WF == 0 && g_rb_probe && act_slope == 0.f && waves == 16) return launch_rb24<true, 16, true, 16>(a, st);
-        if (waves == 4) return act_slope == 0.f ? launch_rb24<true, 4, false, 8, 0, 0, WF>(a, st) : launch_rb24<false, 4, false, 8, 0, 0, WF>(a, st);
-#define RB24_PICK(R_)                                                                                                              \
-        (waves == 16 ? (g_rb24_store == 1 ? launch_rb24<R_, 16, false, 16, 1, 0, WF>(a, st) : launch_rb24<R_, 16, false, 16, 0, 0, WF>(a, st)) \
-                     : (g_rb24_store == 1 ? launch_rb24<R_, 8, false, 8, 1, 0, WF>(a, st) : launch_rb24<R_, 8, false, 8, 0, 0, WF>(a, st)))
-        return act_slope == 0.f ? RB24_PICK(true) : RB24_PICK(false);
-#undef RB24_PICK
-    };
-    return rv_resblock_chain<RB24Args>("resblock24_chain", RB_PXB, rb_blob(WF), src, batch, h, w, n, blobs, blob_stride, act_slope, scratch0,
-                                       scratch1, out, stream, launch);
+// wf = 1: the blobs are in the fp16 weight format (REFVSR_RESBLOCK24_F16W_BLOB_BYTES each, refvsr_resblock24_chain_f16w).
+static int rb24_chain(int wf, const void* const* src, int batch, int h, int w, int n, const void* blobs, size_t blob_stride,
+                      float act_slope, void* scratch0, void* scratch1, void* const* out, void* stream) {
+    return rv_resblock_chain<RB24Args>("resblock24_chain", RB_PXB, rb_blob(wf), src, batch, h, w, n, blobs, blob_stride, act_slope, scratch0,
+                                       scratch1, out, stream, [=](RB24Args& a, hipStream_t st) { return rb24_launch(a, 0, wf, st); });
 }
 
 extern "C" int refvsr_resblock24_chain(const void* src, int h, int w, int n, const void* blobs, size_t blob_stride,
                                        float act_slope, void* scratch0, void* scratch1, void* out, void* stream) {
     RV_CHECK(src && out, "resblock24_chain: bad args");
-    return rb24_chain_impl<0>(&src, 1, h, w, n, blobs, blob_stride, act_slope, scratch0, scratch1, &out, stream);
+    return rb24_chain(0, &src, 1, h, w, n, blobs, blob_stride, act_slope, scratch0, scratch1, &out, stream);
 }
 
 extern "C" int refvsr_resblock24_chain_batch(const void* const* src, int batch, int h, int w, int n, const void* blobs, size_t blob_stride,
                                              float act_slope, void* scratch0, void* scratch1, void* const* out, void* stream) {
-    return rb24_chain_impl<0>(src, batch, h, w, n, blobs, blob_stride, act_slope, scratch0, scratch1, out, stream);
+    return rb24_chain(0, src, batch, h, w, n, blobs, blob_stride, act_slope, scratch0, scratch1, out, stream);
 }
 
 // The same two entry points on fp16-format blobs (ABI 15, packing.py:pack_resblock24_f16w): two MFMAs per pixel group and K-step
@@ -555,11 +520,11 @@ extern "C" int refvsr_resblock24_f16w_blob_bytes(void) { return rb_blob(1); }
 extern "C" int refvsr_resblock24_chain_f16w(const void* src, int h, int w, int n, const void* blobs, size_t blob_stride,
                                             float act_slope, void* scratch0, void* scratch1, void* out, void* stream) {
     RV_CHECK(src && out, "resblock24_chain: bad args");
-    return rb24_chain_impl<1>(&src, 1, h, w, n, blobs, blob_stride, act_slope, scratch0, scratch1, &out, stream);
+    return rb24_chain(1, &src, 1, h, w, n, blobs, blob_stride, act_slope, scratch0, scratch1, &out, stream);
 }
 extern "C" int refvsr_resblock24_chain_batch_f16w(const void* const* src, int batch, int h, int w, int n, const void* blobs, size_t blob_stride,
                                                   float act_slope, void* scratch0, void* scratch1, void* const* out, void* stream) {
-    return rb24_chain_impl<1>(src, batch, h, w, n, blobs, blob_stride, act_slope, scratch0, scratch1, out, stream);
+    return rb24_chain(1, src, batch, h, w, n, blobs, blob_stride, act_slope, scratch0, scratch1, out, stream);
 }
 
 // The last two convs of the upsampler in ONE launch (RefVSR.py:91-92,116-118,288,297, mid_channels = 24):
@@ -589,25 +554,13 @@ extern "C" int refvsr_conv_hr_last_fmt(const void* src, int h, int w, const void
     a.h = h; a.w = w; a.act_slope = act_slope;
     a.src = (const unsigned char*)src; a.out = (unsigned char*)out; a.blob = (const unsigned char*)blob;
     a.base_lr = base_lr; a.bh = bh; a.bw = bw; a.base_step = (float)bh / (float)h; a.out_fmt = out_fmt;
-    hipStream_t st = (hipStream_t)stream;
-    const int nt8 = rv_cdiv(w, RB_TW) * rv_cdiv(h, 8);
-    const int waves = g_rb24_waves == 8 || g_rb24_waves == 16 ? g_rb24_waves : (nt8 >= 4 * rv_stream_cus(st) ? 16 : 8);
-    return waves == 16 ? launch_rb24<false, 16, false, 16, 0, 1>(a, st) : launch_rb24<false, 8, false, 8, 0, 1>(a, st);
+    return rb24_launch(a, 1, 0, (hipStream_t)stream);
 }
 
 // K-block (K-step s, quarter q) of the blob's fragment order -> (ty, tx, cg) of the 3x3 x 24-channel window, or -1 for the
-// zero block: the single source of truth for the host packer (refvsr_amd/packing.py checks itself against it).
+// zero block: the NCG = 3 plan of conv24_plan.h, the single source of truth for the host packer (refvsr_amd/packing.py checks itself
+// against it).
 extern "C" int refvsr_resblock24_kblock(int s, int q) {
     if (s < 0 || s >= RB_S || q < 0 || q > 3) return -2;
-    int ty, u;
-    if (s < 6) {
-        const int perm[4] = {0, 2, 1, 3};
-        ty = s >> 1;
-        u = 4 * (s & 1) + perm[q];
-    } else {
-        if (q == 3) return -1;
-        ty = q;
-        u = 8;
-    }
-    return (ty << 16) | ((u / 3) << 8) | (u % 3);
+    return c24_kblock(3, s, q);
 }

@@ -181,6 +181,78 @@ def test_multimap_entry_points_validate_before_device_work(libpath):
     expect(h.refvsr_warp_planar_batch(arr(at(0), P(0)), 2, 1, 8, 8, s2, 8, 8, o2, None), 'null pointer (pair 1)')
 
 
+def test_fixed_channel_entry_points_validate_before_device_work(libpath):
+    """conv32 / conv48 / conv_last / conv_hr_last: shape support comes first (fixed_plan.h:c24_plan), then the argument checks, all
+    before anything touches the device; refvsr_resblock24_kblock is the NCG = 3 K plan behind a range check."""
+    from refvsr_amd import hip
+    h = hip.lib()
+    P = ctypes.c_void_p
+    buf = (ctypes.c_char * 65536)()
+    at = lambda off: ctypes.cast(ctypes.addressof(buf) + off, P)
+
+    def expect(rc, text):
+        assert rc != 0 and h.refvsr_last_error().decode() == text, h.refvsr_last_error()
+
+    conv = lambda f, c0, src1, c1, h_, blob, act, out: f(at(0), c0, src1, c1, h_, 8, blob, act, None, None, 1.0, out, None)
+    for name, f, bad in (('conv32', h.refvsr_conv32, (24, 0)), ('conv32', h.refvsr_conv32_f16w, (32, 8)), ('conv48', h.refvsr_conv48, (24, 24))):
+        ok = (8, 0) if name == 'conv32' else (16, 0)
+        expect(conv(f, bad[0], None, bad[1], 0, None, 2.0, at(0)), '%s: %d + %d input channels not supported' % (name, bad[0], bad[1]))   # before every other check
+        expect(conv(f, ok[0], None, 0, 0, at(1024), 1.0, at(4096)), name + ': bad args')
+        expect(conv(f, ok[0], at(2048), 0, 8, at(1024), 1.0, at(4096)), name + ': src1 / c1 mismatch')
+        expect(conv(f, ok[0], None, 0, 8, at(1032), 1.0, at(4096)), name + ': blob must be 16-byte aligned')
+        expect(conv(f, ok[0], None, 0, 8, at(1024), 2.0, at(4096)), name + ': activation slopes must lie in [0, 1]')
+        expect(conv(f, ok[0], None, 0, 8, at(1024), 1.0, at(0)), name + ': in-place operation is not supported')
+        expect(conv(f, ok[0], None, 0, 1 << 24, at(1024), 1.0, at(4096)), name + ': map too large for 32-bit offsets')
+    expect(conv(h.refvsr_conv48, 8, None, 48, 8, at(1024), 1.0, at(4096)), 'conv48: src1 / c1 mismatch')
+
+    last = lambda c, h_, blob, base, bh, out, fmt: h.refvsr_conv_last_fmt(at(0), c, h_, 8, blob, base, bh, 8, out, fmt, None)
+    expect(last(16, 8, at(1024), at(2048), 8, at(4096), 7), 'conv_last: unknown result format 7')
+    expect(last(16, 8, None, None, 0, None, 0), 'conv_last: 16 input channels not supported (24 | 48)')
+    expect(last(24, 8, at(1024), at(2048), 3, at(4096), 0), 'conv_last: base frame 3x8 does not divide the output 8x8')
+    expect(last(24, 8, None, at(2048), 8, at(4096), 0), 'conv_last: bad args')
+    expect(last(48, 8, at(1032), at(2048), 8, at(4096), 0), 'conv_last: blob must be 16-byte aligned')
+    expect(last(48, 8, at(1024), at(2048), 8, at(0), 0), 'conv_last: in-place operation is not supported')
+    expect(h.refvsr_conv_last(at(0), 20, 8, 8, at(1024), at(2048), 8, 8, at(4096), None), 'conv_last: 20 input channels not supported (24 | 48)')
+
+    hr = lambda h_, blob, act, base, bh, out, fmt: h.refvsr_conv_hr_last_fmt(at(0), h_, 8, blob, act, base, bh, 8, out, fmt, None)
+    expect(hr(8, at(1024), 0.1, None, 8, at(4096), 0), 'conv_hr_last: bad args')
+    expect(hr(0, at(1024), 0.1, at(2048), 8, at(4096), 0), 'conv_hr_last: bad args')
+    expect(hr(8, at(1024), 0.1, at(2048), 8, at(4096), 3), 'conv_hr_last: unknown result format 3')
+    expect(hr(8, at(1032), 0.1, at(2048), 8, at(4096), 0), 'conv_hr_last: blob must be 16-byte aligned')
+    expect(hr(8, at(1024), 0.0, at(2048), 8, at(4096), 0), 'conv_hr_last: activation slope must lie in (0, 1]')
+    expect(hr(8, at(1024), 0.1, at(2048), 3, at(4096), 0), 'conv_hr_last: base frame 3x8 does not divide the output 8x8')
+    expect(hr(1 << 24, at(1024), 0.1, at(2048), 1 << 24, at(4096), 0), 'conv_hr_last: map too large for 32-bit offsets')
+    expect(h.refvsr_conv_hr_last(at(0), 8, 8, None, 0.1, at(2048), 8, 8, at(4096), None), 'conv_hr_last: bad args')
+
+    for s, q in ((-1, 0), (7, 0), (0, -1), (0, 4), (7, 4)):
+        assert h.refvsr_resblock24_kblock(s, q) == -2
+    assert [h.refvsr_resblock24_kblock(6, q) for q in range(4)] == [514, 66050, 131586, -1]     # u = 8 of rows 0..2, then the zero block
+    assert [h.refvsr_resblock24_kblock(s, q) for s in range(7) for q in range(4)] == [h.refvsr_conv24_kblock(3, s, q) for s in range(7) for q in range(4)]
+
+
+def test_blob_sizes_are_the_recorded_ones(libpath):
+    """Every *_blob_bytes export for every (c0, c1) of {8, 16, 20, 24, 32, 48} x {0, 8, 24, 48} (c of {8, 16, 24, 32, 48, 96}): the sizes the
+    library reported before they were expressed through fixed_plan.h:c24_blob_bytes, -1 for every other shape."""
+    from refvsr_amd import hip
+    h = hip.lib()
+    pairs = {'conv24': {(8, 24): 27776, (16, 0): 15488, (24, 0): 21632, (24, 24): 43136},
+             'conv32': {(8, 0): 12416, (32, 0): 36992},
+             'conv48': {(8, 48): 110848, (16, 0): 30976, (48, 0): 86272, (48, 48): 166144},
+             'conv24_f16w': {(8, 24): 18560, (16, 0): 10368, (24, 0): 14464, (24, 24): 28800},
+             'conv32_f16w': {(8, 0): 6272, (32, 0): 18560}}
+    for name, want in pairs.items():
+        f = getattr(h, 'refvsr_%s_blob_bytes' % name)
+        for c0 in (8, 16, 20, 24, 32, 48):
+            for c1 in (0, 8, 24, 48):
+                assert f(c0, c1) == want.get((c0, c1), -1), (name, c0, c1)
+    single = {'conv_shuffle2': {24: 86528, 48: 345088}, 'conv_shuffle2_f16w': {24: 43520}, 'conv_last': {24: 7296, 48: 14464}}
+    for name, want in single.items():
+        f = getattr(h, 'refvsr_%s_blob_bytes' % name)
+        for c in (8, 16, 24, 32, 48, 96):
+            assert f(c) == want.get(c, -1), (name, c)
+    assert h.refvsr_resblock24_f16w_blob_bytes() == 28928
+
+
 
 def test_cu_budget_argument_checks_and_constants(libpath):
     """ABI 13 / 14 host-side contracts that need no GPU: REFVSR_MAX_MAPS of the library equals the binding's copy (checked at load
