@@ -24,7 +24,7 @@ import torch
 from . import ops
 from .config import resolve_weight_precision
 from .knobs import env_flag
-from .packing import pack_conv
+from .packing import pack_conv, pack_conv_hr_last, pack_conv_last
 from .weights import VGG_MEAN, VGG_STD, round16
 
 _uid = itertools.count()
@@ -546,18 +546,22 @@ class Engine(object):
             torch.cuda.current_stream(dev).synchronize()
         return z
 
-    def _chain(self, kind, pairs, dev):
-        """The table of a run of fused blocks for one kernel family (kind: 'rb24' | 'rb48' | 'generic'), built once per run and kept
-        with the packed weights it points into."""
+    def _chain(self, make, pairs, *dev):
+        """The table of a run of fused blocks, make(pairs, *dev) (ops.ResblockChain: the generic kernel's pointer table; the ops.BlobChain
+        of the 24- or the 48-channel kernel), built once per run and kept with the packed weights it points into."""
         chains = self.W.chains
-        key = tuple(id(c1) for c1, _ in pairs)
-        if kind != 'generic':
-            key = (kind,) + key
+        key = (make,) + tuple(id(c1) for c1, _ in pairs)
         ch = chains.get(key)
         if ch is None:
-            ch = chains[key] = (ops.ResblockChain(pairs) if kind == 'generic' else
-                                (ops.Resblock24Chain if kind == 'rb24' else ops.Resblock48Chain)(pairs, dev))
+            ch = chains[key] = make(pairs, *dev)
         return ch
+
+    def _head_blob(self, key, pack, names, dev):
+        """A blob of the output head, pack(w, b, ...) of the raw weights of the convs `names`: packed once, kept with the weights."""
+        blob = self.W.chains.get(key)
+        if blob is None:
+            blob = self.W.chains[key] = pack(*[t for n in names for t in self.cw(n).raw]).to(dev).contiguous()
+        return blob
 
     def _block_chain(self, x, pairs, act):
         return self._block_chain_b([x], pairs, act)[0]
@@ -571,7 +575,7 @@ class Engine(object):
         h, w, c = xs[0].shape
         if self.fuse_resblocks and self.rb24 and c == 24 and pairs[0][0].raw is not None:
             # mid_channels = 24 (the RefVSR_small family): the compile-time-specialised kernel, one blob per block
-            ch = self._chain('rb24', pairs, xs[0].device)
+            ch = self._chain(ops.Resblock24Chain, pairs, xs[0].device)
             if self.chain_events is None:
                 return list(ops.resblock24_chain_b(ch, xs, act, stack=False))
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -587,13 +591,13 @@ class Engine(object):
             # 1080 x 1920 the two forms are equal stand-alone (396 vs 405 us: 32 tiles per workgroup, each swapping 168 KB of
             # weights, against conv48's 16 x 32 tiles on sixteen waves) and the 1080p -> 8K frame is 0.7 % slower with the fused
             # block (6.76 vs 6.81 frames/s) -> the large maps keep the two launches (profiles/r04_resblock48.txt)
-            ch = self._chain('rb48', pairs, xs[0].device)
+            ch = self._chain(ops.Resblock48Chain, pairs, xs[0].device)
             if len(xs) == 1 or self.rb48_multimap:
                 return list(ops.resblock48_chain_b(ch, xs, act, stack=False))
             return [ops.resblock48_chain(ch, x, act) for x in xs]
         if self.fuse_resblocks and self.chain_calls and ops.resblock_chain_ok(c):
             # one library call per run (same launches, same results): 156 of the ~330 launches of a frame
-            ch = self._chain('generic', pairs, None)
+            ch = self._chain(ops.ResblockChain, pairs)
             return [ops.resblock_chain(ch, x, act) for x in xs]
         out = []
         for x in xs:
@@ -914,18 +918,12 @@ class Engine(object):
             out = ops.conv(self.cw('upsample2.upsample_conv'), out, act=0.1)  # lrelu commutes with pixel_shuffle
         if self.fuse_tail and self.C == 24 and ops.conv_last_ok(24, out.shape[0], out.shape[1]):
             # conv_hr + conv_last + the bicubic base + the clamps in one launch: the HR map between the two convs stays in LDS
-            blob = self.W.chains.get('conv_hr_last_blob')
-            if blob is None:
-                from .packing import pack_conv_hr_last
-                blob = self.W.chains['conv_hr_last_blob'] = pack_conv_hr_last(*self.cw('conv_hr').raw, *self.cw('conv_last').raw).to(out.device).contiguous()
+            blob = self._head_blob('conv_hr_last_blob', pack_conv_hr_last, ('conv_hr', 'conv_last'), out.device)
             return ops.conv_hr_last(blob, out, lr_center, act=0.1, result_dtype=self.result_dtype, result_layout=self.result_layout)
         out = ops.conv(self.cw('conv_hr'), out, act=0.1)
         if self.fuse_head and ops.conv_last_ok(self.C, out.shape[0], out.shape[1]):
             # conv_last + the bicubic base + the clamps in one launch: the base map is evaluated per output value
-            blob = self.W.chains.get('conv_last_blob')
-            if blob is None:
-                from .packing import pack_conv_last
-                blob = self.W.chains['conv_last_blob'] = pack_conv_last(*self.cw('conv_last').raw).to(out.device).contiguous()
+            blob = self._head_blob('conv_last_blob', pack_conv_last, ('conv_last',), out.device)
             return ops.conv_last(blob, out, lr_center, result_dtype=self.result_dtype, result_layout=self.result_layout)
         base = ops.bicubic_scale(lr_center, self.cfg.scale, clamp01=True)
         return ops.convert_result(ops.conv(self.cw('conv_last'), out, planar_out=True, res_planar=base, clamp=(0.0, 1.0)), self.result_dtype,

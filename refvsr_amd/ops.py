@@ -11,6 +11,7 @@ import torch
 
 from . import hip
 from .knobs import env_flag
+from .packing import BlobFlags, blob_plan, pack_conv24, pack_conv_shuffle2, pack_resblock
 from .hip import (OUT_NHWC16, OUT_NHWC16_SHUFFLE2, OUT_PLANAR32, RS_BICUBIC, RS_BILINEAR,  # noqa: F401
                   RS_BILINEAR_AC, RS_NEAREST)
 
@@ -104,7 +105,7 @@ CONV24 = not env_flag('REFVSR_NO_CONV24')      # A/B knob: the generic conv kern
 class ConvWeights(object):
     """Packed weights of one conv on the device (see packing.pack_conv)."""
     __slots__ = ('wpack', 'bias', 'cout', 'ksteps', 'mt', 'ksize', 'cpads', 'shuffle', 'f32', 'hi_only', 'desc', 'odtype', 'raw', 'blob24',
-                 'wfmt', 'blob_wfmt')
+                 'wfmt', 'blob_wfmt', 'blob_kind')
 
     def __init__(self, pk, device, wfmt='hi_lo'):
         self.wpack = pk['wpack'].to(device).contiguous()
@@ -119,26 +120,19 @@ class ConvWeights(object):
         d.f32 = 2 if self.hi_only else int(self.f32)
         self.odtype = torch.float32 if self.f32 else torch.float16
         self.raw = pk.get('raw')      # (weight, bias) fp32 cpu tensors when the packer kept them (repacking for specialised kernels)
-        # 3x3 convs with 24 / 48 output channels of the supported input shapes also carry the blob of the specialised kernel
-        # (conv24.hip; the attribute keeps its first name)
-        # wfmt: the engine's weight format (Weights.wfmt; 'fp16': the packer was handed fp16-representable weights).  blob_wfmt: the
-        # format of blob24 -- 'fp16' where the shape has a refvsr_*_f16w twin (24 | 32 outputs, the C = 24 pixel-shuffle conv), which
-        # every launch of this conv then calls; other shapes keep the hi + lo layout (lo halves = 0 on such weights)
+        # the shapes of packing.blob_plan also carry the blob of their specialised kernel (conv24.hip; the attribute keeps its first
+        # name), in the format blob_wfmt, which every launch of this conv then picks its entry point by.  wfmt: the engine's weight
+        # format (Weights.wfmt)
         self.wfmt = wfmt
-        self.blob_wfmt = 'hi_lo'
-        self.blob24 = None
-        if self.raw is not None and pk.get('src_channels') is not None and CONV24 and not self.hi_only:
-            from .packing import conv24_ok, conv_shuffle2_ok, pack_conv24, pack_conv_shuffle2
-            two48 = self.cout == 48 and len(pk['src_channels']) == 2     # 48 + 48 -> 48 as two channel halves (A/B knob)
-            if (conv24_ok(tuple(self.raw[0].shape), pk['src_channels'], self.shuffle, self.f32) and not (self.cout == 32 and env_flag('REFVSR_NO_CONV32'))
-                    and not (two48 and env_flag('REFVSR_NO_CONV48X2'))):
-                if wfmt == 'fp16' and self.cout in (24, 32):
-                    self.blob_wfmt = 'fp16'
-                self.blob24 = pack_conv24(self.raw[0], self.raw[1], pk['src_channels'], wfmt=self.blob_wfmt).to(device).contiguous()
-            elif self.shuffle and conv_shuffle2_ok(tuple(self.raw[0].shape), pk['src_channels'], self.f32) and not env_flag('REFVSR_NO_CONV_SHUFFLE2'):
-                if wfmt == 'fp16' and self.raw[0].shape[1] == 24:
-                    self.blob_wfmt = 'fp16'
-                self.blob24 = pack_conv_shuffle2(self.raw[0], self.raw[1], wfmt=self.blob_wfmt).to(device).contiguous()     # refvsr_conv_shuffle2
+        self.blob_kind, self.blob_wfmt, self.blob24 = None, 'hi_lo', None
+        srcs = pk.get('src_channels')
+        if self.raw is not None and srcs is not None:
+            flags = BlobFlags(not CONV24, env_flag('REFVSR_NO_CONV32'), env_flag('REFVSR_NO_CONV48X2'), env_flag('REFVSR_NO_CONV_SHUFFLE2'))
+            self.blob_kind, self.blob_wfmt = blob_plan(tuple(self.raw[0].shape), srcs, self.shuffle, self.f32, self.hi_only, wfmt, flags)
+            if self.blob_kind == 'conv24':
+                self.blob24 = pack_conv24(*self.raw, srcs, wfmt=self.blob_wfmt).to(device).contiguous()
+            elif self.blob_kind == 'shuffle2':
+                self.blob24 = pack_conv_shuffle2(*self.raw, wfmt=self.blob_wfmt).to(device).contiguous()
 
 
 def _entry(name, f16w):
@@ -149,6 +143,41 @@ def _entry(name, f16w):
 def _c24(cw, name):
     """Entry point `name` of the conv24 family, or its _f16w twin when cw's blob is in the fp16 weight format."""
     return _entry(name, cw.blob_wfmt == 'fp16')
+
+
+_CONV_ENTRY = {24: 'conv24', 32: 'conv32', 48: 'conv48'}
+
+
+def _conv_route(cw, c0, c1, mul, res, h, w, stride, pad, planar, act, post, B=None):
+    """The library entry (its name without 'refvsr_') a conv call on h x w maps takes.  conv() (B None): 'conv_shuffle2' | 'conv24' |
+    'conv32' | 'conv48' | 'conv_mfma' (the generic kernel).  conv_b() over B >= 2 maps: 'conv_shuffle2_batch' | 'conv24_batch' |
+    'per_map' (conv() map by map).  c0, c1: the sources' channel strides (c1 None: one source); mul, res: the operand (of map 0) or
+    None; planar: a planar output or residual."""
+    miss = 'conv_mfma' if B is None else 'per_map'
+    if cw.blob24 is None or stride != 1 or pad != 1 or planar or not 0.0 <= act <= 1.0:
+        return miss
+    if B is not None and not multimap_ok(B):            # conv_b only: the multi-map kernels take 2 .. REFVSR_MAX_MAPS maps
+        return miss
+    co = cw.cout
+    if cw.shuffle:
+        # the 2^31 bound (32-bit element offsets in the specialised kernels: 8K HR maps go generic) is over cout alone here: the
+        # [2h, 2w, C] output has the bytes of h x w x 4 C, the largest map of the call
+        if c1 is not None or mul is not None or res is not None or post != 1.0 or h * w * co * 2 >= 2 ** 31:
+            return miss
+        if B is None:
+            return 'conv_shuffle2'
+        return 'conv_shuffle2_batch' if c0 == 24 else miss      # conv_b only: the multi-map kernel exists for C = 24 alone
+    if not 0.0 <= post <= 1.0:
+        return miss
+    if B is not None:
+        # conv_b only: 24 outputs alone have a multi-map kernel; the sources must match the packed ones (conv() asserts that before it
+        # asks) and be on the library's own list
+        if co != 24 or [c0] + ([] if c1 is None else [c1]) != list(cw.cpads) or not hip.lib().refvsr_conv24_supported(c0, c1 or 0):
+            return miss
+    # here the bound is over the widest map of the call, sources included (8 + 24 -> 24, 48 + 48 -> 48 ...)
+    if (mul is not None and mul.shape[2] != co) or (res is not None and res.shape[2] != co) or h * w * max(co, c0, c1 or 0) * 2 >= 2 ** 31:
+        return miss
+    return _CONV_ENTRY[co] if B is None else 'conv24_batch'
 
 
 def conv(cw, src0, src1=None, stride=1, pad=None, act=1.0, mul=None, res=None, post=1.0,
@@ -170,27 +199,23 @@ def conv(cw, src0, src1=None, stride=1, pad=None, act=1.0, mul=None, res=None, p
     assert src1 is None or src1.shape[:2] == src0.shape[:2]
     assert [c0] + ([c1] if src1 is not None else []) == list(cw.cpads), \
         'conv input channels %s do not match packed weights %s' % ([c0, c1], cw.cpads)
-    k = cw.ksize
     if pad is None:
-        pad = k // 2
-    co_ = cw.cout
-    if (cw.shuffle and cw.blob24 is not None and stride == 1 and pad == 1 and not planar_out and res_planar is None and
-            src1 is None and mul is None and res is None and 0.0 <= act <= 1.0 and post == 1.0 and h * w * co_ * 2 < 2 ** 31):
+        pad = cw.ksize // 2
+    entry = _conv_route(cw, c0, None if src1 is None else c1, mul, res, h, w, stride, pad, planar_out or res_planar is not None, act, post)
+    if entry == 'conv_shuffle2':
         # C -> 4 C conv + pixel shuffle on the compile-time-specialised kernel (csrc/conv24.hip, SHUF variant)
         out = torch.empty((2 * h, 2 * w, c0), dtype=torch.float16, device=src0.device)
-        hip.check(_c24(cw, 'refvsr_conv_shuffle2')(_ptr(src0), c0, h, w, _ptr(cw.blob24), act, _ptr(out), _stream()), 'conv_shuffle2')
+        hip.check(_c24(cw, 'refvsr_conv_shuffle2')(_ptr(src0), c0, h, w, _ptr(cw.blob24), act, _ptr(out), _stream()), entry)
         return out
-    if (cw.blob24 is not None and not cw.shuffle and stride == 1 and pad == 1 and not planar_out and res_planar is None and
-            0.0 <= act <= 1.0 and 0.0 <= post <= 1.0 and (mul is None or mul.shape[2] == co_) and (res is None or res.shape[2] == co_) and
-            h * w * max(co_, c0, c1) * 2 < 2 ** 31):         # (32-bit element offsets in the specialised kernels: 8K HR maps go generic)
+    if entry != 'conv_mfma':
         # compile-time-specialised kernel (24 | 32 | 48 output channels, 3x3): csrc/conv24.hip
         for m_ in (mul, res):
             if m_ is not None:
                 _nhwc(m_)
                 assert tuple(m_.shape[:2]) == (h, w)
-        out = torch.empty((h, w, co_), dtype=torch.float16, device=src0.device)
-        fn = _c24(cw, 'refvsr_conv%d' % co_)
-        hip.check(fn(_ptr(src0), c0, _ptr(src1), c1, h, w, _ptr(cw.blob24), act, _ptr(mul), _ptr(res), post, _ptr(out), _stream()), 'conv%d' % co_)
+        out = torch.empty((h, w, cw.cout), dtype=torch.float16, device=src0.device)
+        fn = _c24(cw, 'refvsr_' + entry)
+        hip.check(fn(_ptr(src0), c0, _ptr(src1), c1, h, w, _ptr(cw.blob24), act, _ptr(mul), _ptr(res), post, _ptr(out), _stream()), entry)
         return out
     return _conv_mfma(cw, src0, src1, None, stride, pad, act, mul, res, post, planar_out, res_planar, add_const, clamp)
 
@@ -315,47 +340,38 @@ def resblock_chain(chain, x, act, post=1.0):
     return out
 
 
-class _BlobChain(object):
-    """A run of fused blocks as one device buffer [n, stride] of per-block blobs.  pairs: [(conv1, conv2)] ConvWeights whose packer
-    kept the raw fp32 weights, or [((w1, b1), (w2, b2))] raw tensors; pack(w1, b1, w2, b2): the blob of one block, `stride` bytes."""
+class BlobChain(object):
+    """A run of fused c-channel blocks (c = 24 | 48) for refvsr_resblock<c>_chain as one device buffer [n, stride] of per-block blobs
+    (packing.pack_resblock).  pairs: [(conv1, conv2)] ConvWeights whose packer kept the raw fp32 weights, or [((w1, b1), (w2, b2))]
+    raw tensors.  wfmt (c = 24): 'hi_lo' | 'fp16' (the blobs of refvsr_resblock24_chain_f16w); None = the weight format of the
+    ConvWeights (raw tensors: 'hi_lo').  The 48-channel block has no fp16-format twin: always 'hi_lo'."""
 
-    def __init__(self, pairs, device, pack, stride):
-        blobs = []
-        for a, b in pairs:
-            (w1, b1), (w2, b2) = (a.raw if isinstance(a, ConvWeights) else a), (b.raw if isinstance(b, ConvWeights) else b)
-            blobs.append(pack(w1, b1, w2, b2))
-        self.n = len(blobs)
-        self.blobs = torch.stack(blobs, 0).to(device).contiguous()
-        self.stride = self.blobs.shape[1]
-        assert self.stride == stride and self.blobs.data_ptr() % 16 == 0
-
-
-class Resblock24Chain(_BlobChain):
-    """A run of 24-channel fused blocks for refvsr_resblock24_chain: blobs [n, 43264] (packing.pack_resblock24).
-    wfmt: 'hi_lo' | 'fp16' (blobs [n, 28928] of packing.pack_resblock24_f16w for refvsr_resblock24_chain_f16w); None = the weight
-    format of the ConvWeights (raw tensors: 'hi_lo')."""
-
-    def __init__(self, pairs, device, wfmt=None):
-        from .packing import pack_resblock24, pack_resblock24_f16w
+    def __init__(self, pairs, device, c, wfmt=None):
         pairs = list(pairs)
-        if wfmt is None:
-            fmts = set(c.wfmt if isinstance(c, ConvWeights) else 'hi_lo' for p in pairs for c in p)
+        if c != 24:
+            assert wfmt is None
+            wfmt = 'hi_lo'
+        elif wfmt is None:
+            fmts = set(x.wfmt if isinstance(x, ConvWeights) else 'hi_lo' for p in pairs for x in p)
             assert len(fmts) == 1, 'one weight format per chain: %s' % sorted(fmts)
             wfmt = fmts.pop()
-        assert wfmt in ('hi_lo', 'fp16'), wfmt
         self.wfmt = wfmt
-        if wfmt == 'fp16':
-            _BlobChain.__init__(self, pairs, device, pack_resblock24_f16w, hip.RESBLOCK24_F16W_BLOB_BYTES)
-        else:
-            _BlobChain.__init__(self, pairs, device, pack_resblock24, hip.RESBLOCK24_BLOB_BYTES)
+        self.n = len(pairs)
+        raw = lambda x: x.raw if isinstance(x, ConvWeights) else x
+        self.blobs = torch.stack([pack_resblock(c, wfmt, *raw(a), *raw(b)) for a, b in pairs], 0).to(device).contiguous()
+        self.stride = self.blobs.shape[1]
+        assert self.stride == _RB_BLOB_BYTES[c, wfmt] and self.blobs.data_ptr() % 16 == 0
 
 
-class Resblock48Chain(_BlobChain):
-    """A run of 48-channel fused blocks for refvsr_resblock48_chain: blobs [n, 172544] (packing.pack_resblock48)."""
+_RB_BLOB_BYTES = {(24, 'hi_lo'): hip.RESBLOCK24_BLOB_BYTES, (24, 'fp16'): hip.RESBLOCK24_F16W_BLOB_BYTES, (48, 'hi_lo'): hip.RESBLOCK48_BLOB_BYTES}
 
-    def __init__(self, pairs, device):
-        from .packing import pack_resblock48
-        _BlobChain.__init__(self, pairs, device, pack_resblock48, hip.RESBLOCK48_BLOB_BYTES)
+
+def Resblock24Chain(pairs, device, wfmt=None):
+    return BlobChain(pairs, device, 24, wfmt)
+
+
+def Resblock48Chain(pairs, device):
+    return BlobChain(pairs, device, 48)
 
 
 _RB24_KNOBS_SET = False
@@ -441,7 +457,7 @@ def _conf_alpha(conf_as, conf_bs, up, w0, b0, cw, slope0, slope1, want_max, B=No
     for t_ in list(a_s) + list(b_s):
         _planar(t_, 1)
         assert t_.shape == a_s[0].shape
-    assert cw.blob24 is not None and cw.cpads == [16] and cw.cout in ((24, 48) if B is None else (24,))
+    assert conf_alpha_ok(cw, B)
     assert tuple(w0.shape) == (16, 2, 3, 3) and w0.is_cuda and w0.dtype == torch.float32 and w0.is_contiguous() and b0.numel() == 16
     lead = (B,) if B else ()
     h, w = a_s[0].shape[1:]
@@ -555,8 +571,9 @@ def conv_last_ok(c, h, w):
     return bool(hip.lib().refvsr_conv_last_supported(int(c))) and h * w * c * 2 < 2 ** 31
 
 
-def conf_alpha_ok(cw):
-    return cw.blob24 is not None and cw.cpads == [16] and cw.cout in (24, 48) and not cw.shuffle
+def conf_alpha_ok(cw, B=None):
+    """cw can be the 16 -> C conv of refvsr_conf_alpha (B None: C = 24 | 48) or of refvsr_conf_alpha_batch over B maps (C = 24)."""
+    return cw.blob24 is not None and cw.cpads == [16] and cw.cout in ((24, 48) if B is None else (24,)) and not cw.shuffle
 
 
 def _pack_nhwc(x, cs, name, align, dtype):
@@ -1150,15 +1167,15 @@ def conv_b(cw, src0s, src1s=None, act=1.0, muls=None, ress=None, post=1.0, stack
                 _nhwc(t_)
                 assert tuple(t_.shape[:2]) == (h, w)
     dev = src0s[0].device
-    if (multimap_ok(B) and cw.shuffle and cw.blob24 is not None and c0 == 24 and src1s is None and muls is None and ress is None and
-            0.0 <= act <= 1.0 and post == 1.0 and h * w * cw.cout * 2 < 2 ** 31):
+    # (conv_b has no stride / pad / planar options: what conv() makes of their defaults)
+    entry = _conv_route(cw, c0, None if src1s is None else c1, None if muls is None else muls[0], None if ress is None else ress[0], h, w,
+                        1, cw.ksize // 2, False, act, post, B)
+    if entry == 'conv_shuffle2_batch':
         out = torch.empty((B, 2 * h, 2 * w, c0), dtype=torch.float16, device=dev)
         hip.check(_c24(cw, 'refvsr_conv_shuffle2_batch')(_parr(src0s), B, c0, h, w, _ptr(cw.blob24), act, _parr(list(out)), _stream()),
                   'conv_shuffle2_batch')
         return out
-    if (multimap_ok(B) and cw.blob24 is not None and not cw.shuffle and cw.cout == 24 and 0.0 <= act <= 1.0 and 0.0 <= post <= 1.0 and
-            [c0] + ([c1] if src1s is not None else []) == list(cw.cpads) and hip.lib().refvsr_conv24_supported(c0, c1) and
-            (muls is None or muls[0].shape[2] == 24) and (ress is None or ress[0].shape[2] == 24) and h * w * max(24, c0, c1) * 2 < 2 ** 31):
+    if entry == 'conv24_batch':
         out = torch.empty((B, h, w, 24), dtype=torch.float16, device=dev)
         hip.check(_c24(cw, 'refvsr_conv24_batch')(_parr(src0s), c0, _parr(src1s) if src1s is not None else None, c1, B, h, w, _ptr(cw.blob24),
                                                 act, _parr(muls) if muls is not None else None, _parr(ress) if ress is not None else None,

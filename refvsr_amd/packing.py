@@ -13,9 +13,22 @@ GEMM view: D[row][pixel] = sum_k Wk[row][k] * X[k][pixel].
 Rows are the conv output channels, except for pixel-shuffle convs where row r = sub*C + c holds
 conv channel c*4 + sub so that a lane's 4 consecutive rows are 4 consecutive channels of ONE
 output pixel (mmedit upsample.py:49-50 pixel_shuffle fused into the store).
+
+The specialised 3x3 kernels (csrc/conv24.hip, resblock24.hip, resblock48.hip) read blobs instead: one fragment filler (_fill_frags)
+over the K order c24_kblock and a table of row layouts (_ROW_LAYOUTS) builds the fragments of every one of them; blob_plan says which
+blob a conv carries.
 """
+import collections
+
 import numpy as np
 import torch
+
+from . import hip
+
+
+def _np(x):
+    """fp32 numpy array of a tensor (any device, any dtype) or of anything numpy takes."""
+    return x.detach().cpu().float().numpy() if isinstance(x, torch.Tensor) else np.asarray(x, np.float32)
 
 
 def _pad8(c):
@@ -94,8 +107,7 @@ def pack_conv(w, b, src_channels, shuffle=False, mt=None, f32=False, hi_only=Fal
     """Returns dict(wpack, bias fp32 [nz*MT*16], cout, ksteps, mt, ksize, cpads, shuffle, f32, hi_only).
     wpack: fp16 [nz,S,MT,2,64,8] (hi, lo), fp16 [nz,S,MT,1,64,8] (hi_only: plain fp16 weights, descriptor mode 2: the streamed
     kernels only -- SPyNet's 7x7 convs) or fp32 [nz,S,MT,64,4]."""
-    w = w.detach().cpu().float().numpy() if isinstance(w, torch.Tensor) else np.asarray(w, np.float32)
-    b = b.detach().cpu().float().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, np.float32)
+    w, b = _np(w), _np(b)
     cout, cin, ks, _ = w.shape
     grp = 4 if f32 else 8
     assert not (f32 and shuffle)
@@ -131,101 +143,37 @@ def pack_conv(w, b, src_channels, shuffle=False, mt=None, f32=False, hi_only=Fal
                 src_channels=list(src_channels))
 
 
-# ---- the 24-channel fused residual block (csrc/resblock24.hip) ---------------------------------------------------------
-RB24_S, RB24_NF, RB24_BLOB = 7, 3, 43264          # K-steps, fragments per K-step, bytes per block (REFVSR_RESBLOCK24_BLOB_BYTES)
-
-
+# ---- blobs of the specialised 3x3 kernels (csrc/conv24.hip, resblock24.hip, resblock48.hip) ---------------------------------------
 def rb24_kblock(s, q):
-    """K-block (K-step s, quarter q = lane >> 4) of the blob's K order -> (ty, tx, cg) of the 3x3 x 24-channel window, or None
-    for the zero block (csrc/resblock24.hip:refvsr_resblock24_kblock is the same table; tests/test_host.py pins them together).
-    The nine 16-byte slots u = 3*tx + cg of one window row are consecutive in the x tile: K-step 2*ty + a takes
-    u = 4a + {0,2,1,3}[q], K-step 6 takes u = 8 of rows ty = q."""
-    if s < 6:
-        ty, u = s >> 1, 4 * (s & 1) + (0, 2, 1, 3)[q]
-    else:
-        if q == 3:
-            return None
-        ty, u = q, 8
-    return ty, u // 3, u % 3
+    """K-block (K-step s, quarter q = lane >> 4) of the fused 24-channel block's K order -> (ty, tx, cg) of the 3x3 x 24-channel
+    window, or None for the zero block: the three-group table of c24_kblock (csrc/resblock24.hip:refvsr_resblock24_kblock makes the
+    same reduction; tests/test_host.py pins them together)."""
+    return c24_kblock(3, s, q)
+
+
+def pack_resblock(c, wfmt, w1, b1, w2, b2):
+    """One fused c-channel block (c = 24 | 48) -> uint8 blob: the fragment parts of the two convs' pack_conv24 blobs back to back,
+    then their two bias tails (32 | 64 floats each):  [conv1 fragments][conv2 fragments][b1][b2]."""
+    tail = 4 * _nbias(c)
+    blobs = []
+    for w, b in ((w1, b1), (w2, b2)):
+        assert tuple(w.shape) == (c, c, 3, 3), tuple(w.shape)
+        blobs.append(pack_conv24(w, b, [c], wfmt=wfmt))
+    return torch.cat([x[:-tail] for x in blobs] + [x[-tail:] for x in blobs])
 
 
 def pack_resblock24(w1, b1, w2, b2):
-    """One fused block -> uint8 [43264]:  [conv1 fragments][conv2 fragments][b1: 32 floats][b2: 32 floats].
-    Fragments of a conv: fp16 [7 K-steps][3][64 lanes][8]; lane l = (q = l >> 4, r = l & 15) holds the 8 input channels of
-    K-block rb24_kblock(s, q) for row r of   f = 0: hi(W[r])   f = 1: lo(W[r])   f = 2: hi(W[16 + r]) if r < 8 else lo(W[8 + r]),
-    hi = fp16(w), lo = fp16(w - hi)."""
-    out = np.zeros(RB24_BLOB, np.uint8)
-    o = 0
-    for w in (w1, w2):
-        w = w.detach().cpu().float().numpy() if isinstance(w, torch.Tensor) else np.asarray(w, np.float32)
-        assert w.shape == (24, 24, 3, 3), w.shape
-        hi = w.astype(np.float16)
-        lo = (w - hi.astype(np.float32)).astype(np.float16)
-        frag = np.zeros((RB24_S, RB24_NF, 4, 16, 8), np.float16)       # [s][f][q][r][8]
-        for s_ in range(RB24_S):
-            for q in range(4):
-                kb = rb24_kblock(s_, q)
-                if kb is None:
-                    continue
-                ty, tx, cg = kb
-                ch = slice(cg * 8, cg * 8 + 8)
-                frag[s_, 0, q] = hi[0:16, ch, ty, tx]
-                frag[s_, 1, q] = lo[0:16, ch, ty, tx]
-                frag[s_, 2, q, 0:8] = hi[16:24, ch, ty, tx]
-                frag[s_, 2, q, 8:16] = lo[16:24, ch, ty, tx]
-        raw = frag.reshape(-1).view(np.uint8)
-        out[o:o + raw.size] = raw
-        o += raw.size
-    assert o == 2 * RB24_S * RB24_NF * 1024
-    for b in (b1, b2):
-        b = b.detach().cpu().float().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, np.float32)
-        bb = np.zeros(32, np.float32)
-        bb[:24] = b
-        out[o:o + 128] = bb.view(np.uint8)
-        o += 128
-    assert o == RB24_BLOB
-    return torch.from_numpy(out)
-
-
-RB24_NF_F16W, RB24_F16W_BLOB = 2, 28928     # fp16 weight format (REFVSR_RESBLOCK24_F16W_BLOB_BYTES, ABI 15)
+    """uint8 [43264] for refvsr_resblock24_chain: fragments fp16 [7 K-steps][3][64 lanes][8] per conv (row layout 'hi_lo24')."""
+    return pack_resblock(24, 'hi_lo', w1, b1, w2, b2)
 
 
 def pack_resblock24_f16w(w1, b1, w2, b2):
-    """One fused block in the fp16 weight format -> uint8 [28928] for refvsr_resblock24_chain_f16w (config.weight_precision = 'fp16'):
-    [conv1: 7 K-steps x 2 fragments x 64 lanes x 8 halfs][conv2: same][b1: 32 floats][b2: 32 floats].  Lane l = (q, r) of K-step s
-    holds the 8 input channels of K-block rb24_kblock(s, q) for row r of   f = 0: fp16(W[r])   f = 1: fp16(W[16 + r]) if r < 8, else 0.
-    No lo halves: the kernel computes with fp16(W), bit for bit what refvsr_resblock24_chain computes on pack_resblock24(fp16(W))."""
-    out = np.zeros(RB24_F16W_BLOB, np.uint8)
-    o = 0
-    for w in (w1, w2):
-        w = w.detach().cpu().float().numpy() if isinstance(w, torch.Tensor) else np.asarray(w, np.float32)
-        assert w.shape == (24, 24, 3, 3), w.shape
-        hi = w.astype(np.float16)
-        frag = np.zeros((RB24_S, RB24_NF_F16W, 4, 16, 8), np.float16)  # [s][f][q][r][8]
-        for s_ in range(RB24_S):
-            for q in range(4):
-                kb = rb24_kblock(s_, q)
-                if kb is None:
-                    continue
-                ty, tx, cg = kb
-                ch = slice(cg * 8, cg * 8 + 8)
-                frag[s_, 0, q] = hi[0:16, ch, ty, tx]
-                frag[s_, 1, q, 0:8] = hi[16:24, ch, ty, tx]
-        raw = frag.reshape(-1).view(np.uint8)
-        out[o:o + raw.size] = raw
-        o += raw.size
-    assert o == 2 * RB24_S * RB24_NF_F16W * 1024
-    for b in (b1, b2):
-        b = b.detach().cpu().float().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, np.float32)
-        bb = np.zeros(32, np.float32)
-        bb[:24] = b
-        out[o:o + 128] = bb.view(np.uint8)
-        o += 128
-    assert o == RB24_F16W_BLOB
-    return torch.from_numpy(out)
+    """uint8 [28928] for refvsr_resblock24_chain_f16w (config.weight_precision = 'fp16'): [7 K-steps][2 fragments] per conv (row
+    layout 'fp16').  No lo halves: the kernel computes with fp16(W), bit for bit what refvsr_resblock24_chain computes on
+    pack_resblock24(fp16(W))."""
+    return pack_resblock(24, 'fp16', w1, b1, w2, b2)
 
 
-# ---- 24-output-channel 3x3 convs (csrc/conv24.hip) -----------------------------------------------------------------------
 def c24_steps(ncg):
     return {1: 3, 2: 5, 3: 7, 4: 9, 6: 14, 7: 18, 12: 27}[ncg]
 
@@ -269,46 +217,28 @@ def c24_kblock(ncg, s, q):
     raise ValueError(ncg)
 
 
-def pack_conv_hr_last(w_hr, b_hr, w_last, b_last):
-    """uint8 [43264] blob for refvsr_conv_hr_last (mid_channels = 24): the resblock24 block layout with conv1 = conv_hr (24 -> 24)
-    and conv2 = the output head conv_last (24 -> 3): its fragment slot (s, 0) holds hi(W_last) in rows 0-2 and lo(W_last) in rows
-    8-10 of K-block rb24_kblock(s, q), slots (s, 1) and (s, 2) stay zero; b1 = conv_hr's bias, b2 = [b_last, 0, ...]."""
-    w_last = w_last.detach().cpu().float().numpy() if isinstance(w_last, torch.Tensor) else np.asarray(w_last, np.float32)
-    b_last = b_last.detach().cpu().float().numpy() if isinstance(b_last, torch.Tensor) else np.asarray(b_last, np.float32)
-    assert tuple(w_last.shape) == (3, 24, 3, 3), w_last.shape
-    out = pack_resblock24(w_hr, b_hr, np.zeros((24, 24, 3, 3), np.float32), np.zeros(24, np.float32)).numpy().copy()
-    hi = w_last.astype(np.float16)
-    lo = (w_last - hi.astype(np.float32)).astype(np.float16)
-    frag = np.zeros((RB24_S, RB24_NF, 4, 16, 8), np.float16)
-    for s_ in range(RB24_S):
-        for q in range(4):
-            kb = rb24_kblock(s_, q)
-            if kb is None:
-                continue
-            ty, tx, cg = kb
-            ch = slice(cg * 8, cg * 8 + 8)
-            frag[s_, 0, q, 0:3] = hi[:, ch, ty, tx]
-            frag[s_, 0, q, 8:11] = lo[:, ch, ty, tx]
-    wb = RB24_S * RB24_NF * 1024
-    out[wb:2 * wb] = frag.reshape(-1).view(np.uint8)
-    bb = np.zeros(32, np.float32)
-    bb[:3] = b_last
-    out[2 * wb + 128:2 * wb + 256] = bb.view(np.uint8)
-    return torch.from_numpy(out)
+# Row layouts of a fragment set: cout -> [(f, r, half, c, n)]: rows c .. c + n of hi (half 0: fp16(w)) or lo (half 1: fp16(w - hi)) go
+# to rows r .. r + n of fragment f; rows nobody names stay zero.  NF = 1 + the largest f.
+_ROW_LAYOUTS = {
+    # 24 outputs, hi + lo (NF = 3): f = 0: hi(W[r])   f = 1: lo(W[r])   f = 2: hi(W[16 + r]) if r < 8 else lo(W[8 + r])
+    'hi_lo24': lambda cout: [(0, 0, 0, 0, 16), (1, 0, 1, 0, 16), (2, 0, 0, 16, 8), (2, 8, 1, 16, 8)],
+    # 16 m outputs, hi + lo (NF = cout / 8): f = 2 m: hi(W[16 m + r])   f = 2 m + 1: lo(W[16 m + r])
+    'hi_lo16': lambda cout: [(2 * m + half, 0, half, 16 * m, 16) for m in range(cout // 16) for half in (0, 1)],
+    # plain fp16 (NF = ceil(cout / 16)): f = m: fp16(W[16 m + r]), rows past the output channels zero
+    'fp16': lambda cout: [(m, 0, 0, 16 * m, min(16, cout - 16 * m)) for m in range((cout + 15) // 16)],
+    # the 3-row output head (NF = 1): rows 0-2 = hi(W[r]), rows 8-10 = lo(W[r - 8]) (the kernel folds rows r and r + 8)
+    'head': lambda cout: [(0, 0, 0, 0, 3), (0, 8, 1, 0, 3)],
+}
 
 
-def pack_conv_last(w, b):
-    """uint8 blob of the output head for refvsr_conv_last: 3x3, C -> 3 (C = 24 | 48).  [S K-steps][ONE fragment: 64 lanes x 8 halfs]
-    + 32 bias floats; lane l = (q, r) of K-step s holds the 8 input channels of K-block c24_kblock(C / 8, s, q) for fragment row r:
-    rows 0-2 = hi(W[r]) = fp16(w), rows 8-10 = lo(W[r - 8]) = fp16(w - hi), all other rows zero (the kernel folds rows r and r + 8)."""
-    w = w.detach().cpu().float().numpy() if isinstance(w, torch.Tensor) else np.asarray(w, np.float32)
-    b = b.detach().cpu().float().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, np.float32)
-    assert w.shape[0] == 3 and w.shape[1] in (24, 48) and tuple(w.shape[2:]) == (3, 3), w.shape
-    Wk, _, ncg = kmatrix(w, [w.shape[1]])                       # [3, 9 * ncg * 8]
+def _fill_frags(Wk, ncg, layout):
+    """Wk [cout, 9 * ncg * 8] (kmatrix: K-block g = tap * ncg + cg) -> fp16 [S][NF][4][16][8]: lane l = (q = l >> 4, r = l & 15) of
+    K-step s holds the 8 (padded) input channels of K-block c24_kblock(ncg, s, q) for row r of fragment f of the row layout."""
+    halves = [Wk.astype(np.float16)]
+    halves.append((Wk - halves[0].astype(np.float32)).astype(np.float16))
+    rows = _ROW_LAYOUTS[layout](Wk.shape[0])
     S = c24_steps(ncg)
-    hi = Wk.astype(np.float16)
-    lo = (Wk - hi.astype(np.float32)).astype(np.float16)
-    frag = np.zeros((S, 1, 4, 16, 8), np.float16)
+    frag = np.zeros((S, 1 + max(f for f, _, _, _, _ in rows), 4, 16, 8), np.float16)
     for s_ in range(S):
         for q in range(4):
             kb = c24_kblock(ncg, s_, q)
@@ -316,33 +246,56 @@ def pack_conv_last(w, b):
                 continue
             ty, tx, cg = kb
             g = (ty * 3 + tx) * ncg + cg
-            frag[s_, 0, q, 0:3] = hi[:, g * 8:g * 8 + 8]
-            frag[s_, 0, q, 8:11] = lo[:, g * 8:g * 8 + 8]
-    out = np.zeros(S * 1024 + 128, np.uint8)
-    raw = frag.reshape(-1).view(np.uint8)
-    out[:raw.size] = raw
-    bb = np.zeros(32, np.float32)
-    bb[:3] = b
-    out[raw.size:] = bb.view(np.uint8)
-    return torch.from_numpy(out)
+            for f, r, half, c, n in rows:
+                frag[s_, f, q, r:r + n] = halves[half][c:c + n, g * 8:g * 8 + 8]
+    return frag
 
 
-RB48_WB = 14 * 6 * 1024                       # fragment bytes of one 48 -> 48 conv (csrc/resblock48.hip)
-RB48_BLOB = 2 * RB48_WB + 512
+def _blob(frag, b, nb):
+    """uint8 blob of one conv: the fragments, then nb bias floats (b, zero-padded)."""
+    bb = np.zeros(nb, np.float32)
+    bb[:len(b)] = b
+    return torch.from_numpy(np.concatenate([frag.reshape(-1).view(np.uint8), bb.view(np.uint8)]))
+
+
+def _nbias(cout):
+    return 64 if cout == 48 else 32
+
+
+def pack_conv_hr_last(w_hr, b_hr, w_last, b_last):
+    """uint8 [43264] blob for refvsr_conv_hr_last (mid_channels = 24): the resblock24 block layout with conv1 = conv_hr (24 -> 24)
+    and conv2 = the output head conv_last (24 -> 3): pack_conv_last's one fragment per K-step in slot (s, 0), slots (s, 1) and (s, 2)
+    zero; b1 = conv_hr's bias, b2 = [b_last, 0, ...]."""
+    assert tuple(w_hr.shape) == (24, 24, 3, 3) and tuple(w_last.shape) == (3, 24, 3, 3), (tuple(w_hr.shape), tuple(w_last.shape))
+    hr, last = pack_conv24(w_hr, b_hr, [24]), pack_conv_last(w_last, b_last)
+    conv2 = torch.zeros((RB24_S, RB24_NF, 1024), dtype=torch.uint8)
+    conv2[:, 0] = last[:-128].view(RB24_S, 1024)
+    return torch.cat([hr[:-128], conv2.view(-1), hr[-128:], last[-128:]])
+
+
+def pack_conv_last(w, b):
+    """uint8 blob of the output head for refvsr_conv_last: 3x3, C -> 3 (C = 24 | 48).  [S K-steps][ONE fragment: 64 lanes x 8 halfs]
+    in the row layout 'head' + 32 bias floats."""
+    w, b = _np(w), _np(b)
+    assert w.shape[0] == 3 and w.shape[1] in (24, 48) and tuple(w.shape[2:]) == (3, 3), w.shape
+    Wk, _, ncg = kmatrix(w, [w.shape[1]])
+    return _blob(_fill_frags(Wk, ncg, 'head'), b, 32)
+
+
+# blob sizes of the fused blocks (csrc/resblock24.hip, resblock48.hip), from their K-steps, fragments per K-step and bias floats
+RB24_S, RB24_NF, RB24_NF_F16W = c24_steps(3), 3, 2          # the 24-channel block: hi + lo | fp16 weight format
+RB24_WB = RB24_S * RB24_NF * 1024                           # fragment bytes of one 24 -> 24 conv
+RB24_BLOB = 2 * (RB24_WB + 128)
+RB24_F16W_BLOB = 2 * (RB24_S * RB24_NF_F16W * 1024 + 128)
+RB48_WB = c24_steps(6) * 6 * 1024                           # fragment bytes of one 48 -> 48 conv
+RB48_BLOB = 2 * (RB48_WB + 256)
+assert (RB24_BLOB, RB24_F16W_BLOB, RB48_BLOB) == (hip.RESBLOCK24_BLOB_BYTES, hip.RESBLOCK24_F16W_BLOB_BYTES, hip.RESBLOCK48_BLOB_BYTES)
 
 
 def pack_resblock48(w1, b1, w2, b2):
-    """One fused 48-channel block -> uint8 [172544] for refvsr_resblock48_chain: the fragment parts of the two refvsr_conv48 blobs
-    (pack_conv24: [14 K-steps][6 fragments = hi | lo of output channels 0-15, 16-31, 32-47][64 lanes][8 halfs]) back to back, then
-    b1 and b2 as 64 floats each (48.. = 0)."""
-    out = np.zeros(RB48_BLOB, np.uint8)
-    for i, (w, b) in enumerate(((w1, b1), (w2, b2))):
-        assert tuple(w.shape) == (48, 48, 3, 3), tuple(w.shape)
-        blob = pack_conv24(w, b, [48]).numpy()
-        assert blob.size == RB48_WB + 256
-        out[i * RB48_WB:(i + 1) * RB48_WB] = blob[:RB48_WB]
-        out[2 * RB48_WB + i * 256:2 * RB48_WB + (i + 1) * 256] = blob[RB48_WB:]
-    return torch.from_numpy(out)
+    """uint8 [172544] for refvsr_resblock48_chain: [14 K-steps][6 fragments = hi | lo of output channels 0-15, 16-31, 32-47] per
+    conv (row layout 'hi_lo16'), b1 and b2 as 64 floats each (48.. = 0)."""
+    return pack_resblock(48, 'hi_lo', w1, b1, w2, b2)
 
 
 def conv24_ok(w_shape, src_channels, shuffle=False, f32=False, shuffle_group=False, half_group=False):
@@ -369,59 +322,43 @@ def conv_shuffle2_ok(w_shape, src_channels, f32=False):
     return ks == 3 and not f32 and list(src_channels) in ([24], [48]) and cin == src_channels[0] and cout == 4 * cin
 
 
+# The four A/B knobs of blob_plan as plain booleans (True: that family of specialised kernels is switched off)
+BlobFlags = collections.namedtuple('BlobFlags', 'no_conv24 no_conv32 no_conv48x2 no_conv_shuffle2')
+BlobFlags.__new__.__defaults__ = (False,) * 4
+
+
+def blob_plan(w_shape, src_channels, shuffle=False, f32=False, hi_only=False, wfmt='hi_lo', flags=BlobFlags()):
+    """(kind, blob_wfmt) of the specialised blob a conv carries next to its generic packing.  kind: None | 'conv24' (pack_conv24:
+    refvsr_conv24 / 32 / 48) | 'shuffle2' (pack_conv_shuffle2).  wfmt: the engine's weight format ('fp16': the packer was handed
+    fp16-representable weights); blob_wfmt: the format of the blob -- 'fp16' where the shape has a refvsr_*_f16w twin (24 | 32
+    outputs, the C = 24 pixel-shuffle conv), other shapes keep the hi + lo layout (lo halves = 0 on such weights)."""
+    cout, cin = w_shape[0], w_shape[1]
+    if flags.no_conv24 or hi_only:
+        return None, 'hi_lo'
+    two48 = cout == 48 and len(src_channels) == 2                # 48 + 48 -> 48 as two channel halves (A/B knob)
+    if (conv24_ok(w_shape, src_channels, shuffle, f32) and not (cout == 32 and flags.no_conv32) and
+            not (two48 and flags.no_conv48x2)):
+        return 'conv24', 'fp16' if wfmt == 'fp16' and cout in (24, 32) else 'hi_lo'
+    if shuffle and conv_shuffle2_ok(w_shape, src_channels, f32) and not flags.no_conv_shuffle2:
+        return 'shuffle2', 'fp16' if wfmt == 'fp16' and cin == 24 else 'hi_lo'
+    return None, 'hi_lo'
+
+
 def pack_conv24(w, b, src_channels, shuffle_group=False, half_group=False, wfmt='hi_lo'):
-    """uint8 blob of one conv for refvsr_conv24 / refvsr_conv48: fp16 [S][NF][64 lanes][8] + bias floats (32 | 64).  Lane
-    l = (q = l >> 4, r = l & 15) of K-step s holds the 8 (padded) input channels of K-block c24_kblock(ncg, s, q) for row r of
-    fragment f (hi = fp16(w), lo = fp16(w - hi)):
-      24 outputs (NF = 3): f = 0: hi(W[r])   f = 1: lo(W[r])   f = 2: hi(W[16 + r]) if r < 8 else lo(W[8 + r])
-      32 | 48 outputs (NF = 4 | 6): f = 2 m: hi(W[16 m + r])   f = 2 m + 1: lo(W[16 m + r])
-    wfmt='fp16' (the refvsr_*_f16w twins, ABI 15): plain fp16 weights, one fragment per 16 output rows, f = m: fp16(W[16 m + r]) (rows
-    past the output channels zero): NF = 2 | 2 | 3 for 24 | 32 | 48 outputs, same bias tail."""
+    """uint8 blob of one conv for refvsr_conv24 / refvsr_conv48: fp16 [S][NF][64 lanes][8] (_fill_frags) + bias floats (32 | 64), in
+    the row layout 'hi_lo24' (24 outputs) | 'hi_lo16' (32 | 48 outputs: NF = 4 | 6), or for wfmt='fp16' (the refvsr_*_f16w twins,
+    ABI 15) 'fp16': NF = 2 | 2 | 3 for 24 | 32 | 48 outputs, same bias tail."""
     assert wfmt in ('hi_lo', 'fp16'), wfmt
-    w = w.detach().cpu().float().numpy() if isinstance(w, torch.Tensor) else np.asarray(w, np.float32)
-    b = b.detach().cpu().float().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, np.float32)
+    w, b = _np(w), _np(b)
     assert conv24_ok(w.shape, src_channels, shuffle_group=shuffle_group, half_group=half_group), (w.shape, src_channels)
     cout = w.shape[0]
     if cout == 48 and [_pad8(c) for c in src_channels] == [48, 48]:
         # 48 + 48 -> 48 (refvsr_conv48's two-source form): two channel-half blobs of the 24-output layout (NCG = 12 plan), back to back
         return torch.cat([pack_conv24(w[0:24], b[0:24], src_channels, half_group=True, wfmt=wfmt),
                           pack_conv24(w[24:48], b[24:48], src_channels, half_group=True, wfmt=wfmt)])
-    Wk, _, ncg = kmatrix(w, src_channels)                       # [cout, 9 * ncg * 8], K-block g = tap * ncg + cg
-    S = c24_steps(ncg)
-    f16w = wfmt == 'fp16'
-    nf = (cout + 15) // 16 if f16w else 3 if cout == 24 else cout // 8
-    hi = Wk.astype(np.float16)
-    lo = (Wk - hi.astype(np.float32)).astype(np.float16)
-    frag = np.zeros((S, nf, 4, 16, 8), np.float16)
-    for s_ in range(S):
-        for q in range(4):
-            kb = c24_kblock(ncg, s_, q)
-            if kb is None:
-                continue
-            ty, tx, cg = kb
-            g = (ty * 3 + tx) * ncg + cg
-            cols = slice(g * 8, g * 8 + 8)
-            if f16w:
-                for m in range(nf):
-                    rows = hi[16 * m:min(16 * m + 16, cout), cols]
-                    frag[s_, m, q, 0:rows.shape[0]] = rows
-            elif cout == 24:
-                frag[s_, 0, q] = hi[0:16, cols]
-                frag[s_, 1, q] = lo[0:16, cols]
-                frag[s_, 2, q, 0:8] = hi[16:24, cols]
-                frag[s_, 2, q, 8:16] = lo[16:24, cols]
-            else:
-                for m in range(cout // 16):
-                    frag[s_, 2 * m, q] = hi[16 * m:16 * m + 16, cols]
-                    frag[s_, 2 * m + 1, q] = lo[16 * m:16 * m + 16, cols]
-    nb = 64 if cout == 48 else 32
-    out = np.zeros(S * nf * 1024 + nb * 4, np.uint8)
-    raw = frag.reshape(-1).view(np.uint8)
-    out[:raw.size] = raw
-    bb = np.zeros(nb, np.float32)
-    bb[:cout] = b
-    out[raw.size:] = bb.view(np.uint8)
-    return torch.from_numpy(out)
+    Wk, _, ncg = kmatrix(w, src_channels)
+    layout = 'fp16' if wfmt == 'fp16' else 'hi_lo24' if cout == 24 else 'hi_lo16'
+    return _blob(_fill_frags(Wk, ncg, layout), b, _nbias(cout))
 
 
 def pack_conv_shuffle2(w, b, wfmt='hi_lo'):
@@ -430,8 +367,7 @@ def pack_conv_shuffle2(w, b, wfmt='hi_lo'):
     a lane's four consecutive accumulator rows to be four consecutive channels of one sub-pixel:
       C = 24: blob z = dy, row R -> sub-pixel dx = R // 24, channel R % 24;   C = 48: blob z = 2 dy + dx, row R = channel R.
     wfmt='fp16': the blobs in pack_conv24's fp16 weight format (refvsr_conv_shuffle2_f16w, C = 24)."""
-    w = w.detach().cpu().float() if isinstance(w, torch.Tensor) else torch.from_numpy(np.asarray(w, np.float32))
-    b = b.detach().cpu().float() if isinstance(b, torch.Tensor) else torch.from_numpy(np.asarray(b, np.float32))
+    w, b = _np(w), _np(b)
     c = w.shape[1]
     assert conv_shuffle2_ok(tuple(w.shape), [c]), tuple(w.shape)
     blobs = []
