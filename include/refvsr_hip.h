@@ -526,6 +526,31 @@ size_t refvsr_conf_colormap_workspace_bytes(int n, int h, int w);
 int refvsr_colormap_table(unsigned char* out768);
 
 /* ------------------------------------------------------------------------------------------
+ * Parameter fingerprint (extension, no ABI bump: added symbols only).  Protects the packed weights against the loaders that
+ * write parameters in place: ckpt_manager.py:50-60 goes through load_state_dict, whose copy_ moves the tensors' version
+ * counters, but `p.data.copy_(w)` and `p.data = w` -- the same loader written by hand -- move none, and a host-side detector
+ * cannot see them.  refvsr_param_fingerprint reads the parameters themselves:
+ *   F = sum over all words of mix64(((uint64)g << 32) | word)  (mod 2^64)
+ *   word: the 32-bit pattern of an fp32 element (-0 and NaN payloads count); g: the element's index over the concatenated
+ *   table, in table order, < 2^32; mix64: splitmix64's finaliser, a bijection of the 64-bit words:
+ *       z ^= z >> 30; z *= 0xbf58476d1ce4e5b9; z ^= z >> 27; z *= 0x94d049bb133111eb; z ^= z >> 31.
+ *   One changed word changes F; swapped contents change F (the position term); every summation order gives the same bits.
+ *   chunks: DEVICE array of nchunks 16-byte entries { const uint32_t* base; uint32_t g0; uint32_t n; } -- n <=
+ *           REFVSR_FINGERPRINT_CHUNK_WORDS words at the 4-byte aligned address base, the first of them global index g0
+ *           (refvsr_amd/fingerprint.py:chunk_table); 16-byte aligned; 1 <= nchunks <= REFVSR_FINGERPRINT_MAX_CHUNKS.  The entries
+ *           are read by the kernel: their contents are the caller's responsibility.
+ *   workspace: device, 16-byte aligned, workspace_bytes >= refvsr_param_fingerprint_workspace_bytes(nchunks) (host only; 0 for a
+ *           chunk count that refvsr_param_fingerprint rejects); out: device, 8-byte aligned, one 64-bit word.
+ * Two launches on `stream` (one workgroup per chunk: 16-byte loads from a chunk's first aligned word on, 4-byte loads for the
+ * <= 3 words before and after; one workgroup that sums the partial sums), integer arithmetic only, plain vector stores, no
+ * atomics.  Every argument is checked before the first launch.
+ * ------------------------------------------------------------------------------------------ */
+#define REFVSR_FINGERPRINT_CHUNK_WORDS 4096
+#define REFVSR_FINGERPRINT_MAX_CHUNKS (1 << 22)
+size_t refvsr_param_fingerprint_workspace_bytes(int nchunks);
+int refvsr_param_fingerprint(const void* chunks, int nchunks, void* workspace, size_t workspace_bytes, void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Inter-frame alignment
  * ------------------------------------------------------------------------------------------ */
 /* models/utils.py:35-43 `warp`: linspace(-1,1) base grid + flow/((Win-1)/2), grid_sample(bilinear,

@@ -93,6 +93,7 @@ def base_config(project='', mode='', config_='', data='', LRS='', batch_size=8):
     c.result_dtype = 'float32'  # 'float16' | 'uint8': the output head stores rint(255 v) itself (extension; host consumers quantise anyway)
     c.result_layout = 'chw'     # 'hwc': the result is the [.., 3, sh, sw] view of dense [.., sh, sw, 3] memory (extension; what image writers consume)
     c.weight_precision = 'hi_lo'  # 'fp16' | 'amp': plain fp16 conv weights, the reference's AMP arithmetic (resolve_weight_precision)
+    c.weight_check = 'auto'     # 'sync' | 'off': when the packed weights are checked against the parameters' device fingerprint (fingerprint.weight_check_policy)
     return c
 
 

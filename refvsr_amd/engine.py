@@ -332,6 +332,13 @@ class Engine(object):
         self.ctx_strict = False
         self._fw_up_wait = None              # split hand-off: makes the current stream wait for fw_feat_up's arrival (import_state_head)
 
+    def drain(self):
+        """The host waits for everything this engine has in flight on its internal streams.  Called before the packed weights are
+        replaced: the calls in flight read the old blobs on the internal streams, where nothing records them for the allocator."""
+        for st in set(self._pipe or ()) | ({self._side} if self._side is not None else set()):
+            st.synchronize()
+        self._inflight.clear()
+
     def set_pipelined(self, on=True):
         """Opt in to cross-call pipelining: forward() is then given `frame_ids` (one hashable id per window frame; equal ids
         <=> equal (lr, ref) content within a stream) and spreads consecutive calls over the engine's internal streams.

@@ -506,6 +506,10 @@ def build_config(argv=None):
     ap.add_argument('--weight_precision', default='hi_lo', choices=['hi_lo', 'fp16', 'amp'],
                     help="extension: conv weights of the engine ('fp16' = the reference's fp16-autocast arithmetic, mid_channels = 24 "
                          "models only; 'amp' = 'fp16' where the config sets is_amp)")
+    ap.add_argument('--weight_check', default='auto', choices=['auto', 'sync', 'off'],
+                    help="extension: when the packed weights are checked against a device fingerprint of the parameters ('auto' = "
+                         "synchronously where the host waits anyway or a clip starts, asynchronously in steady state; 'sync' = every call; "
+                         "'off' = the host-side detector alone)")
     ap.add_argument('--metrics', default='host', choices=['host', 'device'],
                     help="extension: where PSNR / SSIM are computed ('device' = one refvsr_score_frames launch per network call in float64, "
                          "16 bytes per frame cross to the host and with --quantitative_only the frame never does; SSIM agrees with the host "
@@ -518,6 +522,7 @@ def build_config(argv=None):
     cfg.result_dtype = args.result_dtype
     cfg.result_layout = args.result_layout
     cfg.weight_precision = args.weight_precision
+    cfg.weight_check = args.weight_check
     cfg.input_dtype = args.input_dtype
     if args.network:
         cfg.network = args.network

@@ -21,6 +21,7 @@ INGEST_MAX_FRAMES = 16                      # REFVSR_INGEST_MAX_FRAMES: byte fra
 SCORE_MAX_FRAMES = 16                       # REFVSR_SCORE_MAX_FRAMES: frame pairs per refvsr_score_frames launch
 SCORE_MAX_RECTS = 8                         # REFVSR_SCORE_MAX_RECTS: rectangles per refvsr_score_regions launch
 COLORMAP_MAX_MAPS = 16                      # REFVSR_COLORMAP_MAX_MAPS: maps per refvsr_conf_colormap launch
+FINGERPRINT_CHUNK_WORDS = 4096              # REFVSR_FINGERPRINT_CHUNK_WORDS: words per chunk-table entry of refvsr_param_fingerprint
 RESBLOCK24_BLOB_BYTES = 43264
 RESBLOCK24_F16W_BLOB_BYTES = 28928          # the fp16 weight format (ABI 15)
 RESBLOCK48_BLOB_BYTES = 172544
@@ -159,6 +160,8 @@ SIGNATURES = {
     # confidence maps as images (added symbols, ABI 15 unchanged)
     'refvsr_conf_colormap': [_P, _I, _I, _I, _P, _P, _Z, _P],
     'refvsr_colormap_table': [_P],               # copies the 256 x 3 byte colour table to host memory
+    # parameter fingerprint (added symbols, ABI 15 unchanged): device chunk table, chunks, workspace, its bytes, out, stream
+    'refvsr_param_fingerprint': [_P, _I, _P, _Z, _P, _P],
 }
 # fp16 weight format (ABI 15): <name>_f16w twins with the signature of the function they are named after
 _F16W_TWINS = ('refvsr_resblock24_chain', 'refvsr_resblock24_chain_batch', 'refvsr_conv24', 'refvsr_conv24_batch', 'refvsr_conv32',
@@ -167,7 +170,8 @@ SIGNATURES.update((name + '_f16w', SIGNATURES[name]) for name in _F16W_TWINS)
 _SPECIAL = {'refvsr_abi_version': (C.c_int, []), 'refvsr_last_error': (C.c_char_p, []),
             'refvsr_score_workspace_bytes': (C.c_size_t, [_I, _I, _I]),
             'refvsr_score_regions_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I]),
-            'refvsr_conf_colormap_workspace_bytes': (C.c_size_t, [_I, _I, _I])}
+            'refvsr_conf_colormap_workspace_bytes': (C.c_size_t, [_I, _I, _I]),
+            'refvsr_param_fingerprint_workspace_bytes': (C.c_size_t, [_I])}
 EXPORTS = tuple(sorted(list(SIGNATURES) + list(_SPECIAL)))
 
 _lib = None

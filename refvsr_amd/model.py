@@ -14,13 +14,19 @@ the HIP engine (refvsr_amd/engine.py).
 """
 import collections
 import importlib
+import operator
+import os
 
 import torch
 import torch.nn as nn
 
 from . import hip, ops
 from .engine import Engine, Weights
+from .fingerprint import WEIGHT_CHECKS, weight_check_policy
 from .weights import state_spec, strip_module_prefix
+
+
+_VERSION = operator.attrgetter('_version')
 
 
 def _register(root, dotted, param):
@@ -91,26 +97,146 @@ class Network(nn.Module):
         self._packed = None
         self._packed_key = None
         self._engines = []
+        # weight check (config.weight_check, fingerprint.weight_check_policy): the device fingerprint of the parameters that were packed,
+        # the chunk table it is taken with, and the asynchronous checks in flight
+        self._fp_table = None               # ops.FingerprintTable of the cached parameter list; None: the host-side detector alone
+        self._fp_ptrs = None                # (data pointers, device) the table was built for
+        self._fp0 = None                    # fingerprint of the packed parameters (python int, the int64 view of the 64 bits)
+        self._fp_dev = None
+        self._fp_slots = None               # free slots of the ring: (device int64 [1], pinned int64 [1], event)
+        self._fp_pending = collections.deque()      # (slot, call number) of the launched checks, oldest first
+        self._calls = 0
+        self._just_reset = True             # the next call is the first after construction / .to() / reset() / invalidate()
+        self._stale = False                 # invalidate(), or a mismatch found late: the next call re-packs
 
     # -- weights ------------------------------------------------------------------------------
     def _weights_key(self):
-        # cheap change detector (a full walk over named_parameters() costs > 1 ms per call): cached parameter list,
-        # summed in-place version counters, storage address and device of the first / last tensor
+        # cheap change detector (a full walk over named_parameters() costs > 1 ms per call): cached parameter list, summed in-place
+        # version counters (copy_ under no_grad), the storage address of EVERY tensor (`p.data = w` anywhere), device and dtype of the
+        # first.  What it cannot see -- an in-place write through .data -- the device fingerprint sees (_check_fingerprint)
         if self._plist is None:
             self._plist = list(self.parameters())
         pl = self._plist
-        return (len(pl), sum(p._version for p in pl), pl[0].data_ptr(), pl[-1].data_ptr(), pl[0].device, pl[0].dtype)
+        return (len(pl), sum(map(_VERSION, pl)), tuple(map(torch.Tensor.data_ptr, pl)), pl[0].device, pl[0].dtype)
 
     def _apply(self, fn, *a, **k):               # .to() / .cuda() / .half() replace parameter storage
         self._plist = None
+        self._just_reset = True
         return super()._apply(fn, *a, **k)
 
-    def _weights(self, device):
+    def weight_check_mode(self):
+        mode = getattr(self.config, 'weight_check', None) or 'auto'
+        if mode not in WEIGHT_CHECKS:
+            raise ValueError('weight_check must be one of %s, got %r' % (', '.join(WEIGHT_CHECKS), mode))
+        return mode
+
+    def _fingerprint_table(self, device, ptrs):
+        """The chunk table of the cached parameter list (whose data pointers are `ptrs`), rebuilt when a pointer moved; None for a
+        parameter set the kernel does not read -- not all contiguous float32 on `device` (a .half() net, parameters left on the
+        host): the host-side detector alone."""
+        if self._fp_ptrs != (ptrs, str(device)):
+            pl = self._plist
+            ok = all(p.is_cuda and p.device == device and p.dtype == torch.float32 and p.is_contiguous() and p.numel() > 0 for p in pl)
+            self._fp_table = ops.FingerprintTable([p.detach() for p in pl]) if ok else None
+            self._fp_ptrs = (ptrs, str(device))
+        return self._fp_table
+
+    def _fp_ring(self, device):
+        if self._fp_slots is None or self._fp_dev != str(device):
+            self._fp_drop_pending()
+            self._fp_dev = str(device)
+            depth = max(1, int(getattr(self.config, 'pipe_depth', None) or os.environ.get('REFVSR_PIPE_DEPTH') or 3)) + 1
+            self._fp_slots = [(torch.empty(1, dtype=torch.int64, device=device), torch.empty(1, dtype=torch.int64).pin_memory(),
+                               torch.cuda.Event()) for _ in range(depth)]
+        return self._fp_slots
+
+    def _fp_drop_pending(self):
+        """Forget the checks in flight (their reference value is being replaced); their slots are reused once the copies landed."""
+        while self._fp_pending:
+            slot, _ = self._fp_pending.popleft()
+            slot[2].synchronize()
+            self._fp_slots.append(slot)
+
+    def _fp_examine(self, wait_all=False):
+        """Look at the launched checks that have completed (wait_all: at all of them; otherwise without waiting): the number of the
+        earliest call whose fingerprint was not the packed one, or None."""
+        bad = None
+        while self._fp_pending and (wait_all or self._fp_pending[0][0][2].query()):
+            slot, call = self._fp_pending.popleft()
+            if wait_all:
+                slot[2].synchronize()
+            if slot[1].item() != self._fp0 and bad is None:
+                bad = call
+            self._fp_slots.append(slot)
+        return bad
+
+    def _check_fingerprint(self, device, how):
+        """One call's fingerprint check, `how` = 'sync' | 'async' (fingerprint.weight_check_policy), on the caller's current stream --
+        where the caller's writes to the parameters are ordered.  Returns True when the parameters are no longer the packed ones
+        (the caller re-packs); raises when an EARLIER call's check says so: results were returned from stale weights since then."""
+        tab = self._fingerprint_table(device, self._packed_key[0][2])
+        if tab is None:
+            return False
+        slots = self._fp_ring(device)
+        bad = self._fp_examine()
+        if bad is None and not slots:
+            slot, call = self._fp_pending.popleft()             # every slot in flight: wait for the oldest
+            slot[2].synchronize()
+            bad = call if slot[1].item() != self._fp0 else None
+            slots.append(slot)
+        stale_now = False
+        if bad is None:
+            with torch.cuda.device(device):
+                if how == 'sync':
+                    now = int(ops.param_fingerprint(tab).item())           # (the read waits for the caller's stream: every check before it landed)
+                    bad = self._fp_examine(wait_all=True)
+                    stale_now = now != self._fp0
+                else:
+                    slot = slots.pop()
+                    ops.param_fingerprint(tab, out=slot[0])
+                    slot[1].copy_(slot[0], non_blocking=True)
+                    slot[2].record()
+                    self._fp_pending.append((slot, self._calls))
+        if bad is not None:
+            n = self._calls - bad
+            self._stale = True
+            self._fp_drop_pending()
+            self.reset()
+            raise RuntimeError('refvsr_amd: the parameters were changed in place before call %d of this network (%d call%s ago) and the '
+                               'asynchronous weight check has only now seen it: the results returned since that call were computed with '
+                               'the old packed weights and are stale.  The weights are re-packed and the recurrent state is reset: '
+                               'the next call is right, restart the clip with is_first_frame=True.  Call invalidate() after writing '
+                               'parameters through .data inside a pipelined stream, or set config.weight_check = \'sync\'.'
+                               % (bad, n, '' if n == 1 else 's'))
+        return stale_now
+
+    def _weights(self, device, call=None):
+        """The packed weights of the current parameters.  call = (has frame_ids, first frame) for a network call: the device
+        fingerprint check of config.weight_check runs as well (None: the host-side detector alone)."""
         key = (self._weights_key(), str(device))
-        if self._packed is None or self._packed_key != key:
+        stale = self._packed is None or self._packed_key != key or self._stale
+        if call is not None:
+            self._calls += 1
+            if not stale:
+                how = weight_check_policy(self.weight_check_mode(), call[0], call[1], self._just_reset)
+                if how != 'none':
+                    stale = self._check_fingerprint(device, how)
+            self._just_reset = False
+        if stale:
+            # the internal streams of a pipelined engine may still be reading the old blobs (nothing records them on those streams):
+            # wait for the calls in flight before the allocator may hand the blobs' memory to the new ones
+            for e in self._engines:
+                e.drain()
+            self._fp_drop_pending()
             sd = collections.OrderedDict(('Network.' + k, v.detach()) for k, v in self.named_parameters())
             self._packed = self._weights_cls(self.config, sd, device)
             self._packed_key = key
+            self._stale = False
+            # the fingerprint of what was packed, on the caller's stream, read synchronously: a pack costs far more than this read
+            tab = self._fingerprint_table(device, key[0][2])
+            if tab is not None:
+                with torch.cuda.device(device):
+                    self._fp0 = int(ops.param_fingerprint(tab).item())
             for e in self._engines:
                 # everything an engine caches (per-frame matching / encodings / flows, the forward-branch state) was
                 # computed with the old weights
@@ -120,8 +246,15 @@ class Network(nn.Module):
 
     def reset(self):
         """Forget the recurrent state (start a new clip)."""
+        self._just_reset = True
         for e in self._engines:
             e.reset_state()
+
+    def invalidate(self):
+        """Announce that parameters were written in a way the host cannot see (through .data): the next call re-packs the weights
+        and restarts the recurrent state.  The documented way to change weights inside a pipelined stream."""
+        self._stale = True
+        self._just_reset = True
 
     # mirrors the attributes of the reference module that callers / tests look at
     @property
@@ -137,8 +270,9 @@ class Network(nn.Module):
         for e in self._engines:
             e.set_pipelined(on)
 
-    def ensure_engines(self, n, device):
-        W = self._weights(device)
+    def ensure_engines(self, n, device, call=None):
+        """call: (has frame_ids, first frame) when a network call asks -- its weight check runs (see _weights)."""
+        W = self._weights(device, call)
         while len(self._engines) < n:
             self._engines.append(self._engine_cls(self.config, W))
         return self._engines
@@ -158,7 +292,7 @@ class Network(nn.Module):
             raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path'
                                % lrs.device)
         n = lrs.shape[0]
-        self.ensure_engines(n, lrs.device)
+        self.ensure_engines(n, lrs.device, (frame_ids is not None, bool(is_first_frame)))
         # the engine's internal streams will read the inputs when `input_ready` says so, not in the caller's stream order: a
         # dtype / layout conversion here would be pending work on the caller's stream that nothing waits for -- refused
         # instead of raced against.  (input_ready=None waits for the caller's stream, conversions included; calls that take
@@ -216,7 +350,7 @@ class Network(nn.Module):
         if lrs.dtype != refs.dtype:
             raise RuntimeError('forward_group: lrs and refs must both be uint8 or both float32 (got %s and %s)' % (lrs.dtype, refs.dtype))
         assert len(frame_ids) == lrs.shape[0] and lrs.shape == refs.shape
-        eng = self.ensure_engines(1, lrs.device)[0]
+        eng = self.ensure_engines(1, lrs.device, (True, bool(is_first_frame)))[0]
         wins = [(lrs[b], refs[b], [(0, f) for f in frame_ids[b]]) for b in range(lrs.shape[0])]
         res = eng.forward_group(wins, bool(is_first_frame), input_ready, want_vis=bool(want_conf))
         vis = None
@@ -235,7 +369,7 @@ class Network(nn.Module):
         if not lrs.is_cuda:
             raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path' % lrs.device)
         lrs, refs = _inputs(lrs, refs, 'phase_a')
-        self.ensure_engines(lrs.shape[0], lrs.device)
+        self.ensure_engines(lrs.shape[0], lrs.device, (frame_ids is not None, bool(first_hint)))
         return [self._engines[b].phase_a(lrs[b], refs[b], None if frame_ids is None else [(b, f) for f in frame_ids],
                                          first_hint) for b in range(lrs.shape[0])]
 
@@ -247,7 +381,7 @@ class Network(nn.Module):
         if not lrs[0].is_cuda:
             raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path' % lrs[0].device)
         assert len(lrs) == len(refs) == len(frame_ids)
-        eng = self.ensure_engines(1, lrs[0].device)[0]
+        eng = self.ensure_engines(1, lrs[0].device, (True, False))[0]
         wins = [_inputs(lrs[b], refs[b], 'phase_a_group') + ([(0, f) for f in frame_ids[b]],) for b in range(len(lrs))]
         return [[h] for h in eng.phase_a_group(wins, first_hints, streams)]
 
@@ -319,6 +453,11 @@ class SRNet(nn.Module):
         """frame_ids, input_ready (optional extensions, not in the reference): one id per window frame / when the inputs are
         final -- see Engine.forward and Engine.set_pipelined."""
         return self.Network.forward(x, ref, is_first_frame, is_log=is_log, is_train=is_train, frame_ids=frame_ids, input_ready=input_ready)
+
+    def invalidate(self):
+        """Parameters were written through .data (extension, not in the reference): the next call re-packs the weights -- see
+        Network.invalidate."""
+        self.Network.invalidate()
 
     def forward_group(self, x, ref, frame_ids, is_first_frame=False, input_ready=None, want_conf=False):
         """B consecutive windows of one stream in one call (extension, not in the reference): see Network.forward_group."""

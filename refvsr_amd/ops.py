@@ -7,9 +7,10 @@ import ctypes as C
 import math
 import os
 
+import numpy as np
 import torch
 
-from . import hip
+from . import fingerprint, hip
 from .knobs import env_flag
 from .packing import BlobFlags, blob_plan, pack_conv24, pack_conv_shuffle2, pack_resblock
 from .hip import (OUT_NHWC16, OUT_NHWC16_SHUFFLE2, OUT_PLANAR32, RS_BICUBIC, RS_BILINEAR,  # noqa: F401
@@ -936,6 +937,54 @@ def conf_colormap(maps):
         pm, po = _parr(maps[s0:s0 + n]), _parr(outs[s0:s0 + n])
         hip.check(hip.lib().refvsr_conf_colormap(pm, n, h, w, po, _ptr(ws), ws.numel() * 4, st), 'conf_colormap')
     return outs
+
+
+class FingerprintTable(object):
+    """The device chunk table of refvsr_param_fingerprint for one list of tensors (fingerprint.chunk_entries), with one workspace per
+    stream that used it.  Valid while the tensors keep their storage: `pointers` is what the owner compares (Network rebuilds the
+    table when the tuple of data_ptr()s changes).  The tensors are referenced, so their storage cannot be reused under the table."""
+
+    def __init__(self, tensors):
+        tensors = list(tensors)
+        if not tensors:
+            raise ValueError('param_fingerprint: empty tensor list')
+        dev = tensors[0].device
+        for t in tensors:
+            if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous()):
+                raise RuntimeError('param_fingerprint: contiguous float32 tensors of one GPU (got %s, %s, contiguous=%s)'
+                                   % (t.dtype, t.device, t.is_contiguous()))
+        self.tensors = tensors
+        self.pointers = tuple(t.data_ptr() for t in tensors)
+        ent = fingerprint.chunk_entries(self.pointers, [t.numel() for t in tensors], hip.FINGERPRINT_CHUNK_WORDS)
+        self.nchunks = len(ent)
+        self.device = dev
+        self.chunks = torch.from_numpy(ent.view(np.int64).reshape(-1, 2).copy()).to(dev)
+        self._ws = {}
+
+    def workspace(self, st):
+        ws = self._ws.get(st.value)
+        if ws is None:
+            if len(self._ws) > 16:
+                self._ws.clear()
+            ws = self._ws[st.value] = torch.empty(hip.lib().refvsr_param_fingerprint_workspace_bytes(self.nchunks) // 8 + 1, dtype=torch.int64,
+                                                  device=self.device)
+        return ws
+
+
+def param_fingerprint(tensors, out=None):
+    """The 64-bit fingerprint of a table of contiguous cuda float32 tensors (refvsr_param_fingerprint; fingerprint.
+    param_fingerprint_model restates it): F = sum of mix64((g << 32) | word) over all 32-bit words, g the word's index over the
+    concatenated table -- one changed bit changes F.  tensors: a list of tensors (the chunk table is built and uploaded for the call)
+    or an ops.FingerprintTable (built once).  Returns `out`, a device int64 [1] (the 64 bits, read as signed), written on the current
+    stream with no synchronisation."""
+    tab = tensors if isinstance(tensors, FingerprintTable) else FingerprintTable(tensors)
+    if out is None:
+        out = torch.empty(1, dtype=torch.int64, device=tab.device)
+    assert out.is_cuda and out.device == tab.device and out.dtype == torch.int64 and out.numel() == 1
+    st = _stream()
+    ws = tab.workspace(st)
+    hip.check(hip.lib().refvsr_param_fingerprint(_ptr(tab.chunks), tab.nchunks, _ptr(ws), ws.numel() * 8, _ptr(out), st), 'param_fingerprint')
+    return out
 
 
 def warp_nhwc16(x, flow):
