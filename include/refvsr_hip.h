@@ -122,6 +122,29 @@ int refvsr_set_conv_workgroup_cap(int cap);
  * plan function and the same knob object as the launcher.  Host only: no launch, no device call.  A descriptor the launcher
  * rejects is rejected here with the same message (returns 1). */
 int refvsr_conv_variant(const RefvsrConv* d, int* key);
+/* The same for the fixed-channel kernels (added symbols, ABI 15 unchanged; no reference counterpart; host only: no launch, no
+ * refvsr_init -- the block query asks for the device's CU count where `stream` has no CU budget, as its launcher does).  `op` names
+ * the entry point and gives (x0, x1) their meaning: */
+enum {
+    REFVSR_C24_CONV24 = 0,      /* refvsr_conv24*:        (c0, c1) input channels of the two sources                     */
+    REFVSR_C24_CONV32 = 1,      /* refvsr_conv32*:        (c0, c1)                                                       */
+    REFVSR_C24_CONV48 = 2,      /* refvsr_conv48:         (c0, c1)                                                       */
+    REFVSR_C24_SHUFFLE2 = 3,    /* refvsr_conv_shuffle2*: (c, 0)                                                         */
+    REFVSR_C24_CONF_ALPHA = 4,  /* refvsr_conf_alpha*:    (cout, up); h x w = the confidence maps                        */
+    REFVSR_C24_CONV_LAST = 5    /* refvsr_conv_last*:     (c, 0)                                                         */
+};
+/* refvsr_conv24_variant: which conv24_kernel instantiation that entry point (mm = 1: its `_batch` form over `batch` maps, wf = 1: its
+ * `_f16w` twin) would launch on h x w maps under this process's REFVSR_CONV48_WAVES, as the packed key of
+ * refvsr_amd/csrc/fixed_plan.h (c24_variant_key: COUT | NCG0 << 6 | NCG1 << 10 | NWV << 14 | TH << 19 | WPS << 24 | SHUF << 27 |
+ * CONF << 33 | HALF << 35 | MM << 36 | WF << 37), with the launch's tile count and dynamic LDS bytes (n_tiles, lds: optional).  The
+ * same plan function and the same knob object as the entry points, whose first failing shape check it reports with their message;
+ * a shape without a kernel in the asked weight format is an error with the message the dispatch gives (returns 1).
+ * refvsr_resblock24_variant: which resblock24_kernel instantiation a refvsr_resblock24_chain* launch over `batch` maps (head = 0; wf,
+ * relu = act_slope == 0) or refvsr_conv_hr_last (head = 1) would run on `stream` right now -- under refvsr_set_resblock24_waves /
+ * _store, a probe buffer being set (refvsr_set_probe) and the CU budget of `stream` -- as rb24_variant_key: RELU | NWV << 1 |
+ * PROBE << 6 | TH << 7 | STORE << 12 | HEAD << 13 | WF << 14. */
+int refvsr_conv24_variant(int op, int x0, int x1, int mm, int wf, int batch, int h, int w, long long* key, int* n_tiles, int* lds);
+int refvsr_resblock24_variant(int head, int wf, int relu, int batch, int h, int w, void* stream, int* key, int* n_tiles, int* lds);
 /* Packing contract of `wpack` (host-side helpers, no GPU needed): K-slot of K-block (ty, tx, cg) of a ks x ks conv over
  * ncg 16-byte channel groups, and the number of 4-slot K-steps; refvsr_amd/packing.py:kslot/ksteps are the same closed
  * forms and tests/test_capi.py pins the two against each other.  Return the value (>= 0), not a status. */

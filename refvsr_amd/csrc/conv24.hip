@@ -550,6 +550,9 @@ static const C24Knobs& c24_knobs() {
     return knobs;
 }
 
+// what a plan outside RV_C24_VARIANTS is reported with
+static const char* c24_no_kernel(const C24Plan& p) { return p.no_twin ? p.no_twin : "conv24: no kernel for this plan"; }
+
 // the launch of a plan with its filled arguments
 static int c24_dispatch(C24Args& a, const C24Plan& p, void* stream) {
     switch (p.key()) {                                             // key and launcher of a case: the same entry of RV_C24_VARIANTS (fixed_plan.h)
@@ -557,8 +560,28 @@ static int c24_dispatch(C24Args& a, const C24Plan& p, void* stream) {
         RV_C24_VARIANTS(RV_C24_CASE)
 #undef RV_C24_CASE
     }
-    RV_CHECK(false, "%s", p.no_twin ? p.no_twin : "conv24: no kernel for this plan");
+    RV_CHECK(false, "%s", c24_no_kernel(p));
     return 1;
+}
+
+// Test query (refvsr_hip.h): the plan an entry point would launch, by c24_plan under c24_knobs() -- the function and the knob object
+// of the entry points above.  Host only: no launch, no refvsr_init, no HIP call
+extern "C" int refvsr_conv24_variant(int op, int x0, int x1, int mm, int wf, int batch, int h, int w, long long* key, int* n_tiles, int* lds) {
+    RV_CHECK(key != nullptr, "conv24_variant: null key");
+    RV_CHECK(op >= C24_CONV24 && op <= C24_CONV_LAST && (mm == 0 || mm == 1) && (wf == 0 || wf == 1) && h > 0 && w > 0, "conv24_variant: bad args");
+    C24Plan p;
+    if (int rc = c24_plan((C24Op)op, x0, x1, mm, wf, mm ? batch : 1, h, w, c24_knobs(), &p)) return rc;
+    bool listed = false;
+    switch (p.key()) {
+#define RV_C24_CASE(...) case c24_variant_key(__VA_ARGS__):
+        RV_C24_VARIANTS(RV_C24_CASE) listed = !p.no_twin;
+#undef RV_C24_CASE
+    }
+    RV_CHECK(listed, "%s", c24_no_kernel(p));
+    *key = p.key();
+    if (n_tiles) *n_tiles = p.n_tiles;
+    if (lds) *lds = p.lds;
+    return 0;
 }
 
 extern "C" int refvsr_conv24_supported(int c0, int c1) { return c24_supported(C24_CONV24, c0, c1); }

@@ -103,13 +103,14 @@ static_assert(rb_blob(1) == REFVSR_RESBLOCK24_F16W_BLOB_BYTES, "blob size is par
 
 // ---- conv24_kernel: the plan ---------------------------------------------------------------------------------------------------------
 // the ops of conv24.hip and their shape arguments (x0, x1)
+// (the values are public: refvsr_conv24_variant takes them)
 enum C24Op {
-    C24_CONV24,        // refvsr_conv24*: (c0, c1) input channels of the two sources
-    C24_CONV32,        // refvsr_conv32*: (c0, c1)
-    C24_CONV48,        // refvsr_conv48: (c0, c1)
-    C24_SHUFFLE2,      // refvsr_conv_shuffle2*: (c, -)
-    C24_CONF_ALPHA,    // refvsr_conf_alpha*: (cout, up); h x w = the confidence maps, the conv runs on the (up h) x (up w) grid
-    C24_CONV_LAST,     // refvsr_conv_last*: (c, -)
+    C24_CONV24 = REFVSR_C24_CONV24,            // refvsr_conv24*: (c0, c1) input channels of the two sources
+    C24_CONV32 = REFVSR_C24_CONV32,            // refvsr_conv32*: (c0, c1)
+    C24_CONV48 = REFVSR_C24_CONV48,            // refvsr_conv48: (c0, c1)
+    C24_SHUFFLE2 = REFVSR_C24_SHUFFLE2,        // refvsr_conv_shuffle2*: (c, -)
+    C24_CONF_ALPHA = REFVSR_C24_CONF_ALPHA,    // refvsr_conf_alpha*: (cout, up); h x w = the confidence maps, the conv runs on the (up h) x (up w) grid
+    C24_CONV_LAST = REFVSR_C24_CONV_LAST,      // refvsr_conv_last*: (c, -)
 };
 constexpr bool c24_supported(C24Op op, int x0, int x1) {
     return op == C24_CONV24   ? (x0 == 24 && x1 == 0) || (x0 == 16 && x1 == 0) || (x0 == 8 && x1 == 24) || (x0 == 24 && x1 == 24)

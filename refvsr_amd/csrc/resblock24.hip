@@ -463,6 +463,27 @@ extern "C" int refvsr_set_resblock24_waves(int waves) {
     return 0;
 }
 
+// The plan of a launch on `st` at this moment: ONE place where the setters' state, the probe buffer and the stream's CU budget meet
+// rb24_plan -- the launcher and the query below both come through here
+static int rb24_plan_now(int head, int wf, bool relu, int h, int w, int batch, hipStream_t st, Rb24Plan* p) {
+    Rb24Knobs knobs = rb24_knobs();
+    knobs.probe = g_rb_probe != nullptr;
+    return rb24_plan(head, wf, relu, h, w, batch, rv_stream_cus(st), knobs, p);
+}
+
+// Test query (refvsr_hip.h): no launch, no refvsr_init
+extern "C" int refvsr_resblock24_variant(int head, int wf, int relu, int batch, int h, int w, void* stream, int* key, int* n_tiles, int* lds) {
+    RV_CHECK(key != nullptr, "resblock24_variant: null key");
+    RV_CHECK((head == 0 || head == 1) && (wf == 0 || wf == 1) && !(head && wf) && h > 0 && w > 0 && batch >= 1 && batch <= REFVSR_MAX_MAPS,
+             "resblock24_variant: bad args");
+    Rb24Plan p;
+    if (int rc = rb24_plan_now(head, wf, relu != 0, h, w, batch, (hipStream_t)stream, &p)) return rc;
+    *key = p.key();
+    if (n_tiles) *n_tiles = p.n_tiles;
+    if (lds) *lds = p.lds;
+    return 0;
+}
+
 template <bool RELU, int NWV, bool PROBE, int TH, int STORE, int HEAD, int WF>
 static int launch_rb24(RB24Args& a, const Rb24Plan& p, hipStream_t st) {
     constexpr int RB_LDS = rb_lds_wf(TH, WF);
@@ -478,10 +499,8 @@ static int launch_rb24(RB24Args& a, const Rb24Plan& p, hipStream_t st) {
 
 // plan (fixed_plan.h:rb24_plan) and launch of one block (head = 0) or of the output head over the filled arguments
 static int rb24_launch(RB24Args& a, int head, int wf, hipStream_t st) {
-    Rb24Knobs knobs = rb24_knobs();
-    knobs.probe = g_rb_probe != nullptr;
     Rb24Plan p;
-    if (int rc = rb24_plan(head, wf, a.act_slope == 0.f, a.h, a.w, a.batch, rv_stream_cus(st), knobs, &p)) return rc;
+    if (int rc = rb24_plan_now(head, wf, a.act_slope == 0.f, a.h, a.w, a.batch, st, &p)) return rc;
     a.probe = g_rb_probe; a.probe_iter = g_rb_probe_iter;
     switch (p.key()) {                                             // key and launcher of a case: the same entry of RV_RB24_VARIANTS (fixed_plan.h)
 #define RV_RB24_CASE(...) case rb24_variant_key(__VA_ARGS__): return launch_rb24<__VA_ARGS__>(a, p, st);

@@ -14,6 +14,7 @@ RS_BICUBIC, RS_BILINEAR, RS_BILINEAR_AC, RS_NEAREST = 0, 1, 2, 3
 RESULT_F32, RESULT_F16, RESULT_U8 = 0, 1, 2
 RESULT_HWC = 0x10                           # REFVSR_RESULT_HWC: flag bit of an out_fmt, the result is interleaved [h][w][3]
 INGEST_PLANAR, INGEST_HWC = 0, 1
+C24_CONV24, C24_CONV32, C24_CONV48, C24_SHUFFLE2, C24_CONF_ALPHA, C24_CONV_LAST = range(6)      # REFVSR_C24_*: `op` of refvsr_conv24_variant
 MATCH_KP, MATCH_ROWCHUNK, MATCH_COLBLOCK = 152, 256, 512
 ABI_VERSION = 15
 MAX_MAPS = 4
@@ -63,6 +64,10 @@ SIGNATURES = {
     'refvsr_conv_mfma': [C.POINTER(RefvsrConv), _P],
     'refvsr_set_conv_workgroup_cap': [_I],
     'refvsr_conv_variant': [C.POINTER(RefvsrConv), C.POINTER(C.c_int)],      # the planned kernel variant's key (added symbol, ABI 15 unchanged)
+    # the same for the fixed-channel kernels (added symbols, ABI 15 unchanged): op (C24_*), x0, x1, mm, wf, batch, h, w -> key, n_tiles,
+    # lds | head, wf, relu, batch, h, w, stream -> key, n_tiles, lds
+    'refvsr_conv24_variant': [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    'refvsr_resblock24_variant': [_I, _I, _I, _I, _I, _I, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     'refvsr_kslot': [_I, _I, _I, _I, _I],        # returns the slot, not a status
     'refvsr_ksteps': [_I, _I],                   # returns the K-step count
     'refvsr_set_probe': [_P, _I],

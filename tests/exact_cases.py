@@ -242,11 +242,29 @@ def ref_blocks(A, p):
 def ref_conf_alpha(A, p):
     """refvsr_conf_alpha, up = 1:  t = fp16(lrelu(conv_{2->16}(cat[conf_a, conf_b]) + b0, slope0)) (conv24.hip:272, an fp32 FMA chain
     over fp32 weights: exact on one-tap weights), alpha = fp16(lrelu(conv_{16->C}(t) + b, slope1)) (the conv24 epilogue),
-    conf_max = max(conf_a, conf_b) (conv24.hip:284)."""
+    conf_max = max(conf_a, conf_b) (conv24.hip:284).
+    up = 2 (CONF = 2): P = clamp01(bicubic x2 of the pair) in fp32 (conv24.hip conf_stage: rv_bicubic_at with a source step of 0.5,
+    fminf / fmaxf), the rest as above on the (2 h) x (2 w) grid; no conf_max.  The bicubic is sampling_cases.ref_resize, the float64
+    restatement of the resize kernel that shares rv_bicubic_at (float32 under the 'f32' arithmetic); p['mut'] hands it a mutation."""
     P = torch.cat([p['conf_a'], p['conf_b']], 0)
+    if p.get('up', 1) == 2:
+        P = bicubic_up2(P, np.float32 if A.mode == 'f32' else np.float64, p.get('mut'))
     t = A.conv(P, p['w0'], p['b0']).lrelu(p['slope0']).half()
     y = A.conv(t, p['w'], p['b']).lrelu(p['slope1']).half()
+    if p.get('up', 1) == 2:
+        return {'out': y.v.double()}, y.g
     return {'out': y.v.double(), 'cmax': torch.maximum(p['conf_a'], p['conf_b'])}, y.g
+
+
+def bicubic_up2(P, T=np.float64, mut=None, clamp=True, transposed=False):
+    """clamp01(F.interpolate(P, x2, bicubic)) of a [C, h, w] float64 tensor by sampling_cases.ref_resize over the number type T
+    (transposed: columns first -- the other summation order)."""
+    import sampling_cases as sc                             # (imports this module)
+    x = P.numpy().transpose(0, 2, 1) if transposed else P.numpy()
+    c, h, w = x.shape
+    out = sc.ref_resize(T, dict(x=np.ascontiguousarray(x), mode=sc.RS_BICUBIC, out_hw=(2 * h, 2 * w), src_scale=(0.5, 0.5), clamp01=clamp), mut)['out']
+    out = out.transpose(0, 2, 1) if transposed else out
+    return torch.from_numpy(np.ascontiguousarray(out.astype(np.float64)))
 
 
 def ref_conv_last(A, p):
@@ -535,12 +553,47 @@ def _placement(j, c):
     return plan
 
 
-def _conf_case(name, seed, C, hw, want_max=False, wfmt='hi_lo'):
+def _conf_case(name, seed, C, hw, want_max=False, wfmt='hi_lo', up=1, staging=False):
+    """hw: the confidence maps.  up = 2 has two forms (the hi + lo budget does not fit behind a generic bicubic sample: 2^-16-granule
+    samples rounded to fp16, times 2^-17-granule weights):
+      K (staging False): the maps hold -64 | 65 in 2 x 2-pixel cells placed at random, so that every up-sampled sample lies outside
+        (0, 1) and the clamp makes it exactly 0 or 1 (asserted below on the case's own data) -- from there the up = 1 construction.
+      S (staging True): rich maps in {-1, 0, 1}; BOTH convs one-tap with weights +-1 | +-1/2 (lo = 0), the first conv's bias chosen per
+        channel so that w P + b0 lies in [1, 2] -- exactly representable in fp32 and never an fp16 subnormal: each output is a
+        relocated, rescaled copy of ONE sample rounded once to fp16, every tap, clamp and border of the bicubic shows."""
     g = rng(seed)
     h, w = hw
-    p = dict(conf_a=int_map(g, 1, h, w), conf_b=int_map(g, 1, h, w), w0=onetap_weights(g, 16, 2), b0=dyadic_vec(g, 16, -1, 1, 0.5),
-             slope0=0.5, w=dyadic_weights(g, C, 16, 3), b=dyadic_vec(g, C), slope1=0.25)
-    return Case(name, 'conf_alpha', dict(entry='conf_alpha', want_max=want_max, wfmt=wfmt), p, 'hi' if wfmt == 'fp16' else 'f64', None, seed)
+    run = dict(entry='conf_alpha', want_max=want_max, wfmt=wfmt, up=up)
+    if up == 1:
+        p = dict(conf_a=int_map(g, 1, h, w), conf_b=int_map(g, 1, h, w), w0=onetap_weights(g, 16, 2), b0=dyadic_vec(g, 16, -1, 1, 0.5),
+                 slope0=0.5, w=dyadic_weights(g, C, 16, 3), b=dyadic_vec(g, C), slope1=0.25)
+        return Case(name, 'conf_alpha', run, p, 'hi' if wfmt == 'fp16' else 'f64', None, seed)
+    assert up == 2 and not want_max
+    if not staging:
+        cells = lambda: pick(g, [-64.0, 65.0], (1, (h + 1) // 2, (w + 1) // 2)).repeat_interleave(2, 1).repeat_interleave(2, 2)[:, :h, :w].contiguous()
+        p = dict(conf_a=cells(), conf_b=cells(), w0=onetap_weights(g, 16, 2), b0=dyadic_vec(g, 16, -1, 1, 0.5), slope0=0.5,
+                 w=dyadic_weights(g, C, 16, 3), b=dyadic_vec(g, C), slope1=0.25, up=2)
+        raw = bicubic_up2(torch.cat([p['conf_a'], p['conf_b']], 0), clamp=False)
+        assert not ((raw > 0) & (raw < 1)).any(), '%s: an up-sampled sample lies inside (0, 1)' % name
+        assert (raw <= 0).any() and (raw >= 1).any()
+        return Case(name, 'conf_alpha', run, p, 'hi' if wfmt == 'fp16' else 'f64', None, seed)
+    w0 = onetap_weights(g, 16, 2)
+    v0 = w0.sum((1, 2, 3))                                            # the one weight of each output channel
+    b0 = torch.where(v0 == -1.0, 2.0, torch.where(v0 == -0.5, 1.5, 1.0)).to(F64)
+    p = dict(conf_a=int_map(g, 1, h, w), conf_b=int_map(g, 1, h, w), w0=w0, b0=b0, slope0=0.5, w=onetap_weights(g, C, 16), b=dyadic_vec(g, C),
+             slope1=0.25, up=2)
+    return Case(name, 'conf_alpha', run, p, 'hi' if wfmt == 'fp16' else 'f64', 'drop_hi', seed)
+
+
+def conf_up2_classes(p):
+    """(samples clamped at 0, clamped at 1, strictly between) of an up = 2 case, with the proof that the fp32 bicubic is exact on its
+    maps: float32 equals float64, rows first equals columns first."""
+    P = torch.cat([p['conf_a'], p['conf_b']], 0)
+    raw = bicubic_up2(P, clamp=False)
+    for T in (np.float32, np.float64):
+        for tr in (False, True):
+            assert torch.equal(bicubic_up2(P, T, clamp=False, transposed=tr), raw), 'the bicubic is not exact on this case (%s, transposed %s)' % (T.__name__, tr)
+    return int((raw <= 0).sum()), int((raw >= 1).sum()), int(((raw > 0) & (raw < 1)).sum())
 
 
 def _last_case(name, seed, C, hw, lo0=None, g_exp=-17, mag_exp=-3, xr=1):

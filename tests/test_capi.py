@@ -144,6 +144,100 @@ def test_conv_variant_query_is_the_launchers_plan(libpath):
     assert h.refvsr_conv_mfma(ctypes.byref(d), None) != 0 and b'ksteps mismatch' in h.refvsr_last_error()
 
 
+def test_fixed_variant_queries_are_the_launchers_plans(libpath):
+    """refvsr_conv24_variant / refvsr_resblock24_variant (added symbols, ABI 15 unchanged): host only -- they answer here, where no
+    device exists -- with the packed key, tile count and LDS bytes of the planned conv24_kernel / resblock24_kernel instantiation, and
+    reject what the entry points reject, with the same message."""
+    from refvsr_amd import hip
+    h = hip.lib()
+    src = open(os.path.join(ROOT, 'include', 'refvsr_hip.h')).read()
+    ops = [n for n, _ in sorted(re.findall(r'REFVSR_C24_([A-Z0-9_]+) = (\d)', src), key=lambda t: int(t[1]))]
+    assert ops == ['CONV24', 'CONV32', 'CONV48', 'SHUFFLE2', 'CONF_ALPHA', 'CONV_LAST']
+    assert [getattr(hip, 'C24_' + n) for n in ops] == list(range(6))
+    key, n, lds = ctypes.c_longlong(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+    c24 = lambda *a: h.refvsr_conv24_variant(*a, ctypes.byref(key), ctypes.byref(n), ctypes.byref(lds))
+    k = lambda COUT, NCG0, NCG1, NWV, TH, WPS, SHUF=0, CONF=0, HALF=0, MM=0, WF=0: (
+        COUT | NCG0 << 6 | NCG1 << 10 | NWV << 14 | TH << 19 | WPS << 24 | SHUF << 27 | CONF << 33 | HALF << 35 | MM << 36 | WF << 37)
+    # (op, x0, x1, mm, wf, batch, h, w) -> (key, tiles, LDS bytes); none of these depends on REFVSR_CONV48_WAVES
+    for args, want in (((hip.C24_CONV24, 24, 0, 0, 0, 1, 19, 45), (k(24, 3, 0, 8, 8, 4), 6, 37952)),
+                       ((hip.C24_CONV24, 8, 24, 1, 1, 3, 19, 45), (k(24, 1, 3, 8, 8, 4, MM=1, WF=1), 18, 45760)),
+                       ((hip.C24_CONV24, 24, 0, 0, 0, 7, 19, 45), (k(24, 3, 0, 8, 8, 4), 6, 37952)),      # a single-map entry has no batch
+                       ((hip.C24_CONV32, 8, 0, 0, 1, 1, 8, 32), (k(32, 1, 0, 8, 8, 4, WF=1), 1, 11712)),
+                       ((hip.C24_CONV48, 48, 48, 0, 0, 1, 19, 45), (k(24, 6, 6, 16, 8, 4, HALF=1), 6, 153792)),
+                       ((hip.C24_SHUFFLE2, 48, 0, 0, 0, 1, 33, 70), (k(48, 6, 0, 16, 16, 4, SHUF=48), 9, 154816)),
+                       ((hip.C24_CONF_ALPHA, 24, 2, 1, 0, 3, 19, 45), (k(24, 2, 0, 8, 8, 4, CONF=2, MM=1), 45, 36480)),      # 38 x 90: the doubled grid
+                       ((hip.C24_CONV_LAST, 24, 0, 0, 0, 1, 75, 301), (k(3, 3, 0, 8, 8, 4), 100, 23616))):
+        assert c24(*args) == 0, h.refvsr_last_error()
+        assert (key.value, n.value, lds.value) == want, args
+    assert h.refvsr_conv24_variant(hip.C24_CONV24, 24, 0, 0, 0, 1, 19, 45, ctypes.byref(key), None, None) == 0      # tile count and LDS bytes are optional
+    if not os.environ.get('REFVSR_CONV48_WAVES'):
+        assert c24(hip.C24_CONV48, 48, 0, 0, 0, 1, 33, 70) == 0 and key.value == k(48, 6, 0, 16, 16, 4)
+
+    P = ctypes.c_void_p
+    buf = (ctypes.c_char * 65536)()
+    at = lambda off: ctypes.cast(ctypes.addressof(buf) + off, P)
+    arr = lambda *ps: (P * len(ps))(*[p.value for p in ps])
+
+    def expect(query, entry, text):
+        """the query's message, then the entry point's: both `text`"""
+        assert query() != 0
+        got = h.refvsr_last_error().decode()
+        assert got == text, got
+        if entry is not None:
+            assert entry() != 0 and h.refvsr_last_error().decode() == text, h.refvsr_last_error()
+
+    s2, o2 = arr(at(0), at(4096)), arr(at(8192), at(12288))
+    conv = lambda f, c0, c1: f(at(0), c0, None, c1, 8, 8, at(1024), 1.0, None, None, 1.0, at(4096), None)
+    expect(lambda: c24(hip.C24_CONV24, 20, 0, 0, 0, 1, 8, 8), lambda: conv(h.refvsr_conv24, 20, 0), 'conv24: 20 + 0 input channels not supported')
+    expect(lambda: c24(hip.C24_CONV24, 24, 0, 1, 0, 5, 8, 8), lambda: h.refvsr_conv24_batch(s2, 24, None, 0, 5, 8, 8, at(1024), 1.0, None, None, 1.0, o2, None),
+           'conv24_batch: 1..4 maps per launch')
+    expect(lambda: c24(hip.C24_CONV32, 24, 0, 0, 1, 1, 8, 8), lambda: conv(h.refvsr_conv32_f16w, 24, 0), 'conv32: 24 + 0 input channels not supported')
+    expect(lambda: c24(hip.C24_CONV48, 24, 24, 0, 0, 1, 8, 8), lambda: conv(h.refvsr_conv48, 24, 24), 'conv48: 24 + 24 input channels not supported')
+    expect(lambda: c24(hip.C24_SHUFFLE2, 48, 0, 1, 0, 2, 8, 8), lambda: h.refvsr_conv_shuffle2_batch(s2, 2, 48, 8, 8, at(1024), 1.0, o2, None),
+           'conv_shuffle2_batch: 48 channels not supported (24)')
+    expect(lambda: c24(hip.C24_SHUFFLE2, 48, 0, 0, 1, 1, 8, 8), None,
+           'conv_shuffle2_f16w: 24 channels only (the mid_channels = 24 family)')      # a shape without a twin: the dispatch's message (the entry
+    #                                                                                    point gives it behind refvsr_init, which needs a device)
+    conf = lambda f, cout, up: f(at(0), at(512), 8, 8, up, at(1024), at(2048), 0.2, at(3072), cout, 0.2, at(8192), None, None)
+    expect(lambda: c24(hip.C24_CONF_ALPHA, 24, 3, 0, 0, 1, 8, 8), lambda: conf(h.refvsr_conf_alpha, 24, 3), 'conf_alpha: up must be 1 or 2')
+    expect(lambda: c24(hip.C24_CONF_ALPHA, 32, 1, 0, 0, 1, 8, 8), lambda: conf(h.refvsr_conf_alpha, 32, 1), 'conf_alpha: 32 output channels not supported (24 | 48)')
+    expect(lambda: c24(hip.C24_CONF_ALPHA, 48, 1, 0, 1, 1, 8, 8), None,
+           'conf_alpha_f16w: 24 output channels only (the mid_channels = 24 family)')
+    expect(lambda: c24(hip.C24_CONF_ALPHA, 48, 1, 1, 0, 2, 8, 8),
+           lambda: h.refvsr_conf_alpha_batch(s2, s2, 2, 8, 8, 1, at(1024), at(2048), 0.2, at(3072), 48, 0.2, o2, None, None), 'conf_alpha_batch: 48 output channels not supported (24)')
+    expect(lambda: c24(hip.C24_CONV_LAST, 16, 0, 0, 0, 1, 8, 8), lambda: h.refvsr_conv_last(at(0), 16, 8, 8, at(1024), at(2048), 8, 8, at(4096), None),
+           'conv_last: 16 input channels not supported (24 | 48)')
+    # the query's own arguments
+    key.value = -1
+    assert h.refvsr_conv24_variant(hip.C24_CONV24, 24, 0, 0, 0, 1, 8, 8, None, None, None) != 0 and b'null key' in h.refvsr_last_error()
+    for bad in ((6, 24, 0, 0, 0, 1, 8, 8), (-1, 24, 0, 0, 0, 1, 8, 8), (0, 24, 0, 2, 0, 1, 8, 8), (0, 24, 0, 0, 2, 1, 8, 8), (0, 24, 0, 0, 0, 1, 0, 8)):
+        assert c24(*bad) != 0 and h.refvsr_last_error() == b'conv24_variant: bad args' and key.value == -1
+    assert c24(hip.C24_CONV32, 32, 0, 1, 0, 2, 8, 8) != 0 and h.refvsr_last_error() == b'conv24: no kernel for this plan'      # conv32 has no `_batch` form
+
+    # resblock24: the setters and the probe buffer are the process's state (restored); no stream budget registered: by-size uses the device's CUs
+    rkey = ctypes.c_int(-1)
+    rb = lambda *a: h.refvsr_resblock24_variant(*a, None, ctypes.byref(rkey), ctypes.byref(n), ctypes.byref(lds))
+    rk = lambda RELU, NWV, PROBE, TH, STORE, HEAD, WF: RELU | NWV << 1 | PROBE << 6 | TH << 7 | STORE << 12 | HEAD << 13 | WF << 14
+    try:
+        for waves, store, probe, args, want in ((8, 1, 0, (0, 0, 1, 3, 19, 45), (rk(1, 8, 0, 8, 1, 0, 0), 18, 64000)),
+                                                (16, 0, 0, (0, 1, 0, 1, 33, 70), (rk(0, 16, 0, 16, 0, 0, 1), 9, 63488)),
+                                                (4, 1, 0, (0, 0, 1, 1, 19, 45), (rk(1, 4, 0, 8, 0, 0, 0), 6, 64000)),
+                                                (4, 1, 0, (1, 0, 0, 1, 19, 45), (rk(0, 8, 0, 8, 0, 1, 0), 6, 64000)),      # the head has no four-wave kernel: by size
+                                                (16, 1, 1, (0, 0, 1, 1, 33, 70), (rk(1, 16, 1, 16, 0, 0, 0), 9, 77824)),
+                                                (16, 1, 1, (0, 1, 1, 1, 33, 70), (rk(1, 16, 0, 16, 1, 0, 1), 9, 63488))):     # no probe kernel in the fp16 format
+            assert h.refvsr_set_resblock24_waves(waves) == 0 and h.refvsr_set_resblock24_store(store) == 0
+            h.refvsr_set_probe(at(0) if probe else None, 0)                  # (never written: nothing is launched)
+            assert rb(*args) == 0, h.refvsr_last_error()
+            assert (rkey.value, n.value, lds.value) == want, (waves, store, probe, args)
+    finally:
+        h.refvsr_set_probe(None, 0)
+        h.refvsr_set_resblock24_waves(0)
+        h.refvsr_set_resblock24_store(1)
+    assert h.refvsr_resblock24_variant(0, 0, 1, 1, 8, 8, None, None, None, None) != 0 and b'null key' in h.refvsr_last_error()
+    for bad in ((2, 0, 1, 1, 8, 8), (1, 1, 0, 1, 8, 8), (0, 2, 1, 1, 8, 8), (0, 0, 1, 5, 8, 8), (0, 0, 1, 0, 8, 8), (0, 0, 1, 1, 0, 8)):
+        assert rb(*bad) != 0 and h.refvsr_last_error() == b'resblock24_variant: bad args'
+
+
 def test_multimap_entry_points_validate_before_device_work(libpath):
     """The ABI 11 entry points (host arrays of per-map device pointers): batch bounds, null table entries, shape support and aliasing are
     rejected with a message before anything touches the device."""
