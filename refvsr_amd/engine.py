@@ -942,33 +942,44 @@ class Engine(object):
         earlier positions in this window) whose content is identical -- or, when the caller supplies frame ids,
         whose id matches (no device work, no synchronisation).  8-bit frames: the new contexts' conversions run as one
         ingest launch at the end, or are left in the caller's `ingest` list (one launch over several windows)."""
+        return self._frames_group([(lrs, refs, frame_ids)], ingest)[0]
+
+    def _frames_group(self, wins, ingest=None):
+        """_frames for the B >= 1 windows [(lrs, refs, frame_ids)] of a call; B >= 2: named by frame ids."""
         pend = [] if ingest is None else ingest
-        frames = self._window_frames(lrs, refs, frame_ids, pend)
+        out = [self._window_frames(*wins[0], pend)] if len(wins) == 1 else self._id_frames(wins, pend)
         if ingest is None:
             ops.ingest_u8(pend)
-        return frames
+        return out
+
+    def _id_frames(self, wins, pend):
+        """The id-keyed lookup for B >= 1 windows: a frame's context comes from the id cache, else from the contexts prepared / imported
+        ahead of their first window (prepare_context), else it is new.  The cache keeps the union of the windows' frames."""
+        if self.id_cache and next(iter(self.id_cache.values())).lr.shape != wins[0][0].shape[1:]:
+            self.id_cache, self.flow_cache = {}, {}
+        out = []
+        for lrs, refs, ids in wins:
+            assert len(ids) == lrs.shape[0]
+            for i, fid in enumerate(ids):
+                if fid not in self.id_cache:
+                    self.id_cache[fid] = self.ctx_pinned.pop(fid, None) or FrameCtx(lrs[i], refs[i], pend)
+            out.append([self.id_cache[fid] for fid in ids])
+        keep = set(fid for _, _, ids in wins for fid in ids)
+        self.id_cache = {k: v for k, v in self.id_cache.items() if k in keep}
+        self._keep_flows(out)
+        return out
+
+    def _keep_flows(self, frs):
+        """The flow cache keeps the pairs of the windows `frs`; the last one is the previous window of the next call."""
+        live = set(f.uid for fr in frs for f in fr)
+        self.flow_cache = {k2: v for k2, v in self.flow_cache.items() if k2[0] in live and k2[1] in live}
+        self.prev_window = frs[-1]
 
     def _window_frames(self, lrs, refs, frame_ids, pend):
         t = lrs.shape[0]
         frames = [None] * t
         if frame_ids is not None and self.cache:
-            assert len(frame_ids) == t
-            if self.id_cache and next(iter(self.id_cache.values())).lr.shape != lrs.shape[1:]:
-                self.id_cache, self.flow_cache = {}, {}
-            for i, fid in enumerate(frame_ids):
-                fr = self.id_cache.get(fid)
-                if fr is None:
-                    fr = self.ctx_pinned.pop(fid, None)            # prepared / imported ahead of its first window (prepare_context)
-                    if fr is None:
-                        fr = FrameCtx(lrs[i], refs[i], pend)
-                    self.id_cache[fid] = fr
-                frames[i] = fr
-            keep = set(frame_ids)
-            self.id_cache = {k: v for k, v in self.id_cache.items() if k in keep}
-            live = set(f.uid for f in frames)
-            self.flow_cache = {k2: v for k2, v in self.flow_cache.items() if k2[0] in live and k2[1] in live}
-            self.prev_window = frames
-            return frames
+            return self._id_frames([(lrs, refs, frame_ids)], pend)[0]
         if not self.cache:
             self.flow_cache = {}
             return [FrameCtx(lrs[i], refs[i], pend) for i in range(t)]
@@ -1003,9 +1014,7 @@ class Engine(object):
         for i in range(t):
             if frames[i] is None:
                 frames[i] = FrameCtx(lrs[i], refs[i], pend)
-        live = set(f.uid for f in frames)
-        self.flow_cache = {k2: v for k2, v in self.flow_cache.items() if k2[0] in live and k2[1] in live}
-        self.prev_window = frames
+        self._keep_flows([frames])
         return frames
 
     # ------------------------------------------------------------------ pipelined forward (opt-in)
@@ -1120,21 +1129,29 @@ class Engine(object):
             for st in share:
                 x.record_stream(st)
 
-    def _prepare_window(self, fr, start, share, n_ctx, head=False):
-        """P section of a pipelined call for one window, on the current stream: prepares fr[start:] and publishes each frame for
-        `share`; a frame prepared here carries `ready`, the event its consumers on the other streams wait for.  Frames newer than
-        n_ctx were cloned by this call.  head: the frame at the window's end also runs the first `bw_head_blocks` layers of its
-        backward step (a function of that frame alone: load balance between the streams)."""
-        for f in fr:
-            if f.uid > n_ctx:
-                for st in share:
-                    f.lr.record_stream(st)
-                    f.ref.record_stream(st)
+    def _prepare_window(self, fr, start, share, n_ctx=None, head=False, pyramid_first=True, ready_if_prepared=False):
+        """P section of a call for one window, on the current stream -- the one place that publishes a prepared frame and records its
+        `ready`: prepares fr[start:] and publishes each frame for `share`; a frame prepared here carries `ready`, the event its
+        consumers on the other streams wait for.  n_ctx: frames newer than that uid were cloned by this call, their copies are
+        recorded on `share` up front (None: the caller records the windows' copies itself).  head: the frame at the window's end also
+        runs the first `bw_head_blocks` layers of its backward step (a function of that frame alone: load balance between the
+        streams).  pyramid_first: the SPyNet pyramid of a new frame before its preparation (pipelined calls), else behind it
+        (phase_a_group).  ready_if_prepared: a frame that was prepared elsewhere without `ready` (on this stream, ahead of its window:
+        prepare_context / import_context) gets the event as well (phase_a_group; a pipelined call only publishes it -- what it finds
+        was prepared on M by a reference-order call, behind which every internal stream waited)."""
+        if n_ctx is not None:
+            for f in fr:
+                if f.uid > n_ctx:
+                    for st in share:
+                        f.lr.record_stream(st)
+                        f.ref.record_stream(st)
         t = len(fr)
         for i in range(start, t):          # (a restarting forward branch walks the first frames too: cached)
             f = fr[i]
-            if f.conf is None:
-                self.pyramid(f)
+            new = f.conf is None
+            if new:
+                if pyramid_first:
+                    self.pyramid(f)
                 self.prepare_frame(f)
                 if head and i == t - 1 and self.bw_head_blocks >= 0:
                     h, w = f.lr.shape[1:]
@@ -1142,26 +1159,24 @@ class Engine(object):
                     f.bw_head = (self.bw_head_blocks, self.resblocks(f.lr8, zf, 'backward_resblocks', stop=self.bw_head_blocks))
                     for st in share:
                         f.bw_head[1].record_stream(st)
+            if f.ready is None:
+                self.pyramid(f)
                 self._publish(f, share)
-                f.ready = torch.cuda.Event()
-                f.ready.record()
-            else:
-                if f.pyr is None:
-                    self.pyramid(f)
-                if f.ready is None:          # prepared on M by a first-frame call: make it safe on the other streams too
-                    self._publish(f, share)
+                if new or ready_if_prepared:
+                    f.ready = torch.cuda.Event()
+                    f.ready.record()
 
     @torch.no_grad()
     def _forward_pipelined(self, lrs, refs, is_first_frame, want_vis, frame_ids, input_ready=None):
         """Same computation as _forward_seq, spread over the internal streams so that consecutive calls overlap: P prepares the
         window's new frame and its flows while M is still walking the previous call's backward branch and F its forward-branch step.
-        Round 6: a steady call IS a frame group of one window (_forward_group_pipelined: one implementation of the P | F | M schedule
-        for one window per call, B windows per call and -- forward_multi -- n samples per call); only the gradio mode and a call without
+        Round 6: a steady call IS a frame group of one window (_pipe_call: the one implementation of the P | F | M schedule for one
+        window per call, B windows per call and -- forward_multi -- n samples per call); only the gradio mode and a call without
         a carried state that is not a first frame (an error of the caller, reported by _forward_seq) take the reference order on M."""
         dev = lrs.device
         # A window whose forward branch restarts -- a reset_branch roll-over of a running stream (RefVSR.py:168-170) and, since round 6,
         # a caller's FIRST FRAME -- differs from a steady one only in its forward branch: t // 2 + 1 steps from zeros over the window's
-        # first frames instead of one step from the carried state.  It stays on the three streams (`rst` in _forward_group_pipelined): no
+        # first frames instead of one step from the carried state.  It stays on the three streams (`rst` in _pipe_call): no
         # drain of the calls in flight, no serial pass on M, no refill of the pipeline behind it (a first frame used to cost 11.5 ms of
         # serial launches on M at 270p; a clip's first call now overlaps like any other).
         if not bool(self.cfg.EVAL.is_gradio) and (is_first_frame or self.fw_feat is not None):
@@ -1175,8 +1190,7 @@ class Engine(object):
         for st in (P, F_, Mo):
             M.wait_stream(st)
         with ops.on_stream(M):
-            out, vis = self._forward_seq(lrs, refs, True if (self.max_frame_itr_num is not None and self.frame_itr_num == self.max_frame_itr_num)
-                                         else is_first_frame, want_vis, frame_ids)
+            out, vis = self._forward_seq(lrs, refs, is_first_frame, want_vis, frame_ids)     # (a roll-over: _branch_restarts)
         for st in (F_, P, Mo):
             st.wait_stream(M)
         self._pipe_end(caller, M, [out], vis)
@@ -1198,40 +1212,13 @@ class Engine(object):
                     ops.CONV24 and self.cache and self.overlap and not bool(self.cfg.EVAL.is_gradio) and
                     ops.conf_alpha_ok(self.cw('conf_fusion.1.0')) and ops.conf_alpha_ok(self.cw('conf_fusion2.1.0')))
 
-    def _frames_group(self, wins):
-        """_frames (id-keyed form) for the B windows of a group: the cache keeps the union of their frames (8-bit frames: converted
-        by one ingest launch)."""
-        keep = set()
-        for _, _, ids in wins:
-            keep.update(ids)
-        lr0 = wins[0][0]
-        if self.id_cache and next(iter(self.id_cache.values())).lr.shape != lr0.shape[1:]:
-            self.id_cache, self.flow_cache = {}, {}
-        out, pend = [], []
-        for lrs, refs, ids in wins:
-            assert len(ids) == lrs.shape[0]
-            frames = []
-            for i, fid in enumerate(ids):
-                fr = self.id_cache.get(fid)
-                if fr is None:
-                    fr = self.ctx_pinned.pop(fid, None)
-                    if fr is None:
-                        fr = FrameCtx(lrs[i], refs[i], pend)
-                    self.id_cache[fid] = fr
-                frames.append(fr)
-            out.append(frames)
-        ops.ingest_u8(pend)                                      # (8-bit frames: the group's new frames in one launch)
-        self.id_cache = {k: v for k, v in self.id_cache.items() if k in keep}
-        live = set(f.uid for fr in out for f in fr)
-        self.flow_cache = {k2: v for k2, v in self.flow_cache.items() if k2[0] in live and k2[1] in live}
-        self.prev_window = out[-1]
-        return out
-
-    def _itr_after(self, k):
-        """frame_itr_num as the k-th window from now will find it (the counter restarts at max_frame_itr_num, RefVSR.py:168-170,292-295)."""
+    def _itr_after(self, k, first=False):
+        """frame_itr_num as the k-th window from now will find it: the counter restarts at max_frame_itr_num and -- first -- at the next
+        window, a caller's first frame (RefVSR.py:168-170,292-295).  The one place that advances the counter: a call over k windows
+        leaves _itr_after(k, first) behind."""
         itr = int(self.frame_itr_num)
-        for _ in range(k):
-            if self.max_frame_itr_num is not None and itr == self.max_frame_itr_num:
+        for j in range(k):
+            if (first and j == 0) or (self.max_frame_itr_num is not None and itr == self.max_frame_itr_num):
                 itr = 0
             itr += 1
         return itr
@@ -1251,7 +1238,8 @@ class Engine(object):
         i = 0
         if is_first_frame:
             self.id_cache, self.flow_cache = {}, {}               # a new clip: ids of the previous one must not match (as in forward())
-        if self.group_ok() and self.pipelined:
+        grouped = self.group_ok() and self.pipelined                # (weight look-ups: once per call)
+        if grouped:
             # before the first internal stream exists: an engine driven through forward_group runs P | F | M from its first call on
             # (a rebuild later would leave the first set of streams behind, and with more streams than hardware queues the
             # stream -> queue mapping decides which sections serialise); REFVSR_PIPE_LAYOUT / config.pipe_layout override it
@@ -1261,9 +1249,8 @@ class Engine(object):
                 # the longest run of steady windows from i on (the iteration counter advances by one per window)
                 j = i
                 head = bool(i == 0 and is_first_frame)              # (round 6: a first frame is a member of its group like a roll-over)
-                if (self.group_ok() and self.pipelined and not bool(self.cfg.EVAL.is_gradio) and (self.fw_feat is not None or head)):
-                    # (a roll-over window stays inside the group: only its forward branch is the long one, `rst` in
-                    #  _forward_group_pipelined)
+                if grouped and (self.fw_feat is not None or head):         # (group_ok() excludes the gradio mode)
+                    # (a roll-over window stays inside the group: only its forward branch is the long one, `rst` in _pipe_call)
                     while j < len(wins) and j - i < ops.hip.MAX_MAPS:
                         j += 1
                 if j - i >= 2:
@@ -1280,89 +1267,125 @@ class Engine(object):
         return (outs, vis) if want_vis else outs
 
     def _forward_group_pipelined(self, wins, input_ready, want_vis=False, first=False):
-        """B >= 1 steady windows of this stream on the internal streams (the ONE implementation of the P | F | M schedule, round 6):
-        P prepares the windows' new frames and flows, F walks the B forward-branch steps frame by frame, M the B backward branches --
-        multi-map launches for B >= 2, the single-map launch list for B = 1 (one forward() per frame: the first layers of its backward
-        branch, a function of the new frame alone, run with the frame's preparation on P: `bw_head_blocks`) -- then the upsamplers.
+        """B >= 1 windows of this stream on the internal streams (the group form of _pipe_call): P prepares the windows' new frames and
+        flows, F walks the B forward-branch steps frame by frame, M the B backward branches -- multi-map launches for B >= 2, the
+        single-map launch list for B = 1 (one forward() per frame: the first layers of its backward branch, a function of the new frame
+        alone, run with the frame's preparation on P: `bw_head_blocks`) -- then the upsamplers.
         first: wins[0] is a caller's first frame (RefVSR.py:257-258,292-295): its forward branch starts from zeros like a roll-over's, the
         iteration counter restarts.  Returns (results, the windows' vis dicts -- None unless want_vis)."""
         B = len(wins)
         t, _, h, w = wins[0][0].shape
-        ctr, dev = t // 2, wins[0][0].device
         for lrs, refs, _ in wins:
-            self._check_window(lrs, refs)
             assert tuple(lrs.shape) == (t, 3, h, w)
-        if first:
-            # the counter as the roll-over logic wants it: the first window restarts (RefVSR.py:292-295: frame_itr_num = 0, then + 1)
-            self.frame_itr_num = self.max_frame_itr_num if self.max_frame_itr_num is not None else 0
-        else:
-            assert tuple(self.fw_feat.shape[:2]) == (h, w), 'frame size changed without is_first_frame=True'
-        # windows of the group at which the forward branch restarts (reset_branch roll-over, a caller's first frame): their backward
-        # branches are chains like the others', their forward branch is the long one (from zeros over the window's first frames)
-        rst = [bool(self.max_frame_itr_num is not None and self._itr_after(b) == self.max_frame_itr_num) for b in range(B)]
-        if first:
-            rst[0] = True
-        share = tuple(self._pipe_streams(dev))
-        M0, M1, F_, P = share
+
+        def f_step(frs, rst, share, timed):
+            # the forward-branch steps, one frame after the other (the carried state); one hand-over event per window
+            fws, evs = [], []
+            for b, fr in enumerate(frs):
+                self._carried_state_to(share[2], fr, rst[b])
+                fw = self._forward_branch(fr, (lambda a, b_, fr=fr: self.flow(fr[a], fr[b_], share)), t, h, w, rst[b])
+                for x in fw:
+                    x.record_stream(share[0])
+                    x.record_stream(share[1])
+                e = torch.cuda.Event(enable_timing=timed)
+                e.record()
+                fws.append(fw)
+                evs.append(e)
+            return fws, evs
         # B = 1: the backward branch + upsampler of consecutive calls are independent of each other (only the forward branch carries
         # state): calls alternate between the two M streams of the wider models (mid_channels = 24: M0 is M1, see _pipe_streams).
         # Groups stay on one (two M streams alternating between groups: 210.5 vs 220.4 frames/s, profiles/r05_group_knobs_ab.txt)
-        M = M0 if (B > 1 or (self._pipe_calls & 1) == 0) else M1
-        self._pipe_calls += 1
-        self._await_fw_up(self.fw_feat_up)
-        # the host may run at most pipe_depth calls ahead of the GPU (each call in flight holds its intermediates: ~0.3 GB at 270p; a
+        # The host may run at most pipe_depth calls ahead of the GPU (each call in flight holds its intermediates: ~0.3 GB at 270p; a
         # group holds B calls' worth).  Depth 3 since round 4: with 2 the host had ~2.4 ms of slack when it issued a call and a 6 ms
         # hiccup of the host reached the GPU as a gap (profiles/r04_stream_layout_ab.txt)
-        caller = self._pipe_begin([x for lrs, refs, _ in wins for x in (lrs, refs)], input_ready,
-                                  self.pipe_depth if B == 1 else max(1, self.pipe_depth - 1), share)
-        sev = self.stream_events                     # bench.py: per-call (start, end) HIP events of the P / F / M sections
-        mark = (lambda st: None) if sev is None else _timed_event
-        tev = {'n': B}
+        return self._pipe_call([(self, win) for win in wins], [x for lrs, refs, _ in wins for x in (lrs, refs)], input_ready, f_step,
+                               alternate_m=B == 1, depth=self.pipe_depth if B == 1 else max(1, self.pipe_depth - 1), first=first,
+                               want_vis=want_vis, sev=self.stream_events)
+
+    def _carried_state_to(self, F_, fr, restart):
+        """Before a forward-branch step on F: the stream waits for the frames the step reads and owns the carried state."""
+        ctr = len(fr) // 2
+        for f in (fr[:ctr + 2] if restart else (fr[ctr], fr[ctr + 1])):
+            if f.ready is not None:
+                F_.wait_event(f.ready)
+        for x in (self.fw_feat, self.fw_feat_up, self.fw_conf, self.fw_flow):
+            if x is not None:                             # (None: a first frame without a previous clip)
+                x.record_stream(F_)
+
+    def _share_pipe(self, engines):
+        """One set of internal streams, one queue of calls in flight and one call counter for all `engines`: this engine's."""
+        for e in engines:
+            if e is not self:
+                e._layout_default, e._pipe, e._inflight = self._layout_default, self._pipe, self._inflight
+                if self._pipe is not None:
+                    e.pipe_layout, e._pipe_calls = self.pipe_layout, self._pipe_calls
+
+    def _pipe_call(self, lanes, tensors, input_ready, f_step, alternate_m, depth, first=False, want_vis=False, sev=None):
+        """The ONE implementation of the P | F | M schedule, over lanes = [(engine, window (lrs, refs, frame_ids))]: the B
+        consecutive windows of one engine (a frame group; one window: a forward() call) or one window each of n engines (forward_multi).
+        Stream set-up and _pipe_begin over the inputs `tensors`; P: every lane's frames, preparation (_prepare_window) and flows, engine
+        by engine; F: f_step(frs, rst, share, timed) -> (per lane (feat, 2x feat, conf) of its forward-branch step, per lane the event
+        behind which they are final) -- the one section in which the call forms differ; M: the lanes' backward branches step by step
+        (multi-map launches for >= 2 lanes), then each lane's upsampler behind its hand-over event; counters; _pipe_end.
+        alternate_m: consecutive calls alternate between the two M streams; depth: calls in flight; first: lane 0 is a caller's first
+        frame; sev: bench.py's list of per-call section events.  Returns (results, the lanes' vis dicts -- None unless want_vis)."""
+        engines = [e for b, (e, _) in enumerate(lanes) if all(e is not e2 for e2, _ in lanes[:b])]
+        wins = [win for _, win in lanes]
+        t, h, w = self._check_window(wins[0][0], wins[0][1])
+        for lrs, refs, _ in wins[1:]:
+            self._check_window(lrs, refs)
+        ctr, dev = t // 2, wins[0][0].device
+        # lanes at which the forward branch restarts (reset_branch roll-over, a caller's first frame): their backward branches are
+        # chains like the others', their forward branch is the long one (from zeros over the window's first frames)
+        rst = [e._branch_restarts(first and e is lanes[0][0], h, w, ahead=sum(1 for e2, _ in lanes[:b] if e2 is e)) for b, (e, _) in enumerate(lanes)]
+        share = tuple(self._pipe_streams(dev))
+        M0, M1, F_, P = share
+        M = M0 if (not alternate_m or (self._pipe_calls & 1) == 0) else M1
+        self._pipe_calls += 1
+        self._share_pipe(engines)
+        for e in engines:
+            e._await_fw_up(e.fw_feat_up)
+        caller = self._pipe_begin(tensors, input_ready, depth, share)
+        mark = (lambda st: None) if sev is None else _timed_event     # bench.py: per-call (start, end) HIP events of the P / F / M sections
+        tev = {'n': len(lanes)}
         # ---- P: everything that is a function of single frames / frame pairs, for all windows of the call
         with ops.on_stream(P):
             tev['P0'] = mark(P)
             n_ctx = next(_uid)
-            frs = self._frames_group(wins)                        # new frames are cloned here, on P
-            for b, fr in enumerate(frs):
-                # (a group's own preparation computes no backward head: its whole first step is cheaper as multi-map launches)
-                self._prepare_window(fr, 0 if rst[b] else ctr, share, n_ctx, head=B == 1)
-            # the call's new flows in batched SPyNet passes: the backward flows and the forward flow of every window (`held`: kept
-            # until the end of the issue, the cache may trim them)
-            held = self.flows([pr for b, fr in enumerate(frs) for pr in _flow_pairs(fr, rst[b])], share)
+            pend, frs, held = [], [None] * len(lanes), []
+            mine = [[b for b, (e2, _) in enumerate(lanes) if e2 is e] for e in engines]
+            for e, bs in zip(engines, mine):                          # new frames are cloned here, on P
+                for b, fr in zip(bs, e._frames_group([wins[b] for b in bs], pend)):
+                    frs[b] = fr
+            ops.ingest_u8(pend)                                       # (8-bit frames: the call's new frames in one launch)
+            for e, bs in zip(engines, mine):
+                for b in bs:
+                    # (a group's own preparation computes no backward head: its whole first step is cheaper as multi-map launches)
+                    e._prepare_window(frs[b], 0 if rst[b] else ctr, share, n_ctx, head=len(lanes) == 1)
+                # the engine's new flows in batched SPyNet passes: the backward flows and the forward flow of every window (`held`:
+                # kept until the end of the issue, the cache may trim them)
+                held.append(e.flows([pr for b in bs for pr in _flow_pairs(frs[b], rst[b])], share))
             tev['P1'] = mark(P)
-        # ---- F: the forward-branch steps, one frame after the other (the carried state)
-        fws, ev_fw = [], []
+        # ---- F: the forward-branch steps (the carried state)
         with ops.on_stream(F_):
             tev['F0'] = mark(F_)
-            for b, fr in enumerate(frs):
-                for f in (fr[:ctr + 2] if rst[b] else (fr[ctr], fr[ctr + 1])):
-                    if f.ready is not None:
-                        F_.wait_event(f.ready)
-                for x in (self.fw_feat, self.fw_feat_up, self.fw_conf, self.fw_flow):
-                    if x is not None:                             # (None: a first frame without a previous clip)
-                        x.record_stream(F_)
-                fw = self._forward_branch(fr, (lambda a, b_, fr=fr: self.flow(fr[a], fr[b_], share)), t, h, w, rst[b])
-                for x in fw:
-                    x.record_stream(M0)
-                    x.record_stream(M1)
-                e = torch.cuda.Event(enable_timing=sev is not None)
-                e.record()
-                fws.append(fw)
-                ev_fw.append(e)
+            fws, ev_fw = f_step(frs, rst, share, sev is not None)
             tev['F1'] = ev_fw[-1]
-        # ---- M: the B backward branches step by step (B >= 2: multi-map launches), then the upsamplers
+        # ---- M: the backward branches step by step (>= 2 lanes: multi-map launches), then the upsamplers
         outs, vis = [], None
         with ops.on_stream(M):
             tev['M0'] = mark(M)
-            bw_ups, bw_confs = self._backward_chains(frs, lambda b, i: self.flow(frs[b][i], frs[b][i + 1], share), wait=True)
+            bw_ups, bw_confs = self._backward_chains(frs, lambda b, i: lanes[b][0].flow(frs[b][i], frs[b][i + 1], share), wait=True)
             for b, fr in enumerate(frs):
-                M.wait_event(ev_fw[b])
+                if b == 0 or ev_fw[b] is not ev_fw[b - 1]:
+                    M.wait_event(ev_fw[b])
                 outs.append(self.compute_up(bw_ups[b], fws[b][1], bw_confs[b], fws[b][2], fr[ctr].lr))
             if want_vis:
                 # (after the window's compute_up, on M: f.conf is `ready`, fws[b] was waited for above)
                 vis = [self._conf_vis(fr[ctr], bw_confs[b], fws[b][2]) for b, fr in enumerate(frs)]
         del held
-        self.frame_itr_num = self._itr_after(B)                       # (+ B, through the roll-overs inside the group; RefVSR.py:292-295)
+        for b, (e, _) in enumerate(lanes):                            # (through the roll-overs inside a group; RefVSR.py:292-295)
+            e.frame_itr_num = e._itr_after(1, first and b == 0)
         done = self._pipe_end(caller, M, outs, vis, timing=sev is not None)
         if sev is not None:
             tev['M1'] = done
@@ -1382,84 +1405,44 @@ class Engine(object):
         more than REFVSR_MAX_MAPS samples and engines without the multi-map launch list run one forward() per sample."""
         n = len(engines)
         lead = engines[0]
-        if lead.group_ok() and lead.pipelined:
+        group_ok = lead.group_ok()
+        if group_ok and lead.pipelined:
             for e in engines:                       # P | F | M from the first stream on, like an engine driven through forward_group
                 e._layout_default = 'pfm'
-        steady = (not is_first_frame and 2 <= n <= ops.hip.MAX_MAPS and lead.group_ok() and
+        steady = (not is_first_frame and 2 <= n <= ops.hip.MAX_MAPS and group_ok and
                   all(e.pipelined and e.fw_feat is not None and e.W is lead.W and
                       (e.max_frame_itr_num is None or e.frame_itr_num != e.max_frame_itr_num) and
                       tuple(e.fw_feat.shape[:2]) == tuple(lrs.shape[3:]) for e in engines))
-        for e in engines[1:]:                       # one set of internal streams for all samples: the lead's
-            e._layout_default, e._pipe, e._inflight = lead._layout_default, lead._pipe, lead._inflight
-            if lead._pipe is not None:
-                e.pipe_layout, e._pipe_calls = lead.pipe_layout, lead._pipe_calls
+        lead._share_pipe(engines)                   # one set of internal streams for all samples: the lead's
         if not steady:
             outs = []
             for b, e in enumerate(engines):
                 outs.append(e.forward(lrs[b], refs[b], bool(is_first_frame), frame_ids=frame_ids[b], input_ready=input_ready)[0])
-                for e2 in engines:                  # (the lead may just have created the streams)
-                    if e2 is not e:
-                        e2._pipe, e2._inflight = e._pipe, e._inflight
-                        if e._pipe is not None:
-                            e2.pipe_layout, e2._pipe_calls = e.pipe_layout, e._pipe_calls
+                e._share_pipe(engines)              # (the lead may just have created the streams)
             return outs
         with torch.cuda.device(lrs.device):
             return lead._forward_multi_pipelined(engines, lrs, refs, frame_ids, input_ready)
 
     def _forward_multi_pipelined(self, engines, lrs, refs, frame_ids, input_ready):
-        n, t = lrs.shape[:2]
-        ctr, dev = t // 2, lrs.device
-        for b in range(n):
-            self._check_window(lrs[b], refs[b])
-        share = tuple(self._pipe_streams(dev))
-        M0, M1, F_, P = share
-        self._pipe_calls += 1
-        for e in engines:
-            e._pipe, e.pipe_layout, e._pipe_calls = self._pipe, self.pipe_layout, self._pipe_calls
-            e._await_fw_up(e.fw_feat_up)
-        caller = self._pipe_begin((lrs, refs), input_ready, self.pipe_depth, share)
-        # ---- P: per-sample preparation of the new frames and flows
-        frs = []
-        with ops.on_stream(P):
-            n_ctx = next(_uid)
-            if lrs.dtype == torch.uint8:
-                # 8-bit frames: every sample's new frames in one ingest launch before any preparation
-                pend = []
-                frs = [e._frames(lrs[b], refs[b], frame_ids[b], pend) for b, e in enumerate(engines)]
-                ops.ingest_u8(pend)
-            for b, e in enumerate(engines):
-                if len(frs) == b:
-                    frs.append(e._frames(lrs[b], refs[b], frame_ids[b]))
-                e._prepare_window(frs[b], ctr, share, n_ctx)
-                e.flows(_flow_pairs(frs[b], False), share)
-        # ---- F: the forward-branch step of all samples as multi-map launches
-        with ops.on_stream(F_):
+        """The multi-sample form of _pipe_call: the forward-branch step of all samples as ONE multi-map _prop_step, one hand-over event."""
+        ctr = lrs.shape[1] // 2
+
+        def f_step(frs, rst, share, timed):
             for e, fr in zip(engines, frs):
-                for f in (fr[ctr], fr[ctr + 1]):
-                    if f.ready is not None:
-                        F_.wait_event(f.ready)
-                for x in (e.fw_feat, e.fw_feat_up, e.fw_conf, e.fw_flow):
-                    x.record_stream(F_)
-            fw_feat, fw_up, fw_conf = self._prop_step([fr[ctr] for fr in frs], 'forward_resblocks', [e.fw_feat for e in engines],
-                                                        [e.fw_feat_up for e in engines], [e.fw_conf for e in engines],
-                                                        [e.fw_flow for e in engines])
+                e._carried_state_to(share[2], fr, False)
+            fw = self._prop_step([fr[ctr] for fr in frs], 'forward_resblocks', [e.fw_feat for e in engines],
+                                 [e.fw_feat_up for e in engines], [e.fw_conf for e in engines], [e.fw_flow for e in engines])
             for b, (e, fr) in enumerate(zip(engines, frs)):                               # RefVSR.py:279-283
-                e.fw_feat, e.fw_feat_up, e.fw_conf = fw_feat[b], fw_up[b], fw_conf[b]
+                e.fw_feat, e.fw_feat_up, e.fw_conf = fw[0][b], fw[1][b], fw[2][b]
                 e.fw_flow = e.flow(fr[ctr + 1], fr[ctr], share)
-            for x in list(fw_up) + list(fw_conf):
-                x.record_stream(M0)
-                x.record_stream(M1)
-            ev_fw = torch.cuda.Event()
-            ev_fw.record()
-        # ---- M: the backward branches of all samples step by step as multi-map launches, then the upsamplers
-        with ops.on_stream(M0):
-            bw_ups, bw_confs = self._backward_chains(frs, lambda b, i: engines[b].flow(frs[b][i], frs[b][i + 1], share), wait=True)
-            M0.wait_event(ev_fw)
-            outs = [self.compute_up(bw_ups[b], fw_up[b], bw_confs[b], fw_conf[b], fr[ctr].lr) for b, fr in enumerate(frs)]
-        for e in engines:
-            e.frame_itr_num += 1
-        self._pipe_end(caller, M0, outs)
-        return outs
+            for x in list(fw[1]) + list(fw[2]):
+                x.record_stream(share[0])
+                x.record_stream(share[1])
+            ev = torch.cuda.Event()
+            ev.record()
+            return list(zip(*fw)), [ev] * len(frs)
+        return self._pipe_call([(e, (lrs[b], refs[b], frame_ids[b])) for b, e in enumerate(engines)], (lrs, refs), input_ready, f_step,
+                               alternate_m=False, depth=self.pipe_depth)[0]
 
     def _side_stream(self, dev):
         """The one side stream of the sequential path (the forward-branch step under the new frame's preparation)."""
@@ -1591,24 +1574,7 @@ class Engine(object):
         shard.run_wavefront: every rank runs phase A of all its frames concurrently, then the ranks run phase B one
         after the other along the state hand-off chain.  first_hint: the call is expected to be a first frame / reset
         frame, prepare frames 0..ctr-1 now instead of lazily in phase B."""
-        t, h, w = self._check_window(lrs, refs)
-        ctr, dev = t // 2, lrs.device
-        with torch.cuda.device(dev), ops.on_stream(torch.cuda.current_stream(dev)):
-            zero_flow = torch.zeros((2, h, w), dtype=torch.float32, device=dev) if bool(self.cfg.EVAL.is_gradio) else None
-            fr = self._frames(lrs, refs, frame_ids)
-            flow = (lambda a, b: zero_flow) if zero_flow is not None else (lambda a, b: self.flow(fr[a], fr[b]))
-            if zero_flow is None:
-                self.flows(_flow_pairs(fr, first_hint))
-            for i in range(0 if first_hint else ctr, t):
-                self.prepare_frame(fr[i])
-            [bw_up], [conf_bw] = self._backward_chains([fr], lambda b, i: flow(i, i + 1))
-            # the flows the forward branch will ask for, computed here (parallel phase) and pinned in the handle: the
-            # flow cache only keeps pairs of the current window
-            flows = {(ctr + 1, ctr): flow(ctr + 1, ctr)}
-            if first_hint:
-                for i in range(1, ctr + 1):
-                    flows[(i, i - 1)] = flow(i, i - 1)
-        return dict(fr=fr, flows=flows, zero_flow=zero_flow, bw_up=bw_up, conf_bw=conf_bw, t=t, h=h, w=w)
+        return self._phase_a([(lrs, refs, frame_ids)], [bool(first_hint)])[0]
 
     @torch.no_grad()
     def phase_a_group(self, wins, first_hints=None, streams=None):
@@ -1617,7 +1583,7 @@ class Engine(object):
         independent chains over identical weights (RefVSR.py:211-238 restarts from zeros in every window) and run as multi-map launches
         (_prop_step: one launch per layer over B maps, the launch list of a frame group's M section), every flow the B windows ask for
         comes out of batched SPyNet passes.  Returns the B handles phase_a would return, bit for bit
-        (tests/test_gpu_e2e.py::test_phase_a_group_equals_phase_a); engines without the multi-map launch list run phase_a per window.
+        (tests/test_gpu_e2e.py::test_phase_a_group_equals_phase_a); engines without the multi-map launch list run window by window.
         streams=None: everything on the current stream, like phase_a.
         streams=(M, consumers): the stream layout of a frame group for the sharded executor -- the per-frame preparation and
         the flows on the CURRENT stream (the executor's lane a = P), the backward chains on M behind per-frame / per-flow events, so that
@@ -1626,9 +1592,17 @@ class Engine(object):
         B = len(wins)
         hints = [False] * B if first_hints is None else [bool(v) for v in first_hints]
         if B > ops.hip.MAX_MAPS or not self.group_ok() or (B == 1 and streams is None):
-            return [self.phase_a(lrs, refs, ids, hints[b]) for b, (lrs, refs, ids) in enumerate(wins)]
+            return [self._phase_a([win], [hints[b]])[0] for b, win in enumerate(wins)]
+        return self._phase_a(wins, hints, streams, grouped=True)
+
+    def _phase_a(self, wins, hints, streams=None, grouped=False):
+        """The one body of phase A, for B >= 1 windows: frames -> flows -> preparation -> backward chains -> the pinned forward flows ->
+        handles.  Takes the gradio mode (zero flows), a window without frame ids (B = 1: frames recognised by content) and engines
+        without the group schedule (B = 1).  grouped: phase_a_group's schedule -- the preparation BEFORE the flows (one batched SPyNet
+        pass over every flow the B windows ask for) and the chains in a stream section of their own, on streams[0] when `streams` is
+        given (then the preparation is _prepare_window's, published for those streams); else phase_a's: flows first, one section."""
         t, h, w = self._check_window(wins[0][0], wins[0][1])
-        for lrs, refs, ids in wins:
+        for lrs, refs, ids in wins if grouped else ():
             assert self._check_window(lrs, refs) == (t, h, w) and ids is not None, 'a group needs windows of one geometry, named by frame ids'
         ctr, dev = t // 2, wins[0][0].device
         P = torch.cuda.current_stream(dev)
@@ -1636,19 +1610,49 @@ class Engine(object):
         if streams is not None:
             M = streams[0]
             share = [P, M] + [st for st in streams[1] if st is not P and st is not M]
+        gradio = bool(self.cfg.EVAL.is_gradio)
+        zero_flow = fl_all = done_p = None
+
+        def flow(fr, a, b):
+            return zero_flow if gradio else self.flow(fr[a], fr[b], share)
+
+        def chains():
+            ready = None
+            if share is not None:
+                M.wait_event(done_p)                               # (everything this group reads was produced on P before this point)
+                for fl in fl_all:
+                    fl.record_stream(M)
+            bw_ups, bw_confs = self._backward_chains(frs, lambda b, i: flow(frs[b], i, i + 1))
+            if share is not None:
+                ready = torch.cuda.Event()
+                ready.record()
+            out = []
+            for b, fr in enumerate(frs):
+                # the flows the forward branch will ask for, computed here (parallel phase) and pinned in the handle: the
+                # flow cache only keeps pairs of the current window
+                flows = {(ctr + 1, ctr): flow(fr, ctr + 1, ctr)}
+                if hints[b]:
+                    for i in range(1, ctr + 1):
+                        flows[(i, i - 1)] = flow(fr, i, i - 1)
+                out.append(dict(fr=fr, flows=flows, zero_flow=zero_flow, bw_up=bw_ups[b], conf_bw=bw_confs[b], t=t, h=h, w=w, ready=ready,
+                                bw_flows=fl_all if share is not None else None))     # (alive until the executor's final synchronisation)
+            return out
         with torch.cuda.device(dev), ops.on_stream(P):
+            if gradio:
+                zero_flow = torch.zeros((2, h, w), dtype=torch.float32, device=dev)
             frs = self._frames_group(wins)
             need = [pr for b, fr in enumerate(frs) for pr in _flow_pairs(fr, hints[b])]
+            if not grouped and not gradio:
+                self.flows(need)
             for b, fr in enumerate(frs):
-                for i in range(0 if hints[b] else ctr, t):
-                    self.prepare_frame(fr[i])
-                    if share is not None and fr[i].ready is None:
-                        # (also contexts prepared / imported ahead on this stream: safe on the other streams from here on)
-                        if fr[i].pyr is None:
-                            self.pyramid(fr[i])
-                        self._publish(fr[i], share)
-                        fr[i].ready = torch.cuda.Event()
-                        fr[i].ready.record()
+                if share is not None:
+                    # (also contexts prepared / imported ahead on this stream: safe on the other streams from here on)
+                    self._prepare_window(fr, 0 if hints[b] else ctr, share, pyramid_first=False, ready_if_prepared=True)
+                else:
+                    for i in range(0 if hints[b] else ctr, t):
+                        self.prepare_frame(fr[i])
+            if not grouped:
+                return chains()
             fl_all = self.flows(need, share)
             if share is not None:
                 for fr in frs:                                     # frames a window merely contains: their copies are read by nobody else
@@ -1659,24 +1663,7 @@ class Engine(object):
                 done_p = torch.cuda.Event()
                 done_p.record()
         with torch.cuda.device(dev), ops.on_stream(M):
-            if share is not None:
-                M.wait_event(done_p)                               # (everything this group reads was produced on P before this point)
-                for fl in fl_all:
-                    fl.record_stream(M)
-            feat_ups, confs = self._backward_chains(frs, lambda b, i: self.flow(frs[b][i], frs[b][i + 1], share))
-            ready = None
-            if share is not None:
-                ready = torch.cuda.Event()
-                ready.record()
-            out = []
-            for b, fr in enumerate(frs):
-                flows = {(ctr + 1, ctr): self.flow(fr[ctr + 1], fr[ctr], share)}
-                if hints[b]:
-                    for i in range(1, ctr + 1):
-                        flows[(i, i - 1)] = self.flow(fr[i], fr[i - 1], share)
-                out.append(dict(fr=fr, flows=flows, zero_flow=None, bw_up=feat_ups[b], conf_bw=confs[b], t=t, h=h, w=w, ready=ready,
-                                bw_flows=fl_all if share is not None else None))     # (alive until the executor's final synchronisation)
-        return out
+            return chains()
 
     @torch.no_grad()
     def phase_b1(self, pa, is_first_frame):
@@ -1684,34 +1671,40 @@ class Engine(object):
         counter (:292-295).  Must be called in frame order; leaves the step's outputs in the handle for phase_b2.  The
         multi-GPU wavefront runs B1 of all local frames, hands the state over, and only then runs the upsamplers (B2), so
         that the serial chain over the ranks carries nothing but the forward-branch steps."""
-        fr, t, h, w = pa['fr'], pa['t'], pa['h'], pa['w']
-        ctr = t // 2
-        is_first_frame = self._branch_restarts(is_first_frame, h, w)
+        fr = pa['fr']
+        restart = self._branch_restarts(is_first_frame, pa['h'], pa['w'])
         with ops.on_stream(torch.cuda.current_stream()):
             def flow(a, b):
                 if pa['zero_flow'] is not None:
                     return pa['zero_flow']
                 hit = pa['flows'].get((a, b))
                 return hit if hit is not None else self.flow(fr[a], fr[b])
-            if is_first_frame:
-                for i in range(0, ctr):
+            if restart:
+                for i in range(0, pa['t'] // 2):
                     self.prepare_frame(fr[i])                  # no-op when phase A had the hint
-            _, feat_up, conf = self._forward_branch(fr, flow, t, h, w, is_first_frame)
-            if is_first_frame:                                                      # :292-295
-                self.frame_itr_num = 0
-            self.frame_itr_num += 1
-        pa['fw_up'], pa['conf_fw'] = feat_up, conf
+            self._b1(pa, flow, restart)
         return pa
+
+    def _b1(self, pa, flow, restart):
+        """The forward-branch step of a handle on the current stream and the iteration counter (RefVSR.py:240-283,292-295); leaves the
+        step's outputs in the handle and returns them."""
+        fw = self._forward_branch(pa['fr'], flow, pa['t'], pa['h'], pa['w'], restart)
+        self.frame_itr_num = self._itr_after(1, restart)
+        pa['fw_up'], pa['conf_fw'] = fw[1:]
+        return fw
+
+    def _b2(self, pa, want_vis):
+        """BW/FW fusion + upsampler (RefVSR.py:288-297) of a handle on the current stream, and the eval `vis` maps when asked for."""
+        f = pa['fr'][pa['t'] // 2]
+        out = self.compute_up(pa['bw_up'], pa['fw_up'], pa['conf_bw'], pa['conf_fw'], f.lr)
+        return out, (self._conf_vis(f, pa['conf_bw'], pa['conf_fw']) if want_vis else None)
 
     @torch.no_grad()
     def phase_b2(self, pa, want_vis=False):
         """BW/FW fusion + upsampler (RefVSR.py:288-297) of a frame whose phase_b1 has run: independent of the carried state
         and of the other frames."""
-        fr, ctr = pa['fr'], pa['t'] // 2
         with ops.on_stream(torch.cuda.current_stream()):
-            out = self.compute_up(pa['bw_up'], pa['fw_up'], pa['conf_bw'], pa['conf_fw'], fr[ctr].lr)
-            vis = self._conf_vis(fr[ctr], pa['conf_bw'], pa['conf_fw']) if want_vis else None
-        return out, vis
+            return self._b2(pa, want_vis)
 
     @torch.no_grad()
     def phase_b(self, pa, is_first_frame, want_vis=False, after_state=None):
@@ -1723,11 +1716,14 @@ class Engine(object):
             after_state()
         return self.phase_b2(pa, want_vis)
 
-    def _branch_restarts(self, is_first_frame, h, w):
-        """Whether a call restarts the forward branch (a caller's first frame or a reset_branch roll-over, RefVSR.py:168-170); a call
-        that does not must find a carried state of its frame size."""
-        if self.max_frame_itr_num is not None and self.frame_itr_num == self.max_frame_itr_num:
-            is_first_frame = True
+    def _branch_restarts(self, is_first_frame, h, w, ahead=0):
+        """Whether the window `ahead` windows from now restarts the forward branch: the next window when it is a caller's first frame
+        (is_first_frame), any window at a reset_branch roll-over (RefVSR.py:168-170).  A next window that does not restart must find a
+        carried state of its frame size."""
+        is_first_frame = bool(is_first_frame and ahead == 0) or (self.max_frame_itr_num is not None and
+                                                                 self._itr_after(ahead, is_first_frame) == self.max_frame_itr_num)
+        if ahead > 0:
+            return is_first_frame
         if not is_first_frame and self.fw_feat is None:
             raise RuntimeError('is_first_frame=False but no forward state is held (first call of a stream '
                                'must pass is_first_frame=True, cf. RefVSR.py:257-258)')
@@ -1811,6 +1807,7 @@ class Engine(object):
         if not gradio and t > 1:
             # every flow this call consumes, in one batched SPyNet pass before the streams fork (cached pairs cost nothing)
             self.flows(_flow_pairs(fr, is_first_frame), share)
+        pa = dict(fr=fr, t=t, h=h, w=w)                    # the call as phase A + B1 + B2 on one handle
         if overlap:
             for i in range(ctr, t):
                 self.pyramid(fr[i])                        # shared by both streams: build on main before the fork
@@ -1819,26 +1816,18 @@ class Engine(object):
             with ops.on_stream(side):
                 for x in (self.fw_feat, self.fw_feat_up, self.fw_conf, self.fw_flow):
                     x.record_stream(side)
-                fw = self._forward_branch(fr, flow, t, h, w, False)
+                fw = self._b1(pa, flow, False)
         for i in range(range_start, t):                                             # :196-204 (+ per-frame RAP parts)
             self.prepare_frame(fr[i])
-
-        [bw_up], [conf_bw] = self._backward_chains([fr], lambda b, i: flow(i, i + 1))
-
-        # ---- forward branch (:240-283)
+        [pa['bw_up']], [pa['conf_bw']] = self._backward_chains([fr], lambda b, i: flow(i, i + 1))
         if overlap:
             main.wait_stream(side)
             for x in fw:
                 x.record_stream(main)
         else:
-            fw = self._forward_branch(fr, flow, t, h, w, is_first_frame)
-        feat, feat_up, conf = fw
-        out = self.compute_up(bw_up, feat_up, conf_bw, conf, fr[ctr].lr)            # :288-289,297
-        if is_first_frame:                                                          # :292-295
-            self.frame_itr_num = 0
-        self.frame_itr_num += 1
-        vis = self._conf_vis(fr[ctr], conf_bw, conf) if want_vis else None
+            self._b1(pa, flow, is_first_frame)                                      # :240-283,292-295
+        out, vis = self._b2(pa, want_vis)                                           # :288-289,297
         if want_log:
-            dbg = self._debug_vis(fr, t, is_first_frame, range_start, fw_flow_in, flow, conf_bw, conf, want_vis)
+            dbg = self._debug_vis(fr, t, is_first_frame, range_start, fw_flow_in, flow, pa['conf_bw'], pa['conf_fw'], want_vis)
             return out, (vis, dbg)
         return out, vis

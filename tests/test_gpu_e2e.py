@@ -460,6 +460,36 @@ def test_two_phase_forward_is_bit_identical(dev):
                 assert torch.equal(got, want[f]), '%s: two-phase frame %d differs (hinted=%s)' % (name, f, hinted)
 
 
+def test_gradio_mode_call_forms_are_bit_identical(dev):
+    """EVAL.is_gradio (zero flows, RefVSR.py:183-191): the sequential stream, the same stream through phase_a + phase_b and the same
+    stream through a pipelined module with frame ids (the reference order on M) give the same frames bit for bit."""
+    from refvsr_amd.synth import make_clip, window_indices
+    nfr, t = 5, 3
+    lr, rf, _ = make_clip(nfr, 32, 48, seed=17)
+    lr, rf = lr.to(dev), rf.to(dev)
+    wins = [window_indices(f, nfr, t) for f in range(nfr)]
+
+    def gradio_net():
+        net, cfg, _ = make_net('config_RefVSR_small_L1', t, dev, save_sample=False)
+        cfg.EVAL.is_gradio = True
+        return net
+    net = gradio_net()
+    want = [net(lr[w][None], rf[w][None], f == 0)['result'].clone() for f, w in enumerate(wins)]
+    plain, _, _ = make_net('config_RefVSR_small_L1', t, dev, save_sample=False)
+    assert not torch.equal(plain(lr[wins[0]][None], rf[wins[0]][None], True)['result'], want[0]), 'the gradio mode changed nothing'
+    net = gradio_net()
+    for f, w in enumerate(wins):
+        h = net.Network.phase_a(lr[w][None], rf[w][None], frame_ids=w)
+        assert torch.equal(net.Network.phase_b(h, f == 0)['result'], want[f]), 'gradio: two-phase frame %d differs' % f
+    net = gradio_net()
+    net.Network.set_pipelined(True)
+    outs = [net(lr[w][None].contiguous(), rf[w][None].contiguous(), f == 0, frame_ids=w)['result'] for f, w in enumerate(wins)]
+    torch.cuda.synchronize()
+    assert net.Network.engine(0).takes_pipelined_path(wins[0])
+    for f in range(nfr):
+        assert torch.equal(outs[f], want[f]), 'gradio: pipelined frame %d differs' % f
+
+
 def test_phase_a_group_equals_phase_a(dev):
     """Engine.phase_a_group (round 6: phase A of several windows of a clip in one pass -- batched SPyNet, the backward branches as
     multi-map launches; what shard.run_wavefront(group=) runs on lane a) returns the handles phase_a returns: the upsampled frames
