@@ -145,6 +145,16 @@ enum {
  * PROBE << 6 | TH << 7 | STORE << 12 | HEAD << 13 | WF << 14. */
 int refvsr_conv24_variant(int op, int x0, int x1, int mm, int wf, int batch, int h, int w, long long* key, int* n_tiles, int* lds);
 int refvsr_resblock24_variant(int head, int wf, int relu, int batch, int h, int w, void* stream, int* key, int* n_tiles, int* lds);
+/* The same for the two other fused-block kernels (added symbols, ABI 15 unchanged).  refvsr_resblock48_variant: which
+ * resblock48_kernel<RELU, PROBE> a refvsr_resblock48_chain* launch over `batch` maps would run right now, as RELU | PROBE << 1 (RELU =
+ * act_slope == 0; PROBE = a probe buffer is set (refvsr_set_probe) AND RELU: the leaky kernel has no probe form).
+ * refvsr_resblock_lean_variant: which resblock_lean_kernel<MT, WIDE, NWV> refvsr_resblock_lean / refvsr_resblock_chain would run on
+ * c-channel maps under refvsr_set_resblock_waves, as MT | WIDE << 2 | NWV << 3.  n_tiles, lds (dynamic LDS bytes) and grid (the
+ * workgroups a launch on `stream` would get: min(n_tiles, CUs of the stream x occupancy, a multiple of 8, at least 8)) are optional.
+ * The launchers plan through the same function.  With grid == NULL the query is host only (no launch, no refvsr_init); with it the
+ * kernel's LDS attribute is set and, for the lean kernel, the runtime is asked for its occupancy, as at a launch. */
+int refvsr_resblock48_variant(float act_slope, int batch, int h, int w, void* stream, int* key, int* n_tiles, int* grid, int* lds);
+int refvsr_resblock_lean_variant(int c, int h, int w, void* stream, int* key, int* n_tiles, int* grid, int* lds);
 /* Packing contract of `wpack` (host-side helpers, no GPU needed): K-slot of K-block (ty, tx, cg) of a ks x ks conv over
  * ncg 16-byte channel groups, and the number of 4-slot K-steps; refvsr_amd/packing.py:kslot/ksteps are the same closed
  * forms and tests/test_capi.py pins the two against each other.  Return the value (>= 0), not a status. */

@@ -378,15 +378,57 @@ __global__ __launch_bounds__(R48_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) 
 extern unsigned long long* g_rb_probe;             // runtime.hip: refvsr_set_probe
 extern int g_rb_probe_iter;
 
-template <bool RELU, bool PROBE = false>
-static int launch_rb48(RB48Args& a, hipStream_t st) {
+// every instantiation X(RELU, PROBE), written down once
+#define R48_VARIANTS(X) X(false, false) X(true, false) X(true, true)
+constexpr int r48_variant_key(bool relu, bool probe) { return (int)relu | (int)probe << 1; }
+
+// grid cap of one instantiation on `st` (one 135 KB workgroup per CU) and the instantiation's one-time set-up
+template <bool RELU, bool PROBE>
+static int rb48_cap(hipStream_t st, int* cap) {
     static RvLaunchCap lc = {};
-    int cap;                                                              // one 135 KB workgroup per CU
-    if (int rc = rv_launch_cap(lc, &resblock48_kernel<RELU, PROBE>, 0, R48_LDS, R48_LDS, st, &cap)) return rc;
-    a.tiles_x = rv_cdiv(a.w, R48_TW);
-    a.tpm = a.tiles_x * rv_cdiv(a.h, R48_TH);
-    a.n_tiles = a.tpm * (a.batch > 1 ? a.batch : 1);
-    a.grid = a.n_tiles < cap ? a.n_tiles : cap;
+    return rv_launch_cap(lc, &resblock48_kernel<RELU, PROBE>, 0, R48_LDS, R48_LDS, st, cap);
+}
+
+// The plan of a launch on `st` at this moment: the instantiation (the probe kernel where a probe buffer is set; it exists for ReLU
+// only: tools/probe_resblock48.py), the tiles and -- want_grid -- the workgroups.  The launcher and the query below both come through
+// here.
+struct Rb48Plan { int key, tiles_x, tpm, n_tiles, grid; };
+static int rb48_plan_now(float act_slope, int batch, int h, int w, hipStream_t st, bool want_grid, Rb48Plan* p) {
+    const bool relu = act_slope == 0.f;
+    p->key = r48_variant_key(relu, relu && g_rb_probe != nullptr);
+    p->tiles_x = rv_cdiv(w, R48_TW);
+    p->tpm = p->tiles_x * rv_cdiv(h, R48_TH);
+    p->n_tiles = p->tpm * (batch > 1 ? batch : 1);
+    p->grid = 0;
+    if (!want_grid) return 0;
+    int cap = 0, rc = 1;
+    switch (p->key) {                                                     // key and kernel of a case come from the same list entry
+#define R48_CASE(...) case r48_variant_key(__VA_ARGS__): rc = rb48_cap<__VA_ARGS__>(st, &cap); break;
+        R48_VARIANTS(R48_CASE)
+#undef R48_CASE
+    }
+    if (rc) return rc;
+    p->grid = p->n_tiles < cap ? p->n_tiles : cap;
+    return 0;
+}
+
+// Test query (refvsr_hip.h): no launch; grid == nullptr: host only
+extern "C" int refvsr_resblock48_variant(float act_slope, int batch, int h, int w, void* stream, int* key, int* n_tiles, int* grid, int* lds) {
+    RV_CHECK(key != nullptr, "resblock48_variant: null key");
+    RV_CHECK(act_slope >= 0.f && act_slope <= 1.f && h > 0 && w > 0 && batch >= 1 && batch <= REFVSR_MAX_MAPS, "resblock48_variant: bad args");
+    if (grid) RV_CHECK(refvsr_init() == 0, "init failed");
+    Rb48Plan p;
+    if (int rc = rb48_plan_now(act_slope, batch, h, w, (hipStream_t)stream, grid != nullptr, &p)) return rc;
+    *key = p.key;
+    if (n_tiles) *n_tiles = p.n_tiles;
+    if (grid) *grid = p.grid;
+    if (lds) *lds = R48_LDS;
+    return 0;
+}
+
+template <bool RELU, bool PROBE>
+static int launch_rb48(RB48Args& a, const Rb48Plan& p, hipStream_t st) {
+    a.tiles_x = p.tiles_x; a.tpm = p.tpm; a.n_tiles = p.n_tiles; a.grid = p.grid;
     hipLaunchKernelGGL((resblock48_kernel<RELU, PROBE>), dim3(a.grid), dim3(R48_NT), R48_LDS, st, a);
     RV_LAUNCH_CHECK();
     return 0;
@@ -398,8 +440,15 @@ static int rb48_chain_impl(const void* const* src, int batch, int h, int w, int 
                            void* scratch0, void* scratch1, void* const* out, void* stream) {
     const auto launch = [=](RB48Args& a, hipStream_t st) -> int {
         a.probe = g_rb_probe; a.probe_iter = g_rb_probe_iter;
-        return (g_rb_probe && act_slope == 0.f) ? launch_rb48<true, true>(a, st)       // tools/probe_resblock48.py
-               : act_slope == 0.f ? launch_rb48<true>(a, st) : launch_rb48<false>(a, st);
+        Rb48Plan p;
+        if (int rc = rb48_plan_now(a.act_slope, a.batch, a.h, a.w, st, true, &p)) return rc;
+        switch (p.key) {
+#define R48_CASE(...) case r48_variant_key(__VA_ARGS__): return launch_rb48<__VA_ARGS__>(a, p, st);
+            R48_VARIANTS(R48_CASE)
+#undef R48_CASE
+        }
+        refvsr_set_error("resblock48_chain: no kernel for key %d", p.key);
+        return 1;
     };
     return rv_resblock_chain<RB48Args>("resblock48_chain", R48_GPX, R48_BLOB, src, batch, h, w, n, blobs, blob_stride, act_slope, scratch0,
                                        scratch1, out, stream, launch);

@@ -369,22 +369,64 @@ extern "C" int refvsr_set_resblock_waves(int waves) {
     return 0;
 }
 
+// every instantiation X(MT, WIDE, NWV), written down once.  (MT = 1 is c <= 16: at most two channel groups, 72 chunk slots per
+// staged row -- never WIDE: tests/test_block_variant_cases.py asks the query below for every c that fits.)
+#define RL_VARIANTS(X) X(1, false, 8) X(2, false, 8) X(2, true, 8) X(1, false, 4) X(2, false, 4) X(2, true, 4)
+constexpr int rl_variant_key(int MT, bool wide, int waves) { return MT | (int)wide << 2 | waves << 3; }
+
+// grid cap of one instantiation with `lds` bytes on `st` and the instantiation's one-time set-up
 template <int MT, bool WIDE, int NWV>
-static int launch_lean(ResLeanArgs& a, size_t lds, hipStream_t st) {
+static int rl_cap(size_t lds, hipStream_t st, int* cap) {
     static RvLaunchCap lc = {};
-    int cap;
-    if (int rc = rv_launch_cap(lc, &resblock_lean_kernel<MT, WIDE, NWV>, NWV * 64, 160 * 1024, lds, st, &cap)) return rc;
-    const int gx = a.n_tiles < cap ? a.n_tiles : cap;
-    a.grid = gx;
-    hipLaunchKernelGGL((resblock_lean_kernel<MT, WIDE, NWV>), dim3(gx), dim3(NWV * 64), lds, st, a);
-    RV_LAUNCH_CHECK();
+    return rv_launch_cap(lc, &resblock_lean_kernel<MT, WIDE, NWV>, NWV * 64, 160 * 1024, lds, st, cap);
+}
+
+// The launch of a c-channel block on `st` at this moment: the carve, the instantiation under refvsr_set_resblock_waves, the tiles
+// and -- want_grid -- the workgroups.  The launcher and the query below both come through here.
+struct RlLaunch { RlPlan p; int key, tiles_x, n_tiles, grid; };
+static int rl_plan_now(int c, int h, int w, hipStream_t st, bool want_grid, RlLaunch* l) {
+    l->p = rl_plan(c);
+    l->key = rl_variant_key(l->p.MT, l->p.wide, g_lean_waves);
+    l->tiles_x = rv_cdiv(w, RL_TW);
+    l->n_tiles = l->tiles_x * rv_cdiv(h, RL_TH);
+    l->grid = 0;
+    int cap = 0, rc = -1;
+    switch (l->key) {                                             // key and kernel of a case come from the same list entry
+#define RL_CASE(...) case rl_variant_key(__VA_ARGS__): rc = want_grid ? rl_cap<__VA_ARGS__>(l->p.lds, st, &cap) : 0; break;
+        RL_VARIANTS(RL_CASE)
+#undef RL_CASE
+    }
+    if (rc < 0) {
+        refvsr_set_error("resblock_lean: no kernel for MT=%d wide=%d waves=%d", l->p.MT, (int)l->p.wide, g_lean_waves);
+        return 1;
+    }
+    if (rc) return rc;
+    if (want_grid) l->grid = l->n_tiles < cap ? l->n_tiles : cap;
     return 0;
 }
 
-// every instantiation X(MT, WIDE, NWV), written down once
-#define RL_VARIANTS(X)                                                             \
-    X(1, false, 8) X(2, false, 8) X(1, true, 8) X(2, true, 8) X(1, false, 4) X(2, false, 4) X(1, true, 4) X(2, true, 4)
-constexpr int rl_variant_key(int MT, bool wide, int waves) { return MT | (int)wide << 2 | waves << 3; }
+// Test query (refvsr_hip.h): no launch; grid == nullptr: host only
+extern "C" int refvsr_resblock_lean_variant(int c, int h, int w, void* stream, int* key, int* n_tiles, int* grid, int* lds) {
+    RV_CHECK(key != nullptr, "resblock_lean_variant: null key");
+    RV_CHECK(h > 0 && w > 0, "resblock_lean_variant: bad args");
+    RV_CHECK(refvsr_resblock_lean_fits(c), "resblock_lean: channel count %d not supported by the fused kernel", c);
+    if (grid) RV_CHECK(refvsr_init() == 0, "init failed");
+    RlLaunch l;
+    if (int rc = rl_plan_now(c, h, w, (hipStream_t)stream, grid != nullptr, &l)) return rc;
+    *key = l.key;
+    if (n_tiles) *n_tiles = l.n_tiles;
+    if (grid) *grid = l.grid;
+    if (lds) *lds = (int)l.p.lds;
+    return 0;
+}
+
+template <int MT, bool WIDE, int NWV>
+static int launch_lean(ResLeanArgs& a, const RlLaunch& l, hipStream_t st) {
+    a.tiles_x = l.tiles_x; a.n_tiles = l.n_tiles; a.grid = l.grid;
+    hipLaunchKernelGGL((resblock_lean_kernel<MT, WIDE, NWV>), dim3(a.grid), dim3(NWV * 64), l.p.lds, st, a);
+    RV_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int refvsr_resblock_lean(const void* src, int c, int h, int w, const void* w1, const float* b1,
                                     const void* w2, const float* b2, int ksteps, float act_slope, float post_slope,
@@ -395,7 +437,9 @@ extern "C" int refvsr_resblock_lean(const void* src, int c, int h, int w, const 
     RV_CHECK(act_slope >= 0.f && act_slope <= 1.f && post_slope >= 0.f && post_slope <= 1.f,
              "resblock_lean: activation slopes must lie in [0, 1]");
     RV_CHECK(refvsr_init() == 0, "init failed");
-    const RlPlan p = rl_plan(c);
+    RlLaunch l;
+    if (int rc = rl_plan_now(c, h, w, (hipStream_t)stream, true, &l)) return rc;
+    const RlPlan& p = l.p;
     RV_CHECK(p.S == ksteps, "resblock_lean: ksteps mismatch (%d vs %d)", ksteps, p.S);
     ResLeanArgs a;
     memset(&a, 0, sizeof(a));
@@ -407,10 +451,8 @@ extern "C" int refvsr_resblock_lean(const void* src, int c, int h, int w, const 
     a.act_slope = act_slope; a.post_slope = post_slope;
     a.probe = g_rb_probe; a.probe_iter = g_rb_probe_iter;
     a.tab_bytes = p.tab_bytes; a.w_bytes = p.w_bytes;
-    a.tiles_x = rv_cdiv(w, RL_TW);
-    a.n_tiles = a.tiles_x * rv_cdiv(h, RL_TH);
-    switch (rl_variant_key(p.MT, p.wide, g_lean_waves)) {         // key and launcher of a case come from the same list entry
-#define RL_CASE(...) case rl_variant_key(__VA_ARGS__): return launch_lean<__VA_ARGS__>(a, p.lds, (hipStream_t)stream);
+    switch (l.key) {                                              // key and launcher of a case come from the same list entry
+#define RL_CASE(...) case rl_variant_key(__VA_ARGS__): return launch_lean<__VA_ARGS__>(a, l, (hipStream_t)stream);
         RL_VARIANTS(RL_CASE)
 #undef RL_CASE
     }

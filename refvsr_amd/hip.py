@@ -68,6 +68,10 @@ SIGNATURES = {
     # lds | head, wf, relu, batch, h, w, stream -> key, n_tiles, lds
     'refvsr_conv24_variant': [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     'refvsr_resblock24_variant': [_I, _I, _I, _I, _I, _I, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    # and for the two other fused blocks (added symbols, ABI 15 unchanged): act_slope, batch, h, w, stream -> key, n_tiles, grid, lds |
+    # c, h, w, stream -> key, n_tiles, grid, lds (grid = None: host only)
+    'refvsr_resblock48_variant': [_F, _I, _I, _I, _P] + [C.POINTER(C.c_int)] * 4,
+    'refvsr_resblock_lean_variant': [_I, _I, _I, _P] + [C.POINTER(C.c_int)] * 4,
     'refvsr_kslot': [_I, _I, _I, _I, _I],        # returns the slot, not a status
     'refvsr_ksteps': [_I, _I],                   # returns the K-step count
     'refvsr_set_probe': [_P, _I],

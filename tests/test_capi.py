@@ -238,6 +238,42 @@ def test_fixed_variant_queries_are_the_launchers_plans(libpath):
         assert rb(*bad) != 0 and h.refvsr_last_error() == b'resblock24_variant: bad args'
 
 
+def test_block_variant_queries_are_the_launchers_plans(libpath):
+    """refvsr_resblock48_variant / refvsr_resblock_lean_variant (added symbols, ABI 15 unchanged): with a null grid pointer they are host
+    only -- they answer here -- with the key, tile count and LDS bytes of the planned resblock48_kernel / resblock_lean_kernel
+    instantiation under the process's probe buffer and wave setter (restored), and reject bad arguments with a message."""
+    from refvsr_amd import hip
+    h = hip.lib()
+    buf = (ctypes.c_char * 64)()
+    key, n, lds = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+    r48 = lambda *a: h.refvsr_resblock48_variant(*a, None, ctypes.byref(key), ctypes.byref(n), None, ctypes.byref(lds))
+    rl = lambda *a: h.refvsr_resblock_lean_variant(*a, None, ctypes.byref(key), ctypes.byref(n), None, ctypes.byref(lds))
+    try:
+        for probe, args, want in ((0, (0.25, 1, 43, 77), (0, 18, 134912)), (0, (0.0, 3, 43, 77), (1, 54, 134912)),
+                                  (1, (0.0, 1, 7, 5), (3, 1, 134912)), (1, (0.25, 1, 19, 45), (0, 6, 134912))):      # the leaky kernel has no probe form
+            h.refvsr_set_probe(ctypes.cast(buf, ctypes.c_void_p) if probe else None, 0)      # (never written: nothing is launched)
+            assert r48(*args) == 0, h.refvsr_last_error()
+            assert (key.value, n.value, lds.value) == want, (probe, args)
+        h.refvsr_set_probe(None, 0)
+        for waves, args, want in ((8, (24, 19, 45), (2 | 8 << 3, 6, 78560)), (4, (8, 43, 77), (1 | 4 << 3, 18, 19552)),
+                                  (4, (32, 7, 5), (2 | 1 << 2 | 4 << 3, 1, 108832))):
+            assert h.refvsr_set_resblock_waves(waves) == 0
+            assert rl(*args) == 0, h.refvsr_last_error()
+            assert (key.value, n.value, lds.value) == want, (waves, args)
+    finally:
+        h.refvsr_set_probe(None, 0)
+        h.refvsr_set_resblock_waves(8)
+    assert h.refvsr_resblock48_variant(0.0, 1, 8, 8, None, ctypes.byref(key), None, None, None) == 0       # tile count, grid and LDS bytes are optional
+    assert h.refvsr_resblock48_variant(0.0, 1, 8, 8, None, None, None, None, None) != 0 and b'null key' in h.refvsr_last_error()
+    for bad in ((-0.5, 1, 8, 8), (1.5, 1, 8, 8), (0.0, 0, 8, 8), (0.0, 5, 8, 8), (0.0, 1, 0, 8), (0.0, 1, 8, 0)):
+        assert r48(*bad) != 0 and h.refvsr_last_error() == b'resblock48_variant: bad args'
+    assert h.refvsr_resblock_lean_variant(24, 8, 8, None, None, None, None, None) != 0 and b'null key' in h.refvsr_last_error()
+    for bad in ((24, 0, 8), (24, 8, 0)):
+        assert rl(*bad) != 0 and h.refvsr_last_error() == b'resblock_lean_variant: bad args'
+    for c in (48, 20, 0):
+        assert rl(c, 8, 8) != 0 and h.refvsr_last_error() == b'resblock_lean: channel count %d not supported by the fused kernel' % c
+
+
 def test_multimap_entry_points_validate_before_device_work(libpath):
     """The ABI 11 entry points (host arrays of per-map device pointers): batch bounds, null table entries, shape support and aliasing are
     rejected with a message before anything touches the device."""
