@@ -584,6 +584,42 @@ size_t refvsr_param_fingerprint_workspace_bytes(int nchunks);
 int refvsr_param_fingerprint(const void* chunks, int nchunks, void* workspace, size_t workspace_bytes, void* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Y'CbCr 4:2:0 result frames (extension, no ABI bump: added symbols only).  The reference's consumer hands the RGB result to an
+ * image writer (evaluation/eval_qual_quan.py:117-119, cv2.imwrite of `output * 255`); a video consumer -- an encoder, a raw-video
+ * pipe, a .y4m file -- takes 4:2:0 instead and today converts those 3 bytes per pixel on the CPU.  The three entry points replace
+ * that host-side conversion (cv2.cvtColor(.., COLOR_RGB2YUV_I420) and its like) behind the result: 1.5 samples per pixel leave
+ * the device.  The specification is the numpy model refvsr_amd/yuv.py; the kernel returns its bits.
+ *   A frame is ONE dense buffer of 3 h w / 2 samples (h, w even):
+ *     REFVSR_YUV_NV12     Y [h][w], then interleaved CbCr [h/2][w/2][2]     8-bit
+ *     REFVSR_YUV_I420     Y [h][w], Cb [h/2][w/2], Cr [h/2][w/2]            8-bit
+ *     REFVSR_YUV_P010     the NV12 layout, 16-bit little-endian samples, the 10-bit code in the high bits (code << 6)
+ *     REFVSR_YUV_I420P10  the I420 layout, 16-bit little-endian samples, the code in the low bits
+ *   coef9: HOST array of nine doubles kr, kg, kb, icb, icr, oy, sy, oc, sc (yuv.py:coefficients: matrix, range and depth).
+ *   Source value in float64: a float32 / float16 result widened exactly, a uint8 byte u as u / 255.0.  Per pixel, every operation
+ *   rounded on its own (no fused multiply-add):  ey = (kr r + kg g) + kb b;  Y = rint(oy + sy ey);  ecb = (b - ey) icb;
+ *   ecr = (r - ey) icr;  per 2 x 2 block (centre-sited)  m = ((e00 + e01) + (e10 + e11)) 0.25;  C = rint(oc + sc m);  rint rounds
+ *   half to even and every code is clamped to [0, 2^d - 1] before the cast.
+ * refvsr_yuv420_max_frames: replaces nothing -- REFVSR_YUV420_MAX_FRAMES of the built library (a value, not a status).
+ * refvsr_yuv420_bytes: replaces the consumer's own buffer arithmetic (h * w * 3 / 2 samples) -- the bytes of one frame, 0 for odd
+ *   or non-positive h, w or an unknown format (host only).
+ * refvsr_result_to_yuv420: replaces the consumer's RGB -> 4:2:0 conversion of nframes <= REFVSR_YUV420_MAX_FRAMES results of one
+ *   h x w in ONE launch on `stream`:
+ *     src: HOST array of device pointers to the results, src_fmt = REFVSR_RESULT_F32 | F16 | U8, optionally | REFVSR_RESULT_HWC
+ *          ([3][h][w] or [h][w][3]: the six forms a result can have), aligned to their samples;
+ *     dst: HOST array of device pointers to refvsr_yuv420_bytes(h, w, yuv_fmt) bytes each, aligned to their samples (a group of pixels
+ *          whose addresses miss the vectors' alignment is written element by element); no destination may overlap a source or
+ *          another destination.
+ *   Every argument is checked before any device work: null table, null entry, frame count, unknown formats, odd or non-positive
+ *   h / w, alignment, overlap, 3 h w samples beyond 32-bit byte offsets.
+ * ------------------------------------------------------------------------------------------ */
+#define REFVSR_YUV420_MAX_FRAMES 16
+enum { REFVSR_YUV_NV12 = 0, REFVSR_YUV_I420 = 1, REFVSR_YUV_P010 = 2, REFVSR_YUV_I420P10 = 3 };
+int refvsr_yuv420_max_frames(void);
+size_t refvsr_yuv420_bytes(int h, int w, int yuv_fmt);
+int refvsr_result_to_yuv420(const void* const* src, int src_fmt, void* const* dst, int nframes, int h, int w, int yuv_fmt,
+                            const double* coef9, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Inter-frame alignment
  * ------------------------------------------------------------------------------------------ */
 /* models/utils.py:35-43 `warp`: linspace(-1,1) base grid + flow/((Win-1)/2), grid_sample(bilinear,

@@ -92,6 +92,9 @@ def base_config(project='', mode='', config_='', data='', LRS='', batch_size=8):
     c.fuse_resblocks = True     # conv-act-conv+residual pairs in one launch where the LDS budget allows
     c.result_dtype = 'float32'  # 'float16' | 'uint8': the output head stores rint(255 v) itself (extension; host consumers quantise anyway)
     c.result_layout = 'chw'     # 'hwc': the result is the [.., 3, sh, sw] view of dense [.., sh, sw, 3] memory (extension; what image writers consume)
+    c.result_yuv = None         # 'nv12' | 'i420' | 'p010' | 'i420p10': the calls also return 'yuv', the results as Y'CbCr 4:2:0 frames (extension; what video consumers take)
+    c.yuv_matrix = 'bt709'      # 'bt601': luma coefficients of 'yuv'
+    c.yuv_range = 'limited'     # 'full': code range of 'yuv'
     c.weight_precision = 'hi_lo'  # 'fp16' | 'amp': plain fp16 conv weights, the reference's AMP arithmetic (resolve_weight_precision)
     c.weight_check = 'auto'     # 'sync' | 'off': when the packed weights are checked against the parameters' device fingerprint (fingerprint.weight_check_policy)
     return c

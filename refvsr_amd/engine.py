@@ -21,7 +21,7 @@ import os
 
 import torch
 
-from . import ops
+from . import ops, yuv
 from .config import resolve_weight_precision
 from .knobs import env_flag
 from .packing import pack_conv, pack_conv_hr_last, pack_conv_last
@@ -303,6 +303,9 @@ class Engine(object):
         # result layout (extension; default 'chw' = planar): 'hwc' -- the output head stores the frame interleaved (REFVSR_RESULT_HWC),
         # the result is the [3, sh, sw] view of dense [sh, sw, 3] memory: what image writers and encoders consume, the same values
         self.result_layout = ops.check_result_layout(getattr(config, 'result_layout', None))
+        # Y'CbCr 4:2:0 copies of the results (extension; default None = off, no launch): the network calls also return 'yuv', one
+        # refvsr_result_to_yuv420 launch per call on the stream that receives 'result' (model.py:Network._with_yuv)
+        self.result_yuv = yuv.resolve(getattr(config, 'result_yuv', None), getattr(config, 'yuv_matrix', None), getattr(config, 'yuv_range', None))
         self._pipe = None
         # stream layout of the pipelined mode when nothing is configured: 'pf_m' for one forward() per frame (round 4); an engine that
         # is driven through forward_group switches to 'pfm' (P | F | M) at its first group: with the backward branches batched the

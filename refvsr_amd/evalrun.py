@@ -171,6 +171,13 @@ def evaluate(config, net=None, log=print):
     conf = 'conf_map' in str(E.eval_mode)
     if conf:
         config.save_sample = True            # eval_quan_conf_map.py:23: Network.forward(is_log=True) then returns 'eval_vis'
+    video = getattr(E, 'video_out', None)
+    if video and (fov or conf):
+        raise RuntimeError(VIDEO_MODE_MESSAGE % E.eval_mode)
+    if video and video != 'y4m':
+        raise RuntimeError("--video_out: 'y4m' is the only container (got %r)" % (video,))
+    if video and getattr(config, 'result_yuv', None) not in ('i420', 'i420p10'):
+        raise RuntimeError("--video_out y4m needs config.result_yuv = 'i420' | 'i420p10' (Y4M frames are planar), got %r" % (getattr(config, 'result_yuv', None),))
     if fov and config.flag_HD_in:
         raise RuntimeError('--eval_mode %s: flag_HD_in configs are not supported (the reference scores a cv2.resize(INTER_CUBIC) of the result)' % E.eval_mode)
     if net is None:
@@ -201,7 +208,7 @@ def evaluate(config, net=None, log=print):
     was_pipelined = bool(engines[0].pipelined) if engines else bool(getattr(config, 'pipelined', False))
     if G > 1:
         net.Network.set_pipelined(True)          # (restored at the end: the caller's plain net(...) calls keep their stream contract)
-    st = {'clip_p': 0.0, 'clip_s': 0.0, 'clip_t': 0.0, 'clip_n': 0, 'first_line': True, 'prev': None, 'clip_fov': 0.0}
+    st = {'clip_p': 0.0, 'clip_s': 0.0, 'clip_t': 0.0, 'clip_n': 0, 'first_line': True, 'prev': None, 'clip_fov': 0.0, 'video': None, 'video_clip': None}
     # --metrics device (extension, default 'host' = the loop below as it always was): the scores come from ONE refvsr_score_frames launch
     # per network call, on the caller's current stream (which already waits for the results, pipelined mode included: INTEGRATION.md),
     # and cross to the host as 16 bytes per frame; the frame itself is only copied when an image is written
@@ -238,6 +245,26 @@ def evaluate(config, net=None, log=print):
         k = len(CONF_MAP_DIRS)
         return [dict((CONF_MAP_DIRS[j][0], imgs[b * k + j]) for j in range(k)) for b in range(len(vis_list))]
 
+    def write_video(it, y):
+        """--video_out y4m (extension): the frame's 'yuv' [1, 3sh/2, sw] -- 1.5 samples per pixel cross to the host -- appended to
+        <out_root>/y4m/<clip>.y4m, one file per clip."""
+        from .yuv import Y4MWriter
+        a = y[0].cpu().numpy()
+        if st['video_clip'] != it['video_name']:
+            close_video()
+            path = os.path.join(out_root, 'y4m', '%s.y4m' % it['video_name'])
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            st['video'] = Y4MWriter(path, a.shape[0] * 2 // 3, a.shape[1], config.result_yuv, getattr(E, 'video_fps', None) or (30, 1),
+                                    getattr(config, 'yuv_range', None) or 'limited')
+            st['video_clip'] = it['video_name']
+            res.setdefault('videos', []).append(path)
+        st['video'].write(a)
+
+    def close_video():
+        if st['video'] is not None:
+            st['video'].close()
+        st['video'] = st['video_clip'] = None
+
     def emit_conf(it, out, lr_c, dt, imgs):
         out_raw = out[0].cpu()
         out_cpu = out_raw.float() / 255.0 if out_raw.dtype == torch.uint8 else out_raw.float()
@@ -261,7 +288,9 @@ def evaluate(config, net=None, log=print):
         res['seconds'].append(dt)
         res['frames'] += 1
 
-    def emit(it, out, lr_c, dt, scored=None, vis=None):
+    def emit(it, out, lr_c, dt, scored=None, vis=None, yuv=None):
+        if video:
+            write_video(it, yuv)
         if conf:
             return emit_conf(it, out, lr_c, dt, scored if scored is not None else colour([vis])[0])
         if on_device and scored is None:
@@ -342,7 +371,7 @@ def evaluate(config, net=None, log=print):
         else:
             scored = score_device(outs, pending) if on_device else [None] * len(pending)
         for b, it in enumerate(pending):
-            emit(it, outs[b], lrs[b, c], dt, scored[b])
+            emit(it, outs[b], lrs[b, c], dt, scored[b], yuv=got['yuv'][b] if video else None)
         del pending[:]
 
     def clip_summary():
@@ -361,6 +390,7 @@ def evaluate(config, net=None, log=print):
     try:
         _evaluate_loop(net, ds, dev, E, G, st, emit, flush, clip_summary, conf)
     finally:
+        close_video()
         if G > 1 and not was_pipelined:
             torch.cuda.synchronize()
             net.Network.set_pipelined(False)
@@ -415,7 +445,7 @@ def _evaluate_loop(net, ds, dev, E, G, st, emit, flush, clip_summary, conf=False
             kw = {'frame_ids': it['frame_ids']} if use_ids else {}
             got = net(lr, rf, it['is_first'], is_log=conf, is_train=False, **kw)
             torch.cuda.synchronize()
-            emit(it, got['result'], lr[0, lr.shape[1] // 2], time.time() - t0, vis=got['eval_vis'] if conf else None)
+            emit(it, got['result'], lr[0, lr.shape[1] // 2], time.time() - t0, vis=got['eval_vis'] if conf else None, yuv=got.get('yuv'))
         flush(pending)
 
 
@@ -463,6 +493,9 @@ def _fov_clip_summary(config, score_path, it, table, t, log):
     log(block)
     with open(score_path, 'a') as fh:
         fh.write(block)
+
+
+VIDEO_MODE_MESSAGE = ("--video_out writes the frames of the qual_quan loop; --eval_mode %s writes no result video (drop --video_out)")
 
 
 # ------------------------------------------------------------------------------------------------ CLI
@@ -517,8 +550,23 @@ def build_config(argv=None):
                          "the flag_HD_in configs (.._8K), whose result is `scale` times the ground truth, are scored on the result's bicubic "
                          "down-scale -- PSNR of the clamped, SSIM of the unclamped image -- which 'device' fuses into the same launch "
                          "(refvsr_score_frames_down, float64 taps) and 'host' takes from F.interpolate in float32: SSIM then agrees to ~1e-9)")
+    ap.add_argument('--video_out', default=None, choices=['y4m'],
+                    help="extension: also write the results as video, one <out_root>/y4m/<clip>.y4m per clip; the frames are converted to "
+                         "Y'CbCr 4:2:0 on the device (one refvsr_result_to_yuv420 launch per network call) and 1.5 samples per pixel are "
+                         "copied to the host; scores, images and score files are unchanged (not with the FOV / conf_map eval modes)")
+    ap.add_argument('--video_fps', default='30', help="extension: frame rate of --video_out, N or N:D (e.g. 30000:1001)")
+    ap.add_argument('--video_depth', type=int, default=8, choices=[8, 10], help='extension: bits per sample of --video_out (8: C420jpeg, 10: C420p10)')
+    ap.add_argument('--yuv_matrix', default='bt709', choices=['bt709', 'bt601'], help='extension: luma coefficients of --video_out')
+    ap.add_argument('--yuv_range', default='limited', choices=['limited', 'full'], help='extension: code range of --video_out')
     args, _ = ap.parse_known_args(argv)
+    if args.video_out and ('FOV' in str(args.eval_mode) or 'conf_map' in str(args.eval_mode)):
+        raise RuntimeError(VIDEO_MODE_MESSAGE % args.eval_mode)
+    from .yuv import parse_fps
+    video_fps = parse_fps(args.video_fps)
     cfg = get_config(args.project, args.mode, args.config, args.data)
+    if args.video_out:
+        cfg.yuv_matrix, cfg.yuv_range = args.yuv_matrix, args.yuv_range
+        cfg.result_yuv = 'i420' if args.video_depth == 8 else 'i420p10'
     cfg.result_dtype = args.result_dtype
     cfg.result_layout = args.result_layout
     cfg.weight_precision = args.weight_precision
@@ -536,6 +584,7 @@ def build_config(argv=None):
     E.eval_mode, E.test_set, E.data = args.eval_mode, args.test_set, args.data
     E.frame_group = args.frame_group
     E.metrics = args.metrics
+    E.video_out, E.video_fps = args.video_out, video_fps
     cfg.save_sample = args.save_sample or 'conf_map' in str(args.eval_mode)      # (eval_quan_conf_map.py:23)
     cfg.device = 'cpu' if args.cpu else 'cuda'
     cfg.cuda = not args.cpu

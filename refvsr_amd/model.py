@@ -281,9 +281,20 @@ class Network(nn.Module):
         """n results [3,sh,sw] -> [n,3,sh,sw] in the engines' result layout (config.result_layout = 'hwc': dense [n,sh,sw,3] memory)."""
         return ops.stack_results(results, self._engines[0].result_layout)
 
+    def _with_yuv(self, outs, frames, stacked):
+        """config.result_yuv (extension; None = off: nothing is launched, no key): outs['yuv'] = the call's results [3,sh,sw] as Y'CbCr
+        4:2:0 frames, batched as 'result' is -- [n, 3sh/2, sw] (stacked) or a tuple of [1, 3sh/2, sw].  ONE refvsr_result_to_yuv420
+        launch per network call on the caller's current stream: the stream that receives 'result' and already waits for it,
+        pipelined mode included (the rule of the device scorers).  'result' itself is returned as it was."""
+        want = self._engines[0].result_yuv
+        if want is not None:
+            y = ops.result_to_yuv420(frames, *want)
+            outs['yuv'] = y if stacked else tuple(y[b:b + 1] for b in range(y.shape[0]))
+        return outs
+
     def forward(self, lrs, refs, is_first_frame, is_log=False, is_train=False, frame_ids=None, input_ready=None):
         """Same contract as RefVSR.py:151: lrs, refs [n,t,3,h,w] in [0,1] (or uint8: byte / 255, see _inputs); returns OrderedDict with
-        'result' [n,3,4h,4w] (+ 'eval_vis' when is_log and config.save_sample).
+        'result' [n,3,4h,4w] (+ 'eval_vis' when is_log and config.save_sample; + 'yuv' [n,6h,4w] under config.result_yuv).
         frame_ids / input_ready: extensions (window cache keyed by ids; when the inputs are final -- Engine.set_pipelined)."""
         if is_train:
             raise NotImplementedError('refvsr_amd implements the inference path only (is_train=False)')
@@ -310,7 +321,7 @@ class Network(nn.Module):
                                                  [[(b, f) for f in frame_ids] for b in range(n)], input_ready)
             outs = collections.OrderedDict()
             outs['result'] = self._stack(res)
-            return outs
+            return self._with_yuv(outs, res, True)
         for b in range(n):
             out, vis = self._engines[b].forward(lrs[b], refs[b], bool(is_first_frame), want_vis,
                                                 None if frame_ids is None else [(b, f) for f in frame_ids], want_log=bool(is_log),
@@ -329,12 +340,12 @@ class Network(nn.Module):
             for k in vis_all[0]:
                 ev[k] = torch.stack([v[k] for v in vis_all], 0)
             outs['eval_vis'] = ev
-        return outs
+        return self._with_yuv(outs, results, True)
 
     def forward_group(self, lrs, refs, frame_ids, is_first_frame=False, input_ready=None, want_conf=False):
         """B CONSECUTIVE windows of one stream in one call (extension; see Engine.forward_group): lrs, refs [B,t,3,h,w] -- window b
         is what the b-th of B consecutive forward() calls would get as its n = 1 input -- frame_ids: B lists of t ids.  Returns
-        OrderedDict{'result': tuple of B tensors [1,3,sh,sw]}, bit-identical to the B calls; the backward branches and the
+        OrderedDict{'result': tuple of B tensors [1,3,sh,sw]} (+ 'yuv': B tensors [1,3sh/2,sw] under config.result_yuv), bit-identical to the B calls; the backward branches and the
         upsamplers' inputs of the B frames run as multi-map launches, the forward-branch steps frame by frame.
         want_conf: the dict also carries 'eval_vis', a tuple of B OrderedDicts of [1,1,h,w] float32 maps -- what forward(window b, ..,
         is_log=True) returns as 'eval_vis' under config.save_sample (RefVSR.py:318-322), bit for bit.  (RefVSR_IR has no such maps:
@@ -360,7 +371,7 @@ class Network(nn.Module):
         outs['result'] = tuple(r.unsqueeze(0) for r in res)
         if vis is not None and all(v is not None for v in vis):
             outs['eval_vis'] = tuple(collections.OrderedDict((k, x.unsqueeze(0)) for k, x in v.items()) for v in vis)
-        return outs
+        return self._with_yuv(outs, res, False)
 
     # ---- two-phase forward for the multi-GPU wavefront (refvsr_amd/shard.py:run_wavefront; not in the reference) ----
     def phase_a(self, lrs, refs, frame_ids=None, first_hint=False):

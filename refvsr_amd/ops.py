@@ -902,6 +902,44 @@ def score_regions(outs, gts, rects):
     return sums
 
 
+_irange = range       # (result_to_yuv420 has an argument of that name)
+
+
+def result_to_yuv420(frames, fmt='nv12', matrix='bt709', range='limited'):
+    """Result frames -> Y'CbCr 4:2:0 on the device (refvsr_result_to_yuv420; the bits of yuv.rgb_to_yuv420): a [B, 3 h / 2, w] tensor,
+    torch.uint8 ('nv12' | 'i420') or torch.uint16 ('p010' | 'i420p10'), frame b one dense buffer (yuv.planes gives its views), on the
+    current stream, no synchronisation.  frames: a [B,3,h,w] tensor or B tensors [3,h,w], float32 / float16 / uint8 (what the output
+    head stores), contiguous or channels-last (config.result_layout = 'hwc'), h and w even.  matrix: 'bt709' | 'bt601'; range:
+    'limited' | 'full'.  One launch per REFVSR_YUV420_MAX_FRAMES frames."""
+    from . import yuv
+    coef = (C.c_double * 9)(*yuv.coefficients(fmt, matrix, range))
+    frames = list(frames)
+    if not frames:
+        raise RuntimeError('result_to_yuv420: at least one frame')
+    f0 = frames[0]
+    fmts = {torch.float32: hip.RESULT_F32, torch.float16: hip.RESULT_F16, torch.uint8: hip.RESULT_U8}
+    if not (f0.is_cuda and f0.dtype in fmts and f0.dim() == 3 and f0.shape[0] == 3):
+        raise RuntimeError('result_to_yuv420: cuda float32 | float16 | uint8 results [3,h,w] (got %s %s %s)' % (f0.device.type, f0.dtype, tuple(f0.shape)))
+    _, h, w = f0.shape
+    if h % 2 or w % 2:
+        raise RuntimeError('result_to_yuv420: 4:2:0 needs even h and w (got %d x %d)' % (h, w))
+    lay = result_layout_of(f0)
+    for f in frames:
+        if f.shape != f0.shape or f.dtype != f0.dtype or not f.is_cuda:
+            raise RuntimeError('result_to_yuv420: frames must all be %s [3, %d, %d] (got %s %s)' % (f0.dtype, h, w, f.dtype, tuple(f.shape)))
+        if lay is None or result_layout_of(f) != lay:
+            raise RuntimeError('result_to_yuv420: results must be dense and of one layout, contiguous [3, h, w] or the channels-last view of '
+                               '[h, w, 3] (config.result_layout), got strides %s' % (tuple(f.stride()),))
+    sfmt = fmts[f0.dtype] | (hip.RESULT_HWC if lay == 'hwc' else 0)
+    out = torch.empty((len(frames),) + yuv.frame_shape(h, w), dtype=torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16, device=f0.device)
+    st = _stream()
+    for s0 in _irange(0, len(frames), hip.YUV420_MAX_FRAMES):
+        chunk = frames[s0:s0 + hip.YUV420_MAX_FRAMES]
+        hip.check(hip.lib().refvsr_result_to_yuv420(_parr(chunk), sfmt, _parr([out[s0 + i] for i in _irange(len(chunk))]), len(chunk), h, w,
+                                                    yuv.FORMAT_IDS[fmt], coef, st), 'result_to_yuv420')
+    return out
+
+
 _COLORMAP_WS = {}     # (device, stream handle, h, w) -> workspace of one full refvsr_conf_colormap launch
 
 

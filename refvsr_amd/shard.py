@@ -365,6 +365,9 @@ class EngineExecutor(object):
     def __init__(self, net, device, h, w, nframes, frame_num, keep_on_device=True, pipelined=True, inputs_materialised=False,
                  split_handoff=True, split_phase_a=True):
         self.net, self.dev, self.h, self.w, self.nframes, self.t = net, device, h, w, nframes, frame_num
+        if getattr(getattr(net.Network, 'config', None), 'result_yuv', None) is not None:
+            raise RuntimeError("the sharded runner returns RGB results only: config.result_yuv = %r is not supported here (convert the "
+                               "gathered results with ops.result_to_yuv420, or run a single-GPU engine)" % (net.Network.config.result_yuv,))
         self.keep = keep_on_device
         self.eng = net.Network.ensure_engines(1, device)[0]
         # run_wavefront: the hand-off as [header | feat | flow | conf] + [feat_up]; the forward-branch step of the receiver starts on

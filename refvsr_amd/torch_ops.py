@@ -28,6 +28,7 @@ Op set (argument conventions of ops.py: `planar` = float32 [C,H,W], `nhwc16` = f
   ingest_u8(x)                                           uint8 [..., 3, h, w] (planar or channels-last) -> float32 x / 255, exact
   score_frames(outs, gts, win)                           [B,3,h,w] results / ground truths -> float64 [B,2] = {mse, ssim} on the device
   score_regions(outs, gts, rects)                        the same pairs, rects = flat [4 R] ints -> float64 [B,R,2] = {sum (a-b)^2, sum S}
+  result_to_yuv420(frames, fmt, matrix, range)           [B,3,h,w] results -> [B, 3h/2, w] uint8 | uint16 4:2:0 frames (yuv.py's bits)
 """
 from typing import List, Optional, Tuple
 
@@ -295,8 +296,23 @@ def register():
                      lambda: 'score_regions takes 1..%d rectangles as a flat list of y0, y1, x0, x1' % hip.SCORE_MAX_RECTS)
         return torch.empty((outs.shape[0], len(rects) // 4, 2), dtype=torch.float64, device=outs.device)
 
+    @op('result_to_yuv420')
+    def result_to_yuv420(frames: torch.Tensor, fmt: str, matrix: str, range: str) -> torch.Tensor:
+        return ops.result_to_yuv420(frames, fmt, matrix, range)
+
+    @result_to_yuv420.register_fake
+    def _(frames, fmt, matrix, range):
+        from . import yuv
+        torch._check(frames.dim() == 4 and frames.shape[1] == 3 and frames.shape[2] % 2 == 0 and frames.shape[3] % 2 == 0,
+                     lambda: 'result_to_yuv420 takes [B,3,h,w] results with even h and w')
+        torch._check(fmt in yuv.FORMATS, lambda: 'result_to_yuv420: unknown yuv format')
+        torch._check(matrix in yuv.MATRICES, lambda: "result_to_yuv420: yuv_matrix must be 'bt709' or 'bt601'")
+        torch._check(range in yuv.RANGES, lambda: "result_to_yuv420: yuv_range must be 'limited' or 'full'")
+        return torch.empty((frames.shape[0], 3 * frames.shape[2] // 2, frames.shape[3]),
+                           dtype=torch.uint8 if yuv.FORMATS[fmt][0] == 8 else torch.uint16, device=frames.device)
+
 
 OP_NAMES = ('conv_mfma', 'conv24', 'resblock', 'resblock24_chain', 'resblock24_chain_batch', 'conv24_batch', 'warp_batch', 'match_argmax', 'warp', 'warp_planar', 'spynet_level_input', 'block_gather',
-            'block_gather_rgb', 'aligned_sample', 'resize', 'pack_nhwc16', 'unpack_nhwc16', 'ingest_u8', 'score_frames', 'score_regions')
+            'block_gather_rgb', 'aligned_sample', 'resize', 'pack_nhwc16', 'unpack_nhwc16', 'ingest_u8', 'score_frames', 'score_regions', 'result_to_yuv420')
 
 register()
