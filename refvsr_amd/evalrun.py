@@ -22,6 +22,7 @@ Counterpart of the reference's eval stack, restated from its behaviour:
         --ckpt_abs_name ckpt/RefVSR_small_L1.pytorch --data_offset /data --output_offset ./result --frame_num 5
 """
 import argparse
+import collections
 import datetime
 import os
 import sys
@@ -154,319 +155,11 @@ def load_checkpoint(net, path):
     return net.load_state_dict(sd, strict=False)
 
 
-def evaluate(config, net=None, log=print):
-    """eval_qual_quan counterpart.  Returns dict(psnr=[..], ssim=[..], frames=N, seconds=[..]).
-    'FOV' in EVAL.eval_mode: eval_quan_FOV counterpart -- the same loop; a frame's score is its FOV table (metrics.fov_table,
-    [6 keys][fi, fo, fr][psnr, ssim]), whose key 1 fi pair is the per-frame line; the summaries are the reference's six-row blocks; no
-    image is written (the reference has that part commented out); the tables are returned as res['fov'].
-    'conf_map' in EVAL.eval_mode: eval_quan_conf_map counterpart -- the same loop without scores (psnr / ssim stay empty; --metrics,
-    -qualitative_only and -quantitative_only have no effect, as in the reference's loop): per frame the input, the result and the four
-    maps of 'eval_vis' coloured by ONE ops.conf_colormap launch per network call (CONF_MAP_DIRS names the folders); with --frame_group
-    G > 1 the maps come from forward_group(want_conf=True).  RefVSR_IR has no such maps (the reference fails on None['conf_map'])."""
-    if 'conf_map' in str(config.EVAL.eval_mode) and config.network == 'RefVSR_IR':
-        raise RuntimeError('--eval_mode %s: RefVSR_IR returns no confidence maps (config %s)' % (config.EVAL.eval_mode, config.get('config')))
-    from . import SRNet
-    E = config.EVAL
-    fov = 'FOV' in str(E.eval_mode)
-    conf = 'conf_map' in str(E.eval_mode)
-    if conf:
-        config.save_sample = True            # eval_quan_conf_map.py:23: Network.forward(is_log=True) then returns 'eval_vis'
-    video = getattr(E, 'video_out', None)
-    if video and (fov or conf):
-        raise RuntimeError(VIDEO_MODE_MESSAGE % E.eval_mode)
-    if video and video != 'y4m':
-        raise RuntimeError("--video_out: 'y4m' is the only container (got %r)" % (video,))
-    if video and getattr(config, 'result_yuv', None) not in ('i420', 'i420p10'):
-        raise RuntimeError("--video_out y4m needs config.result_yuv = 'i420' | 'i420p10' (Y4M frames are planar), got %r" % (getattr(config, 'result_yuv', None),))
-    if fov and config.flag_HD_in:
-        raise RuntimeError('--eval_mode %s: flag_HD_in configs are not supported (the reference scores a cv2.resize(INTER_CUBIC) of the result)' % E.eval_mode)
-    if net is None:
-        if config.device != 'cuda':
-            raise RuntimeError('refvsr_amd has no CPU path; run on the GPU (drop --cpu)')
-        net = SRNet(config).to('cuda').eval()
-        if E.ckpt_abs_name:
-            log('Loading checkpoint %s: %s' % (E.ckpt_abs_name, load_checkpoint(net, E.ckpt_abs_name)))
-    if conf:
-        net.Network.config.save_sample = True            # (a caller's net may carry a config of its own)
-    ckpt_name = os.path.basename(E.ckpt_abs_name) if E.ckpt_abs_name else 'seeded'
-    date = datetime.datetime.now().strftime('%Y_%m_%d_%H%M')
-    root = os.path.join(E.LOG_DIR.save, E.eval_mode, ckpt_name.split('.')[0])
-    out_root = os.path.join(root, E.data, date)
-    os.makedirs(root, exist_ok=True)
-    score_path = os.path.join(root, 'score_%s_%s.txt' % (E.data, E.eval_mode))
-    ds = ClipSet(config)
-    dev = next(net.parameters()).device
-    res = {'psnr': [], 'ssim': [], 'seconds': [], 'frames': 0}
-    if fov:
-        res['fov'] = []
-    # --frame_group G (extension, default 1 = the reference's loop): G consecutive windows of a clip per network call
-    # (SRNet.forward_group: the backward branches of the G frames as multi-map launches; results bit-identical); the per-frame time in
-    # the score lines is then the group's time / G
-    G = max(1, int(getattr(E, 'frame_group', 1) or 1))
-    # (the state to restore is the net's own: a caller's net may have been switched on without config.pipelined saying so)
-    engines = getattr(net.Network, '_engines', None)
-    was_pipelined = bool(engines[0].pipelined) if engines else bool(getattr(config, 'pipelined', False))
-    if G > 1:
-        net.Network.set_pipelined(True)          # (restored at the end: the caller's plain net(...) calls keep their stream contract)
-    st = {'clip_p': 0.0, 'clip_s': 0.0, 'clip_t': 0.0, 'clip_n': 0, 'first_line': True, 'prev': None, 'clip_fov': 0.0, 'video': None, 'video_clip': None}
-    # --metrics device (extension, default 'host' = the loop below as it always was): the scores come from ONE refvsr_score_frames launch
-    # per network call, on the caller's current stream (which already waits for the results, pipelined mode included: INTEGRATION.md),
-    # and cross to the host as 16 bytes per frame; the frame itself is only copied when an image is written
-    on_device = getattr(E, 'metrics', 'host') == 'device' and not getattr(E, 'qualitative_only', False) and not conf
-
-    def score_device(outs, items):
-        from . import ops
-        from .metrics import psnr_from_mse
-        gts = [it['HR_UW'].to(dev) for it in items]              # (decoded bytes, channels-last: a quarter of the float frame)
-        # flag_HD_in: the result is `scale` times the ground truth and the scores are those of its bicubic down-scale, which the
-        # kernel forms while it stages its tiles (refvsr_score_frames_down): the big frame is read once where it lies
-        down = int(config.scale) if config.flag_HD_in else 1     # (no FOV mode here: evaluate() refuses it for these configs)
-        for o, g in zip(outs, gts):
-            if tuple(o[0].shape) != (3, down * g.shape[-2], down * g.shape[-1]):
-                raise RuntimeError('--metrics device: result %s and ground truth %s differ in shape' % (tuple(o[0].shape), tuple(g.shape)))
-        if fov:
-            # one refvsr_score_regions launch: 7 rectangles x 16 bytes per frame cross to the host
-            from .metrics import fov_rects, fov_table
-            h, w = gts[0].shape[-2:]
-            sums = ops.score_regions([o[0] for o in outs], gts, fov_rects(h, w)).cpu().numpy()
-            tables = [fov_table(sm, h, w) for sm in sums]
-            return [(float(t[0, 0, 0]), float(t[0, 0, 1]), t) for t in tables]
-        if down == 1:
-            sc = ops.score_frames([o[0] for o in outs], gts, win=7).cpu().tolist()
-        else:
-            sc = ops.score_frames([o[0] for o in outs], gts, win=7, down=down).cpu().tolist()
-        return [(psnr_from_mse(m), s) for m, s in sc]
-
-    def colour(vis_list):
-        """The windows' 'eval_vis' dicts -> per window {folder: uint8 [h, w, 3] on the host}: one conf_colormap launch for all maps."""
-        from . import ops
-        maps = [v[src] for v in vis_list for _, src in CONF_MAP_DIRS]
-        imgs = [x.cpu() for x in ops.conf_colormap(maps)]
-        k = len(CONF_MAP_DIRS)
-        return [dict((CONF_MAP_DIRS[j][0], imgs[b * k + j]) for j in range(k)) for b in range(len(vis_list))]
-
-    def write_video(it, y):
-        """--video_out y4m (extension): the frame's 'yuv' [1, 3sh/2, sw] -- 1.5 samples per pixel cross to the host -- appended to
-        <out_root>/y4m/<clip>.y4m, one file per clip."""
-        from .yuv import Y4MWriter
-        a = y[0].cpu().numpy()
-        if st['video_clip'] != it['video_name']:
-            close_video()
-            path = os.path.join(out_root, 'y4m', '%s.y4m' % it['video_name'])
-            os.makedirs(os.path.dirname(path), exist_ok=True)
-            st['video'] = Y4MWriter(path, a.shape[0] * 2 // 3, a.shape[1], config.result_yuv, getattr(E, 'video_fps', None) or (30, 1),
-                                    getattr(config, 'yuv_range', None) or 'limited')
-            st['video_clip'] = it['video_name']
-            res.setdefault('videos', []).append(path)
-        st['video'].write(a)
-
-    def close_video():
-        if st['video'] is not None:
-            st['video'].close()
-        st['video'] = st['video_clip'] = None
-
-    def emit_conf(it, out, lr_c, dt, imgs):
-        out_raw = out[0].cpu()
-        out_cpu = out_raw.float() / 255.0 if out_raw.dtype == torch.uint8 else out_raw.float()
-        line = '[EVAL {}|{}|{}][{}/{}][{}/{}] {} ({:.5f}sec)'.format(
-            config.mode, E.data, it['video_name'], it['video_idx'] + 1, it['video_len'], it['frame_idx'] + 1, it['frame_len'],
-            it['frame_name'], dt)
-        log(line)
-        with open(score_path, 'w' if st['first_line'] else 'a') as fh:
-            fh.write(line + '\n')
-        st['first_line'] = False
-        stem = it['frame_name'].split('.')[0]
-        for fmt in ('png', 'jpg'):
-            base = os.path.join(out_root, fmt)
-            write_frame(os.path.join(base, 'input', it['video_name'], '%s.%s' % (stem, fmt)), lr_c)
-            write_frame(os.path.join(base, 'output', it['video_name'], '%s.%s' % (stem, fmt)), out_raw if out_raw.dtype == torch.uint8 else out_cpu)
-            for folder, _ in CONF_MAP_DIRS:
-                write_frame(os.path.join(base, folder, it['video_name'], '%s.%s' % (stem, fmt)), imgs[folder].permute(2, 0, 1))
-        st['clip_t'] += dt
-        st['clip_n'] += 1
-        st['prev'] = it
-        res['seconds'].append(dt)
-        res['frames'] += 1
-
-    def emit(it, out, lr_c, dt, scored=None, vis=None, yuv=None):
-        if video:
-            write_video(it, yuv)
-        if conf:
-            return emit_conf(it, out, lr_c, dt, scored if scored is not None else colour([vis])[0])
-        if on_device and scored is None:
-            scored = score_device([out], [it])[0]
-        if scored is not None and (fov or getattr(E, 'quantitative_only', False)):
-            out_raw = out_cpu = None                 # (nothing reads the frame: it stays on the device)
-        else:
-            out_raw = out[0].cpu()
-            # (result_dtype 'uint8' / 'float16', extensions: the scores are then those of the quantised frame; the PNG bytes are the same)
-            out_cpu = out_raw.float() / 255.0 if out_raw.dtype == torch.uint8 else out_raw.float()
-        p = s = 0.0
-        table = None
-        if scored is not None:
-            p, s = scored[:2]
-            table = scored[2] if fov else None
-        elif fov:
-            from .metrics import fov_scores_host
-            gt = it['HR_UW']
-            out_cpu = out_cpu.contiguous()           # (host scores are taken on the planar frame whatever --result_layout says)
-            if out_cpu.shape != gt.shape:
-                raise RuntimeError('--eval_mode %s: result %s and ground truth %s differ in shape' % (E.eval_mode, tuple(out_cpu.shape), tuple(gt.shape)))
-            table = fov_scores_host(out_cpu, gt)
-            p, s = float(table[0, 0, 0]), float(table[0, 0, 1])
-        elif not getattr(E, 'qualitative_only', False):
-            gt = it['HR_UW']
-            sc_cpu = out_cpu.contiguous()            # (host scores are taken on the planar frame whatever --result_layout says)
-            if config.flag_HD_in:
-                # the result is `scale` times the ground truth; both scores are those of its bicubic down-scale: the PSNR of the
-                # clamped image (models/loss/Loss.py:91-92,141), the SSIM of the unclamped one (eval_qual_quan.py:85-92, whose
-                # cv2.resize(INTER_CUBIC) is this filter at an exact integer factor)
-                d = F.interpolate(sc_cpu[None], scale_factor=1.0 / config.scale, mode='bicubic', align_corners=False)[0]
-                p = psnr(d.clamp(0, 1), gt)
-                s = ssim(d, gt)
-            else:
-                p = psnr(sc_cpu, gt)
-                s = ssim(sc_cpu, gt)
-        line = '[EVAL {}|{}|{}][{}/{}][{}/{}] {} PSNR: {:.5f} SSIM: {:.5f} ({:.5f}sec)'.format(
-            config.mode, E.data, it['video_name'], it['video_idx'] + 1, it['video_len'], it['frame_idx'] + 1,
-            it['frame_len'], it['frame_name'], p, s, dt)
-        log(line)
-        with open(score_path, 'w' if st['first_line'] else 'a') as fh:
-            fh.write(line + '\n')
-        st['first_line'] = False
-        if not fov and not getattr(E, 'quantitative_only', False):
-            stem = it['frame_name'].split('.')[0]
-            for fmt in ('png', 'jpg'):
-                base = os.path.join(out_root, fmt)
-                write_frame(os.path.join(base, 'input', it['video_name'], '%s.%s' % (stem, fmt)), lr_c)
-                write_frame(os.path.join(base, 'output', it['video_name'], '%s.%s' % (stem, fmt)), out_raw if out_raw.dtype == torch.uint8 else out_cpu)
-        st['clip_p'] += p
-        st['clip_s'] += s
-        st['clip_t'] += dt
-        st['clip_n'] += 1
-        st['prev'] = it
-        if fov:
-            st['clip_fov'] = st['clip_fov'] + table
-            res['fov'].append(table)
-        res['psnr'].append(p)
-        res['ssim'].append(s)
-        res['seconds'].append(dt)
-        res['frames'] += 1
-
-    def flush(pending, first=False):
-        if not pending:
-            return
-        t0 = time.time()
-        lrs, rfs = (stack_frames([it[k] for it in pending]).to(dev) for k in ('LR_UW', 'LR_REF_W'))
-        if lrs.dtype != torch.uint8:
-            lrs, rfs = lrs.float().contiguous(), rfs.float().contiguous()
-        kw = {'want_conf': True} if conf else {}
-        got = net.forward_group(lrs, rfs, [it['frame_ids'] for it in pending], is_first_frame=first, **kw)
-        outs = got['result']
-        torch.cuda.synchronize()
-        dt = (time.time() - t0) / len(pending)
-        c = lrs.shape[1] // 2
-        if conf:
-            scored = colour(got['eval_vis'])         # (the windows' images, in the place of their scores)
-        else:
-            scored = score_device(outs, pending) if on_device else [None] * len(pending)
-        for b, it in enumerate(pending):
-            emit(it, outs[b], lrs[b, c], dt, scored[b], yuv=got['yuv'][b] if video else None)
-        del pending[:]
-
-    def clip_summary():
-        """The clip's MEAN line / block, named for the clip it summarises; resets the clip's sums."""
-        if st['clip_n']:
-            n = st['clip_n']
-            if fov:
-                _fov_clip_summary(config, score_path, st['prev'], st['clip_fov'] / n, st['clip_t'] / n, log)
-            elif conf:
-                _conf_clip_summary(config, score_path, st['prev'], st['clip_t'] / n, log)
-            else:
-                _clip_summary(config, score_path, st['prev'], st['clip_p'], st['clip_s'], st['clip_t'], n, log)
-        st['clip_p'] = st['clip_s'] = st['clip_t'] = st['clip_fov'] = 0.0
-        st['clip_n'] = 0
-
-    try:
-        _evaluate_loop(net, ds, dev, E, G, st, emit, flush, clip_summary, conf)
-    finally:
-        close_video()
-        if G > 1 and not was_pipelined:
-            torch.cuda.synchronize()
-            net.Network.set_pipelined(False)
-    clip_summary()
-    n = max(res['frames'], 1)
-    if fov:
-        total = fov_block('\n[TOTAL {}|{}] \n'.format(ckpt_name, E.data), sum(res['fov']) / n if res['fov'] else np.zeros((6, 3, 2)),
-                          ') ({:.5f}sec)\n\n'.format(sum(res['seconds']) / n))
-        log(total)
-        with open(score_path, 'a') as fh:
-            fh.write(total)
-    elif conf:
-        total = '\n[TOTAL {}|{}] ({:.5f}sec)'.format(ckpt_name, E.data, sum(res['seconds']) / n)
-        log(total)
-        with open(score_path, 'a') as fh:
-            fh.write(total + '\n')
-    else:
-        total = '\n[TOTAL {}|{}] PSNR: {:.5f} SSIM: {:.5f} ({:.5f}sec)'.format(
-            ckpt_name, E.data, sum(res['psnr']) / n, sum(res['ssim']) / n, sum(res['seconds']) / n)
-        log(total)
-        with open(score_path, 'a') as fh:
-            fh.write(total + '\n')
-    res['score_file'], res['output_root'] = score_path, out_root
-    return res
-
-
-def _evaluate_loop(net, ds, dev, E, G, st, emit, flush, clip_summary, conf=False):
-    """The per-frame loop of evaluate() (eval_qual_quan.py:39-128, eval_quan_FOV.py:55-232, eval_quan_conf_map.py:32-174): emit scores
-    and logs a frame, clip_summary closes a clip.  conf: a one-window call is the reference's own, net(.., is_log=True), whose
-    'eval_vis' goes to emit; in a grouped run every call is a forward_group, a clip's first frame one of a single window."""
-    with torch.no_grad():
-        pending = []
-        for i in range(len(ds)):
-            it = ds[i]
-            if it.get('is_continue'):
-                continue
-            if it['is_first']:
-                flush(pending)
-                clip_summary()
-                net.Network.reset()
-            use_ids = getattr(E, 'use_frame_ids', True) and 'frame_ids' in it
-            if G > 1 and use_ids and conf and it['is_first']:
-                flush([it], first=True)
-                continue
-            if G > 1 and use_ids and not it['is_first']:
-                pending.append(it)
-                if len(pending) == G:
-                    flush(pending)
-                continue
-            t0 = time.time()
-            lr, rf = it['LR_UW'][None].to(dev), it['LR_REF_W'][None].to(dev)
-            kw = {'frame_ids': it['frame_ids']} if use_ids else {}
-            got = net(lr, rf, it['is_first'], is_log=conf, is_train=False, **kw)
-            torch.cuda.synchronize()
-            emit(it, got['result'], lr[0, lr.shape[1] // 2], time.time() - t0, vis=got['eval_vis'] if conf else None, yuv=got.get('yuv'))
-        flush(pending)
-
-
-def _clip_summary(config, score_path, it, p, s, t, n, log):
-    line = '[MEAN EVAL {}|{}|{}][{}/{}] PSNR: {:.5f} SSIM: {:.5f} ({:.5f}sec)\n'.format(
-        config.mode, config.EVAL.data, it['video_name'], it['video_idx'], it['video_len'], p / n, s / n, t / n)
-    log(line)
-    with open(score_path, 'a') as fh:
-        fh.write(line + '\n')
-
-
 # folder of the reference's output tree <- key of 'eval_vis' (eval_quan_conf_map.py:64-77,148-165)
 CONF_MAP_DIRS = (('conf_map_norm', 'conf_map'), ('conf_map_prop_norm', 'conf_map_prop'),
                  ('conf_map_prop_b_norm', 'conf_map_prop_backward'), ('conf_map_prop_f_norm', 'conf_map_prop_forward'))
 
-
-def _conf_clip_summary(config, score_path, it, t, log):
-    line = '[MEAN EVAL {}|{}|{}][{}/{}] ({:.5f}sec)\n'.format(config.mode, config.EVAL.data, it['video_name'], it['video_idx'], it['video_len'], t)
-    log(line)
-    with open(score_path, 'a') as fh:
-        fh.write(line + '\n')
+VIDEO_MODE_MESSAGE = ("--video_out writes the frames of the qual_quan loop; --eval_mode %s writes no result video (drop --video_out)")
 
 
 def fov_block(head, table, tail):
@@ -487,15 +180,294 @@ def fov_block(head, table, tail):
     return out + tail
 
 
-def _fov_clip_summary(config, score_path, it, table, t, log):
-    block = fov_block('[MEAN EVAL {}|{}|{}][{}/{}] ({:.5f}sec) \n'.format(config.mode, config.EVAL.data, it['video_name'], it['video_idx'],
-                                                                         it['video_len'], t), table, ') \n\n')
-    log(block)
-    with open(score_path, 'a') as fh:
-        fh.write(block)
+# A frame's score is a pair (v, maps): v a float64 array whose first two numbers are the PSNR / SSIM of the frame's line -- [psnr, ssim],
+# a FOV table, or empty (no scores) -- which is also what a clip and the run sum up; maps {folder: uint8 [h, w, 3]}, the frame's
+# confidence images (conf_map mode alone).
+def _scores_tail(v):
+    return 'PSNR: {:.5f} SSIM: {:.5f} '.format(v.flat[0], v.flat[1]) if v.size else ''
 
 
-VIDEO_MODE_MESSAGE = ("--video_out writes the frames of the qual_quan loop; --eval_mode %s writes no result video (drop --video_out)")
+def _line_summary(head, v, t, total):
+    """One line (eval_qual_quan.py:106-124,140-143; eval_quan_conf_map.py:115,179): a clip's ends in a newline, the run's begins with one."""
+    body = '{} {}({:.5f}sec)'.format(head, _scores_tail(v), t)
+    return '\n' + body if total else body + '\n'
+
+
+def _fov_summary(head, v, t, total):
+    """The reference's six-row block (eval_quan_FOV.py:93-111 a clip's, :245-264 the run's)."""
+    if total:
+        return fov_block('\n{} \n'.format(head), v, ') ({:.5f}sec)\n\n'.format(t))
+    return fov_block('{} ({:.5f}sec) \n'.format(head, t), v, ') \n\n')
+
+
+def _host_scores(run, frame, it):
+    """PSNR / SSIM of the planar float frame on the host (whatever --result_layout says); -qualitative_only: zeros, as the line prints."""
+    if run.qualitative_only:
+        return np.zeros(2)
+    gt, frame = it['HR_UW'], frame.contiguous()
+    if run.config.flag_HD_in:
+        # the result is `scale` times the ground truth; both scores are those of its bicubic down-scale: the PSNR of the clamped image
+        # (models/loss/Loss.py:91-92,141), the SSIM of the unclamped one (eval_qual_quan.py:85-92, whose cv2.resize(INTER_CUBIC) is this
+        # filter at an exact integer factor)
+        d = F.interpolate(frame[None], scale_factor=1.0 / run.config.scale, mode='bicubic', align_corners=False)[0]
+        return np.array([psnr(d.clamp(0, 1), gt), ssim(d, gt)])
+    return np.array([psnr(frame, gt), ssim(frame, gt)])
+
+
+def _host_fov(run, frame, it):
+    from .metrics import fov_scores_host
+    gt, frame = it['HR_UW'], frame.contiguous()
+    if frame.shape != gt.shape:
+        raise RuntimeError('--eval_mode %s: result %s and ground truth %s differ in shape' % (run.config.EVAL.eval_mode, tuple(frame.shape), tuple(gt.shape)))
+    return fov_scores_host(frame, gt)
+
+
+def _device_scores(run, outs, items, vis=None):
+    """--metrics device (extension, default 'host'): the scores of a network call's frames from ONE refvsr_score_frames launch (FOV: one
+    refvsr_score_regions launch) on the caller's current stream -- which already waits for the results, pipelined mode included:
+    INTEGRATION.md -- crossing to the host as 16 bytes per frame (FOV: 7 rectangles x 16); the frame itself is only copied when an
+    image is written."""
+    from . import ops
+    from .metrics import fov_rects, fov_table, psnr_from_mse
+    gts = [it['HR_UW'].to(run.dev) for it in items]              # (decoded bytes, channels-last: a quarter of the float frame)
+    # flag_HD_in: the result is `scale` times the ground truth and the scores are those of its bicubic down-scale, which the
+    # kernel forms while it stages its tiles (refvsr_score_frames_down): the big frame is read once where it lies
+    down = int(run.config.scale) if run.config.flag_HD_in else 1     # (no FOV mode here: evaluate() refuses it for these configs)
+    for o, g in zip(outs, gts):
+        if tuple(o[0].shape) != (3, down * g.shape[-2], down * g.shape[-1]):
+            raise RuntimeError('--metrics device: result %s and ground truth %s differ in shape' % (tuple(o[0].shape), tuple(g.shape)))
+    if run.mode is FOV:
+        h, w = gts[0].shape[-2:]
+        sums = ops.score_regions([o[0] for o in outs], gts, fov_rects(h, w)).cpu().numpy()
+        return [(fov_table(sm, h, w), {}) for sm in sums]
+    sc = ops.score_frames([o[0] for o in outs], gts, win=7, **({'down': down} if down != 1 else {})).cpu().tolist()
+    return [(np.array([psnr_from_mse(m), s]), {}) for m, s in sc]
+
+
+def _colour(run, outs, items, vis):
+    """The windows' 'eval_vis' dicts -> per window its images on the host, in the place of its scores: ONE conf_colormap launch."""
+    from . import ops
+    imgs = [x.cpu() for x in ops.conf_colormap([v[src] for v in vis for _, src in CONF_MAP_DIRS])]
+    k = len(CONF_MAP_DIRS)
+    return [(np.zeros(0), dict((CONF_MAP_DIRS[j][0], imgs[b * k + j]) for j in range(k))) for b in range(len(vis))]
+
+
+# What the three modes differ in -- host: a frame's score when no launch of the call gave it; writes: whether the input / result (/ map)
+# images are written; summary: the text of a clip's MEAN and the run's TOTAL; total: the run's v; end: what the score file gets after a summary
+Mode = collections.namedtuple('Mode', 'host writes summary total end')
+QUAL = Mode(_host_scores, lambda run: not run.quantitative_only, _line_summary,
+            lambda res, n: np.array([sum(res['psnr']) / n, sum(res['ssim']) / n]), '\n')
+FOV = Mode(_host_fov, lambda run: False, _fov_summary, lambda res, n: sum(res['fov']) / n if res['fov'] else np.zeros((6, 3, 2)), '')
+CONF = Mode(None, lambda run: True, _line_summary, lambda res, n: np.zeros(0), '\n')
+
+
+def _host_frame(out):
+    """A result [1,3,h,w] on the host -> (what write_frame takes: 'uint8' results stay bytes, the float frame the host scores take).
+    (result_dtype 'uint8' / 'float16', extensions: the scores are then those of the quantised frame; the PNG bytes are the same.)"""
+    raw = out[0].cpu()
+    frame = raw.float()
+    return (raw, frame / 255.0) if raw.dtype == torch.uint8 else (frame, frame)
+
+
+class _Run(object):
+    """One evaluate() call: its options, each read once; the clip's sums; the video writer; the result dict."""
+
+    def __init__(self, config, net, log, mode):
+        E = config.EVAL
+        self.config, self.net, self.log, self.mode, self.data = config, net, log, mode, E.data
+        self.qualitative_only = bool(getattr(E, 'qualitative_only', False))
+        self.quantitative_only = bool(getattr(E, 'quantitative_only', False))
+        self.writes, self.video, self.use_ids = mode.writes(self), getattr(E, 'video_out', None), getattr(E, 'use_frame_ids', True)
+        # --frame_group G (extension, default 1 = the reference's loop): G consecutive windows of a clip per network call
+        # (SRNet.forward_group: the backward branches of the G frames as multi-map launches; results bit-identical); the per-frame time in
+        # the score lines is then the group's time / G
+        self.G = max(1, int(getattr(E, 'frame_group', 1) or 1))
+        self.ckpt_name = os.path.basename(E.ckpt_abs_name) if E.ckpt_abs_name else 'seeded'
+        root = os.path.join(E.LOG_DIR.save, E.eval_mode, self.ckpt_name.split('.')[0])
+        self.out_root = os.path.join(root, E.data, datetime.datetime.now().strftime('%Y_%m_%d_%H%M'))
+        os.makedirs(root, exist_ok=True)
+        self.score_path = os.path.join(root, 'score_%s_%s.txt' % (E.data, E.eval_mode))
+        self.ds = ClipSet(config)
+        self.dev = next(net.parameters()).device
+        # what scores (or colours) all frames of a network call in one launch; None: every frame is scored on the host
+        on_device = getattr(E, 'metrics', 'host') == 'device' and not self.qualitative_only
+        self.launch = _colour if mode is CONF else _device_scores if on_device else None
+        # (the state to restore is the net's own: a caller's net may have been switched on without config.pipelined saying so)
+        engines = getattr(net.Network, '_engines', None)
+        self.was_pipelined = bool(engines[0].pipelined) if engines else bool(getattr(config, 'pipelined', False))
+        self.res = {'psnr': [], 'ssim': [], 'seconds': [], 'frames': 0}
+        if mode is FOV:
+            self.res['fov'] = []
+        self.said, self.writer, self.writer_clip, self.prev = False, None, None, None
+        self.clip_v, self.clip_t, self.clip_n = 0.0, 0.0, 0
+
+    def say(self, text, end='\n'):
+        """log + score file: the run's first write starts the file."""
+        self.log(text)
+        with open(self.score_path, 'a' if self.said else 'w') as fh:
+            fh.write(text + end)
+        self.said = True
+
+    def write_video(self, it, y):
+        """--video_out y4m (extension): the frame's 'yuv' [1, 3sh/2, sw] -- 1.5 samples per pixel cross to the host -- appended to
+        <out_root>/y4m/<clip>.y4m, one file per clip."""
+        from .yuv import Y4MWriter
+        a = y[0].cpu().numpy()
+        if self.writer_clip != it['video_name']:
+            self.close_video()
+            path = os.path.join(self.out_root, 'y4m', '%s.y4m' % it['video_name'])
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            self.writer = Y4MWriter(path, a.shape[0] * 2 // 3, a.shape[1], self.config.result_yuv, getattr(self.config.EVAL, 'video_fps', None) or (30, 1),
+                                    getattr(self.config, 'yuv_range', None) or 'limited')
+            self.writer_clip = it['video_name']
+            self.res.setdefault('videos', []).append(path)
+        self.writer.write(a)
+
+    def close_video(self):
+        if self.writer is not None:
+            self.writer.close()
+        self.writer = self.writer_clip = None
+
+    def emit(self, it, out, lr_c, dt, score, yuv):
+        """One frame of a call: its video frame, its score (the host's unless the call's launch gave it), its line, its images, the sums."""
+        if self.video:
+            self.write_video(it, yuv)
+        if score is None or self.writes:                 # (else nothing reads the frame: it stays on the device)
+            img, frame = _host_frame(out)
+        v, maps = score if score is not None else (self.mode.host(self, frame, it), {})
+        self.say('[EVAL {}|{}|{}][{}/{}][{}/{}] {} {}({:.5f}sec)'.format(
+            self.config.mode, self.data, it['video_name'], it['video_idx'] + 1, it['video_len'], it['frame_idx'] + 1, it['frame_len'],
+            it['frame_name'], _scores_tail(v), dt))
+        if self.writes:
+            name = os.path.join(it['video_name'], it['frame_name'].split('.')[0])
+            for fmt in ('png', 'jpg'):
+                for folder, im in [('input', lr_c), ('output', img)] + [(f, m.permute(2, 0, 1)) for f, m in maps.items()]:
+                    write_frame(os.path.join(self.out_root, fmt, folder, '%s.%s' % (name, fmt)), im)
+        self.clip_v, self.clip_t, self.clip_n, self.prev = self.clip_v + v, self.clip_t + dt, self.clip_n + 1, it
+        if v.size:
+            self.res['psnr'].append(float(v.flat[0]))
+            self.res['ssim'].append(float(v.flat[1]))
+        if self.mode is FOV:
+            self.res['fov'].append(v)
+        self.res['seconds'].append(dt)
+        self.res['frames'] += 1
+
+    def call(self, items, group=False, first=False):
+        """One network call for the windows `items` and what follows it.  The two entries are the reference's own net(window) and
+        forward_group; conf_map: the first is called with is_log=True and returns 'eval_vis', the second with want_conf=True.  Timed: from
+        before the inputs' copy to the device to after the synchronize; scoring, colouring and writing are not."""
+        t0 = time.time()
+        if group:
+            lrs, rfs = (stack_frames([it[k] for it in items]).to(self.dev) for k in ('LR_UW', 'LR_REF_W'))
+            if lrs.dtype != torch.uint8:
+                lrs, rfs = lrs.float().contiguous(), rfs.float().contiguous()
+            got = self.net.forward_group(lrs, rfs, [it['frame_ids'] for it in items], is_first_frame=first, **({'want_conf': True} if self.mode is CONF else {}))
+            outs, vis, yuv = got['result'], got['eval_vis'] if self.mode is CONF else None, got.get('yuv')
+        else:
+            it, = items
+            lrs, rfs = it['LR_UW'][None].to(self.dev), it['LR_REF_W'][None].to(self.dev)
+            kw = {'frame_ids': it['frame_ids']} if self.use_ids and 'frame_ids' in it else {}
+            got = self.net(lrs, rfs, it['is_first'], is_log=self.mode is CONF, is_train=False, **kw)
+            outs, vis, yuv = [got['result']], [got['eval_vis']] if self.mode is CONF else None, [got.get('yuv')]
+        torch.cuda.synchronize()
+        dt = (time.time() - t0) / len(items)
+        scores = self.launch(self, outs, items, vis) if self.launch else [None] * len(items)
+        for b, it in enumerate(items):
+            self.emit(it, outs[b], lrs[b, lrs.shape[1] // 2], dt, scores[b], yuv[b] if self.video else None)
+
+    def clip_summary(self):
+        """The clip's MEAN line / block, named for the clip it summarises; resets the clip's sums."""
+        if self.clip_n:
+            head = '[MEAN EVAL {}|{}|{}][{}/{}]'.format(self.config.mode, self.data, self.prev['video_name'], self.prev['video_idx'], self.prev['video_len'])
+            self.say(self.mode.summary(head, self.clip_v / self.clip_n, self.clip_t / self.clip_n, False), self.mode.end)
+        self.clip_v, self.clip_t, self.clip_n = 0.0, 0.0, 0
+
+    def total(self):
+        n = max(self.res['frames'], 1)
+        head = '[TOTAL {}|{}]'.format(self.ckpt_name, self.data)
+        self.say(self.mode.summary(head, self.mode.total(self.res, n), sum(self.res['seconds']) / n, True), self.mode.end)
+
+    def loop(self):
+        """The per-frame loop (eval_qual_quan.py:39-128, eval_quan_FOV.py:55-232, eval_quan_conf_map.py:32-174).  In a grouped run the
+        frames after a clip's first wait for a full group; the first goes alone through net(window) -- conf_map: through a forward_group
+        of its one window, so that every call of the run returns its maps the same way."""
+        pending = []
+
+        def flush():
+            if pending:
+                self.call(pending, group=True)
+                del pending[:]
+        for i in range(len(self.ds)):
+            it = self.ds[i]
+            if it.get('is_continue'):
+                continue
+            if it['is_first']:
+                flush()
+                self.clip_summary()
+                self.net.Network.reset()
+            grouped = self.G > 1 and self.use_ids and 'frame_ids' in it
+            if grouped and not it['is_first']:
+                pending.append(it)
+                if len(pending) == self.G:
+                    flush()
+            elif grouped and self.mode is CONF:
+                self.call([it], group=True, first=True)
+            else:
+                self.call([it])
+        flush()
+
+
+def evaluate(config, net=None, log=print):
+    """The reference's three evaluation loops as one; `--eval_mode` picks the per-mode entry (QUAL / FOV / CONF above).
+    Returns dict(psnr=[..], ssim=[..], frames=N, seconds=[..], score_file, output_root).
+    qual_quan (any other name): eval_qual_quan counterpart -- per frame PSNR / SSIM (--metrics host | device) and the input and result
+    images (-quantitative_only: no images; -qualitative_only: no scores; --video_out y4m: also a video per clip, res['videos']).
+    A name with FOV in it: eval_quan_FOV counterpart -- a frame's score is its FOV table (metrics.fov_table, [6 keys][fi, fo, fr][psnr, ssim]),
+    whose key 1 fi pair is the per-frame line; the summaries are the reference's six-row blocks; no image is written (the reference has
+    that part commented out); the tables are returned as res['fov'].
+    A name with conf_map in it: eval_quan_conf_map counterpart -- no scores (psnr / ssim stay empty; --metrics, -qualitative_only and
+    -quantitative_only have no effect, as in the reference's loop): per frame the input, the result and the four maps of 'eval_vis'
+    coloured by ONE ops.conf_colormap launch per network call (CONF_MAP_DIRS names the folders); with --frame_group G > 1 the maps come
+    from forward_group(want_conf=True).  RefVSR_IR has no such maps (the reference fails on None['conf_map'])."""
+    E = config.EVAL
+    mode = FOV if 'FOV' in str(E.eval_mode) else CONF if 'conf_map' in str(E.eval_mode) else QUAL
+    video = getattr(E, 'video_out', None)
+    if mode is CONF and config.network == 'RefVSR_IR':
+        raise RuntimeError('--eval_mode %s: RefVSR_IR returns no confidence maps (config %s)' % (E.eval_mode, config.get('config')))
+    if video and mode is not QUAL:
+        raise RuntimeError(VIDEO_MODE_MESSAGE % E.eval_mode)
+    if video and video != 'y4m':
+        raise RuntimeError("--video_out: 'y4m' is the only container (got %r)" % (video,))
+    if video and getattr(config, 'result_yuv', None) not in ('i420', 'i420p10'):
+        raise RuntimeError("--video_out y4m needs config.result_yuv = 'i420' | 'i420p10' (Y4M frames are planar), got %r" % (getattr(config, 'result_yuv', None),))
+    if mode is FOV and config.flag_HD_in:
+        raise RuntimeError('--eval_mode %s: flag_HD_in configs are not supported (the reference scores a cv2.resize(INTER_CUBIC) of the result)' % E.eval_mode)
+    if mode is CONF:
+        config.save_sample = True            # eval_quan_conf_map.py:23: Network.forward(is_log=True) then returns 'eval_vis'
+    if net is None:
+        from . import SRNet
+        if config.device != 'cuda':
+            raise RuntimeError('refvsr_amd has no CPU path; run on the GPU (drop --cpu)')
+        net = SRNet(config).to('cuda').eval()
+        if E.ckpt_abs_name:
+            log('Loading checkpoint %s: %s' % (E.ckpt_abs_name, load_checkpoint(net, E.ckpt_abs_name)))
+    if mode is CONF:
+        net.Network.config.save_sample = True            # (a caller's net may carry a config of its own)
+    run = _Run(config, net, log, mode)
+    if run.G > 1:
+        net.Network.set_pipelined(True)          # (restored at the end: the caller's plain net(...) calls keep their stream contract)
+    try:
+        with torch.no_grad():
+            run.loop()
+    finally:
+        run.close_video()
+        if run.G > 1 and not run.was_pipelined:
+            torch.cuda.synchronize()
+            net.Network.set_pipelined(False)
+    run.clip_summary()
+    run.total()
+    run.res['score_file'], run.res['output_root'] = run.score_path, run.out_root
+    return run.res
 
 
 # ------------------------------------------------------------------------------------------------ CLI
