@@ -620,6 +620,38 @@ int refvsr_result_to_yuv420(const void* const* src, int src_fmt, void* const* ds
                             const double* coef9, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Y'CbCr 4:2:0 input frames (extension, no ABI bump: added symbols only).  The reference's loader reads PNGs into RGB bytes
+ * (data_loader/utils.py:12-41); a video decoder delivers NV12 or P010 and a .y4m file holds I420.  The two entry points stand in for
+ * that loader for video sources: they replace the consumer's host-side Y'CbCr -> RGB conversion (cv2.cvtColor(..,
+ * COLOR_YUV2RGB_NV12) and its like) in front of the network, so that 1.5 samples per pixel reach the device instead of 3.  The
+ * specification is the numpy model refvsr_amd/yuv.py:yuv420_to_rgb; the kernel returns its bits.
+ *   Frames and formats as above (REFVSR_YUV_*); a P010 sample's code is sample >> 6 (the low six bits are ignored), an I420P10
+ *   sample's is sample & 1023.
+ *   coef: HOST array of nine doubles oy, iy = 1 / sy, oc, ic = 1 / sc, cr_r = 2 (1 - kr), cb_b = 2 (1 - kb), kr, kb, ikg = 1 / kg
+ *   (yuv.py:decode_coefficients): no division happens on the device.
+ *   Chroma at luma pixel (y, x), centre-sited (the inverse siting of the box average refvsr_result_to_yuv420 takes): (cy, cx) =
+ *   (y >> 1, x >> 1), cy' = clamp(cy + (y & 1 ? 1 : -1), 0, h / 2 - 1), cx' likewise,
+ *   m = (9 C[cy][cx] + 3 C[cy'][cx] + 3 C[cy][cx'] + C[cy'][cx']) / 16 (an integer below 2^15 times a power of two: exact);
+ *   REFVSR_YUV_CHROMA_NEAREST: m = C[cy][cx].
+ *   Per pixel in float64, every operation rounded on its own (no fused multiply-add):  ey = (Y - oy) iy;  ecb = (mcb - oc) ic;
+ *   ecr = (mcr - oc) ic;  r = ey + cr_r ecr;  b = ey + cb_b ecb;  g = ((ey - kr r) - kb b) ikg;  each of r, g, b clamped to [0, 1]
+ *   (decoded video is routinely out of gamut), then rounded once to float32.
+ * refvsr_yuv420_in_max_frames: replaces nothing -- REFVSR_YUV420_IN_MAX_FRAMES of the built library (a value, not a status).
+ * refvsr_yuv420_to_rgb: nframes <= REFVSR_YUV420_IN_MAX_FRAMES frames of one h x w (even, >= 2, h w <= 2^29) in ONE launch on `stream`:
+ *     src: HOST array of device pointers, one dense frame each at any multiple of its sample size (8-bit frames inside a
+ *          [t, 3h/2, w] window are 3 h w / 2 bytes apart: odd phases are the normal case);
+ *     dst: HOST array of device pointers to planar fp32 [3][h][w], 16-byte aligned: the engine's own frame format, what
+ *          refvsr_ingest_u8 writes.
+ *   Every argument is checked before any device work: null table, null entry, frame count, odd or non-positive h / w, unknown
+ *   format or chroma mode, null coefficients, alignment.
+ * ------------------------------------------------------------------------------------------ */
+#define REFVSR_YUV420_IN_MAX_FRAMES 16
+enum { REFVSR_YUV_CHROMA_BILINEAR = 0, REFVSR_YUV_CHROMA_NEAREST = 1 };
+int refvsr_yuv420_in_max_frames(void);
+int refvsr_yuv420_to_rgb(const void* const* src, float* const* dst, int nframes, int h, int w, int format, int chroma,
+                         const double* coef, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Inter-frame alignment
  * ------------------------------------------------------------------------------------------ */
 /* models/utils.py:35-43 `warp`: linspace(-1,1) base grid + flow/((Win-1)/2), grid_sample(bilinear,

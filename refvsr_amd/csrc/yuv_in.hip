@@ -1,0 +1,214 @@
+// Y'CbCr 4:2:0 input frames (extension: the reference's loader reads PNGs, data_loader/utils.py:12-41; a video decoder delivers NV12 or
+// P010 and a .y4m file holds I420, 1.5 samples per pixel where RGB has 3).  refvsr_yuv420_to_rgb turns up to REFVSR_YUV420_IN_MAX_FRAMES
+// NV12 | I420 | P010 | I420P10 frames of one geometry into the planar fp32 frames the engine owns, in one launch -- the twin of
+// refvsr_ingest_u8 on the way in and the inverse of refvsr_result_to_yuv420 (yuv.hip) on the way out.
+//
+// Exactness: the kernel returns the bits of refvsr_amd/yuv.py:yuv420_to_rgb.  The chroma tap sum (9 a + 3 b + 3 c + d, below 2^15) is
+// formed in integers and is exact in any order; everything behind it is float64 with every operation rounded on its own, in the
+// model's order, the nine coefficients computed once in Python (no division on the device).  Contraction is OFF for this file by
+// construction, to keep the kernel the same function as the model -- but no test can pin that: the final rounding to float32 hides
+// nearly every one-ulp float64 difference a fused multiply-add could make.  float32 arithmetic is NOT the same function (it differs
+// on about 42 % of random samples).
+//
+// Shape: bandwidth-bound (1.5 or 3 bytes in, 12 out per pixel), no reuse worth LDS.  A thread owns 2 luma rows x 8 columns: the two
+// rows share their chroma row pair, the three chroma rows (above, own, below) come from cache.  A workgroup is 64 column groups x 4 row
+// pairs, so every wave walks ONE row pair and the address phase of each of its loads is wave-uniform: a source frame lies at any
+// multiple of its sample size (8-bit frames inside a [t, 3h/2, w] window are 3hw/2 bytes apart: 702 at 18 x 26) and w is only even,
+// so a row piece is loaded with the widest of 16 / 8 / 4 / 2 / 1-byte loads its address allows; a ragged row end goes element by
+// element.  Destination rows are 8-byte aligned: float4 stores where w % 4 == 0, float2 otherwise.  One work item per thread, the
+// grid sized by the work (no loop); blockIdx.y is the frame.  Plain vector stores only.
+#pragma clang fp contract(off)
+#include "common.h"
+
+struct YuvInArgs {
+    const void* src[REFVSR_YUV420_IN_MAX_FRAMES];
+    float* dst[REFVSR_YUV420_IN_MAX_FRAMES];
+    int h, w;
+    int gpr;                 // column groups of 8 per row pair
+    int gxb;                 // workgroups along a row pair
+    int nearest;             // chroma mode: 0 bilinear (centre-sited), 1 nearest
+    double k[9];             // oy, iy, oc, ic, cr_r, cb_b, kr, kb, ikg
+};
+
+template <int L> struct YinWord;
+template <> struct YinWord<16> { using T = uint4; };
+template <> struct YinWord<8> { using T = uint2; };
+template <> struct YinWord<4> { using T = uint32_t; };
+template <> struct YinWord<2> { using T = uint16_t; };
+template <> struct YinWord<1> { using T = uint8_t; };
+
+template <int L, int B>
+__device__ __forceinline__ void yin_words(const void* p, void* v) {
+    using T = typename YinWord<L>::T;
+#pragma unroll
+    for (int q = 0; q < B / L; ++q) reinterpret_cast<T*>(v)[q] = reinterpret_cast<const T*>(p)[q];
+}
+
+// N samples (2 .. 16 bytes) from an address aligned to its sample: all of them (n == N) with the widest loads the address allows, or
+// the first n element by element (the rest are 0)
+template <typename S, int N>
+__device__ __forceinline__ void yin_load(const S* __restrict__ p, int n, S* v) {
+    constexpr int B = N * (int)sizeof(S);
+    const uintptr_t a = (uintptr_t)p;
+    if (n == N) {
+        if (B >= 16 && (a & 15) == 0) yin_words<B >= 16 ? 16 : B, B>(p, v);
+        else if (B >= 8 && (a & 7) == 0) yin_words<B >= 8 ? 8 : B, B>(p, v);
+        else if (B >= 4 && (a & 3) == 0) yin_words<B >= 4 ? 4 : B, B>(p, v);
+        else if (sizeof(S) == 2 || (a & 1) == 0) yin_words<2, B>(p, v);
+        else yin_words<1, B>(p, v);
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = i < n ? p[i] : (S)0;
+    }
+}
+
+template <int FMT, typename S>
+__device__ __forceinline__ int yin_code(S s) {
+    if constexpr (FMT == REFVSR_YUV_P010) return (int)s >> 6;                  // the low six bits are ignored, whatever they hold
+    else if constexpr (FMT == REFVSR_YUV_I420P10) return (int)s & 1023;
+    else return (int)s;
+}
+
+template <int FMT>
+__global__ void __launch_bounds__(256) yuv420_in_kernel(YuvInArgs a) {
+    constexpr bool D10 = FMT == REFVSR_YUV_P010 || FMT == REFVSR_YUV_I420P10;
+    constexpr bool SEMI = FMT == REFVSR_YUV_NV12 || FMT == REFVSR_YUV_P010;
+    using S = typename std::conditional<D10, uint16_t, uint8_t>::type;
+    const int h = a.h, w = a.w, h2 = h >> 1, w2 = w >> 1;
+    const int by = (int)(blockIdx.x / a.gxb) * 4 + (int)threadIdx.y;           // the row pair: one per wave
+    const int g = (int)(blockIdx.x % a.gxb) * 64 + (int)threadIdx.x;
+    if (by >= h2 || g >= a.gpr) return;
+    const S* __restrict__ src = reinterpret_cast<const S*>(a.src[blockIdx.y]);
+    float* __restrict__ dst = a.dst[blockIdx.y];
+    const size_t hw = (size_t)h * w;
+    const int x0 = g * 8;
+    const int n = w - x0 < 8 ? w - x0 : 8;                                     // pixels of the group per row (even)
+    const int nb = n >> 1;                                                     // its chroma blocks
+    const int bx0 = x0 >> 1;
+    const int cxl = bx0 > 0 ? bx0 - 1 : 0, cxr = bx0 + nb < w2 ? bx0 + nb : w2 - 1;       // the clamped neighbour columns
+
+    // luma: two row pieces
+    alignas(16) S yv[2][8];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) yin_load<S, 8>(src + (size_t)(2 * by + r) * w + x0, n, yv[r]);
+
+    // chroma codes of the rows above (clamped), own, below (clamped): [left neighbour | the group's four blocks | right neighbour]
+    int cb[3][6], cr[3][6];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int cy = q == 0 ? (by > 0 ? by - 1 : 0) : q == 1 ? by : (by + 1 < h2 ? by + 1 : h2 - 1);
+        int rb, rr;
+        cb[q][5] = cr[q][5] = 0;                                               // (read by the unused pixels of a ragged group)
+        if constexpr (SEMI) {
+            const S* row = src + hw + (size_t)cy * w;
+            alignas(16) S c[8];
+            alignas(4) S l[2], e[2];
+            yin_load<S, 8>(row + x0, n, c);
+            yin_load<S, 2>(row + 2 * cxl, 2, l);
+            yin_load<S, 2>(row + 2 * cxr, 2, e);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { cb[q][1 + j] = yin_code<FMT>(c[2 * j]); cr[q][1 + j] = yin_code<FMT>(c[2 * j + 1]); }
+            cb[q][0] = yin_code<FMT>(l[0]);
+            cr[q][0] = yin_code<FMT>(l[1]);
+            rb = yin_code<FMT>(e[0]);
+            rr = yin_code<FMT>(e[1]);
+        } else {
+            const S* rowb = src + hw + (size_t)cy * w2;
+            const S* rowr = rowb + (hw >> 2);
+            alignas(8) S c0[4], c1[4];
+            yin_load<S, 4>(rowb + bx0, nb, c0);
+            yin_load<S, 4>(rowr + bx0, nb, c1);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { cb[q][1 + j] = yin_code<FMT>(c0[j]); cr[q][1 + j] = yin_code<FMT>(c1[j]); }
+            cb[q][0] = yin_code<FMT>(rowb[cxl]);
+            cr[q][0] = yin_code<FMT>(rowr[cxl]);
+            rb = yin_code<FMT>(rowb[cxr]);
+            rr = yin_code<FMT>(rowr[cxr]);
+        }
+        // the right neighbour stands behind the group's last block (a ragged group ends the row: its neighbour is that block again)
+#pragma unroll
+        for (int j = 1; j <= 4; ++j)
+            if (j == nb) { cb[q][1 + j] = rb; cr[q][1 + j] = rr; }
+    }
+
+    const double oy = a.k[0], iy = a.k[1], oc = a.k[2], ic = a.k[3], cr_r = a.k[4], cb_b = a.k[5], kr = a.k[6], kb = a.k[7], ikg = a.k[8];
+    const bool w4 = (w & 3) == 0;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int f = r == 0 ? 0 : 2;                                          // the far chroma row: above an even y, below an odd one
+        alignas(16) float o[3][8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int c = 1 + (i >> 1), e = (i & 1) ? c + 1 : c - 1;           // own block, and its neighbour on the pixel's side
+            int mb, mr;
+            if (a.nearest) {
+                mb = 16 * cb[1][c];
+                mr = 16 * cr[1][c];
+            } else {
+                mb = 9 * cb[1][c] + 3 * cb[f][c] + 3 * cb[1][e] + cb[f][e];
+                mr = 9 * cr[1][c] + 3 * cr[f][c] + 3 * cr[1][e] + cr[f][e];
+            }
+            const double ey = ((double)yin_code<FMT>(yv[r][i]) - oy) * iy;
+            const double ecb = ((double)mb * 0.0625 - oc) * ic;
+            const double ecr = ((double)mr * 0.0625 - oc) * ic;
+            const double R = ey + cr_r * ecr;
+            const double B = ey + cb_b * ecb;
+            const double G = ((ey - kr * R) - kb * B) * ikg;
+            o[0][i] = (float)fmin(fmax(R, 0.0), 1.0);
+            o[1][i] = (float)fmin(fmax(G, 0.0), 1.0);
+            o[2][i] = (float)fmin(fmax(B, 0.0), 1.0);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float* p = dst + c * hw + (size_t)(2 * by + r) * w + x0;
+            if (n == 8 && w4) {
+                reinterpret_cast<float4*>(p)[0] = reinterpret_cast<const float4*>(o[c])[0];
+                reinterpret_cast<float4*>(p)[1] = reinterpret_cast<const float4*>(o[c])[1];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < nb) reinterpret_cast<float2*>(p)[j] = reinterpret_cast<const float2*>(o[c])[j];
+            }
+        }
+    }
+}
+
+extern "C" int refvsr_yuv420_in_max_frames(void) { return REFVSR_YUV420_IN_MAX_FRAMES; }
+
+extern "C" int refvsr_yuv420_to_rgb(const void* const* src, float* const* dst, int nframes, int h, int w, int format, int chroma,
+                                    const double* coef, void* stream) {
+    RV_CHECK(src && dst, "yuv420_to_rgb: null frame table");
+    RV_CHECK(nframes >= 1 && nframes <= REFVSR_YUV420_IN_MAX_FRAMES, "yuv420_to_rgb: 1..%d frames per launch", REFVSR_YUV420_IN_MAX_FRAMES);
+    RV_CHECK(h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0 && (long)h * w <= (1L << 29),
+             "yuv420_to_rgb: h, w must be even and positive, h * w <= 2^29 (got %d x %d)", h, w);
+    RV_CHECK(format >= REFVSR_YUV_NV12 && format <= REFVSR_YUV_I420P10, "yuv420_to_rgb: unknown yuv format %d", format);
+    RV_CHECK(chroma == REFVSR_YUV_CHROMA_BILINEAR || chroma == REFVSR_YUV_CHROMA_NEAREST,
+             "yuv420_to_rgb: chroma must be REFVSR_YUV_CHROMA_BILINEAR | REFVSR_YUV_CHROMA_NEAREST (got %d)", chroma);
+    RV_CHECK(coef, "yuv420_to_rgb: null coefficients");
+    const uintptr_t smask = (format == REFVSR_YUV_P010 || format == REFVSR_YUV_I420P10) ? 1 : 0;
+    YuvInArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < nframes; ++i) {
+        RV_CHECK(src[i] && dst[i], "yuv420_to_rgb: null pointer (frame %d)", i);
+        RV_CHECK(((uintptr_t)src[i] & smask) == 0 && ((uintptr_t)dst[i] & 15) == 0,
+                 "yuv420_to_rgb: source must be aligned to its samples, destination to 16 bytes (frame %d)", i);
+        a.src[i] = src[i];
+        a.dst[i] = dst[i];
+    }
+    a.h = h;
+    a.w = w;
+    a.gpr = (w + 7) / 8;
+    a.gxb = (a.gpr + 63) / 64;
+    a.nearest = chroma == REFVSR_YUV_CHROMA_NEAREST;
+    for (int i = 0; i < 9; ++i) a.k[i] = coef[i];
+    const dim3 grid((unsigned)(a.gxb * ((h / 2 + 3) / 4)), (unsigned)nframes), block(64, 4);
+    hipStream_t st = (hipStream_t)stream;
+    switch (format) {
+        case REFVSR_YUV_NV12: hipLaunchKernelGGL((yuv420_in_kernel<REFVSR_YUV_NV12>), grid, block, 0, st, a); break;
+        case REFVSR_YUV_I420: hipLaunchKernelGGL((yuv420_in_kernel<REFVSR_YUV_I420>), grid, block, 0, st, a); break;
+        case REFVSR_YUV_P010: hipLaunchKernelGGL((yuv420_in_kernel<REFVSR_YUV_P010>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((yuv420_in_kernel<REFVSR_YUV_I420P10>), grid, block, 0, st, a); break;
+    }
+    RV_LAUNCH_CHECK();
+    return 0;
+}

@@ -47,10 +47,27 @@ def _flow_pairs(fr, restart):
     return need
 
 
-def _input_kind(lrs, refs):
-    """What a window's frames were made from: None for float32 frames, else the byte layouts (ops.u8_layout) of lr and ref.  Contexts
-    of another kind never match by content (a float frame is not compared with a byte frame)."""
+def _input_kind(lrs, refs, input_yuv=None):
+    """What a window's frames were made from: None for float32 frames, the byte layouts (ops.u8_layout) of lr and ref for uint8 RGB
+    frames, ('yuv', format, matrix, range, chroma) for Y'CbCr 4:2:0 frames (config.input_yuv: frames [3h/2, w]).  Contexts of another
+    kind never match by content (a float frame is not compared with a byte frame, nor an RGB byte frame with a 4:2:0 one)."""
+    if input_yuv is not None:
+        return ('yuv',) + tuple(input_yuv)
     return None if lrs.dtype != torch.uint8 else (ops.u8_layout(lrs), ops.u8_layout(refs))
+
+
+def _is_yuv(kind):
+    return kind is not None and kind[0] == 'yuv'
+
+
+def check_yuv_window(lrs, refs, fmt, dim, shape):
+    """config.input_yuv = fmt: lrs and refs are cuda tensors of `dim` dimensions, `shape` in words, dense 4:2:0 frames of the format's
+    sample type; RuntimeError (one line naming the expected shape and dtype) otherwise."""
+    dt = torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16
+    for x in (lrs, refs):
+        if not (x.is_cuda and x.dim() == dim and x.dtype == dt and x.shape == lrs.shape and ops.yuv_window_kind(x, fmt) is not None):
+            raise RuntimeError("input_yuv = '%s': lrs and refs must be contiguous cuda %s %s windows of one shape, 3h/2 rows with even "
+                               "h and w (got %s %s%s)" % (fmt, dt, shape, x.dtype, tuple(x.shape), '' if x.is_contiguous() else ', not contiguous'))
 
 
 # ---- layout of the device messages (state hand-off, contexts): a spec [(name, shape, dtype)] of parts that lie back to back in a
@@ -88,15 +105,28 @@ def msg_views(buf, offset, spec, align=1, clone=False):
 class FrameCtx(object):
     """Per-frame data (functions of one (lr, ref) frame pair only)."""
 
-    def __init__(self, lr, ref, ingest=None):
+    def __init__(self, lr, ref, ingest=None, yuv=None):
         self.uid = next(_uid)
         # the context OWNS its frames (clones): it outlives the call in the window cache, and a caller that refills one
         # static input buffer in place must neither change cached data nor make the content compare see "equal" frames
-        self.kind = _input_kind(lr, ref)
+        self.kind = _input_kind(lr, ref, yuv)
         if self.kind is None:
             self.src = None
             self.lr = lr.clone()    # planar fp32 [3,h,w]
             self.ref = ref.clone()
+        elif _is_yuv(self.kind):
+            # 4:2:0 frames [3h/2, w] (yuv = config.input_yuv resolved): the copies of the source samples (half the bytes of the uint8
+            # kind, an eighth of the fp32 frames) key the content compare; the fp32 frames are filled by refvsr_yuv420_to_rgb -- now,
+            # or in the one launch over a call's new frames (ops.yuv420_ingest)
+            self.src = (lr.clone(), ref.clone())
+            h, w = ops.yuv_geometry(lr)
+            self.lr = torch.empty((3, h, w), dtype=torch.float32, device=lr.device)
+            self.ref = torch.empty((3, h, w), dtype=torch.float32, device=ref.device)
+            pairs = [(self.src[0], self.lr), (self.src[1], self.ref)]
+            if ingest is None:
+                ops.yuv420_ingest(pairs, *yuv)
+            else:
+                ingest.extend(pairs)
         else:
             # 8-bit frames: the byte copies (a quarter of the fp32 size, in the caller's layout) key the content compare; the
             # fp32 frames are filled by refvsr_ingest_u8 -- now, or in the one launch over a call's new frames when the caller
@@ -244,6 +274,7 @@ class Weights(object):
 class Engine(object):
     """Stateful per-stream executor (one stream of consecutive frames, like a reference module
     instance: RefVSR.py:96-101,279-283)."""
+    input_yuv = None            # config.input_yuv resolved by __init__: None (off) or (format, matrix, range, chroma)
 
     def __init__(self, config, weights):
         if config.scale not in (2, 4):
@@ -306,6 +337,10 @@ class Engine(object):
         # Y'CbCr 4:2:0 copies of the results (extension; default None = off, no launch): the network calls also return 'yuv', one
         # refvsr_result_to_yuv420 launch per call on the stream that receives 'result' (model.py:Network._with_yuv)
         self.result_yuv = yuv.resolve(getattr(config, 'result_yuv', None), getattr(config, 'yuv_matrix', None), getattr(config, 'yuv_range', None))
+        # Y'CbCr 4:2:0 input frames (extension; default None = off, no new code runs): windows are [t, 3h/2, w] uint8 | uint16 buffers
+        # of the format, decoded by ONE refvsr_yuv420_to_rgb launch per call over the call's new frames (FrameCtx, _ingest)
+        self.input_yuv = yuv.resolve_input(getattr(config, 'input_yuv', None), getattr(config, 'input_yuv_matrix', None),
+                                           getattr(config, 'input_yuv_range', None), getattr(config, 'input_yuv_chroma', None))
         self._pipe = None
         # stream layout of the pipelined mode when nothing is configured: 'pf_m' for one forward() per frame (round 4); an engine that
         # is driven through forward_group switches to 'pfm' (P | F | M) at its first group: with the backward branches batched the
@@ -483,7 +518,7 @@ class Engine(object):
         assert self.cache, 'contexts are kept by the id-keyed window cache (config.cache_windows)'
         fr = self._ctx(fid)
         if fr is None:
-            fr = self.ctx_pinned[fid] = FrameCtx(lr, ref)
+            fr = self.ctx_pinned[fid] = FrameCtx(lr, ref, yuv=self.input_yuv)
         with torch.cuda.device(lr.device), ops.on_stream(torch.cuda.current_stream(lr.device)):
             self.pyramid(fr)
             strict, self.ctx_strict = self.ctx_strict, False
@@ -524,7 +559,7 @@ class Engine(object):
         assert fr is None or fr.conf is None, 'context %r exists already (prepared)' % (fid,)
         pinned = fr is None
         if fr is None:
-            fr = FrameCtx(lr, ref)
+            fr = FrameCtx(lr, ref, yuv=self.input_yuv)
         with torch.cuda.device(lr.device), ops.on_stream(torch.cuda.current_stream(lr.device)):
             if fr.lr8 is None:
                 fr.lr8 = ops.pack_nhwc16(fr.lr, 8)
@@ -952,20 +987,34 @@ class Engine(object):
         pend = [] if ingest is None else ingest
         out = [self._window_frames(*wins[0], pend)] if len(wins) == 1 else self._id_frames(wins, pend)
         if ingest is None:
-            ops.ingest_u8(pend)
+            self._ingest(pend)
         return out
+
+    def _ingest(self, pend):
+        """The conversions of a call's new frames [(source, fp32 frame)] in one launch: uint8 RGB (refvsr_ingest_u8) or, under
+        config.input_yuv, 4:2:0 frames (refvsr_yuv420_to_rgb); float windows leave nothing pending."""
+        if self.input_yuv is None:
+            ops.ingest_u8(pend)
+        elif pend:
+            ops.yuv420_ingest(pend, *self.input_yuv)
+
+    def _geometry(self, lrs):
+        """(t, h, w) of a window of any kind: [t,3,h,w] RGB frames, or [t, 3h/2, w] 4:2:0 frames under config.input_yuv."""
+        if self.input_yuv is not None:
+            return (lrs.shape[0],) + ops.yuv_geometry(lrs)
+        return lrs.shape[0], lrs.shape[-2], lrs.shape[-1]
 
     def _id_frames(self, wins, pend):
         """The id-keyed lookup for B >= 1 windows: a frame's context comes from the id cache, else from the contexts prepared / imported
         ahead of their first window (prepare_context), else it is new.  The cache keeps the union of the windows' frames."""
-        if self.id_cache and next(iter(self.id_cache.values())).lr.shape != wins[0][0].shape[1:]:
+        if self.id_cache and tuple(next(iter(self.id_cache.values())).lr.shape[1:]) != self._geometry(wins[0][0])[1:]:
             self.id_cache, self.flow_cache = {}, {}
         out = []
         for lrs, refs, ids in wins:
             assert len(ids) == lrs.shape[0]
             for i, fid in enumerate(ids):
                 if fid not in self.id_cache:
-                    self.id_cache[fid] = self.ctx_pinned.pop(fid, None) or FrameCtx(lrs[i], refs[i], pend)
+                    self.id_cache[fid] = self.ctx_pinned.pop(fid, None) or FrameCtx(lrs[i], refs[i], pend, self.input_yuv)
             out.append([self.id_cache[fid] for fid in ids])
         keep = set(fid for _, _, ids in wins for fid in ids)
         self.id_cache = {k: v for k, v in self.id_cache.items() if k in keep}
@@ -985,15 +1034,15 @@ class Engine(object):
             return self._id_frames([(lrs, refs, frame_ids)], pend)[0]
         if not self.cache:
             self.flow_cache = {}
-            return [FrameCtx(lrs[i], refs[i], pend) for i in range(t)]
+            return [FrameCtx(lrs[i], refs[i], pend, self.input_yuv) for i in range(t)]
         prev = self.prev_window
-        if prev and prev[0].lr.shape != lrs.shape[1:]:          # new clip geometry: nothing to reuse
+        if prev and tuple(prev[0].lr.shape[1:]) != self._geometry(lrs)[1:]:          # new clip geometry: nothing to reuse
             prev = []
             self.flow_cache = {}
-        kind = _input_kind(lrs, refs)
+        kind = _input_kind(lrs, refs, self.input_yuv)
         if kind is None:
             same, own = ops.buffers_equal, (lambda f: (f.lr, f.ref))
-        else:                                                    # 8-bit frames: compared with the contexts' byte copies
+        else:                                                    # 8-bit and 4:2:0 frames: compared with the contexts' source copies
             same, own = ops.bytes_equal, (lambda f: f.src)
         if prev:
             # candidates in order of likelihood: the window slid by one (i+1), did not move (i), slid back (i-1);
@@ -1011,12 +1060,12 @@ class Engine(object):
             for n_, (a, b) in enumerate(pp):
                 if eq[2 * n_] and eq[2 * n_ + 1]:
                     if frames[a] is None:
-                        frames[a] = FrameCtx(lrs[a], refs[a], pend)
+                        frames[a] = FrameCtx(lrs[a], refs[a], pend, self.input_yuv)
                     if frames[b] is None:
                         frames[b] = frames[a]
         for i in range(t):
             if frames[i] is None:
-                frames[i] = FrameCtx(lrs[i], refs[i], pend)
+                frames[i] = FrameCtx(lrs[i], refs[i], pend, self.input_yuv)
         self._keep_flows([frames])
         return frames
 
@@ -1277,9 +1326,9 @@ class Engine(object):
         first: wins[0] is a caller's first frame (RefVSR.py:257-258,292-295): its forward branch starts from zeros like a roll-over's, the
         iteration counter restarts.  Returns (results, the windows' vis dicts -- None unless want_vis)."""
         B = len(wins)
-        t, _, h, w = wins[0][0].shape
+        t, h, w = self._geometry(wins[0][0])
         for lrs, refs, _ in wins:
-            assert tuple(lrs.shape) == (t, 3, h, w)
+            assert self._geometry(lrs) == (t, h, w) and lrs.shape == wins[0][0].shape
 
         def f_step(frs, rst, share, timed):
             # the forward-branch steps, one frame after the other (the carried state); one hand-over event per window
@@ -1360,7 +1409,7 @@ class Engine(object):
             for e, bs in zip(engines, mine):                          # new frames are cloned here, on P
                 for b, fr in zip(bs, e._frames_group([wins[b] for b in bs], pend)):
                     frs[b] = fr
-            ops.ingest_u8(pend)                                       # (8-bit frames: the call's new frames in one launch)
+            self._ingest(pend)                                        # (8-bit / 4:2:0 frames: the call's new frames in one launch)
             for e, bs in zip(engines, mine):
                 for b in bs:
                     # (a group's own preparation computes no backward head: its whole first step is cheaper as multi-map launches)
@@ -1415,7 +1464,7 @@ class Engine(object):
         steady = (not is_first_frame and 2 <= n <= ops.hip.MAX_MAPS and group_ok and
                   all(e.pipelined and e.fw_feat is not None and e.W is lead.W and
                       (e.max_frame_itr_num is None or e.frame_itr_num != e.max_frame_itr_num) and
-                      tuple(e.fw_feat.shape[:2]) == tuple(lrs.shape[3:]) for e in engines))
+                      tuple(e.fw_feat.shape[:2]) == lead._geometry(lrs[0])[1:] for e in engines))
         lead._share_pipe(engines)                   # one set of internal streams for all samples: the lead's
         if not steady:
             outs = []
@@ -1536,7 +1585,8 @@ class Engine(object):
     @torch.no_grad()
     def forward(self, lrs, refs, is_first_frame, want_vis=False, frame_ids=None, want_log=False, input_ready=None):
         """lrs, refs: cuda float32 [t,3,h,w] in [0,1], or uint8 [t,3,h,w] (value = byte / 255; contiguous or the channels-last view of
-        [t,h,w,3] bytes).  Returns (result planar [3,4h,4w], vis dict or None).
+        [t,h,w,3] bytes); under config.input_yuv: [t, 3h/2, w] Y'CbCr 4:2:0 frames of that format (uint8 | uint16), dense and
+        contiguous.  Returns (result planar [3,4h,4w], vis dict or None).
         frame_ids (optional): one hashable id per window frame -> the window cache is keyed by id instead of by
         content comparison; together with set_pipelined(True) it enables cross-call stream pipelining."""
         if is_first_frame and frame_ids is not None:
@@ -1558,12 +1608,18 @@ class Engine(object):
 
     # ------------------------------------------------------------------ two-phase forward (multi-GPU wavefront)
     def _check_window(self, lrs, refs):
-        assert lrs.is_cuda and lrs.dim() == 4 and lrs.shape == refs.shape
-        if lrs.dtype != refs.dtype or lrs.dtype not in (torch.float32, torch.uint8):
-            raise RuntimeError('lrs and refs must both be float32 or both uint8 (got %s, %s)' % (lrs.dtype, refs.dtype))
-        if lrs.dtype == torch.uint8 and None in _input_kind(lrs, refs):
-            raise RuntimeError('uint8 windows must be contiguous [t,3,h,w] or the channels-last view of [t,h,w,3] bytes')
-        t, _, h, w = lrs.shape
+        if self.input_yuv is not None:
+            check_yuv_window(lrs, refs, self.input_yuv[0], 3, '[t, 3h/2, w]')
+        elif lrs.dim() == 3:
+            raise RuntimeError('a window is float32 or uint8 [t,3,h,w]; [t, 3h/2, w] Y\'CbCr 4:2:0 windows need config.input_yuv '
+                               '(got %s %s)' % (lrs.dtype, tuple(lrs.shape)))
+        else:
+            assert lrs.is_cuda and lrs.dim() == 4 and lrs.shape == refs.shape
+            if lrs.dtype != refs.dtype or lrs.dtype not in (torch.float32, torch.uint8):
+                raise RuntimeError('lrs and refs must both be float32 or both uint8 (got %s, %s)' % (lrs.dtype, refs.dtype))
+            if lrs.dtype == torch.uint8 and None in _input_kind(lrs, refs):
+                raise RuntimeError('uint8 windows must be contiguous [t,3,h,w] or the channels-last view of [t,h,w,3] bytes')
+        t, h, w = self._geometry(lrs)
         assert t >= 3 and t % 2 == 1 and h % 2 == 0 and w % 2 == 0, 'need odd t >= 3 and even h, w'
         assert not self.hd or (h % 8 == 0 and w % 8 == 0), 'flag_HD_in needs h, w divisible by 8'
         assert not self.vgg7 or (h % 4 == 0 and w % 4 == 0), 'x2 / HD matching needs h, w divisible by 4'

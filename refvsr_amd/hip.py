@@ -14,7 +14,8 @@ RS_BICUBIC, RS_BILINEAR, RS_BILINEAR_AC, RS_NEAREST = 0, 1, 2, 3
 RESULT_F32, RESULT_F16, RESULT_U8 = 0, 1, 2
 RESULT_HWC = 0x10                           # REFVSR_RESULT_HWC: flag bit of an out_fmt, the result is interleaved [h][w][3]
 INGEST_PLANAR, INGEST_HWC = 0, 1
-YUV_NV12, YUV_I420, YUV_P010, YUV_I420P10 = range(4)       # REFVSR_YUV_*: `yuv_fmt` of refvsr_result_to_yuv420
+YUV_NV12, YUV_I420, YUV_P010, YUV_I420P10 = range(4)       # REFVSR_YUV_*: `yuv_fmt` of refvsr_result_to_yuv420, `format` of refvsr_yuv420_to_rgb
+YUV_CHROMA_BILINEAR, YUV_CHROMA_NEAREST = 0, 1             # REFVSR_YUV_CHROMA_*: `chroma` of refvsr_yuv420_to_rgb
 C24_CONV24, C24_CONV32, C24_CONV48, C24_SHUFFLE2, C24_CONF_ALPHA, C24_CONV_LAST = range(6)      # REFVSR_C24_*: `op` of refvsr_conv24_variant
 MATCH_KP, MATCH_ROWCHUNK, MATCH_COLBLOCK = 152, 256, 512
 ABI_VERSION = 15
@@ -24,6 +25,7 @@ SCORE_MAX_FRAMES = 16                       # REFVSR_SCORE_MAX_FRAMES: frame pai
 SCORE_MAX_RECTS = 8                         # REFVSR_SCORE_MAX_RECTS: rectangles per refvsr_score_regions launch
 COLORMAP_MAX_MAPS = 16                      # REFVSR_COLORMAP_MAX_MAPS: maps per refvsr_conf_colormap launch
 YUV420_MAX_FRAMES = 16                      # REFVSR_YUV420_MAX_FRAMES: result frames per refvsr_result_to_yuv420 launch
+YUV420_IN_MAX_FRAMES = 16                   # REFVSR_YUV420_IN_MAX_FRAMES: 4:2:0 input frames per refvsr_yuv420_to_rgb launch
 FINGERPRINT_CHUNK_WORDS = 4096              # REFVSR_FINGERPRINT_CHUNK_WORDS: words per chunk-table entry of refvsr_param_fingerprint
 RESBLOCK24_BLOB_BYTES = 43264
 RESBLOCK24_F16W_BLOB_BYTES = 28928          # the fp16 weight format (ABI 15)
@@ -176,6 +178,9 @@ SIGNATURES = {
     # Y'CbCr 4:2:0 result frames (added symbols, ABI 15 unchanged): src table, src_fmt, dst table, frames, h, w, yuv_fmt, coef9, stream
     'refvsr_result_to_yuv420': [_P, _I, _P, _I, _I, _I, _I, C.POINTER(C.c_double), _P],
     'refvsr_yuv420_max_frames': [],              # returns REFVSR_YUV420_MAX_FRAMES
+    # Y'CbCr 4:2:0 input frames (added symbols, ABI 15 unchanged): src table, dst table, frames, h, w, format, chroma, coef9, stream
+    'refvsr_yuv420_to_rgb': [_P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _P],
+    'refvsr_yuv420_in_max_frames': [],           # returns REFVSR_YUV420_IN_MAX_FRAMES
 }
 # fp16 weight format (ABI 15): <name>_f16w twins with the signature of the function they are named after
 _F16W_TWINS = ('refvsr_resblock24_chain', 'refvsr_resblock24_chain_batch', 'refvsr_conv24', 'refvsr_conv24_batch', 'refvsr_conv32',
@@ -214,7 +219,8 @@ def lib():
                                    (h.refvsr_ingest_max_frames, INGEST_MAX_FRAMES, 'REFVSR_INGEST_MAX_FRAMES'),
                                    (h.refvsr_score_max_frames, SCORE_MAX_FRAMES, 'REFVSR_SCORE_MAX_FRAMES'),
                                    (h.refvsr_score_max_rects, SCORE_MAX_RECTS, 'REFVSR_SCORE_MAX_RECTS'),
-                                   (h.refvsr_yuv420_max_frames, YUV420_MAX_FRAMES, 'REFVSR_YUV420_MAX_FRAMES')):
+                                   (h.refvsr_yuv420_max_frames, YUV420_MAX_FRAMES, 'REFVSR_YUV420_MAX_FRAMES'),
+                                   (h.refvsr_yuv420_in_max_frames, YUV420_IN_MAX_FRAMES, 'REFVSR_YUV420_IN_MAX_FRAMES')):
             if query() != const:
                 raise RuntimeError('refvsr_amd: %s mismatch (library %d, binding %d)' % (name, query(), const))
         _lib = h

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import hip, ops
-from .engine import Engine, Weights
+from .engine import Engine, Weights, check_yuv_window
 from .fingerprint import WEIGHT_CHECKS, weight_check_policy
 from .weights import state_spec, strip_module_prefix
 
@@ -39,11 +39,27 @@ def _register(root, dotted, param):
     mod.register_parameter(parts[-1], param)
 
 
-def _inputs(lrs, refs, what, strict=False):
+def _input_yuv(config):
+    """config.input_yuv checked (yuv.resolve_input): the format, or None (off)."""
+    from . import yuv
+    r = yuv.resolve_input(getattr(config, 'input_yuv', None), getattr(config, 'input_yuv_matrix', None),
+                          getattr(config, 'input_yuv_range', None), getattr(config, 'input_yuv_chroma', None))
+    return None if r is None else r[0]
+
+
+def _inputs(lrs, refs, what, strict=False, input_yuv=None, dim=5):
     """The network's input contract: float frames in [0, 1] (float16 / float64 are converted to float32, as in the reference), or uint8
     frames meaning byte / 255 -- contiguous [.., 3, h, w] or the channels-last view of [.., h, w, 3] bytes, converted exactly on the
     device (refvsr_ingest_u8).  lrs and refs are both uint8 or both not.  strict: inputs the engine reads off the caller's stream order
-    (input_ready= on the pipelined path) are refused instead of converted."""
+    (input_ready= on the pipelined path) are refused instead of converted.
+    input_yuv (config.input_yuv, a format): Y'CbCr 4:2:0 windows [.., t, 3h/2, w] instead (`dim` - 1 dimensions), dense and of the
+    format's sample type, decoded exactly on the device (refvsr_yuv420_to_rgb); nothing is converted here, anything else is refused."""
+    if input_yuv is not None:
+        check_yuv_window(lrs, refs, input_yuv, dim - 1, {5: '[n, t, 3h/2, w]', 4: '[t, 3h/2, w]'}[dim])
+        return lrs, refs
+    if lrs.dim() == dim - 1 and lrs.dtype in (torch.uint8, torch.uint16):
+        raise RuntimeError("%s: windows are float or uint8 [.., t, 3, h, w]; [.., t, 3h/2, w] Y'CbCr 4:2:0 windows need config.input_yuv "
+                           "(got %s %s)" % (what, lrs.dtype, tuple(lrs.shape)))
     if (lrs.dtype == torch.uint8) != (refs.dtype == torch.uint8):
         raise RuntimeError('%s: lrs and refs must both be uint8 or both float (got %s and %s)' % (what, lrs.dtype, refs.dtype))
     if lrs.dtype == torch.uint8:
@@ -295,7 +311,8 @@ class Network(nn.Module):
     def forward(self, lrs, refs, is_first_frame, is_log=False, is_train=False, frame_ids=None, input_ready=None):
         """Same contract as RefVSR.py:151: lrs, refs [n,t,3,h,w] in [0,1] (or uint8: byte / 255, see _inputs); returns OrderedDict with
         'result' [n,3,4h,4w] (+ 'eval_vis' when is_log and config.save_sample; + 'yuv' [n,6h,4w] under config.result_yuv).
-        frame_ids / input_ready: extensions (window cache keyed by ids; when the inputs are final -- Engine.set_pipelined)."""
+        frame_ids / input_ready: extensions (window cache keyed by ids; when the inputs are final -- Engine.set_pipelined).
+        Under config.input_yuv lrs, refs are Y'CbCr 4:2:0 windows [n, t, 3h/2, w] instead (uint8 | uint16 by format, see _inputs)."""
         if is_train:
             raise NotImplementedError('refvsr_amd implements the inference path only (is_train=False)')
         hip.lib()                                              # fail loudly if the extension is missing
@@ -309,7 +326,7 @@ class Network(nn.Module):
         # instead of raced against.  (input_ready=None waits for the caller's stream, conversions included; calls that take
         # the sequential path -- is_log, cache or overlap off -- run in the caller's stream order anyway.)
         strict = input_ready is not None and any(e.takes_pipelined_path(frame_ids, bool(is_log)) for e in self._engines[:n])
-        lrs, refs = _inputs(lrs, refs, 'forward', strict)
+        lrs, refs = _inputs(lrs, refs, 'forward', strict, _input_yuv(self.config))
         want_vis = bool(is_log and self.config.save_sample)
         results, vis_all = [], []
         dbg_all = []
@@ -353,13 +370,17 @@ class Network(nn.Module):
         hip.lib()
         if not lrs.is_cuda:
             raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path' % lrs.device)
-        for t_ in (lrs, refs):
-            ok = t_.dtype == torch.uint8 and ops.u8_layout(t_) is not None or t_.dtype == torch.float32 and t_.is_contiguous()
-            if not ok or t_.dim() != 5:
-                raise RuntimeError('forward_group needs contiguous float32 or uint8 [B,t,3,h,w] inputs, or the channels-last view of uint8 '
-                                   '[B,t,h,w,3] (got %s, contiguous=%s)' % (t_.dtype, t_.is_contiguous()))
-        if lrs.dtype != refs.dtype:
-            raise RuntimeError('forward_group: lrs and refs must both be uint8 or both float32 (got %s and %s)' % (lrs.dtype, refs.dtype))
+        fmt = _input_yuv(self.config)
+        if fmt is not None:                                    # (config.input_yuv: [B, t, 3h/2, w] 4:2:0 windows)
+            check_yuv_window(lrs, refs, fmt, 4, '[B, t, 3h/2, w]')
+        else:
+            for t_ in (lrs, refs):
+                ok = t_.dtype == torch.uint8 and ops.u8_layout(t_) is not None or t_.dtype == torch.float32 and t_.is_contiguous()
+                if not ok or t_.dim() != 5:
+                    raise RuntimeError('forward_group needs contiguous float32 or uint8 [B,t,3,h,w] inputs, or the channels-last view of uint8 '
+                                       '[B,t,h,w,3] (got %s, contiguous=%s)' % (t_.dtype, t_.is_contiguous()))
+            if lrs.dtype != refs.dtype:
+                raise RuntimeError('forward_group: lrs and refs must both be uint8 or both float32 (got %s and %s)' % (lrs.dtype, refs.dtype))
         assert len(frame_ids) == lrs.shape[0] and lrs.shape == refs.shape
         eng = self.ensure_engines(1, lrs.device, (True, bool(is_first_frame)))[0]
         wins = [(lrs[b], refs[b], [(0, f) for f in frame_ids[b]]) for b in range(lrs.shape[0])]
@@ -379,7 +400,7 @@ class Network(nn.Module):
         hip.lib()
         if not lrs.is_cuda:
             raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path' % lrs.device)
-        lrs, refs = _inputs(lrs, refs, 'phase_a')
+        lrs, refs = _inputs(lrs, refs, 'phase_a', input_yuv=_input_yuv(self.config))
         self.ensure_engines(lrs.shape[0], lrs.device, (frame_ids is not None, bool(first_hint)))
         return [self._engines[b].phase_a(lrs[b], refs[b], None if frame_ids is None else [(b, f) for f in frame_ids],
                                          first_hint) for b in range(lrs.shape[0])]
@@ -393,7 +414,8 @@ class Network(nn.Module):
             raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path' % lrs[0].device)
         assert len(lrs) == len(refs) == len(frame_ids)
         eng = self.ensure_engines(1, lrs[0].device, (True, False))[0]
-        wins = [_inputs(lrs[b], refs[b], 'phase_a_group') + ([(0, f) for f in frame_ids[b]],) for b in range(len(lrs))]
+        fmt = _input_yuv(self.config)
+        wins = [_inputs(lrs[b], refs[b], 'phase_a_group', input_yuv=fmt, dim=4) + ([(0, f) for f in frame_ids[b]],) for b in range(len(lrs))]
         return [[h] for h in eng.phase_a_group(wins, first_hints, streams)]
 
     def phase_b1(self, handles, is_first_frame):

@@ -730,14 +730,16 @@ def buffers_equal(pairs):
 
 def bytes_equal(pairs):
     """pairs: list of (a, b) uint8 tensors of one size whose bytes are dense (contiguous, or a channels-last frame: u8_layout; a and b
-    may differ in alignment).  Returns a python list of bools -- True where the raw bytes are equal (one launch per 32 pairs, one D2H
-    sync).  The caller compares frames of one layout only."""
+    may differ in alignment), or contiguous uint16 tensors (4:2:0 frames of 10-bit samples), compared through their bytes.  Returns a
+    python list of bools -- True where the raw bytes are equal (one launch per 32 pairs, one D2H sync).  The caller compares frames
+    of one layout only."""
     if not pairs:
         return []
-    nbytes = pairs[0][0].numel()
+    dt = pairs[0][0].dtype
+    nbytes = pairs[0][0].numel() * dt.itemsize
 
     def check(a, b):
-        assert a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.numel() == b.numel() == nbytes
+        assert dt in (torch.uint8, torch.uint16) and a.dtype == dt and b.dtype == dt and a.numel() * dt.itemsize == b.numel() * dt.itemsize == nbytes
         assert all(x.is_contiguous() or u8_layout(x) is not None for x in (a, b))
     return _pairs_equal(pairs, 'bytes_equal', nbytes, check)
 
@@ -937,6 +939,64 @@ def result_to_yuv420(frames, fmt='nv12', matrix='bt709', range='limited'):
         chunk = frames[s0:s0 + hip.YUV420_MAX_FRAMES]
         hip.check(hip.lib().refvsr_result_to_yuv420(_parr(chunk), sfmt, _parr([out[s0 + i] for i in _irange(len(chunk))]), len(chunk), h, w,
                                                     yuv.FORMAT_IDS[fmt], coef, st), 'result_to_yuv420')
+    return out
+
+
+def yuv_window_kind(x, fmt):
+    """('yuv', fmt) for a tensor whose trailing [3 h / 2, w] frames are dense 4:2:0 buffers of format `fmt` -- the sample type of the
+    format (torch.uint8 | torch.uint16), at least 2-D, contiguous, even h and w -- else None."""
+    from . import yuv
+    dt = torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16
+    if x.dtype != dt or x.dim() < 2 or not x.is_contiguous():
+        return None
+    r, w = x.shape[-2:]
+    if r < 3 or r % 3 or w < 2 or w % 2:                    # (3 h / 2 rows with even h: a multiple of 3)
+        return None
+    return ('yuv', fmt)
+
+
+def yuv_geometry(x):
+    """(h, w) of a tensor of [3 h / 2, w] frames."""
+    return 2 * x.shape[-2] // 3, x.shape[-1]
+
+
+def yuv420_ingest(pairs, fmt='nv12', matrix='bt709', range='limited', chroma='bilinear'):
+    """pairs: [(src [3 h / 2, w] uint8 | uint16 by `fmt`, one dense frame at any address that is a multiple of its sample size, dst
+    float32 [3,h,w] contiguous)] of one h x w: dst = the bits of yuv.yuv420_to_rgb (refvsr_yuv420_to_rgb) -- the twin of ingest_u8.
+    One launch per REFVSR_YUV420_IN_MAX_FRAMES frames, on the current stream."""
+    from . import yuv
+    if not pairs:
+        return
+    coef = (C.c_double * 9)(*yuv.decode_coefficients(fmt, matrix, range))
+    mode = yuv.CHROMA_MODES[yuv.check_chroma(chroma)]
+    h, w = pairs[0][1].shape[1:]
+    for src, dst in pairs:
+        assert yuv_window_kind(src, fmt) is not None and tuple(src.shape) == yuv.frame_shape(h, w), \
+            'yuv420_ingest: dense %s frames [3h/2, w] of one size' % fmt
+        _planar(dst, 3)
+        assert dst.shape[1:] == (h, w)
+    st = _stream()
+    for s0 in _irange(0, len(pairs), hip.YUV420_IN_MAX_FRAMES):
+        chunk = pairs[s0:s0 + hip.YUV420_IN_MAX_FRAMES]
+        hip.check(hip.lib().refvsr_yuv420_to_rgb(_parr([s_ for s_, _ in chunk]), _parr([d for _, d in chunk]), len(chunk), h, w,
+                                                 yuv.FORMAT_IDS[fmt], mode, coef, st), 'yuv420_to_rgb')
+
+
+def yuv420_to_frames(x, h, w, fmt, matrix='bt709', range='limited', chroma='bilinear'):
+    """[..., 3 h / 2, w] 4:2:0 frames (uint8 'nv12' | 'i420', uint16 'p010' | 'i420p10'; other strides and storage that is unaligned
+    for the sample size are copied first) -> a new contiguous float32 [..., 3, h, w] tensor, the bits of yuv.yuv420_to_rgb, frame by
+    frame through refvsr_yuv420_to_rgb (as ingest_frames)."""
+    from . import yuv
+    dt = torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16
+    if not (x.is_cuda and x.dtype == dt and x.dim() >= 2 and tuple(x.shape[-2:]) == yuv.frame_shape(h, w)):
+        raise RuntimeError('yuv420_to_frames: cuda %s [..., %d, %d] frames for %s at %d x %d (got %s %s %s)'
+                           % (dt, 3 * h // 2, w, fmt, h, w, x.device.type, x.dtype, tuple(x.shape)))
+    if not x.is_contiguous():
+        x = x.contiguous()
+    if x.data_ptr() % dt.itemsize:
+        x = x.clone()
+    out = torch.empty(tuple(x.shape[:-2]) + (3, h, w), dtype=torch.float32, device=x.device)
+    yuv420_ingest(list(zip(x.reshape((-1,) + tuple(x.shape[-2:])), out.view(-1, 3, h, w))), fmt, matrix, range, chroma)
     return out
 
 

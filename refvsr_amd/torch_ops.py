@@ -29,6 +29,7 @@ Op set (argument conventions of ops.py: `planar` = float32 [C,H,W], `nhwc16` = f
   score_frames(outs, gts, win)                           [B,3,h,w] results / ground truths -> float64 [B,2] = {mse, ssim} on the device
   score_regions(outs, gts, rects)                        the same pairs, rects = flat [4 R] ints -> float64 [B,R,2] = {sum (a-b)^2, sum S}
   result_to_yuv420(frames, fmt, matrix, range)           [B,3,h,w] results -> [B, 3h/2, w] uint8 | uint16 4:2:0 frames (yuv.py's bits)
+  yuv420_to_rgb(x, h, w, fmt, matrix, range, chroma)     [..., 3h/2, w] uint8 | uint16 4:2:0 frames -> float32 [..., 3, h, w] (yuv.py's bits)
 """
 from typing import List, Optional, Tuple
 
@@ -311,8 +312,24 @@ def register():
         return torch.empty((frames.shape[0], 3 * frames.shape[2] // 2, frames.shape[3]),
                            dtype=torch.uint8 if yuv.FORMATS[fmt][0] == 8 else torch.uint16, device=frames.device)
 
+    @op('yuv420_to_rgb')
+    def yuv420_to_rgb(x: torch.Tensor, h: int, w: int, fmt: str, matrix: str, range: str, chroma: str) -> torch.Tensor:
+        return ops.yuv420_to_frames(x, h, w, fmt, matrix, range, chroma)
+
+    @yuv420_to_rgb.register_fake
+    def _(x, h, w, fmt, matrix, range, chroma):
+        from . import yuv
+        torch._check(fmt in yuv.FORMATS, lambda: 'yuv420_to_rgb: unknown yuv format')
+        torch._check(matrix in yuv.MATRICES, lambda: "yuv420_to_rgb: matrix must be 'bt709' or 'bt601'")
+        torch._check(range in yuv.RANGES, lambda: "yuv420_to_rgb: range must be 'limited' or 'full'")
+        torch._check(chroma in yuv.CHROMA_MODES, lambda: "yuv420_to_rgb: chroma must be 'bilinear' or 'nearest'")
+        torch._check(h > 0 and w > 0 and h % 2 == 0 and w % 2 == 0 and x.dim() >= 2 and x.shape[-2] == 3 * h // 2 and x.shape[-1] == w,
+                     lambda: 'yuv420_to_rgb takes [..., 3h/2, w] frames with even h and w')
+        torch._check(x.dtype == (torch.uint8 if yuv.FORMATS[fmt][0] == 8 else torch.uint16), lambda: 'yuv420_to_rgb: uint8 or uint16 samples by format')
+        return torch.empty(tuple(x.shape[:-2]) + (3, h, w), dtype=torch.float32, device=x.device)
+
 
 OP_NAMES = ('conv_mfma', 'conv24', 'resblock', 'resblock24_chain', 'resblock24_chain_batch', 'conv24_batch', 'warp_batch', 'match_argmax', 'warp', 'warp_planar', 'spynet_level_input', 'block_gather',
-            'block_gather_rgb', 'aligned_sample', 'resize', 'pack_nhwc16', 'unpack_nhwc16', 'ingest_u8', 'score_frames', 'score_regions', 'result_to_yuv420')
+            'block_gather_rgb', 'aligned_sample', 'resize', 'pack_nhwc16', 'unpack_nhwc16', 'ingest_u8', 'score_frames', 'score_regions', 'result_to_yuv420', 'yuv420_to_rgb')
 
 register()

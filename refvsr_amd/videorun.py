@@ -1,0 +1,168 @@
+"""Video in, video out (extension): super-resolve a pair of .y4m files -- the ultra-wide LR stream and the wide reference stream --
+into a .y4m file, 4:2:0 on both sides of the network:
+
+    python -m refvsr_amd.videorun --config config_RefVSR_small_L1 --ckpt_abs_name CKPT --lr uw.y4m --ref w.y4m --out sr.y4m
+        [--frame_num 5] [--frame_group 4] [--video_depth 8|10] [--yuv_matrix bt709|bt601] [--yuv_range limited|full]
+        [--chroma bilinear|nearest]
+
+The files are read frame by frame (yuv.Y4MReader), the windows are the reference's (evalrun.window_indices: clip edges replicate
+frames, data_loader/datasets.py:222-234), the network runs forward_group with frame ids, config.input_yuv taken from the files and
+config.result_yuv = 'i420' | 'i420p10', and 'yuv' goes to the output through yuv.Y4MWriter.  No scores, no images: evalrun.py has those.
+"""
+import argparse
+import collections
+import sys
+import time
+
+import numpy as np
+import torch
+
+from .evalrun import load_checkpoint, window_indices
+from .yuv import Y4MReader, Y4MWriter, check_chroma, check_matrix, check_range, depth_of
+
+
+def open_pair(lr_path, ref_path):
+    """The two readers of a run; ValueError (one line) unless geometry, format and frame count agree."""
+    lr = Y4MReader(lr_path)
+    try:
+        ref = Y4MReader(ref_path)
+    except Exception:
+        lr.close()
+        raise
+    bad = None
+    if (lr.h, lr.w) != (ref.h, ref.w):
+        bad = 'geometry differs (%d x %d and %d x %d)' % (lr.h, lr.w, ref.h, ref.w)
+    elif lr.fmt != ref.fmt:
+        bad = 'format differs (%s and %s)' % (lr.fmt, ref.fmt)
+    elif lr.length != ref.length:
+        bad = 'frame count differs (%d and %d)' % (lr.length, ref.length)
+    elif lr.length < 1:
+        bad = 'no frames'
+    if bad:
+        lr.close()
+        ref.close()
+        raise ValueError('videorun: %s and %s: %s' % (lr_path, ref_path, bad))
+    return lr, ref
+
+
+def configure(config, reader):
+    """The run's fields of `config` from the LR file: input_yuv (always the files' format), input_yuv_range (the file's XCOLORRANGE
+    unless set: EVAL.input_range_set), result_yuv (by EVAL.video_depth; None: the input's depth)."""
+    E = config.EVAL
+    config.input_yuv = reader.fmt
+    if not getattr(E, 'input_range_set', False):
+        config.input_yuv_range = reader.range
+    depth = getattr(E, 'video_depth', None) or depth_of(reader.fmt)
+    if depth not in (8, 10):
+        raise ValueError('videorun: --video_depth must be 8 or 10 (got %r)' % (depth,))
+    config.result_yuv = 'i420' if depth == 8 else 'i420p10'
+    return config
+
+
+def run(config, lr_path, ref_path, out_path, net=None):
+    """Super-resolve lr_path with ref_path into out_path; returns (frames written, seconds in the network calls).  config: a model
+    config (EVAL.frame_group, frame_num, yuv_matrix / yuv_range for the output, input_yuv_matrix / input_yuv_chroma for the input);
+    net: an SRNet built from that config (None: built here, EVAL.ckpt_abs_name loaded) -- its engines must not exist yet, they take
+    the input format from the config at their construction."""
+    lr, ref = open_pair(lr_path, ref_path)
+    writer = None
+    was_pipelined = None
+    try:
+        configure(config, lr)
+        if net is None:
+            from . import SRNet
+            net = SRNet(config).to('cuda').eval()
+            if config.EVAL.ckpt_abs_name:
+                load_checkpoint(net, config.EVAL.ckpt_abs_name)
+        nc = net.Network.config
+        if nc is not config:                              # (a caller's net may carry a config of its own)
+            for k in ('input_yuv', 'input_yuv_range', 'result_yuv'):
+                setattr(nc, k, getattr(config, k))
+        if net.Network._engines and net.Network._engines[0].input_yuv is None:
+            raise RuntimeError('videorun: the network passed in already runs without config.input_yuv; pass a fresh one')
+        dev = next(net.parameters()).device
+        n, t, G = lr.length, int(config.frame_num), max(1, int(getattr(config.EVAL, 'frame_group', 4) or 1))
+        scale = int(config.scale)
+        writer = Y4MWriter(out_path, lr.h * scale, lr.w * scale, config.result_yuv, lr.fps, getattr(config, 'yuv_range', None) or 'limited')
+        was_pipelined = bool(getattr(nc, 'pipelined', False))
+        net.Network.set_pipelined(True)
+        net.Network.reset()
+        held = collections.OrderedDict()                  # frame index -> (lr buffer, ref buffer): the frames the next windows read
+        nread, seconds, first = 0, 0.0, True
+        with torch.no_grad():
+            for f0 in range(0, n, G):
+                fs = list(range(f0, min(f0 + G, n)))
+                wins = [window_indices(f, n, t) for f in fs]
+                while nread <= max(i for w_ in wins for i in w_):
+                    a, b = lr.read(), ref.read()
+                    if a is None or b is None:
+                        raise ValueError('videorun: %s: truncated file' % (lr_path if a is None else ref_path))
+                    held[nread] = (a, b)
+                    nread += 1
+                for k in [k for k in held if k < min(wins[0])]:
+                    del held[k]
+                t0 = time.time()
+                lrs = torch.from_numpy(np.stack([np.stack([held[i][0] for i in w_]) for w_ in wins])).to(dev)
+                rfs = torch.from_numpy(np.stack([np.stack([held[i][1] for i in w_]) for w_ in wins])).to(dev)
+                got = net.Network.forward_group(lrs, rfs, wins, is_first_frame=first)
+                ys = [y[0].cpu().numpy() for y in got['yuv']]
+                seconds += time.time() - t0
+                first = False
+                for y in ys:
+                    writer.write(y)
+        return writer.frames, seconds
+    finally:
+        lr.close()
+        ref.close()
+        if writer is not None:
+            writer.close()
+        if was_pipelined is False:
+            torch.cuda.synchronize()
+            net.Network.set_pipelined(False)
+
+
+def build_config(argv=None):
+    from .config import get_config
+    ap = argparse.ArgumentParser(description='RefVSR on .y4m files: 4:2:0 in, 4:2:0 out (MI355X HIP path)')
+    ap.add_argument('--config', '-c', type=str, default='config_RefVSR_small_L1')
+    ap.add_argument('--ckpt_abs_name', '-ckpt_abs_name', type=str, default=None)
+    ap.add_argument('--lr', required=True, help='the ultra-wide LR stream (.y4m, C420jpeg or C420p10)')
+    ap.add_argument('--ref', required=True, help='the wide reference stream (.y4m of the same geometry, format and length)')
+    ap.add_argument('--out', required=True, help='the result (.y4m)')
+    ap.add_argument('--frame_num', type=int, default=5)
+    ap.add_argument('--frame_group', type=int, default=4)
+    ap.add_argument('--video_depth', type=int, default=None, choices=[8, 10], help='bits per sample of --out (default: the input files\')')
+    ap.add_argument('--yuv_matrix', default='bt709', choices=['bt709', 'bt601'], help='luma coefficients, input and output')
+    ap.add_argument('--yuv_range', default=None, choices=['limited', 'full'], help="code range, input and output (default: the LR file's XCOLORRANGE)")
+    ap.add_argument('--chroma', default='bilinear', choices=['bilinear', 'nearest'], help='chroma up-sampling of the input')
+    args = ap.parse_args(argv)
+    if args.frame_num < 3 or args.frame_num % 2 == 0:
+        raise ValueError('videorun: --frame_num must be odd and >= 3 (got %d)' % args.frame_num)
+    if args.frame_group < 1:
+        raise ValueError('videorun: --frame_group must be >= 1 (got %d)' % args.frame_group)
+    cfg = get_config('RefVSR_CVPR2022', 'eval', args.config, '')
+    cfg.frame_num = args.frame_num
+    cfg.center_idx = cfg.frame_num // 2
+    cfg.yuv_matrix = cfg.input_yuv_matrix = check_matrix(args.yuv_matrix)
+    cfg.input_yuv_chroma = check_chroma(args.chroma)
+    E = cfg.EVAL
+    E.input_range_set = args.yuv_range is not None
+    if args.yuv_range is not None:
+        cfg.yuv_range = cfg.input_yuv_range = check_range(args.yuv_range)
+    E.ckpt_abs_name, E.frame_group, E.video_depth = args.ckpt_abs_name, args.frame_group, args.video_depth
+    cfg.device, cfg.cuda = 'cuda', True
+    return cfg, args
+
+
+def main(argv=None):
+    cfg, args = build_config(argv)
+    if not cfg.EVAL.input_range_set:
+        with Y4MReader(args.lr) as rd:
+            cfg.yuv_range = rd.range              # (the output keeps the input's range unless --yuv_range says otherwise)
+    frames, seconds = run(cfg, args.lr, args.ref, args.out)
+    print('[VIDEO %s] %d frames -> %s (%.5f sec / frame)' % (args.config, frames, args.out, seconds / max(frames, 1)))
+    return 0 if frames else 1
+
+
+if __name__ == '__main__':
+    sys.exit(main())

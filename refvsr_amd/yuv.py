@@ -1,4 +1,5 @@
-"""Y'CbCr 4:2:0 result frames: the specification of refvsr_result_to_yuv420 (csrc/yuv.hip) as a numpy model, and Y4M files.
+"""Y'CbCr 4:2:0 frames, out and in: the specifications of refvsr_result_to_yuv420 (csrc/yuv.hip) and of refvsr_yuv420_to_rgb
+(csrc/yuv_in.hip) as numpy models, and Y4M files.
 
 Pure numpy, no torch (as the models of metrics.py): the kernel returns the bits of rgb_to_yuv420.  Extension -- the reference's
 consumer writes PNG / JPG (evaluation/eval_qual_quan.py:117-119); every video consumer (encoders, raw-video pipes, players, .y4m)
@@ -15,7 +16,21 @@ Arithmetic, all float64, every operation rounded on its own (no fused multiply-a
   pixel   ey = (kr r + kg g) + kb b;  Y = rint(oy + sy ey);  ecb = (b - ey) icb;  ecr = (r - ey) icr
   block   m = ((e00 + e01) + (e10 + e11)) 0.25  (centre-sited: the box average of the unquantised chroma);  C = rint(oc + sc m)
 rint rounds half to even; every code is clamped to [0, 2^d - 1] before the cast (pure blue at full range gives 255.5).
+
+The way in (yuv420_to_rgb; extension -- the reference's loader reads PNGs, data_loader/utils.py:12-41), float64 in the same manner:
+  codes   nv12 / i420: the byte;  p010: sample >> 6 (the low six bits are ignored);  i420p10: sample & 1023
+  chroma  at luma pixel (y, x), centre-sited -- the inverse siting of the box average above:  (cy, cx) = (y >> 1, x >> 1),
+          cy' = clamp(cy + (y & 1 ? 1 : -1), 0, h/2 - 1), cx' likewise,
+          m = (9 C[cy,cx] + 3 C[cy',cx] + 3 C[cy,cx'] + C[cy',cx']) 0.0625  (an integer below 2^15 times a power of two: exact in
+          any order);  chroma = 'nearest': m = C[cy,cx]
+  pixel   ey = (Y - oy) iy;  ecb = (mcb - oc) ic;  ecr = (mcr - oc) ic;  r = ey + cr_r ecr;  b = ey + cb_b ecb;
+          g = ((ey - kr r) - kb b) ikg
+  output  r, g, b clamped to [0, 1] (decoded video is routinely out of gamut; the network's contract is frames in [0, 1]), then
+          rounded once to float32
+with (oy, iy = 1 / sy, oc, ic = 1 / sc, cr_r = 2 (1 - kr), cb_b = 2 (1 - kb), kr, kb, ikg = 1 / kg) of decode_coefficients.
 """
+import os
+
 import numpy as np
 
 # name -> (bit depth, semi-planar (interleaved CbCr), left shift of the code)
@@ -162,6 +177,81 @@ def to_planar(buf, h, w, fmt):
     return pack(y.astype(np.int64) >> shift, cb.astype(np.int64) >> shift, cr.astype(np.int64) >> shift, PLANAR_TWIN.get(fmt, fmt))
 
 
+# ------------------------------------------------------------------------------------------------ the way in
+CHROMA_MODES = {'bilinear': 0, 'nearest': 1}                           # REFVSR_YUV_CHROMA_* of include/refvsr_hip.h
+
+
+def check_chroma(chroma):
+    if chroma not in CHROMA_MODES:
+        raise ValueError("yuv chroma mode must be 'bilinear' or 'nearest', got %r" % (chroma,))
+    return chroma
+
+
+def resolve_input(input_yuv, matrix=None, range=None, chroma=None):
+    """config.input_yuv / input_yuv_matrix / input_yuv_range / input_yuv_chroma checked: None (off) or (format, matrix, range, chroma);
+    ValueError for a bad name, also while the format is off (as resolve)."""
+    m, r, c = check_matrix(matrix or 'bt709'), check_range(range or 'limited'), check_chroma(chroma or 'bilinear')
+    if input_yuv is None:
+        return None
+    if input_yuv not in FORMATS:
+        raise ValueError("input_yuv must be None, 'nv12', 'i420', 'p010' or 'i420p10', got %r" % (input_yuv,))
+    return (input_yuv, m, r, c)
+
+
+def decode_coefficients(fmt='nv12', matrix='bt709', range='limited'):
+    """The nine doubles (oy, iy, oc, ic, cr_r, cb_b, kr, kb, ikg) the decoding model and its kernel both get, computed once in Python
+    float64 from coefficients(): the reciprocals are taken here, no division happens on the device."""
+    kr, kg, kb, _, _, oy, sy, oc, sc = coefficients(fmt, matrix, range)
+    return (oy, 1.0 / sy, oc, 1.0 / sc, 2.0 * (1.0 - kr), 2.0 * (1.0 - kb), kr, kb, 1.0 / kg)
+
+
+def codes(buf, h, w, fmt):
+    """The integer code planes (Y [h, w], Cb [h/2, w/2], Cr [h/2, w/2]; int64) of a frame's buffer."""
+    d, _, shift = FORMATS[check_format(fmt)]
+    buf = np.asarray(buf)
+    if buf.dtype != dtype_of(fmt):
+        raise TypeError('%s frames are %s (got %s)' % (fmt, np.dtype(dtype_of(fmt)).name, buf.dtype))
+    # (p010: the code in the high bits, sample >> 6; the others: the low d bits -- all eight of a byte, sample & 1023 of i420p10)
+    return tuple((p.astype(np.int64) >> shift) & (2 ** d - 1) for p in planes(buf, h, w, fmt))
+
+
+def chroma_taps(c, chroma='bilinear'):
+    """The integer tap sum 16 m [h, w] of a chroma code plane [h/2, w/2] (int64): 9 C[cy,cx] + 3 C[cy',cx] + 3 C[cy,cx'] + C[cy',cx']
+    at every luma pixel, the neighbours clamped at the edges; 'nearest': 16 C[cy,cx]."""
+    h2, w2 = c.shape
+    y, x = np.arange(2 * h2), np.arange(2 * w2)
+    cy, cx = y >> 1, x >> 1
+    if check_chroma(chroma) == 'nearest':
+        return 16 * c[cy][:, cx]
+    cy2 = np.clip(cy + np.where(y & 1, 1, -1), 0, h2 - 1)
+    cx2 = np.clip(cx + np.where(x & 1, 1, -1), 0, w2 - 1)
+    return 9 * c[cy][:, cx] + 3 * c[cy2][:, cx] + 3 * c[cy][:, cx2] + c[cy2][:, cx2]
+
+
+def decode_pre_clamp(buf, h, w, fmt='nv12', matrix='bt709', range='limited', chroma='bilinear'):
+    """(r, g, b) float64 [h, w] of one frame before the clamp to [0, 1] and the rounding to float32."""
+    oy, iy, oc, ic, cr_r, cb_b, kr, kb, ikg = decode_coefficients(fmt, matrix, range)
+    yc, cbc, crc = codes(buf, h, w, fmt)
+    ey = (yc.astype(np.float64) - oy) * iy
+    ecb = (chroma_taps(cbc, chroma).astype(np.float64) * 0.0625 - oc) * ic
+    ecr = (chroma_taps(crc, chroma).astype(np.float64) * 0.0625 - oc) * ic
+    r = ey + cr_r * ecr
+    b = ey + cb_b * ecb
+    g = ((ey - kr * r) - kb * b) * ikg
+    return r, g, b
+
+
+def yuv420_to_rgb(buf, h, w, fmt, matrix='bt709', range='limited', chroma='bilinear'):
+    """The model of the way in: a frame's buffer [3 h / 2, w] (uint8 | uint16 by format) -> float32 [3, h, w] in [0, 1]; a
+    [B, 3 h / 2, w] batch -> [B, 3, h, w]."""
+    buf = np.asarray(buf)
+    if buf.ndim == 3:
+        return np.stack([yuv420_to_rgb(f, h, w, fmt, matrix, range, chroma) for f in buf])
+    if buf.shape != frame_shape(h, w):
+        raise ValueError('a %d x %d frame is %s (got %s)' % (h, w, frame_shape(h, w), buf.shape))
+    return np.stack([np.clip(v, 0.0, 1.0) for v in decode_pre_clamp(buf, h, w, fmt, matrix, range, chroma)]).astype(np.float32)
+
+
 # ------------------------------------------------------------------------------------------------ Y4M
 def parse_fps(text):
     """'30' | '30000:1001' -> (num, den)."""
@@ -215,18 +305,78 @@ class Y4MWriter(object):
         self.close()
 
 
+def parse_y4m_header(line, path):
+    """The header line (without its newline) -> dict(h, w, fps, fmt, range)."""
+    tok = line.decode('ascii', 'replace').split(' ')
+    if tok[0] != 'YUV4MPEG2':
+        raise ValueError('%s: not a YUV4MPEG2 file' % path)
+    f = dict((t[0], t[1:]) for t in tok[1:] if t and t[0] != 'X')
+    x = dict(t[1:].split('=', 1) for t in tok[1:] if t and t[0] == 'X' and '=' in t)
+    fmt = {'420jpeg': 'i420', '420p10': 'i420p10'}[f['C']]
+    return {'h': int(f['H']), 'w': int(f['W']), 'fps': parse_fps(f['F']), 'fmt': fmt, 'range': x.get('COLORRANGE', 'LIMITED').lower()}
+
+
+class Y4MReader(object):
+    """A .y4m file Y4MWriter wrote, read one frame at a time (read_y4m holds the whole file): the header fields of read_y4m as
+    attributes (h, w, fps, fmt, range) and, by iteration or read(), one frame buffer [3 h / 2, w] after the other; read() returns
+    None at the end of the file and raises ValueError for a truncated frame or a missing FRAME marker."""
+
+    def __init__(self, path):
+        self.path = path
+        self.fh = open(path, 'rb')
+        try:
+            line = self.fh.readline(4096)
+            if not line.endswith(b'\n'):
+                raise ValueError('%s: not a YUV4MPEG2 file' % path)
+            hd = parse_y4m_header(line[:-1], path)
+        except Exception:
+            self.close()
+            raise
+        self.h, self.w, self.fps, self.fmt, self.range = hd['h'], hd['w'], hd['fps'], hd['fmt'], hd['range']
+        self.frames = 0             # frames read so far
+        # whole frames in the file, by its size (a truncated last frame is not counted; read() reports it)
+        self.length = (os.fstat(self.fh.fileno()).st_size - len(line)) // (6 + frame_bytes(self.h, self.w, self.fmt))
+
+    def read(self):
+        mark = self.fh.read(6)
+        if not mark:
+            return None
+        if mark != b'FRAME\n':
+            raise ValueError('%s: FRAME marker expected before frame %d' % (self.path, self.frames))
+        nbytes = frame_bytes(self.h, self.w, self.fmt)
+        raw = self.fh.read(nbytes)
+        if len(raw) != nbytes:
+            raise ValueError('%s: truncated frame %d' % (self.path, self.frames))
+        self.frames += 1
+        dt = dtype_of(self.fmt)
+        return np.frombuffer(raw, dtype=np.dtype(dt).newbyteorder('<')).astype(dt).reshape(frame_shape(self.h, self.w))
+
+    def __iter__(self):
+        while True:
+            f = self.read()
+            if f is None:
+                return
+            yield f
+
+    def close(self):
+        if self.fh is not None:
+            self.fh.close()
+            self.fh = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def read_y4m(path):
     """-> dict(h, w, fps=(num, den), fmt='i420' | 'i420p10', range, frames=[buffers [3 h / 2, w]]) of a file Y4MWriter wrote."""
     with open(path, 'rb') as fh:
         data = fh.read()
     end = data.index(b'\n')
-    tok = data[:end].decode('ascii').split(' ')
-    if tok[0] != 'YUV4MPEG2':
-        raise ValueError('%s: not a YUV4MPEG2 file' % path)
-    f = dict((t[0], t[1:]) for t in tok[1:] if t[0] != 'X')
-    x = dict(t[1:].split('=', 1) for t in tok[1:] if t[0] == 'X' and '=' in t)
-    h, w = int(f['H']), int(f['W'])
-    fmt = {'420jpeg': 'i420', '420p10': 'i420p10'}[f['C']]
+    hd = parse_y4m_header(data[:end], path)
+    h, w, fmt = hd['h'], hd['w'], hd['fmt']
     nbytes = frame_bytes(h, w, fmt)
     frames, pos = [], end + 1
     while pos < len(data):
@@ -238,4 +388,4 @@ def read_y4m(path):
             raise ValueError('%s: truncated frame %d' % (path, len(frames)))
         frames.append(np.frombuffer(raw, dtype=np.dtype(dtype_of(fmt)).newbyteorder('<')).astype(dtype_of(fmt)).reshape(frame_shape(h, w)))
         pos += nbytes
-    return {'h': h, 'w': w, 'fps': parse_fps(f['F']), 'fmt': fmt, 'range': x.get('COLORRANGE', 'LIMITED').lower(), 'frames': frames}
+    return dict(hd, frames=frames)
