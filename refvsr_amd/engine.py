@@ -21,7 +21,7 @@ import os
 
 import torch
 
-from . import ops, yuv
+from . import inputs, ops, yuv
 from .config import resolve_weight_precision
 from .knobs import env_flag
 from .packing import pack_conv, pack_conv_hr_last, pack_conv_last
@@ -45,29 +45,6 @@ def _flow_pairs(fr, restart):
     if restart:
         need += [(fr[i], fr[i - 1]) for i in range(1, ctr + 1)]
     return need
-
-
-def _input_kind(lrs, refs, input_yuv=None):
-    """What a window's frames were made from: None for float32 frames, the byte layouts (ops.u8_layout) of lr and ref for uint8 RGB
-    frames, ('yuv', format, matrix, range, chroma) for Y'CbCr 4:2:0 frames (config.input_yuv: frames [3h/2, w]).  Contexts of another
-    kind never match by content (a float frame is not compared with a byte frame, nor an RGB byte frame with a 4:2:0 one)."""
-    if input_yuv is not None:
-        return ('yuv',) + tuple(input_yuv)
-    return None if lrs.dtype != torch.uint8 else (ops.u8_layout(lrs), ops.u8_layout(refs))
-
-
-def _is_yuv(kind):
-    return kind is not None and kind[0] == 'yuv'
-
-
-def check_yuv_window(lrs, refs, fmt, dim, shape):
-    """config.input_yuv = fmt: lrs and refs are cuda tensors of `dim` dimensions, `shape` in words, dense 4:2:0 frames of the format's
-    sample type; RuntimeError (one line naming the expected shape and dtype) otherwise."""
-    dt = torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16
-    for x in (lrs, refs):
-        if not (x.is_cuda and x.dim() == dim and x.dtype == dt and x.shape == lrs.shape and ops.yuv_window_kind(x, fmt) is not None):
-            raise RuntimeError("input_yuv = '%s': lrs and refs must be contiguous cuda %s %s windows of one shape, 3h/2 rows with even "
-                               "h and w (got %s %s%s)" % (fmt, dt, shape, x.dtype, tuple(x.shape), '' if x.is_contiguous() else ', not contiguous'))
 
 
 # ---- layout of the device messages (state hand-off, contexts): a spec [(name, shape, dtype)] of parts that lie back to back in a
@@ -108,37 +85,18 @@ class FrameCtx(object):
     def __init__(self, lr, ref, ingest=None, yuv=None):
         self.uid = next(_uid)
         # the context OWNS its frames (clones): it outlives the call in the window cache, and a caller that refills one
-        # static input buffer in place must neither change cached data nor make the content compare see "equal" frames
-        self.kind = _input_kind(lr, ref, yuv)
-        if self.kind is None:
-            self.src = None
-            self.lr = lr.clone()    # planar fp32 [3,h,w]
-            self.ref = ref.clone()
-        elif _is_yuv(self.kind):
-            # 4:2:0 frames [3h/2, w] (yuv = config.input_yuv resolved): the copies of the source samples (half the bytes of the uint8
-            # kind, an eighth of the fp32 frames) key the content compare; the fp32 frames are filled by refvsr_yuv420_to_rgb -- now,
-            # or in the one launch over a call's new frames (ops.yuv420_ingest)
-            self.src = (lr.clone(), ref.clone())
-            h, w = ops.yuv_geometry(lr)
-            self.lr = torch.empty((3, h, w), dtype=torch.float32, device=lr.device)
-            self.ref = torch.empty((3, h, w), dtype=torch.float32, device=ref.device)
-            pairs = [(self.src[0], self.lr), (self.src[1], self.ref)]
-            if ingest is None:
-                ops.yuv420_ingest(pairs, *yuv)
-            else:
-                ingest.extend(pairs)
+        # static input buffer in place must neither change cached data nor make the content compare see "equal" frames.
+        # A kind that keeps the copies as `src` (8-bit, 4:2:0: they key the content compare) decodes the planar fp32 frames [3,h,w]
+        # from them -- now, or in the one launch over a call's new frames when the caller collects the pairs in `ingest`
+        source = inputs.source_of(lr, ref, yuv)             # (yuv: config.input_yuv resolved, Engine.input_yuv)
+        self.kind = source.key
+        copies = (lr.clone(), ref.clone())
+        self.src = copies if source.keeps_source else None
+        (self.lr, self.ref), pairs = source.frames(copies)
+        if ingest is None:
+            source.decode(pairs)
         else:
-            # 8-bit frames: the byte copies (a quarter of the fp32 size, in the caller's layout) key the content compare; the
-            # fp32 frames are filled by refvsr_ingest_u8 -- now, or in the one launch over a call's new frames when the caller
-            # collects them in `ingest` (ops.ingest_u8)
-            self.src = (lr.clone(), ref.clone())
-            self.lr = torch.empty(lr.shape, dtype=torch.float32, device=lr.device)
-            self.ref = torch.empty(ref.shape, dtype=torch.float32, device=ref.device)
-            pairs = [(self.src[0], self.lr), (self.src[1], self.ref)]
-            if ingest is None:
-                ops.ingest_u8(pairs)
-            else:
-                ingest.extend(pairs)
+            ingest.extend(pairs)
         self.lr8 = None         # nhwc16 [h,w,8]
         self.pyr = None         # SPyNet pyramid of lr, coarse -> fine
         self.conf = None        # planar [1,h,w]
@@ -337,8 +295,7 @@ class Engine(object):
         # Y'CbCr 4:2:0 copies of the results (extension; default None = off, no launch): the network calls also return 'yuv', one
         # refvsr_result_to_yuv420 launch per call on the stream that receives 'result' (model.py:Network._with_yuv)
         self.result_yuv = yuv.resolve(getattr(config, 'result_yuv', None), getattr(config, 'yuv_matrix', None), getattr(config, 'yuv_range', None))
-        # Y'CbCr 4:2:0 input frames (extension; default None = off, no new code runs): windows are [t, 3h/2, w] uint8 | uint16 buffers
-        # of the format, decoded by ONE refvsr_yuv420_to_rgb launch per call over the call's new frames (FrameCtx, _ingest)
+        # Y'CbCr 4:2:0 input frames (extension; default None = off): the windows' input source (inputs.py) is the 4:2:0 one
         self.input_yuv = yuv.resolve_input(getattr(config, 'input_yuv', None), getattr(config, 'input_yuv_matrix', None),
                                            getattr(config, 'input_yuv_range', None), getattr(config, 'input_yuv_chroma', None))
         self._pipe = None
@@ -976,10 +933,9 @@ class Engine(object):
 
     # ------------------------------------------------------------------ window bookkeeping
     def _frames(self, lrs, refs, frame_ids=None, ingest=None):
-        """Wrap the t frames of this window, reusing per-frame contexts of the previous window (or of
-        earlier positions in this window) whose content is identical -- or, when the caller supplies frame ids,
-        whose id matches (no device work, no synchronisation).  8-bit frames: the new contexts' conversions run as one
-        ingest launch at the end, or are left in the caller's `ingest` list (one launch over several windows)."""
+        """Wrap the t frames of this window, reusing per-frame contexts of the previous window (or of earlier positions in this window)
+        whose content is identical -- or, when the caller supplies frame ids, whose id matches (no device work, no synchronisation).
+        The new contexts' decodes (inputs.py) run as one launch at the end, or stay in the caller's `ingest` list (one over several windows)."""
         return self._frames_group([(lrs, refs, frame_ids)], ingest)[0]
 
     def _frames_group(self, wins, ingest=None):
@@ -987,22 +943,16 @@ class Engine(object):
         pend = [] if ingest is None else ingest
         out = [self._window_frames(*wins[0], pend)] if len(wins) == 1 else self._id_frames(wins, pend)
         if ingest is None:
-            self._ingest(pend)
+            self._source(wins[0]).decode(pend)
         return out
 
-    def _ingest(self, pend):
-        """The conversions of a call's new frames [(source, fp32 frame)] in one launch: uint8 RGB (refvsr_ingest_u8) or, under
-        config.input_yuv, 4:2:0 frames (refvsr_yuv420_to_rgb); float windows leave nothing pending."""
-        if self.input_yuv is None:
-            ops.ingest_u8(pend)
-        elif pend:
-            ops.yuv420_ingest(pend, *self.input_yuv)
+    def _source(self, win):
+        """The input source (inputs.source_of) of a window (lrs, refs, ..); the windows of one call are of one kind."""
+        return inputs.source_of(win[0], win[1], self.input_yuv)
 
     def _geometry(self, lrs):
         """(t, h, w) of a window of any kind: [t,3,h,w] RGB frames, or [t, 3h/2, w] 4:2:0 frames under config.input_yuv."""
-        if self.input_yuv is not None:
-            return (lrs.shape[0],) + ops.yuv_geometry(lrs)
-        return lrs.shape[0], lrs.shape[-2], lrs.shape[-1]
+        return (lrs.shape[0],) + tuple(self._source((lrs, lrs)).geometry(lrs))
 
     def _id_frames(self, wins, pend):
         """The id-keyed lookup for B >= 1 windows: a frame's context comes from the id cache, else from the contexts prepared / imported
@@ -1039,11 +989,8 @@ class Engine(object):
         if prev and tuple(prev[0].lr.shape[1:]) != self._geometry(lrs)[1:]:          # new clip geometry: nothing to reuse
             prev = []
             self.flow_cache = {}
-        kind = _input_kind(lrs, refs, self.input_yuv)
-        if kind is None:
-            same, own = ops.buffers_equal, (lambda f: (f.lr, f.ref))
-        else:                                                    # 8-bit and 4:2:0 frames: compared with the contexts' source copies
-            same, own = ops.bytes_equal, (lambda f: f.src)
+        source = self._source((lrs, refs))                       # (8-bit and 4:2:0 frames: compared with the contexts' source copies)
+        kind, same, own = source.key, source.equal, source.own
         if prev:
             # candidates in order of likelihood: the window slid by one (i+1), did not move (i), slid back (i-1);
             # all candidate pairs are compared by ONE kernel launch + one D2H sync
@@ -1409,7 +1356,7 @@ class Engine(object):
             for e, bs in zip(engines, mine):                          # new frames are cloned here, on P
                 for b, fr in zip(bs, e._frames_group([wins[b] for b in bs], pend)):
                     frs[b] = fr
-            self._ingest(pend)                                        # (8-bit / 4:2:0 frames: the call's new frames in one launch)
+            self._source(wins[0]).decode(pend)                        # (8-bit / 4:2:0 frames: the call's new frames in one launch)
             for e, bs in zip(engines, mine):
                 for b in bs:
                     # (a group's own preparation computes no backward head: its whole first step is cheaper as multi-map launches)
@@ -1608,16 +1555,12 @@ class Engine(object):
 
     # ------------------------------------------------------------------ two-phase forward (multi-GPU wavefront)
     def _check_window(self, lrs, refs):
-        if self.input_yuv is not None:
-            check_yuv_window(lrs, refs, self.input_yuv[0], 3, '[t, 3h/2, w]')
-        elif lrs.dim() == 3:
-            raise RuntimeError('a window is float32 or uint8 [t,3,h,w]; [t, 3h/2, w] Y\'CbCr 4:2:0 windows need config.input_yuv '
-                               '(got %s %s)' % (lrs.dtype, tuple(lrs.shape)))
-        else:
+        inputs.check_window(lrs, refs, self.input_yuv and self.input_yuv[0], 4, 'Engine', 't')
+        if self.input_yuv is None:                               # (the engine converts nothing)
             assert lrs.is_cuda and lrs.dim() == 4 and lrs.shape == refs.shape
             if lrs.dtype != refs.dtype or lrs.dtype not in (torch.float32, torch.uint8):
                 raise RuntimeError('lrs and refs must both be float32 or both uint8 (got %s, %s)' % (lrs.dtype, refs.dtype))
-            if lrs.dtype == torch.uint8 and None in _input_kind(lrs, refs):
+            if None in (self._source((lrs, refs)).key or ()):
                 raise RuntimeError('uint8 windows must be contiguous [t,3,h,w] or the channels-last view of [t,h,w,3] bytes')
         t, h, w = self._geometry(lrs)
         assert t >= 3 and t % 2 == 1 and h % 2 == 0 and w % 2 == 0, 'need odd t >= 3 and even h, w'

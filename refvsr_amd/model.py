@@ -20,8 +20,8 @@ import os
 import torch
 import torch.nn as nn
 
-from . import hip, ops
-from .engine import Engine, Weights, check_yuv_window
+from . import hip, inputs, ops
+from .engine import Engine, Weights
 from .fingerprint import WEIGHT_CHECKS, weight_check_policy
 from .weights import state_spec, strip_module_prefix
 
@@ -47,35 +47,35 @@ def _input_yuv(config):
     return None if r is None else r[0]
 
 
-def _inputs(lrs, refs, what, strict=False, input_yuv=None, dim=5):
-    """The network's input contract: float frames in [0, 1] (float16 / float64 are converted to float32, as in the reference), or uint8
-    frames meaning byte / 255 -- contiguous [.., 3, h, w] or the channels-last view of [.., h, w, 3] bytes, converted exactly on the
-    device (refvsr_ingest_u8).  lrs and refs are both uint8 or both not.  strict: inputs the engine reads off the caller's stream order
-    (input_ready= on the pipelined path) are refused instead of converted.
-    input_yuv (config.input_yuv, a format): Y'CbCr 4:2:0 windows [.., t, 3h/2, w] instead (`dim` - 1 dimensions), dense and of the
-    format's sample type, decoded exactly on the device (refvsr_yuv420_to_rgb); nothing is converted here, anything else is refused."""
-    if input_yuv is not None:
-        check_yuv_window(lrs, refs, input_yuv, dim - 1, {5: '[n, t, 3h/2, w]', 4: '[t, 3h/2, w]'}[dim])
-        return lrs, refs
-    if lrs.dim() == dim - 1 and lrs.dtype in (torch.uint8, torch.uint16):
-        raise RuntimeError("%s: windows are float or uint8 [.., t, 3, h, w]; [.., t, 3h/2, w] Y'CbCr 4:2:0 windows need config.input_yuv "
-                           "(got %s %s)" % (what, lrs.dtype, tuple(lrs.shape)))
-    if (lrs.dtype == torch.uint8) != (refs.dtype == torch.uint8):
-        raise RuntimeError('%s: lrs and refs must both be uint8 or both float (got %s and %s)' % (what, lrs.dtype, refs.dtype))
-    if lrs.dtype == torch.uint8:
-        if strict:
-            for t_ in (lrs, refs):
-                if ops.u8_layout(t_) is None:
-                    raise RuntimeError('%s: pipelined mode with input_ready= needs uint8 inputs that are contiguous or the channels-last '
-                                       'view of [.., h, w, 3] bytes (got strides %s): convert before the producer signals, or pass '
-                                       'input_ready=None' % (what, tuple(t_.stride())))
-        return tuple(t_ if ops.u8_layout(t_) is not None else t_.contiguous() for t_ in (lrs, refs))
-    if strict:
+_STRICT = {True: '%s: pipelined mode with input_ready= needs uint8 inputs that are contiguous or the channels-last view of [.., h, w, 3] bytes '
+                 '(got strides %s): convert before the producer signals, or pass input_ready=None',
+           False: 'pipelined mode with input_ready= needs contiguous float32 inputs (got %s, contiguous=%s): convert before the producer '
+                  'signals, or pass input_ready=None'}
+
+
+def _inputs(lrs, refs, what, strict=False, input_yuv=None, dim=5, convert=True):
+    """The network's input contract, the ONE entry check (the kinds: inputs.py): float frames in [0, 1] (float16 / float64 are converted
+    to float32, as in the reference), or uint8 frames meaning byte / 255 -- contiguous [.., 3, h, w] or the channels-last view of
+    [.., h, w, 3] bytes, converted exactly on the device (refvsr_ingest_u8); lrs and refs are both uint8 or both not.  strict: inputs the
+    engine reads off the caller's stream order (input_ready= on the pipelined path) are refused instead of converted; convert False
+    (forward_group): what would need a conversion is refused, in forward_group's own words and order.  input_yuv (config.input_yuv, a
+    format): dense Y'CbCr 4:2:0 windows [.., t, 3h/2, w] instead (`dim` - 1 dimensions), decoded on the device; nothing is converted."""
+    if input_yuv is None and not convert:
         for t_ in (lrs, refs):
-            if t_.dtype != torch.float32 or not t_.is_contiguous():
-                raise RuntimeError('pipelined mode with input_ready= needs contiguous float32 inputs (got %s, contiguous=%s): '
-                                   'convert before the producer signals, or pass input_ready=None' % (t_.dtype, t_.is_contiguous()))
-    return lrs.float().contiguous(), refs.float().contiguous()
+            if not inputs.as_is(t_) or t_.dim() != dim:
+                raise RuntimeError('%s needs contiguous float32 or uint8 [B,t,3,h,w] inputs, or the channels-last view of uint8 '
+                                   '[B,t,h,w,3] (got %s, contiguous=%s)' % (what, t_.dtype, t_.is_contiguous()))
+        if lrs.dtype != refs.dtype:
+            raise RuntimeError('%s: lrs and refs must both be uint8 or both float32 (got %s and %s)' % (what, lrs.dtype, refs.dtype))
+        return lrs, refs
+    inputs.check_window(lrs, refs, input_yuv, dim, what, 'B, t' if not convert else {5: 'n, t', 4: 't'}[dim])
+    if input_yuv is not None:
+        return lrs, refs
+    u8 = lrs.dtype == torch.uint8
+    for t_ in (lrs, refs):
+        if strict and not inputs.as_is(t_):
+            raise RuntimeError(_STRICT[u8] % ((what, tuple(t_.stride())) if u8 else (t_.dtype, t_.is_contiguous())))
+    return tuple(t_ if inputs.as_is(t_) else t_.contiguous() if u8 else t_.float().contiguous() for t_ in (lrs, refs))
 
 
 class _FlowNetHandle(nn.Module):
@@ -293,6 +293,24 @@ class Network(nn.Module):
             self._engines.append(self._engine_cls(self.config, W))
         return self._engines
 
+    def _device(self, x):
+        """The preamble of every entry that takes frames: the library is loaded (fails loudly if missing), the frames are on the GPU."""
+        hip.lib()
+        if not x.is_cuda:
+            raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path' % x.device)
+        return x.device
+
+    def _outs(self, results, vis=None, dbg=None):
+        """The OrderedDict a call returns for the n results [3,sh,sw] of its samples: 'vis' (is_log; dbg: the samples' debug dicts),
+        'result' [n,3,sh,sw] (n == 1: a view, no 25 MB copy), 'eval_vis' (vis: the samples' map dicts; RefVSR_IR has none)."""
+        outs = collections.OrderedDict()
+        if dbg is not None:                                    # RefVSR.py:162-164,219-221,262-263,301-316
+            outs['vis'] = collections.OrderedDict((k, torch.stack([d[k] for d in dbg], 0)) for k in (dbg[0] if dbg else ()))
+        outs['result'] = results[0].unsqueeze(0) if len(results) == 1 else self._stack(results)
+        if vis is not None and vis[0] is not None:
+            outs['eval_vis'] = collections.OrderedDict((k, torch.stack([v[k] for v in vis], 0)) for k in vis[0])
+        return outs
+
     def _stack(self, results):
         """n results [3,sh,sw] -> [n,3,sh,sw] in the engines' result layout (config.result_layout = 'hwc': dense [n,sh,sw,3] memory)."""
         return ops.stack_results(results, self._engines[0].result_layout)
@@ -315,12 +333,8 @@ class Network(nn.Module):
         Under config.input_yuv lrs, refs are Y'CbCr 4:2:0 windows [n, t, 3h/2, w] instead (uint8 | uint16 by format, see _inputs)."""
         if is_train:
             raise NotImplementedError('refvsr_amd implements the inference path only (is_train=False)')
-        hip.lib()                                              # fail loudly if the extension is missing
-        if not lrs.is_cuda:
-            raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path'
-                               % lrs.device)
         n = lrs.shape[0]
-        self.ensure_engines(n, lrs.device, (frame_ids is not None, bool(is_first_frame)))
+        self.ensure_engines(n, self._device(lrs), (frame_ids is not None, bool(is_first_frame)))
         # the engine's internal streams will read the inputs when `input_ready` says so, not in the caller's stream order: a
         # dtype / layout conversion here would be pending work on the caller's stream that nothing waits for -- refused
         # instead of raced against.  (input_ready=None waits for the caller's stream, conversions included; calls that take
@@ -328,17 +342,14 @@ class Network(nn.Module):
         strict = input_ready is not None and any(e.takes_pipelined_path(frame_ids, bool(is_log)) for e in self._engines[:n])
         lrs, refs = _inputs(lrs, refs, 'forward', strict, _input_yuv(self.config))
         want_vis = bool(is_log and self.config.save_sample)
-        results, vis_all = [], []
-        dbg_all = []
+        results, vis_all, dbg_all = [], [], []
         if (n > 1 and frame_ids is not None and not is_log and
                 all(e.takes_pipelined_path(frame_ids, False) and e.group_ok() for e in self._engines[:n])):
             # round 5: the n samples are n independent streams over identical weights -- in steady state their forward-branch steps and
             # backward branches run as multi-map launches (Engine.forward_multi); same results as the loop below, bit for bit
             res = self._engine_cls.forward_multi(self._engines[:n], lrs, refs, bool(is_first_frame),
                                                  [[(b, f) for f in frame_ids] for b in range(n)], input_ready)
-            outs = collections.OrderedDict()
-            outs['result'] = self._stack(res)
-            return self._with_yuv(outs, res, True)
+            return self._with_yuv(self._outs(res), res, True)
         for b in range(n):
             out, vis = self._engines[b].forward(lrs[b], refs[b], bool(is_first_frame), want_vis,
                                                 None if frame_ids is None else [(b, f) for f in frame_ids], want_log=bool(is_log),
@@ -348,16 +359,7 @@ class Network(nn.Module):
                 dbg_all.append(dbg)
             results.append(out)
             vis_all.append(vis)
-        outs = collections.OrderedDict()
-        if is_log:                                             # RefVSR.py:162-164,219-221,262-263,301-316
-            outs['vis'] = collections.OrderedDict((k, torch.stack([d[k] for d in dbg_all], 0)) for k in dbg_all[0])
-        outs['result'] = results[0].unsqueeze(0) if n == 1 else self._stack(results)        # (n == 1: a view, no 25 MB copy)
-        if want_vis and vis_all[0] is not None:                # (RefVSR_IR has no 'eval_vis')
-            ev = collections.OrderedDict()
-            for k in vis_all[0]:
-                ev[k] = torch.stack([v[k] for v in vis_all], 0)
-            outs['eval_vis'] = ev
-        return self._with_yuv(outs, results, True)
+        return self._with_yuv(self._outs(results, vis_all if want_vis else None, dbg_all if is_log else None), results, True)
 
     def forward_group(self, lrs, refs, frame_ids, is_first_frame=False, input_ready=None, want_conf=False):
         """B CONSECUTIVE windows of one stream in one call (extension; see Engine.forward_group): lrs, refs [B,t,3,h,w] -- window b
@@ -367,27 +369,13 @@ class Network(nn.Module):
         want_conf: the dict also carries 'eval_vis', a tuple of B OrderedDicts of [1,1,h,w] float32 maps -- what forward(window b, ..,
         is_log=True) returns as 'eval_vis' under config.save_sample (RefVSR.py:318-322), bit for bit.  (RefVSR_IR has no such maps:
         no 'eval_vis' key, as in forward().)  Off (the default), no launch is added."""
-        hip.lib()
-        if not lrs.is_cuda:
-            raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path' % lrs.device)
-        fmt = _input_yuv(self.config)
-        if fmt is not None:                                    # (config.input_yuv: [B, t, 3h/2, w] 4:2:0 windows)
-            check_yuv_window(lrs, refs, fmt, 4, '[B, t, 3h/2, w]')
-        else:
-            for t_ in (lrs, refs):
-                ok = t_.dtype == torch.uint8 and ops.u8_layout(t_) is not None or t_.dtype == torch.float32 and t_.is_contiguous()
-                if not ok or t_.dim() != 5:
-                    raise RuntimeError('forward_group needs contiguous float32 or uint8 [B,t,3,h,w] inputs, or the channels-last view of uint8 '
-                                       '[B,t,h,w,3] (got %s, contiguous=%s)' % (t_.dtype, t_.is_contiguous()))
-            if lrs.dtype != refs.dtype:
-                raise RuntimeError('forward_group: lrs and refs must both be uint8 or both float32 (got %s and %s)' % (lrs.dtype, refs.dtype))
+        dev = self._device(lrs)
+        _inputs(lrs, refs, 'forward_group', input_yuv=_input_yuv(self.config), convert=False)
         assert len(frame_ids) == lrs.shape[0] and lrs.shape == refs.shape
-        eng = self.ensure_engines(1, lrs.device, (True, bool(is_first_frame)))[0]
+        eng = self.ensure_engines(1, dev, (True, bool(is_first_frame)))[0]
         wins = [(lrs[b], refs[b], [(0, f) for f in frame_ids[b]]) for b in range(lrs.shape[0])]
         res = eng.forward_group(wins, bool(is_first_frame), input_ready, want_vis=bool(want_conf))
-        vis = None
-        if want_conf:
-            res, vis = res
+        res, vis = res if want_conf else (res, None)
         outs = collections.OrderedDict()
         outs['result'] = tuple(r.unsqueeze(0) for r in res)
         if vis is not None and all(v is not None for v in vis):
@@ -397,11 +385,9 @@ class Network(nn.Module):
     # ---- two-phase forward for the multi-GPU wavefront (refvsr_amd/shard.py:run_wavefront; not in the reference) ----
     def phase_a(self, lrs, refs, frame_ids=None, first_hint=False):
         """State-independent part of forward() (preparation + backward branch) for lrs, refs [n,t,3,h,w]."""
-        hip.lib()
-        if not lrs.is_cuda:
-            raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path' % lrs.device)
+        dev = self._device(lrs)
         lrs, refs = _inputs(lrs, refs, 'phase_a', input_yuv=_input_yuv(self.config))
-        self.ensure_engines(lrs.shape[0], lrs.device, (frame_ids is not None, bool(first_hint)))
+        self.ensure_engines(lrs.shape[0], dev, (frame_ids is not None, bool(first_hint)))
         return [self._engines[b].phase_a(lrs[b], refs[b], None if frame_ids is None else [(b, f) for f in frame_ids],
                                          first_hint) for b in range(lrs.shape[0])]
 
@@ -409,11 +395,9 @@ class Network(nn.Module):
         """phase_a of B windows of ONE clip in one pass (round 6; see Engine.phase_a_group): lrs, refs [B,t,3,h,w], frame_ids B lists of t
         ids (or sequences of B window tensors [t,3,h,w]).  Returns B handle lists (one per window, each what phase_a returns for an
         n = 1 call)."""
-        hip.lib()
-        if not lrs[0].is_cuda:
-            raise RuntimeError('refvsr_amd.Network runs on the GPU only (got a %s tensor); there is no CPU path' % lrs[0].device)
+        dev = self._device(lrs[0])
         assert len(lrs) == len(refs) == len(frame_ids)
-        eng = self.ensure_engines(1, lrs[0].device, (True, False))[0]
+        eng = self.ensure_engines(1, dev, (True, False))[0]
         fmt = _input_yuv(self.config)
         wins = [_inputs(lrs[b], refs[b], 'phase_a_group', input_yuv=fmt, dim=4) + ([(0, f) for f in frame_ids[b]],) for b in range(len(lrs))]
         return [[h] for h in eng.phase_a_group(wins, first_hints, streams)]
@@ -428,16 +412,7 @@ class Network(nn.Module):
         """State-free rest of phase_b (BW/FW fusion + upsampler); same return value as forward()."""
         want_vis = bool(is_log and self.config.save_sample)
         res = [self._engines[b].phase_b2(h, want_vis) for b, h in enumerate(handles)]
-        outs = collections.OrderedDict()
-        if is_log:
-            outs['vis'] = collections.OrderedDict()
-        outs['result'] = res[0][0].unsqueeze(0) if len(res) == 1 else self._stack([r[0] for r in res])
-        if want_vis:
-            ev = collections.OrderedDict()
-            for k in res[0][1]:
-                ev[k] = torch.stack([r[1][k] for r in res], 0)
-            outs['eval_vis'] = ev
-        return outs
+        return self._outs([r[0] for r in res], [r[1] for r in res] if want_vis else None, [] if is_log else None)
 
     def phase_b(self, handles, is_first_frame, is_log=False, after_state=None):
         """State-dependent rest (forward-branch step + upsampler); same return value as forward().
@@ -445,16 +420,7 @@ class Network(nn.Module):
         want_vis = bool(is_log and self.config.save_sample)
         res = [self._engines[b].phase_b(h, bool(is_first_frame), want_vis, after_state if b == 0 else None)
                for b, h in enumerate(handles)]
-        outs = collections.OrderedDict()
-        if is_log:
-            outs['vis'] = collections.OrderedDict()
-        outs['result'] = res[0][0].unsqueeze(0) if len(res) == 1 else self._stack([r[0] for r in res])
-        if want_vis:
-            ev = collections.OrderedDict()
-            for k in res[0][1]:
-                ev[k] = torch.stack([r[1][k] for r in res], 0)
-            outs['eval_vis'] = ev
-        return outs
+        return self._outs([r[0] for r in res], [r[1] for r in res] if want_vis else None, [] if is_log else None)
 
 
 class SRNet(nn.Module):

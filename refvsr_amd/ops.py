@@ -703,29 +703,24 @@ def max2(a, b):
     return out
 
 
-def _pairs_equal(pairs, name, nbytes, check):
-    """refvsr_<name> over (a, b) pairs of nbytes bytes each, check(a, b) asserted per pair: one launch per 32 pairs, one D2H sync."""
+def _pairs_equal(pairs, name, ok):
+    """refvsr_<name> over (a, b) pairs of one size in bytes, ok(a, b) asserted per pair: one launch per 32 pairs, one D2H sync."""
+    if not pairs:
+        return []
+    nbytes = pairs[0][0].numel() * pairs[0][0].dtype.itemsize
     flags = torch.ones(len(pairs), dtype=torch.int32, device=pairs[0][0].device)
     for s0 in range(0, len(pairs), 32):
         chunk = pairs[s0:s0 + 32]
         for a, b in chunk:
-            check(a, b)
+            assert ok(a, b) and a.dtype == b.dtype == pairs[0][0].dtype and a.numel() == b.numel() == pairs[0][0].numel()
         hip.check(getattr(hip.lib(), 'refvsr_' + name)(_parr([a for a, _ in chunk]), _parr([b for _, b in chunk]), len(chunk), nbytes,
                                                        C.c_void_p(flags.data_ptr() + 4 * s0), _stream()), name)
     return [bool(v) for v in flags.cpu().tolist()]
 
 
 def buffers_equal(pairs):
-    """pairs: list of (a, b) float32 tensors of one common shape.  Returns a python list of bools
-    (one launch per 32 pairs, one D2H sync)."""
-    if not pairs:
-        return []
-    nbytes = pairs[0][0].numel() * 4
-
-    def check(a, b):
-        assert a.shape == b.shape and a.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
-        assert a.numel() * 4 == nbytes
-    return _pairs_equal(pairs, 'buffers_equal', nbytes, check)
+    """pairs: list of (a, b) float32 tensors of one common shape.  Returns a python list of bools (one launch per 32 pairs, one D2H sync)."""
+    return _pairs_equal(pairs, 'buffers_equal', lambda a, b: a.shape == b.shape and a.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous())
 
 
 def bytes_equal(pairs):
@@ -733,15 +728,8 @@ def bytes_equal(pairs):
     may differ in alignment), or contiguous uint16 tensors (4:2:0 frames of 10-bit samples), compared through their bytes.  Returns a
     python list of bools -- True where the raw bytes are equal (one launch per 32 pairs, one D2H sync).  The caller compares frames
     of one layout only."""
-    if not pairs:
-        return []
-    dt = pairs[0][0].dtype
-    nbytes = pairs[0][0].numel() * dt.itemsize
-
-    def check(a, b):
-        assert dt in (torch.uint8, torch.uint16) and a.dtype == dt and b.dtype == dt and a.numel() * dt.itemsize == b.numel() * dt.itemsize == nbytes
-        assert all(x.is_contiguous() or u8_layout(x) is not None for x in (a, b))
-    return _pairs_equal(pairs, 'bytes_equal', nbytes, check)
+    return _pairs_equal(pairs, 'bytes_equal', lambda a, b: a.dtype in (torch.uint8, torch.uint16) and
+                        all(x.is_contiguous() or u8_layout(x) is not None for x in (a, b)))
 
 
 def u8_layout(x):
@@ -763,43 +751,50 @@ def ingest_table():
     return list(t)
 
 
+def _decode_frames(pairs, name, what, ok, max_frames, launch):
+    """ingest_u8 / yuv420_ingest over pairs [(src frame, dst float32 [3,h,w] contiguous)] of one h x w: ok(src, h, w) asserted per pair
+    (`what`), then one launch(srcs, dsts, n, h, w) of refvsr_<name> per max_frames frames, on the current stream."""
+    h, w = pairs[0][1].shape[1:]
+    for src, dst in pairs:
+        assert ok(src, h, w) and _planar(dst, 3).shape[1:] == (h, w), what
+    for s0 in range(0, len(pairs), max_frames):
+        chunk = pairs[s0:s0 + max_frames]
+        hip.check(launch(_parr([s_ for s_, _ in chunk]), _parr([d for _, d in chunk]), len(chunk), h, w), name)
+
+
+def _frames_of(x, nd, dense, align, h, w, decode):
+    """ingest_frames / yuv420_to_frames: x [..., <nd frame dimensions>] made dense (a copy otherwise) in storage aligned to `align` bytes
+    (a copy otherwise: it keeps the strides of a dense tensor), a new contiguous float32 [..., 3, h, w] allocated, both viewed as
+    frames and handed to decode([(src frame, dst frame)]).  Returns the new tensor."""
+    if not dense(x):
+        x = x.contiguous()
+    if x.data_ptr() % align:
+        x = x.clone()
+    out = torch.empty(tuple(x.shape[:-nd]) + (3, h, w), dtype=torch.float32, device=x.device)
+    if x.is_contiguous():
+        frames = x.reshape((-1,) + tuple(x.shape[-nd:]))
+    else:                                            # (channels-last uint8 RGB)
+        frames = x.movedim(-3, -1).reshape(-1, h, w, 3).permute(0, 3, 1, 2)
+    decode(list(zip(frames, out.view(-1, 3, h, w))))
+    return out
+
+
 def ingest_u8(pairs):
     """pairs: [(src uint8 [3,h,w] (u8_layout not None), dst float32 [3,h,w] contiguous)] of one h x w: dst = src / 255 exactly as the
     reference loader computes it (refvsr_ingest_u8).  One launch per layout and REFVSR_INGEST_MAX_FRAMES frames."""
-    if not pairs:
-        return
-    h, w = pairs[0][1].shape[1:]
-    by_layout = {}
-    for src, dst in pairs:
-        lay = u8_layout(src)
-        assert lay is not None and src.shape == (3, h, w), 'ingest_u8: uint8 [3,h,w] planar or channels-last frames of one size'
-        _planar(dst, 3)
-        assert dst.shape[1:] == (h, w)
-        by_layout.setdefault(lay, []).append((src, dst))
-    for lay, pp in sorted(by_layout.items()):
-        for s0 in range(0, len(pp), hip.INGEST_MAX_FRAMES):
-            chunk = pp[s0:s0 + hip.INGEST_MAX_FRAMES]
-            ps = (C.c_void_p * len(chunk))(*[s.data_ptr() for s, _ in chunk])
-            pd = (C.c_void_p * len(chunk))(*[d.data_ptr() for _, d in chunk])
-            hip.check(hip.lib().refvsr_ingest_u8(ps, pd, len(chunk), h, w, lay, _stream()), 'ingest_u8')
+    what = 'ingest_u8: uint8 [3,h,w] planar or channels-last frames of one size'
+    lays = [u8_layout(src) for src, _ in pairs]
+    assert None not in lays, what
+    for lay in sorted(set(lays)):
+        _decode_frames([p for p, l_ in zip(pairs, lays) if l_ == lay], 'ingest_u8', what, lambda src, h, w: src.shape == pairs[0][1].shape,
+                       hip.INGEST_MAX_FRAMES, lambda ps, pd, n, h, w: hip.lib().refvsr_ingest_u8(ps, pd, n, h, w, lay, _stream()))
 
 
 def ingest_frames(x):
     """uint8 [..., 3, h, w] (planar or channels-last; other strides and unaligned storage are copied first) -> a new contiguous
     float32 tensor of the same shape, x / 255 as the reference loader computes it, frame by frame through refvsr_ingest_u8."""
     assert x.is_cuda and x.dtype == torch.uint8 and x.dim() >= 3 and x.shape[-3] == 3, 'ingest_frames: cuda uint8 [..., 3, h, w]'
-    h, w = x.shape[-2:]
-    if u8_layout(x) is None:
-        x = x.contiguous()
-    if x.data_ptr() % 4:
-        x = x.clone()                            # (keeps the strides of a dense tensor, in fresh aligned storage)
-    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    if x.is_contiguous():
-        frames = x.reshape(-1, 3, h, w)
-    else:
-        frames = x.movedim(-3, -1).reshape(-1, h, w, 3).permute(0, 3, 1, 2)
-    ingest_u8(list(zip(frames, out.view(-1, 3, h, w))))
-    return out
+    return _frames_of(x, 3, lambda x_: u8_layout(x_) is not None, 4, x.shape[-2], x.shape[-1], ingest_u8)
 
 
 _SCORE_WS = {}        # (device, stream handle, h, w) -> workspace of one full refvsr_score_frames launch
@@ -969,17 +964,9 @@ def yuv420_ingest(pairs, fmt='nv12', matrix='bt709', range='limited', chroma='bi
         return
     coef = (C.c_double * 9)(*yuv.decode_coefficients(fmt, matrix, range))
     mode = yuv.CHROMA_MODES[yuv.check_chroma(chroma)]
-    h, w = pairs[0][1].shape[1:]
-    for src, dst in pairs:
-        assert yuv_window_kind(src, fmt) is not None and tuple(src.shape) == yuv.frame_shape(h, w), \
-            'yuv420_ingest: dense %s frames [3h/2, w] of one size' % fmt
-        _planar(dst, 3)
-        assert dst.shape[1:] == (h, w)
-    st = _stream()
-    for s0 in _irange(0, len(pairs), hip.YUV420_IN_MAX_FRAMES):
-        chunk = pairs[s0:s0 + hip.YUV420_IN_MAX_FRAMES]
-        hip.check(hip.lib().refvsr_yuv420_to_rgb(_parr([s_ for s_, _ in chunk]), _parr([d for _, d in chunk]), len(chunk), h, w,
-                                                 yuv.FORMAT_IDS[fmt], mode, coef, st), 'yuv420_to_rgb')
+    _decode_frames(pairs, 'yuv420_to_rgb', 'yuv420_ingest: dense %s frames [3h/2, w] of one size' % fmt,
+                   lambda src, h, w: yuv_window_kind(src, fmt) is not None and tuple(src.shape) == yuv.frame_shape(h, w), hip.YUV420_IN_MAX_FRAMES,
+                   lambda ps, pd, n, h, w: hip.lib().refvsr_yuv420_to_rgb(ps, pd, n, h, w, yuv.FORMAT_IDS[fmt], mode, coef, _stream()))
 
 
 def yuv420_to_frames(x, h, w, fmt, matrix='bt709', range='limited', chroma='bilinear'):
@@ -991,13 +978,7 @@ def yuv420_to_frames(x, h, w, fmt, matrix='bt709', range='limited', chroma='bili
     if not (x.is_cuda and x.dtype == dt and x.dim() >= 2 and tuple(x.shape[-2:]) == yuv.frame_shape(h, w)):
         raise RuntimeError('yuv420_to_frames: cuda %s [..., %d, %d] frames for %s at %d x %d (got %s %s %s)'
                            % (dt, 3 * h // 2, w, fmt, h, w, x.device.type, x.dtype, tuple(x.shape)))
-    if not x.is_contiguous():
-        x = x.contiguous()
-    if x.data_ptr() % dt.itemsize:
-        x = x.clone()
-    out = torch.empty(tuple(x.shape[:-2]) + (3, h, w), dtype=torch.float32, device=x.device)
-    yuv420_ingest(list(zip(x.reshape((-1,) + tuple(x.shape[-2:])), out.view(-1, 3, h, w))), fmt, matrix, range, chroma)
-    return out
+    return _frames_of(x, 2, torch.Tensor.is_contiguous, dt.itemsize, h, w, lambda pairs: yuv420_ingest(pairs, fmt, matrix, range, chroma))
 
 
 _COLORMAP_WS = {}     # (device, stream handle, h, w) -> workspace of one full refvsr_conf_colormap launch

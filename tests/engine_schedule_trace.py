@@ -5,7 +5,7 @@ An Engine is built with Engine.__new__ and driven through its public methods onl
 phase_a_group, phase_b1 / phase_b2 / phase_b), so the same file records the traces from one tree and checks another.
 torch.cuda.Stream / Event / current_stream / device and ops.on_stream are named fakes that log; windows, frames and maps are
 stand-ins whose record_stream logs; the leaves below the schedule (pyramid, prepare_frame, the backward head, _prop_step,
-compute_up, _conf_vis, ops.ingest_u8, the SPyNet body) log one token each.  The window cache, the flow cache and its events are
+compute_up, _conf_vis, ops.ingest_u8, ops.yuv420_ingest, the SPyNet body) log one token each.  The window cache, the flow cache and its events are
 the engine's own.  A trace line is '<current stream>| <what>'; runs of record_stream calls and of wait_event calls share a line (State.run).
 
 Recording (from the repository root):  python tests/engine_schedule_trace.py tests/golden/engine_schedule.json
@@ -153,17 +153,20 @@ class T(object):
     """A stand-in tensor: a name, a shape, a dtype and a content token (what the content compare of the window cache sees)."""
     device, is_cuda = DEV, True
 
-    def __init__(self, name, shape, dtype=torch.float32, content=None):
-        self.name, self.shape, self.dtype, self.content = name, tuple(shape), dtype, content
+    def __init__(self, name, shape, dtype=torch.float32, content=None, layout=0):
+        self.name, self.shape, self.dtype, self.content, self.layout = name, tuple(shape), dtype, content, layout
 
     def record_stream(self, st):
         S.run('rs', self.name, st.name)
 
     def clone(self):
-        return T(self.name + "'", self.shape, self.dtype, self.content)
+        return T(self.name + "'", self.shape, self.dtype, self.content, self.layout)
 
     def contiguous(self):
         return self
+
+    def is_contiguous(self):
+        return True
 
     def dim(self):
         return len(self.shape)
@@ -187,24 +190,34 @@ class T(object):
     view = reshape
 
 
-class Window(T):
-    """A window [t,3,h,w] of the frames `nums` of a clip: lrs[i] is the frame itself ('lr5'), whatever window it is asked from."""
+YUV_DTYPES = {'nv12': torch.uint8, 'p010': torch.uint16}
 
-    def __init__(self, kind, nums, dtype):
-        T.__init__(self, '%ss[%s]' % (kind, ','.join(str(n) for n in nums)), (len(nums), 3, H, W), dtype)
+
+def frame_shape(yuv):
+    """One frame of a window: [3,h,w] RGB, or the dense 4:2:0 buffer [3h/2, w] of config.input_yuv."""
+    return (3 * H // 2, W) if yuv else (3, H, W)
+
+
+class Window(T):
+    """A window [t,3,h,w] of the frames `nums` of a clip: lrs[i] is the frame itself ('lr5'), whatever window it is asked from.
+    yuv (a format): a 4:2:0 window [t, 3h/2, w] of the format's sample type; layout: what ops.u8_layout says of a uint8 window."""
+
+    def __init__(self, kind, nums, dtype, yuv=None, layout=0):
+        T.__init__(self, '%ss[%s]' % (kind, ','.join(str(n) for n in nums)), (len(nums),) + frame_shape(yuv),
+                   YUV_DTYPES[yuv] if yuv else dtype, layout=layout)
         self.kind, self.nums = kind, list(nums)
 
     def __getitem__(self, i):
         name = '%s%d' % (self.kind, self.nums[i])
-        return T(name, (3, H, W), self.dtype, content=name)
+        return T(name, self.shape[1:], self.dtype, content=name, layout=self.layout)
 
 
 class Samples(T):
     """The n windows of a forward_multi call, [n,t,3,h,w]; sample b's frames are named 'b.lr5'."""
 
-    def __init__(self, kind, nums, n, dtype):
-        T.__init__(self, '%ss%d[%s]' % (kind, n, ','.join(str(x) for x in nums)), (n, len(nums), 3, H, W), dtype)
-        self.wins = [Window('%d.%s' % (b, kind), nums, dtype) for b in range(n)]
+    def __init__(self, kind, nums, n, dtype, yuv=None):
+        T.__init__(self, '%ss%d[%s]' % (kind, n, ','.join(str(x) for x in nums)), (n, len(nums)) + frame_shape(yuv), YUV_DTYPES[yuv] if yuv else dtype)
+        self.wins = [Window('%d.%s' % (b, kind), nums, dtype, yuv) for b in range(n)]
 
     def __getitem__(self, b):
         return self.wins[b]
@@ -259,15 +272,24 @@ def patch_all(setattr_):
         if pairs:
             S.add('ingest_u8 %s' % names([src for src, _ in pairs]))
     setattr_(ops, 'ingest_u8', ingest_u8)
-    setattr_(ops, 'u8_layout', lambda x: 0)
+    setattr_(ops, 'u8_layout', lambda x: x.layout)
+
+    def yuv420_ingest(pairs, *params):
+        if pairs:
+            S.add('yuv420_ingest %s %s' % (' '.join(params), names([src for src, _ in pairs])))
+    setattr_(ops, 'yuv420_ingest', yuv420_ingest)
+    setattr_(ops, 'yuv_window_kind', lambda x, fmt: ('yuv', fmt) if x.dtype == YUV_DTYPES[fmt] and x.shape[-2] % 3 == 0 else None)
+    setattr_(ops, 'yuv_geometry', lambda x: (2 * x.shape[-2] // 3, x.shape[-1]))
     setattr_(ops, 'conf_alpha_ok', lambda cw, B=None: True)
 
-    def equal(pairs):
-        if pairs:
-            S.add('compare %d' % len(pairs))
-        return [a.content == b.content for a, b in pairs]
-    setattr_(ops, 'buffers_equal', equal)
-    setattr_(ops, 'bytes_equal', equal)
+    def equal(what):
+        def same(pairs):
+            if pairs:
+                S.add('compare %s%d' % (what, len(pairs)))
+            return [a.content == b.content for a, b in pairs]
+        return same
+    setattr_(ops, 'buffers_equal', equal(''))
+    setattr_(ops, 'bytes_equal', equal('bytes '))
     setattr_(ops, 'warp_planar', lambda x, fl: S.add('warp_planar %s %s' % (x.name, fl.name)) or T('warp%d' % S.tok(), x.shape))
 
     # ---- the SPyNet body under Engine.flow / Engine._flow_batch: one token when a pass starts, one per resize that ends it
@@ -304,9 +326,10 @@ def patch_all(setattr_):
     setattr_(engine.Engine, '_conf_vis', staticmethod(conf_vis))
 
 
-def make_engine(C=24, layout=None, pipelined=False, overlap=True, gradio=False, reset=None, weights=None, group=True):
-    from refvsr_amd import engine
+def make_engine(C=24, layout=None, pipelined=False, overlap=True, gradio=False, reset=None, weights=None, group=True, input_yuv=None):
+    from refvsr_amd import engine, yuv
     e = engine.Engine.__new__(engine.Engine)
+    e.input_yuv = yuv.resolve_input(input_yuv)
     e.cfg = type('Cfg', (), dict(reset_branch=reset, pipe_layout=layout, cu_split=None, scale=4,
                                  EVAL=type('Eval', (), dict(is_gradio=gradio))()))()
     e.W = weights if weights is not None else type('Wts', (), dict(chains={}, conv=Named(lambda n: CW(n, ('w', 'b'))),
@@ -372,15 +395,15 @@ def name_pipe(e):
     return pipe
 
 
-def window(f, dtype=torch.float32, last=None):
+def window(f, dtype=torch.float32, last=None, yuv=None, ref_layout=0):
     """The window of centre frame f of a clip of frames 0 .. last (edges replicate, datasets.py:233-234) + its frame ids."""
     nums = [min(max(f + d, 0), last if last is not None else f + 1) for d in range(-(T_FRAMES // 2), T_FRAMES // 2 + 1)]
-    return Window('lr', nums, dtype), Window('ref', nums, dtype), list(nums)
+    return Window('lr', nums, dtype, yuv), Window('ref', nums, dtype, yuv, ref_layout), list(nums)
 
 
-def samples(f, n, dtype=torch.float32):
+def samples(f, n, dtype=torch.float32, yuv=None):
     nums = [max(f + d, 0) for d in range(-(T_FRAMES // 2), T_FRAMES // 2 + 1)]
-    return Samples('lr', nums, n, dtype), Samples('ref', nums, n, dtype), [['%d.%d' % (b, x) for x in nums] for b in range(n)]
+    return Samples('lr', nums, n, dtype, yuv), Samples('ref', nums, n, dtype, yuv), [['%d.%d' % (b, x) for x in nums] for b in range(n)]
 
 
 def final_state(engines):
@@ -422,40 +445,42 @@ def _ready(kind):
 
 
 def sc_forward_seq(overlap=True, ids=False, want_log=False, want_vis=False, gradio=False, ready=None, reset=None, calls=2, keep=None,
-                   pipelined=False):
-    e = make_engine(overlap=overlap, gradio=gradio, reset=reset, pipelined=pipelined)
+                   pipelined=False, dtype=torch.float32, yuv=None, cache=True, ref_layouts=None):
+    """dtype: one for every call, or one per call; ref_layouts: per call, what ops.u8_layout says of the call's refs."""
+    e = make_engine(overlap=overlap, gradio=gradio, reset=reset, pipelined=pipelined, input_yuv=yuv)
+    e.cache = cache
     for f in range(calls):
-        lrs, refs, fid = window(f)
+        lrs, refs, fid = window(f, dtype[f] if isinstance(dtype, tuple) else dtype, yuv=yuv, ref_layout=ref_layouts[f] if ref_layouts else 0)
         call('forward %d' % f, keep is None or f in keep)
         e.forward(lrs, refs, f == 0, want_vis=want_vis, frame_ids=fid if ids else None, want_log=want_log, input_ready=_ready(ready))
     return [e]
 
 
 def sc_forward_pipe(C=24, layout=None, gradio=False, ready=None, reset=2, want_vis=False, depth=3, prebuilt=True, calls=3, keep=(1, 2),
-                    dtype=torch.float32):
-    e = make_engine(C=C, layout=layout, pipelined=True, gradio=gradio, reset=reset)
+                    dtype=torch.float32, yuv=None):
+    e = make_engine(C=C, layout=layout, pipelined=True, gradio=gradio, reset=reset, input_yuv=yuv)
     e.pipe_depth = depth
     if prebuilt:
         name_pipe(e)
     for f in range(calls):                                    # first frame, steady, a reset_branch roll-over (reset = 2), steady
-        lrs, refs, fid = window(f, dtype)
+        lrs, refs, fid = window(f, dtype, yuv=yuv)
         call('forward %d' % f, f in keep)
         e.forward(lrs, refs, f == 0, want_vis=want_vis, frame_ids=fid, input_ready=_ready(ready))
     return [e]
 
 
 def sc_group(B=2, C=24, layout=None, first_inside=False, reset=None, want_vis=False, events=False, ready=None, pipelined=True, group=True,
-             gradio=False, prior_clip=False, groups=1, dtype=torch.float32):
-    e = make_engine(C=C, layout=layout, pipelined=pipelined, reset=reset, group=group, gradio=gradio)
+             gradio=False, prior_clip=False, groups=1, dtype=torch.float32, yuv=None):
+    e = make_engine(C=C, layout=layout, pipelined=pipelined, reset=reset, group=group, gradio=gradio, input_yuv=yuv)
     if pipelined:
         name_pipe(e)
     f0 = 0
     for f in range(2 if prior_clip else 0):                   # a clip before this one: the counter and the caches are not fresh
-        lrs, refs, fid = window(f)
+        lrs, refs, fid = window(f, yuv=yuv)
         call('prior clip: forward %d' % f, False)
         e.forward(lrs, refs, f == 0, frame_ids=fid)
     if not first_inside:
-        lrs, refs, fid = window(0, dtype)
+        lrs, refs, fid = window(0, dtype, yuv=yuv)
         call('forward 0', False)
         e.forward(lrs, refs, True, frame_ids=fid)
         f0 = 1
@@ -464,7 +489,7 @@ def sc_group(B=2, C=24, layout=None, first_inside=False, reset=None, want_vis=Fa
         if events:
             e.stream_events = []
         call('forward_group %d..%d' % (f0, f0 + B - 1))
-        e.forward_group([window(f, dtype) for f in range(f0, f0 + B)], is_first_frame=first_inside and g == 0, input_ready=_ready(ready),
+        e.forward_group([window(f, dtype, yuv=yuv) for f in range(f0, f0 + B)], is_first_frame=first_inside and g == 0, input_ready=_ready(ready),
                         want_vis=want_vis)
         if events:
             extra['stream_events.%d' % g] = [dict((k, v if k == 'n' else '%s@%s' % (v.name, v.stream)) for k, v in sorted(ev.items()))
@@ -473,22 +498,22 @@ def sc_group(B=2, C=24, layout=None, first_inside=False, reset=None, want_vis=Fa
     return [e], extra
 
 
-def sc_multi(n=2, C=24, dtype=torch.float32, ready=None, reset=None, layout=None, prebuilt=False, calls=2, keep=(1,)):
-    lead = make_engine(C=C, pipelined=True, reset=reset, layout=layout)
-    engines = [lead] + [make_engine(C=C, pipelined=True, reset=reset, layout=layout, weights=lead.W) for _ in range(n - 1)]
+def sc_multi(n=2, C=24, dtype=torch.float32, ready=None, reset=None, layout=None, prebuilt=False, calls=2, keep=(1,), yuv=None):
+    lead = make_engine(C=C, pipelined=True, reset=reset, layout=layout, input_yuv=yuv)
+    engines = [lead] + [make_engine(C=C, pipelined=True, reset=reset, layout=layout, weights=lead.W, input_yuv=yuv) for _ in range(n - 1)]
     if prebuilt:
         name_pipe(lead)
     for f in range(calls):                                    # the first call falls back through one forward() per sample
-        lrs, refs, fids = samples(f, n, dtype)
+        lrs, refs, fids = samples(f, n, dtype, yuv)
         call('forward_multi %d' % f, f in keep)
         type(lead).forward_multi(engines, lrs, refs, f == 0, fids, input_ready=_ready(ready))
     return engines
 
 
-def sc_phase(ids=True, hint=True, gradio=False, reset=None, want_vis=False):
-    e = make_engine(gradio=gradio, reset=reset)
+def sc_phase(ids=True, hint=True, gradio=False, reset=None, want_vis=False, yuv=None):
+    e = make_engine(gradio=gradio, reset=reset, input_yuv=yuv)
     for f in range(3):
-        lrs, refs, fid = window(f)
+        lrs, refs, fid = window(f, yuv=yuv)
         call('phase_a %d' % f)
         pa = e.phase_a(lrs, refs, fid if ids else None, first_hint=hint and f == 0)
         if f < 2:
@@ -502,12 +527,12 @@ def sc_phase(ids=True, hint=True, gradio=False, reset=None, want_vis=False):
     return [e]
 
 
-def sc_phase_group(B=3, streams=False, hints=True, group=True, C=24, groups=2, keep=None):
-    e = make_engine(C=C, group=group)
+def sc_phase_group(B=3, streams=False, hints=True, group=True, C=24, groups=2, keep=None, yuv=None):
+    e = make_engine(C=C, group=group, input_yuv=yuv)
     lane_a, lane_m, lane_b = Stream(name='A'), Stream(name='GM'), Stream(name='B1')
     f0 = 0
     for g in range(groups):
-        wins = [window(f) for f in range(f0, f0 + B)]
+        wins = [window(f, yuv=yuv) for f in range(f0, f0 + B)]
         on = keep is None or g in keep
         call('phase_a_group %d..%d' % (f0, f0 + B - 1), on)
         with OnStream(lane_a):
@@ -523,14 +548,15 @@ def sc_phase_group(B=3, streams=False, hints=True, group=True, C=24, groups=2, k
     return [e]
 
 
-def sc_context_ahead():
-    """A context prepared ahead of its window (prepare_context) is taken out of ctx_pinned by the id-keyed lookup."""
-    e = make_engine(pipelined=True)
+def sc_context_ahead(dtype=torch.float32, yuv=None):
+    """A context prepared ahead of its window (prepare_context) is taken out of ctx_pinned by the id-keyed lookup; the decode of its
+    8-bit / 4:2:0 frames runs at once (no call collects it)."""
+    e = make_engine(pipelined=True, input_yuv=yuv)
     name_pipe(e)
-    lrs, refs, fid = window(0)
+    lrs, refs, fid = window(0, dtype, yuv=yuv)
     call('forward 0', False)
     e.forward(lrs, refs, True, frame_ids=fid)
-    lrs, refs, fid = window(1)
+    lrs, refs, fid = window(1, dtype, yuv=yuv)
     call('prepare_context 2')
     e.prepare_context(lrs[2], refs[2], 2)
     call('forward 1')
@@ -588,6 +614,21 @@ def scenarios():
     sc['phase_a_group B=2 streams C=48'] = lambda: sc_phase_group(B=2, streams=True, C=48, keep=(1,))
     sc['phase_a_group B=2 streams no group schedule'] = lambda: sc_phase_group(B=2, streams=True, group=False, groups=1)
     sc['contexts prepared ahead'] = sc_context_ahead
+    # ---- the input kinds (float above): the content compare against the contexts' source copies, the decode of a call's new frames
+    #      in one launch, the repeated edge frame of the first window
+    sc['forward seq uint8'] = lambda: sc_forward_seq(calls=3, dtype=torch.uint8)
+    sc['forward seq yuv nv12'] = lambda: sc_forward_seq(calls=3, yuv='nv12', keep=(0, 1))
+    sc['forward seq float then uint8'] = lambda: sc_forward_seq(calls=3, dtype=(torch.float32, torch.uint8, torch.uint8), keep=(1,))
+    sc['forward seq uint8 ref layout changes'] = lambda: sc_forward_seq(calls=3, dtype=torch.uint8, ref_layouts=(0, 1, 1), keep=(1,))
+    sc['forward seq uint8 cache off'] = lambda: sc_forward_seq(dtype=torch.uint8, cache=False, keep=(0,))
+    sc['forward pipelined yuv nv12'] = lambda: sc_forward_pipe(yuv='nv12', calls=2, keep=(1,))
+    sc['forward_group yuv nv12 B=2'] = lambda: sc_group(B=2, yuv='nv12')
+    sc['forward_multi n=2 yuv p010'] = lambda: sc_multi(yuv='p010')
+    for ids in (1, 0):
+        sc['phase_a yuv ids=%d' % ids] = lambda ids=ids: sc_phase(ids=bool(ids), yuv='nv12')
+    sc['phase_a_group B=3 yuv'] = lambda: sc_phase_group(B=3, yuv='nv12', groups=1)
+    sc['contexts prepared ahead uint8'] = lambda: sc_context_ahead(dtype=torch.uint8)
+    sc['contexts prepared ahead yuv'] = lambda: sc_context_ahead(yuv='nv12')
     return sc
 
 

@@ -49,8 +49,19 @@ def test_recorded_traces_reach_every_call_form(golden):
     assert {'C', 'P', 'F', 'FP', 'M0', 'M1', 'M0M1', 'M0M1FP', 'A', 'GM', 'B1', 'S0'} <= streams
     for what in ('wait_event', 'wait_stream', '.record(', '.synchronize()', '| rs ', 'ctx(lr', 'in=#', 'enter ', 'exit ', 'pyramid', 'prepare_frame',
                  'resblocks backward_resblocks', 'prop_step', 'compute_up', 'conf_vis', 'ingest_u8', 'spynet', 'flow_resize', 'compare',
-                 'warp_planar', 'after_state', 'up_from_lr', 'heads=[head('):
+                 'warp_planar', 'after_state', 'up_from_lr', 'heads=[head(', 'compare bytes', 'C| yuv420_ingest nv12', 'P| yuv420_ingest nv12',
+                 'A| yuv420_ingest nv12', 'S1| yuv420_ingest p010'):
         assert any(what in ln for ln in lines), what
+    # the input kinds: a decode launch in every call form, and at once for a context prepared outside a call
+    for name, what in (('forward seq uint8', 'ingest_u8'), ('forward seq yuv nv12', 'yuv420_ingest'), ('forward pipelined yuv nv12', 'yuv420_ingest'),
+                       ('forward_group yuv nv12 B=2', 'yuv420_ingest'), ('forward_multi n=2 yuv p010', 'yuv420_ingest'),
+                       ('phase_a yuv ids=1', 'yuv420_ingest'), ('phase_a yuv ids=0', 'yuv420_ingest'), ('phase_a_group B=3 yuv', 'yuv420_ingest'),
+                       ('contexts prepared ahead uint8', 'ingest_u8'), ('contexts prepared ahead yuv', 'yuv420_ingest')):
+        assert any(what in ln for ln in golden[name]['trace']), (name, what)
+    # a window of another kind or another layout pair: nothing of the previous window is compared (6 = the window's own three frames)
+    for name in ('forward seq float then uint8', 'forward seq uint8 ref layout changes'):
+        tr = golden[name]['trace']
+        assert [ln for ln in tr[tr.index('# forward 1'):tr.index('#- forward 2')] if 'compare' in ln] == ['C| compare bytes 6']
 
 
 def test_stream_events_name_their_streams(golden):
