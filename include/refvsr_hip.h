@@ -652,6 +652,36 @@ int refvsr_yuv420_to_rgb(const void* const* src, float* const* dst, int nframes,
                          const double* coef, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Scene cuts: luma SAD of frame pairs (extension, no ABI bump: added symbols only).  Replaces nothing in the reference: its loader
+ * serves one folder per clip, replicates frames at the clip's edges (data_loader/datasets.py:222-234) and starts every clip with
+ * is_first = True, so it never meets a cut.  A video file has cuts; refvsr_amd/videorun.py (--scene_cut) runs every scene as the
+ * reference would run a clip, and finds the scenes from the sum of absolute luma differences of consecutive LR frames
+ * (refvsr_amd/scene.py turns the sums into the scene score).  The three entry points serve that detector alone.  The specification is
+ * the numpy model refvsr_amd/yuv.py:luma_sad; the kernel returns its integers.
+ *   Frames and formats as above (REFVSR_YUV_*).  Only the luma plane is read: the first h w samples of a frame in every format; a
+ *   P010 sample's code is sample >> 6, an I420P10 sample's is sample & 1023 (as refvsr_yuv420_to_rgb reads them).
+ * refvsr_scene_max_pairs: replaces nothing -- REFVSR_SCENE_MAX_PAIRS of the built library (a value, not a status).
+ * refvsr_luma_sad_workspace_bytes: host only; the workspace of a call with these arguments (any format), 0 for arguments the call
+ *   rejects.
+ * refvsr_luma_sad: sad[i] = sum over the h w luma codes of |Ya_i - Yb_i| for 1 <= npairs <= REFVSR_SCENE_MAX_PAIRS pairs of one h x w
+ *   (even, >= 2, h w <= 2^29), an exact 64-bit integer, in TWO launches on `stream` (partial sums per 16-byte-group chunk with plain
+ *   vector stores, 32-bit: a chunk holds 8 222 samples at most; one workgroup per pair adds them in 64 bits), no host
+ *   synchronisation, no floating point, no atomics:
+ *     a, b: HOST arrays of device pointers, one dense frame each at any multiple of its sample size (frames inside a [t, 3h/2, w]
+ *          window are 3 h w / 2 samples apart: phases that are not 16-byte aligned are the normal case); a[i] == b[i] is allowed
+ *          and gives 0;
+ *     workspace: device, 16-byte aligned, workspace_bytes >= refvsr_luma_sad_workspace_bytes(npairs, h, w);
+ *     sad: device, 8-byte aligned, npairs 64-bit words.
+ *   Every argument is checked before any device work: null tables, pair count, odd or non-positive h / w, unknown format, null
+ *   workspace or sad, their alignment, the workspace size, null entries, entries not aligned to their samples.
+ * ------------------------------------------------------------------------------------------ */
+#define REFVSR_SCENE_MAX_PAIRS 16
+int refvsr_scene_max_pairs(void);
+size_t refvsr_luma_sad_workspace_bytes(int npairs, int h, int w);
+int refvsr_luma_sad(const void* const* a, const void* const* b, int npairs, int h, int w, int yuv_fmt, void* workspace,
+                    size_t workspace_bytes, unsigned long long* sad, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Inter-frame alignment
  * ------------------------------------------------------------------------------------------ */
 /* models/utils.py:35-43 `warp`: linspace(-1,1) base grid + flow/((Win-1)/2), grid_sample(bilinear,

@@ -26,6 +26,7 @@ SCORE_MAX_RECTS = 8                         # REFVSR_SCORE_MAX_RECTS: rectangles
 COLORMAP_MAX_MAPS = 16                      # REFVSR_COLORMAP_MAX_MAPS: maps per refvsr_conf_colormap launch
 YUV420_MAX_FRAMES = 16                      # REFVSR_YUV420_MAX_FRAMES: result frames per refvsr_result_to_yuv420 launch
 YUV420_IN_MAX_FRAMES = 16                   # REFVSR_YUV420_IN_MAX_FRAMES: 4:2:0 input frames per refvsr_yuv420_to_rgb launch
+SCENE_MAX_PAIRS = 16                        # REFVSR_SCENE_MAX_PAIRS: frame pairs per refvsr_luma_sad call
 FINGERPRINT_CHUNK_WORDS = 4096              # REFVSR_FINGERPRINT_CHUNK_WORDS: words per chunk-table entry of refvsr_param_fingerprint
 RESBLOCK24_BLOB_BYTES = 43264
 RESBLOCK24_F16W_BLOB_BYTES = 28928          # the fp16 weight format (ABI 15)
@@ -181,6 +182,10 @@ SIGNATURES = {
     # Y'CbCr 4:2:0 input frames (added symbols, ABI 15 unchanged): src table, dst table, frames, h, w, format, chroma, coef9, stream
     'refvsr_yuv420_to_rgb': [_P, _P, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _P],
     'refvsr_yuv420_in_max_frames': [],           # returns REFVSR_YUV420_IN_MAX_FRAMES
+    # luma SAD of frame pairs for the scene cuts (added symbols, ABI 15 unchanged): a table, b table, pairs, h, w, yuv_fmt, workspace,
+    # its bytes, sad, stream
+    'refvsr_luma_sad': [_P, _P, _I, _I, _I, _I, _P, _Z, _P, _P],
+    'refvsr_scene_max_pairs': [],                # returns REFVSR_SCENE_MAX_PAIRS
 }
 # fp16 weight format (ABI 15): <name>_f16w twins with the signature of the function they are named after
 _F16W_TWINS = ('refvsr_resblock24_chain', 'refvsr_resblock24_chain_batch', 'refvsr_conv24', 'refvsr_conv24_batch', 'refvsr_conv32',
@@ -191,7 +196,8 @@ _SPECIAL = {'refvsr_abi_version': (C.c_int, []), 'refvsr_last_error': (C.c_char_
             'refvsr_score_regions_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I]),
             'refvsr_conf_colormap_workspace_bytes': (C.c_size_t, [_I, _I, _I]),
             'refvsr_param_fingerprint_workspace_bytes': (C.c_size_t, [_I]),
-            'refvsr_yuv420_bytes': (C.c_size_t, [_I, _I, _I])}
+            'refvsr_yuv420_bytes': (C.c_size_t, [_I, _I, _I]),
+            'refvsr_luma_sad_workspace_bytes': (C.c_size_t, [_I, _I, _I])}
 EXPORTS = tuple(sorted(list(SIGNATURES) + list(_SPECIAL)))
 
 _lib = None
@@ -220,7 +226,8 @@ def lib():
                                    (h.refvsr_score_max_frames, SCORE_MAX_FRAMES, 'REFVSR_SCORE_MAX_FRAMES'),
                                    (h.refvsr_score_max_rects, SCORE_MAX_RECTS, 'REFVSR_SCORE_MAX_RECTS'),
                                    (h.refvsr_yuv420_max_frames, YUV420_MAX_FRAMES, 'REFVSR_YUV420_MAX_FRAMES'),
-                                   (h.refvsr_yuv420_in_max_frames, YUV420_IN_MAX_FRAMES, 'REFVSR_YUV420_IN_MAX_FRAMES')):
+                                   (h.refvsr_yuv420_in_max_frames, YUV420_IN_MAX_FRAMES, 'REFVSR_YUV420_IN_MAX_FRAMES'),
+                                   (h.refvsr_scene_max_pairs, SCENE_MAX_PAIRS, 'REFVSR_SCENE_MAX_PAIRS')):
             if query() != const:
                 raise RuntimeError('refvsr_amd: %s mismatch (library %d, binding %d)' % (name, query(), const))
         _lib = h

@@ -981,6 +981,37 @@ def yuv420_to_frames(x, h, w, fmt, matrix='bt709', range='limited', chroma='bili
     return _frames_of(x, 2, torch.Tensor.is_contiguous, dt.itemsize, h, w, lambda pairs: yuv420_ingest(pairs, fmt, matrix, range, chroma))
 
 
+_SAD_WS = {}          # (device, stream handle, h, w) -> workspace of one full refvsr_luma_sad call
+
+
+def luma_sad(frames_a, frames_b, h, w, fmt):
+    """The sums of absolute luma differences of B pairs of 4:2:0 frames of one h x w, computed on the device (refvsr_luma_sad; the
+    integers of yuv.luma_sad): a torch.int64 [B] tensor on the current stream, no synchronisation.  frames_a, frames_b: a
+    [B, 3 h / 2, w] tensor or B tensors [3 h / 2, w] each, uint8 ('nv12' | 'i420') or uint16 ('p010' | 'i420p10'), dense frames at
+    any multiple of their sample size (views into a [t, 3 h / 2, w] window included); the same frame on both sides gives 0.  One call
+    (two launches) per REFVSR_SCENE_MAX_PAIRS pairs."""
+    from . import yuv
+    fa, fb = list(frames_a), list(frames_b)
+    if not fa or len(fa) != len(fb):
+        raise RuntimeError('luma_sad: as many frames on both sides, at least one (got %d and %d)' % (len(fa), len(fb)))
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise RuntimeError('luma_sad: 4:2:0 needs even h and w (got %d x %d)' % (h, w))
+    dev = fa[0].device
+    for f in fa + fb:
+        if not (f.is_cuda and f.device == dev and yuv_window_kind(f, fmt) is not None and tuple(f.shape) == yuv.frame_shape(h, w)):
+            raise RuntimeError('luma_sad: dense cuda %s frames [%d, %d] of one GPU (got %s %s %s)'
+                               % (fmt, 3 * h // 2, w, f.device.type, f.dtype, tuple(f.shape)))
+    st = _stream()
+    ws = _score_workspace(_SAD_WS, dev, st, h, w, lambda: hip.lib().refvsr_luma_sad_workspace_bytes(hip.SCENE_MAX_PAIRS, h, w), 'luma_sad', 4,
+                          'frames must hold at most 2^29 pixels')
+    sad = torch.empty(len(fa), dtype=torch.int64, device=dev)
+    for s0 in _irange(0, len(fa), hip.SCENE_MAX_PAIRS):
+        n = min(hip.SCENE_MAX_PAIRS, len(fa) - s0)
+        hip.check(hip.lib().refvsr_luma_sad(_parr(fa[s0:s0 + n]), _parr(fb[s0:s0 + n]), n, h, w, yuv.FORMAT_IDS[fmt], _ptr(ws), ws.numel() * 4,
+                                            C.c_void_p(sad.data_ptr() + 8 * s0), st), 'luma_sad')
+    return sad
+
+
 _COLORMAP_WS = {}     # (device, stream handle, h, w) -> workspace of one full refvsr_conf_colormap launch
 
 

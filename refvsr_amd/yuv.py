@@ -28,6 +28,9 @@ The way in (yuv420_to_rgb; extension -- the reference's loader reads PNGs, data_
   output  r, g, b clamped to [0, 1] (decoded video is routinely out of gamut; the network's contract is frames in [0, 1]), then
           rounded once to float32
 with (oy, iy = 1 / sy, oc, ic = 1 / sc, cr_r = 2 (1 - kr), cb_b = 2 (1 - kb), kr, kb, ikg = 1 / kg) of decode_coefficients.
+
+luma_sad: the sum of absolute differences of two frames' luma codes (the same codes), the model of refvsr_luma_sad (csrc/scene.hip)
+behind videorun's scene-cut detector (scene.py).
 """
 import os
 
@@ -213,6 +216,13 @@ def codes(buf, h, w, fmt):
         raise TypeError('%s frames are %s (got %s)' % (fmt, np.dtype(dtype_of(fmt)).name, buf.dtype))
     # (p010: the code in the high bits, sample >> 6; the others: the low d bits -- all eight of a byte, sample & 1023 of i420p10)
     return tuple((p.astype(np.int64) >> shift) & (2 ** d - 1) for p in planes(buf, h, w, fmt))
+
+
+def luma_sad(a, b, h, w, fmt):
+    """The model of refvsr_luma_sad (csrc/scene.hip): the sum of absolute differences of the luma codes of two frames' buffers, a
+    Python int (integer arithmetic on codes(): a p010 sample's low six bits and an i420p10 sample's bits above bit 9 do not count)."""
+    ya, yb = codes(a, h, w, fmt)[0], codes(b, h, w, fmt)[0]
+    return int(np.abs(ya - yb).sum(dtype=np.int64))
 
 
 def chroma_taps(c, chroma='bilinear'):
