@@ -652,6 +652,57 @@ int refvsr_yuv420_to_rgb(const void* const* src, float* const* dst, int nframes,
                          const double* coef, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Y'CbCr 4:2:2 and 4:4:4 frames, and left-sited chroma, out and in (extension, no ABI bump: added symbols only).  The two 4:2:0
+ * sections above know one chroma convention, 4:2:0 sited in the centre of its 2 x 2 block (Y4M's C420jpeg).  Video decoders and most
+ * files site chroma on the even luma columns instead (MPEG-2 siting, C420mpeg2: every NV12 / P010 buffer of a hardware decoder), and
+ * results are kept as 4:2:2 or 4:4:4.  The three entry points are the 4:2:0 ones with a sampling and a siting; they replace the same
+ * things in the reference: refvsr_result_to_yuv the consumer's host-side RGB -> Y'CbCr conversion behind the image writer
+ * (evaluation/eval_qual_quan.py:117-119), refvsr_yuv_to_rgb the consumer's Y'CbCr -> RGB conversion in front of the loader's frames
+ * (data_loader/utils.py:12-41).  The specification is the numpy model refvsr_amd/yuv.py (rgb_to_yuv, yuv_to_rgb); the kernels return
+ * its bits.
+ *   yuv_fmt: REFVSR_YUV_* as above -- depth, semi-planarity and shift.  The semi-planar ids (NV12, P010) exist for 4:2:0 only.
+ *   sampling: a frame is ONE dense buffer, Y [h][w], Cb [h/cv][w/ch], Cr [h/cv][w/ch]; h, w even for every sampling (4:4:4 would
+ *   not need it; the engine's frame checks and refvsr_luma_sad do):
+ *     REFVSR_YUV_SAMPLING_420   (cv, ch) = (2, 2)   3 h w / 2 samples
+ *     REFVSR_YUV_SAMPLING_422   (cv, ch) = (1, 2)   2 h w samples
+ *     REFVSR_YUV_SAMPLING_444   (cv, ch) = (1, 1)   3 h w samples
+ *   siting: REFVSR_YUV_SITING_CENTRE (a chroma sample lies in the middle of its luma pair) | REFVSR_YUV_SITING_LEFT (on the pair's
+ *   even column); vertically a 4:2:0 sample lies between its two rows in both.  Checked, then ignored, for 4:4:4.
+ *   The way out, e = ecb | ecr of the 4:2:0 section, unquantised, float64, every operation rounded on its own, l = max(2j - 1, 0):
+ *     4:4:4          m = e[y][x]
+ *     4:2:2 centre   m = (e[y][2j] + e[y][2j+1]) 0.5
+ *     4:2:2 left     m = ((e[y][l] + e[y][2j+1]) + (e[y][2j] + e[y][2j])) 0.25
+ *     4:2:0 left     v[x] = e[2i][x] + e[2i+1][x];  m = ((v[l] + v[2j+1]) + (v[2j] + v[2j])) 0.125
+ *     4:2:0 centre   as refvsr_result_to_yuv420
+ *   then C = rint(oc + sc m) and the clamp, as there.
+ *   The way in, the integer tap sum 16 m at luma pixel (y, x) (below 2^15, exact in any order); everything behind it as
+ *   refvsr_yuv420_to_rgb; cx = x >> 1, cx' = clamp(cx + (x & 1 ? 1 : -1)), cxr = min(cx + 1, w/2 - 1), cy and cy' as there:
+ *     4:4:4                  16 C[y][x]
+ *     4:2:2 centre           12 C[y][cx] + 4 C[y][cx']
+ *     4:2:2 left    even x   16 C[y][cx]                     odd x   8 C[y][cx] + 8 C[y][cxr]
+ *     4:2:0 left    even x   12 C[cy][cx] + 4 C[cy'][cx]     odd x   6 C[cy][cx] + 2 C[cy'][cx] + 6 C[cy][cxr] + 2 C[cy'][cxr]
+ *     4:2:0 centre           as refvsr_yuv420_to_rgb
+ *     REFVSR_YUV_CHROMA_NEAREST, every sampling: 16 x the pixel's own sample
+ * refvsr_yuv_frame_bytes: replaces the consumer's own buffer arithmetic -- the bytes of one frame; 0 for odd or non-positive h, w,
+ *   an unknown format or sampling, or a semi-planar format with a sampling other than 4:2:0 (host only).  With
+ *   REFVSR_YUV_SAMPLING_420 it is refvsr_yuv420_bytes.
+ * refvsr_result_to_yuv: refvsr_result_to_yuv420 with a sampling and a siting -- its arguments, limits (REFVSR_YUV420_MAX_FRAMES
+ *   frames, ONE launch) and checks, dst of refvsr_yuv_frame_bytes(h, w, yuv_fmt, sampling) bytes each.  With 4:2:0 / centre it IS
+ *   refvsr_result_to_yuv420 (the same kernels, the same bits).
+ * refvsr_yuv_to_rgb: refvsr_yuv420_to_rgb with a sampling and a siting -- its arguments, limits (REFVSR_YUV420_IN_MAX_FRAMES frames,
+ *   ONE launch) and checks.  With 4:2:0 / centre it IS refvsr_yuv420_to_rgb.
+ *   Both check every argument before any device work, and refuse an unknown sampling or siting and a semi-planar format with a
+ *   sampling other than 4:2:0.
+ * ------------------------------------------------------------------------------------------ */
+enum { REFVSR_YUV_SAMPLING_420 = 0, REFVSR_YUV_SAMPLING_422 = 1, REFVSR_YUV_SAMPLING_444 = 2 };
+enum { REFVSR_YUV_SITING_CENTRE = 0, REFVSR_YUV_SITING_LEFT = 1 };
+size_t refvsr_yuv_frame_bytes(int h, int w, int yuv_fmt, int sampling);
+int refvsr_result_to_yuv(const void* const* src, int src_fmt, void* const* dst, int nframes, int h, int w, int yuv_fmt, int sampling,
+                         int siting, const double* coef9, void* stream);
+int refvsr_yuv_to_rgb(const void* const* src, float* const* dst, int nframes, int h, int w, int yuv_fmt, int sampling, int siting,
+                      int chroma, const double* coef9, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Scene cuts: luma SAD of frame pairs (extension, no ABI bump: added symbols only).  Replaces nothing in the reference: its loader
  * serves one folder per clip, replicates frames at the clip's edges (data_loader/datasets.py:222-234) and starts every clip with
  * is_first = True, so it never meets a cut.  A video file has cuts; refvsr_amd/videorun.py (--scene_cut) runs every scene as the

@@ -95,10 +95,12 @@ def base_config(project='', mode='', config_='', data='', LRS='', batch_size=8):
     c.result_yuv = None         # 'nv12' | 'i420' | 'p010' | 'i420p10': the calls also return 'yuv', the results as Y'CbCr 4:2:0 frames (extension; what video consumers take)
     c.yuv_matrix = 'bt709'      # 'bt601': luma coefficients of 'yuv'
     c.yuv_range = 'limited'     # 'full': code range of 'yuv'
+    c.yuv_siting = 'centre'     # 'left': chroma of 'yuv' on the even luma columns (MPEG-2 siting); result_yuv also takes 'i422' | 'i444' | 'i422p10' | 'i444p10' ([.., 2h, w] / [.., 3h, w] frames)
     c.input_yuv = None          # 'nv12' | 'i420' | 'p010' | 'i420p10': the windows are Y'CbCr 4:2:0 frames [.., t, 3h/2, w], decoded on the device (extension; what video decoders deliver)
     c.input_yuv_matrix = 'bt709'    # 'bt601': luma coefficients of the input frames
     c.input_yuv_range = 'limited'   # 'full': code range of the input frames
     c.input_yuv_chroma = 'bilinear' # 'nearest': chroma up-sampling of the input frames (bilinear: centre-sited, the inverse siting of 'yuv')
+    c.input_yuv_siting = 'centre'   # 'left': the input frames' chroma lies on the even luma columns -- every NV12 / P010 buffer of a hardware decoder; input_yuv also takes 'i422' | 'i444' | 'i422p10' | 'i444p10'
     c.weight_precision = 'hi_lo'  # 'fp16' | 'amp': plain fp16 conv weights, the reference's AMP arithmetic (resolve_weight_precision)
     c.weight_check = 'auto'     # 'sync' | 'off': when the packed weights are checked against the parameters' device fingerprint (fingerprint.weight_check_policy)
     return c

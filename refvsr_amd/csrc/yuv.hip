@@ -238,3 +238,261 @@ extern "C" int refvsr_result_to_yuv420(const void* const* src, int src_fmt, void
     RV_LAUNCH_CHECK();
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// 4:2:2, 4:4:4 and left-sited 4:2:0 (refvsr_result_to_yuv; 4:2:0 / centre stays the kernel above).  Extension, as the file: the same
+// host-side conversion behind evaluation/eval_qual_quan.py:117-119, for the samplings and the siting results are kept in.  The bits
+// of refvsr_amd/yuv.py:rgb_to_yuv.
+//
+// The shape of the kernel above, per sampling: a thread owns NPX pixels of ROWS source rows (two for 4:2:0, one for 4:2:2 / 4:4:4);
+// loads and stores decide about vectors in the same way (each row's load for itself, the group's stores together).  Left siting takes
+// the odd column LEFT of a chroma pair: m = ((v[l] + v[2j+1]) + (v[2j] + v[2j])) scale, l = max(2j - 1, 0), v = e (4:2:2) or the sum
+// of the pair's two rows (4:2:0).  Inside a group that column is the pair before; for the group's first pair it is the pixel in front
+// of the group, x0 - 1 of the same rows -- another thread's, or another workgroup's, pixel -- which the thread loads for itself
+// (three samples per row, element by element, from the cache line its neighbour reads) and converts again.  The first group of a row
+// has no such pixel: l = 0, the pair's own even column.
+template <typename T, bool HWC, int FMT, int SAMP, bool LEFT>
+__global__ void __launch_bounds__(256) yuv_chroma_kernel(YuvArgs a) {
+    constexpr int NPX = YuvSrc<T>::NPX;
+    constexpr bool D10 = FMT == REFVSR_YUV_P010 || FMT == REFVSR_YUV_I420P10;
+    constexpr bool SEMI = FMT == REFVSR_YUV_NV12 || FMT == REFVSR_YUV_P010;
+    constexpr bool C444 = SAMP == REFVSR_YUV_SAMPLING_444, V2 = SAMP == REFVSR_YUV_SAMPLING_420;
+    static_assert(!SEMI || V2, "semi-planar frames are 4:2:0");
+    static_assert(!(C444 && LEFT), "4:4:4 has no siting");
+    static_assert(!V2 || LEFT, "4:2:0 / centre is yuv420_kernel");
+    constexpr int SHIFT = FMT == REFVSR_YUV_P010 ? 6 : 0;
+    constexpr int ROWS = V2 ? 2 : 1;
+    constexpr int NC = C444 ? NPX : NPX / 2;                         // chroma samples of the group per plane
+    using S = typename std::conditional<D10, uint16_t, uint8_t>::type;
+    constexpr int SRC_BYTES = NPX * (int)sizeof(T);
+    constexpr int ROW_BYTES = NPX * (int)sizeof(S);                  // a Y row piece, and the interleaved chroma of the group
+    constexpr int PLANE_BYTES = NC * (int)sizeof(S);                 // a Cb or Cr piece of the planar formats
+    constexpr uintptr_t ROW_MASK = (ROW_BYTES < 16 ? ROW_BYTES : 16) - 1, PLANE_MASK = (PLANE_BYTES < 16 ? PLANE_BYTES : 16) - 1;
+    constexpr double SCALE = V2 ? 0.125 : 0.25;                      // of the left-sited mean
+    constexpr bool U8 = std::is_same<T, unsigned char>::value;
+    __shared__ double tbl[U8 ? 256 : 1];
+    if constexpr (U8) {
+        for (int i = threadIdx.x; i < 256; i += blockDim.x) tbl[i] = (double)i / 255.0;
+        __syncthreads();
+    }
+    const T* __restrict__ src = reinterpret_cast<const T*>(a.src[blockIdx.y]);
+    S* __restrict__ dst = reinterpret_cast<S*>(a.dst[blockIdx.y]);
+    const int h = a.h, w = a.w, w2 = w >> 1;
+    const long hw = (long)h * w;
+    const long cplane = C444 ? hw : V2 ? hw >> 2 : hw >> 1;          // samples of a chroma plane
+    const double kr = a.k[0], kg = a.k[1], kb = a.k[2], icb = a.k[3], icr = a.k[4], oy = a.k[5], sy = a.k[6], oc = a.k[7], sc = a.k[8];
+    const double maxc = D10 ? 1023.0 : 255.0;
+    const int gpr = (w + NPX - 1) / NPX;                             // groups per row (4:2:0: per row pair)
+    const long items = (long)(h / ROWS) * gpr;
+    for (long k = blockIdx.x * (long)blockDim.x + threadIdx.x; k < items; k += (long)gridDim.x * blockDim.x) {
+        const int by = (int)(k / gpr);
+        const int x0 = (int)(k - (long)by * gpr) * NPX;
+        const int n = w - x0 < NPX ? w - x0 : NPX;                   // pixels of the group per row (even)
+        const long p0 = (long)(ROWS * by) * w + x0;                  // the group's first pixel; a second row's is p0 + w
+        S* const y0 = dst + p0;
+        S* const c0 = dst + hw + (SEMI || C444 ? (long)by * w + x0 : (long)by * w2 + (x0 >> 1));       // interleaved CbCr, or Cb
+        S* const c1 = c0 + cplane;                                                                    // Cr of the planar formats
+
+        const bool full = n == NPX;
+        alignas(16) T v[ROWS][3][NPX];
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            const long pr = p0 + (long)r * w;
+            uintptr_t mis;
+            if constexpr (HWC) mis = (uintptr_t)(src + 3 * pr) & 15;
+            else mis = ((uintptr_t)(src + pr) | (uintptr_t)(src + hw + pr) | (uintptr_t)(src + 2 * hw + pr)) & 15;
+            if (full && mis == 0) {
+                if constexpr (HWC) {
+                    alignas(16) T t[3 * NPX];
+                    yuv_load<3 * SRC_BYTES>(src + 3 * pr, t);
+#pragma unroll
+                    for (int i = 0; i < NPX; ++i) { v[r][0][i] = t[3 * i]; v[r][1][i] = t[3 * i + 1]; v[r][2][i] = t[3 * i + 2]; }
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) yuv_load<SRC_BYTES>(src + c * hw + pr, v[r][c]);
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+#pragma unroll
+                    for (int i = 0; i < NPX; ++i) v[r][c][i] = i < n ? (HWC ? src[3 * (pr + i) + c] : src[c * hw + pr + i]) : (T)0;
+            }
+        }
+
+        // left siting: v[x0 - 1], the odd column in front of the group (x0 >= NPX here: the pixel exists, in the group's own rows)
+        double lb = 0.0, lr = 0.0;
+        if constexpr (LEFT) {
+            if (x0 > 0) {
+#pragma unroll
+                for (int r = 0; r < ROWS; ++r) {
+                    const long q = p0 + (long)r * w - 1;
+                    const double R = yuv_value(HWC ? src[3 * q] : src[q], tbl), G = yuv_value(HWC ? src[3 * q + 1] : src[hw + q], tbl),
+                                 B = yuv_value(HWC ? src[3 * q + 2] : src[2 * hw + q], tbl);
+                    const double ey = (kr * R + kg * G) + kb * B;
+                    const double eb = (B - ey) * icb, er = (R - ey) * icr;
+                    lb = r == 0 ? eb : lb + eb;
+                    lr = r == 0 ? er : lr + er;
+                }
+            }
+        }
+
+        alignas(16) S yy[ROWS][NPX], cc[2 * NC];                     // cc: Cb Cr pairs (semi-planar), or [Cb piece | Cr piece]
+#pragma unroll
+        for (int j = 0; j < NPX / 2; ++j) {
+            double vb[2], vr[2];                                     // v of the pair's even and odd column
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+#pragma unroll
+                for (int d = 0; d < 2; ++d) {
+                    const int i = 2 * j + d;
+                    const double R = yuv_value(v[r][0][i], tbl), G = yuv_value(v[r][1][i], tbl), B = yuv_value(v[r][2][i], tbl);
+                    const double ey = (kr * R + kg * G) + kb * B;
+                    yy[r][i] = yuv_code<S, SHIFT>(oy + sy * ey, maxc);
+                    const double eb = (B - ey) * icb, er = (R - ey) * icr;
+                    vb[d] = r == 0 ? eb : vb[d] + eb;                // 4:2:0: e[2i][x] + e[2i+1][x]
+                    vr[d] = r == 0 ? er : vr[d] + er;
+                }
+            }
+            if constexpr (C444) {
+#pragma unroll
+                for (int d = 0; d < 2; ++d) {
+                    cc[2 * j + d] = yuv_code<S, SHIFT>(oc + sc * vb[d], maxc);
+                    cc[NC + 2 * j + d] = yuv_code<S, SHIFT>(oc + sc * vr[d], maxc);
+                }
+            } else {
+                double mb, mr;
+                if constexpr (LEFT) {
+                    if (j == 0 && x0 == 0) { lb = vb[0]; lr = vr[0]; }          // l = max(2j - 1, 0) = 0
+                    mb = ((lb + vb[1]) + (vb[0] + vb[0])) * SCALE;
+                    mr = ((lr + vr[1]) + (vr[0] + vr[0])) * SCALE;
+                    lb = vb[1];
+                    lr = vr[1];
+                } else {                                             // 4:2:2 centre
+                    mb = (vb[0] + vb[1]) * 0.5;
+                    mr = (vr[0] + vr[1]) * 0.5;
+                }
+                const S cb = yuv_code<S, SHIFT>(oc + sc * mb, maxc), cr = yuv_code<S, SHIFT>(oc + sc * mr, maxc);
+                if constexpr (SEMI) { cc[2 * j] = cb; cc[2 * j + 1] = cr; }
+                else { cc[j] = cb; cc[NC + j] = cr; }
+            }
+        }
+
+        uintptr_t smis = ((uintptr_t)y0 | (uintptr_t)(y0 + (ROWS - 1) * w)) & ROW_MASK;
+        smis |= SEMI ? (uintptr_t)c0 & ROW_MASK : ((uintptr_t)c0 | (uintptr_t)c1) & PLANE_MASK;
+        if (full && smis == 0) {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) yuv_store<ROW_BYTES>(y0 + r * w, yy[r]);
+            if constexpr (SEMI) {
+                yuv_store<ROW_BYTES>(c0, cc);
+            } else {
+                yuv_store<PLANE_BYTES>(c0, cc);
+                yuv_store<PLANE_BYTES>(c1, cc + NC);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+                for (int i = 0; i < NPX; ++i)
+                    if (i < n) y0[r * w + i] = yy[r][i];
+            if constexpr (C444) {
+#pragma unroll
+                for (int i = 0; i < NPX; ++i)
+                    if (i < n) { c0[i] = cc[i]; c1[i] = cc[NC + i]; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < NPX / 2; ++j)
+                    if (2 * j < n) {
+                        if constexpr (SEMI) { c0[2 * j] = cc[2 * j]; c0[2 * j + 1] = cc[2 * j + 1]; }
+                        else { c0[j] = cc[j]; c1[j] = cc[NC + j]; }
+                    }
+            }
+        }
+    }
+}
+
+static inline bool yuv_semi(int f) { return f == REFVSR_YUV_NV12 || f == REFVSR_YUV_P010; }
+static inline bool yuv_sampling_ok(int s) { return s >= REFVSR_YUV_SAMPLING_420 && s <= REFVSR_YUV_SAMPLING_444; }
+
+extern "C" size_t refvsr_yuv_frame_bytes(int h, int w, int yuv_fmt, int sampling) {
+    if (h <= 0 || w <= 0 || h % 2 || w % 2 || !yuv_fmt_ok(yuv_fmt) || !yuv_sampling_ok(sampling)) return 0;
+    if (sampling != REFVSR_YUV_SAMPLING_420 && yuv_semi(yuv_fmt)) return 0;
+    const size_t hw = (size_t)h * w;
+    return (sampling == REFVSR_YUV_SAMPLING_420 ? hw / 2 * 3 : sampling == REFVSR_YUV_SAMPLING_422 ? hw * 2 : hw * 3) * yuv_sample_bytes(yuv_fmt);
+}
+
+template <typename T, bool HWC>
+static void yuv_chroma_launch(int yuv_fmt, int sampling, bool left, dim3 grid, hipStream_t st, const YuvArgs& a) {
+#define YUV_CHROMA_GO(F, S, L) hipLaunchKernelGGL((yuv_chroma_kernel<T, HWC, F, S, L>), grid, dim3(256), 0, st, a)
+    const bool p10 = yuv_fmt == REFVSR_YUV_I420P10;
+    if (sampling == REFVSR_YUV_SAMPLING_420) {                       // left (centre is refvsr_result_to_yuv420)
+        switch (yuv_fmt) {
+            case REFVSR_YUV_NV12: YUV_CHROMA_GO(REFVSR_YUV_NV12, REFVSR_YUV_SAMPLING_420, true); break;
+            case REFVSR_YUV_I420: YUV_CHROMA_GO(REFVSR_YUV_I420, REFVSR_YUV_SAMPLING_420, true); break;
+            case REFVSR_YUV_P010: YUV_CHROMA_GO(REFVSR_YUV_P010, REFVSR_YUV_SAMPLING_420, true); break;
+            default: YUV_CHROMA_GO(REFVSR_YUV_I420P10, REFVSR_YUV_SAMPLING_420, true); break;
+        }
+    } else if (sampling == REFVSR_YUV_SAMPLING_422) {
+        if (left && p10) YUV_CHROMA_GO(REFVSR_YUV_I420P10, REFVSR_YUV_SAMPLING_422, true);
+        else if (left) YUV_CHROMA_GO(REFVSR_YUV_I420, REFVSR_YUV_SAMPLING_422, true);
+        else if (p10) YUV_CHROMA_GO(REFVSR_YUV_I420P10, REFVSR_YUV_SAMPLING_422, false);
+        else YUV_CHROMA_GO(REFVSR_YUV_I420, REFVSR_YUV_SAMPLING_422, false);
+    } else {
+        if (p10) YUV_CHROMA_GO(REFVSR_YUV_I420P10, REFVSR_YUV_SAMPLING_444, false);
+        else YUV_CHROMA_GO(REFVSR_YUV_I420, REFVSR_YUV_SAMPLING_444, false);
+    }
+#undef YUV_CHROMA_GO
+}
+
+extern "C" int refvsr_result_to_yuv(const void* const* src, int src_fmt, void* const* dst, int nframes, int h, int w, int yuv_fmt,
+                                    int sampling, int siting, const double* coef9, void* stream) {
+    RV_CHECK(yuv_fmt_ok(yuv_fmt), "result_to_yuv: unknown yuv format %d", yuv_fmt);
+    RV_CHECK(yuv_sampling_ok(sampling), "result_to_yuv: sampling must be REFVSR_YUV_SAMPLING_420 | _422 | _444 (got %d)", sampling);
+    RV_CHECK(siting == REFVSR_YUV_SITING_CENTRE || siting == REFVSR_YUV_SITING_LEFT,
+             "result_to_yuv: siting must be REFVSR_YUV_SITING_CENTRE | REFVSR_YUV_SITING_LEFT (got %d)", siting);
+    RV_CHECK(sampling == REFVSR_YUV_SAMPLING_420 || !yuv_semi(yuv_fmt),
+             "result_to_yuv: semi-planar frames (NV12, P010) are 4:2:0 only (format %d, sampling %d)", yuv_fmt, sampling);
+    if (sampling == REFVSR_YUV_SAMPLING_420 && siting == REFVSR_YUV_SITING_CENTRE)
+        return refvsr_result_to_yuv420(src, src_fmt, dst, nframes, h, w, yuv_fmt, coef9, stream);
+    RV_CHECK(src && dst, "result_to_yuv: null frame table");
+    RV_CHECK(coef9, "result_to_yuv: null coefficients");
+    RV_CHECK(nframes >= 1 && nframes <= REFVSR_YUV420_MAX_FRAMES, "result_to_yuv: 1..%d frames per launch", REFVSR_YUV420_MAX_FRAMES);
+    RV_CHECK(rv_result_fmt_ok(src_fmt), "result_to_yuv: unknown result format %d", src_fmt);
+    RV_CHECK(h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0, "result_to_yuv: h, w must be even and positive (got %d x %d)", h, w);
+    const int f = src_fmt & REFVSR_RESULT_FMT_MASK;
+    const size_t es = f == REFVSR_RESULT_F32 ? 4 : f == REFVSR_RESULT_F16 ? 2 : 1;
+    RV_CHECK((long long)h * w * 3 * (long long)es < (1ll << 31), "result_to_yuv: frame too large for 32-bit offsets");
+    const size_t sbytes = (size_t)h * w * 3 * es, dbytes = refvsr_yuv_frame_bytes(h, w, yuv_fmt, sampling);
+    YuvArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < nframes; ++i) {
+        RV_CHECK(src[i] && dst[i], "result_to_yuv: null pointer (frame %d)", i);
+        RV_CHECK(((uintptr_t)src[i] & (es - 1)) == 0 && ((uintptr_t)dst[i] & (yuv_sample_bytes(yuv_fmt) - 1)) == 0,
+                 "result_to_yuv: source and destination must be aligned to their samples (frame %d)", i);
+        a.src[i] = src[i];
+        a.dst[i] = dst[i];
+    }
+    for (int i = 0; i < nframes; ++i) {
+        const uintptr_t d0 = (uintptr_t)dst[i];
+        for (int j = 0; j < nframes; ++j) {
+            const uintptr_t s0 = (uintptr_t)src[j], d1 = (uintptr_t)dst[j];
+            RV_CHECK(d0 + dbytes <= s0 || s0 + sbytes <= d0, "result_to_yuv: destination %d overlaps source %d", i, j);
+            RV_CHECK(i == j || d0 + dbytes <= d1 || d1 + dbytes <= d0, "result_to_yuv: destinations %d and %d overlap", i, j);
+        }
+    }
+    a.h = h;
+    a.w = w;
+    for (int i = 0; i < 9; ++i) a.k[i] = coef9[i];
+    hipStream_t st = (hipStream_t)stream;
+    const int npx = f == REFVSR_RESULT_U8 ? YuvSrc<unsigned char>::NPX : YuvSrc<float>::NPX;
+    const long items = (long)(sampling == REFVSR_YUV_SAMPLING_420 ? h / 2 : h) * ((w + npx - 1) / npx);
+    const long want = (items + 255) / 256;
+    long cap = (long)rv_stream_cus(st) * 8 / nframes;                // eight workgroups per CU over all frames
+    if (cap < 32) cap = 32;
+    const dim3 grid((unsigned)(want < cap ? want : cap), (unsigned)nframes);
+    const bool hwc = (src_fmt & REFVSR_RESULT_HWC) != 0, left = siting == REFVSR_YUV_SITING_LEFT && sampling != REFVSR_YUV_SAMPLING_444;
+    if (f == REFVSR_RESULT_F32) hwc ? yuv_chroma_launch<float, true>(yuv_fmt, sampling, left, grid, st, a) : yuv_chroma_launch<float, false>(yuv_fmt, sampling, left, grid, st, a);
+    else if (f == REFVSR_RESULT_F16) hwc ? yuv_chroma_launch<f16, true>(yuv_fmt, sampling, left, grid, st, a) : yuv_chroma_launch<f16, false>(yuv_fmt, sampling, left, grid, st, a);
+    else hwc ? yuv_chroma_launch<unsigned char, true>(yuv_fmt, sampling, left, grid, st, a) : yuv_chroma_launch<unsigned char, false>(yuv_fmt, sampling, left, grid, st, a);
+    RV_LAUNCH_CHECK();
+    return 0;
+}

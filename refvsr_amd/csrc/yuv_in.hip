@@ -212,3 +212,212 @@ extern "C" int refvsr_yuv420_to_rgb(const void* const* src, float* const* dst, i
     RV_LAUNCH_CHECK();
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// 4:2:2, 4:4:4 and left-sited 4:2:0 (refvsr_yuv_to_rgb; 4:2:0 / centre stays the kernel above).  Extension, as the file: the same
+// host-side conversion in front of data_loader/utils.py:12-41, for the frames decoders and files deliver.  The bits of
+// refvsr_amd/yuv.py:yuv_to_rgb.
+//
+// The shape of the kernel above, per sampling: a thread owns 8 columns of ROWS luma rows (two for 4:2:0, one for 4:2:2 / 4:4:4), a
+// wave walks one row (pair), a workgroup 64 column groups (512 pixels) x 4 rows (pairs).  The integer tap sum 16 m factors into a
+// horizontal sum (of weight 4) and the vertical 3 : 1 of 4:2:0 (4:2:2: the row's own sum, x 4):
+//   centre       3 C[cx] + C[cx']
+//   left even x  4 C[cx]            odd x  2 C[cx] + 2 C[cxr],  cxr = min(cx + 1, w/2 - 1)
+// The block right of a group's last one is its neighbour's first (another thread's, or across a 512-pixel span another workgroup's):
+// each thread loads it for itself as the kernel above does, clamped at the row's end.  4:4:4 has no taps: 16 C[y][x].
+template <int FMT, int SAMP, bool LEFT>
+__global__ void __launch_bounds__(256) yuv_chroma_in_kernel(YuvInArgs a) {
+    constexpr bool D10 = FMT == REFVSR_YUV_P010 || FMT == REFVSR_YUV_I420P10;
+    constexpr bool SEMI = FMT == REFVSR_YUV_NV12 || FMT == REFVSR_YUV_P010;
+    constexpr bool C444 = SAMP == REFVSR_YUV_SAMPLING_444, V2 = SAMP == REFVSR_YUV_SAMPLING_420;
+    static_assert(!SEMI || V2, "semi-planar frames are 4:2:0");
+    static_assert(!(C444 && LEFT), "4:4:4 has no siting");
+    static_assert(!V2 || LEFT, "4:2:0 / centre is yuv420_in_kernel");
+    constexpr int ROWS = V2 ? 2 : 1;
+    constexpr int NQ = V2 ? 3 : 1, OWN = V2 ? 1 : 0;                           // chroma rows in registers, and the pixel's own among them
+    constexpr int NCOL = C444 ? 8 : 6;
+    using S = typename std::conditional<D10, uint16_t, uint8_t>::type;
+    const int h = a.h, w = a.w, hr = h / ROWS, w2 = w >> 1;
+    const int by = (int)(blockIdx.x / a.gxb) * 4 + (int)threadIdx.y;           // the row (4:2:0: the row pair): one per wave
+    const int g = (int)(blockIdx.x % a.gxb) * 64 + (int)threadIdx.x;
+    if (by >= hr || g >= a.gpr) return;
+    const S* __restrict__ src = reinterpret_cast<const S*>(a.src[blockIdx.y]);
+    float* __restrict__ dst = a.dst[blockIdx.y];
+    const size_t hw = (size_t)h * w;
+    const size_t cplane = C444 ? hw : V2 ? hw >> 2 : hw >> 1;                  // samples of a chroma plane
+    const int x0 = g * 8;
+    const int n = w - x0 < 8 ? w - x0 : 8;                                     // pixels of the group per row (even)
+    const int nb = n >> 1;                                                     // its chroma blocks
+    const int bx0 = x0 >> 1;
+    const int cxl = bx0 > 0 ? bx0 - 1 : 0, cxr = bx0 + nb < w2 ? bx0 + nb : w2 - 1;       // the clamped neighbour columns
+
+    alignas(16) S yv[ROWS][8];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) yin_load<S, 8>(src + (size_t)(ROWS * by + r) * w + x0, n, yv[r]);
+
+    // chroma codes.  4:4:4: the row's eight samples.  Otherwise [left neighbour | the group's four blocks | right neighbour] of the
+    // row (4:2:0: of the rows above (clamped), own, below (clamped))
+    int cb[NQ][NCOL], cr[NQ][NCOL];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int cy = !V2 ? by : q == 0 ? (by > 0 ? by - 1 : 0) : q == 1 ? by : (by + 1 < hr ? by + 1 : hr - 1);
+        if constexpr (C444) {
+            const S* rowb = src + hw + (size_t)cy * w;
+            alignas(16) S c0[8], c1[8];
+            yin_load<S, 8>(rowb + x0, n, c0);
+            yin_load<S, 8>(rowb + cplane + x0, n, c1);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { cb[q][i] = yin_code<FMT>(c0[i]); cr[q][i] = yin_code<FMT>(c1[i]); }
+        } else {
+            int rb, rr;
+            cb[q][5] = cr[q][5] = 0;                                           // (read by the unused pixels of a ragged group)
+            if constexpr (SEMI) {
+                const S* row = src + hw + (size_t)cy * w;
+                alignas(16) S c[8];
+                alignas(4) S l[2], e[2];
+                yin_load<S, 8>(row + x0, n, c);
+                yin_load<S, 2>(row + 2 * cxl, 2, l);
+                yin_load<S, 2>(row + 2 * cxr, 2, e);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { cb[q][1 + j] = yin_code<FMT>(c[2 * j]); cr[q][1 + j] = yin_code<FMT>(c[2 * j + 1]); }
+                cb[q][0] = yin_code<FMT>(l[0]);
+                cr[q][0] = yin_code<FMT>(l[1]);
+                rb = yin_code<FMT>(e[0]);
+                rr = yin_code<FMT>(e[1]);
+            } else {
+                const S* rowb = src + hw + (size_t)cy * w2;
+                const S* rowr = rowb + cplane;
+                alignas(8) S c0[4], c1[4];
+                yin_load<S, 4>(rowb + bx0, nb, c0);
+                yin_load<S, 4>(rowr + bx0, nb, c1);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { cb[q][1 + j] = yin_code<FMT>(c0[j]); cr[q][1 + j] = yin_code<FMT>(c1[j]); }
+                cb[q][0] = yin_code<FMT>(rowb[cxl]);
+                cr[q][0] = yin_code<FMT>(rowr[cxl]);
+                rb = yin_code<FMT>(rowb[cxr]);
+                rr = yin_code<FMT>(rowr[cxr]);
+            }
+            // the right neighbour stands behind the group's last block (a ragged group ends the row: its neighbour is that block again)
+#pragma unroll
+            for (int j = 1; j <= 4; ++j)
+                if (j == nb) { cb[q][1 + j] = rb; cr[q][1 + j] = rr; }
+        }
+    }
+
+    const double oy = a.k[0], iy = a.k[1], oc = a.k[2], ic = a.k[3], cr_r = a.k[4], cb_b = a.k[5], kr = a.k[6], kb = a.k[7], ikg = a.k[8];
+    const bool w4 = (w & 3) == 0;
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        const int f = !V2 ? 0 : r == 0 ? 0 : 2;                                // the far chroma row: above an even y, below an odd one
+        alignas(16) float o[3][8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            int mb, mr;
+            if constexpr (C444) {
+                mb = 16 * cb[0][i];
+                mr = 16 * cr[0][i];
+            } else {
+                const int c = 1 + (i >> 1);                                    // own block
+                if (a.nearest) {
+                    mb = 16 * cb[OWN][c];
+                    mr = 16 * cr[OWN][c];
+                } else {
+                    // the horizontal sum (of weight 4) of one chroma row
+                    auto hs = [&](const int* row) {
+                        if constexpr (LEFT) return (i & 1) ? 2 * row[c] + 2 * row[c + 1] : 4 * row[c];
+                        else return 3 * row[c] + row[(i & 1) ? c + 1 : c - 1];
+                    };
+                    if constexpr (V2) {
+                        mb = 3 * hs(cb[OWN]) + hs(cb[f]);
+                        mr = 3 * hs(cr[OWN]) + hs(cr[f]);
+                    } else {
+                        mb = 4 * hs(cb[OWN]);
+                        mr = 4 * hs(cr[OWN]);
+                    }
+                }
+            }
+            const double ey = ((double)yin_code<FMT>(yv[r][i]) - oy) * iy;
+            const double ecb = ((double)mb * 0.0625 - oc) * ic;
+            const double ecr = ((double)mr * 0.0625 - oc) * ic;
+            const double R = ey + cr_r * ecr;
+            const double B = ey + cb_b * ecb;
+            const double G = ((ey - kr * R) - kb * B) * ikg;
+            o[0][i] = (float)fmin(fmax(R, 0.0), 1.0);
+            o[1][i] = (float)fmin(fmax(G, 0.0), 1.0);
+            o[2][i] = (float)fmin(fmax(B, 0.0), 1.0);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float* p = dst + c * hw + (size_t)(ROWS * by + r) * w + x0;
+            if (n == 8 && w4) {
+                reinterpret_cast<float4*>(p)[0] = reinterpret_cast<const float4*>(o[c])[0];
+                reinterpret_cast<float4*>(p)[1] = reinterpret_cast<const float4*>(o[c])[1];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (j < nb) reinterpret_cast<float2*>(p)[j] = reinterpret_cast<const float2*>(o[c])[j];
+            }
+        }
+    }
+}
+
+extern "C" int refvsr_yuv_to_rgb(const void* const* src, float* const* dst, int nframes, int h, int w, int yuv_fmt, int sampling,
+                                 int siting, int chroma, const double* coef9, void* stream) {
+    RV_CHECK(yuv_fmt >= REFVSR_YUV_NV12 && yuv_fmt <= REFVSR_YUV_I420P10, "yuv_to_rgb: unknown yuv format %d", yuv_fmt);
+    RV_CHECK(sampling >= REFVSR_YUV_SAMPLING_420 && sampling <= REFVSR_YUV_SAMPLING_444,
+             "yuv_to_rgb: sampling must be REFVSR_YUV_SAMPLING_420 | _422 | _444 (got %d)", sampling);
+    RV_CHECK(siting == REFVSR_YUV_SITING_CENTRE || siting == REFVSR_YUV_SITING_LEFT,
+             "yuv_to_rgb: siting must be REFVSR_YUV_SITING_CENTRE | REFVSR_YUV_SITING_LEFT (got %d)", siting);
+    const bool semi = yuv_fmt == REFVSR_YUV_NV12 || yuv_fmt == REFVSR_YUV_P010, p10 = yuv_fmt == REFVSR_YUV_I420P10;
+    RV_CHECK(sampling == REFVSR_YUV_SAMPLING_420 || !semi,
+             "yuv_to_rgb: semi-planar frames (NV12, P010) are 4:2:0 only (format %d, sampling %d)", yuv_fmt, sampling);
+    if (sampling == REFVSR_YUV_SAMPLING_420 && siting == REFVSR_YUV_SITING_CENTRE)
+        return refvsr_yuv420_to_rgb(src, dst, nframes, h, w, yuv_fmt, chroma, coef9, stream);
+    RV_CHECK(src && dst, "yuv_to_rgb: null frame table");
+    RV_CHECK(nframes >= 1 && nframes <= REFVSR_YUV420_IN_MAX_FRAMES, "yuv_to_rgb: 1..%d frames per launch", REFVSR_YUV420_IN_MAX_FRAMES);
+    RV_CHECK(h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0 && (long)h * w <= (1L << 29),
+             "yuv_to_rgb: h, w must be even and positive, h * w <= 2^29 (got %d x %d)", h, w);
+    RV_CHECK(chroma == REFVSR_YUV_CHROMA_BILINEAR || chroma == REFVSR_YUV_CHROMA_NEAREST,
+             "yuv_to_rgb: chroma must be REFVSR_YUV_CHROMA_BILINEAR | REFVSR_YUV_CHROMA_NEAREST (got %d)", chroma);
+    RV_CHECK(coef9, "yuv_to_rgb: null coefficients");
+    const uintptr_t smask = (yuv_fmt == REFVSR_YUV_P010 || p10) ? 1 : 0;
+    YuvInArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < nframes; ++i) {
+        RV_CHECK(src[i] && dst[i], "yuv_to_rgb: null pointer (frame %d)", i);
+        RV_CHECK(((uintptr_t)src[i] & smask) == 0 && ((uintptr_t)dst[i] & 15) == 0,
+                 "yuv_to_rgb: source must be aligned to its samples, destination to 16 bytes (frame %d)", i);
+        a.src[i] = src[i];
+        a.dst[i] = dst[i];
+    }
+    a.h = h;
+    a.w = w;
+    a.gpr = (w + 7) / 8;
+    a.gxb = (a.gpr + 63) / 64;
+    a.nearest = chroma == REFVSR_YUV_CHROMA_NEAREST;
+    for (int i = 0; i < 9; ++i) a.k[i] = coef9[i];
+    const int hr = sampling == REFVSR_YUV_SAMPLING_420 ? h / 2 : h;           // rows (4:2:0: row pairs), four per workgroup
+    const dim3 grid((unsigned)(a.gxb * ((hr + 3) / 4)), (unsigned)nframes), block(64, 4);
+    hipStream_t st = (hipStream_t)stream;
+    const bool left = siting == REFVSR_YUV_SITING_LEFT;
+#define YUV_CHROMA_IN_GO(F, S, L) hipLaunchKernelGGL((yuv_chroma_in_kernel<F, S, L>), grid, block, 0, st, a)
+    if (sampling == REFVSR_YUV_SAMPLING_420) {                                 // left
+        switch (yuv_fmt) {
+            case REFVSR_YUV_NV12: YUV_CHROMA_IN_GO(REFVSR_YUV_NV12, REFVSR_YUV_SAMPLING_420, true); break;
+            case REFVSR_YUV_I420: YUV_CHROMA_IN_GO(REFVSR_YUV_I420, REFVSR_YUV_SAMPLING_420, true); break;
+            case REFVSR_YUV_P010: YUV_CHROMA_IN_GO(REFVSR_YUV_P010, REFVSR_YUV_SAMPLING_420, true); break;
+            default: YUV_CHROMA_IN_GO(REFVSR_YUV_I420P10, REFVSR_YUV_SAMPLING_420, true); break;
+        }
+    } else if (sampling == REFVSR_YUV_SAMPLING_422) {
+        if (left && p10) YUV_CHROMA_IN_GO(REFVSR_YUV_I420P10, REFVSR_YUV_SAMPLING_422, true);
+        else if (left) YUV_CHROMA_IN_GO(REFVSR_YUV_I420, REFVSR_YUV_SAMPLING_422, true);
+        else if (p10) YUV_CHROMA_IN_GO(REFVSR_YUV_I420P10, REFVSR_YUV_SAMPLING_422, false);
+        else YUV_CHROMA_IN_GO(REFVSR_YUV_I420, REFVSR_YUV_SAMPLING_422, false);
+    } else {
+        if (p10) YUV_CHROMA_IN_GO(REFVSR_YUV_I420P10, REFVSR_YUV_SAMPLING_444, false);
+        else YUV_CHROMA_IN_GO(REFVSR_YUV_I420, REFVSR_YUV_SAMPLING_444, false);
+    }
+#undef YUV_CHROMA_IN_GO
+    RV_LAUNCH_CHECK();
+    return 0;
+}

@@ -295,9 +295,13 @@ class Engine(object):
         # Y'CbCr 4:2:0 copies of the results (extension; default None = off, no launch): the network calls also return 'yuv', one
         # refvsr_result_to_yuv420 launch per call on the stream that receives 'result' (model.py:Network._with_yuv)
         self.result_yuv = yuv.resolve(getattr(config, 'result_yuv', None), getattr(config, 'yuv_matrix', None), getattr(config, 'yuv_range', None))
+        # (its chroma siting, checked while the feature is off too and read by Network._with_yuv beside the format: both are this
+        # engine's, from its construction; anything but 4:2:0 / centre goes through refvsr_result_to_yuv)
+        self.result_yuv_siting = yuv.resolve_siting(getattr(config, 'yuv_siting', None))
         # Y'CbCr 4:2:0 input frames (extension; default None = off): the windows' input source (inputs.py) is the 4:2:0 one
         self.input_yuv = yuv.resolve_input(getattr(config, 'input_yuv', None), getattr(config, 'input_yuv_matrix', None),
-                                           getattr(config, 'input_yuv_range', None), getattr(config, 'input_yuv_chroma', None))
+                                           getattr(config, 'input_yuv_range', None), getattr(config, 'input_yuv_chroma', None),
+                                           getattr(config, 'input_yuv_siting', None))
         self._pipe = None
         # stream layout of the pipelined mode when nothing is configured: 'pf_m' for one forward() per frame (round 4); an engine that
         # is driven through forward_group switches to 'pfm' (P | F | M) at its first group: with the backward branches batched the

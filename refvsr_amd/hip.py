@@ -16,6 +16,8 @@ RESULT_HWC = 0x10                           # REFVSR_RESULT_HWC: flag bit of an 
 INGEST_PLANAR, INGEST_HWC = 0, 1
 YUV_NV12, YUV_I420, YUV_P010, YUV_I420P10 = range(4)       # REFVSR_YUV_*: `yuv_fmt` of refvsr_result_to_yuv420, `format` of refvsr_yuv420_to_rgb
 YUV_CHROMA_BILINEAR, YUV_CHROMA_NEAREST = 0, 1             # REFVSR_YUV_CHROMA_*: `chroma` of refvsr_yuv420_to_rgb
+YUV_SAMPLING_420, YUV_SAMPLING_422, YUV_SAMPLING_444 = range(3)      # REFVSR_YUV_SAMPLING_*: `sampling` of refvsr_result_to_yuv / refvsr_yuv_to_rgb
+YUV_SITING_CENTRE, YUV_SITING_LEFT = 0, 1                  # REFVSR_YUV_SITING_*: `siting` of the same two
 C24_CONV24, C24_CONV32, C24_CONV48, C24_SHUFFLE2, C24_CONF_ALPHA, C24_CONV_LAST = range(6)      # REFVSR_C24_*: `op` of refvsr_conv24_variant
 MATCH_KP, MATCH_ROWCHUNK, MATCH_COLBLOCK = 152, 256, 512
 ABI_VERSION = 15
@@ -186,6 +188,9 @@ SIGNATURES = {
     # its bytes, sad, stream
     'refvsr_luma_sad': [_P, _P, _I, _I, _I, _I, _P, _Z, _P, _P],
     'refvsr_scene_max_pairs': [],                # returns REFVSR_SCENE_MAX_PAIRS
+    # 4:2:2 / 4:4:4 / left-sited frames (added symbols, ABI 15 unchanged): the two 4:2:0 signatures with sampling, siting behind yuv_fmt
+    'refvsr_result_to_yuv': [_P, _I, _P, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _P],
+    'refvsr_yuv_to_rgb': [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _P],
 }
 # fp16 weight format (ABI 15): <name>_f16w twins with the signature of the function they are named after
 _F16W_TWINS = ('refvsr_resblock24_chain', 'refvsr_resblock24_chain_batch', 'refvsr_conv24', 'refvsr_conv24_batch', 'refvsr_conv32',
@@ -197,6 +202,7 @@ _SPECIAL = {'refvsr_abi_version': (C.c_int, []), 'refvsr_last_error': (C.c_char_
             'refvsr_conf_colormap_workspace_bytes': (C.c_size_t, [_I, _I, _I]),
             'refvsr_param_fingerprint_workspace_bytes': (C.c_size_t, [_I]),
             'refvsr_yuv420_bytes': (C.c_size_t, [_I, _I, _I]),
+            'refvsr_yuv_frame_bytes': (C.c_size_t, [_I, _I, _I, _I]),
             'refvsr_luma_sad_workspace_bytes': (C.c_size_t, [_I, _I, _I])}
 EXPORTS = tuple(sorted(list(SIGNATURES) + list(_SPECIAL)))
 

@@ -59,21 +59,26 @@ class _Bytes(_Float):
 
 class _Yuv420(_Bytes):
     """4:2:0 frames [3h/2, w] under config.input_yuv resolved (format, matrix, range, chroma): the copies of the source samples (half
-    the bytes of the uint8 kind) key the compare, the fp32 frames are filled by refvsr_yuv420_to_rgb."""
+    the bytes of the uint8 kind) key the compare, the fp32 frames are filled by refvsr_yuv420_to_rgb.  Also the 4:2:2 / 4:4:4 formats
+    ([2h, w] / [3h, w] frames) and left-sited chroma (a fifth parameter, yuv.resolve_input): those go through refvsr_yuv_to_rgb.  The
+    format -- and so the sampling -- and the siting are part of the key: the same bytes under another declaration never match."""
 
     def __init__(self, params):
         self.params = tuple(params)
+        self.plain = self.params[0] in yuv.FORMATS and len(self.params) == 4          # 4:2:0, centre-sited
 
     @property
     def key(self):
         return ('yuv',) + self.params
 
     def geometry(self, x):
-        return ops.yuv_geometry(x)
+        return ops.yuv_geometry(x) if self.params[0] in yuv.FORMATS else ops.yuv_geometry(x, self.params[0])
 
     def decode(self, pairs):
-        if pairs:
+        if pairs and self.plain:
             ops.yuv420_ingest(pairs, *self.params)
+        elif pairs:
+            ops.yuv_ingest(pairs, *self.params)
 
 
 _FLOAT = _Float()
@@ -98,10 +103,11 @@ def check_window(lrs, refs, fmt, dim, what, lead):
     both float (what else an entry asks of RGB windows, convert or refuse, is its own).  RuntimeError, one line, otherwise."""
     if fmt is not None:
         dt = torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16
+        rows = {'420': '3h/2', '422': '2h', '444': '3h'}[yuv.sampling_of(fmt)]
         for x in (lrs, refs):
             if not (x.is_cuda and x.dim() == dim - 1 and x.dtype == dt and x.shape == lrs.shape and ops.yuv_window_kind(x, fmt) is not None):
-                raise RuntimeError("input_yuv = '%s': lrs and refs must be contiguous cuda %s [%s, 3h/2, w] windows of one shape, 3h/2 rows with even "
-                                   "h and w (got %s %s%s)" % (fmt, dt, lead, x.dtype, tuple(x.shape), '' if x.is_contiguous() else ', not contiguous'))
+                raise RuntimeError("input_yuv = '%s': lrs and refs must be contiguous cuda %s [%s, %s, w] windows of one shape, %s rows with even "
+                                   "h and w (got %s %s%s)" % (fmt, dt, lead, rows, rows, x.dtype, tuple(x.shape), '' if x.is_contiguous() else ', not contiguous'))
     elif lrs.dim() == dim - 1:
         raise RuntimeError("%s: windows are float or uint8 [.., t, 3, h, w]; [.., t, 3h/2, w] Y'CbCr 4:2:0 windows need config.input_yuv "
                            "(got %s %s)" % (what, lrs.dtype, tuple(lrs.shape)))

@@ -909,50 +909,78 @@ def result_to_yuv420(frames, fmt='nv12', matrix='bt709', range='limited'):
     head stores), contiguous or channels-last (config.result_layout = 'hwc'), h and w even.  matrix: 'bt709' | 'bt601'; range:
     'limited' | 'full'.  One launch per REFVSR_YUV420_MAX_FRAMES frames."""
     from . import yuv
+    if fmt not in yuv.FORMATS:
+        yuv.check_format(fmt)
+        raise ValueError('result_to_yuv420: %r is not a 4:2:0 format: ops.result_to_yuv takes it' % (fmt,))
+    return _result_to_yuv('result_to_yuv420', frames, fmt, matrix, range, lambda ps, sfmt, pd, n, h, w, coef, st: hip.lib().refvsr_result_to_yuv420(
+        ps, sfmt, pd, n, h, w, yuv.FORMAT_IDS[fmt], coef, st))
+
+
+def result_to_yuv(frames, fmt='i422', matrix='bt709', range='limited', siting='centre'):
+    """result_to_yuv420 for every format and siting (refvsr_result_to_yuv; the bits of yuv.rgb_to_yuv): fmt also 'i422' | 'i444' |
+    'i422p10' | 'i444p10', a [B, 2 h, w] or [B, 3 h, w] tensor; siting 'centre' | 'left' (checked and ignored for 4:4:4).  A 4:2:0
+    format with siting 'centre' gives result_to_yuv420's bits (the library hands the call to refvsr_result_to_yuv420)."""
+    from . import yuv
+    samp, sit = yuv.SAMPLINGS[yuv.sampling_of(fmt)], yuv.SITINGS[yuv.check_siting(siting)]
+    return _result_to_yuv('result_to_yuv', frames, fmt, matrix, range, lambda ps, sfmt, pd, n, h, w, coef, st: hip.lib().refvsr_result_to_yuv(
+        ps, sfmt, pd, n, h, w, yuv.FORMAT_IDS[yuv.twin_of(fmt)], samp, sit, coef, st))
+
+
+def _result_to_yuv(name, frames, fmt, matrix, range, launch):
+    """The body of result_to_yuv420 / result_to_yuv: the frames checked, the output [B] + yuv.frame_shape(h, w, fmt) allocated, one
+    launch(src table, src format, dst table, n, h, w, coef9, stream) per REFVSR_YUV420_MAX_FRAMES frames."""
+    from . import yuv
     coef = (C.c_double * 9)(*yuv.coefficients(fmt, matrix, range))
     frames = list(frames)
     if not frames:
-        raise RuntimeError('result_to_yuv420: at least one frame')
+        raise RuntimeError('%s: at least one frame' % name)
     f0 = frames[0]
     fmts = {torch.float32: hip.RESULT_F32, torch.float16: hip.RESULT_F16, torch.uint8: hip.RESULT_U8}
     if not (f0.is_cuda and f0.dtype in fmts and f0.dim() == 3 and f0.shape[0] == 3):
-        raise RuntimeError('result_to_yuv420: cuda float32 | float16 | uint8 results [3,h,w] (got %s %s %s)' % (f0.device.type, f0.dtype, tuple(f0.shape)))
+        raise RuntimeError('%s: cuda float32 | float16 | uint8 results [3,h,w] (got %s %s %s)' % (name, f0.device.type, f0.dtype, tuple(f0.shape)))
     _, h, w = f0.shape
     if h % 2 or w % 2:
-        raise RuntimeError('result_to_yuv420: 4:2:0 needs even h and w (got %d x %d)' % (h, w))
+        raise RuntimeError('%s: %s needs even h and w (got %d x %d)' % (name, '4:2:0' if fmt in yuv.FORMATS else fmt, h, w))
     lay = result_layout_of(f0)
     for f in frames:
         if f.shape != f0.shape or f.dtype != f0.dtype or not f.is_cuda:
-            raise RuntimeError('result_to_yuv420: frames must all be %s [3, %d, %d] (got %s %s)' % (f0.dtype, h, w, f.dtype, tuple(f.shape)))
+            raise RuntimeError('%s: frames must all be %s [3, %d, %d] (got %s %s)' % (name, f0.dtype, h, w, f.dtype, tuple(f.shape)))
         if lay is None or result_layout_of(f) != lay:
-            raise RuntimeError('result_to_yuv420: results must be dense and of one layout, contiguous [3, h, w] or the channels-last view of '
-                               '[h, w, 3] (config.result_layout), got strides %s' % (tuple(f.stride()),))
+            raise RuntimeError('%s: results must be dense and of one layout, contiguous [3, h, w] or the channels-last view of '
+                               '[h, w, 3] (config.result_layout), got strides %s' % (name, tuple(f.stride())))
     sfmt = fmts[f0.dtype] | (hip.RESULT_HWC if lay == 'hwc' else 0)
-    out = torch.empty((len(frames),) + yuv.frame_shape(h, w), dtype=torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16, device=f0.device)
+    out = torch.empty((len(frames),) + yuv.frame_shape(h, w, fmt), dtype=torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16, device=f0.device)
     st = _stream()
     for s0 in _irange(0, len(frames), hip.YUV420_MAX_FRAMES):
         chunk = frames[s0:s0 + hip.YUV420_MAX_FRAMES]
-        hip.check(hip.lib().refvsr_result_to_yuv420(_parr(chunk), sfmt, _parr([out[s0 + i] for i in _irange(len(chunk))]), len(chunk), h, w,
-                                                    yuv.FORMAT_IDS[fmt], coef, st), 'result_to_yuv420')
+        hip.check(launch(_parr(chunk), sfmt, _parr([out[s0 + i] for i in _irange(len(chunk))]), len(chunk), h, w, coef, st), name)
     return out
 
 
 def yuv_window_kind(x, fmt):
     """('yuv', fmt) for a tensor whose trailing [3 h / 2, w] frames are dense 4:2:0 buffers of format `fmt` -- the sample type of the
-    format (torch.uint8 | torch.uint16), at least 2-D, contiguous, even h and w -- else None."""
+    format (torch.uint8 | torch.uint16), at least 2-D, contiguous, even h and w -- else None.  A 4:2:2 format: [2 h, w] frames, a
+    4:4:4 one: [3 h, w]."""
     from . import yuv
     dt = torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16
     if x.dtype != dt or x.dim() < 2 or not x.is_contiguous():
         return None
     r, w = x.shape[-2:]
-    if r < 3 or r % 3 or w < 2 or w % 2:                    # (3 h / 2 rows with even h: a multiple of 3)
+    unit = _YUV_ROW_UNIT[yuv.sampling_of(fmt)]              # (3 h / 2 rows with even h: a multiple of 3; 2 h: of 4; 3 h: of 6)
+    if r < unit or r % unit or w < 2 or w % 2:
         return None
     return ('yuv', fmt)
 
 
-def yuv_geometry(x):
-    """(h, w) of a tensor of [3 h / 2, w] frames."""
-    return 2 * x.shape[-2] // 3, x.shape[-1]
+_YUV_ROW_UNIT = {'420': 3, '422': 4, '444': 6}               # the rows of a frame of two luma rows
+
+
+def yuv_geometry(x, fmt=None):
+    """(h, w) of a tensor of [3 h / 2, w] frames; with a format, of that format's frames ([2 h, w] for 4:2:2, [3 h, w] for 4:4:4)."""
+    if fmt is None:
+        return 2 * x.shape[-2] // 3, x.shape[-1]
+    from . import yuv
+    return 2 * x.shape[-2] // _YUV_ROW_UNIT[yuv.sampling_of(fmt)], x.shape[-1]
 
 
 def yuv420_ingest(pairs, fmt='nv12', matrix='bt709', range='limited', chroma='bilinear'):
@@ -967,6 +995,35 @@ def yuv420_ingest(pairs, fmt='nv12', matrix='bt709', range='limited', chroma='bi
     _decode_frames(pairs, 'yuv420_to_rgb', 'yuv420_ingest: dense %s frames [3h/2, w] of one size' % fmt,
                    lambda src, h, w: yuv_window_kind(src, fmt) is not None and tuple(src.shape) == yuv.frame_shape(h, w), hip.YUV420_IN_MAX_FRAMES,
                    lambda ps, pd, n, h, w: hip.lib().refvsr_yuv420_to_rgb(ps, pd, n, h, w, yuv.FORMAT_IDS[fmt], mode, coef, _stream()))
+
+
+def yuv_ingest(pairs, fmt='i422', matrix='bt709', range='limited', chroma='bilinear', siting='centre'):
+    """yuv420_ingest for every format and siting (refvsr_yuv_to_rgb; the bits of yuv.yuv_to_rgb): src frames yuv.frame_shape(h, w, fmt),
+    siting 'centre' | 'left' (checked and ignored for 4:4:4).  A 4:2:0 format with siting 'centre' gives yuv420_ingest's bits (the
+    library hands the call to refvsr_yuv420_to_rgb)."""
+    from . import yuv
+    samp, sit = yuv.SAMPLINGS[yuv.sampling_of(fmt)], yuv.SITINGS[yuv.check_siting(siting)]
+    if not pairs:
+        return
+    coef = (C.c_double * 9)(*yuv.decode_coefficients(fmt, matrix, range))
+    mode = yuv.CHROMA_MODES[yuv.check_chroma(chroma)]
+    fid = yuv.FORMAT_IDS[yuv.twin_of(fmt)]
+    _decode_frames(pairs, 'yuv_to_rgb', 'yuv_ingest: dense %s frames of one size' % fmt,
+                   lambda src, h, w: yuv_window_kind(src, fmt) is not None and tuple(src.shape) == yuv.frame_shape(h, w, fmt), hip.YUV420_IN_MAX_FRAMES,
+                   lambda ps, pd, n, h, w: hip.lib().refvsr_yuv_to_rgb(ps, pd, n, h, w, fid, samp, sit, mode, coef, _stream()))
+
+
+def yuv_to_frames(x, h, w, fmt, matrix='bt709', range='limited', chroma='bilinear', siting='centre'):
+    """yuv420_to_frames for every format and siting: [..., rows, w] frames, rows = yuv.frame_shape(h, w, fmt)[0], -> a new contiguous
+    float32 [..., 3, h, w] tensor, the bits of yuv.yuv_to_rgb, through refvsr_yuv_to_rgb."""
+    from . import yuv
+    yuv.check_siting(siting)
+    dt = torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16
+    rows = yuv.frame_shape(h, w, fmt)[0]
+    if not (x.is_cuda and x.dtype == dt and x.dim() >= 2 and tuple(x.shape[-2:]) == (rows, w)):
+        raise RuntimeError('yuv_to_frames: cuda %s [..., %d, %d] frames for %s at %d x %d (got %s %s %s)'
+                           % (dt, rows, w, fmt, h, w, x.device.type, x.dtype, tuple(x.shape)))
+    return _frames_of(x, 2, torch.Tensor.is_contiguous, dt.itemsize, h, w, lambda pairs: yuv_ingest(pairs, fmt, matrix, range, chroma, siting))
 
 
 def yuv420_to_frames(x, h, w, fmt, matrix='bt709', range='limited', chroma='bilinear'):
@@ -989,7 +1046,8 @@ def luma_sad(frames_a, frames_b, h, w, fmt):
     integers of yuv.luma_sad): a torch.int64 [B] tensor on the current stream, no synchronisation.  frames_a, frames_b: a
     [B, 3 h / 2, w] tensor or B tensors [3 h / 2, w] each, uint8 ('nv12' | 'i420') or uint16 ('p010' | 'i420p10'), dense frames at
     any multiple of their sample size (views into a [t, 3 h / 2, w] window included); the same frame on both sides gives 0.  One call
-    (two launches) per REFVSR_SCENE_MAX_PAIRS pairs."""
+    (two launches) per REFVSR_SCENE_MAX_PAIRS pairs.  A 4:2:2 or 4:4:4 format: [2 h, w] or [3 h, w] frames, read under the format id
+    of the 4:2:0 twin -- the luma plane is the first h w samples of every layout."""
     from . import yuv
     fa, fb = list(frames_a), list(frames_b)
     if not fa or len(fa) != len(fb):
@@ -997,17 +1055,18 @@ def luma_sad(frames_a, frames_b, h, w, fmt):
     if h < 2 or w < 2 or h % 2 or w % 2:
         raise RuntimeError('luma_sad: 4:2:0 needs even h and w (got %d x %d)' % (h, w))
     dev = fa[0].device
+    shape = yuv.frame_shape(h, w, fmt)
     for f in fa + fb:
-        if not (f.is_cuda and f.device == dev and yuv_window_kind(f, fmt) is not None and tuple(f.shape) == yuv.frame_shape(h, w)):
+        if not (f.is_cuda and f.device == dev and yuv_window_kind(f, fmt) is not None and tuple(f.shape) == shape):
             raise RuntimeError('luma_sad: dense cuda %s frames [%d, %d] of one GPU (got %s %s %s)'
-                               % (fmt, 3 * h // 2, w, f.device.type, f.dtype, tuple(f.shape)))
+                               % (fmt, shape[0], w, f.device.type, f.dtype, tuple(f.shape)))
     st = _stream()
     ws = _score_workspace(_SAD_WS, dev, st, h, w, lambda: hip.lib().refvsr_luma_sad_workspace_bytes(hip.SCENE_MAX_PAIRS, h, w), 'luma_sad', 4,
                           'frames must hold at most 2^29 pixels')
     sad = torch.empty(len(fa), dtype=torch.int64, device=dev)
     for s0 in _irange(0, len(fa), hip.SCENE_MAX_PAIRS):
         n = min(hip.SCENE_MAX_PAIRS, len(fa) - s0)
-        hip.check(hip.lib().refvsr_luma_sad(_parr(fa[s0:s0 + n]), _parr(fb[s0:s0 + n]), n, h, w, yuv.FORMAT_IDS[fmt], _ptr(ws), ws.numel() * 4,
+        hip.check(hip.lib().refvsr_luma_sad(_parr(fa[s0:s0 + n]), _parr(fb[s0:s0 + n]), n, h, w, yuv.FORMAT_IDS[yuv.twin_of(fmt)], _ptr(ws), ws.numel() * 4,
                                             C.c_void_p(sad.data_ptr() + 8 * s0), st), 'luma_sad')
     return sad
 

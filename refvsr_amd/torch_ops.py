@@ -30,6 +30,8 @@ Op set (argument conventions of ops.py: `planar` = float32 [C,H,W], `nhwc16` = f
   score_regions(outs, gts, rects)                        the same pairs, rects = flat [4 R] ints -> float64 [B,R,2] = {sum (a-b)^2, sum S}
   result_to_yuv420(frames, fmt, matrix, range)           [B,3,h,w] results -> [B, 3h/2, w] uint8 | uint16 4:2:0 frames (yuv.py's bits)
   yuv420_to_rgb(x, h, w, fmt, matrix, range, chroma)     [..., 3h/2, w] uint8 | uint16 4:2:0 frames -> float32 [..., 3, h, w] (yuv.py's bits)
+  result_to_yuv(frames, fmt, matrix, range, siting)      result_to_yuv420 for every format ('i422', 'i444', .. too) and siting
+  yuv_to_rgb(x, h, w, fmt, matrix, range, chroma, siting)   yuv420_to_rgb for every format and siting: [..., rows of the format, w] frames
 """
 from typing import List, Optional, Tuple
 
@@ -328,8 +330,42 @@ def register():
         torch._check(x.dtype == (torch.uint8 if yuv.FORMATS[fmt][0] == 8 else torch.uint16), lambda: 'yuv420_to_rgb: uint8 or uint16 samples by format')
         return torch.empty(tuple(x.shape[:-2]) + (3, h, w), dtype=torch.float32, device=x.device)
 
+    @op('result_to_yuv')
+    def result_to_yuv(frames: torch.Tensor, fmt: str, matrix: str, range: str, siting: str) -> torch.Tensor:
+        return ops.result_to_yuv(frames, fmt, matrix, range, siting)
+
+    @result_to_yuv.register_fake
+    def _(frames, fmt, matrix, range, siting):
+        from . import yuv
+        torch._check(frames.dim() == 4 and frames.shape[1] == 3 and frames.shape[2] % 2 == 0 and frames.shape[3] % 2 == 0,
+                     lambda: 'result_to_yuv takes [B,3,h,w] results with even h and w')
+        torch._check(fmt in yuv.ALL_FORMATS, lambda: 'result_to_yuv: unknown yuv format')
+        torch._check(matrix in yuv.MATRICES, lambda: "result_to_yuv: yuv_matrix must be 'bt709' or 'bt601'")
+        torch._check(range in yuv.RANGES, lambda: "result_to_yuv: yuv_range must be 'limited' or 'full'")
+        torch._check(siting in yuv.SITINGS, lambda: "result_to_yuv: siting must be 'centre' or 'left'")
+        return torch.empty((frames.shape[0],) + yuv.frame_shape(frames.shape[2], frames.shape[3], fmt),
+                           dtype=torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16, device=frames.device)
+
+    @op('yuv_to_rgb')
+    def yuv_to_rgb(x: torch.Tensor, h: int, w: int, fmt: str, matrix: str, range: str, chroma: str, siting: str) -> torch.Tensor:
+        return ops.yuv_to_frames(x, h, w, fmt, matrix, range, chroma, siting)
+
+    @yuv_to_rgb.register_fake
+    def _(x, h, w, fmt, matrix, range, chroma, siting):
+        from . import yuv
+        torch._check(fmt in yuv.ALL_FORMATS, lambda: 'yuv_to_rgb: unknown yuv format')
+        torch._check(matrix in yuv.MATRICES, lambda: "yuv_to_rgb: matrix must be 'bt709' or 'bt601'")
+        torch._check(range in yuv.RANGES, lambda: "yuv_to_rgb: range must be 'limited' or 'full'")
+        torch._check(chroma in yuv.CHROMA_MODES, lambda: "yuv_to_rgb: chroma must be 'bilinear' or 'nearest'")
+        torch._check(siting in yuv.SITINGS, lambda: "yuv_to_rgb: siting must be 'centre' or 'left'")
+        torch._check(h > 0 and w > 0 and h % 2 == 0 and w % 2 == 0 and x.dim() >= 2 and tuple(x.shape[-2:]) == yuv.frame_shape(h, w, fmt),
+                     lambda: "yuv_to_rgb takes [..., rows, w] frames with even h and w, rows = 3h/2, 2h or 3h by the format's sampling")
+        torch._check(x.dtype == (torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16), lambda: 'yuv_to_rgb: uint8 or uint16 samples by format')
+        return torch.empty(tuple(x.shape[:-2]) + (3, h, w), dtype=torch.float32, device=x.device)
+
 
 OP_NAMES = ('conv_mfma', 'conv24', 'resblock', 'resblock24_chain', 'resblock24_chain_batch', 'conv24_batch', 'warp_batch', 'match_argmax', 'warp', 'warp_planar', 'spynet_level_input', 'block_gather',
-            'block_gather_rgb', 'aligned_sample', 'resize', 'pack_nhwc16', 'unpack_nhwc16', 'ingest_u8', 'score_frames', 'score_regions', 'result_to_yuv420', 'yuv420_to_rgb')
+            'block_gather_rgb', 'aligned_sample', 'resize', 'pack_nhwc16', 'unpack_nhwc16', 'ingest_u8', 'score_frames', 'score_regions', 'result_to_yuv420', 'yuv420_to_rgb', 'result_to_yuv',
+            'yuv_to_rgb')
 
 register()

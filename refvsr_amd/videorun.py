@@ -1,13 +1,16 @@
 """Video in, video out (extension): super-resolve a pair of .y4m files -- the ultra-wide LR stream and the wide reference stream --
-into a .y4m file, 4:2:0 on both sides of the network:
+into a .y4m file, Y'CbCr on both sides of the network (4:2:0, 4:2:2 or 4:4:4; centre- or left-sited chroma, as the files say):
 
     python -m refvsr_amd.videorun --config config_RefVSR_small_L1 --ckpt_abs_name CKPT --lr uw.y4m --ref w.y4m --out sr.y4m
         [--frame_num 5] [--frame_group 4] [--video_depth 8|10] [--yuv_matrix bt709|bt601] [--yuv_range limited|full]
         [--chroma bilinear|nearest] [--scene_cut 0.1 | --cuts 12,40,...]
+        [--in_siting centre|left] [--out_chroma 420|422|444] [--out_siting centre|left]
 
 The files are read frame by frame (yuv.Y4MReader), the windows are the reference's (evalrun.window_indices: clip edges replicate
 frames, data_loader/datasets.py:222-234), the network runs forward_group with frame ids, config.input_yuv taken from the files and
-config.result_yuv = 'i420' | 'i420p10', and 'yuv' goes to the output through yuv.Y4MWriter.  No scores, no images: evalrun.py has those.
+config.result_yuv = 'i420' | 'i420p10' (--out_chroma: the 'i422' / 'i444' forms), and 'yuv' goes to the output through
+yuv.Y4MWriter.  No scores, no images: evalrun.py has those.  The input's sampling and siting are the files' (C420mpeg2: left; C422:
+left; --in_siting overrides what a file says); the output keeps both unless told otherwise, so its C tag is the input's.
 
 A file with cuts (--scene_cut T: found from the LR stream's luma, ops.luma_sad + scene.py; --cuts: given) is run as the reference would
 run its scenes as separate clips: windows clamped at the cuts, no group across one, Network.reset() and is_first_frame at each
@@ -23,14 +26,17 @@ import torch
 
 from . import scene
 from .evalrun import load_checkpoint
-from .yuv import Y4MReader, Y4MWriter, check_chroma, check_matrix, check_range, depth_of
+from .yuv import Y4MReader, Y4MWriter, check_chroma, check_matrix, check_range, check_siting, depth_of, effective_siting, sampling_of
 
 
-def open_pair(lr_path, ref_path):
-    """The two readers of a run; ValueError (one line) unless geometry, format and frame count agree."""
+def open_pair(lr_path, ref_path, siting=None):
+    """The two readers of a run; ValueError (one line) unless geometry, format (sampling, depth and chroma siting) and frame count
+    agree.  siting ('centre' | 'left'; --in_siting): what both files' chroma siting is taken to be, whatever their headers say."""
     lr = Y4MReader(lr_path)
     try:
         ref = Y4MReader(ref_path)
+        if siting is not None:
+            lr.siting, ref.siting = effective_siting(lr.fmt, siting), effective_siting(ref.fmt, siting)
     except Exception:
         lr.close()
         raise
@@ -39,6 +45,8 @@ def open_pair(lr_path, ref_path):
         bad = 'geometry differs (%d x %d and %d x %d)' % (lr.h, lr.w, ref.h, ref.w)
     elif lr.fmt != ref.fmt:
         bad = 'format differs (%s and %s)' % (lr.fmt, ref.fmt)
+    elif lr.siting != ref.siting:
+        bad = 'format differs (%s with %s- and %s-sited chroma; --in_siting declares one for both)' % (lr.fmt, lr.siting, ref.siting)
     elif lr.length != ref.length:
         bad = 'frame count differs (%d and %d)' % (lr.length, ref.length)
     elif lr.length < 1:
@@ -51,16 +59,27 @@ def open_pair(lr_path, ref_path):
 
 
 def configure(config, reader):
-    """The run's fields of `config` from the LR file: input_yuv (always the files' format), input_yuv_range (the file's XCOLORRANGE
-    unless set: EVAL.input_range_set), result_yuv (by EVAL.video_depth; None: the input's depth)."""
+    """The run's fields of `config` from the LR file: input_yuv (always the files' format), input_yuv_siting (the reader's: the file's,
+    or open_pair's override), input_yuv_range (the file's XCOLORRANGE unless set: EVAL.input_range_set), result_yuv (by
+    EVAL.video_depth; None: the input's depth -- and by EVAL.out_chroma '420' | '422' | '444'; None: the input's sampling), yuv_siting
+    (EVAL.out_siting; None: 'left' for 4:2:2 output, which is what its tag means, else the input's)."""
     E = config.EVAL
     config.input_yuv = reader.fmt
+    config.input_yuv_siting = reader.siting
+    out = getattr(E, 'out_chroma', None) or sampling_of(reader.fmt)
+    if str(out) not in ('420', '422', '444'):
+        raise ValueError('videorun: --out_chroma must be 420, 422 or 444 (got %r)' % (out,))
+    siting = getattr(E, 'out_siting', None) or ('left' if str(out) == '422' else reader.siting)
+    try:
+        config.yuv_siting = check_siting(siting)
+    except ValueError:
+        raise ValueError("videorun: --out_siting must be 'centre' or 'left' (got %r)" % (siting,))
     if not getattr(E, 'input_range_set', False):
         config.input_yuv_range = reader.range
     depth = getattr(E, 'video_depth', None) or depth_of(reader.fmt)
     if depth not in (8, 10):
         raise ValueError('videorun: --video_depth must be 8 or 10 (got %r)' % (depth,))
-    config.result_yuv = 'i420' if depth == 8 else 'i420p10'
+    config.result_yuv = 'i%s%s' % (out, '' if depth == 8 else 'p10')
     return config
 
 
@@ -78,7 +97,7 @@ def run(config, lr_path, ref_path, out_path, net=None):
         raise ValueError('videorun: scene_cut and cuts exclude each other')
     if threshold is not None:
         threshold = scene.check_threshold(threshold)
-    lr, ref = open_pair(lr_path, ref_path)
+    lr, ref = open_pair(lr_path, ref_path, getattr(E, 'in_siting', None))
     writer = None
     was_pipelined = None
     try:
@@ -94,14 +113,15 @@ def run(config, lr_path, ref_path, out_path, net=None):
                 load_checkpoint(net, config.EVAL.ckpt_abs_name)
         nc = net.Network.config
         if nc is not config:                              # (a caller's net may carry a config of its own)
-            for k in ('input_yuv', 'input_yuv_range', 'result_yuv'):
+            for k in ('input_yuv', 'input_yuv_range', 'input_yuv_siting', 'result_yuv', 'yuv_siting'):
                 setattr(nc, k, getattr(config, k))
         if net.Network._engines and net.Network._engines[0].input_yuv is None:
             raise RuntimeError('videorun: the network passed in already runs without config.input_yuv; pass a fresh one')
         dev = next(net.parameters()).device
         n, t, G = lr.length, int(config.frame_num), max(1, int(getattr(config.EVAL, 'frame_group', 4) or 1))
         scale = int(config.scale)
-        writer = Y4MWriter(out_path, lr.h * scale, lr.w * scale, config.result_yuv, lr.fps, getattr(config, 'yuv_range', None) or 'limited')
+        writer = Y4MWriter(out_path, lr.h * scale, lr.w * scale, config.result_yuv, lr.fps, getattr(config, 'yuv_range', None) or 'limited',
+                           config.yuv_siting)
         was_pipelined = bool(getattr(nc, 'pipelined', False))
         net.Network.set_pipelined(True)
         net.Network.reset()
@@ -183,7 +203,7 @@ def build_config(argv=None):
     ap = argparse.ArgumentParser(description='RefVSR on .y4m files: 4:2:0 in, 4:2:0 out (MI355X HIP path)')
     ap.add_argument('--config', '-c', type=str, default='config_RefVSR_small_L1')
     ap.add_argument('--ckpt_abs_name', '-ckpt_abs_name', type=str, default=None)
-    ap.add_argument('--lr', required=True, help='the ultra-wide LR stream (.y4m, C420jpeg or C420p10)')
+    ap.add_argument('--lr', required=True, help='the ultra-wide LR stream (.y4m: C420jpeg, C420mpeg2, C420p10, C422, C444 and their 10-bit forms)')
     ap.add_argument('--ref', required=True, help='the wide reference stream (.y4m of the same geometry, format and length)')
     ap.add_argument('--out', required=True, help='the result (.y4m)')
     ap.add_argument('--frame_num', type=int, default=5)
@@ -192,6 +212,11 @@ def build_config(argv=None):
     ap.add_argument('--yuv_matrix', default='bt709', choices=['bt709', 'bt601'], help='luma coefficients, input and output')
     ap.add_argument('--yuv_range', default=None, choices=['limited', 'full'], help="code range, input and output (default: the LR file's XCOLORRANGE)")
     ap.add_argument('--chroma', default='bilinear', choices=['bilinear', 'nearest'], help='chroma up-sampling of the input')
+    ap.add_argument('--in_siting', default=None, choices=['centre', 'left'],
+                    help="chroma siting of the input, whatever the files say (default: the files': C420jpeg centre, C420mpeg2 and C422 left)")
+    ap.add_argument('--out_chroma', default=None, choices=['420', '422', '444'], help="chroma sampling of --out (default: the input files')")
+    ap.add_argument('--out_siting', default=None, choices=['centre', 'left'],
+                    help="chroma siting of --out (default: the input's; left for 4:2:2 output, which is what its tag means)")
     ap.add_argument('--scene_cut', type=float, default=None, metavar='T',
                     help='run every scene as a clip of its own; a frame starts a scene where the scene score of the LR stream\'s luma '
                          '(min(mafd, |mafd - previous mafd|) / 100, mafd = mean absolute luma difference to the previous frame on the 8-bit '
@@ -222,6 +247,7 @@ def build_config(argv=None):
         cfg.yuv_range = cfg.input_yuv_range = check_range(args.yuv_range)
     E.ckpt_abs_name, E.frame_group, E.video_depth = args.ckpt_abs_name, args.frame_group, args.video_depth
     E.scene_cut, E.cuts = scene_cut, cuts
+    E.in_siting, E.out_chroma, E.out_siting = args.in_siting, args.out_chroma, args.out_siting
     cfg.device, cfg.cuda = 'cuda', True
     return cfg, args
 

@@ -31,6 +31,35 @@ with (oy, iy = 1 / sy, oc, ic = 1 / sc, cr_r = 2 (1 - kr), cb_b = 2 (1 - kb), kr
 
 luma_sad: the sum of absolute differences of two frames' luma codes (the same codes), the model of refvsr_luma_sad (csrc/scene.hip)
 behind videorun's scene-cut detector (scene.py).
+
+Samplings and sitings (rgb_to_yuv, yuv_to_rgb: the models of refvsr_result_to_yuv and refvsr_yuv_to_rgb).  Four more planar formats,
+one dense buffer each as above, Y [h, w], Cb [h / cv, w / ch], Cr [h / cv, w / ch]:
+  'i422'  'i422p10'   (cv, ch) = (1, 2)   [2 h, w]      uint8 | uint16, the code in the low bits
+  'i444'  'i444p10'   (cv, ch) = (1, 1)   [3 h, w]
+h and w stay even for all of them (4:4:4 would not need it; the engine's frame checks and refvsr_luma_sad do).  Semi-planar 4:2:2 /
+4:4:4 (NV16, P210, NV24) does not exist here.  siting = 'centre' (a chroma sample lies in the middle of its luma pair: JPEG, the 4:2:0
+above) | 'left' (on the pair's even column: MPEG-2, what decoders deliver as NV12 / P010 and what 4:2:2 means in Y4M); vertically a
+4:2:0 sample lies between its two rows in both.  Siting is checked and then ignored for 4:4:4.
+  luma x   0   1   2   3   4   5
+  centre     0       1       2           sample j at x = 2j + 1/2
+  left     0       1       2             sample j at x = 2j
+  out   e = ecb | ecr as above, unquantised, l = max(2j - 1, 0):
+          4:4:4         m = e
+          4:2:2 centre  m = (e[y,2j] + e[y,2j+1]) 0.5
+          4:2:2 left    m = ((e[y,l] + e[y,2j+1]) + (e[y,2j] + e[y,2j])) 0.25          the [1 2 1] / 4 filter, the left edge clamped
+          4:2:0 left    v[x] = e[2i,x] + e[2i+1,x];  m = ((v[l] + v[2j+1]) + (v[2j] + v[2j])) 0.125
+        then C = rint(oc + sc m) and the clamp, as above
+  in    the integer tap sum 16 m, cx = x >> 1, cx' the clamped neighbour as above, cxr = min(cx + 1, w/2 - 1), cy and cy' as above:
+          4:4:4                 16 C[y,x]
+          4:2:2 centre          12 C[y,cx] + 4 C[y,cx']
+          4:2:2 left   even x   16 C[y,cx]                    odd x  8 C[y,cx] + 8 C[y,cxr]
+          4:2:0 left   even x   12 C[cy,cx] + 4 C[cy',cx]     odd x  6 C[cy,cx] + 2 C[cy',cx] + 6 C[cy,cxr] + 2 C[cy',cxr]
+          'nearest'             16 x the own sample, every sampling
+        everything behind the tap sum as above
+
+Y4M: the C tag names sampling, depth and, for 4:2:0, the siting (420jpeg = 420 = no tag: centre; 420mpeg2: left; 422*: left, Y4M
+defines 4:2:2 as co-sited); what a tag cannot say (420p10 left, 422 centre) is an XCHROMASITING=LEFT | CENTRE token, which the writer
+adds and the reader honours.  Top-left siting (420paldv), mono and interlaced files are refused by name.
 """
 import os
 
@@ -42,12 +71,39 @@ FORMAT_IDS = {'nv12': 0, 'i420': 1, 'p010': 2, 'i420p10': 3}          # REFVSR_Y
 MATRICES = {'bt709': (0.2126, 0.0722), 'bt601': (0.299, 0.114)}       # (kr, kb)
 RANGES = ('limited', 'full')
 PLANAR_TWIN = {'nv12': 'i420', 'p010': 'i420p10'}
+SAMPLINGS = {'420': 0, '422': 1, '444': 2}                            # REFVSR_YUV_SAMPLING_* of include/refvsr_hip.h
+SUBSAMPLING = {'420': (2, 2), '422': (1, 2), '444': (1, 1)}           # (cv, ch): luma rows and columns per chroma sample
+SITINGS = {'centre': 0, 'left': 1}                                    # REFVSR_YUV_SITING_*
+# the 4:2:2 / 4:4:4 formats: name -> (its 4:2:0 twin: depth, sample type, shift and format id are the twin's; sampling)
+CHROMA_FORMATS = {'i422': ('i420', '422'), 'i444': ('i420', '444'), 'i422p10': ('i420p10', '422'), 'i444p10': ('i420p10', '444')}
+ALL_FORMATS = tuple(FORMATS) + tuple(CHROMA_FORMATS)
 
 
 def check_format(fmt):
-    if fmt not in FORMATS:
-        raise ValueError('yuv format must be one of %s, got %r' % (', '.join("'%s'" % k for k in FORMATS), fmt))
+    if fmt not in FORMATS and fmt not in CHROMA_FORMATS:
+        raise ValueError('yuv format must be one of %s, got %r' % (', '.join("'%s'" % k for k in ALL_FORMATS), fmt))
     return fmt
+
+
+def twin_of(fmt):
+    """The 4:2:0 format of the same depth, sample type and shift (a 4:2:0 format is its own): its FORMATS / FORMAT_IDS entries hold
+    for fmt, and refvsr_luma_sad reads fmt's luma plane under the twin's id."""
+    return CHROMA_FORMATS[fmt][0] if check_format(fmt) in CHROMA_FORMATS else fmt
+
+
+def sampling_of(fmt):
+    return CHROMA_FORMATS[fmt][1] if check_format(fmt) in CHROMA_FORMATS else '420'
+
+
+def check_siting(siting, what='yuv siting'):
+    if siting not in SITINGS:
+        raise ValueError("%s must be 'centre' or 'left', got %r" % (what, siting))
+    return siting
+
+
+def effective_siting(fmt, siting):
+    """siting checked; 'centre' for 4:4:4, where it means nothing."""
+    return 'centre' if sampling_of(fmt) == '444' and check_siting(siting) else check_siting(siting)
 
 
 def check_matrix(matrix):
@@ -68,13 +124,19 @@ def resolve(result_yuv, matrix=None, range=None):
     m, r = check_matrix(matrix or 'bt709'), check_range(range or 'limited')
     if result_yuv is None:
         return None
-    if result_yuv not in FORMATS:
-        raise ValueError("result_yuv must be None, 'nv12', 'i420', 'p010' or 'i420p10', got %r" % (result_yuv,))
+    if result_yuv not in FORMATS and result_yuv not in CHROMA_FORMATS:
+        raise ValueError("result_yuv must be None, 'nv12', 'i420', 'p010' or 'i420p10', got %r (or a 4:2:2 / 4:4:4 form: %s)"
+                         % (result_yuv, ', '.join("'%s'" % f for f in CHROMA_FORMATS)))
     return (result_yuv, m, r)
 
 
+def resolve_siting(siting, what='yuv_siting'):
+    """config.yuv_siting / input_yuv_siting checked -- also while the format is off (as resolve): 'centre' (None: the default) | 'left'."""
+    return check_siting(siting or 'centre', what)
+
+
 def depth_of(fmt):
-    return FORMATS[check_format(fmt)][0]
+    return FORMATS[twin_of(fmt)][0]
 
 
 def dtype_of(fmt):
@@ -96,16 +158,18 @@ def coefficients(fmt='nv12', matrix='bt709', range='limited'):
     return (kr, kg, kb, icb, icr, float(oy), float(sy), float(oc), float(sc))
 
 
-def frame_shape(h, w):
-    """[3 h / 2, w]: the view of a frame's buffer."""
+def frame_shape(h, w, fmt=None):
+    """[3 h / 2, w]: the view of a frame's buffer; with a format, that format's: [2 h, w] for 4:2:2, [3 h, w] for 4:4:4."""
     if h <= 0 or w <= 0 or h % 2 or w % 2:
-        raise ValueError('4:2:0 frames need even, positive h and w (got %d x %d)' % (h, w))
-    return (3 * h // 2, w)
+        raise ValueError('4:2:0 frames need even, positive h and w (got %d x %d)' % (h, w) if fmt is None or fmt in FORMATS else
+                         '%s frames need even, positive h and w, as every format here (got %d x %d)' % (fmt, h, w))
+    cv, ch = SUBSAMPLING[sampling_of(fmt)] if fmt is not None else (2, 2)
+    return (h + 2 * (h // cv) // ch, w)
 
 
 def frame_bytes(h, w, fmt):
-    """Bytes of one frame (== refvsr_yuv420_bytes)."""
-    r, c = frame_shape(h, w)
+    """Bytes of one frame (== refvsr_yuv_frame_bytes; 4:2:0: == refvsr_yuv420_bytes)."""
+    r, c = frame_shape(h, w, fmt)
     return r * c * (1 if depth_of(fmt) == 8 else 2)
 
 
@@ -119,8 +183,24 @@ def source_f64(x):
     return x.astype(np.float64)
 
 
-def pre_rounding(rgb, coef):
-    """(oy + sy ey [h, w], oc + sc mcb [h/2, w/2], oc + sc mcr [h/2, w/2]) of one [3, h, w] frame: the values rint sees."""
+def chroma_mean(e, sampling='420', siting='centre'):
+    """The mean m [h / cv, w / ch] of the unquantised chroma e [h, w] (float64) that one chroma sample stands for."""
+    if sampling == '444':
+        return e
+    if check_siting(siting) == 'centre':
+        if sampling == '422':
+            return (e[:, 0::2] + e[:, 1::2]) * 0.5
+        return ((e[0::2, 0::2] + e[0::2, 1::2]) + (e[1::2, 0::2] + e[1::2, 1::2])) * 0.25
+    l = np.maximum(np.arange(0, e.shape[1], 2) - 1, 0)              # the odd column left of the pair, clamped
+    if sampling == '422':
+        return ((e[:, l] + e[:, 1::2]) + (e[:, 0::2] + e[:, 0::2])) * 0.25
+    v = e[0::2] + e[1::2]
+    return ((v[:, l] + v[:, 1::2]) + (v[:, 0::2] + v[:, 0::2])) * 0.125
+
+
+def pre_rounding(rgb, coef, sampling='420', siting='centre'):
+    """(oy + sy ey [h, w], oc + sc mcb [h/2, w/2], oc + sc mcr [h/2, w/2]) of one [3, h, w] frame: the values rint sees (the chroma
+    planes [h / cv, w / ch] of the sampling)."""
     kr, kg, kb, icb, icr, oy, sy, oc, sc = coef
     v = source_f64(rgb)
     assert v.ndim == 3 and v.shape[0] == 3, 'a frame is [3, h, w]'
@@ -129,8 +209,7 @@ def pre_rounding(rgb, coef):
     ey = (kr * r + kg * g) + kb * b
     out = [oy + sy * ey]
     for e in ((b - ey) * icb, (r - ey) * icr):
-        m = ((e[0::2, 0::2] + e[0::2, 1::2]) + (e[1::2, 0::2] + e[1::2, 1::2])) * 0.25
-        out.append(oc + sc * m)
+        out.append(oc + sc * chroma_mean(e, sampling, siting))
     return tuple(out)
 
 
@@ -141,12 +220,12 @@ def quantise(v, depth):
 
 def pack(y, cb, cr, fmt):
     """Integer code planes -> the frame's buffer [3 h / 2, w] in the format's layout and sample type."""
-    d, semi, shift = FORMATS[check_format(fmt)]
+    d, semi, shift = FORMATS[twin_of(fmt)]
     h, w = y.shape
     dt = dtype_of(fmt)
     c = np.stack([cb, cr], axis=-1).reshape(-1) if semi else np.concatenate([cb.reshape(-1), cr.reshape(-1)])
     flat = np.concatenate([np.asarray(y).reshape(-1), c]).astype(np.int64) << shift
-    return flat.astype(dt).reshape(frame_shape(h, w))
+    return flat.astype(dt).reshape(frame_shape(h, w, fmt))
 
 
 def rgb_to_yuv420(rgb, fmt='nv12', matrix='bt709', range='limited'):
@@ -160,17 +239,31 @@ def rgb_to_yuv420(rgb, fmt='nv12', matrix='bt709', range='limited'):
     return pack(quantise(yv, d), quantise(cbv, d), quantise(crv, d), fmt)
 
 
+def rgb_to_yuv(rgb, fmt='i422', matrix='bt709', range='limited', siting='centre'):
+    """The model of every sampling and siting: a [3, h, w] result -> the frame's buffer frame_shape(h, w, fmt); a [B, 3, h, w] batch
+    -> [B, ...].  A 4:2:0 format with siting = 'centre' is rgb_to_yuv420."""
+    rgb = np.asarray(rgb)
+    if rgb.ndim == 4:
+        return np.stack([rgb_to_yuv(f, fmt, matrix, range, siting) for f in rgb])
+    d = depth_of(fmt)
+    yv, cbv, crv = pre_rounding(rgb, coefficients(fmt, matrix, range), sampling_of(fmt), effective_siting(fmt, siting))
+    return pack(quantise(yv, d), quantise(cbv, d), quantise(crv, d), fmt)
+
+
 def planes(buf, h, w, fmt):
-    """The (Y [h, w], Cb [h/2, w/2], Cr [h/2, w/2]) views of a frame's buffer; together they tile it exactly."""
-    d, semi, _ = FORMATS[check_format(fmt)]
+    """The (Y [h, w], Cb [h/2, w/2], Cr [h/2, w/2]) views of a frame's buffer (the chroma planes [h / cv, w / ch] of the format's
+    sampling); together they tile it exactly."""
+    d, semi, _ = FORMATS[twin_of(fmt)]
+    cv, ch = SUBSAMPLING[sampling_of(fmt)]
     flat = np.asarray(buf).reshape(-1)
-    assert flat.size == 3 * h * w // 2 and frame_shape(h, w), 'a frame holds 3 h w / 2 samples'
-    n, q = h * w, h * w // 4
+    rows, _ = frame_shape(h, w, fmt)
+    assert flat.size == rows * w, 'a %s frame holds %d samples' % (fmt, rows * w)
+    n, q = h * w, (h // cv) * (w // ch)
     y = flat[:n].reshape(h, w)
     if semi:
         c = flat[n:].reshape(h // 2, w // 2, 2)
         return y, c[..., 0], c[..., 1]
-    return y, flat[n:n + q].reshape(h // 2, w // 2), flat[n + q:].reshape(h // 2, w // 2)
+    return y, flat[n:n + q].reshape(h // cv, w // ch), flat[n + q:].reshape(h // cv, w // ch)
 
 
 def to_planar(buf, h, w, fmt):
@@ -190,15 +283,18 @@ def check_chroma(chroma):
     return chroma
 
 
-def resolve_input(input_yuv, matrix=None, range=None, chroma=None):
-    """config.input_yuv / input_yuv_matrix / input_yuv_range / input_yuv_chroma checked: None (off) or (format, matrix, range, chroma);
-    ValueError for a bad name, also while the format is off (as resolve)."""
+def resolve_input(input_yuv, matrix=None, range=None, chroma=None, siting=None):
+    """config.input_yuv / input_yuv_matrix / input_yuv_range / input_yuv_chroma / input_yuv_siting checked: None (off) or (format,
+    matrix, range, chroma) -- with 'left' behind it where the frames are left-sited (centre, and 4:4:4, keep the four: the arguments of
+    ops.yuv420_ingest; the five are those of ops.yuv_ingest); ValueError for a bad name, also while the format is off (as resolve)."""
     m, r, c = check_matrix(matrix or 'bt709'), check_range(range or 'limited'), check_chroma(chroma or 'bilinear')
+    s = resolve_siting(siting, 'input_yuv_siting')
     if input_yuv is None:
         return None
-    if input_yuv not in FORMATS:
-        raise ValueError("input_yuv must be None, 'nv12', 'i420', 'p010' or 'i420p10', got %r" % (input_yuv,))
-    return (input_yuv, m, r, c)
+    if input_yuv not in FORMATS and input_yuv not in CHROMA_FORMATS:
+        raise ValueError("input_yuv must be None, 'nv12', 'i420', 'p010' or 'i420p10', got %r (or a 4:2:2 / 4:4:4 form: %s)"
+                         % (input_yuv, ', '.join("'%s'" % f for f in CHROMA_FORMATS)))
+    return (input_yuv, m, r, c) if effective_siting(input_yuv, s) == 'centre' else (input_yuv, m, r, c, s)
 
 
 def decode_coefficients(fmt='nv12', matrix='bt709', range='limited'):
@@ -210,7 +306,7 @@ def decode_coefficients(fmt='nv12', matrix='bt709', range='limited'):
 
 def codes(buf, h, w, fmt):
     """The integer code planes (Y [h, w], Cb [h/2, w/2], Cr [h/2, w/2]; int64) of a frame's buffer."""
-    d, _, shift = FORMATS[check_format(fmt)]
+    d, _, shift = FORMATS[twin_of(fmt)]
     buf = np.asarray(buf)
     if buf.dtype != dtype_of(fmt):
         raise TypeError('%s frames are %s (got %s)' % (fmt, np.dtype(dtype_of(fmt)).name, buf.dtype))
@@ -225,26 +321,41 @@ def luma_sad(a, b, h, w, fmt):
     return int(np.abs(ya - yb).sum(dtype=np.int64))
 
 
-def chroma_taps(c, chroma='bilinear'):
+def chroma_taps(c, chroma='bilinear', sampling='420', siting='centre'):
     """The integer tap sum 16 m [h, w] of a chroma code plane [h/2, w/2] (int64): 9 C[cy,cx] + 3 C[cy',cx] + 3 C[cy,cx'] + C[cy',cx']
-    at every luma pixel, the neighbours clamped at the edges; 'nearest': 16 C[cy,cx]."""
+    at every luma pixel, the neighbours clamped at the edges; 'nearest': 16 C[cy,cx].  With a sampling and a siting: the plane is
+    [h / cv, w / ch] and the sum is the module text's."""
+    if sampling == '444':
+        check_chroma(chroma), check_siting(siting)
+        return 16 * c
     h2, w2 = c.shape
-    y, x = np.arange(2 * h2), np.arange(2 * w2)
-    cy, cx = y >> 1, x >> 1
+    cv = SUBSAMPLING[sampling][0]
+    y, x = np.arange(cv * h2), np.arange(2 * w2)
+    cy, cx = y >> (cv - 1), x >> 1
     if check_chroma(chroma) == 'nearest':
+        check_siting(siting)
         return 16 * c[cy][:, cx]
+    # two horizontal taps of weights (wa, wb), together 4; then the vertical 3 : 1 of 4:2:0, or x 4
+    if check_siting(siting) == 'centre':
+        cx2 = np.clip(cx + np.where(x & 1, 1, -1), 0, w2 - 1)
+        wa, wb = 3, 1
+    else:
+        cx2 = np.minimum(cx + 1, w2 - 1)
+        wa, wb = np.where(x & 1, 2, 4), np.where(x & 1, 2, 0)
+    if sampling == '422':
+        return 4 * wa * c[:, cx] + 4 * wb * c[:, cx2]
     cy2 = np.clip(cy + np.where(y & 1, 1, -1), 0, h2 - 1)
-    cx2 = np.clip(cx + np.where(x & 1, 1, -1), 0, w2 - 1)
-    return 9 * c[cy][:, cx] + 3 * c[cy2][:, cx] + 3 * c[cy][:, cx2] + c[cy2][:, cx2]
+    return 3 * wa * c[cy][:, cx] + wa * c[cy2][:, cx] + 3 * wb * c[cy][:, cx2] + wb * c[cy2][:, cx2]
 
 
-def decode_pre_clamp(buf, h, w, fmt='nv12', matrix='bt709', range='limited', chroma='bilinear'):
+def decode_pre_clamp(buf, h, w, fmt='nv12', matrix='bt709', range='limited', chroma='bilinear', siting='centre'):
     """(r, g, b) float64 [h, w] of one frame before the clamp to [0, 1] and the rounding to float32."""
     oy, iy, oc, ic, cr_r, cb_b, kr, kb, ikg = decode_coefficients(fmt, matrix, range)
     yc, cbc, crc = codes(buf, h, w, fmt)
+    sampling = sampling_of(fmt)
     ey = (yc.astype(np.float64) - oy) * iy
-    ecb = (chroma_taps(cbc, chroma).astype(np.float64) * 0.0625 - oc) * ic
-    ecr = (chroma_taps(crc, chroma).astype(np.float64) * 0.0625 - oc) * ic
+    ecb = (chroma_taps(cbc, chroma, sampling, siting).astype(np.float64) * 0.0625 - oc) * ic
+    ecr = (chroma_taps(crc, chroma, sampling, siting).astype(np.float64) * 0.0625 - oc) * ic
     r = ey + cr_r * ecr
     b = ey + cb_b * ecb
     g = ((ey - kr * r) - kb * b) * ikg
@@ -262,6 +373,17 @@ def yuv420_to_rgb(buf, h, w, fmt, matrix='bt709', range='limited', chroma='bilin
     return np.stack([np.clip(v, 0.0, 1.0) for v in decode_pre_clamp(buf, h, w, fmt, matrix, range, chroma)]).astype(np.float32)
 
 
+def yuv_to_rgb(buf, h, w, fmt, matrix='bt709', range='limited', chroma='bilinear', siting='centre'):
+    """The model of the way in for every sampling and siting: a frame's buffer frame_shape(h, w, fmt) -> float32 [3, h, w] in [0, 1];
+    a [B, ...] batch -> [B, 3, h, w].  A 4:2:0 format with siting = 'centre' is yuv420_to_rgb."""
+    buf = np.asarray(buf)
+    if buf.ndim == 3:
+        return np.stack([yuv_to_rgb(f, h, w, fmt, matrix, range, chroma, siting) for f in buf])
+    if buf.shape != frame_shape(h, w, fmt):
+        raise ValueError('a %d x %d %s frame is %s (got %s)' % (h, w, fmt, frame_shape(h, w, fmt), buf.shape))
+    return np.stack([np.clip(v, 0.0, 1.0) for v in decode_pre_clamp(buf, h, w, fmt, matrix, range, chroma, siting)]).astype(np.float32)
+
+
 # ------------------------------------------------------------------------------------------------ Y4M
 def parse_fps(text):
     """'30' | '30000:1001' -> (num, den)."""
@@ -275,20 +397,40 @@ def parse_fps(text):
     return num, den
 
 
-def y4m_header(h, w, fmt, fps=(30, 1), range='limited'):
-    frame_shape(h, w)
+# C tag -> (format, the siting the tag means; None: 4:4:4 has none)
+Y4M_TAGS = {'420jpeg': ('i420', 'centre'), '420': ('i420', 'centre'), '420mpeg2': ('i420', 'left'), '420p10': ('i420p10', 'centre'),
+            '422': ('i422', 'left'), '422p10': ('i422p10', 'left'), '444': ('i444', None), '444p10': ('i444p10', None)}
+Y4M_DEFAULT_SITING = {'420': 'centre', '422': 'left', '444': 'centre'}        # of a sampling, where nobody says otherwise
+
+
+def y4m_tag(fmt, siting=None):
+    """(C tag, XCHROMASITING value or None) of a planar format; siting None: the sampling's default."""
     if fmt in PLANAR_TWIN:
         raise ValueError("%r is not a Y4M format (Y4M frames are planar): use %r" % (fmt, PLANAR_TWIN[fmt]))
-    tag = 'C420jpeg' if depth_of(fmt) == 8 else 'C420p10'
-    return ('YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 %s XCOLORRANGE=%s\n' % (w, h, fps[0], fps[1], tag, check_range(range).upper())).encode('ascii')
+    sampling, p10 = sampling_of(fmt), 'p10' if depth_of(fmt) == 10 else ''
+    siting = effective_siting(fmt, Y4M_DEFAULT_SITING[sampling] if siting is None else siting)
+    if sampling == '420':
+        tag = ('420jpeg' if siting == 'centre' else '420mpeg2') if not p10 else '420p10'
+    else:
+        tag = sampling + p10
+    means = Y4M_TAGS[tag][1]
+    return 'C' + tag, None if means is None or means == siting else siting.upper()
+
+
+def y4m_header(h, w, fmt, fps=(30, 1), range='limited', siting=None):
+    frame_shape(h, w, check_format(fmt))
+    tag, extra = y4m_tag(fmt, siting)
+    return ('YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 %s XCOLORRANGE=%s%s\n' % (w, h, fps[0], fps[1], tag, check_range(range).upper(),
+                                                                        ' XCHROMASITING=%s' % extra if extra else '')).encode('ascii')
 
 
 class Y4MWriter(object):
     """A .y4m file of 'i420' (C420jpeg) or 'i420p10' (C420p10, little-endian samples) frames: the header, then `FRAME\\n` and the
-    planes Y, Cb, Cr per frame -- which is the frame's buffer as it lies in memory."""
+    planes Y, Cb, Cr per frame -- which is the frame's buffer as it lies in memory.  Also 'i422', 'i444' and their 10-bit forms, and
+    a siting (y4m_tag has the tags; None: the sampling's default)."""
 
-    def __init__(self, path, h, w, fmt='i420', fps=(30, 1), range='limited'):
-        self.header = y4m_header(h, w, fmt, fps, range)
+    def __init__(self, path, h, w, fmt='i420', fps=(30, 1), range='limited', siting=None):
+        self.header = y4m_header(h, w, fmt, fps, range, siting)
         self.h, self.w, self.fmt = h, w, fmt
         self.frames = 0
         self.fh = open(path, 'wb')
@@ -296,9 +438,9 @@ class Y4MWriter(object):
 
     def write(self, buf):
         a = np.asarray(buf)
-        if a.shape != frame_shape(self.h, self.w) or a.dtype != dtype_of(self.fmt):
+        if a.shape != frame_shape(self.h, self.w, self.fmt) or a.dtype != dtype_of(self.fmt):
             raise ValueError('Y4MWriter: %s frames are %s %s (got %s %s)' % (self.fmt, np.dtype(dtype_of(self.fmt)).name,
-                                                                          frame_shape(self.h, self.w), a.dtype, a.shape))
+                                                                          frame_shape(self.h, self.w, self.fmt), a.dtype, a.shape))
         self.fh.write(b'FRAME\n')
         self.fh.write(np.ascontiguousarray(a).astype(a.dtype.newbyteorder('<'), copy=False).tobytes())
         self.frames += 1
@@ -316,14 +458,34 @@ class Y4MWriter(object):
 
 
 def parse_y4m_header(line, path):
-    """The header line (without its newline) -> dict(h, w, fps, fmt, range)."""
+    """The header line (without its newline) -> dict(h, w, fps, fmt, range, siting); siting is 'centre' for 4:4:4."""
     tok = line.decode('ascii', 'replace').split(' ')
     if tok[0] != 'YUV4MPEG2':
         raise ValueError('%s: not a YUV4MPEG2 file' % path)
     f = dict((t[0], t[1:]) for t in tok[1:] if t and t[0] != 'X')
     x = dict(t[1:].split('=', 1) for t in tok[1:] if t and t[0] == 'X' and '=' in t)
-    fmt = {'420jpeg': 'i420', '420p10': 'i420p10'}[f['C']]
-    return {'h': int(f['H']), 'w': int(f['W']), 'fps': parse_fps(f['F']), 'fmt': fmt, 'range': x.get('COLORRANGE', 'LIMITED').lower()}
+    for k in 'WHF':
+        if k not in f:
+            raise ValueError('%s: the YUV4MPEG2 header has no %s token' % (path, k))
+    if f.get('I', 'p') not in ('p', '?'):
+        raise ValueError('%s: interlaced file (I%s): only progressive frames are read' % (path, f['I']))
+    tag = f.get('C', '420')                                          # no C token: 4:2:0, the format's default
+    if tag not in Y4M_TAGS:
+        why = 'top-left sited chroma' if tag == '420paldv' else 'no chroma' if tag.startswith('mono') else 'unknown chroma tag'
+        raise ValueError('%s: C%s (%s) is not read: one of %s' % (path, tag, why, ', '.join('C' + k for k in Y4M_TAGS)))
+    fmt, siting = Y4M_TAGS[tag]
+    said = x.get('CHROMASITING')
+    if said is not None:
+        if said.lower() not in SITINGS:
+            raise ValueError('%s: XCHROMASITING=%s: LEFT or CENTRE' % (path, said))
+        siting = said.lower()
+    try:
+        h, w = int(f['H']), int(f['W'])
+        frame_shape(h, w, fmt)
+    except ValueError as e:
+        raise ValueError('%s: %s' % (path, e))
+    return {'h': h, 'w': w, 'fps': parse_fps(f['F']), 'fmt': fmt, 'range': x.get('COLORRANGE', 'LIMITED').lower(),
+            'siting': effective_siting(fmt, siting or 'centre')}
 
 
 class Y4MReader(object):
@@ -342,7 +504,7 @@ class Y4MReader(object):
         except Exception:
             self.close()
             raise
-        self.h, self.w, self.fps, self.fmt, self.range = hd['h'], hd['w'], hd['fps'], hd['fmt'], hd['range']
+        self.h, self.w, self.fps, self.fmt, self.range, self.siting = hd['h'], hd['w'], hd['fps'], hd['fmt'], hd['range'], hd['siting']
         self.frames = 0             # frames read so far
         # whole frames in the file, by its size (a truncated last frame is not counted; read() reports it)
         self.length = (os.fstat(self.fh.fileno()).st_size - len(line)) // (6 + frame_bytes(self.h, self.w, self.fmt))
@@ -359,7 +521,7 @@ class Y4MReader(object):
             raise ValueError('%s: truncated frame %d' % (self.path, self.frames))
         self.frames += 1
         dt = dtype_of(self.fmt)
-        return np.frombuffer(raw, dtype=np.dtype(dt).newbyteorder('<')).astype(dt).reshape(frame_shape(self.h, self.w))
+        return np.frombuffer(raw, dtype=np.dtype(dt).newbyteorder('<')).astype(dt).reshape(frame_shape(self.h, self.w, self.fmt))
 
     def __iter__(self):
         while True:
@@ -396,6 +558,6 @@ def read_y4m(path):
         raw = data[pos:pos + nbytes]
         if len(raw) != nbytes:
             raise ValueError('%s: truncated frame %d' % (path, len(frames)))
-        frames.append(np.frombuffer(raw, dtype=np.dtype(dtype_of(fmt)).newbyteorder('<')).astype(dtype_of(fmt)).reshape(frame_shape(h, w)))
+        frames.append(np.frombuffer(raw, dtype=np.dtype(dtype_of(fmt)).newbyteorder('<')).astype(dtype_of(fmt)).reshape(frame_shape(h, w, fmt)))
         pos += nbytes
     return dict(hd, frames=frames)
