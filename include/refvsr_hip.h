@@ -703,6 +703,39 @@ int refvsr_yuv_to_rgb(const void* const* src, float* const* dst, int nframes, in
                       int chroma, const double* coef9, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Antialiased bicubic resize of RGB frames (extension, no ABI bump: added symbols only).  Replaces two things of the reference's
+ * world that are not in its code: the offline step that made the dataset's LRx4 folders (the 4x bicubic down-scales the *_L1 configs
+ * are trained and scored on, configs/config.py:120-152 reads them ready-made), and the consumer's resize of a result behind the image
+ * writer (evaluation/eval_qual_quan.py:117-119).  The filter is Keys' cubic with a = -0.5 stretched by the down-scale ratio (support
+ * 2 scale, weights normalised per output sample): Pillow's, MATLAB imresize's and F.interpolate(mode='bicubic', antialias=True,
+ * align_corners=False)'s.  It is NOT the bicubic of refvsr_resize / refvsr_score_frames_down (A = -0.75, four taps, no antialias).
+ * The specification is the numpy model refvsr_amd/resize.py (aa_taps, resize_aa_model); the kernel returns its bits.
+ * refvsr_resize_max_frames: replaces nothing -- REFVSR_RESIZE_MAX_FRAMES of the built library (a value, not a status).
+ * refvsr_resize_aa: nframes <= REFVSR_RESIZE_MAX_FRAMES frames of one h x w -> oh x ow in ONE launch on `stream`, no host
+ *   synchronisation, no intermediate in global memory (the horizontal sums of a tile live in LDS as float64):
+ *     src: HOST array of device pointers, one dense 3 x h x w frame each in src_fmt = REFVSR_RESULT_F32 | _F16 | _U8, planar or
+ *          | REFVSR_RESULT_HWC, at any multiple of its sample size; a byte means the float32 refvsr_ingest_u8 gives it;
+ *     dst: HOST array of device pointers to dense planar [3][oh][ow] frames, dst_fmt = REFVSR_RESULT_F32 (any 4-byte alignment) or
+ *          REFVSR_RESULT_U8 (any address);
+ *     lo_x, cnt_x [ow] int32, wx [ow][maxcnt_x] float64, lo_y, cnt_y [oh], wy [oh][maxcnt_y]: DEVICE tables, the taps of
+ *          resize.py:aa_taps(w, ow) and aa_taps(h, oh): output column j is the sum over k < cnt_x[j] of wx[j][k] src[lo_x[j] + k],
+ *          added in ascending k from the first product, every operation rounded on its own; rows the same over the unrounded
+ *          horizontal sums.  The device computes no weight.  The host cannot read the tables: the kernel clamps every index they
+ *          yield into the rows and columns it staged, so a wrong table gives wrong samples, never an access outside the frames;
+ *     clamp: 1: float32(clamp(D, 0, 1)), one rounding; 0: float32(D).  A byte destination is rint(255 clamp(D, 0, 1)), half to
+ *          even, whatever `clamp` says.
+ *   Limits: h <= 8 oh and w <= 8 ow (at most 33 taps), no limit on up-scaling, frames below 2^31 bytes.
+ *   Every argument is checked before any device work: null tables, frame count, format ids, sizes and ratio, clamp, cnt against
+ *   maxcnt (maxcnt_x, maxcnt_y in 1 .. min(33, the taps an axis of these sizes can have)), table alignment, null entries, entries
+ *   not aligned to their samples, overlaps.
+ * ------------------------------------------------------------------------------------------ */
+#define REFVSR_RESIZE_MAX_FRAMES 16
+int refvsr_resize_max_frames(void);
+int refvsr_resize_aa(const void* const* src, int src_fmt, void* const* dst, int dst_fmt, int nframes, int h, int w, int oh, int ow,
+                     const int32_t* lo_x, const int32_t* cnt_x, const double* wx, const int32_t* lo_y, const int32_t* cnt_y,
+                     const double* wy, int maxcnt_x, int maxcnt_y, int clamp, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Scene cuts: luma SAD of frame pairs (extension, no ABI bump: added symbols only).  Replaces nothing in the reference: its loader
  * serves one folder per clip, replicates frames at the clip's edges (data_loader/datasets.py:222-234) and starts every clip with
  * is_first = True, so it never meets a cut.  A video file has cuts; refvsr_amd/videorun.py (--scene_cut) runs every scene as the

@@ -29,6 +29,7 @@ COLORMAP_MAX_MAPS = 16                      # REFVSR_COLORMAP_MAX_MAPS: maps per
 YUV420_MAX_FRAMES = 16                      # REFVSR_YUV420_MAX_FRAMES: result frames per refvsr_result_to_yuv420 launch
 YUV420_IN_MAX_FRAMES = 16                   # REFVSR_YUV420_IN_MAX_FRAMES: 4:2:0 input frames per refvsr_yuv420_to_rgb launch
 SCENE_MAX_PAIRS = 16                        # REFVSR_SCENE_MAX_PAIRS: frame pairs per refvsr_luma_sad call
+RESIZE_MAX_FRAMES = 16                      # REFVSR_RESIZE_MAX_FRAMES: frames per refvsr_resize_aa launch
 FINGERPRINT_CHUNK_WORDS = 4096              # REFVSR_FINGERPRINT_CHUNK_WORDS: words per chunk-table entry of refvsr_param_fingerprint
 RESBLOCK24_BLOB_BYTES = 43264
 RESBLOCK24_F16W_BLOB_BYTES = 28928          # the fp16 weight format (ABI 15)
@@ -191,6 +192,10 @@ SIGNATURES = {
     # 4:2:2 / 4:4:4 / left-sited frames (added symbols, ABI 15 unchanged): the two 4:2:0 signatures with sampling, siting behind yuv_fmt
     'refvsr_result_to_yuv': [_P, _I, _P, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _P],
     'refvsr_yuv_to_rgb': [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _P],
+    # antialiased bicubic resize (added symbols, ABI 15 unchanged): src table, src_fmt, dst table, dst_fmt, frames, h, w, oh, ow, lo_x,
+    # cnt_x, wx, lo_y, cnt_y, wy (device tables of resize.aa_taps), maxcnt_x, maxcnt_y, clamp, stream
+    'refvsr_resize_aa': [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    'refvsr_resize_max_frames': [],              # returns REFVSR_RESIZE_MAX_FRAMES
 }
 # fp16 weight format (ABI 15): <name>_f16w twins with the signature of the function they are named after
 _F16W_TWINS = ('refvsr_resblock24_chain', 'refvsr_resblock24_chain_batch', 'refvsr_conv24', 'refvsr_conv24_batch', 'refvsr_conv32',
@@ -233,7 +238,8 @@ def lib():
                                    (h.refvsr_score_max_rects, SCORE_MAX_RECTS, 'REFVSR_SCORE_MAX_RECTS'),
                                    (h.refvsr_yuv420_max_frames, YUV420_MAX_FRAMES, 'REFVSR_YUV420_MAX_FRAMES'),
                                    (h.refvsr_yuv420_in_max_frames, YUV420_IN_MAX_FRAMES, 'REFVSR_YUV420_IN_MAX_FRAMES'),
-                                   (h.refvsr_scene_max_pairs, SCENE_MAX_PAIRS, 'REFVSR_SCENE_MAX_PAIRS')):
+                                   (h.refvsr_scene_max_pairs, SCENE_MAX_PAIRS, 'REFVSR_SCENE_MAX_PAIRS'),
+                                   (h.refvsr_resize_max_frames, RESIZE_MAX_FRAMES, 'REFVSR_RESIZE_MAX_FRAMES')):
             if query() != const:
                 raise RuntimeError('refvsr_amd: %s mismatch (library %d, binding %d)' % (name, query(), const))
         _lib = h

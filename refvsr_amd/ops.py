@@ -957,6 +957,67 @@ def _result_to_yuv(name, frames, fmt, matrix, range, launch):
     return out
 
 
+_RESIZE_TAPS = {}     # (device, h, w, oh, ow) -> the device tap tables of one geometry (resize.aa_taps of both axes) and their widths
+
+
+def _resize_taps(dev, h, w, oh, ow):
+    """The cached device tables of resize_aa for one geometry: (lo_x, cnt_x, wx, lo_y, cnt_y, wy, maxcnt_x, maxcnt_y); built on the
+    host by resize.aa_taps and uploaded once (the first call of a geometry copies; later calls launch only)."""
+    from . import resize
+    key = (dev, h, w, oh, ow)
+    taps = _RESIZE_TAPS.get(key)
+    if taps is None:
+        if len(_RESIZE_TAPS) > 16:
+            _RESIZE_TAPS.clear()
+        (lx, cx, wx), (ly, cy, wy) = resize.aa_taps(w, ow), resize.aa_taps(h, oh)
+        taps = _RESIZE_TAPS[key] = tuple(torch.from_numpy(np.ascontiguousarray(a_)).to(dev) for a_ in (lx, cx, wx, ly, cy, wy)) + (wx.shape[1], wy.shape[1])
+    return taps
+
+
+def resize_aa(frames, oh, ow, out='float32', clamp=True):
+    """Antialiased bicubic resize on the device (refvsr_resize_aa; the bits of resize.resize_aa_model): a new contiguous [B,3,oh,ow]
+    tensor, torch.float32 (clamp True: clamped to [0, 1] before its one rounding) or torch.uint8 (out = 'uint8': rint of 255 x the
+    clamped value, half to even), on the current stream, no synchronisation.  frames: a [B,3,h,w] tensor or B tensors [3,h,w], float32 /
+    float16 / uint8 (a byte means the float32 ingest_u8 gives it), contiguous or channels-last (config.result_layout = 'hwc'), dense,
+    of one geometry.  h <= 8 oh and w <= 8 ow; up-scaling has no limit.  The filter is Keys' cubic, a = -0.5, stretched by the
+    down-scale ratio and normalised: the 'BI' degradation, what made the dataset's LRx4 folders -- not the engine's A = -0.75 bicubic.
+    One launch per REFVSR_RESIZE_MAX_FRAMES frames; the tap tables are cached per (h, w, oh, ow)."""
+    from . import resize
+    if out not in ('float32', 'uint8'):
+        raise RuntimeError("resize_aa: out must be 'float32' or 'uint8' (got %r)" % (out,))
+    frames = list(frames)
+    if not frames:
+        raise RuntimeError('resize_aa: at least one frame')
+    f0 = frames[0]
+    fmts = {torch.float32: hip.RESULT_F32, torch.float16: hip.RESULT_F16, torch.uint8: hip.RESULT_U8}
+    if not (f0.is_cuda and f0.dtype in fmts and f0.dim() == 3 and f0.shape[0] == 3):
+        raise RuntimeError('resize_aa: cuda float32 | float16 | uint8 frames [3,h,w] (got %s %s %s)' % (f0.device.type, f0.dtype, tuple(f0.shape)))
+    _, h, w = f0.shape
+    try:
+        resize.check_sizes(h, oh, 'resize_aa')
+        resize.check_sizes(w, ow, 'resize_aa')
+        oh, ow = int(oh), int(ow)
+    except (TypeError, ValueError) as e:
+        raise RuntimeError(str(e) if isinstance(e, ValueError) else 'resize_aa: oh, ow must be integers (got %r, %r)' % (oh, ow))
+    lay = result_layout_of(f0)
+    for f in frames:
+        if f.shape != f0.shape or f.dtype != f0.dtype or not f.is_cuda:
+            raise RuntimeError('resize_aa: frames must all be %s [3, %d, %d] (got %s %s)' % (f0.dtype, h, w, f.dtype, tuple(f.shape)))
+        if lay is None or result_layout_of(f) != lay:
+            raise RuntimeError('resize_aa: frames must be dense and of one layout, contiguous [3, h, w] or the channels-last view of '
+                               '[h, w, 3] (config.result_layout), got strides %s' % (tuple(f.stride()),))
+    sfmt = fmts[f0.dtype] | (hip.RESULT_HWC if lay == 'hwc' else 0)
+    lx, cx, wx, ly, cy, wy, mx, my = _resize_taps(f0.device, h, w, oh, ow)
+    res = torch.empty((len(frames), 3, oh, ow), dtype=torch.float32 if out == 'float32' else torch.uint8, device=f0.device)
+    dfmt = hip.RESULT_F32 if out == 'float32' else hip.RESULT_U8
+    st = _stream()
+    for s0 in _irange(0, len(frames), hip.RESIZE_MAX_FRAMES):
+        chunk = frames[s0:s0 + hip.RESIZE_MAX_FRAMES]
+        hip.check(hip.lib().refvsr_resize_aa(_parr(chunk), sfmt, _parr([res[s0 + i] for i in _irange(len(chunk))]), dfmt, len(chunk), h, w, oh, ow,
+                                             _ptr(lx), _ptr(cx), _ptr(wx), _ptr(ly), _ptr(cy), _ptr(wy), mx, my, 1 if clamp else 0, st), 'resize_aa')
+    return res
+
+
 def yuv_window_kind(x, fmt):
     """('yuv', fmt) for a tensor whose trailing [3 h / 2, w] frames are dense 4:2:0 buffers of format `fmt` -- the sample type of the
     format (torch.uint8 | torch.uint16), at least 2-D, contiguous, even h and w -- else None.  A 4:2:2 format: [2 h, w] frames, a

@@ -32,6 +32,7 @@ Op set (argument conventions of ops.py: `planar` = float32 [C,H,W], `nhwc16` = f
   yuv420_to_rgb(x, h, w, fmt, matrix, range, chroma)     [..., 3h/2, w] uint8 | uint16 4:2:0 frames -> float32 [..., 3, h, w] (yuv.py's bits)
   result_to_yuv(frames, fmt, matrix, range, siting)      result_to_yuv420 for every format ('i422', 'i444', .. too) and siting
   yuv_to_rgb(x, h, w, fmt, matrix, range, chroma, siting)   yuv420_to_rgb for every format and siting: [..., rows of the format, w] frames
+  resize_aa(frames, oh, ow, out, clamp)                  [B,3,h,w] frames -> [B,3,oh,ow] float32 | uint8, antialiased bicubic (resize.py's bits)
 """
 from typing import List, Optional, Tuple
 
@@ -363,9 +364,22 @@ def register():
         torch._check(x.dtype == (torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16), lambda: 'yuv_to_rgb: uint8 or uint16 samples by format')
         return torch.empty(tuple(x.shape[:-2]) + (3, h, w), dtype=torch.float32, device=x.device)
 
+    @op('resize_aa')
+    def resize_aa(frames: torch.Tensor, oh: int, ow: int, out: str, clamp: bool) -> torch.Tensor:
+        return ops.resize_aa(frames, oh, ow, out, clamp)
+
+    @resize_aa.register_fake
+    def _(frames, oh, ow, out, clamp):
+        torch._check(frames.dim() == 4 and frames.shape[1] == 3, lambda: 'resize_aa takes [B,3,h,w] frames')
+        torch._check(frames.dtype in (torch.float32, torch.float16, torch.uint8), lambda: 'resize_aa: float32 | float16 | uint8 frames')
+        torch._check(out in ('float32', 'uint8'), lambda: "resize_aa: out must be 'float32' or 'uint8'")
+        torch._check(oh >= 1 and ow >= 1 and frames.shape[2] <= 8 * oh and frames.shape[3] <= 8 * ow,
+                     lambda: 'resize_aa: positive sizes, a down-scale ratio of at most 8 per axis')
+        return torch.empty((frames.shape[0], 3, oh, ow), dtype=torch.float32 if out == 'float32' else torch.uint8, device=frames.device)
+
 
 OP_NAMES = ('conv_mfma', 'conv24', 'resblock', 'resblock24_chain', 'resblock24_chain_batch', 'conv24_batch', 'warp_batch', 'match_argmax', 'warp', 'warp_planar', 'spynet_level_input', 'block_gather',
             'block_gather_rgb', 'aligned_sample', 'resize', 'pack_nhwc16', 'unpack_nhwc16', 'ingest_u8', 'score_frames', 'score_regions', 'result_to_yuv420', 'yuv420_to_rgb', 'result_to_yuv',
-            'yuv_to_rgb')
+            'yuv_to_rgb', 'resize_aa')
 
 register()
