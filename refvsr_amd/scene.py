@@ -116,22 +116,29 @@ class GroupPlanner(object):
     """plan_groups, group by group.  push(is_cut) classifies the next frame (0, 1, ...; frame 0's answer is ignored: it always starts
     a scene); pop() returns the next group once `need()` frames are classified -- the frames up to the last one its windows can
     read, min(f0 + G + t // 2, n): exactly the frames the run has to have read for that group anyway -- and None before that or
-    behind the last group (done())."""
+    behind the last group (done()).
+    n = None: the length is not known (a pipe).  need() is f0 + G + t // 2 and pop() returns a group as soon as that many frames are
+    classified; finish() says that the frames pushed so far are all there are (n = known): pop() then drains the remaining groups and
+    done() becomes true behind the last one.  The pops are those of plan_groups(n, t, G, cuts) either way."""
 
     def __init__(self, n, t, G):
-        self.n, self.t, self.G = int(n), int(t), int(G)
+        self.n, self.t, self.G = None if n is None else int(n), int(t), int(G)
         self.known = 0                     # frames classified so far
         self.cuts = []
         self._f0, self._s = 0, 0           # first frame of the next group, first frame of its scene
 
+    def finish(self):
+        if self.n is None:
+            self.n = self.known
+
     def done(self):
-        return self._f0 >= self.n
+        return self.n is not None and self._f0 >= self.n
 
     def need(self):
-        return min(self._f0 + self.G + self.t // 2, self.n)
+        return self._f0 + self.G + self.t // 2 if self.n is None else min(self._f0 + self.G + self.t // 2, self.n)
 
     def push(self, is_cut):
-        if self.known >= self.n:
+        if self.n is not None and self.known >= self.n:
             raise ValueError('GroupPlanner: all %d frames are classified' % self.n)
         if is_cut and self.known > 0:
             self.cuts.append(self.known)
@@ -141,7 +148,8 @@ class GroupPlanner(object):
         if self.done() or self.known < self.need():
             return None
         f0, s = self._f0, self._s
-        e = min([c for c in self.cuts if c > f0] + [self.n])           # the scene's end, if it lies inside the frames known
+        # (a length not known yet lies beyond the known frames, as a scene's end there does)
+        e = min([c for c in self.cuts if c > f0] + [self.known + 1 if self.n is None else self.n])      # the scene's end, if it lies inside the frames known
         hi = min(f0 + self.G, e)
         # a window reads frames below min(f + t // 2 + 1, e): an end beyond the known frames is beyond every window of the group, and
         # the clamp at any such end gives the same indices

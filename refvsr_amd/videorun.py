@@ -6,6 +6,7 @@ into a .y4m file, Y'CbCr on both sides of the network (4:2:0, 4:2:2 or 4:4:4; ce
         [--chroma bilinear|nearest] [--scene_cut 0.1 | --cuts 12,40,...]
         [--in_siting centre|left] [--out_chroma 420|422|444] [--out_siting centre|left]
         [--in_down K [--score scores.txt]] [--out_size WxH]
+        [--io sync|stream|auto] [--io_depth 2] [--io_timeout 120]
 
 The files are read frame by frame (yuv.Y4MReader), the windows are the reference's (evalrun.window_indices: clip edges replicate
 frames, data_loader/datasets.py:222-234), the network runs forward_group with frame ids, config.input_yuv taken from the files and
@@ -24,9 +25,25 @@ runs on those frames as RGB windows (uint8 from 8-bit files: what an LRx4 PNG ho
 (ops.score_frames): a line `frame psnr ssim` per frame and a final `mean` line.  --out_size WxH writes the result at another size:
 config.result_yuv off, each group's results through ops.resize_aa and ops.result_to_yuv.  All three are off by default, and off
 means the calls, the launches and the bytes of a run without them.
+
+Pipes (--io).  Frames of this size come from a decoder process and go to an encoder process: --lr, --ref and --out may be FIFOs, one of
+--lr / --ref and --out may be '-' (with --out - every message goes to stderr):
+
+    DECODER .. | python -m refvsr_amd.videorun .. --lr - --ref w.fifo --out - | ENCODER ..
+
+--io sync is the loop above: read, stack and upload, forward_group, read back, write, one after the other on one thread, three
+regular files.  --io stream is the same plan and the same calls -- configure(), prepare(), scene.GroupPlanner with the length unknown,
+forward_group with the same windows, ids and is_first_frame, Network.reset() at each scene -- and the same bytes, with the I/O around
+the calls instead of between them (run_stream): one reader thread per input and one writer thread (streamio.py; host memory and file
+descriptors only, every GPU call is made on the caller's thread and stream); every file frame goes to the device once, from a pinned
+staging ring into a frame store, and the windows are stacked there (the sync loop uploads a frame t times); results leave through a
+pinned ring behind an event, --io_depth groups in flight, only the oldest waited for.  --io auto (default) is stream when one of the
+three ends is '-' or no regular file, else sync.  An input that delivers nothing for --io_timeout seconds ends the run instead of
+hanging it.  config.EVAL.io_stats says where the wall time went; profiles/videorun_stream_timing.txt has it measured.
 """
 import argparse
 import collections
+import os
 import sys
 import time
 
@@ -36,7 +53,7 @@ import torch
 from . import metrics, scene
 from .evalrun import load_checkpoint
 from .yuv import (Y4MReader, Y4MWriter, check_chroma, check_matrix, check_range, check_siting, depth_of, effective_siting, resolve_input,
-                  sampling_of)
+                  sampling_of, sink_name)
 
 
 def open_pair(lr_path, ref_path, siting=None):
@@ -50,13 +67,9 @@ def open_pair(lr_path, ref_path, siting=None):
     except Exception:
         lr.close()
         raise
-    bad = None
-    if (lr.h, lr.w) != (ref.h, ref.w):
-        bad = 'geometry differs (%d x %d and %d x %d)' % (lr.h, lr.w, ref.h, ref.w)
-    elif lr.fmt != ref.fmt:
-        bad = 'format differs (%s and %s)' % (lr.fmt, ref.fmt)
-    elif lr.siting != ref.siting:
-        bad = 'format differs (%s with %s- and %s-sited chroma; --in_siting declares one for both)' % (lr.fmt, lr.siting, ref.siting)
+    bad = pair_mismatch(lr, ref)
+    if bad:
+        pass
     elif lr.length != ref.length:
         bad = 'frame count differs (%d and %d)' % (lr.length, ref.length)
     elif lr.length < 1:
@@ -66,6 +79,17 @@ def open_pair(lr_path, ref_path, siting=None):
         ref.close()
         raise ValueError('videorun: %s and %s: %s' % (lr_path, ref_path, bad))
     return lr, ref
+
+
+def pair_mismatch(lr, ref):
+    """What keeps two readers from being the streams of one run -- geometry, format, chroma siting -- or None."""
+    if (lr.h, lr.w) != (ref.h, ref.w):
+        return 'geometry differs (%d x %d and %d x %d)' % (lr.h, lr.w, ref.h, ref.w)
+    if lr.fmt != ref.fmt:
+        return 'format differs (%s and %s)' % (lr.fmt, ref.fmt)
+    if lr.siting != ref.siting:
+        return 'format differs (%s with %s- and %s-sited chroma; --in_siting declares one for both)' % (lr.fmt, lr.siting, ref.siting)
+    return None
 
 
 def configure(config, reader):
@@ -139,13 +163,17 @@ def run(config, lr_path, ref_path, out_path, net=None):
     its own; the cuts the run used are left in config.EVAL.scene_cuts (a tuple; empty without the options), and under scene_cut the
     seconds include the detector's upload and its ops.luma_sad call per group.
     EVAL.in_down / EVAL.score_file / EVAL.out_size: the module header; the scores are left in config.EVAL.scores, a list of (frame,
-    psnr, ssim), and the seconds include the decode, the resizes and the scorer."""
+    psnr, ssim), and the seconds include the decode, the resizes and the scorer.
+    EVAL.io ('sync' | 'stream' | 'auto'; None: 'auto'), EVAL.io_depth, EVAL.io_timeout: the module header and run_stream(), which takes
+    over when the mode is 'stream' -- the paths may then be '-', FIFOs or binary file objects, and the seconds are the loop's wall time."""
     E = config.EVAL
     threshold, cuts = getattr(E, 'scene_cut', None), getattr(E, 'cuts', None)
     if threshold is not None and cuts is not None:
         raise ValueError('videorun: scene_cut and cuts exclude each other')
     if threshold is not None:
         threshold = scene.check_threshold(threshold)
+    if io_mode(getattr(E, 'io', None), lr_path, ref_path, out_path) == 'stream':
+        return run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts)
     lr, ref = open_pair(lr_path, ref_path, getattr(E, 'in_siting', None))
     writer = None
     was_pipelined = None
@@ -154,27 +182,11 @@ def run(config, lr_path, ref_path, out_path, net=None):
             cuts = scene.check_cuts(cuts or (), lr.length)
         except ValueError as e:
             raise ValueError('videorun: %s (%d frames)' % (e, lr.length))
-        configure(config, lr)
-        if net is None:
-            from . import SRNet
-            net = SRNet(config).to('cuda').eval()
-            if config.EVAL.ckpt_abs_name:
-                load_checkpoint(net, config.EVAL.ckpt_abs_name)
+        net, dev, t, G, out_range, out_hw = prepare(config, lr, net)
         nc = net.Network.config
-        if nc is not config:                              # (a caller's net may carry a config of its own)
-            for k in ('input_yuv', 'input_yuv_range', 'input_yuv_siting', 'result_yuv', 'yuv_siting'):
-                setattr(nc, k, getattr(config, k))
         down, size, score_file = E.in_down, E.out_size, E.score_file
-        if net.Network._engines and (net.Network._engines[0].input_yuv is None) != (down is not None):
-            raise RuntimeError('videorun: the network passed in already runs %s config.input_yuv; pass a fresh one' % ('with' if down else 'without'))
-        if net.Network._engines and size is not None and net.Network._engines[0].result_yuv is not None:
-            raise RuntimeError('videorun: the network passed in already runs with config.result_yuv; pass a fresh one')
-        dev = next(net.parameters()).device
-        n, t, G = lr.length, int(config.frame_num), max(1, int(getattr(config.EVAL, 'frame_group', 4) or 1))
-        scale = int(config.scale)
-        out_range = getattr(config, 'yuv_range', None) or 'limited'
-        rh, rw = (lr.h * scale, lr.w * scale) if down is None else (lr.h // down * scale, lr.w // down * scale)
-        writer = Y4MWriter(out_path, rh if size is None else size[1], rw if size is None else size[0], E.out_yuv, lr.fps, out_range, config.yuv_siting)
+        n = lr.length
+        writer = Y4MWriter(out_path, out_hw[0], out_hw[1], E.out_yuv, lr.fps, out_range, config.yuv_siting)
         scores = []
         was_pipelined = bool(getattr(nc, 'pipelined', False))
         net.Network.set_pipelined(True)
@@ -198,25 +210,12 @@ def run(config, lr_path, ref_path, out_path, net=None):
         small = {}                                        # --in_down: frame index -> (lr, ref) down-scaled [3, h / K, w / K] (+ the LR decode)
 
         def down_scaled(wins):
-            """--in_down: the windows as RGB tensors [B, t, 3, h / K, w / K].  A file frame not seen yet goes to the device once, is
-            decoded once at file size and resized once -- the LR and the reference frames of a call together; the LR stream's float32
-            decode stays as the ground truth of --score."""
-            from . import ops
-            for k in [k for k in small if k not in held]:
-                del small[k]
-            new = sorted({i for w_ in wins for i in w_ if i not in small})
-            if new:
-                x = torch.from_numpy(np.stack([held[i][j] for j in (0, 1) for i in new])).to(dev)
-                full = ops.yuv_to_frames(x, lr.h, lr.w, *decode)
-                lo = ops.resize_aa(full, lr.h // down, lr.w // down, 'uint8' if depth_of(lr.fmt) == 8 else 'float32')
-                for q, i in enumerate(new):
-                    small[i] = (lo[q], lo[len(new) + q], full[q] if score_file is not None else None)
-            return tuple(torch.stack([torch.stack([small[i][j] for i in w_]) for w_ in wins]) for j in (0, 1))
+            """--in_down (down_scaled_windows): a file frame not seen yet goes to the device once."""
+            return down_scaled_windows(small, held, wins, lr, down, decode, score_file is not None,
+                                       lambda new: torch.from_numpy(np.stack([held[i][j] for j in (0, 1) for i in new])).to(dev))
 
         if down is not None:
-            r_in = resolve_input(lr.fmt, getattr(config, 'input_yuv_matrix', None), getattr(config, 'input_yuv_range', None),
-                                 getattr(config, 'input_yuv_chroma', None), lr.siting)
-            decode = r_in if len(r_in) == 5 else r_in + ('centre',)          # fmt, matrix, range, chroma, siting of ops.yuv_to_frames
+            decode = decode_args(config, lr)
 
         def detected_groups():
             """The plan under --scene_cut, group by group: the new LR frames of a group and the last one before them go to the device
@@ -290,6 +289,333 @@ def run(config, lr_path, ref_path, out_path, net=None):
             net.Network.set_pipelined(False)
 
 
+IO_MODES = ('sync', 'stream', 'auto')
+
+
+def is_stream_end(p):
+    """An end of the run that is not a regular file: '-', a file object, a FIFO, a device (/dev/null).  A path that does not exist yet
+    is the regular file it will be."""
+    return not isinstance(p, str) or p == '-' or (os.path.exists(p) and not os.path.isfile(p))
+
+
+def io_mode(io, lr_path, ref_path, out_path):
+    """EVAL.io checked and resolved: 'sync' | 'stream'.  'auto' (None: the default) is 'stream' when one of the three ends is no
+    regular file; 'sync' needs three regular files; at most one input can be '-'."""
+    io = io or 'auto'
+    if io not in IO_MODES:
+        raise ValueError('videorun: --io must be one of %s (got %r)' % (', '.join(IO_MODES), io))
+    if lr_path == '-' and ref_path == '-':
+        raise ValueError("videorun: --lr and --ref cannot both be '-': there is one standard input")
+    piped = [p for p in (lr_path, ref_path, out_path) if is_stream_end(p)]
+    if io == 'sync' and piped:
+        raise ValueError('videorun: --io sync reads and writes regular files (%s is none): --io stream, or --io auto' % sink_name(piped[0]))
+    return 'stream' if io == 'stream' or piped else 'sync'
+
+
+def check_io_depth(d):
+    """EVAL.io_depth: the groups in flight in the stream loop, 1..4 (None: 2)."""
+    if d is None:
+        return 2
+    if isinstance(d, bool) or int(d) != d or not 1 <= int(d) <= 4:
+        raise ValueError('videorun: --io_depth must be an integer 1..4 (got %r)' % (d,))
+    return int(d)
+
+
+def check_io_timeout(s):
+    """EVAL.io_timeout: the seconds a source may deliver nothing, or the sink take nothing, before the run ends (None: 120)."""
+    if s is None:
+        return 120.0
+    try:
+        v = float(s)
+    except (TypeError, ValueError):
+        v = float('nan')
+    if not 0.0 < v < float('inf'):
+        raise ValueError('videorun: --io_timeout must be a positive number of seconds (got %r)' % (s,))
+    return v
+
+
+def sample_dtype(fmt):
+    return torch.uint8 if depth_of(fmt) == 8 else torch.uint16
+
+
+def stacked(frames):
+    """torch.stack of device frames of one shape; 16-bit samples are stacked as int16 bit patterns (a plain copy either way)."""
+    if frames[0].dtype != torch.uint16:
+        return torch.stack(frames)
+    return torch.stack([f.view(torch.int16) for f in frames]).view(torch.uint16)
+
+
+def held_bound(t, G, D):
+    """The frames of one input stream the stream loop holds at most, on the device (frame store + the slots of the groups in flight) as
+    in the pinned staging ring: t + (D + 1) G + 2."""
+    return t + (D + 1) * G + 2
+
+
+def run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts):
+    """run() under EVAL.io = 'stream' (module header): the same configure(), plan (scene.GroupPlanner, length unknown), calls and
+    bytes, with reader and writer threads (streamio.py) around the calls and every file frame uploaded once.  All GPU calls are made
+    here, on the caller's thread and current stream; the threads touch pinned host memory and file descriptors only.
+
+    A frame goes from its pinned staging buffer to a device slot of the frame store (non_blocking), the windows of a group are stacked
+    on the device from the store and handed to forward_group with input_ready=None -- the engine's internal streams wait for the
+    caller's stream, which has the copies and the stacking on it, and record the windows for the allocator (INTEGRATION, input_ready).
+    The group's frames are copied to pinned output buffers (non_blocking) with an event behind them; up to EVAL.io_depth groups are
+    in flight, and only the oldest one's event is ever waited for.  Until that event has completed the group keeps what its call was
+    given and what it returned -- the windows, the store slots evicted under it, its staging and output buffers.  At a scene start the
+    groups in flight are retired first: Network.reset() finds the device where the sync loop's reset finds it.
+    Returns (frames written, wall seconds of the loop); config.EVAL.io_stats has the split."""
+    from . import ops, streamio
+    from .yuv import Y4MStreamReader, frame_shape
+    E = config.EVAL
+    D, timeout = check_io_depth(getattr(E, 'io_depth', None)), check_io_timeout(getattr(E, 'io_timeout', None))
+    t, G = int(config.frame_num), max(1, int(getattr(E, 'frame_group', 4) or 1))
+    ring = (D + 1) * G + t // 2                       # D groups in flight and one being read; the first group reads t // 2 ahead
+    assert ring <= held_bound(t, G, D)
+    in_siting = getattr(E, 'in_siting', None)
+    names = [sink_name(p) for p in (lr_path, ref_path)]
+    both = 'videorun: %s and %s' % tuple(names)
+    io = streamio.Run()
+    srcs = [streamio.FrameSource(io, lambda stop, p=p: Y4MStreamReader(p, stop), name, ring, timeout) for p, name in zip((lr_path, ref_path), names)]
+    sink = writer = None
+    was_pipelined, finished = None, False
+    wall0 = time.time()
+    stats = dict(frames=0, uploads=0, groups=0, max_in_flight=0, max_held=0, read_wait=0.0, device_wait=0.0, write_wait=0.0, wall=0.0)
+    try:
+        tens = []                                         # per input: id(numpy view) -> the pinned tensor it views
+
+        def staging(rd):
+            pin = torch.empty((ring,) + frame_shape(rd.h, rd.w, rd.fmt), dtype=sample_dtype(rd.fmt)).pin_memory()
+            views = [pin[i].numpy() for i in range(ring)]
+            tens.append(dict((id(v), pin[i]) for i, v in enumerate(views)))
+            return views
+
+        # each ring goes to its thread as soon as that stream's header is here: the LR thread drains its pipe while the other opens
+        lr = srcs[0].header()
+        if in_siting is not None:
+            lr.siting = effective_siting(lr.fmt, in_siting)
+        srcs[0].provide(staging(lr))
+        ref = srcs[1].header()
+        if in_siting is not None:
+            ref.siting = effective_siting(ref.fmt, in_siting)
+        bad = pair_mismatch(lr, ref)
+        if bad:
+            raise ValueError('%s: %s' % (both, bad))
+        srcs[1].provide(staging(ref))
+        try:
+            cuts = scene.check_cuts(cuts or ())
+        except ValueError as e:
+            raise ValueError('videorun: %s' % (e,))
+        if getattr(E, 'out_range_from_input', False):     # (main(): the output keeps the input's range unless --yuv_range says otherwise)
+            config.yuv_range = lr.range
+        net, dev, t, G, out_range, out_hw = prepare(config, lr, net)
+        nc = net.Network.config
+        down, size, score_file = E.in_down, E.out_size, E.score_file
+        decode = decode_args(config, lr) if down is not None else None
+        writer = Y4MWriter(out_path, out_hw[0], out_hw[1], E.out_yuv, lr.fps, out_range, config.yuv_siting)
+        out_pin = torch.empty(((D + 1) * G,) + frame_shape(out_hw[0], out_hw[1], E.out_yuv),
+                              dtype=sample_dtype(E.out_yuv)).pin_memory()
+        out_views = [out_pin[i].numpy() for i in range(out_pin.shape[0])]
+        out_tens = dict((id(v), out_pin[i]) for i, v in enumerate(out_views))
+        sink = streamio.FrameSink(io, writer, out_views, sink_name(out_path), timeout)
+        was_pipelined = bool(getattr(nc, 'pipelined', False))
+        net.Network.set_pipelined(True)
+        net.Network.reset()
+
+        planner = scene.GroupPlanner(None, t, G)
+        det = scene.SceneDetector(lr.h, lr.w, depth_of(lr.fmt), threshold) if threshold is not None else None
+        cutset = set(cuts)
+        store = collections.OrderedDict()                 # frame index -> (lr slot, ref slot) on the device: what the next windows read
+        small = {}                                        # --in_down: frame index -> (lr, ref) down-scaled (+ the LR decode), as in run()
+        flight = collections.deque()                      # the groups in flight, oldest first
+        staged = []                                       # staging buffers uploaded since the last call: (source, buffer)
+        scores = []
+        nread, ended = 0, False
+
+        def retire():
+            """The oldest group in flight: wait for its event, hand its frames to the sink, give its staging buffers back."""
+            g = flight.popleft()
+            t0 = time.time()
+            g['event'].synchronize()
+            stats['device_wait'] += time.time() - t0
+            if g['scores'] is not None:
+                scores.extend((f, metrics.psnr_from_mse(m), s_) for f, (m, s_) in zip(g['fs'], g['scores'].tolist()))
+            for src, b in g['staged']:
+                src.give(b)
+            for b in g['out']:
+                sink.put(b)
+            stats['frames'] += len(g['out'])
+
+        def read_to(upto):
+            """Frames [nread, upto) of both streams, as far as they go, into the store -- ONE upload per file frame -- and classified."""
+            nonlocal nread, ended
+            new = []
+            while not ended and nread < upto:
+                pair = streamio.next_pair(srcs[0], srcs[1])
+                if pair is None:
+                    ended = True
+                    break
+                slots = []
+                for j, (_, b) in enumerate(pair):
+                    slots.append(tens[j][id(b)].to(dev, non_blocking=True, copy=True))
+                    staged.append((srcs[j], b))
+                store[nread] = tuple(slots)
+                stats['uploads'] += 2
+                new.append(nread)
+                nread += 1
+            if det is None:
+                for k in new:
+                    planner.push(k in cutset)
+            else:
+                if new and new[0] == 0:
+                    planner.push(False)                   # (frame 0 opens the first scene)
+                pairs = [k for k in new if k > 0]
+                if pairs:                                 # one ops.luma_sad call on the store's slots: no upload of its own
+                    t0 = time.time()
+                    sads = ops.luma_sad([store[k][0] for k in pairs], [store[k - 1][0] for k in pairs], lr.h, lr.w, lr.fmt).cpu().tolist()
+                    stats['device_wait'] += time.time() - t0
+                    for sad in sads:
+                        planner.push(det.push(sad))
+            if ended:
+                if nread == 0:
+                    raise ValueError('%s: no frames' % both)
+                try:
+                    scene.check_cuts(cuts, nread)
+                except ValueError as e:
+                    raise ValueError('videorun: %s (%d frames)' % (e, nread))
+                planner.finish()
+
+        def down_scaled(wins):
+            """--in_down (down_scaled_windows), from the store: no upload of its own."""
+            return down_scaled_windows(small, store, wins, lr, down, decode, score_file is not None,
+                                       lambda new: stacked([store[i][j] for j in (0, 1) for i in new]))
+
+        with torch.no_grad():
+            while True:
+                if len(flight) >= D:
+                    retire()
+                if not ended:
+                    read_to(planner.need())
+                group = planner.pop()
+                if group is None:
+                    assert planner.done()
+                    break
+                fs, wins, first = group
+                held = [store.pop(k) for k in [k for k in store if k < min(wins[0])]]     # below the oldest window still to come
+                stats['max_held'] = max(stats['max_held'], len(store) + len(held) + sum(len(g['held']) for g in flight))
+                if first and fs[0] > 0:                   # a scene is a clip of its own: the state of the last one ends here
+                    while flight:
+                        retire()
+                    net.Network.reset()
+                if down is None:
+                    lrs, rfs = (stacked([store[i][j] for w_ in wins for i in w_]).unflatten(0, (len(wins), t)) for j in (0, 1))
+                else:
+                    lrs, rfs = down_scaled(wins)
+                got = net.Network.forward_group(lrs, rfs, wins, is_first_frame=first)
+                sc = None
+                if score_file is not None:                # (the unscaled result against the LR file frame: one 16-byte row per frame)
+                    sc_d = ops.score_frames([r[0] for r in got['result']], [small[f][2] for f in fs])
+                    sc = torch.empty(sc_d.shape, dtype=sc_d.dtype).pin_memory()
+                    sc.copy_(sc_d, non_blocking=True)
+                if size is None:
+                    ys = [y[0] for y in got['yuv']]
+                else:
+                    ys = resized_yuv(ops, [r[0] for r in got['result']], size, E.out_yuv, getattr(config, 'yuv_matrix', None) or 'bt709', out_range,
+                                     config.yuv_siting)
+                out = []
+                for y in ys:
+                    out.append(sink.take())
+                    out_tens[id(out[-1])].copy_(y, non_blocking=True)
+                event = torch.cuda.Event()
+                event.record()
+                flight.append(dict(event=event, fs=fs, out=out, staged=staged, held=held, scores=sc, keep=(lrs, rfs, got, ys)))
+                staged = []
+                stats['groups'] += 1
+                stats['max_in_flight'] = max(stats['max_in_flight'], len(flight))
+            while flight:
+                retire()
+            sink.finish()
+        config.EVAL.scene_cuts = tuple(det.cuts) if det is not None else tuple(cuts)
+        if score_file is not None:
+            config.EVAL.scores = scores
+            write_scores(score_file, scores)
+        finished = True
+        return writer.frames, time.time() - wall0
+    finally:
+        # no device work pending, no thread alive, whatever happened; the first error stays the one that is raised
+        try:
+            if was_pipelined is not None:
+                torch.cuda.synchronize()
+        finally:
+            for x in srcs + ([sink] if sink is not None else []):
+                x.close()
+            stats['read_wait'] = sum(s.waited for s in srcs)
+            stats['write_wait'] = sink.waited if sink is not None else 0.0
+            stats['wall'] = time.time() - wall0
+            config.EVAL.io_stats = stats
+            try:
+                if writer is not None:
+                    writer.close()
+            except ValueError:
+                if finished:                              # (behind an earlier error that one is the one to raise)
+                    raise
+            finally:
+                if was_pipelined is False:
+                    net.Network.set_pipelined(False)
+
+
+def prepare(config, lr, net=None):
+    """What both loops do between the LR header and the first frame: configure(), the network (built here unless passed in) with the
+    run's formats in its config, the refusals of a network that already runs otherwise.  Returns (net, device, t, G, the output's
+    range, the output's (h, w))."""
+    E = config.EVAL
+    configure(config, lr)
+    if net is None:
+        from . import SRNet
+        net = SRNet(config).to('cuda').eval()
+        if config.EVAL.ckpt_abs_name:
+            load_checkpoint(net, config.EVAL.ckpt_abs_name)
+    nc = net.Network.config
+    if nc is not config:                              # (a caller's net may carry a config of its own)
+        for k in ('input_yuv', 'input_yuv_range', 'input_yuv_siting', 'result_yuv', 'yuv_siting'):
+            setattr(nc, k, getattr(config, k))
+    down, size = E.in_down, E.out_size
+    if net.Network._engines and (net.Network._engines[0].input_yuv is None) != (down is not None):
+        raise RuntimeError('videorun: the network passed in already runs %s config.input_yuv; pass a fresh one' % ('with' if down else 'without'))
+    if net.Network._engines and size is not None and net.Network._engines[0].result_yuv is not None:
+        raise RuntimeError('videorun: the network passed in already runs with config.result_yuv; pass a fresh one')
+    dev = next(net.parameters()).device
+    t, G = int(config.frame_num), max(1, int(getattr(config.EVAL, 'frame_group', 4) or 1))
+    scale = int(config.scale)
+    out_range = getattr(config, 'yuv_range', None) or 'limited'
+    rh, rw = (lr.h * scale, lr.w * scale) if down is None else (lr.h // down * scale, lr.w // down * scale)
+    return net, dev, t, G, out_range, ((rh, rw) if size is None else (size[1], size[0]))
+
+
+def decode_args(config, lr):
+    """--in_down: fmt, matrix, range, chroma, siting of ops.yuv_to_frames for the files' frames."""
+    r_in = resolve_input(lr.fmt, getattr(config, 'input_yuv_matrix', None), getattr(config, 'input_yuv_range', None),
+                         getattr(config, 'input_yuv_chroma', None), lr.siting)
+    return r_in if len(r_in) == 5 else r_in + ('centre',)
+
+
+def down_scaled_windows(small, held, wins, lr, down, decode, keep_full, load):
+    """--in_down: the windows as RGB tensors [B, t, 3, h / K, w / K].  small: frame index -> (lr, ref) down-scaled (+ the LR decode
+    under keep_full: the ground truth of --score), kept for the frames in `held` (the frames the run still holds).  A file frame not
+    in it yet is decoded once at file size (ops.yuv_to_frames) and resized once (ops.resize_aa: uint8 from 8-bit files, float32 from
+    10-bit ones) -- the LR and the reference frames of a call together; load(new) -> their buffers on the device, [2 len(new), rows,
+    w], the LR frames first."""
+    from . import ops
+    for k in [k for k in small if k not in held]:
+        del small[k]
+    new = sorted({i for w_ in wins for i in w_ if i not in small})
+    if new:
+        full = ops.yuv_to_frames(load(new), lr.h, lr.w, *decode)
+        lo = ops.resize_aa(full, lr.h // down, lr.w // down, 'uint8' if depth_of(lr.fmt) == 8 else 'float32')
+        for q, i in enumerate(new):
+            small[i] = (lo[q], lo[len(new) + q], full[q] if keep_full else None)
+    return tuple(torch.stack([torch.stack([small[i][j] for i in w_]) for w_ in wins]) for j in (0, 1))
+
+
 def resized_yuv(ops, results, size, fmt, matrix, range, siting):
     """--out_size: results [3, sh, sw] -> [B, rows, W] frames of `fmt` at size = (W, H): ops.resize_aa (clamped float32), then
     ops.result_to_yuv -- one launch each per group."""
@@ -341,6 +667,13 @@ def build_config(argv=None):
     ap.add_argument('--out_size', type=str, default=None, metavar='WxH',
                     help='write the result at W x H (even; at least an eighth of the result per axis, up-scaling allowed) through the '
                          'antialiased bicubic instead of at scale x input')
+    ap.add_argument('--io', default='auto', choices=list(IO_MODES),
+                    help="sync: read, run and write one after the other (regular files).  stream: reader and writer threads around the "
+                         "network calls, every file frame uploaded once; --lr or --ref (one of them) and --out may be '-' or a FIFO.  "
+                         "auto (default): stream when --lr, --ref or --out is '-' or no regular file, else sync")
+    ap.add_argument('--io_depth', type=int, default=2, metavar='D', help='--io stream: frame groups in flight, 1..4 (default 2)')
+    ap.add_argument('--io_timeout', type=float, default=120.0, metavar='S',
+                    help='--io stream: seconds an input may deliver nothing, or the output take nothing, before the run ends (default 120)')
     args = ap.parse_args(argv)
     if args.scene_cut is not None and args.cuts is not None:
         raise ValueError('videorun: --scene_cut and --cuts exclude each other')
@@ -368,18 +701,32 @@ def build_config(argv=None):
     E.in_down, E.score_file, E.out_size = check_in_down(args.in_down), args.score, check_out_size(args.out_size)
     if E.score_file is not None and E.in_down != int(cfg.scale):
         raise ValueError('videorun: --score needs --in_down %d, the scale of the config (got --in_down %s)' % (int(cfg.scale), E.in_down))
+    E.io_depth, E.io_timeout = check_io_depth(args.io_depth), check_io_timeout(args.io_timeout)
+    E.io = io_mode(args.io, args.lr, args.ref, args.out)
     cfg.device, cfg.cuda = 'cuda', True
     return cfg, args
 
 
 def main(argv=None):
     cfg, args = build_config(argv)
-    if not cfg.EVAL.input_range_set:
+    if cfg.EVAL.io == 'stream':
+        cfg.EVAL.out_range_from_input = not cfg.EVAL.input_range_set          # (the header is read once: by the reader run() opens)
+    elif not cfg.EVAL.input_range_set:
         with Y4MReader(args.lr) as rd:
             cfg.yuv_range = rd.range              # (the output keeps the input's range unless --yuv_range says otherwise)
-    frames, seconds = run(cfg, args.lr, args.ref, args.out)
+    if args.out == '-':                           # the frames own stdout: whatever the run prints goes to stderr
+        import contextlib
+        with contextlib.redirect_stdout(sys.stderr):
+            frames, seconds = run(cfg, args.lr, args.ref, sys.__stdout__.buffer)
+    else:
+        frames, seconds = run(cfg, args.lr, args.ref, args.out)
     scenes = '' if cfg.EVAL.scene_cut is None and cfg.EVAL.cuts is None else ', %d scenes' % (len(cfg.EVAL.scene_cuts) + 1)
-    print('[VIDEO %s] %d frames -> %s (%.5f sec / frame%s)' % (args.config, frames, args.out, seconds / max(frames, 1), scenes))
+    line = '[VIDEO %s] %d frames -> %s (%.5f sec / frame%s)' % (args.config, frames, args.out, seconds / max(frames, 1), scenes)
+    if cfg.EVAL.io == 'stream':
+        st = cfg.EVAL.io_stats
+        line += ' [stream: the whole loop; waits %.3f s read, %.3f s device, %.3f s write; %d uploads, %d groups, %d in flight]' % (
+            st['read_wait'], st['device_wait'], st['write_wait'], st['uploads'], st['groups'], st['max_in_flight'])
+    print(line, file=sys.stderr if args.out == '-' else sys.stdout)           # (with --out - the frames own stdout)
     return 0 if frames else 1
 
 

@@ -61,7 +61,10 @@ Y4M: the C tag names sampling, depth and, for 4:2:0, the siting (420jpeg = 420 =
 defines 4:2:2 as co-sited); what a tag cannot say (420p10 left, 422 centre) is an XCHROMASITING=LEFT | CENTRE token, which the writer
 adds and the reader honours.  Top-left siting (420paldv), mono and interlaced files are refused by name.
 """
+import io
 import os
+import select
+import sys
 
 import numpy as np
 
@@ -424,31 +427,55 @@ def y4m_header(h, w, fmt, fps=(30, 1), range='limited', siting=None):
                                                                         ' XCHROMASITING=%s' % extra if extra else '')).encode('ascii')
 
 
+def sink_name(f):
+    """What messages call a source or a sink: the path, '<stdin>' / '<stdout>' style names of file objects, '-' as it is."""
+    return f if isinstance(f, str) else str(getattr(f, 'name', None) or '<%s>' % type(f).__name__)
+
+
 class Y4MWriter(object):
     """A .y4m file of 'i420' (C420jpeg) or 'i420p10' (C420p10, little-endian samples) frames: the header, then `FRAME\\n` and the
     planes Y, Cb, Cr per frame -- which is the frame's buffer as it lies in memory.  Also 'i422', 'i444' and their 10-bit forms, and
-    a siting (y4m_tag has the tags; None: the sampling's default)."""
+    a siting (y4m_tag has the tags; None: the sampling's default).
+    path: a path, '-' (sys.stdout.buffer) or a binary file object -- a pipe to an encoder; close() flushes and closes only a file
+    opened here.  A sink that went away (BrokenPipeError) is a one-line ValueError naming it."""
 
     def __init__(self, path, h, w, fmt='i420', fps=(30, 1), range='limited', siting=None):
         self.header = y4m_header(h, w, fmt, fps, range, siting)
         self.h, self.w, self.fmt = h, w, fmt
         self.frames = 0
-        self.fh = open(path, 'wb')
-        self.fh.write(self.header)
+        self.name = sink_name(path)
+        self.owned = not (path == '-' or hasattr(path, 'write'))
+        self.fh = open(path, 'wb') if self.owned else sys.stdout.buffer if path == '-' else path
+        try:
+            self._put(self.header)
+        except Exception:
+            self.fh, fh = None, self.fh
+            if self.owned:
+                fh.close()
+            raise
+
+    def _put(self, *parts):
+        try:
+            for p in parts:
+                self.fh.write(p)
+        except BrokenPipeError:
+            raise ValueError('%s: the sink closed the pipe behind frame %d' % (self.name, self.frames))
 
     def write(self, buf):
         a = np.asarray(buf)
         if a.shape != frame_shape(self.h, self.w, self.fmt) or a.dtype != dtype_of(self.fmt):
             raise ValueError('Y4MWriter: %s frames are %s %s (got %s %s)' % (self.fmt, np.dtype(dtype_of(self.fmt)).name,
                                                                           frame_shape(self.h, self.w, self.fmt), a.dtype, a.shape))
-        self.fh.write(b'FRAME\n')
-        self.fh.write(np.ascontiguousarray(a).astype(a.dtype.newbyteorder('<'), copy=False).tobytes())
+        self._put(b'FRAME\n', np.ascontiguousarray(a).astype(a.dtype.newbyteorder('<'), copy=False).tobytes())
         self.frames += 1
 
     def close(self):
         if self.fh is not None:
-            self.fh.close()
-            self.fh = None
+            fh, self.fh = self.fh, None
+            try:
+                fh.close() if self.owned else fh.flush()
+            except BrokenPipeError:
+                raise ValueError('%s: the sink closed the pipe behind frame %d' % (self.name, self.frames))
 
     def __enter__(self):
         return self
@@ -534,6 +561,143 @@ class Y4MReader(object):
         if self.fh is not None:
             self.fh.close()
             self.fh = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class StreamStopped(Exception):
+    """Y4MStreamReader: its `stop` event was set while it waited for data."""
+
+
+class Y4MStreamReader(object):
+    """A Y4M stream read strictly front to back -- a pipe from a decoder: no seek, no stat, so `length` is None and the end shows
+    when it comes.  source: a path (a regular file or a FIFO; opened unbuffered), '-' (sys.stdin.buffer) or a binary file object.
+    The attributes of Y4MReader (h, w, fps, fmt, range, siting, frames); read() returns the next frame buffer or None at a clean end
+    of the stream, readinto(buf) fills a caller's writable, C-contiguous array of the frame's shape and dtype (a pinned staging buffer)
+    and returns True, or False at the end.  Every read loops over short reads: a pipe delivers what is there.  A frame marker is a
+    line -- `FRAME`, optional space-separated parameters, `\\n`, at most 80 bytes; a stream that ends inside a frame raises
+    ValueError('..: truncated frame k').  The header goes through parse_y4m_header: what Y4MReader refuses is refused here, in the
+    same words.
+    stop (None, or an object with is_set(): a threading.Event): where the source is an unbuffered descriptor (a path, '-', a raw
+    file object), a wait for data ends with StreamStopped within 0.1 s of the event -- a reader thread can always be ended."""
+
+    length = None
+
+    def __init__(self, source, stop=None):
+        self.path = sink_name(source)
+        self.stop = stop
+        self.owned = isinstance(source, str) and source != '-'
+        if self.owned:
+            self.fh = open(source, 'rb', buffering=0)
+        elif source == '-':
+            self.fh = getattr(sys.stdin.buffer, 'raw', sys.stdin.buffer)       # (nothing is buffered yet when a run starts)
+        else:
+            self.fh = source
+        self._fd = None
+        if isinstance(self.fh, io.RawIOBase):                                   # unbuffered: the descriptor says whether data waits
+            try:
+                self._fd = self.fh.fileno()
+            except (OSError, ValueError, AttributeError):
+                self._fd = None
+        self.frames = 0
+        try:
+            line = bytearray()
+            while not line.endswith(b'\n') and len(line) < 4096:                # byte by byte: nothing behind the newline is taken
+                c = self._some(1)
+                if not c:
+                    break
+                line += c
+            if not line.endswith(b'\n'):
+                raise ValueError('%s: not a YUV4MPEG2 file' % self.path)
+            hd = parse_y4m_header(bytes(line[:-1]), self.path)
+        except Exception:
+            self.close()
+            raise
+        self.h, self.w, self.fps, self.fmt, self.range, self.siting = hd['h'], hd['w'], hd['fps'], hd['fmt'], hd['range'], hd['siting']
+
+    def _wait(self):
+        if self._fd is not None and self.stop is not None:
+            while not select.select([self._fd], [], [], 0.1)[0]:
+                if self.stop.is_set():
+                    raise StreamStopped(self.path)
+
+    def _some(self, n):
+        """Up to n bytes, b'' at the end of the stream."""
+        while True:
+            self._wait()
+            got = self.fh.read(n)
+            if got is not None:                                                 # (None: a non-blocking descriptor without data)
+                return got
+
+    def _fill(self, view):
+        """Reads until `view` (a byte memoryview) is full; the bytes read -- less than len(view) only at the end of the stream."""
+        pos, into = 0, getattr(self.fh, 'readinto', None)
+        while pos < len(view):
+            self._wait()
+            if into is not None:
+                k = into(view[pos:])
+            else:
+                got = self.fh.read(len(view) - pos)
+                k = None if got is None else len(got)
+                if k:
+                    view[pos:pos + k] = got
+            if k is None:
+                continue
+            if k == 0:
+                break
+            pos += k
+        return pos
+
+    def _marker(self):
+        """The FRAME line of the next frame: True, or False at a clean end of the stream."""
+        mark = bytearray(6)
+        k = self._fill(memoryview(mark))
+        if k == 0:
+            return False
+        bad = k < 6 or bytes(mark[:5]) != b'FRAME' or mark[5:6] not in (b'\n', b' ')
+        while not bad and not mark.endswith(b'\n'):                             # parameters: to the end of the line
+            c = self._some(1)
+            mark += c
+            bad = not c or len(mark) > 80
+        if bad:
+            raise ValueError('%s: FRAME marker expected before frame %d' % (self.path, self.frames))
+        return True
+
+    def readinto(self, buf):
+        shape, dt = frame_shape(self.h, self.w, self.fmt), np.dtype(dtype_of(self.fmt))
+        if not isinstance(buf, np.ndarray) or buf.shape != shape or buf.dtype != dt or not buf.flags.c_contiguous or not buf.flags.writeable:
+            raise ValueError('%s: readinto needs a writable, contiguous %s array of shape %s (got %s)' % (
+                self.path, dt.name, shape, '%s %s' % (buf.dtype, buf.shape) if isinstance(buf, np.ndarray) else type(buf).__name__))
+        if not self._marker():
+            return False
+        view = memoryview(buf).cast('B')
+        if self._fill(view) != len(view):
+            raise ValueError('%s: truncated frame %d' % (self.path, self.frames))
+        if sys.byteorder == 'big' and dt.itemsize > 1:                          # (the stream's samples are little-endian)
+            buf.byteswap(True)
+        self.frames += 1
+        return True
+
+    def read(self):
+        buf = np.empty(frame_shape(self.h, self.w, self.fmt), dtype_of(self.fmt))
+        return buf if self.readinto(buf) else None
+
+    def __iter__(self):
+        while True:
+            f = self.read()
+            if f is None:
+                return
+            yield f
+
+    def close(self):
+        if self.fh is not None:
+            fh, self.fh = self.fh, None
+            if self.owned:
+                fh.close()
 
     def __enter__(self):
         return self
