@@ -688,9 +688,10 @@ int refvsr_yuv420_to_rgb(const void* const* src, float* const* dst, int nframes,
  *   REFVSR_YUV_SAMPLING_420 it is refvsr_yuv420_bytes.
  * refvsr_result_to_yuv: refvsr_result_to_yuv420 with a sampling and a siting -- its arguments, limits (REFVSR_YUV420_MAX_FRAMES
  *   frames, ONE launch) and checks, dst of refvsr_yuv_frame_bytes(h, w, yuv_fmt, sampling) bytes each.  With 4:2:0 / centre it IS
- *   refvsr_result_to_yuv420 (the same kernels, the same bits).
+ *   refvsr_result_to_yuv420: one checked launch stands behind both symbols, the same kernel instance runs, and a refusal carries
+ *   that entry's name.
  * refvsr_yuv_to_rgb: refvsr_yuv420_to_rgb with a sampling and a siting -- its arguments, limits (REFVSR_YUV420_IN_MAX_FRAMES frames,
- *   ONE launch) and checks.  With 4:2:0 / centre it IS refvsr_yuv420_to_rgb.
+ *   ONE launch) and checks.  With 4:2:0 / centre it IS refvsr_yuv420_to_rgb, in the same sense.
  *   Both check every argument before any device work, and refuse an unknown sampling or siting and a semi-planar format with a
  *   sampling other than 4:2:0.
  * ------------------------------------------------------------------------------------------ */

@@ -25,7 +25,7 @@
 // reads initialised words only.  The scheme of fingerprint.hip and score.hip.
 //
 // Resource usage (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): the figures next to the kernels.
-#include "common.h"
+#include "yuv_common.h"
 
 #define SN_THREADS 256
 #define SN_VPT 2                              // 16-byte groups of frame a per thread
@@ -154,7 +154,7 @@ __global__ void __launch_bounds__(SN_THREADS) sn_finish_kernel(const uint32_t* _
     if (tid == 0) sad[blockIdx.x] = all;
 }
 
-static bool sn_geometry_ok(int h, int w) { return h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0 && (long)h * w <= (1L << 29); }
+static bool sn_geometry_ok(int h, int w) { return yuv_geometry_ok(h, w) && (long)h * w <= (1L << 29); }
 
 extern "C" int refvsr_scene_max_pairs(void) { return REFVSR_SCENE_MAX_PAIRS; }
 
@@ -170,14 +170,14 @@ extern "C" int refvsr_luma_sad(const void* const* a, const void* const* b, int n
     RV_CHECK(a && b, "luma_sad: null frame table");
     RV_CHECK(npairs >= 1 && npairs <= REFVSR_SCENE_MAX_PAIRS, "luma_sad: 1..%d pairs per call (got %d)", REFVSR_SCENE_MAX_PAIRS, npairs);
     RV_CHECK(sn_geometry_ok(h, w), "luma_sad: h, w must be even and positive, h * w <= 2^29 (got %d x %d)", h, w);
-    RV_CHECK(yuv_fmt >= REFVSR_YUV_NV12 && yuv_fmt <= REFVSR_YUV_I420P10, "luma_sad: unknown yuv format %d", yuv_fmt);
+    RV_CHECK(yuv_fmt_ok(yuv_fmt), "luma_sad: unknown yuv format %d", yuv_fmt);
     RV_CHECK(workspace && sad, "luma_sad: null workspace / sad");
     RV_CHECK(((uintptr_t)workspace & 15) == 0, "luma_sad: workspace must be 16-byte aligned");
     RV_CHECK(((uintptr_t)sad & 7) == 0, "luma_sad: sad must be 8-byte aligned");
     const size_t needed = refvsr_luma_sad_workspace_bytes(npairs, h, w);
     RV_CHECK(workspace_bytes >= needed, "luma_sad: workspace too small (%zu bytes, %zu needed)", workspace_bytes, needed);
-    const bool d10 = yuv_fmt == REFVSR_YUV_P010 || yuv_fmt == REFVSR_YUV_I420P10;
-    const uintptr_t smask = d10 ? 1 : 0;
+    const bool d10 = yuv_d10(yuv_fmt);
+    const uintptr_t smask = yuv_sample_bytes(yuv_fmt) - 1;
     SceneArgs g;
     memset(&g, 0, sizeof(g));
     for (int i = 0; i < npairs; ++i) {

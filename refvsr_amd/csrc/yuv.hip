@@ -1,24 +1,37 @@
-// Y'CbCr 4:2:0 result frames (extension: the reference's consumer writes PNG / JPG from the RGB result, evaluation/
-// eval_qual_quan.py:117-119; a video consumer converts that RGB to 4:2:0 on the CPU first).  refvsr_result_to_yuv420 turns up to
+// Y'CbCr result frames (extension: the reference's consumer writes PNG / JPG from the RGB result, evaluation/eval_qual_quan.py:117-119;
+// a video consumer converts that RGB to 4:2:0, 4:2:2 or 4:4:4 on the CPU first).  refvsr_result_to_yuv turns up to
 // REFVSR_YUV420_MAX_FRAMES result frames of one geometry -- any of the six forms the output head stores, float32 | float16 | uint8,
-// planar or interleaved -- into NV12 | I420 | P010 | I420P10 buffers in one launch.
+// planar or interleaved -- into frames of one format, sampling and siting in one launch; refvsr_result_to_yuv420 is its 4:2:0 /
+// centre form: NV12 | I420 | P010 | I420P10 buffers.  ONE kernel template, an instance per (source, format, sampling, siting).
 //
-// Exactness: the kernel returns the bits of refvsr_amd/yuv.py:rgb_to_yuv420.  Everything is float64 with every operation rounded on
-// its own: contraction is OFF for this file (one fused multiply-add moves rint at a tie).  A byte u is the float64 quotient u / 255.0
+// Exactness: the kernel returns the bits of refvsr_amd/yuv.py:rgb_to_yuv.  Everything is float64 with every operation rounded on its
+// own: contraction is OFF for this file (one fused multiply-add moves rint at a tie).  A byte u is the float64 quotient u / 255.0
 // (a 256-entry LDS table filled by that division), a float widens exactly.
 //
-// Shape: bandwidth-bound, no reuse.  A thread owns NPX pixels of two source rows (NPX / 2 chroma blocks): 16 pixels of a byte source,
-// 8 of a float one.  Whole, aligned groups load 16 bytes at a time from each row (planar: from each plane and row) and store the
-// group's Y row pieces and chroma as one vector each.  A ragged row end goes element by element.  So does a source row's load when
-// its address (planar: any of its three planes' addresses) misses 16 bytes -- each of the two rows decides for itself -- and so do
-// the group's stores when any of them (two Y row pieces, the chroma piece or pieces) misses min(16, the piece's bytes): the stores
+// Shape: bandwidth-bound, no reuse.  A thread owns NPX pixels of ROWS source rows (two for 4:2:0, one for 4:2:2 / 4:4:4): 16 pixels
+// of a byte source, 8 of a float one.  Whole, aligned groups load 16 bytes at a time from each row (planar: from each plane and row)
+// and store the group's Y row pieces and chroma as one vector each.  A ragged row end goes element by element.  So does a source
+// row's load when its address (planar: any of its three planes' addresses) misses 16 bytes -- each row decides for itself -- and so
+// do the group's stores when any of them (the Y row pieces, the chroma piece or pieces) misses min(16, the piece's bytes): the stores
 // decide together, because one branch per store costs 1.5 x the registers (140 -> 229 VGPRs for byte sources) on the path every
 // real frame takes.  A frame whose row pitches, source and destination, are multiples of 16 bytes on 16-byte bases (every result
 // of the engine at 1080p / 8K) is all vectors; float32 rows of w = 2 (mod 4) load every even row wide and every odd row by element
 // and store by element.  Grid-stride over the frame's groups, sized to the stream's CUs; blockIdx.y is the frame.  Plain vector
 // stores only.
+//
+// The mean one chroma sample stands for, e = ecb | ecr unquantised:
+//   4:4:4          e
+//   4:2:2 centre   (e[2j] + e[2j+1]) 0.5
+//   4:2:0 centre   ((e00 + e01) + (e10 + e11)) 0.25: the first row's pair sum, then + the second row's.  NOT the column sums below:
+//                  that is another float64 function and moves ties
+//   left           the odd column LEFT of the pair joins: m = ((v[l] + v[2j+1]) + (v[2j] + v[2j])) scale, l = max(2j - 1, 0), v = e
+//                  (4:2:2, scale 0.25) or the sum of the pair's two rows (4:2:0, 0.125).  Inside a group that column is the pair
+//                  before; for the group's first pair it is the pixel in front of the group, x0 - 1 of the same rows -- another
+//                  thread's, or another workgroup's, pixel -- which the thread loads for itself (three samples per row, element by
+//                  element, from the cache line its neighbour reads) and converts again.  The first group of a row has no such
+//                  pixel: l = 0, the pair's own even column.
 #pragma clang fp contract(off)
-#include "common.h"
+#include "yuv_common.h"
 
 struct YuvArgs {
     const void* src[REFVSR_YUV420_MAX_FRAMES];
@@ -60,211 +73,18 @@ __device__ __forceinline__ S yuv_code(double v, double maxc) {
     return (S)((unsigned)(int)c << SHIFT);
 }
 
-template <typename T, bool HWC, int FMT>
-__global__ void __launch_bounds__(256) yuv420_kernel(YuvArgs a) {
-    constexpr int NPX = YuvSrc<T>::NPX;
-    constexpr bool D10 = FMT == REFVSR_YUV_P010 || FMT == REFVSR_YUV_I420P10;
-    constexpr bool SEMI = FMT == REFVSR_YUV_NV12 || FMT == REFVSR_YUV_P010;
-    constexpr int SHIFT = FMT == REFVSR_YUV_P010 ? 6 : 0;
-    using S = typename std::conditional<D10, uint16_t, uint8_t>::type;
-    constexpr int SRC_BYTES = NPX * (int)sizeof(T);                  // one plane's piece of a row; interleaved: three of them
-    constexpr int ROW_BYTES = NPX * (int)sizeof(S);                  // a Y row piece, and the interleaved chroma of the group
-    constexpr int PLANE_BYTES = ROW_BYTES / 2;                       // a Cb or Cr piece of the planar formats
-    constexpr uintptr_t ROW_MASK = (ROW_BYTES < 16 ? ROW_BYTES : 16) - 1, PLANE_MASK = (PLANE_BYTES < 16 ? PLANE_BYTES : 16) - 1;
-    constexpr bool U8 = std::is_same<T, unsigned char>::value;
-    __shared__ double tbl[U8 ? 256 : 1];
-    if constexpr (U8) {
-        for (int i = threadIdx.x; i < 256; i += blockDim.x) tbl[i] = (double)i / 255.0;
-        __syncthreads();
-    }
-    const T* __restrict__ src = reinterpret_cast<const T*>(a.src[blockIdx.y]);
-    S* __restrict__ dst = reinterpret_cast<S*>(a.dst[blockIdx.y]);
-    const int h = a.h, w = a.w, w2 = w >> 1;
-    const long hw = (long)h * w;
-    const double kr = a.k[0], kg = a.k[1], kb = a.k[2], icb = a.k[3], icr = a.k[4], oy = a.k[5], sy = a.k[6], oc = a.k[7], sc = a.k[8];
-    const double maxc = D10 ? 1023.0 : 255.0;
-    const int gpr = (w + NPX - 1) / NPX;                             // groups per row pair
-    const long items = (long)(h >> 1) * gpr;
-    for (long k = blockIdx.x * (long)blockDim.x + threadIdx.x; k < items; k += (long)gridDim.x * blockDim.x) {
-        const int by = (int)(k / gpr);
-        const int x0 = (int)(k - (long)by * gpr) * NPX;
-        const int n = w - x0 < NPX ? w - x0 : NPX;                   // pixels of the group per row (even)
-        const long p0 = (long)(2 * by) * w + x0;                     // the group's first pixel; the second row's is p0 + w
-        S* const y0 = dst + p0;
-        S* const c0 = dst + hw + (SEMI ? (long)by * w + x0 : (long)by * w2 + (x0 >> 1));       // interleaved CbCr, or Cb
-        S* const c1 = c0 + (hw >> 2);                                                         // Cr of the planar formats
-
-        // A whole group (n == NPX) loads a row as vectors where that row's addresses are 16-byte aligned, each row for itself, and
-        // stores as vectors where all of its store addresses are aligned (the header comment has the cases and the reason).
-        const bool full = n == NPX;
-        alignas(16) T v[2][3][NPX];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const long pr = p0 + (long)r * w;
-            uintptr_t mis;
-            if constexpr (HWC) mis = (uintptr_t)(src + 3 * pr) & 15;
-            else mis = ((uintptr_t)(src + pr) | (uintptr_t)(src + hw + pr) | (uintptr_t)(src + 2 * hw + pr)) & 15;
-            if (full && mis == 0) {
-                if constexpr (HWC) {
-                    alignas(16) T t[3 * NPX];
-                    yuv_load<3 * SRC_BYTES>(src + 3 * pr, t);
-#pragma unroll
-                    for (int i = 0; i < NPX; ++i) { v[r][0][i] = t[3 * i]; v[r][1][i] = t[3 * i + 1]; v[r][2][i] = t[3 * i + 2]; }
-                } else {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) yuv_load<SRC_BYTES>(src + c * hw + pr, v[r][c]);
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-#pragma unroll
-                    for (int i = 0; i < NPX; ++i) v[r][c][i] = i < n ? (HWC ? src[3 * (pr + i) + c] : src[c * hw + pr + i]) : (T)0;
-            }
-        }
-
-        alignas(16) S yy[2][NPX], cc[NPX];                           // cc: Cb Cr pairs (semi-planar), or [Cb piece | Cr piece]
-#pragma unroll
-        for (int j = 0; j < NPX / 2; ++j) {
-            double scb = 0.0, scr = 0.0;
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                double eb[2], er[2];
-#pragma unroll
-                for (int d = 0; d < 2; ++d) {
-                    const int i = 2 * j + d;
-                    const double R = yuv_value(v[r][0][i], tbl), G = yuv_value(v[r][1][i], tbl), B = yuv_value(v[r][2][i], tbl);
-                    const double ey = (kr * R + kg * G) + kb * B;
-                    yy[r][i] = yuv_code<S, SHIFT>(oy + sy * ey, maxc);
-                    eb[d] = (B - ey) * icb;
-                    er[d] = (R - ey) * icr;
-                }
-                // ((e00 + e01) + (e10 + e11)): the first row's pair sum, then + the second row's
-                scb = r == 0 ? eb[0] + eb[1] : scb + (eb[0] + eb[1]);
-                scr = r == 0 ? er[0] + er[1] : scr + (er[0] + er[1]);
-            }
-            const S cb = yuv_code<S, SHIFT>(oc + sc * (scb * 0.25), maxc), cr = yuv_code<S, SHIFT>(oc + sc * (scr * 0.25), maxc);
-            if constexpr (SEMI) { cc[2 * j] = cb; cc[2 * j + 1] = cr; }
-            else { cc[j] = cb; cc[NPX / 2 + j] = cr; }
-        }
-
-        uintptr_t smis = ((uintptr_t)y0 | (uintptr_t)(y0 + w)) & ROW_MASK;
-        smis |= SEMI ? (uintptr_t)c0 & ROW_MASK : ((uintptr_t)c0 | (uintptr_t)c1) & PLANE_MASK;
-        if (full && smis == 0) {
-            yuv_store<ROW_BYTES>(y0, yy[0]);
-            yuv_store<ROW_BYTES>(y0 + w, yy[1]);
-            if constexpr (SEMI) {
-                yuv_store<ROW_BYTES>(c0, cc);
-            } else {
-                yuv_store<PLANE_BYTES>(c0, cc);
-                yuv_store<PLANE_BYTES>(c1, cc + NPX / 2);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NPX; ++i)
-                if (i < n) { y0[i] = yy[0][i]; y0[w + i] = yy[1][i]; }
-#pragma unroll
-            for (int j = 0; j < NPX / 2; ++j)
-                if (2 * j < n) {
-                    if constexpr (SEMI) { c0[2 * j] = cc[2 * j]; c0[2 * j + 1] = cc[2 * j + 1]; }
-                    else { c0[j] = cc[j]; c1[j] = cc[NPX / 2 + j]; }
-                }
-        }
-    }
-}
-
-static inline bool yuv_fmt_ok(int f) { return f >= REFVSR_YUV_NV12 && f <= REFVSR_YUV_I420P10; }
-static inline size_t yuv_sample_bytes(int f) { return f == REFVSR_YUV_P010 || f == REFVSR_YUV_I420P10 ? 2 : 1; }
-
-extern "C" int refvsr_yuv420_max_frames(void) { return REFVSR_YUV420_MAX_FRAMES; }
-
-extern "C" size_t refvsr_yuv420_bytes(int h, int w, int yuv_fmt) {
-    if (h <= 0 || w <= 0 || h % 2 || w % 2 || !yuv_fmt_ok(yuv_fmt)) return 0;
-    return (size_t)h * w / 2 * 3 * yuv_sample_bytes(yuv_fmt);
-}
-
-template <typename T, bool HWC>
-static void yuv_launch(int yuv_fmt, dim3 grid, hipStream_t st, const YuvArgs& a) {
-    switch (yuv_fmt) {
-        case REFVSR_YUV_NV12: hipLaunchKernelGGL((yuv420_kernel<T, HWC, REFVSR_YUV_NV12>), grid, dim3(256), 0, st, a); break;
-        case REFVSR_YUV_I420: hipLaunchKernelGGL((yuv420_kernel<T, HWC, REFVSR_YUV_I420>), grid, dim3(256), 0, st, a); break;
-        case REFVSR_YUV_P010: hipLaunchKernelGGL((yuv420_kernel<T, HWC, REFVSR_YUV_P010>), grid, dim3(256), 0, st, a); break;
-        default: hipLaunchKernelGGL((yuv420_kernel<T, HWC, REFVSR_YUV_I420P10>), grid, dim3(256), 0, st, a); break;
-    }
-}
-
-extern "C" int refvsr_result_to_yuv420(const void* const* src, int src_fmt, void* const* dst, int nframes, int h, int w, int yuv_fmt,
-                                       const double* coef9, void* stream) {
-    RV_CHECK(src && dst, "result_to_yuv420: null frame table");
-    RV_CHECK(coef9, "result_to_yuv420: null coefficients");
-    RV_CHECK(nframes >= 1 && nframes <= REFVSR_YUV420_MAX_FRAMES, "result_to_yuv420: 1..%d frames per launch", REFVSR_YUV420_MAX_FRAMES);
-    RV_CHECK(rv_result_fmt_ok(src_fmt), "result_to_yuv420: unknown result format %d", src_fmt);
-    RV_CHECK(yuv_fmt_ok(yuv_fmt), "result_to_yuv420: unknown yuv format %d", yuv_fmt);
-    RV_CHECK(h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0, "result_to_yuv420: h, w must be even and positive (got %d x %d)", h, w);
-    const int f = src_fmt & REFVSR_RESULT_FMT_MASK;
-    const size_t es = f == REFVSR_RESULT_F32 ? 4 : f == REFVSR_RESULT_F16 ? 2 : 1;
-    RV_CHECK((long long)h * w * 3 * (long long)es < (1ll << 31), "result_to_yuv420: frame too large for 32-bit offsets");
-    const size_t sbytes = (size_t)h * w * 3 * es, dbytes = refvsr_yuv420_bytes(h, w, yuv_fmt);
-    YuvArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int i = 0; i < nframes; ++i) {
-        RV_CHECK(src[i] && dst[i], "result_to_yuv420: null pointer (frame %d)", i);
-        RV_CHECK(((uintptr_t)src[i] & (es - 1)) == 0 && ((uintptr_t)dst[i] & (yuv_sample_bytes(yuv_fmt) - 1)) == 0,
-                 "result_to_yuv420: source and destination must be aligned to their samples (frame %d)", i);
-        a.src[i] = src[i];
-        a.dst[i] = dst[i];
-    }
-    for (int i = 0; i < nframes; ++i) {
-        const uintptr_t d0 = (uintptr_t)dst[i];
-        for (int j = 0; j < nframes; ++j) {
-            const uintptr_t s0 = (uintptr_t)src[j], d1 = (uintptr_t)dst[j];
-            RV_CHECK(d0 + dbytes <= s0 || s0 + sbytes <= d0, "result_to_yuv420: destination %d overlaps source %d", i, j);
-            RV_CHECK(i == j || d0 + dbytes <= d1 || d1 + dbytes <= d0, "result_to_yuv420: destinations %d and %d overlap", i, j);
-        }
-    }
-    a.h = h;
-    a.w = w;
-    for (int i = 0; i < 9; ++i) a.k[i] = coef9[i];
-    hipStream_t st = (hipStream_t)stream;
-    const int npx = f == REFVSR_RESULT_U8 ? YuvSrc<unsigned char>::NPX : YuvSrc<float>::NPX;
-    const long items = (long)(h / 2) * ((w + npx - 1) / npx);
-    const long want = (items + 255) / 256;
-    long cap = (long)rv_stream_cus(st) * 8 / nframes;                // eight workgroups per CU over all frames
-    if (cap < 32) cap = 32;
-    const dim3 grid((unsigned)(want < cap ? want : cap), (unsigned)nframes);
-    const bool hwc = (src_fmt & REFVSR_RESULT_HWC) != 0;
-    if (f == REFVSR_RESULT_F32) hwc ? yuv_launch<float, true>(yuv_fmt, grid, st, a) : yuv_launch<float, false>(yuv_fmt, grid, st, a);
-    else if (f == REFVSR_RESULT_F16) hwc ? yuv_launch<f16, true>(yuv_fmt, grid, st, a) : yuv_launch<f16, false>(yuv_fmt, grid, st, a);
-    else hwc ? yuv_launch<unsigned char, true>(yuv_fmt, grid, st, a) : yuv_launch<unsigned char, false>(yuv_fmt, grid, st, a);
-    RV_LAUNCH_CHECK();
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------------
-// 4:2:2, 4:4:4 and left-sited 4:2:0 (refvsr_result_to_yuv; 4:2:0 / centre stays the kernel above).  Extension, as the file: the same
-// host-side conversion behind evaluation/eval_qual_quan.py:117-119, for the samplings and the siting results are kept in.  The bits
-// of refvsr_amd/yuv.py:rgb_to_yuv.
-//
-// The shape of the kernel above, per sampling: a thread owns NPX pixels of ROWS source rows (two for 4:2:0, one for 4:2:2 / 4:4:4);
-// loads and stores decide about vectors in the same way (each row's load for itself, the group's stores together).  Left siting takes
-// the odd column LEFT of a chroma pair: m = ((v[l] + v[2j+1]) + (v[2j] + v[2j])) scale, l = max(2j - 1, 0), v = e (4:2:2) or the sum
-// of the pair's two rows (4:2:0).  Inside a group that column is the pair before; for the group's first pair it is the pixel in front
-// of the group, x0 - 1 of the same rows -- another thread's, or another workgroup's, pixel -- which the thread loads for itself
-// (three samples per row, element by element, from the cache line its neighbour reads) and converts again.  The first group of a row
-// has no such pixel: l = 0, the pair's own even column.
 template <typename T, bool HWC, int FMT, int SAMP, bool LEFT>
-__global__ void __launch_bounds__(256) yuv_chroma_kernel(YuvArgs a) {
+__global__ void __launch_bounds__(256) yuv_kernel(YuvArgs a) {
     constexpr int NPX = YuvSrc<T>::NPX;
-    constexpr bool D10 = FMT == REFVSR_YUV_P010 || FMT == REFVSR_YUV_I420P10;
-    constexpr bool SEMI = FMT == REFVSR_YUV_NV12 || FMT == REFVSR_YUV_P010;
+    constexpr bool D10 = yuv_d10(FMT), SEMI = yuv_semi(FMT);
     constexpr bool C444 = SAMP == REFVSR_YUV_SAMPLING_444, V2 = SAMP == REFVSR_YUV_SAMPLING_420;
     static_assert(!SEMI || V2, "semi-planar frames are 4:2:0");
     static_assert(!(C444 && LEFT), "4:4:4 has no siting");
-    static_assert(!V2 || LEFT, "4:2:0 / centre is yuv420_kernel");
     constexpr int SHIFT = FMT == REFVSR_YUV_P010 ? 6 : 0;
     constexpr int ROWS = V2 ? 2 : 1;
     constexpr int NC = C444 ? NPX : NPX / 2;                         // chroma samples of the group per plane
     using S = typename std::conditional<D10, uint16_t, uint8_t>::type;
-    constexpr int SRC_BYTES = NPX * (int)sizeof(T);
+    constexpr int SRC_BYTES = NPX * (int)sizeof(T);                  // one plane's piece of a row; interleaved: three of them
     constexpr int ROW_BYTES = NPX * (int)sizeof(S);                  // a Y row piece, and the interleaved chroma of the group
     constexpr int PLANE_BYTES = NC * (int)sizeof(S);                 // a Cb or Cr piece of the planar formats
     constexpr uintptr_t ROW_MASK = (ROW_BYTES < 16 ? ROW_BYTES : 16) - 1, PLANE_MASK = (PLANE_BYTES < 16 ? PLANE_BYTES : 16) - 1;
@@ -279,7 +99,7 @@ __global__ void __launch_bounds__(256) yuv_chroma_kernel(YuvArgs a) {
     S* __restrict__ dst = reinterpret_cast<S*>(a.dst[blockIdx.y]);
     const int h = a.h, w = a.w, w2 = w >> 1;
     const long hw = (long)h * w;
-    const long cplane = C444 ? hw : V2 ? hw >> 2 : hw >> 1;          // samples of a chroma plane
+    const long cplane = yuv_chroma_plane(hw, SAMP);
     const double kr = a.k[0], kg = a.k[1], kb = a.k[2], icb = a.k[3], icr = a.k[4], oy = a.k[5], sy = a.k[6], oc = a.k[7], sc = a.k[8];
     const double maxc = D10 ? 1023.0 : 255.0;
     const int gpr = (w + NPX - 1) / NPX;                             // groups per row (4:2:0: per row pair)
@@ -293,6 +113,8 @@ __global__ void __launch_bounds__(256) yuv_chroma_kernel(YuvArgs a) {
         S* const c0 = dst + hw + (SEMI || C444 ? (long)by * w + x0 : (long)by * w2 + (x0 >> 1));       // interleaved CbCr, or Cb
         S* const c1 = c0 + cplane;                                                                    // Cr of the planar formats
 
+        // A whole group (n == NPX) loads a row as vectors where that row's addresses are 16-byte aligned, each row for itself, and
+        // stores as vectors where all of its store addresses are aligned (the header comment has the cases and the reason).
         const bool full = n == NPX;
         alignas(16) T v[ROWS][3][NPX];
 #pragma unroll
@@ -339,7 +161,7 @@ __global__ void __launch_bounds__(256) yuv_chroma_kernel(YuvArgs a) {
         alignas(16) S yy[ROWS][NPX], cc[2 * NC];                     // cc: Cb Cr pairs (semi-planar), or [Cb piece | Cr piece]
 #pragma unroll
         for (int j = 0; j < NPX / 2; ++j) {
-            double vb[2], vr[2];                                     // v of the pair's even and odd column
+            double vb[2], vr[2];                                     // v of the pair's even and odd column; 4:2:0 / centre: the rows' pair sums
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) {
 #pragma unroll
@@ -349,8 +171,13 @@ __global__ void __launch_bounds__(256) yuv_chroma_kernel(YuvArgs a) {
                     const double ey = (kr * R + kg * G) + kb * B;
                     yy[r][i] = yuv_code<S, SHIFT>(oy + sy * ey, maxc);
                     const double eb = (B - ey) * icb, er = (R - ey) * icr;
-                    vb[d] = r == 0 ? eb : vb[d] + eb;                // 4:2:0: e[2i][x] + e[2i+1][x]
-                    vr[d] = r == 0 ? er : vr[d] + er;
+                    if constexpr (V2 && !LEFT) {                     // e[r][2j] + e[r][2j+1]
+                        vb[r] = d == 0 ? eb : vb[r] + eb;
+                        vr[r] = d == 0 ? er : vr[r] + er;
+                    } else {                                         // 4:2:0: e[2i][x] + e[2i+1][x]
+                        vb[d] = r == 0 ? eb : vb[d] + eb;
+                        vr[d] = r == 0 ? er : vr[d] + er;
+                    }
                 }
             }
             if constexpr (C444) {
@@ -367,9 +194,9 @@ __global__ void __launch_bounds__(256) yuv_chroma_kernel(YuvArgs a) {
                     mr = ((lr + vr[1]) + (vr[0] + vr[0])) * SCALE;
                     lb = vb[1];
                     lr = vr[1];
-                } else {                                             // 4:2:2 centre
-                    mb = (vb[0] + vb[1]) * 0.5;
-                    mr = (vr[0] + vr[1]) * 0.5;
+                } else {                                             // centre: the pair (4:2:2), the two rows' pair sums (4:2:0)
+                    mb = (vb[0] + vb[1]) * (V2 ? 0.25 : 0.5);
+                    mr = (vr[0] + vr[1]) * (V2 ? 0.25 : 0.5);
                 }
                 const S cb = yuv_code<S, SHIFT>(oc + sc * mb, maxc), cr = yuv_code<S, SHIFT>(oc + sc * mr, maxc);
                 if constexpr (SEMI) { cc[2 * j] = cb; cc[2 * j + 1] = cr; }
@@ -390,84 +217,56 @@ __global__ void __launch_bounds__(256) yuv_chroma_kernel(YuvArgs a) {
             }
         } else {
 #pragma unroll
-            for (int r = 0; r < ROWS; ++r)
+            for (int i = 0; i < NPX; ++i)
+                if (i < n) {
 #pragma unroll
-                for (int i = 0; i < NPX; ++i)
-                    if (i < n) y0[r * w + i] = yy[r][i];
-            if constexpr (C444) {
+                    for (int r = 0; r < ROWS; ++r) y0[r * w + i] = yy[r][i];
+                }
 #pragma unroll
-                for (int i = 0; i < NPX; ++i)
-                    if (i < n) { c0[i] = cc[i]; c1[i] = cc[NC + i]; }
-            } else {
-#pragma unroll
-                for (int j = 0; j < NPX / 2; ++j)
-                    if (2 * j < n) {
-                        if constexpr (SEMI) { c0[2 * j] = cc[2 * j]; c0[2 * j + 1] = cc[2 * j + 1]; }
-                        else { c0[j] = cc[j]; c1[j] = cc[NC + j]; }
-                    }
-            }
+            for (int j = 0; j < NC; ++j)
+                if ((C444 ? j : 2 * j) < n) {
+                    if constexpr (SEMI) { c0[2 * j] = cc[2 * j]; c0[2 * j + 1] = cc[2 * j + 1]; }
+                    else { c0[j] = cc[j]; c1[j] = cc[NC + j]; }
+                }
         }
     }
 }
 
-static inline bool yuv_semi(int f) { return f == REFVSR_YUV_NV12 || f == REFVSR_YUV_P010; }
-static inline bool yuv_sampling_ok(int s) { return s >= REFVSR_YUV_SAMPLING_420 && s <= REFVSR_YUV_SAMPLING_444; }
+extern "C" int refvsr_yuv420_max_frames(void) { return REFVSR_YUV420_MAX_FRAMES; }
 
-extern "C" size_t refvsr_yuv_frame_bytes(int h, int w, int yuv_fmt, int sampling) {
-    if (h <= 0 || w <= 0 || h % 2 || w % 2 || !yuv_fmt_ok(yuv_fmt) || !yuv_sampling_ok(sampling)) return 0;
-    if (sampling != REFVSR_YUV_SAMPLING_420 && yuv_semi(yuv_fmt)) return 0;
-    const size_t hw = (size_t)h * w;
-    return (sampling == REFVSR_YUV_SAMPLING_420 ? hw / 2 * 3 : sampling == REFVSR_YUV_SAMPLING_422 ? hw * 2 : hw * 3) * yuv_sample_bytes(yuv_fmt);
-}
+extern "C" size_t refvsr_yuv420_bytes(int h, int w, int yuv_fmt) { return yuv_frame_bytes(h, w, yuv_fmt, REFVSR_YUV_SAMPLING_420); }
+
+extern "C" size_t refvsr_yuv_frame_bytes(int h, int w, int yuv_fmt, int sampling) { return yuv_frame_bytes(h, w, yuv_fmt, sampling); }
 
 template <typename T, bool HWC>
-static void yuv_chroma_launch(int yuv_fmt, int sampling, bool left, dim3 grid, hipStream_t st, const YuvArgs& a) {
-#define YUV_CHROMA_GO(F, S, L) hipLaunchKernelGGL((yuv_chroma_kernel<T, HWC, F, S, L>), grid, dim3(256), 0, st, a)
-    const bool p10 = yuv_fmt == REFVSR_YUV_I420P10;
-    if (sampling == REFVSR_YUV_SAMPLING_420) {                       // left (centre is refvsr_result_to_yuv420)
-        switch (yuv_fmt) {
-            case REFVSR_YUV_NV12: YUV_CHROMA_GO(REFVSR_YUV_NV12, REFVSR_YUV_SAMPLING_420, true); break;
-            case REFVSR_YUV_I420: YUV_CHROMA_GO(REFVSR_YUV_I420, REFVSR_YUV_SAMPLING_420, true); break;
-            case REFVSR_YUV_P010: YUV_CHROMA_GO(REFVSR_YUV_P010, REFVSR_YUV_SAMPLING_420, true); break;
-            default: YUV_CHROMA_GO(REFVSR_YUV_I420P10, REFVSR_YUV_SAMPLING_420, true); break;
-        }
-    } else if (sampling == REFVSR_YUV_SAMPLING_422) {
-        if (left && p10) YUV_CHROMA_GO(REFVSR_YUV_I420P10, REFVSR_YUV_SAMPLING_422, true);
-        else if (left) YUV_CHROMA_GO(REFVSR_YUV_I420, REFVSR_YUV_SAMPLING_422, true);
-        else if (p10) YUV_CHROMA_GO(REFVSR_YUV_I420P10, REFVSR_YUV_SAMPLING_422, false);
-        else YUV_CHROMA_GO(REFVSR_YUV_I420, REFVSR_YUV_SAMPLING_422, false);
-    } else {
-        if (p10) YUV_CHROMA_GO(REFVSR_YUV_I420P10, REFVSR_YUV_SAMPLING_444, false);
-        else YUV_CHROMA_GO(REFVSR_YUV_I420, REFVSR_YUV_SAMPLING_444, false);
-    }
-#undef YUV_CHROMA_GO
+static void yuv_launch(int yuv_fmt, int sampling, bool left, dim3 grid, hipStream_t st, const YuvArgs& a) {
+#define YUV_GO(F, S, L)                                                                           \
+    if (yuv_fmt == REFVSR_YUV_##F && sampling == REFVSR_YUV_SAMPLING_##S && left == L)            \
+        hipLaunchKernelGGL((yuv_kernel<T, HWC, REFVSR_YUV_##F, REFVSR_YUV_SAMPLING_##S, L>), grid, dim3(256), 0, st, a);
+    YUV_INSTANCES(YUV_GO)
+#undef YUV_GO
 }
 
-extern "C" int refvsr_result_to_yuv(const void* const* src, int src_fmt, void* const* dst, int nframes, int h, int w, int yuv_fmt,
-                                    int sampling, int siting, const double* coef9, void* stream) {
-    RV_CHECK(yuv_fmt_ok(yuv_fmt), "result_to_yuv: unknown yuv format %d", yuv_fmt);
-    RV_CHECK(yuv_sampling_ok(sampling), "result_to_yuv: sampling must be REFVSR_YUV_SAMPLING_420 | _422 | _444 (got %d)", sampling);
-    RV_CHECK(siting == REFVSR_YUV_SITING_CENTRE || siting == REFVSR_YUV_SITING_LEFT,
-             "result_to_yuv: siting must be REFVSR_YUV_SITING_CENTRE | REFVSR_YUV_SITING_LEFT (got %d)", siting);
-    RV_CHECK(sampling == REFVSR_YUV_SAMPLING_420 || !yuv_semi(yuv_fmt),
-             "result_to_yuv: semi-planar frames (NV12, P010) are 4:2:0 only (format %d, sampling %d)", yuv_fmt, sampling);
-    if (sampling == REFVSR_YUV_SAMPLING_420 && siting == REFVSR_YUV_SITING_CENTRE)
-        return refvsr_result_to_yuv420(src, src_fmt, dst, nframes, h, w, yuv_fmt, coef9, stream);
-    RV_CHECK(src && dst, "result_to_yuv: null frame table");
-    RV_CHECK(coef9, "result_to_yuv: null coefficients");
-    RV_CHECK(nframes >= 1 && nframes <= REFVSR_YUV420_MAX_FRAMES, "result_to_yuv: 1..%d frames per launch", REFVSR_YUV420_MAX_FRAMES);
-    RV_CHECK(rv_result_fmt_ok(src_fmt), "result_to_yuv: unknown result format %d", src_fmt);
-    RV_CHECK(h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0, "result_to_yuv: h, w must be even and positive (got %d x %d)", h, w);
+// The checked launch of both entries, `name` in front of its messages.  yuv_fmt is checked again where the 4:2:0 entry has always
+// checked it: behind the result format.
+static int yuv_convert(const char* name, const void* const* src, int src_fmt, void* const* dst, int nframes, int h, int w, int yuv_fmt,
+                       int sampling, int siting, const double* coef9, void* stream) {
+    RV_CHECK(src && dst, "%s: null frame table", name);
+    RV_CHECK(coef9, "%s: null coefficients", name);
+    RV_CHECK(nframes >= 1 && nframes <= REFVSR_YUV420_MAX_FRAMES, "%s: 1..%d frames per launch", name, REFVSR_YUV420_MAX_FRAMES);
+    RV_CHECK(rv_result_fmt_ok(src_fmt), "%s: unknown result format %d", name, src_fmt);
+    RV_CHECK(yuv_fmt_ok(yuv_fmt), "%s: unknown yuv format %d", name, yuv_fmt);
+    RV_CHECK(yuv_geometry_ok(h, w), "%s: h, w must be even and positive (got %d x %d)", name, h, w);
     const int f = src_fmt & REFVSR_RESULT_FMT_MASK;
     const size_t es = f == REFVSR_RESULT_F32 ? 4 : f == REFVSR_RESULT_F16 ? 2 : 1;
-    RV_CHECK((long long)h * w * 3 * (long long)es < (1ll << 31), "result_to_yuv: frame too large for 32-bit offsets");
-    const size_t sbytes = (size_t)h * w * 3 * es, dbytes = refvsr_yuv_frame_bytes(h, w, yuv_fmt, sampling);
+    RV_CHECK((long long)h * w * 3 * (long long)es < (1ll << 31), "%s: frame too large for 32-bit offsets", name);
+    const size_t sbytes = (size_t)h * w * 3 * es, dbytes = yuv_frame_bytes(h, w, yuv_fmt, sampling);
     YuvArgs a;
     memset(&a, 0, sizeof(a));
     for (int i = 0; i < nframes; ++i) {
-        RV_CHECK(src[i] && dst[i], "result_to_yuv: null pointer (frame %d)", i);
+        RV_CHECK(src[i] && dst[i], "%s: null pointer (frame %d)", name, i);
         RV_CHECK(((uintptr_t)src[i] & (es - 1)) == 0 && ((uintptr_t)dst[i] & (yuv_sample_bytes(yuv_fmt) - 1)) == 0,
-                 "result_to_yuv: source and destination must be aligned to their samples (frame %d)", i);
+                 "%s: source and destination must be aligned to their samples (frame %d)", name, i);
         a.src[i] = src[i];
         a.dst[i] = dst[i];
     }
@@ -475,8 +274,8 @@ extern "C" int refvsr_result_to_yuv(const void* const* src, int src_fmt, void* c
         const uintptr_t d0 = (uintptr_t)dst[i];
         for (int j = 0; j < nframes; ++j) {
             const uintptr_t s0 = (uintptr_t)src[j], d1 = (uintptr_t)dst[j];
-            RV_CHECK(d0 + dbytes <= s0 || s0 + sbytes <= d0, "result_to_yuv: destination %d overlaps source %d", i, j);
-            RV_CHECK(i == j || d0 + dbytes <= d1 || d1 + dbytes <= d0, "result_to_yuv: destinations %d and %d overlap", i, j);
+            RV_CHECK(d0 + dbytes <= s0 || s0 + sbytes <= d0, "%s: destination %d overlaps source %d", name, i, j);
+            RV_CHECK(i == j || d0 + dbytes <= d1 || d1 + dbytes <= d0, "%s: destinations %d and %d overlap", name, i, j);
         }
     }
     a.h = h;
@@ -490,9 +289,26 @@ extern "C" int refvsr_result_to_yuv(const void* const* src, int src_fmt, void* c
     if (cap < 32) cap = 32;
     const dim3 grid((unsigned)(want < cap ? want : cap), (unsigned)nframes);
     const bool hwc = (src_fmt & REFVSR_RESULT_HWC) != 0, left = siting == REFVSR_YUV_SITING_LEFT && sampling != REFVSR_YUV_SAMPLING_444;
-    if (f == REFVSR_RESULT_F32) hwc ? yuv_chroma_launch<float, true>(yuv_fmt, sampling, left, grid, st, a) : yuv_chroma_launch<float, false>(yuv_fmt, sampling, left, grid, st, a);
-    else if (f == REFVSR_RESULT_F16) hwc ? yuv_chroma_launch<f16, true>(yuv_fmt, sampling, left, grid, st, a) : yuv_chroma_launch<f16, false>(yuv_fmt, sampling, left, grid, st, a);
-    else hwc ? yuv_chroma_launch<unsigned char, true>(yuv_fmt, sampling, left, grid, st, a) : yuv_chroma_launch<unsigned char, false>(yuv_fmt, sampling, left, grid, st, a);
+    if (f == REFVSR_RESULT_F32) hwc ? yuv_launch<float, true>(yuv_fmt, sampling, left, grid, st, a) : yuv_launch<float, false>(yuv_fmt, sampling, left, grid, st, a);
+    else if (f == REFVSR_RESULT_F16) hwc ? yuv_launch<f16, true>(yuv_fmt, sampling, left, grid, st, a) : yuv_launch<f16, false>(yuv_fmt, sampling, left, grid, st, a);
+    else hwc ? yuv_launch<unsigned char, true>(yuv_fmt, sampling, left, grid, st, a) : yuv_launch<unsigned char, false>(yuv_fmt, sampling, left, grid, st, a);
     RV_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int refvsr_result_to_yuv420(const void* const* src, int src_fmt, void* const* dst, int nframes, int h, int w, int yuv_fmt,
+                                       const double* coef9, void* stream) {
+    return yuv_convert("result_to_yuv420", src, src_fmt, dst, nframes, h, w, yuv_fmt, REFVSR_YUV_SAMPLING_420, REFVSR_YUV_SITING_CENTRE, coef9, stream);
+}
+
+extern "C" int refvsr_result_to_yuv(const void* const* src, int src_fmt, void* const* dst, int nframes, int h, int w, int yuv_fmt,
+                                    int sampling, int siting, const double* coef9, void* stream) {
+    RV_CHECK(yuv_fmt_ok(yuv_fmt), "result_to_yuv: unknown yuv format %d", yuv_fmt);
+    RV_CHECK(yuv_sampling_ok(sampling), "result_to_yuv: sampling must be REFVSR_YUV_SAMPLING_420 | _422 | _444 (got %d)", sampling);
+    RV_CHECK(yuv_siting_ok(siting), "result_to_yuv: siting must be REFVSR_YUV_SITING_CENTRE | REFVSR_YUV_SITING_LEFT (got %d)", siting);
+    RV_CHECK(sampling == REFVSR_YUV_SAMPLING_420 || !yuv_semi(yuv_fmt),
+             "result_to_yuv: semi-planar frames (NV12, P010) are 4:2:0 only (format %d, sampling %d)", yuv_fmt, sampling);
+    // (4:2:0 / centre answers in the 4:2:0 entry's name)
+    const bool plain = sampling == REFVSR_YUV_SAMPLING_420 && siting == REFVSR_YUV_SITING_CENTRE;
+    return yuv_convert(plain ? "result_to_yuv420" : "result_to_yuv", src, src_fmt, dst, nframes, h, w, yuv_fmt, sampling, siting, coef9, stream);
 }

@@ -60,12 +60,12 @@ class _Bytes(_Float):
 class _Yuv420(_Bytes):
     """4:2:0 frames [3h/2, w] under config.input_yuv resolved (format, matrix, range, chroma): the copies of the source samples (half
     the bytes of the uint8 kind) key the compare, the fp32 frames are filled by refvsr_yuv420_to_rgb.  Also the 4:2:2 / 4:4:4 formats
-    ([2h, w] / [3h, w] frames) and left-sited chroma (a fifth parameter, yuv.resolve_input): those go through refvsr_yuv_to_rgb.  The
-    format -- and so the sampling -- and the siting are part of the key: the same bytes under another declaration never match."""
+    ([2h, w] / [3h, w] frames) and left-sited chroma (a fifth parameter, yuv.resolve_input): those go through refvsr_yuv_to_rgb (ops.yuv_decode
+    chooses).  The format -- and so the sampling -- and the siting are part of the key: the same bytes under another declaration never
+    match."""
 
     def __init__(self, params):
         self.params = tuple(params)
-        self.plain = self.params[0] in yuv.FORMATS and len(self.params) == 4          # 4:2:0, centre-sited
 
     @property
     def key(self):
@@ -75,10 +75,8 @@ class _Yuv420(_Bytes):
         return ops.yuv_geometry(x) if self.params[0] in yuv.FORMATS else ops.yuv_geometry(x, self.params[0])
 
     def decode(self, pairs):
-        if pairs and self.plain:
-            ops.yuv420_ingest(pairs, *self.params)
-        elif pairs:
-            ops.yuv_ingest(pairs, *self.params)
+        if pairs:
+            ops.yuv_decode(pairs, self.params)
 
 
 _FLOAT = _Float()

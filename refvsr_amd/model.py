@@ -323,12 +323,9 @@ class Network(nn.Module):
         pipelined mode included (the rule of the device scorers).  'result' itself is returned as it was."""
         want = self._engines[0].result_yuv
         if want is not None:
-            from . import yuv
             # (format and siting are both the engine's, taken from the config at its construction; an engine that declares no
-            # siting is centre-sited)
-            siting = yuv.effective_siting(want[0], getattr(self._engines[0], 'result_yuv_siting', 'centre'))
-            # (4:2:2 / 4:4:4 frames -- [n, 2sh, sw] / [n, 3sh, sw] -- and left-sited chroma: refvsr_result_to_yuv, one launch as well)
-            y = ops.result_to_yuv420(frames, *want) if want[0] in yuv.FORMATS and siting == 'centre' else ops.result_to_yuv(frames, *(want + (siting,)))
+            # siting is centre-sited.  4:2:2 / 4:4:4 frames -- [n, 2sh, sw] / [n, 3sh, sw] -- and left-sited chroma: one launch as well)
+            y = ops.result_yuv(frames, want, getattr(self._engines[0], 'result_yuv_siting', 'centre'))
             outs['yuv'] = y if stacked else tuple(y[b:b + 1] for b in range(y.shape[0]))
         return outs
 

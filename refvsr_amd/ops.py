@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 
-from . import fingerprint, hip
+from . import fingerprint, hip, yuv
 from .knobs import env_flag
 from .packing import BlobFlags, blob_plan, pack_conv24, pack_conv_shuffle2, pack_resblock
 from .hip import (OUT_NHWC16, OUT_NHWC16_SHUFFLE2, OUT_PLANAR32, RS_BICUBIC, RS_BILINEAR,  # noqa: F401
@@ -908,7 +908,6 @@ def result_to_yuv420(frames, fmt='nv12', matrix='bt709', range='limited'):
     current stream, no synchronisation.  frames: a [B,3,h,w] tensor or B tensors [3,h,w], float32 / float16 / uint8 (what the output
     head stores), contiguous or channels-last (config.result_layout = 'hwc'), h and w even.  matrix: 'bt709' | 'bt601'; range:
     'limited' | 'full'.  One launch per REFVSR_YUV420_MAX_FRAMES frames."""
-    from . import yuv
     if fmt not in yuv.FORMATS:
         yuv.check_format(fmt)
         raise ValueError('result_to_yuv420: %r is not a 4:2:0 format: ops.result_to_yuv takes it' % (fmt,))
@@ -919,8 +918,7 @@ def result_to_yuv420(frames, fmt='nv12', matrix='bt709', range='limited'):
 def result_to_yuv(frames, fmt='i422', matrix='bt709', range='limited', siting='centre'):
     """result_to_yuv420 for every format and siting (refvsr_result_to_yuv; the bits of yuv.rgb_to_yuv): fmt also 'i422' | 'i444' |
     'i422p10' | 'i444p10', a [B, 2 h, w] or [B, 3 h, w] tensor; siting 'centre' | 'left' (checked and ignored for 4:4:4).  A 4:2:0
-    format with siting 'centre' gives result_to_yuv420's bits (the library hands the call to refvsr_result_to_yuv420)."""
-    from . import yuv
+    format with siting 'centre' gives result_to_yuv420's bits (the same kernel instance)."""
     samp, sit = yuv.SAMPLINGS[yuv.sampling_of(fmt)], yuv.SITINGS[yuv.check_siting(siting)]
     return _result_to_yuv('result_to_yuv', frames, fmt, matrix, range, lambda ps, sfmt, pd, n, h, w, coef, st: hip.lib().refvsr_result_to_yuv(
         ps, sfmt, pd, n, h, w, yuv.FORMAT_IDS[yuv.twin_of(fmt)], samp, sit, coef, st))
@@ -929,7 +927,6 @@ def result_to_yuv(frames, fmt='i422', matrix='bt709', range='limited', siting='c
 def _result_to_yuv(name, frames, fmt, matrix, range, launch):
     """The body of result_to_yuv420 / result_to_yuv: the frames checked, the output [B] + yuv.frame_shape(h, w, fmt) allocated, one
     launch(src table, src format, dst table, n, h, w, coef9, stream) per REFVSR_YUV420_MAX_FRAMES frames."""
-    from . import yuv
     coef = (C.c_double * 9)(*yuv.coefficients(fmt, matrix, range))
     frames = list(frames)
     if not frames:
@@ -1022,7 +1019,6 @@ def yuv_window_kind(x, fmt):
     """('yuv', fmt) for a tensor whose trailing [3 h / 2, w] frames are dense 4:2:0 buffers of format `fmt` -- the sample type of the
     format (torch.uint8 | torch.uint16), at least 2-D, contiguous, even h and w -- else None.  A 4:2:2 format: [2 h, w] frames, a
     4:4:4 one: [3 h, w]."""
-    from . import yuv
     dt = torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16
     if x.dtype != dt or x.dim() < 2 or not x.is_contiguous():
         return None
@@ -1038,65 +1034,70 @@ _YUV_ROW_UNIT = {'420': 3, '422': 4, '444': 6}               # the rows of a fra
 
 def yuv_geometry(x, fmt=None):
     """(h, w) of a tensor of [3 h / 2, w] frames; with a format, of that format's frames ([2 h, w] for 4:2:2, [3 h, w] for 4:4:4)."""
-    if fmt is None:
-        return 2 * x.shape[-2] // 3, x.shape[-1]
-    from . import yuv
-    return 2 * x.shape[-2] // _YUV_ROW_UNIT[yuv.sampling_of(fmt)], x.shape[-1]
+    return 2 * x.shape[-2] // _YUV_ROW_UNIT[yuv.sampling_of(fmt) if fmt else '420'], x.shape[-1]
 
 
 def yuv420_ingest(pairs, fmt='nv12', matrix='bt709', range='limited', chroma='bilinear'):
     """pairs: [(src [3 h / 2, w] uint8 | uint16 by `fmt`, one dense frame at any address that is a multiple of its sample size, dst
     float32 [3,h,w] contiguous)] of one h x w: dst = the bits of yuv.yuv420_to_rgb (refvsr_yuv420_to_rgb) -- the twin of ingest_u8.
     One launch per REFVSR_YUV420_IN_MAX_FRAMES frames, on the current stream."""
-    from . import yuv
-    if not pairs:
-        return
-    coef = (C.c_double * 9)(*yuv.decode_coefficients(fmt, matrix, range))
-    mode = yuv.CHROMA_MODES[yuv.check_chroma(chroma)]
-    _decode_frames(pairs, 'yuv420_to_rgb', 'yuv420_ingest: dense %s frames [3h/2, w] of one size' % fmt,
-                   lambda src, h, w: yuv_window_kind(src, fmt) is not None and tuple(src.shape) == yuv.frame_shape(h, w), hip.YUV420_IN_MAX_FRAMES,
-                   lambda ps, pd, n, h, w: hip.lib().refvsr_yuv420_to_rgb(ps, pd, n, h, w, yuv.FORMAT_IDS[fmt], mode, coef, _stream()))
+    _yuv_ingest('yuv420_to_rgb', 'yuv420_ingest: dense %s frames [3h/2, w] of one size' % fmt, pairs, fmt, matrix, range, chroma,
+                lambda ps, pd, n, h, w, mode, coef, st: hip.lib().refvsr_yuv420_to_rgb(ps, pd, n, h, w, yuv.FORMAT_IDS[fmt], mode, coef, st))
 
 
 def yuv_ingest(pairs, fmt='i422', matrix='bt709', range='limited', chroma='bilinear', siting='centre'):
     """yuv420_ingest for every format and siting (refvsr_yuv_to_rgb; the bits of yuv.yuv_to_rgb): src frames yuv.frame_shape(h, w, fmt),
-    siting 'centre' | 'left' (checked and ignored for 4:4:4).  A 4:2:0 format with siting 'centre' gives yuv420_ingest's bits (the
-    library hands the call to refvsr_yuv420_to_rgb)."""
-    from . import yuv
-    samp, sit = yuv.SAMPLINGS[yuv.sampling_of(fmt)], yuv.SITINGS[yuv.check_siting(siting)]
+    siting 'centre' | 'left' (checked and ignored for 4:4:4).  A 4:2:0 format with siting 'centre': yuv420_ingest's kernel and bits."""
+    fid, samp, sit = yuv.FORMAT_IDS[yuv.twin_of(fmt)], yuv.SAMPLINGS[yuv.sampling_of(fmt)], yuv.SITINGS[yuv.check_siting(siting)]
+    _yuv_ingest('yuv_to_rgb', 'yuv_ingest: dense %s frames of one size' % fmt, pairs, fmt, matrix, range, chroma,
+                lambda ps, pd, n, h, w, mode, coef, st: hip.lib().refvsr_yuv_to_rgb(ps, pd, n, h, w, fid, samp, sit, mode, coef, st))
+
+
+def _yuv_ingest(name, what, pairs, fmt, matrix, range, chroma, launch):
+    """The body of yuv420_ingest / yuv_ingest: nothing for no pairs; else the coefficients and the chroma mode, the pairs checked
+    (`what`), one launch(src table, dst table, n, h, w, mode, coef9, stream) of refvsr_<name> per REFVSR_YUV420_IN_MAX_FRAMES frames."""
     if not pairs:
         return
     coef = (C.c_double * 9)(*yuv.decode_coefficients(fmt, matrix, range))
     mode = yuv.CHROMA_MODES[yuv.check_chroma(chroma)]
-    fid = yuv.FORMAT_IDS[yuv.twin_of(fmt)]
-    _decode_frames(pairs, 'yuv_to_rgb', 'yuv_ingest: dense %s frames of one size' % fmt,
-                   lambda src, h, w: yuv_window_kind(src, fmt) is not None and tuple(src.shape) == yuv.frame_shape(h, w, fmt), hip.YUV420_IN_MAX_FRAMES,
-                   lambda ps, pd, n, h, w: hip.lib().refvsr_yuv_to_rgb(ps, pd, n, h, w, fid, samp, sit, mode, coef, _stream()))
+    _decode_frames(pairs, name, what, lambda src, h, w: yuv_window_kind(src, fmt) is not None and tuple(src.shape) == yuv.frame_shape(h, w, fmt),
+                   hip.YUV420_IN_MAX_FRAMES, lambda ps, pd, n, h, w: launch(ps, pd, n, h, w, mode, coef, _stream()))
+
+
+def yuv_decode(pairs, params):
+    """pairs decoded under config.input_yuv resolved (yuv.resolve_input): the four parameters of a centre-sited 4:2:0 format are
+    yuv420_ingest's, everything else -- a 4:2:2 / 4:4:4 format, a fifth parameter 'left' -- yuv_ingest's."""
+    (yuv420_ingest if params[0] in yuv.FORMATS and len(params) == 4 else yuv_ingest)(pairs, *params)
+
+
+def result_yuv(frames, params, siting='centre'):
+    """frames under config.result_yuv resolved (yuv.resolve) and the engine's siting: a centre-sited 4:2:0 format is
+    result_to_yuv420's, everything else result_to_yuv's."""
+    siting = yuv.effective_siting(params[0], siting)
+    return result_to_yuv420(frames, *params) if params[0] in yuv.FORMATS and siting == 'centre' else result_to_yuv(frames, *(params + (siting,)))
 
 
 def yuv_to_frames(x, h, w, fmt, matrix='bt709', range='limited', chroma='bilinear', siting='centre'):
     """yuv420_to_frames for every format and siting: [..., rows, w] frames, rows = yuv.frame_shape(h, w, fmt)[0], -> a new contiguous
     float32 [..., 3, h, w] tensor, the bits of yuv.yuv_to_rgb, through refvsr_yuv_to_rgb."""
-    from . import yuv
     yuv.check_siting(siting)
-    dt = torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16
-    rows = yuv.frame_shape(h, w, fmt)[0]
-    if not (x.is_cuda and x.dtype == dt and x.dim() >= 2 and tuple(x.shape[-2:]) == (rows, w)):
-        raise RuntimeError('yuv_to_frames: cuda %s [..., %d, %d] frames for %s at %d x %d (got %s %s %s)'
-                           % (dt, rows, w, fmt, h, w, x.device.type, x.dtype, tuple(x.shape)))
-    return _frames_of(x, 2, torch.Tensor.is_contiguous, dt.itemsize, h, w, lambda pairs: yuv_ingest(pairs, fmt, matrix, range, chroma, siting))
+    return _yuv_to_frames('yuv_to_frames', x, h, w, fmt, lambda pairs: yuv_ingest(pairs, fmt, matrix, range, chroma, siting))
 
 
 def yuv420_to_frames(x, h, w, fmt, matrix='bt709', range='limited', chroma='bilinear'):
     """[..., 3 h / 2, w] 4:2:0 frames (uint8 'nv12' | 'i420', uint16 'p010' | 'i420p10'; other strides and storage that is unaligned
     for the sample size are copied first) -> a new contiguous float32 [..., 3, h, w] tensor, the bits of yuv.yuv420_to_rgb, frame by
     frame through refvsr_yuv420_to_rgb (as ingest_frames)."""
-    from . import yuv
-    dt = torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16
-    if not (x.is_cuda and x.dtype == dt and x.dim() >= 2 and tuple(x.shape[-2:]) == yuv.frame_shape(h, w)):
-        raise RuntimeError('yuv420_to_frames: cuda %s [..., %d, %d] frames for %s at %d x %d (got %s %s %s)'
-                           % (dt, 3 * h // 2, w, fmt, h, w, x.device.type, x.dtype, tuple(x.shape)))
-    return _frames_of(x, 2, torch.Tensor.is_contiguous, dt.itemsize, h, w, lambda pairs: yuv420_ingest(pairs, fmt, matrix, range, chroma))
+    return _yuv_to_frames('yuv420_to_frames', x, h, w, fmt, lambda pairs: yuv420_ingest(pairs, fmt, matrix, range, chroma))
+
+
+def _yuv_to_frames(name, x, h, w, fmt, ingest):
+    """The body of yuv420_to_frames / yuv_to_frames: x checked against the format's frames at h x w, then _frames_of with `ingest`."""
+    dt, rows = torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16, yuv.frame_shape(h, w, fmt)[0]
+    if not (x.is_cuda and x.dtype == dt and x.dim() >= 2 and tuple(x.shape[-2:]) == (rows, w)):
+        raise RuntimeError('%s: cuda %s [..., %d, %d] frames for %s at %d x %d (got %s %s %s)'
+                           % (name, dt, rows, w, fmt, h, w, x.device.type, x.dtype, tuple(x.shape)))
+    return _frames_of(x, 2, torch.Tensor.is_contiguous, dt.itemsize, h, w, ingest)
 
 
 _SAD_WS = {}          # (device, stream handle, h, w) -> workspace of one full refvsr_luma_sad call
@@ -1109,7 +1110,6 @@ def luma_sad(frames_a, frames_b, h, w, fmt):
     any multiple of their sample size (views into a [t, 3 h / 2, w] window included); the same frame on both sides gives 0.  One call
     (two launches) per REFVSR_SCENE_MAX_PAIRS pairs.  A 4:2:2 or 4:4:4 format: [2 h, w] or [3 h, w] frames, read under the format id
     of the 4:2:0 twin -- the luma plane is the first h w samples of every layout."""
-    from . import yuv
     fa, fb = list(frames_a), list(frames_b)
     if not fa or len(fa) != len(fb):
         raise RuntimeError('luma_sad: as many frames on both sides, at least one (got %d and %d)' % (len(fa), len(fb)))

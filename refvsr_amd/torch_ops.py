@@ -300,6 +300,33 @@ def register():
                      lambda: 'score_regions takes 1..%d rectangles as a flat list of y0, y1, x0, x1' % hip.SCORE_MAX_RECTS)
         return torch.empty((outs.shape[0], len(rects) // 4, 2), dtype=torch.float64, device=outs.device)
 
+    def yuv_fake_args(name, formats, fmt, matrix, range, chroma=None, siting=None):
+        """The string arguments of the four yuv fakes checked, in the order each of them checks them; the sample dtype of `fmt`.  The
+        way out (no chroma mode) calls matrix and range by their config names."""
+        from . import yuv
+        field = 'yuv_' if chroma is None else ''
+        torch._check(fmt in formats, lambda: '%s: unknown yuv format' % name)
+        torch._check(matrix in yuv.MATRICES, lambda: "%s: %smatrix must be 'bt709' or 'bt601'" % (name, field))
+        torch._check(range in yuv.RANGES, lambda: "%s: %srange must be 'limited' or 'full'" % (name, field))
+        torch._check(chroma is None or chroma in yuv.CHROMA_MODES, lambda: "%s: chroma must be 'bilinear' or 'nearest'" % name)
+        torch._check(siting is None or siting in yuv.SITINGS, lambda: "%s: siting must be 'centre' or 'left'" % name)
+        return torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16
+
+    def yuv_fake_out(name, formats, frames, fmt, matrix, range, siting=None):
+        from . import yuv
+        torch._check(frames.dim() == 4 and frames.shape[1] == 3 and frames.shape[2] % 2 == 0 and frames.shape[3] % 2 == 0,
+                     lambda: '%s takes [B,3,h,w] results with even h and w' % name)
+        dt = yuv_fake_args(name, formats, fmt, matrix, range, None, siting)
+        return torch.empty((frames.shape[0],) + yuv.frame_shape(frames.shape[2], frames.shape[3], fmt), dtype=dt, device=frames.device)
+
+    def yuv_fake_in(name, formats, takes, x, h, w, fmt, matrix, range, chroma, siting=None):
+        from . import yuv
+        dt = yuv_fake_args(name, formats, fmt, matrix, range, chroma, siting)
+        torch._check(h > 0 and w > 0 and h % 2 == 0 and w % 2 == 0 and x.dim() >= 2 and tuple(x.shape[-2:]) == yuv.frame_shape(h, w, fmt),
+                     lambda: '%s takes %s' % (name, takes))
+        torch._check(x.dtype == dt, lambda: '%s: uint8 or uint16 samples by format' % name)
+        return torch.empty(tuple(x.shape[:-2]) + (3, h, w), dtype=torch.float32, device=x.device)
+
     @op('result_to_yuv420')
     def result_to_yuv420(frames: torch.Tensor, fmt: str, matrix: str, range: str) -> torch.Tensor:
         return ops.result_to_yuv420(frames, fmt, matrix, range)
@@ -307,13 +334,7 @@ def register():
     @result_to_yuv420.register_fake
     def _(frames, fmt, matrix, range):
         from . import yuv
-        torch._check(frames.dim() == 4 and frames.shape[1] == 3 and frames.shape[2] % 2 == 0 and frames.shape[3] % 2 == 0,
-                     lambda: 'result_to_yuv420 takes [B,3,h,w] results with even h and w')
-        torch._check(fmt in yuv.FORMATS, lambda: 'result_to_yuv420: unknown yuv format')
-        torch._check(matrix in yuv.MATRICES, lambda: "result_to_yuv420: yuv_matrix must be 'bt709' or 'bt601'")
-        torch._check(range in yuv.RANGES, lambda: "result_to_yuv420: yuv_range must be 'limited' or 'full'")
-        return torch.empty((frames.shape[0], 3 * frames.shape[2] // 2, frames.shape[3]),
-                           dtype=torch.uint8 if yuv.FORMATS[fmt][0] == 8 else torch.uint16, device=frames.device)
+        return yuv_fake_out('result_to_yuv420', yuv.FORMATS, frames, fmt, matrix, range)
 
     @op('yuv420_to_rgb')
     def yuv420_to_rgb(x: torch.Tensor, h: int, w: int, fmt: str, matrix: str, range: str, chroma: str) -> torch.Tensor:
@@ -322,14 +343,7 @@ def register():
     @yuv420_to_rgb.register_fake
     def _(x, h, w, fmt, matrix, range, chroma):
         from . import yuv
-        torch._check(fmt in yuv.FORMATS, lambda: 'yuv420_to_rgb: unknown yuv format')
-        torch._check(matrix in yuv.MATRICES, lambda: "yuv420_to_rgb: matrix must be 'bt709' or 'bt601'")
-        torch._check(range in yuv.RANGES, lambda: "yuv420_to_rgb: range must be 'limited' or 'full'")
-        torch._check(chroma in yuv.CHROMA_MODES, lambda: "yuv420_to_rgb: chroma must be 'bilinear' or 'nearest'")
-        torch._check(h > 0 and w > 0 and h % 2 == 0 and w % 2 == 0 and x.dim() >= 2 and x.shape[-2] == 3 * h // 2 and x.shape[-1] == w,
-                     lambda: 'yuv420_to_rgb takes [..., 3h/2, w] frames with even h and w')
-        torch._check(x.dtype == (torch.uint8 if yuv.FORMATS[fmt][0] == 8 else torch.uint16), lambda: 'yuv420_to_rgb: uint8 or uint16 samples by format')
-        return torch.empty(tuple(x.shape[:-2]) + (3, h, w), dtype=torch.float32, device=x.device)
+        return yuv_fake_in('yuv420_to_rgb', yuv.FORMATS, '[..., 3h/2, w] frames with even h and w', x, h, w, fmt, matrix, range, chroma)
 
     @op('result_to_yuv')
     def result_to_yuv(frames: torch.Tensor, fmt: str, matrix: str, range: str, siting: str) -> torch.Tensor:
@@ -338,14 +352,7 @@ def register():
     @result_to_yuv.register_fake
     def _(frames, fmt, matrix, range, siting):
         from . import yuv
-        torch._check(frames.dim() == 4 and frames.shape[1] == 3 and frames.shape[2] % 2 == 0 and frames.shape[3] % 2 == 0,
-                     lambda: 'result_to_yuv takes [B,3,h,w] results with even h and w')
-        torch._check(fmt in yuv.ALL_FORMATS, lambda: 'result_to_yuv: unknown yuv format')
-        torch._check(matrix in yuv.MATRICES, lambda: "result_to_yuv: yuv_matrix must be 'bt709' or 'bt601'")
-        torch._check(range in yuv.RANGES, lambda: "result_to_yuv: yuv_range must be 'limited' or 'full'")
-        torch._check(siting in yuv.SITINGS, lambda: "result_to_yuv: siting must be 'centre' or 'left'")
-        return torch.empty((frames.shape[0],) + yuv.frame_shape(frames.shape[2], frames.shape[3], fmt),
-                           dtype=torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16, device=frames.device)
+        return yuv_fake_out('result_to_yuv', yuv.ALL_FORMATS, frames, fmt, matrix, range, siting)
 
     @op('yuv_to_rgb')
     def yuv_to_rgb(x: torch.Tensor, h: int, w: int, fmt: str, matrix: str, range: str, chroma: str, siting: str) -> torch.Tensor:
@@ -354,15 +361,8 @@ def register():
     @yuv_to_rgb.register_fake
     def _(x, h, w, fmt, matrix, range, chroma, siting):
         from . import yuv
-        torch._check(fmt in yuv.ALL_FORMATS, lambda: 'yuv_to_rgb: unknown yuv format')
-        torch._check(matrix in yuv.MATRICES, lambda: "yuv_to_rgb: matrix must be 'bt709' or 'bt601'")
-        torch._check(range in yuv.RANGES, lambda: "yuv_to_rgb: range must be 'limited' or 'full'")
-        torch._check(chroma in yuv.CHROMA_MODES, lambda: "yuv_to_rgb: chroma must be 'bilinear' or 'nearest'")
-        torch._check(siting in yuv.SITINGS, lambda: "yuv_to_rgb: siting must be 'centre' or 'left'")
-        torch._check(h > 0 and w > 0 and h % 2 == 0 and w % 2 == 0 and x.dim() >= 2 and tuple(x.shape[-2:]) == yuv.frame_shape(h, w, fmt),
-                     lambda: "yuv_to_rgb takes [..., rows, w] frames with even h and w, rows = 3h/2, 2h or 3h by the format's sampling")
-        torch._check(x.dtype == (torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16), lambda: 'yuv_to_rgb: uint8 or uint16 samples by format')
-        return torch.empty(tuple(x.shape[:-2]) + (3, h, w), dtype=torch.float32, device=x.device)
+        return yuv_fake_in('yuv_to_rgb', yuv.ALL_FORMATS, "[..., rows, w] frames with even h and w, rows = 3h/2, 2h or 3h by the format's sampling",
+                           x, h, w, fmt, matrix, range, chroma, siting)
 
     @op('resize_aa')
     def resize_aa(frames: torch.Tensor, oh: int, ow: int, out: str, clamp: bool) -> torch.Tensor:

@@ -121,16 +121,21 @@ def check_range(range):
     return range
 
 
+def _config_format(fmt, field):
+    """config.result_yuv / input_yuv (not None) checked: the format, or the field's ValueError."""
+    if fmt not in FORMATS and fmt not in CHROMA_FORMATS:
+        raise ValueError("%s must be None, 'nv12', 'i420', 'p010' or 'i420p10', got %r (or a 4:2:2 / 4:4:4 form: %s)"
+                         % (field, fmt, ', '.join("'%s'" % f for f in CHROMA_FORMATS)))
+    return fmt
+
+
 def resolve(result_yuv, matrix=None, range=None):
     """config.result_yuv / yuv_matrix / yuv_range checked: None (off) or (format, matrix, range); ValueError for a bad name -- also
     for a bad matrix or range while the format is off, so that a typo does not wait for the day the feature is switched on."""
     m, r = check_matrix(matrix or 'bt709'), check_range(range or 'limited')
     if result_yuv is None:
         return None
-    if result_yuv not in FORMATS and result_yuv not in CHROMA_FORMATS:
-        raise ValueError("result_yuv must be None, 'nv12', 'i420', 'p010' or 'i420p10', got %r (or a 4:2:2 / 4:4:4 form: %s)"
-                         % (result_yuv, ', '.join("'%s'" % f for f in CHROMA_FORMATS)))
-    return (result_yuv, m, r)
+    return (_config_format(result_yuv, 'result_yuv'), m, r)
 
 
 def resolve_siting(siting, what='yuv_siting'):
@@ -231,26 +236,20 @@ def pack(y, cb, cr, fmt):
     return flat.astype(dt).reshape(frame_shape(h, w, fmt))
 
 
-def rgb_to_yuv420(rgb, fmt='nv12', matrix='bt709', range='limited'):
-    """The model: a [3, h, w] result (float32 | float16 | uint8, any strides) -> the frame's buffer [3 h / 2, w]; a [B, 3, h, w] batch
-    -> [B, 3 h / 2, w]."""
-    rgb = np.asarray(rgb)
-    if rgb.ndim == 4:
-        return np.stack([rgb_to_yuv420(f, fmt, matrix, range) for f in rgb])
-    d = depth_of(fmt)
-    yv, cbv, crv = pre_rounding(rgb, coefficients(fmt, matrix, range))
-    return pack(quantise(yv, d), quantise(cbv, d), quantise(crv, d), fmt)
-
-
 def rgb_to_yuv(rgb, fmt='i422', matrix='bt709', range='limited', siting='centre'):
-    """The model of every sampling and siting: a [3, h, w] result -> the frame's buffer frame_shape(h, w, fmt); a [B, 3, h, w] batch
-    -> [B, ...].  A 4:2:0 format with siting = 'centre' is rgb_to_yuv420."""
+    """The model of every format and siting: a [3, h, w] result (float32 | float16 | uint8, any strides) -> the frame's buffer
+    frame_shape(h, w, fmt); a [B, 3, h, w] batch -> [B, ...]."""
     rgb = np.asarray(rgb)
     if rgb.ndim == 4:
         return np.stack([rgb_to_yuv(f, fmt, matrix, range, siting) for f in rgb])
     d = depth_of(fmt)
     yv, cbv, crv = pre_rounding(rgb, coefficients(fmt, matrix, range), sampling_of(fmt), effective_siting(fmt, siting))
     return pack(quantise(yv, d), quantise(cbv, d), quantise(crv, d), fmt)
+
+
+def rgb_to_yuv420(rgb, fmt='nv12', matrix='bt709', range='limited'):
+    """rgb_to_yuv of a 4:2:0 format, centre-sited: the frame's buffer [3 h / 2, w]."""
+    return rgb_to_yuv(rgb, fmt, matrix, range, 'centre')
 
 
 def planes(buf, h, w, fmt):
@@ -294,9 +293,7 @@ def resolve_input(input_yuv, matrix=None, range=None, chroma=None, siting=None):
     s = resolve_siting(siting, 'input_yuv_siting')
     if input_yuv is None:
         return None
-    if input_yuv not in FORMATS and input_yuv not in CHROMA_FORMATS:
-        raise ValueError("input_yuv must be None, 'nv12', 'i420', 'p010' or 'i420p10', got %r (or a 4:2:2 / 4:4:4 form: %s)"
-                         % (input_yuv, ', '.join("'%s'" % f for f in CHROMA_FORMATS)))
+    _config_format(input_yuv, 'input_yuv')
     return (input_yuv, m, r, c) if effective_siting(input_yuv, s) == 'centre' else (input_yuv, m, r, c, s)
 
 
@@ -365,26 +362,22 @@ def decode_pre_clamp(buf, h, w, fmt='nv12', matrix='bt709', range='limited', chr
     return r, g, b
 
 
-def yuv420_to_rgb(buf, h, w, fmt, matrix='bt709', range='limited', chroma='bilinear'):
-    """The model of the way in: a frame's buffer [3 h / 2, w] (uint8 | uint16 by format) -> float32 [3, h, w] in [0, 1]; a
-    [B, 3 h / 2, w] batch -> [B, 3, h, w]."""
-    buf = np.asarray(buf)
-    if buf.ndim == 3:
-        return np.stack([yuv420_to_rgb(f, h, w, fmt, matrix, range, chroma) for f in buf])
-    if buf.shape != frame_shape(h, w):
-        raise ValueError('a %d x %d frame is %s (got %s)' % (h, w, frame_shape(h, w), buf.shape))
-    return np.stack([np.clip(v, 0.0, 1.0) for v in decode_pre_clamp(buf, h, w, fmt, matrix, range, chroma)]).astype(np.float32)
-
-
 def yuv_to_rgb(buf, h, w, fmt, matrix='bt709', range='limited', chroma='bilinear', siting='centre'):
-    """The model of the way in for every sampling and siting: a frame's buffer frame_shape(h, w, fmt) -> float32 [3, h, w] in [0, 1];
-    a [B, ...] batch -> [B, 3, h, w].  A 4:2:0 format with siting = 'centre' is yuv420_to_rgb."""
+    """The model of the way in for every format and siting: a frame's buffer frame_shape(h, w, fmt) (uint8 | uint16 by format) ->
+    float32 [3, h, w] in [0, 1]; a [B, ...] batch -> [B, 3, h, w]."""
     buf = np.asarray(buf)
     if buf.ndim == 3:
         return np.stack([yuv_to_rgb(f, h, w, fmt, matrix, range, chroma, siting) for f in buf])
     if buf.shape != frame_shape(h, w, fmt):
         raise ValueError('a %d x %d %s frame is %s (got %s)' % (h, w, fmt, frame_shape(h, w, fmt), buf.shape))
     return np.stack([np.clip(v, 0.0, 1.0) for v in decode_pre_clamp(buf, h, w, fmt, matrix, range, chroma, siting)]).astype(np.float32)
+
+
+def yuv420_to_rgb(buf, h, w, fmt, matrix='bt709', range='limited', chroma='bilinear'):
+    """yuv_to_rgb of a 4:2:0 format, centre-sited: a frame's buffer [3 h / 2, w], or a [B, 3 h / 2, w] batch."""
+    if np.shape(buf)[-2:] != frame_shape(h, w):
+        raise ValueError('a %d x %d frame is %s (got %s)' % (h, w, frame_shape(h, w), np.shape(buf)[-2:]))
+    return yuv_to_rgb(buf, h, w, fmt, matrix, range, chroma, 'centre')
 
 
 # ------------------------------------------------------------------------------------------------ Y4M

@@ -426,6 +426,47 @@ def test_result_to_yuv_rejects_bad_arguments_without_a_gpu(L):
             assert f(src, 0, dst, 1, 8, 8, fmt, samp, 1, coef, None) != 0 and 'semi-planar' in err() and '\n' not in err()
 
 
+def _refusals(L, entry, cases, good, order, extra=()):
+    """[(prefix, text behind it)] of `entry` for every case: `good` with the case's arguments replaced, passed in `order` (`extra`: the
+    (position, value) pairs of the arguments only the general entry has)."""
+    out = []
+    for case in cases:
+        args = [dict(good, **case)[k] for k in order] + [None]                 # (the stream)
+        for pos, val in extra:
+            args.insert(pos, val)
+        assert entry(*args) != 0, case
+        out.append(tuple(L.refvsr_last_error().decode().split(': ', 1)))
+    return out
+
+
+def test_both_entries_of_a_direction_refuse_in_the_same_words(L):
+    """One list of bad arguments per direction, fed to the 4:2:0 entry and to the general entry under every sampling and siting it
+    launches: the text behind the prefix is the same.  (What the 4:2:0 entry cannot say -- a sampling, a siting -- is not in the
+    lists: the two tests above hold those.)"""
+    hw_bad = [dict(h=h, w=w) for h, w in ((7, 8), (8, 9), (0, 8), (8, 0), (1, 1), (-2, 8))]
+    out_good = dict(src=_ptrs(4096), sfmt=0, dst=_ptrs(1 << 20), n=1, h=8, w=8, fmt=1, coef=(ctypes.c_double * 9)(*yuv.coefficients('i420')))
+    out_bad = ([dict(src=None), dict(dst=None), dict(coef=None)] + [dict(n=n) for n in (0, -1, 17)] + [dict(sfmt=s) for s in (-1, 3, 0x13, 0x20)]
+               + [dict(fmt=f) for f in (-1, 4, 9)] + hw_bad + [dict(h=1 << 14, w=1 << 14), dict(src=_ptrs(0)), dict(dst=_ptrs(0)),
+                  dict(src=_ptrs(4096, 0), dst=_ptrs(1 << 20, 1 << 21), n=2), dict(src=_ptrs(4098)), dict(sfmt=2, dst=_ptrs((1 << 20) + 1), fmt=3),
+                  dict(sfmt=2, dst=_ptrs(4096)), dict(src=_ptrs(4096, 8192), sfmt=2, dst=_ptrs(1 << 20, (1 << 20) + 16), n=2)])
+    in_good = dict(src=_ptrs(4096), dst=_ptrs(8192), n=1, h=8, w=8, fmt=1, chroma=0, coef=(ctypes.c_double * 9)(*yuv.decode_coefficients('i420')))
+    in_bad = ([dict(src=None), dict(dst=None), dict(src=_ptrs(0)), dict(dst=_ptrs(0)), dict(src=_ptrs(4096, 0), dst=_ptrs(8192, 16384), n=2)]
+              + [dict(n=n) for n in (0, -1, 17)] + hw_bad + [dict(h=1 << 15, w=1 << 15)] + [dict(fmt=f) for f in (-1, 4, 9)]
+              + [dict(chroma=c) for c in (-1, 2)] + [dict(coef=None)] + [dict(dst=_ptrs(d)) for d in (8196, 8200, 8193)] + [dict(src=_ptrs(4097), fmt=3)])
+    for plain, general, names, good, bad, order in (
+            (L.refvsr_result_to_yuv420, L.refvsr_result_to_yuv, ('result_to_yuv420', 'result_to_yuv'), out_good, out_bad,
+             ('src', 'sfmt', 'dst', 'n', 'h', 'w', 'fmt', 'coef')),
+            (L.refvsr_yuv420_to_rgb, L.refvsr_yuv_to_rgb, ('yuv420_to_rgb', 'yuv_to_rgb'), in_good, in_bad,
+             ('src', 'dst', 'n', 'h', 'w', 'fmt', 'chroma', 'coef'))):
+        want = _refusals(L, plain, bad, good, order)
+        assert all(prefix == names[0] and text for prefix, text in want), want
+        at = order.index('fmt') + 1                                            # sampling, siting stand behind the format
+        for samp, sit in ((0, 0), (0, 1), (1, 0), (1, 1), (2, 0), (2, 1)):
+            got = _refusals(L, general, bad, good, order, ((at, samp), (at + 1, sit)))
+            assert [t for _, t in got] == [t for _, t in want], (names[1], samp, sit)
+            assert all(prefix in names for prefix, _ in got), got
+
+
 # ------------------------------------------------------------------------------------------------ config, engine entry, videorun
 def test_config_fields_are_validated_while_the_feature_is_off():
     from refvsr_amd import get_config

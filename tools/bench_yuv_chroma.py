@@ -6,9 +6,10 @@
      source and destination through a set larger than the 256 MB Infinity Cache (every launch reads from HBM), 'hot' re-uses one
      set.  us per launch, TB/s over the algorithmic bytes (every source sample read once, every output sample written once) and that
      rate's share of the 8 TB/s HBM roof.  No bar.
-  2. the unchanged 4:2:0 / centre launches of a PARENT library (--parent: the librefvsr_hip.so of a built checkout of the parent
-     commit) and of this tree's, loaded side by side into this process, in alternating passes.  A slowdown beyond the spread of the
-     parent's own passes is a regression.
+  2. the 4:2:0 launches of a PARENT library (--parent: the librefvsr_hip.so of a built checkout of the parent commit) and of this
+     tree's, loaded side by side into this process, in alternating passes: centre-sited through the 4:2:0 entries, each way and from
+     a uint8 channels-last result, left-sited on the way out through the general entry.  A slowdown beyond the spread of the parent's
+     own passes is a regression.
   3. forward_group (four windows, pipelined, config_RefVSR_small_L1, 270 x 480 -> 1080 x 1920) frames/s with result_yuv = 'i444p10'
      (6 bytes of 'yuv' per output pixel beside the result) against result_yuv = None, alternating passes; then the same with what
      a consumer takes copied to pinned host memory after every group: 'yuv' where there is one (1.5 or 6 bytes per pixel), the
@@ -162,44 +163,59 @@ def kernels_out(lib, st):
 
 
 def bind_parent(path):
-    """The parent library's two 4:2:0 launches, bound beside this tree's (another file: another copy of the code and its state)."""
+    """The parent library's four conversion entries, bound beside this tree's (another file: another copy of the code and its state)."""
     lib = C.CDLL(path)
-    for name in ('refvsr_yuv420_to_rgb', 'refvsr_result_to_yuv420'):
+    for name in ('refvsr_yuv420_to_rgb', 'refvsr_result_to_yuv420', 'refvsr_yuv_to_rgb', 'refvsr_result_to_yuv'):
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = hip.SIGNATURES[name], C.c_int
     return lib
 
 
+# (way, format, siting, the results' form on the way out).  Centre goes through the 4:2:0 entries, left through the general ones:
+# the left-sited 4:2:0 instances of the way out are the ones whose instruction stream is not the parent's (profiles/yuv_one_kernel.txt)
+AB_ROWS = (('in ', 'nv12', 'centre', None), ('out', 'nv12', 'centre', 'f32'), ('in ', 'i420', 'centre', None), ('out', 'i420', 'centre', 'f32'),
+           ('in ', 'i420p10', 'centre', None), ('out', 'i420p10', 'centre', 'f32'), ('out', 'nv12', 'centre', 'u8 hwc'),
+           ('out', 'nv12', 'left', 'f32'), ('out', 'i420p10', 'left', 'f32'), ('out', 'i420', 'left', 'u8 hwc'))
+
+
 def parent_ab(lib, parent_path, st, passes=5):
     say()
-    say('== 2. the unchanged 4:2:0 / centre launches, parent library against this tree\'s in one process: us per launch (rotated), one '
-        'figure per pass of %d launches, passes alternating parent, new, parent, ...' % LAUNCHES)
+    say('== 2. the 4:2:0 launches, parent library against this tree\'s in one process: us per launch (rotated), one figure per pass of '
+        '%d launches, passes alternating parent, new, parent, ...' % LAUNCHES)
     if not parent_path or not os.path.exists(parent_path):
         say('not measured: no parent library at %r' % (parent_path,))
         return
     old = bind_parent(parent_path)
     rs = np.random.RandomState(3)
     for h, w, nf in GEOMETRIES:
-        for fmt in ('nv12', 'i420p10'):
-            fid = yuv.FORMAT_IDS[fmt]
-            cin = (C.c_double * 9)(*yuv.decode_coefficients(fmt, 'bt709', 'limited'))
-            cout = (C.c_double * 9)(*yuv.coefficients(fmt, 'bt709', 'limited'))
-            ybytes, fbytes = nf * yuv.frame_bytes(h, w, fmt), nf * 12 * h * w
+        for way, fmt, siting, form in AB_ROWS:
+            fid, samp, sit = ids(fmt, siting)
+            coef = (C.c_double * 9)(*(yuv.decode_coefficients if way == 'in ' else yuv.coefficients)(fmt, 'bt709', 'limited'))
+            u8 = form == 'u8 hwc'
+            ybytes, fbytes = nf * yuv.frame_bytes(h, w, fmt), nf * (3 if u8 else 12) * h * w
             nset = max(2, CACHE_BYTES // (ybytes + fbytes) + 2)
             host = (rs.randint(0, 2 ** yuv.depth_of(fmt), (nf,) + yuv.frame_shape(h, w)) << yuv.FORMATS[fmt][2]).astype(yuv.dtype_of(fmt))
             ys = [torch.from_numpy(host).to(dev) for _ in range(nset)]
-            fs = [torch.rand((nf, 3, h, w), dtype=torch.float32, device=dev) for _ in range(nset)]
+            fs = [torch.randint(0, 256, (nf, h, w, 3), dtype=torch.uint8, device=dev) if u8 else torch.rand((nf, 3, h, w), dtype=torch.float32, device=dev)
+                  for _ in range(nset)]
             py, pf = tables(ys, nf), tables(fs, nf)
-            for way, call in (('in ', lambda L_, k: L_.refvsr_yuv420_to_rgb(py[k], pf[k], nf, h, w, fid, 0, cin, st)),
-                              ('out', lambda L_, k: L_.refvsr_result_to_yuv420(pf[k], hip.RESULT_F32, py[k], nf, h, w, fid, cout, st))):
-                assert call(old, 0) == 0 and call(lib, 0) == 0
-                mk = lambda L_: [(lambda k=i % nset: call(L_, k)) for i in range(LAUNCHES)]
-                r = alternate({'parent': mk(old), 'new': mk(lib)}, passes)
-                sp = max(r['parent']) - min(r['parent'])
-                d = med(r['new']) - med(r['parent'])
-                say('%4dx%-4d x %d %s %-7s  parent %s  median %.1f | new %s  median %.1f | new - parent %+.1f us, spread of the parent\'s passes %.1f: %s'
-                    % (h, w, nf, way, fmt, ' '.join('%.1f' % x for x in r['parent']), med(r['parent']), ' '.join('%.1f' % x for x in r['new']), med(r['new']),
-                       d, sp, 'within the spread' if d <= sp else 'SLOWER than the spread'))
+            sfmt = hip.RESULT_U8 | hip.RESULT_HWC if u8 else hip.RESULT_F32
+            if way == 'in ' and siting == 'centre':
+                call = lambda L_, k: L_.refvsr_yuv420_to_rgb(py[k], pf[k], nf, h, w, fid, 0, coef, st)
+            elif siting == 'centre':
+                call = lambda L_, k: L_.refvsr_result_to_yuv420(pf[k], sfmt, py[k], nf, h, w, fid, coef, st)
+            elif way == 'in ':
+                call = lambda L_, k: L_.refvsr_yuv_to_rgb(py[k], pf[k], nf, h, w, fid, samp, sit, 0, coef, st)
+            else:
+                call = lambda L_, k: L_.refvsr_result_to_yuv(pf[k], sfmt, py[k], nf, h, w, fid, samp, sit, coef, st)
+            assert call(old, 0) == 0 and call(lib, 0) == 0
+            mk = lambda L_: [(lambda k=i % nset: call(L_, k)) for i in range(LAUNCHES)]
+            r = alternate({'parent': mk(old), 'new': mk(lib)}, passes)
+            sp = max(r['parent']) - min(r['parent'])
+            d = med(r['new']) - med(r['parent'])
+            say('%4dx%-4d x %d %s %-7s %-6s %-6s  parent %s  median %.1f | new %s  median %.1f | new - parent %+.1f us, spread of the parent\'s passes %.1f: %s'
+                % (h, w, nf, way, fmt, siting, form or '', ' '.join('%.1f' % x for x in r['parent']), med(r['parent']), ' '.join('%.1f' % x for x in r['new']),
+                   med(r['new']), d, sp, 'within the spread' if d <= sp else 'SLOWER than the spread'))
             del ys, fs, py, pf
             torch.cuda.empty_cache()
 
