@@ -737,6 +737,44 @@ int refvsr_resize_aa(const void* const* src, int src_fmt, void* const* dst, int 
                      const double* wy, int maxcnt_x, int maxcnt_y, int clamp, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Baseline JPEG of Y'CbCr frames (extension, no ABI bump: added symbols only).  Replaces the consumer's host-side JPEG writer
+ * (evaluation/eval_qual_quan.py:107-129: a JPEG per frame through the image library): the entropy-coded data of one JPEG scan per frame
+ * is made on the device from the frames refvsr_result_to_yuv wrote, so that about a tenth of the 4:2:0 bytes crosses to the host.  The
+ * specification is the numpy model refvsr_amd/jpeg.py (encode_model); the kernels return its bytes.  JFIF means BT.601, full range,
+ * centre-sited chroma: the caller converts with those.  Headers (SOI .. SOS) and EOI are the host's (jpeg.py:header).
+ * refvsr_jpeg_max_frames: replaces nothing -- REFVSR_JPEG_MAX_FRAMES of the built library (a value, not a status).
+ * refvsr_jpeg_capacity: host only, replaces nothing; an upper bound of one frame's entropy-coded bytes (jpeg.py:capacity says how it
+ *   is derived), 0 for arguments the call rejects.
+ * refvsr_jpeg_workspace_bytes: host only, replaces nothing; the workspace of a call with these arguments, 0 for arguments it rejects.
+ * refvsr_jpeg_encode: nframes <= REFVSR_JPEG_MAX_FRAMES frames of one h x w (even, 2..65535, at most 2^23 blocks) in FIVE launches on
+ *   `stream` (transform; entropy pass counting bytes per restart interval; prefix sums; offsets; entropy pass writing at the final
+ *   offsets), plain vector stores only:
+ *     src: HOST array of device pointers, one dense 8-bit planar frame each (REFVSR_YUV_I420's layout at sampling
+ *          REFVSR_YUV_SAMPLING_420 | _444; 4:2:2 is not built), at any address;
+ *     qtables [2][64] float64 (luma, chroma; natural order), dct [8][8] float64 (jpeg.py:dct_table), huffman_lut [4][256] uint32
+ *          (jpeg.py:huffman_lut: length << 16 | code of DC luma, AC luma, DC chroma, AC chroma): DEVICE tables made by the host; the
+ *          device computes no cosine and no table.  A wrong table gives wrong bytes, never an access outside the buffers: every
+ *          store is checked against the frame's counted size;
+ *     restart: MCUs per restart interval, 1..65535; every interval is one wave's work;
+ *     dst: DEVICE, dst_capacity bytes: the data of the frames back to back, RST markers included, no header, no EOI;
+ *     sizes, offsets: DEVICE, 8-byte aligned, nframes 64-bit words each: frame i's data is dst[offsets[i] .. offsets[i] + sizes[i]).
+ *          A frame that does not fit dst_capacity behind the frames ahead of it is not written; sizes still holds what it needs.
+ *          Nothing is written past dst + dst_capacity;
+ *     workspace: DEVICE, 16-byte aligned, workspace_bytes >= refvsr_jpeg_workspace_bytes(nframes, h, w, sampling, restart).
+ *   With dst_capacity >= nframes * refvsr_jpeg_capacity(..) nothing can overflow and the call does not wait.  With less it waits for
+ *   the stream, reads the sizes and returns REFVSR_JPEG_OVERFLOW (with a message) if a frame did not fit.
+ *   Every argument is checked before any device work.
+ * ------------------------------------------------------------------------------------------ */
+#define REFVSR_JPEG_MAX_FRAMES 16
+#define REFVSR_JPEG_OVERFLOW 3
+int refvsr_jpeg_max_frames(void);
+size_t refvsr_jpeg_capacity(int h, int w, int sampling, int restart);
+size_t refvsr_jpeg_workspace_bytes(int nframes, int h, int w, int sampling, int restart);
+int refvsr_jpeg_encode(const void* const* src, int nframes, int h, int w, int sampling, const double* qtables, const double* dct,
+                       const uint32_t* huffman_lut, int restart, void* dst, size_t dst_capacity, long long* sizes, long long* offsets,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Scene cuts: luma SAD of frame pairs (extension, no ABI bump: added symbols only).  Replaces nothing in the reference: its loader
  * serves one folder per clip, replicates frames at the clip's edges (data_loader/datasets.py:222-234) and starts every clip with
  * is_first = True, so it never meets a cut.  A video file has cuts; refvsr_amd/videorun.py (--scene_cut) runs every scene as the

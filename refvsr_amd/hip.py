@@ -30,6 +30,8 @@ YUV420_MAX_FRAMES = 16                      # REFVSR_YUV420_MAX_FRAMES: result f
 YUV420_IN_MAX_FRAMES = 16                   # REFVSR_YUV420_IN_MAX_FRAMES: 4:2:0 input frames per refvsr_yuv420_to_rgb launch
 SCENE_MAX_PAIRS = 16                        # REFVSR_SCENE_MAX_PAIRS: frame pairs per refvsr_luma_sad call
 RESIZE_MAX_FRAMES = 16                      # REFVSR_RESIZE_MAX_FRAMES: frames per refvsr_resize_aa launch
+JPEG_MAX_FRAMES = 16                        # REFVSR_JPEG_MAX_FRAMES: frames per refvsr_jpeg_encode call
+JPEG_OVERFLOW = 3                           # REFVSR_JPEG_OVERFLOW: the return code of a frame that did not fit dst_capacity
 FINGERPRINT_CHUNK_WORDS = 4096              # REFVSR_FINGERPRINT_CHUNK_WORDS: words per chunk-table entry of refvsr_param_fingerprint
 RESBLOCK24_BLOB_BYTES = 43264
 RESBLOCK24_F16W_BLOB_BYTES = 28928          # the fp16 weight format (ABI 15)
@@ -196,6 +198,10 @@ SIGNATURES = {
     # cnt_x, wx, lo_y, cnt_y, wy (device tables of resize.aa_taps), maxcnt_x, maxcnt_y, clamp, stream
     'refvsr_resize_aa': [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     'refvsr_resize_max_frames': [],              # returns REFVSR_RESIZE_MAX_FRAMES
+    # baseline JPEG of Y'CbCr frames (added symbols, ABI 15 unchanged): src table, frames, h, w, sampling, qtables, dct, huffman LUT
+    # (device tables of jpeg.py), restart, dst, its capacity, sizes, offsets (device int64), workspace, its bytes, stream
+    'refvsr_jpeg_encode': [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _Z, _P, _P, _P, _Z, _P],
+    'refvsr_jpeg_max_frames': [],                # returns REFVSR_JPEG_MAX_FRAMES
 }
 # fp16 weight format (ABI 15): <name>_f16w twins with the signature of the function they are named after
 _F16W_TWINS = ('refvsr_resblock24_chain', 'refvsr_resblock24_chain_batch', 'refvsr_conv24', 'refvsr_conv24_batch', 'refvsr_conv32',
@@ -208,7 +214,9 @@ _SPECIAL = {'refvsr_abi_version': (C.c_int, []), 'refvsr_last_error': (C.c_char_
             'refvsr_param_fingerprint_workspace_bytes': (C.c_size_t, [_I]),
             'refvsr_yuv420_bytes': (C.c_size_t, [_I, _I, _I]),
             'refvsr_yuv_frame_bytes': (C.c_size_t, [_I, _I, _I, _I]),
-            'refvsr_luma_sad_workspace_bytes': (C.c_size_t, [_I, _I, _I])}
+            'refvsr_luma_sad_workspace_bytes': (C.c_size_t, [_I, _I, _I]),
+            'refvsr_jpeg_capacity': (C.c_size_t, [_I, _I, _I, _I]),
+            'refvsr_jpeg_workspace_bytes': (C.c_size_t, [_I, _I, _I, _I, _I])}
 EXPORTS = tuple(sorted(list(SIGNATURES) + list(_SPECIAL)))
 
 _lib = None
@@ -239,7 +247,8 @@ def lib():
                                    (h.refvsr_yuv420_max_frames, YUV420_MAX_FRAMES, 'REFVSR_YUV420_MAX_FRAMES'),
                                    (h.refvsr_yuv420_in_max_frames, YUV420_IN_MAX_FRAMES, 'REFVSR_YUV420_IN_MAX_FRAMES'),
                                    (h.refvsr_scene_max_pairs, SCENE_MAX_PAIRS, 'REFVSR_SCENE_MAX_PAIRS'),
-                                   (h.refvsr_resize_max_frames, RESIZE_MAX_FRAMES, 'REFVSR_RESIZE_MAX_FRAMES')):
+                                   (h.refvsr_resize_max_frames, RESIZE_MAX_FRAMES, 'REFVSR_RESIZE_MAX_FRAMES'),
+                                   (h.refvsr_jpeg_max_frames, JPEG_MAX_FRAMES, 'REFVSR_JPEG_MAX_FRAMES')):
             if query() != const:
                 raise RuntimeError('refvsr_amd: %s mismatch (library %d, binding %d)' % (name, query(), const))
         _lib = h

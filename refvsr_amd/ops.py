@@ -1100,6 +1100,104 @@ def _yuv_to_frames(name, x, h, w, fmt, ingest):
     return _frames_of(x, 2, torch.Tensor.is_contiguous, dt.itemsize, h, w, ingest)
 
 
+_JPEG_TABLES = {}     # (device, quality, fmt) -> the device tables of refvsr_jpeg_encode: (qtables, dct, huffman LUT)
+
+
+def _jpeg_tables(dev, quality, fmt):
+    """The cached device tables of jpeg_encode for one (quality, fmt): the float64 quantisation tables [2, 64], the DCT matrix
+    jpeg.dct_table() and jpeg.huffman_lut(), made on the host and uploaded once."""
+    from . import jpeg
+    key = (dev, quality, fmt)
+    tabs = _JPEG_TABLES.get(key)
+    if tabs is None:
+        if len(_JPEG_TABLES) > 16:
+            _JPEG_TABLES.clear()
+        q = np.stack(jpeg.quant_tables(quality)).astype(np.float64)
+        tabs = _JPEG_TABLES[key] = tuple(torch.from_numpy(np.ascontiguousarray(a_)).to(dev)
+                                          for a_ in (q, jpeg.dct_table(), jpeg.huffman_lut().view(np.int32)))
+    return tabs
+
+
+def _jpeg_frames(name, yuv_frames, h, w, fmt, quality, restart):
+    """The arguments of jpeg_encode / jpeg_encode_device checked, in the order format, quality, restart, size, dtype, shape, device:
+    (the frames as a list of dense [rows, w] tensors, quality, restart).  Names and numbers are ValueErrors, tensors RuntimeErrors, as
+    in result_to_yuv."""
+    from . import jpeg
+    jpeg.check_format(fmt)
+    quality, restart = jpeg.check_quality(quality), jpeg.check_restart(restart)
+    if isinstance(h, bool) or isinstance(w, bool) or not isinstance(h, int) or not isinstance(w, int):
+        raise ValueError('%s: h and w must be integers (got %r, %r)' % (name, h, w))
+    jpeg.check_size(h, w)
+    shape = yuv.frame_shape(h, w, fmt)
+    if isinstance(yuv_frames, torch.Tensor):
+        if yuv_frames.dim() < 2 or tuple(yuv_frames.shape[-2:]) != shape:
+            raise RuntimeError('%s: %s frames at %d x %d are [.., %d, %d] (got %s)' % (name, fmt, h, w, shape[0], shape[1], tuple(yuv_frames.shape)))
+        frames = [yuv_frames] if yuv_frames.dim() == 2 else list(yuv_frames.flatten(0, -3).unbind(0))
+    else:
+        frames = list(yuv_frames)
+    if not frames:
+        raise RuntimeError('%s: at least one frame' % name)
+    for f in frames:
+        if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8:
+            raise RuntimeError('%s: frames are torch.uint8 (8-bit %s; got %s)' % (name, fmt, getattr(f, 'dtype', type(f).__name__)))
+        if tuple(f.shape) != shape or not f.is_contiguous():
+            raise RuntimeError('%s: every frame is one dense [%d, %d] buffer (%s at %d x %d; got %s, strides %s)'
+                               % (name, shape[0], shape[1], fmt, h, w, tuple(f.shape), tuple(f.stride())))
+    for f in frames:
+        if not f.is_cuda or f.device != frames[0].device:
+            raise RuntimeError('%s: frames must lie on one GPU (got %s)' % (name, f.device))
+    return frames, quality, restart
+
+
+def jpeg_encode_device(yuv_frames, h, w, fmt, quality=90, restart=None):
+    """The entropy-coded data of B frames, made on the device (refvsr_jpeg_encode; the bytes of jpeg.entropy_data), for callers that
+    issue the copies themselves: (dst, offsets, sizes) -- dst a torch.uint8 [B * bound] tensor, bound = refvsr_jpeg_capacity, offsets
+    and sizes torch.int64 [B] device tensors: frame i's data is dst[offsets[i] : offsets[i] + sizes[i]]; jpeg.assemble(jpeg.header(..),
+    data) makes the file.  On the current stream, no synchronisation.  yuv_frames: the 'yuv' frames of a call or of result_to_yuv(frames,
+    'i420' | 'i444', 'bt601', 'full', 'centre'): a [.., 3 h / 2, w] | [.., 3 h, w] torch.uint8 tensor or a list of such frames, each one
+    dense buffer at any address.  One launch set per REFVSR_JPEG_MAX_FRAMES frames (each set's frames lie back to back from the set's
+    first slot on)."""
+    frames, quality, restart = _jpeg_frames('jpeg_encode_device', yuv_frames, h, w, fmt, quality, restart)
+    dev = frames[0].device
+    lib = hip.lib()
+    samp = yuv.SAMPLINGS[yuv.sampling_of(fmt)]
+    bound = lib.refvsr_jpeg_capacity(h, w, samp, restart)
+    if bound == 0:
+        raise RuntimeError('jpeg_encode_device: frames of %d x %d hold too many blocks' % (h, w))
+    qt, dct, lut = _jpeg_tables(dev, quality, fmt)
+    n = len(frames)
+    dst = torch.empty(n * bound, dtype=torch.uint8, device=dev)
+    meta = torch.empty((2, n), dtype=torch.int64, device=dev)
+    st = _stream()
+    for s0 in _irange(0, n, hip.JPEG_MAX_FRAMES):
+        chunk = frames[s0:s0 + hip.JPEG_MAX_FRAMES]
+        wsb = lib.refvsr_jpeg_workspace_bytes(len(chunk), h, w, samp, restart)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        hip.check(lib.refvsr_jpeg_encode(_parr(chunk), len(chunk), h, w, samp, _ptr(qt), _ptr(dct), _ptr(lut), restart,
+                                         C.c_void_p(dst.data_ptr() + s0 * bound), len(chunk) * bound, C.c_void_p(meta.data_ptr() + 8 * (n + s0)),
+                                         C.c_void_p(meta.data_ptr() + 8 * s0), _ptr(ws), wsb, st), 'jpeg_encode')
+        if s0:
+            meta[0, s0:s0 + len(chunk)] += s0 * bound                   # (a set's offsets count from its own first slot)
+    return dst, meta[0], meta[1]
+
+
+def jpeg_encode(yuv_frames, h, w, fmt, quality=90, restart=None):
+    """B frames -> B complete JFIF files (bytes; the bytes of jpeg.encode_model): jpeg_encode_device, then the sizes are read -- the one
+    synchronisation -- and exactly the compressed bytes are copied to the host, where header and EOI are put around each frame's data.
+    quality: 1..100; restart: MCUs per restart interval, None: jpeg.DEFAULT_RESTART."""
+    from . import jpeg
+    frames, quality, restart = _jpeg_frames('jpeg_encode', yuv_frames, h, w, fmt, quality, restart)
+    dst, offsets, sizes = jpeg_encode_device(frames, h, w, fmt, quality, restart)
+    off, size = offsets.cpu().tolist(), sizes.cpu().tolist()
+    head = jpeg.header(h, w, fmt, quality, restart)
+    out = []
+    for s0 in _irange(0, len(frames), hip.JPEG_MAX_FRAMES):             # a launch set's frames lie back to back: one copy per set
+        s1 = min(s0 + hip.JPEG_MAX_FRAMES, len(frames))
+        data = dst[off[s0]:off[s1 - 1] + size[s1 - 1]].cpu().numpy().tobytes()
+        out.extend(jpeg.assemble(head, data[off[i] - off[s0]:off[i] - off[s0] + size[i]]) for i in _irange(s0, s1))
+    return out
+
+
 _SAD_WS = {}          # (device, stream handle, h, w) -> workspace of one full refvsr_luma_sad call
 
 

@@ -9,7 +9,8 @@ plain numpy arrays in the tests).
     `(index, buffer)` to a bounded queue (`get()`; None behind the last frame);
   * `next_pair`: the next frame of two sources, or the one-line ValueError of a pair whose lengths differ;
   * `FrameSink`: one writer thread.  `put(buffer)` takes frames in order, the thread writes them through a yuv.Y4MWriter and hands
-    the buffers back (`take()`).
+    the buffers back (`take()`); `put(buffer, length)` writes the first `length` elements only -- the variable-length frames of a
+    jpeg.MJPEGWriter.
 
 The two inputs are read CONCURRENTLY, each by its own thread, and a source reads ahead as far as its ring reaches before anybody asks:
 a producer that fills one FIFO before it opens the other (a decoder that writes the first LR frames, then opens the reference stream)
@@ -159,8 +160,9 @@ def next_pair(a, b, what='videorun'):
 
 class FrameSink(object):
     """The output behind a writer thread.  writer: a yuv.Y4MWriter (written to by the thread alone); buffers: the ring.  take() -> a
-    free buffer (waits for the writer: `waited`); put(buffer) queues a frame, in order; finish() waits until everything queued is
-    written.  The writer is not closed here: who opened it closes it."""
+    free buffer (waits for the writer: `waited`); put(buffer) queues a frame, in order -- put(buffer, length): the frame is
+    buffer[:length] (a jpeg.MJPEGWriter's compressed frame in a slot of the ring); put(buffer, data=bytes): the frame is `data`, the
+    buffer only returns to the ring in its turn (a frame larger than a slot); finish() waits until everything queued is written.  The writer is not closed here: who opened it closes it."""
 
     def __init__(self, run, writer, buffers, name, io_timeout=120.0):
         self.run, self.writer, self.name, self.io_timeout = run, writer, name, float(io_timeout)
@@ -179,13 +181,14 @@ class FrameSink(object):
         try:
             while not run.stop.is_set():
                 try:
-                    buf = self._todo.get(timeout=SLICE)
+                    item = self._todo.get(timeout=SLICE)
                 except queue.Empty:
                     continue
-                if buf is self._end:
+                if item is self._end:
                     self._finished.set()
                     return
-                self.writer.write(buf)
+                buf, length, data = item
+                self.writer.write(data if data is not None else buf if length is None else buf[:length])
                 self._free.put(buf)
         except BaseException as e:                      # noqa: B902
             run.fail(e)
@@ -196,10 +199,10 @@ class FrameSink(object):
         self.outstanding += 1
         return buf
 
-    def put(self, buf):
+    def put(self, buf, length=None, data=None):
         self.run.check()
         self.outstanding -= 1
-        self._todo.put(buf)
+        self._todo.put((buf, length, data))
 
     def finish(self):
         self._todo.put(self._end)

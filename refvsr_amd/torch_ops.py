@@ -33,6 +33,8 @@ Op set (argument conventions of ops.py: `planar` = float32 [C,H,W], `nhwc16` = f
   result_to_yuv(frames, fmt, matrix, range, siting)      result_to_yuv420 for every format ('i422', 'i444', .. too) and siting
   yuv_to_rgb(x, h, w, fmt, matrix, range, chroma, siting)   yuv420_to_rgb for every format and siting: [..., rows of the format, w] frames
   resize_aa(frames, oh, ow, out, clamp)                  [B,3,h,w] frames -> [B,3,oh,ow] float32 | uint8, antialiased bicubic (resize.py's bits)
+  jpeg_encode(x, h, w, fmt, quality, restart)            [B, 3h/2 | 3h, w] uint8 'i420' | 'i444' frames -> (data uint8, offsets, sizes int64 [B]):
+                                                         the device form of ops.jpeg_encode_device (jpeg.py's bytes); restart 0 = the default
 """
 from typing import List, Optional, Tuple
 
@@ -377,9 +379,25 @@ def register():
                      lambda: 'resize_aa: positive sizes, a down-scale ratio of at most 8 per axis')
         return torch.empty((frames.shape[0], 3, oh, ow), dtype=torch.float32 if out == 'float32' else torch.uint8, device=frames.device)
 
+    @op('jpeg_encode')
+    def jpeg_encode(x: torch.Tensor, h: int, w: int, fmt: str, quality: int, restart: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        dst, offsets, sizes = ops.jpeg_encode_device(x, h, w, fmt, quality, restart or None)
+        return dst, offsets.clone(), sizes.clone()                      # (fresh tensors: the two are rows of one buffer)
+
+    @jpeg_encode.register_fake
+    def _(x, h, w, fmt, quality, restart):
+        from . import jpeg, yuv
+        torch._check(fmt in jpeg.FORMATS, lambda: "jpeg_encode: fmt must be 'i420' or 'i444'")
+        torch._check(1 <= quality <= 100 and 0 <= restart <= 65535, lambda: 'jpeg_encode: quality 1..100, restart 0 (default) | 1..65535')
+        torch._check(2 <= h <= 65535 and 2 <= w <= 65535 and h % 2 == 0 and w % 2 == 0 and x.dtype == torch.uint8 and x.dim() == 3
+                     and tuple(x.shape[-2:]) == yuv.frame_shape(h, w, fmt), lambda: 'jpeg_encode takes [B, rows, w] uint8 frames of even h and w')
+        n = x.shape[0]
+        return (torch.empty(n * jpeg.capacity(h, w, fmt, restart or None), dtype=torch.uint8, device=x.device),
+                torch.empty(n, dtype=torch.int64, device=x.device), torch.empty(n, dtype=torch.int64, device=x.device))
+
 
 OP_NAMES = ('conv_mfma', 'conv24', 'resblock', 'resblock24_chain', 'resblock24_chain_batch', 'conv24_batch', 'warp_batch', 'match_argmax', 'warp', 'warp_planar', 'spynet_level_input', 'block_gather',
             'block_gather_rgb', 'aligned_sample', 'resize', 'pack_nhwc16', 'unpack_nhwc16', 'ingest_u8', 'score_frames', 'score_regions', 'result_to_yuv420', 'yuv420_to_rgb', 'result_to_yuv',
-            'yuv_to_rgb', 'resize_aa')
+            'yuv_to_rgb', 'resize_aa', 'jpeg_encode')
 
 register()

@@ -7,6 +7,7 @@ into a .y4m file, Y'CbCr on both sides of the network (4:2:0, 4:2:2 or 4:4:4; ce
         [--in_siting centre|left] [--out_chroma 420|422|444] [--out_siting centre|left]
         [--in_down K [--score scores.txt]] [--out_size WxH]
         [--io sync|stream|auto] [--io_depth 2] [--io_timeout 120]
+        [--out_format y4m|mjpeg] [--jpeg_quality 90]
 
 The files are read frame by frame (yuv.Y4MReader), the windows are the reference's (evalrun.window_indices: clip edges replicate
 frames, data_loader/datasets.py:222-234), the network runs forward_group with frame ids, config.input_yuv taken from the files and
@@ -25,6 +26,14 @@ runs on those frames as RGB windows (uint8 from 8-bit files: what an LRx4 PNG ho
 (ops.score_frames): a line `frame psnr ssim` per frame and a final `mean` line.  --out_size WxH writes the result at another size:
 config.result_yuv off, each group's results through ops.resize_aa and ops.result_to_yuv.  All three are off by default, and off
 means the calls, the launches and the bytes of a run without them.
+
+--out sr.mjpeg (or --out_format mjpeg) writes an MJPEG stream: one baseline JPEG file per frame, back to back (jpeg.MJPEGWriter), the
+entropy-coded data made on the device (ops.jpeg_encode: about a tenth of the 4:2:0 bytes leaves it).  JFIF fixes the output's colour:
+config.result_yuv = 'i420' ('i444' with --out_chroma 444), BT.601, full range, centre-sited, 8 bits, whatever the input files say --
+--yuv_matrix and --yuv_range then describe the input only.  --out_chroma 422, --video_depth 10 and --out_siting left are refused; a
+10-bit input with an 8-bit JPEG result is fine, and --out_size, --in_down, --score, --scene_cut and --cuts combine with it as with
+y4m.  The stream carries no frame rate: ffmpeg reads it with -f mjpeg -framerate N.  Off by default: a run without the options makes
+no new launch and writes the bytes it wrote before.
 
 Pipes (--io).  Frames of this size come from a decoder process and go to an encoder process: --lr, --ref and --out may be FIFOs, one of
 --lr / --ref and --out may be '-' (with --out - every message goes to stderr):
@@ -92,6 +101,36 @@ def pair_mismatch(lr, ref):
     return None
 
 
+OUT_FORMATS = ('y4m', 'mjpeg')
+
+
+def out_format(fmt, out_path):
+    """EVAL.out_format checked and resolved: 'y4m' | 'mjpeg'; None: by the extension of a path, .mjpeg / .mjpg is mjpeg, everything
+    else (and '-' and file objects) y4m."""
+    if fmt is None:
+        return 'mjpeg' if isinstance(out_path, str) and out_path.lower().endswith(('.mjpeg', '.mjpg')) else 'y4m'
+    if fmt not in OUT_FORMATS:
+        raise ValueError('videorun: --out_format must be y4m or mjpeg (got %r)' % (fmt,))
+    return fmt
+
+
+def check_mjpeg(E):
+    """The refusals of an MJPEG result, one line each, and EVAL.jpeg_quality (None: 90) checked; the sampling of the result."""
+    from . import jpeg
+    out = getattr(E, 'out_chroma', None)
+    if out is not None and str(out) not in ('420', '444'):
+        raise ValueError('videorun: an mjpeg result is 4:2:0 or 4:4:4 (--out_chroma %s is not built)' % (out,))
+    if getattr(E, 'video_depth', None) not in (None, 8):
+        raise ValueError('videorun: an mjpeg result has 8 bits per sample (got --video_depth %s)' % (E.video_depth,))
+    if getattr(E, 'out_siting', None) not in (None, 'centre'):
+        raise ValueError("videorun: an mjpeg result has centre-sited chroma, as JFIF defines it (got --out_siting %s)" % (E.out_siting,))
+    try:
+        E.jpeg_quality = jpeg.check_quality(90 if getattr(E, 'jpeg_quality', None) is None else E.jpeg_quality)
+    except ValueError:
+        raise ValueError('videorun: --jpeg_quality must be an integer 1..100 (got %r)' % (E.jpeg_quality,))
+    return str(out or '420')
+
+
 def configure(config, reader):
     """The run's fields of `config` from the LR file: input_yuv (always the files' format), input_yuv_siting (the reader's: the file's,
     or open_pair's override), input_yuv_range (the file's XCOLORRANGE unless set: EVAL.input_range_set), result_yuv (by
@@ -99,8 +138,12 @@ def configure(config, reader):
     (EVAL.out_siting; None: 'left' for 4:2:2 output, which is what its tag means, else the input's).
     EVAL.in_down (K; None: off): input_yuv is None -- the network gets RGB windows, run() decodes and down-scales the files' frames;
     the file must be K times an even size.  EVAL.out_size ((W, H); None: off): result_yuv is None -- run() resizes and converts -- and
-    the format the run would have used is left in EVAL.out_yuv (always set).  EVAL.score_file needs in_down == config.scale."""
+    the format the run would have used is left in EVAL.out_yuv (always set).  EVAL.score_file needs in_down == config.scale.
+    EVAL.out_format == 'mjpeg': the result is what JFIF means -- 'i420' ('i444' under out_chroma 444), 8 bits, and config.yuv_matrix =
+    'bt601', yuv_range = 'full', yuv_siting = 'centre' for the output, whatever the files say (check_mjpeg has the refusals)."""
     E = config.EVAL
+    mjpeg = getattr(E, 'out_format', None) == 'mjpeg'
+    mjpeg_sampling = check_mjpeg(E) if mjpeg else None
     down, size, score = check_in_down(getattr(E, 'in_down', None)), check_out_size(getattr(E, 'out_size', None)), getattr(E, 'score_file', None)
     if score is not None and down != int(config.scale):
         raise ValueError('videorun: --score needs --in_down %d, the scale of the config: the result is scored against the file frame '
@@ -114,22 +157,32 @@ def configure(config, reader):
     E.in_down, E.out_size, E.score_file = down, size, score
     config.input_yuv = reader.fmt if down is None else None
     config.input_yuv_siting = reader.siting
-    out = getattr(E, 'out_chroma', None) or sampling_of(reader.fmt)
+    out = mjpeg_sampling or getattr(E, 'out_chroma', None) or sampling_of(reader.fmt)
     if str(out) not in ('420', '422', '444'):
         raise ValueError('videorun: --out_chroma must be 420, 422 or 444 (got %r)' % (out,))
-    siting = getattr(E, 'out_siting', None) or ('left' if str(out) == '422' else reader.siting)
+    siting = 'centre' if mjpeg else getattr(E, 'out_siting', None) or ('left' if str(out) == '422' else reader.siting)
     try:
         config.yuv_siting = check_siting(siting)
     except ValueError:
         raise ValueError("videorun: --out_siting must be 'centre' or 'left' (got %r)" % (siting,))
     if not getattr(E, 'input_range_set', False):
         config.input_yuv_range = reader.range
-    depth = getattr(E, 'video_depth', None) or depth_of(reader.fmt)
+    depth = 8 if mjpeg else getattr(E, 'video_depth', None) or depth_of(reader.fmt)
     if depth not in (8, 10):
         raise ValueError('videorun: --video_depth must be 8 or 10 (got %r)' % (depth,))
     E.out_yuv = 'i%s%s' % (out, '' if depth == 8 else 'p10')
     config.result_yuv = E.out_yuv if size is None else None
+    if mjpeg:
+        config.yuv_matrix, config.yuv_range = 'bt601', 'full'
     return config
+
+
+def open_writer(E, out_path, out_hw, fps, out_range, siting):
+    """The run's writer: a yuv.Y4MWriter, or a jpeg.MJPEGWriter under EVAL.out_format == 'mjpeg'."""
+    if getattr(E, 'out_format', None) == 'mjpeg':
+        from .jpeg import MJPEGWriter
+        return MJPEGWriter(out_path)
+    return Y4MWriter(out_path, out_hw[0], out_hw[1], E.out_yuv, fps, out_range, siting)
 
 
 def check_in_down(k):
@@ -172,6 +225,7 @@ def run(config, lr_path, ref_path, out_path, net=None):
         raise ValueError('videorun: scene_cut and cuts exclude each other')
     if threshold is not None:
         threshold = scene.check_threshold(threshold)
+    E.out_format = out_format(getattr(E, 'out_format', None), out_path)
     if io_mode(getattr(E, 'io', None), lr_path, ref_path, out_path) == 'stream':
         return run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts)
     lr, ref = open_pair(lr_path, ref_path, getattr(E, 'in_siting', None))
@@ -186,7 +240,8 @@ def run(config, lr_path, ref_path, out_path, net=None):
         nc = net.Network.config
         down, size, score_file = E.in_down, E.out_size, E.score_file
         n = lr.length
-        writer = Y4MWriter(out_path, out_hw[0], out_hw[1], E.out_yuv, lr.fps, out_range, config.yuv_siting)
+        writer = open_writer(E, out_path, out_hw, lr.fps, out_range, config.yuv_siting)
+        mjpeg = E.out_format == 'mjpeg'
         scores = []
         was_pipelined = bool(getattr(nc, 'pipelined', False))
         net.Network.set_pipelined(True)
@@ -266,11 +321,16 @@ def run(config, lr_path, ref_path, out_path, net=None):
                     sc = ops.score_frames([r[0] for r in got['result']], [small[f][2] for f in fs]).cpu().tolist()
                     scores.extend((f, metrics.psnr_from_mse(m), s_) for f, (m, s_) in zip(fs, sc))
                 if size is None:
-                    ys = [y[0].cpu().numpy() for y in got['yuv']]
+                    ys = [y[0] for y in got['yuv']]
                 else:
                     from . import ops
                     ys = resized_yuv(ops, [r[0] for r in got['result']], size, E.out_yuv, getattr(config, 'yuv_matrix', None) or 'bt709', out_range,
-                                     config.yuv_siting).cpu().numpy()
+                                     config.yuv_siting)
+                if mjpeg:                                 # (the files of the group: only the compressed bytes leave the device)
+                    from . import ops
+                    ys = ops.jpeg_encode(ys, out_hw[0], out_hw[1], E.out_yuv, E.jpeg_quality)
+                else:
+                    ys = [y.cpu().numpy() for y in ys] if size is None else ys.cpu().numpy()
                 seconds += time.time() - t0
                 for y in ys:
                     writer.write(y)
@@ -411,9 +471,20 @@ def run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts):
         nc = net.Network.config
         down, size, score_file = E.in_down, E.out_size, E.score_file
         decode = decode_args(config, lr) if down is not None else None
-        writer = Y4MWriter(out_path, out_hw[0], out_hw[1], E.out_yuv, lr.fps, out_range, config.yuv_siting)
-        out_pin = torch.empty(((D + 1) * G,) + frame_shape(out_hw[0], out_hw[1], E.out_yuv),
-                              dtype=sample_dtype(E.out_yuv)).pin_memory()
+        writer = open_writer(E, out_path, out_hw, lr.fps, out_range, config.yuv_siting)
+        mjpeg = E.out_format == 'mjpeg'
+        if mjpeg:
+            # a slot of the ring holds a file of up to the frame's own bytes: header, data, EOI (a larger one -- noise at quality 100 --
+            # takes the slow way in retire())
+            from . import jpeg
+            head = jpeg.header(out_hw[0], out_hw[1], E.out_yuv, E.jpeg_quality)
+            head_np = np.frombuffer(head, np.uint8)
+            slot = len(head) + int(np.prod(frame_shape(out_hw[0], out_hw[1], E.out_yuv))) + 2
+            copies = torch.cuda.Stream(dev)               # the retired group's copies: never behind the groups still in flight
+            out_pin = torch.empty(((D + 1) * G, slot), dtype=torch.uint8).pin_memory()
+        else:
+            out_pin = torch.empty(((D + 1) * G,) + frame_shape(out_hw[0], out_hw[1], E.out_yuv),
+                                  dtype=sample_dtype(E.out_yuv)).pin_memory()
         out_views = [out_pin[i].numpy() for i in range(out_pin.shape[0])]
         out_tens = dict((id(v), out_pin[i]) for i, v in enumerate(out_views))
         sink = streamio.FrameSink(io, writer, out_views, sink_name(out_path), timeout)
@@ -441,9 +512,31 @@ def run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts):
                 scores.extend((f, metrics.psnr_from_mse(m), s_) for f, (m, s_) in zip(g['fs'], g['scores'].tolist()))
             for src, b in g['staged']:
                 src.give(b)
+            if g['jpeg'] is not None:
+                g['out'] = retire_jpeg(*g['jpeg'])
             for b in g['out']:
-                sink.put(b)
+                sink.put(*b) if isinstance(b, tuple) else sink.put(b)
             stats['frames'] += len(g['out'])
+
+        def retire_jpeg(dst, meta):
+            """The files of a retired group: its sizes came with its event; exactly the compressed bytes of every frame are copied into
+            a slot of the pinned ring, between the header and EOI the host writes there.  -> [(buffer, length, data)] for sink.put."""
+            offs, sizes = meta[0].tolist(), meta[1].tolist()
+            out = []
+            with torch.cuda.stream(copies):
+                for o, n in zip(offs, sizes):
+                    b = sink.take()
+                    if len(head) + n + 2 <= slot:
+                        out_tens[id(b)][len(head):len(head) + n].copy_(dst[o:o + n], non_blocking=True)
+                        out.append((b, len(head) + n + 2, None))
+                    else:
+                        out.append((b, None, jpeg.assemble(head, dst[o:o + n].cpu().numpy().tobytes())))
+            copies.synchronize()
+            for b, n, data in out:
+                if data is None:
+                    b[:len(head)] = head_np
+                    b[n - 2:n] = (0xff, 0xd9)
+            return out
 
         def read_to(upto):
             """Frames [nread, upto) of both streams, as far as they go, into the store -- ONE upload per file frame -- and classified."""
@@ -521,13 +614,20 @@ def run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts):
                 else:
                     ys = resized_yuv(ops, [r[0] for r in got['result']], size, E.out_yuv, getattr(config, 'yuv_matrix', None) or 'bt709', out_range,
                                      config.yuv_siting)
-                out = []
-                for y in ys:
-                    out.append(sink.take())
-                    out_tens[id(out[-1])].copy_(y, non_blocking=True)
+                out, enc = [], None
+                if mjpeg:                                 # the encode goes out with the group; its sizes come back with its event
+                    dst, offsets, sizes = ops.jpeg_encode_device(ys, out_hw[0], out_hw[1], E.out_yuv, E.jpeg_quality)
+                    meta = torch.empty((2, len(ys)), dtype=torch.int64).pin_memory()
+                    meta[0].copy_(offsets, non_blocking=True)
+                    meta[1].copy_(sizes, non_blocking=True)
+                    enc = (dst, meta)
+                else:
+                    for y in ys:
+                        out.append(sink.take())
+                        out_tens[id(out[-1])].copy_(y, non_blocking=True)
                 event = torch.cuda.Event()
                 event.record()
-                flight.append(dict(event=event, fs=fs, out=out, staged=staged, held=held, scores=sc, keep=(lrs, rfs, got, ys)))
+                flight.append(dict(event=event, fs=fs, out=out, staged=staged, held=held, scores=sc, jpeg=enc, keep=(lrs, rfs, got, ys)))
                 staged = []
                 stats['groups'] += 1
                 stats['max_in_flight'] = max(stats['max_in_flight'], len(flight))
@@ -576,7 +676,8 @@ def prepare(config, lr, net=None):
             load_checkpoint(net, config.EVAL.ckpt_abs_name)
     nc = net.Network.config
     if nc is not config:                              # (a caller's net may carry a config of its own)
-        for k in ('input_yuv', 'input_yuv_range', 'input_yuv_siting', 'result_yuv', 'yuv_siting'):
+        for k in ('input_yuv', 'input_yuv_range', 'input_yuv_siting', 'result_yuv', 'yuv_siting') + (
+                ('yuv_matrix', 'yuv_range') if getattr(E, 'out_format', None) == 'mjpeg' else ()):
             setattr(nc, k, getattr(config, k))
     down, size = E.in_down, E.out_size
     if net.Network._engines and (net.Network._engines[0].input_yuv is None) != (down is not None):
@@ -639,7 +740,11 @@ def build_config(argv=None):
     ap.add_argument('--ckpt_abs_name', '-ckpt_abs_name', type=str, default=None)
     ap.add_argument('--lr', required=True, help='the ultra-wide LR stream (.y4m: C420jpeg, C420mpeg2, C420p10, C422, C444 and their 10-bit forms)')
     ap.add_argument('--ref', required=True, help='the wide reference stream (.y4m of the same geometry, format and length)')
-    ap.add_argument('--out', required=True, help='the result (.y4m)')
+    ap.add_argument('--out', required=True, help='the result (.y4m; .mjpeg / .mjpg: an MJPEG stream)')
+    ap.add_argument('--out_format', default=None, choices=list(OUT_FORMATS),
+                    help='y4m, or mjpeg: one baseline JPEG per frame, coded on the device, BT.601 full range as JFIF defines it '
+                         '(default: by the extension of --out, .mjpeg / .mjpg is mjpeg)')
+    ap.add_argument('--jpeg_quality', type=int, default=90, metavar='Q', help='--out_format mjpeg: the quality 1..100 (default 90)')
     ap.add_argument('--frame_num', type=int, default=5)
     ap.add_argument('--frame_group', type=int, default=4)
     ap.add_argument('--video_depth', type=int, default=None, choices=[8, 10], help='bits per sample of --out (default: the input files\')')
@@ -702,6 +807,9 @@ def build_config(argv=None):
     if E.score_file is not None and E.in_down != int(cfg.scale):
         raise ValueError('videorun: --score needs --in_down %d, the scale of the config (got --in_down %s)' % (int(cfg.scale), E.in_down))
     E.io_depth, E.io_timeout = check_io_depth(args.io_depth), check_io_timeout(args.io_timeout)
+    E.out_format, E.jpeg_quality = out_format(args.out_format, args.out), args.jpeg_quality
+    if E.out_format == 'mjpeg':
+        check_mjpeg(E)
     E.io = io_mode(args.io, args.lr, args.ref, args.out)
     cfg.device, cfg.cuda = 'cuda', True
     return cfg, args
