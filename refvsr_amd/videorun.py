@@ -17,7 +17,7 @@ left; --in_siting overrides what a file says); the output keeps both unless told
 
 A file with cuts (--scene_cut T: found from the LR stream's luma, ops.luma_sad + scene.py; --cuts: given) is run as the reference would
 run its scenes as separate clips: windows clamped at the cuts, no group across one, Network.reset() and is_first_frame at each
-(scene.plan_groups / scene.GroupPlanner).  With neither option the file is one clip, as before.
+(scene.GroupPlanner).  With neither option the file is one clip, as before.
 
 --in_down K (2..8) evaluates the way the paper does: every file frame is decoded once at file size (ops.yuv_to_frames) and down-scaled
 once by K with the antialiased bicubic ops.resize_aa -- the 'BI' degradation that made the dataset's LRx4 folders -- and the network
@@ -41,17 +41,22 @@ Pipes (--io).  Frames of this size come from a decoder process and go to an enco
     DECODER .. | python -m refvsr_amd.videorun .. --lr - --ref w.fifo --out - | ENCODER ..
 
 --io sync is the loop above: read, stack and upload, forward_group, read back, write, one after the other on one thread, three
-regular files.  --io stream is the same plan and the same calls -- configure(), prepare(), scene.GroupPlanner with the length unknown,
-forward_group with the same windows, ids and is_first_frame, Network.reset() at each scene -- and the same bytes, with the I/O around
-the calls instead of between them (run_stream): one reader thread per input and one writer thread (streamio.py; host memory and file
-descriptors only, every GPU call is made on the caller's thread and stream); every file frame goes to the device once, from a pinned
-staging ring into a frame store, and the windows are stacked there (the sync loop uploads a frame t times); results leave through a
-pinned ring behind an event, --io_depth groups in flight, only the oldest waited for.  --io auto (default) is stream when one of the
-three ends is '-' or no regular file, else sync.  An input that delivers nothing for --io_timeout seconds ends the run instead of
-hanging it.  config.EVAL.io_stats says where the wall time went; profiles/videorun_stream_timing.txt has it measured.
+regular files (run_sync).  --io stream is the same plan and the same calls -- configure(), prepare(), scene.GroupPlanner with the
+length unknown, forward_group with the same windows, ids and is_first_frame, Network.reset() at each scene -- and the same bytes, with
+the I/O around the calls instead of between them (run_stream): one reader thread per input and one writer thread (streamio.py; host
+memory and file descriptors only, every GPU call is made on the caller's thread and stream); every file frame goes to the device once,
+from a pinned staging ring into a frame store, and the windows are stacked there (the sync loop uploads a frame t times); results leave
+through a pinned ring behind an event, --io_depth groups in flight, only the oldest waited for.  --io auto (default) is stream when one
+of the three ends is '-' or no regular file, else sync.  An input that delivers nothing for --io_timeout seconds ends the run instead
+of hanging it.  config.EVAL.io_stats says where the wall time went; profiles/videorun_stream_timing.txt has it measured.
+
+What a feature adds is written once (DESIGN.md 2.r'; tests/test_videorun_runs.py pins both loops call by call on the CPU): options()
+is EVAL as one checked record, check_pair() / checked_cuts() the header stage, prepare() gives the one Plan both loops read, classify()
+turns frames into scenes, group_step() is a group on the device, finish() and pipelined() the tail; a loop keeps how frames come and go.
 """
 import argparse
 import collections
+import contextlib
 import os
 import sys
 import time
@@ -61,47 +66,12 @@ import torch
 
 from . import metrics, scene
 from .evalrun import load_checkpoint
-from .yuv import (Y4MReader, Y4MWriter, check_chroma, check_matrix, check_range, check_siting, depth_of, effective_siting, resolve_input,
+from .yuv import (Y4MReader, Y4MWriter, check_chroma, check_matrix, check_range, depth_of, effective_siting, resolve_input,
                   sampling_of, sink_name)
 
 
-def open_pair(lr_path, ref_path, siting=None):
-    """The two readers of a run; ValueError (one line) unless geometry, format (sampling, depth and chroma siting) and frame count
-    agree.  siting ('centre' | 'left'; --in_siting): what both files' chroma siting is taken to be, whatever their headers say."""
-    lr = Y4MReader(lr_path)
-    try:
-        ref = Y4MReader(ref_path)
-        if siting is not None:
-            lr.siting, ref.siting = effective_siting(lr.fmt, siting), effective_siting(ref.fmt, siting)
-    except Exception:
-        lr.close()
-        raise
-    bad = pair_mismatch(lr, ref)
-    if bad:
-        pass
-    elif lr.length != ref.length:
-        bad = 'frame count differs (%d and %d)' % (lr.length, ref.length)
-    elif lr.length < 1:
-        bad = 'no frames'
-    if bad:
-        lr.close()
-        ref.close()
-        raise ValueError('videorun: %s and %s: %s' % (lr_path, ref_path, bad))
-    return lr, ref
-
-
-def pair_mismatch(lr, ref):
-    """What keeps two readers from being the streams of one run -- geometry, format, chroma siting -- or None."""
-    if (lr.h, lr.w) != (ref.h, ref.w):
-        return 'geometry differs (%d x %d and %d x %d)' % (lr.h, lr.w, ref.h, ref.w)
-    if lr.fmt != ref.fmt:
-        return 'format differs (%s and %s)' % (lr.fmt, ref.fmt)
-    if lr.siting != ref.siting:
-        return 'format differs (%s with %s- and %s-sited chroma; --in_siting declares one for both)' % (lr.fmt, lr.siting, ref.siting)
-    return None
-
-
 OUT_FORMATS = ('y4m', 'mjpeg')
+IO_MODES = ('sync', 'stream', 'auto')
 
 
 def out_format(fmt, out_path):
@@ -114,84 +84,19 @@ def out_format(fmt, out_path):
     return fmt
 
 
-def check_mjpeg(E):
-    """The refusals of an MJPEG result, one line each, and EVAL.jpeg_quality (None: 90) checked; the sampling of the result."""
-    from . import jpeg
-    out = getattr(E, 'out_chroma', None)
-    if out is not None and str(out) not in ('420', '444'):
-        raise ValueError('videorun: an mjpeg result is 4:2:0 or 4:4:4 (--out_chroma %s is not built)' % (out,))
-    if getattr(E, 'video_depth', None) not in (None, 8):
-        raise ValueError('videorun: an mjpeg result has 8 bits per sample (got --video_depth %s)' % (E.video_depth,))
-    if getattr(E, 'out_siting', None) not in (None, 'centre'):
-        raise ValueError("videorun: an mjpeg result has centre-sited chroma, as JFIF defines it (got --out_siting %s)" % (E.out_siting,))
-    try:
-        E.jpeg_quality = jpeg.check_quality(90 if getattr(E, 'jpeg_quality', None) is None else E.jpeg_quality)
-    except ValueError:
-        raise ValueError('videorun: --jpeg_quality must be an integer 1..100 (got %r)' % (E.jpeg_quality,))
-    return str(out or '420')
+def _integer(flag, lo, hi, default):
+    """check(v): an integer lo..hi; None: the default."""
+    def check(v):
+        if v is None:
+            return default
+        if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError('videorun: %s must be an integer %d..%d (got %r)' % (flag, lo, hi, v))
+        return int(v)
+    return check
 
 
-def configure(config, reader):
-    """The run's fields of `config` from the LR file: input_yuv (always the files' format), input_yuv_siting (the reader's: the file's,
-    or open_pair's override), input_yuv_range (the file's XCOLORRANGE unless set: EVAL.input_range_set), result_yuv (by
-    EVAL.video_depth; None: the input's depth -- and by EVAL.out_chroma '420' | '422' | '444'; None: the input's sampling), yuv_siting
-    (EVAL.out_siting; None: 'left' for 4:2:2 output, which is what its tag means, else the input's).
-    EVAL.in_down (K; None: off): input_yuv is None -- the network gets RGB windows, run() decodes and down-scales the files' frames;
-    the file must be K times an even size.  EVAL.out_size ((W, H); None: off): result_yuv is None -- run() resizes and converts -- and
-    the format the run would have used is left in EVAL.out_yuv (always set).  EVAL.score_file needs in_down == config.scale.
-    EVAL.out_format == 'mjpeg': the result is what JFIF means -- 'i420' ('i444' under out_chroma 444), 8 bits, and config.yuv_matrix =
-    'bt601', yuv_range = 'full', yuv_siting = 'centre' for the output, whatever the files say (check_mjpeg has the refusals)."""
-    E = config.EVAL
-    mjpeg = getattr(E, 'out_format', None) == 'mjpeg'
-    mjpeg_sampling = check_mjpeg(E) if mjpeg else None
-    down, size, score = check_in_down(getattr(E, 'in_down', None)), check_out_size(getattr(E, 'out_size', None)), getattr(E, 'score_file', None)
-    if score is not None and down != int(config.scale):
-        raise ValueError('videorun: --score needs --in_down %d, the scale of the config: the result is scored against the file frame '
-                         '(got --in_down %s)' % (int(config.scale), down))
-    if down is not None and (reader.h % down or reader.w % down or (reader.h // down) % 2 or (reader.w // down) % 2):
-        raise ValueError('videorun: --in_down %d needs frames of %d times an even size (got %d x %d)' % (down, down, reader.w, reader.h))
-    if size is not None:
-        rh, rw = (int(config.scale) * (v // (down or 1)) for v in (reader.h, reader.w))
-        if rw > 8 * size[0] or rh > 8 * size[1]:
-            raise ValueError('videorun: --out_size %dx%d is less than an eighth of the %dx%d result on an axis' % (size + (rw, rh)))
-    E.in_down, E.out_size, E.score_file = down, size, score
-    config.input_yuv = reader.fmt if down is None else None
-    config.input_yuv_siting = reader.siting
-    out = mjpeg_sampling or getattr(E, 'out_chroma', None) or sampling_of(reader.fmt)
-    if str(out) not in ('420', '422', '444'):
-        raise ValueError('videorun: --out_chroma must be 420, 422 or 444 (got %r)' % (out,))
-    siting = 'centre' if mjpeg else getattr(E, 'out_siting', None) or ('left' if str(out) == '422' else reader.siting)
-    try:
-        config.yuv_siting = check_siting(siting)
-    except ValueError:
-        raise ValueError("videorun: --out_siting must be 'centre' or 'left' (got %r)" % (siting,))
-    if not getattr(E, 'input_range_set', False):
-        config.input_yuv_range = reader.range
-    depth = 8 if mjpeg else getattr(E, 'video_depth', None) or depth_of(reader.fmt)
-    if depth not in (8, 10):
-        raise ValueError('videorun: --video_depth must be 8 or 10 (got %r)' % (depth,))
-    E.out_yuv = 'i%s%s' % (out, '' if depth == 8 else 'p10')
-    config.result_yuv = E.out_yuv if size is None else None
-    if mjpeg:
-        config.yuv_matrix, config.yuv_range = 'bt601', 'full'
-    return config
-
-
-def open_writer(E, out_path, out_hw, fps, out_range, siting):
-    """The run's writer: a yuv.Y4MWriter, or a jpeg.MJPEGWriter under EVAL.out_format == 'mjpeg'."""
-    if getattr(E, 'out_format', None) == 'mjpeg':
-        from .jpeg import MJPEGWriter
-        return MJPEGWriter(out_path)
-    return Y4MWriter(out_path, out_hw[0], out_hw[1], E.out_yuv, fps, out_range, siting)
-
-
-def check_in_down(k):
-    """EVAL.in_down: None (off) or an integer 2..8."""
-    if k is None:
-        return None
-    if isinstance(k, bool) or int(k) != k or not 2 <= int(k) <= 8:
-        raise ValueError('videorun: --in_down must be an integer 2..8 (got %r)' % (k,))
-    return int(k)
+check_in_down = _integer('--in_down', 2, 8, None)     # EVAL.in_down: None (off) or K
+check_io_depth = _integer('--io_depth', 1, 4, 2)      # EVAL.io_depth: the groups in flight in the stream loop
 
 
 def check_out_size(size):
@@ -207,149 +112,76 @@ def check_out_size(size):
     return w, h
 
 
-def run(config, lr_path, ref_path, out_path, net=None):
-    """Super-resolve lr_path with ref_path into out_path; returns (frames written, seconds in the network calls).  config: a model
-    config (EVAL.frame_group, frame_num, yuv_matrix / yuv_range for the output, input_yuv_matrix / input_yuv_chroma for the input);
-    net: an SRNet built from that config (None: built here, EVAL.ckpt_abs_name loaded) -- its engines must not exist yet, they take
-    the input format from the config at their construction.
-    EVAL.scene_cut (a scene-score threshold in (0, 1]) or EVAL.cuts (frame indices in (0, n), increasing) make every scene a clip of
-    its own; the cuts the run used are left in config.EVAL.scene_cuts (a tuple; empty without the options), and under scene_cut the
-    seconds include the detector's upload and its ops.luma_sad call per group.
-    EVAL.in_down / EVAL.score_file / EVAL.out_size: the module header; the scores are left in config.EVAL.scores, a list of (frame,
-    psnr, ssim), and the seconds include the decode, the resizes and the scorer.
-    EVAL.io ('sync' | 'stream' | 'auto'; None: 'auto'), EVAL.io_depth, EVAL.io_timeout: the module header and run_stream(), which takes
-    over when the mode is 'stream' -- the paths may then be '-', FIFOs or binary file objects, and the seconds are the loop's wall time."""
-    E = config.EVAL
-    threshold, cuts = getattr(E, 'scene_cut', None), getattr(E, 'cuts', None)
-    if threshold is not None and cuts is not None:
-        raise ValueError('videorun: scene_cut and cuts exclude each other')
-    if threshold is not None:
-        threshold = scene.check_threshold(threshold)
-    E.out_format = out_format(getattr(E, 'out_format', None), out_path)
-    if io_mode(getattr(E, 'io', None), lr_path, ref_path, out_path) == 'stream':
-        return run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts)
-    lr, ref = open_pair(lr_path, ref_path, getattr(E, 'in_siting', None))
-    writer = None
-    was_pipelined = None
+def check_io_timeout(s):
+    """EVAL.io_timeout: the seconds a source may deliver nothing, or the sink take nothing, before the run ends (None: 120)."""
+    if s is None:
+        return 120.0
     try:
+        v = float(s)
+    except (TypeError, ValueError):
+        v = float('nan')
+    if not 0.0 < v < float('inf'):
+        raise ValueError('videorun: --io_timeout must be a positive number of seconds (got %r)' % (s,))
+    return v
+
+
+def _one_of(flag, values, text):
+    """check(v): None stays None (the run decides from the input), anything else is one of `values` (compared as written)."""
+    def check(v):
+        if v is not None and str(v) not in values:
+            raise ValueError('videorun: %s must be %s (got %r)' % (flag, text, v))
+        return v
+    return check
+
+
+def _or(default):
+    return lambda v: default if v is None else v
+
+
+# The EVAL fields videorun knows: name -> check; check(value) is the checked value, check(None) the default of a field that is not set.
+OPTIONS = collections.OrderedDict((
+    ('ckpt_abs_name', _or(None)), ('frame_group', lambda g: max(1, int(4 if g is None else g or 1))),
+    ('scene_cut', lambda th: None if th is None else scene.check_threshold(th)), ('cuts', _or(None)),
+    ('in_siting', _or(None)), ('out_chroma', _one_of('--out_chroma', ('420', '422', '444'), '420, 422 or 444')),
+    ('out_siting', _one_of('--out_siting', ('centre', 'left'), "'centre' or 'left'")), ('video_depth', _one_of('--video_depth', ('8', '10'), '8 or 10')),
+    ('in_down', check_in_down), ('score_file', _or(None)), ('out_size', check_out_size),
+    ('io', _or('auto')), ('io_depth', check_io_depth), ('io_timeout', check_io_timeout),
+    ('out_format', _or(None)), ('jpeg_quality', _or(90)),
+    # input_range_set: config.input_yuv_range is given, not the file's to set; out_range_from_input: config.yuv_range is the LR header's
+    ('input_range_set', bool), ('out_range_from_input', bool),
+))
+Options = collections.namedtuple('Options', tuple(OPTIONS))
+
+
+def options(config, paths=None):
+    """config.EVAL as a checked, immutable record (OPTIONS), or the one-line ValueError of a field or of a pair of fields (refusals).
+    paths = (lr, ref, out): out_format and io are resolved against them -- 'y4m' | 'mjpeg' and 'sync' | 'stream'; without them
+    (configure() called on its own) they stay what EVAL says."""
+    o = dict((name, check(getattr(config.EVAL, name, None))) for name, check in OPTIONS.items())
+    if paths is not None:
+        o['out_format'], o['io'] = out_format(o['out_format'], paths[2]), io_mode(o['io'], *paths)
+    refusals(o, int(config.scale))
+    return Options(**o)
+
+
+def refusals(o, scale):
+    """What the fields refuse of each other, one line each."""
+    if o['scene_cut'] is not None and o['cuts'] is not None:
+        raise ValueError('videorun: scene_cut and cuts exclude each other')
+    if o['score_file'] is not None and o['in_down'] != scale:
+        raise ValueError('videorun: --score needs --in_down %d, the scale of the config (got --in_down %s)' % (scale, o['in_down']))
+    if o['out_format'] == 'mjpeg':
+        from . import jpeg
+        if o['out_chroma'] is not None and str(o['out_chroma']) not in ('420', '444'):
+            raise ValueError('videorun: an mjpeg result is 4:2:0 or 4:4:4 (--out_chroma %s is not built)' % (o['out_chroma'],))
+        if o['video_depth'] not in (None, 8):
+            raise ValueError('videorun: an mjpeg result has 8 bits per sample (got --video_depth %s)' % (o['video_depth'],))
+        if o['out_siting'] not in (None, 'centre'):
+            raise ValueError("videorun: an mjpeg result has centre-sited chroma, as JFIF defines it (got --out_siting %s)" % (o['out_siting'],))
         try:
-            cuts = scene.check_cuts(cuts or (), lr.length)
-        except ValueError as e:
-            raise ValueError('videorun: %s (%d frames)' % (e, lr.length))
-        net, dev, t, G, out_range, out_hw = prepare(config, lr, net)
-        nc = net.Network.config
-        down, size, score_file = E.in_down, E.out_size, E.score_file
-        n = lr.length
-        writer = open_writer(E, out_path, out_hw, lr.fps, out_range, config.yuv_siting)
-        mjpeg = E.out_format == 'mjpeg'
-        scores = []
-        was_pipelined = bool(getattr(nc, 'pipelined', False))
-        net.Network.set_pipelined(True)
-        net.Network.reset()
-        held = collections.OrderedDict()                  # frame index -> (lr buffer, ref buffer): the frames the next windows read
-        nread, seconds = 0, 0.0
-
-        def read_to(upto):
-            """Frames [nread, upto) of both files into `held`; the new LR buffers."""
-            nonlocal nread
-            new = []
-            while nread < upto:
-                a, b = lr.read(), ref.read()
-                if a is None or b is None:
-                    raise ValueError('videorun: %s: truncated file' % (lr_path if a is None else ref_path))
-                held[nread] = (a, b)
-                new.append(a)
-                nread += 1
-            return new
-
-        small = {}                                        # --in_down: frame index -> (lr, ref) down-scaled [3, h / K, w / K] (+ the LR decode)
-
-        def down_scaled(wins):
-            """--in_down (down_scaled_windows): a file frame not seen yet goes to the device once."""
-            return down_scaled_windows(small, held, wins, lr, down, decode, score_file is not None,
-                                       lambda new: torch.from_numpy(np.stack([held[i][j] for j in (0, 1) for i in new])).to(dev))
-
-        if down is not None:
-            decode = decode_args(config, lr)
-
-        def detected_groups():
-            """The plan under --scene_cut, group by group: the new LR frames of a group and the last one before them go to the device
-            once, ONE ops.luma_sad call scores the new consecutive pairs, scene.SceneDetector turns the integers into cuts."""
-            nonlocal seconds
-            from . import ops
-            det = scene.SceneDetector(lr.h, lr.w, depth_of(lr.fmt), threshold)
-            planner = scene.GroupPlanner(n, t, G)
-            last = None                                   # the LR frame ahead of the next new ones
-            while not planner.done():
-                new = read_to(planner.need())
-                if new:
-                    t0 = time.time()
-                    if last is None:
-                        planner.push(False)               # (frame 0 opens the first scene)
-                    fr = ([] if last is None else [last]) + new
-                    if len(fr) > 1:
-                        x = torch.from_numpy(np.stack(fr)).to(dev)
-                        for sad in ops.luma_sad(x[1:], x[:-1], lr.h, lr.w, lr.fmt).cpu().tolist():
-                            planner.push(det.push(sad))
-                    last = new[-1]
-                    seconds += time.time() - t0
-                yield planner.pop()
-            found.extend(det.cuts)
-
-        found = []
-        if threshold is not None:
-            groups = detected_groups()
-        else:
-            found.extend(cuts)
-            groups = scene.plan_groups(n, t, G, cuts)
-        with torch.no_grad():
-            for fs, wins, first in groups:
-                read_to(max(i for w_ in wins for i in w_) + 1)
-                for k in [k for k in held if k < min(wins[0])]:
-                    del held[k]
-                t0 = time.time()
-                if first and fs[0] > 0:                   # a scene is a clip of its own: the state of the last one ends here
-                    net.Network.reset()
-                if down is None:
-                    lrs = torch.from_numpy(np.stack([np.stack([held[i][0] for i in w_]) for w_ in wins])).to(dev)
-                    rfs = torch.from_numpy(np.stack([np.stack([held[i][1] for i in w_]) for w_ in wins])).to(dev)
-                else:
-                    lrs, rfs = down_scaled(wins)
-                got = net.Network.forward_group(lrs, rfs, wins, is_first_frame=first)
-                if score_file is not None:                # (the unscaled result against the LR file frame: one 16-byte row per frame)
-                    from . import ops
-                    sc = ops.score_frames([r[0] for r in got['result']], [small[f][2] for f in fs]).cpu().tolist()
-                    scores.extend((f, metrics.psnr_from_mse(m), s_) for f, (m, s_) in zip(fs, sc))
-                if size is None:
-                    ys = [y[0] for y in got['yuv']]
-                else:
-                    from . import ops
-                    ys = resized_yuv(ops, [r[0] for r in got['result']], size, E.out_yuv, getattr(config, 'yuv_matrix', None) or 'bt709', out_range,
-                                     config.yuv_siting)
-                if mjpeg:                                 # (the files of the group: only the compressed bytes leave the device)
-                    from . import ops
-                    ys = ops.jpeg_encode(ys, out_hw[0], out_hw[1], E.out_yuv, E.jpeg_quality)
-                else:
-                    ys = [y.cpu().numpy() for y in ys] if size is None else ys.cpu().numpy()
-                seconds += time.time() - t0
-                for y in ys:
-                    writer.write(y)
-        config.EVAL.scene_cuts = tuple(found)
-        if score_file is not None:
-            config.EVAL.scores = scores
-            write_scores(score_file, scores)
-        return writer.frames, seconds
-    finally:
-        lr.close()
-        ref.close()
-        if writer is not None:
-            writer.close()
-        if was_pipelined is False:
-            torch.cuda.synchronize()
-            net.Network.set_pipelined(False)
-
-
-IO_MODES = ('sync', 'stream', 'auto')
+            o['jpeg_quality'] = jpeg.check_quality(o['jpeg_quality'])
+        except ValueError:
+            raise ValueError('videorun: --jpeg_quality must be an integer 1..100 (got %r)' % (o['jpeg_quality'],))
 
 
 def is_stream_end(p):
@@ -372,26 +204,317 @@ def io_mode(io, lr_path, ref_path, out_path):
     return 'stream' if io == 'stream' or piped else 'sync'
 
 
-def check_io_depth(d):
-    """EVAL.io_depth: the groups in flight in the stream loop, 1..4 (None: 2)."""
-    if d is None:
-        return 2
-    if isinstance(d, bool) or int(d) != d or not 1 <= int(d) <= 4:
-        raise ValueError('videorun: --io_depth must be an integer 1..4 (got %r)' % (d,))
-    return int(d)
+def open_pair(lr_path, ref_path, siting=None):
+    """The two readers of a run; ValueError (one line) unless geometry, format (sampling, depth and chroma siting) and frame count
+    agree.  siting ('centre' | 'left'; --in_siting): what both files' chroma siting is taken to be, whatever their headers say."""
+    with contextlib.ExitStack() as opened:
+        lr = opened.enter_context(Y4MReader(lr_path))
+        ref = opened.enter_context(Y4MReader(ref_path))
+        check_pair(lr, ref, siting, (lr_path, ref_path))
+        opened.pop_all()                              # (both stay open: the run closes them)
+    return lr, ref
 
 
-def check_io_timeout(s):
-    """EVAL.io_timeout: the seconds a source may deliver nothing, or the sink take nothing, before the run ends (None: 120)."""
-    if s is None:
-        return 120.0
+def check_pair(lr, ref, siting, names):
+    """The header stage of both loops: the --in_siting override, then the one-line ValueError of two readers that are not the streams
+    of one run -- pair_mismatch, and where the lengths are known (regular files) a frame count that differs or is 0."""
+    if siting is not None:
+        lr.siting, ref.siting = effective_siting(lr.fmt, siting), effective_siting(ref.fmt, siting)
+    bad = pair_mismatch(lr, ref)
+    if bad is None and lr.length is not None and ref.length is not None:
+        if lr.length != ref.length:
+            bad = 'frame count differs (%d and %d)' % (lr.length, ref.length)
+        elif lr.length < 1:
+            bad = 'no frames'
+    if bad:
+        raise ValueError('videorun: %s and %s: %s' % (names[0], names[1], bad))
+
+
+def pair_mismatch(lr, ref):
+    """What keeps two readers from being the streams of one run -- geometry, format, chroma siting -- or None."""
+    if (lr.h, lr.w) != (ref.h, ref.w):
+        return 'geometry differs (%d x %d and %d x %d)' % (lr.h, lr.w, ref.h, ref.w)
+    if lr.fmt != ref.fmt:
+        return 'format differs (%s and %s)' % (lr.fmt, ref.fmt)
+    if lr.siting != ref.siting:
+        return 'format differs (%s with %s- and %s-sited chroma; --in_siting declares one for both)' % (lr.fmt, lr.siting, ref.siting)
+    return None
+
+
+def checked_cuts(cuts, n=None):
+    """EVAL.cuts as scene.check_cuts takes them (n: the frame count, where it is known), its refusal in videorun's words."""
     try:
-        v = float(s)
-    except (TypeError, ValueError):
-        v = float('nan')
-    if not 0.0 < v < float('inf'):
-        raise ValueError('videorun: --io_timeout must be a positive number of seconds (got %r)' % (s,))
-    return v
+        return scene.check_cuts(cuts or (), n)
+    except ValueError as e:
+        raise ValueError('videorun: %s%s' % (e, '' if n is None else ' (%d frames)' % n))
+
+
+def configure(config, reader, opt=None):
+    """The run's fields of `config` from the LR file: input_yuv (always the files' format), input_yuv_siting (the reader's: the file's,
+    or check_pair's override), input_yuv_range (the file's XCOLORRANGE unless set: EVAL.input_range_set), result_yuv (by
+    EVAL.video_depth; None: the input's depth -- and by EVAL.out_chroma '420' | '422' | '444'; None: the input's sampling), yuv_siting
+    (EVAL.out_siting; None: 'left' for 4:2:2 output, which is what its tag means, else the input's).
+    EVAL.in_down (K; None: off): input_yuv is None -- the network gets RGB windows, the run decodes and down-scales the files' frames;
+    the file must be K times an even size.  EVAL.out_size ((W, H); None: off): result_yuv is None -- the run resizes and converts --
+    and the format the run would have used is left in EVAL.out_yuv (always set).  EVAL.score_file needs in_down == config.scale.
+    EVAL.out_format == 'mjpeg': the result is what JFIF means -- 'i420' ('i444' under out_chroma 444), 8 bits, and config.yuv_matrix =
+    'bt601', yuv_range = 'full', yuv_siting = 'centre' for the output, whatever the files say (refusals() has what it refuses).
+    opt: the run's options() (None: taken from config.EVAL here)."""
+    E = config.EVAL
+    opt = opt or options(config)
+    mjpeg, down, size = opt.out_format == 'mjpeg', opt.in_down, opt.out_size
+    if down is not None and (reader.h % down or reader.w % down or (reader.h // down) % 2 or (reader.w // down) % 2):
+        raise ValueError('videorun: --in_down %d needs frames of %d times an even size (got %d x %d)' % (down, down, reader.w, reader.h))
+    if size is not None:
+        rh, rw = (int(config.scale) * (v // (down or 1)) for v in (reader.h, reader.w))
+        if rw > 8 * size[0] or rh > 8 * size[1]:
+            raise ValueError('videorun: --out_size %dx%d is less than an eighth of the %dx%d result on an axis' % (size + (rw, rh)))
+    E.in_down, E.out_size, E.score_file = down, size, opt.score_file
+    config.input_yuv = reader.fmt if down is None else None
+    config.input_yuv_siting = reader.siting
+    out = str(opt.out_chroma or ('420' if mjpeg else sampling_of(reader.fmt)))
+    config.yuv_siting = 'centre' if mjpeg else opt.out_siting or ('left' if out == '422' else reader.siting)
+    if not opt.input_range_set:
+        config.input_yuv_range = reader.range
+    depth = 8 if mjpeg else opt.video_depth or depth_of(reader.fmt)
+    E.out_yuv = 'i%s%s' % (out, '' if depth == 8 else 'p10')
+    config.result_yuv = E.out_yuv if size is None else None
+    if mjpeg:
+        E.jpeg_quality = opt.jpeg_quality
+        config.yuv_matrix, config.yuv_range = 'bt601', 'full'
+    return config
+
+
+# What both loops read of a run: t frames per window, G per group; down, size, score_file: --in_down K, --out_size (W, H), --score FILE
+# (None: off); decode: the arguments of ops.yuv_to_frames under --in_down; the output's format, (h, w), range, matrix, siting, JPEG quality
+Plan = collections.namedtuple('Plan', 'opt net dev t G down size score_file decode out_yuv out_hw out_range matrix siting mjpeg quality')
+
+
+def prepare(config, lr, net=None, opt=None):
+    """What both loops do between the LR header and the first frame: configure(), the network (built here unless passed in) with the
+    run's formats in its config, the refusals of a network that already runs otherwise.  Returns the run's Plan."""
+    opt = opt or options(config)
+    configure(config, lr, opt)
+    mjpeg, down, size = opt.out_format == 'mjpeg', opt.in_down, opt.out_size
+    if net is None:
+        from . import SRNet
+        net = SRNet(config).to('cuda').eval()
+        if opt.ckpt_abs_name:
+            load_checkpoint(net, opt.ckpt_abs_name)
+    nc = net.Network.config
+    if nc is not config:                              # (a caller's net may carry a config of its own)
+        for k in ('input_yuv', 'input_yuv_range', 'input_yuv_siting', 'result_yuv', 'yuv_siting') + (('yuv_matrix', 'yuv_range') if mjpeg else ()):
+            setattr(nc, k, getattr(config, k))
+    if net.Network._engines and (net.Network._engines[0].input_yuv is None) != (down is not None):
+        raise RuntimeError('videorun: the network passed in already runs %s config.input_yuv; pass a fresh one' % ('with' if down else 'without'))
+    if net.Network._engines and size is not None and net.Network._engines[0].result_yuv is not None:
+        raise RuntimeError('videorun: the network passed in already runs with config.result_yuv; pass a fresh one')
+    scale = int(config.scale)
+    rh, rw = (lr.h * scale, lr.w * scale) if down is None else (lr.h // down * scale, lr.w // down * scale)
+    decode = None
+    if down is not None:                              # fmt, matrix, range, chroma, siting of ops.yuv_to_frames for the files' frames
+        decode = (resolve_input(lr.fmt, getattr(config, 'input_yuv_matrix', None), getattr(config, 'input_yuv_range', None),
+                                getattr(config, 'input_yuv_chroma', None), lr.siting) + ('centre',))[:5]
+    return Plan(opt=opt, net=net, dev=next(net.parameters()).device, t=int(config.frame_num), G=opt.frame_group, down=down, size=size,
+                score_file=opt.score_file, decode=decode, out_yuv=config.EVAL.out_yuv,
+                out_hw=(rh, rw) if size is None else (size[1], size[0]), out_range=getattr(config, 'yuv_range', None) or 'limited',
+                matrix=getattr(config, 'yuv_matrix', None) or 'bt709', siting=config.yuv_siting, mjpeg=mjpeg, quality=opt.jpeg_quality)
+
+
+def open_writer(p, out_path, fps):
+    """The run's writer: a yuv.Y4MWriter, or a jpeg.MJPEGWriter for an MJPEG stream."""
+    if p.mjpeg:
+        from .jpeg import MJPEGWriter
+        return MJPEGWriter(out_path)
+    return Y4MWriter(out_path, p.out_hw[0], p.out_hw[1], p.out_yuv, fps, p.out_range, p.siting)
+
+
+def classify(planner, det, cutset, new, sads):
+    """Frames `new` (consecutive indices, just read) -> scenes, into the planner: membership in the given cuts, or under --scene_cut
+    (det: the scene.SceneDetector) frame 0 opens the first scene and ONE sads(pairs) call -- the loop's own: the SADs of the LR frames
+    k in `pairs` against their predecessors, as a list -- scores the new consecutive pairs."""
+    if det is None:
+        for k in new:
+            planner.push(k in cutset)
+        return
+    if new and new[0] == 0:
+        planner.push(False)                           # (frame 0 opens the first scene)
+    pairs = [k for k in new if k > 0]
+    if pairs:
+        for sad in sads(pairs):
+            planner.push(det.push(sad))
+
+
+def group_step(p, group, windows, small, retire_all=None):
+    """One group of the plan on the device, nothing read back: Network.reset() at a scene start (a scene is a clip of its own;
+    retire_all(): what the loop has to finish first), the windows, forward_group, the scores (the unscaled result against the LR file
+    frame, one 16-byte row per frame; None without --score) and the frames to write.  Returns (lrs, rfs, got, scores, frames)."""
+    from . import ops
+    fs, wins, first = group
+    if first and fs[0] > 0:
+        if retire_all is not None:
+            retire_all()
+        p.net.Network.reset()
+    lrs, rfs = windows(wins)
+    got = p.net.Network.forward_group(lrs, rfs, wins, is_first_frame=first)
+    sc = ops.score_frames([r[0] for r in got['result']], [small[f][2] for f in fs]) if p.score_file is not None else None
+    if p.size is None:
+        ys = [y[0] for y in got['yuv']]
+    else:
+        ys = resized_yuv(ops, [r[0] for r in got['result']], p.size, p.out_yuv, p.matrix, p.out_range, p.siting)
+    return lrs, rfs, got, sc, ys
+
+
+def down_scaled_windows(p, lr, small, held, wins, load):
+    """--in_down: the windows as RGB tensors [B, t, 3, h / K, w / K].  small: frame index -> (lr, ref) down-scaled (+ the LR decode
+    under --score: its ground truth), kept for the frames in `held` (the frames the run still holds).  A file frame not in it yet is
+    decoded once at file size (ops.yuv_to_frames) and resized once (ops.resize_aa: uint8 from 8-bit files, float32 from 10-bit ones)
+    -- the LR and the reference frames of a call together; load(new) -> their buffers on the device, [2 len(new), rows, w], LR first."""
+    from . import ops
+    for k in [k for k in small if k not in held]:
+        del small[k]
+    new = sorted({i for w_ in wins for i in w_ if i not in small})
+    if new:
+        full = ops.yuv_to_frames(load(new), lr.h, lr.w, *p.decode)
+        lo = ops.resize_aa(full, lr.h // p.down, lr.w // p.down, 'uint8' if depth_of(lr.fmt) == 8 else 'float32')
+        for q, i in enumerate(new):
+            small[i] = (lo[q], lo[len(new) + q], full[q] if p.score_file is not None else None)
+    return tuple(torch.stack([torch.stack([small[i][j] for i in w_]) for w_ in wins]) for j in (0, 1))
+
+
+def resized_yuv(ops, results, size, fmt, matrix, range, siting):
+    """--out_size: results [3, sh, sw] -> [B, rows, W] frames of `fmt` at size = (W, H): ops.resize_aa (clamped float32), then
+    ops.result_to_yuv -- one launch each per group."""
+    return ops.result_to_yuv(ops.resize_aa(results, size[1], size[0], 'float32', True), fmt, matrix, range, effective_siting(fmt, siting))
+
+
+def score_rows(fs, rows):
+    """--score: (frame, psnr, ssim) of the frames fs from their {mse, ssim} rows (a list, read back)."""
+    return [(f, metrics.psnr_from_mse(m), s_) for f, (m, s_) in zip(fs, rows)]
+
+
+def write_scores(path, scores):
+    """--score: `frame psnr ssim` per frame (repr of the float64s: they read back bit for bit), then `mean psnr ssim` -- the sums in
+    frame order over the count."""
+    with open(path, 'w') as f:
+        for fr, p, s_ in scores:
+            f.write('%d %r %r\n' % (fr, p, s_))
+        k = max(len(scores), 1)
+        f.write('mean %r %r\n' % (sum(p for _, p, _ in scores) / k, sum(s_ for _, _, s_ in scores) / k))
+
+
+def finish(config, p, cuts, scores):
+    """What a finished run leaves behind: EVAL.scene_cuts, and under --score EVAL.scores and the score file."""
+    config.EVAL.scene_cuts = tuple(cuts)
+    if p.score_file is not None:
+        config.EVAL.scores = scores
+        write_scores(p.score_file, scores)
+
+
+@contextlib.contextmanager
+def pipelined(net, always_synchronize=False):
+    """The network pipelined and reset for the run; on the way out, however the run ended, no device work is pending (where the state
+    is restored, or always: the stream loop's copies) and the network is pipelined or not as it was found."""
+    was = bool(getattr(net.Network.config, 'pipelined', False))
+    net.Network.set_pipelined(True)
+    net.Network.reset()
+    try:
+        yield
+    finally:
+        if always_synchronize or not was:
+            torch.cuda.synchronize()
+        if not was:
+            net.Network.set_pipelined(False)
+
+
+def run(config, lr_path, ref_path, out_path, net=None):
+    """Super-resolve lr_path with ref_path into out_path; returns (frames written, seconds in the network calls).  config: a model
+    config (EVAL.frame_group, frame_num, yuv_matrix / yuv_range for the output, input_yuv_matrix / input_yuv_chroma for the input);
+    net: an SRNet built from that config (None: built here, EVAL.ckpt_abs_name loaded) -- its engines must not exist yet, they take
+    the input format from the config at their construction.
+    EVAL.scene_cut (a scene-score threshold in (0, 1]) or EVAL.cuts (frame indices in (0, n), increasing) make every scene a clip of
+    its own; the cuts the run used are left in config.EVAL.scene_cuts (a tuple; empty without the options), and under scene_cut the
+    seconds include the detector's upload and its ops.luma_sad call per group.
+    EVAL.in_down / EVAL.score_file / EVAL.out_size: the module header; the scores are left in config.EVAL.scores, a list of (frame,
+    psnr, ssim), and the seconds include the decode, the resizes and the scorer.
+    EVAL.io ('sync' | 'stream' | 'auto'; None: 'auto'), EVAL.io_depth, EVAL.io_timeout: the module header and run_stream(), which takes
+    over when the mode is 'stream' -- the paths may then be '-', FIFOs or binary file objects, and the seconds are the loop's wall time."""
+    opt = options(config, (lr_path, ref_path, out_path))
+    config.EVAL.out_format = opt.out_format
+    return (run_stream if opt.io == 'stream' else run_sync)(config, opt, lr_path, ref_path, out_path, net)
+
+
+def run_sync(config, opt, lr_path, ref_path, out_path, net):
+    """run() under EVAL.io = 'sync': three regular files, one thread, one step after the other."""
+    from . import ops
+    lr, ref = open_pair(lr_path, ref_path, opt.in_siting)
+    writer = None
+    try:
+        n = lr.length
+        cuts = checked_cuts(opt.cuts, n)
+        if opt.out_range_from_input:
+            config.yuv_range = lr.range
+        p = prepare(config, lr, net, opt)
+        dev = p.dev
+        writer = open_writer(p, out_path, lr.fps)
+        planner = scene.GroupPlanner(n, p.t, p.G)
+        det = scene.SceneDetector(lr.h, lr.w, depth_of(lr.fmt), opt.scene_cut) if opt.scene_cut is not None else None
+        held = collections.OrderedDict()                  # frame index -> (lr buffer, ref buffer): the frames the next windows read
+        small = {}                                        # --in_down: frame index -> (lr, ref) down-scaled [3, h / K, w / K] (+ the LR decode)
+        scores, cutset = [], set(cuts)
+        nread, seconds = 0, 0.0
+
+        def read_to(upto):
+            """Frames [nread, upto) of both files into `held`; their indices."""
+            nonlocal nread
+            new = list(range(nread, upto))
+            for k in new:
+                a, b = lr.read(), ref.read()
+                if a is None or b is None:
+                    raise ValueError('videorun: %s: truncated file' % (lr_path if a is None else ref_path))
+                held[k] = (a, b)
+            nread = max(nread, upto)
+            return new
+
+        def sads(pairs):
+            """The detector's own upload -- the new LR frames and the one before them -- and its ONE ops.luma_sad call; timed."""
+            nonlocal seconds
+            t0 = time.time()
+            x = torch.from_numpy(np.stack([held[k][0] for k in range(pairs[0] - 1, pairs[-1] + 1)])).to(dev)
+            out = ops.luma_sad(x[1:], x[:-1], lr.h, lr.w, lr.fmt).cpu().tolist()
+            seconds += time.time() - t0
+            return out
+
+        def windows(wins):
+            """The host stack of t copies per window, uploaded; --in_down: a file frame not seen yet goes to the device once."""
+            if p.down is None:
+                return tuple(torch.from_numpy(np.stack([np.stack([held[i][j] for i in w_]) for w_ in wins])).to(dev) for j in (0, 1))
+            return down_scaled_windows(p, lr, small, held, wins, lambda new: torch.from_numpy(np.stack([held[i][j] for j in (0, 1) for i in new])).to(dev))
+
+        with pipelined(p.net), torch.no_grad():
+            while not planner.done():
+                classify(planner, det, cutset, read_to(planner.need()), sads)
+                fs, wins, first = planner.pop()
+                for k in [k for k in held if k < min(wins[0])]:
+                    del held[k]
+                t0 = time.time()
+                _, _, _, sc, ys = group_step(p, (fs, wins, first), windows, small)
+                if sc is not None:
+                    scores.extend(score_rows(fs, sc.cpu().tolist()))
+                if p.mjpeg:                               # (the files of the group: only the compressed bytes leave the device)
+                    ys = ops.jpeg_encode(ys, p.out_hw[0], p.out_hw[1], p.out_yuv, p.quality)
+                else:
+                    ys = [y.cpu().numpy() for y in ys] if p.size is None else ys.cpu().numpy()
+                seconds += time.time() - t0
+                for y in ys:
+                    writer.write(y)
+        finish(config, p, det.cuts if det is not None else cuts, scores)
+        return writer.frames, seconds
+    finally:
+        lr.close()
+        ref.close()
+        if writer is not None:
+            writer.close()
 
 
 def sample_dtype(fmt):
@@ -411,7 +534,7 @@ def held_bound(t, G, D):
     return t + (D + 1) * G + 2
 
 
-def run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts):
+def run_stream(config, opt, lr_path, ref_path, out_path, net):
     """run() under EVAL.io = 'stream' (module header): the same configure(), plan (scene.GroupPlanner, length unknown), calls and
     bytes, with reader and writer threads (streamio.py) around the calls and every file frame uploaded once.  All GPU calls are made
     here, on the caller's thread and current stream; the threads touch pinned host memory and file descriptors only.
@@ -426,18 +549,15 @@ def run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts):
     Returns (frames written, wall seconds of the loop); config.EVAL.io_stats has the split."""
     from . import ops, streamio
     from .yuv import Y4MStreamReader, frame_shape
-    E = config.EVAL
-    D, timeout = check_io_depth(getattr(E, 'io_depth', None)), check_io_timeout(getattr(E, 'io_timeout', None))
-    t, G = int(config.frame_num), max(1, int(getattr(E, 'frame_group', 4) or 1))
+    D, timeout = opt.io_depth, opt.io_timeout
+    t, G = int(config.frame_num), opt.frame_group
     ring = (D + 1) * G + t // 2                       # D groups in flight and one being read; the first group reads t // 2 ahead
     assert ring <= held_bound(t, G, D)
-    in_siting = getattr(E, 'in_siting', None)
     names = [sink_name(p) for p in (lr_path, ref_path)]
-    both = 'videorun: %s and %s' % tuple(names)
     io = streamio.Run()
     srcs = [streamio.FrameSource(io, lambda stop, p=p: Y4MStreamReader(p, stop), name, ring, timeout) for p, name in zip((lr_path, ref_path), names)]
     sink = writer = None
-    was_pipelined, finished = None, False
+    finished = False
     wall0 = time.time()
     stats = dict(frames=0, uploads=0, groups=0, max_in_flight=0, max_held=0, read_wait=0.0, device_wait=0.0, write_wait=0.0, wall=0.0)
     try:
@@ -451,55 +571,38 @@ def run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts):
 
         # each ring goes to its thread as soon as that stream's header is here: the LR thread drains its pipe while the other opens
         lr = srcs[0].header()
-        if in_siting is not None:
-            lr.siting = effective_siting(lr.fmt, in_siting)
         srcs[0].provide(staging(lr))
         ref = srcs[1].header()
-        if in_siting is not None:
-            ref.siting = effective_siting(ref.fmt, in_siting)
-        bad = pair_mismatch(lr, ref)
-        if bad:
-            raise ValueError('%s: %s' % (both, bad))
+        check_pair(lr, ref, opt.in_siting, names)
         srcs[1].provide(staging(ref))
-        try:
-            cuts = scene.check_cuts(cuts or ())
-        except ValueError as e:
-            raise ValueError('videorun: %s' % (e,))
-        if getattr(E, 'out_range_from_input', False):     # (main(): the output keeps the input's range unless --yuv_range says otherwise)
+        cuts = checked_cuts(opt.cuts)
+        if opt.out_range_from_input:
             config.yuv_range = lr.range
-        net, dev, t, G, out_range, out_hw = prepare(config, lr, net)
-        nc = net.Network.config
-        down, size, score_file = E.in_down, E.out_size, E.score_file
-        decode = decode_args(config, lr) if down is not None else None
-        writer = open_writer(E, out_path, out_hw, lr.fps, out_range, config.yuv_siting)
-        mjpeg = E.out_format == 'mjpeg'
-        if mjpeg:
+        p = prepare(config, lr, net, opt)
+        dev, out_hw = p.dev, p.out_hw
+        writer = open_writer(p, out_path, lr.fps)
+        if p.mjpeg:
             # a slot of the ring holds a file of up to the frame's own bytes: header, data, EOI (a larger one -- noise at quality 100 --
             # takes the slow way in retire())
             from . import jpeg
-            head = jpeg.header(out_hw[0], out_hw[1], E.out_yuv, E.jpeg_quality)
+            head = jpeg.header(out_hw[0], out_hw[1], p.out_yuv, p.quality)
             head_np = np.frombuffer(head, np.uint8)
-            slot = len(head) + int(np.prod(frame_shape(out_hw[0], out_hw[1], E.out_yuv))) + 2
+            slot = len(head) + int(np.prod(frame_shape(out_hw[0], out_hw[1], p.out_yuv))) + 2
             copies = torch.cuda.Stream(dev)               # the retired group's copies: never behind the groups still in flight
             out_pin = torch.empty(((D + 1) * G, slot), dtype=torch.uint8).pin_memory()
         else:
-            out_pin = torch.empty(((D + 1) * G,) + frame_shape(out_hw[0], out_hw[1], E.out_yuv),
-                                  dtype=sample_dtype(E.out_yuv)).pin_memory()
+            out_pin = torch.empty(((D + 1) * G,) + frame_shape(out_hw[0], out_hw[1], p.out_yuv), dtype=sample_dtype(p.out_yuv)).pin_memory()
         out_views = [out_pin[i].numpy() for i in range(out_pin.shape[0])]
         out_tens = dict((id(v), out_pin[i]) for i, v in enumerate(out_views))
         sink = streamio.FrameSink(io, writer, out_views, sink_name(out_path), timeout)
-        was_pipelined = bool(getattr(nc, 'pipelined', False))
-        net.Network.set_pipelined(True)
-        net.Network.reset()
 
-        planner = scene.GroupPlanner(None, t, G)
-        det = scene.SceneDetector(lr.h, lr.w, depth_of(lr.fmt), threshold) if threshold is not None else None
-        cutset = set(cuts)
+        planner = scene.GroupPlanner(None, p.t, p.G)
+        det = scene.SceneDetector(lr.h, lr.w, depth_of(lr.fmt), opt.scene_cut) if opt.scene_cut is not None else None
         store = collections.OrderedDict()                 # frame index -> (lr slot, ref slot) on the device: what the next windows read
-        small = {}                                        # --in_down: frame index -> (lr, ref) down-scaled (+ the LR decode), as in run()
+        small = {}                                        # --in_down: frame index -> (lr, ref) down-scaled (+ the LR decode), as in run_sync()
         flight = collections.deque()                      # the groups in flight, oldest first
         staged = []                                       # staging buffers uploaded since the last call: (source, buffer)
-        scores = []
+        scores, cutset = [], set(cuts)
         nread, ended = 0, False
 
         def retire():
@@ -509,7 +612,7 @@ def run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts):
             g['event'].synchronize()
             stats['device_wait'] += time.time() - t0
             if g['scores'] is not None:
-                scores.extend((f, metrics.psnr_from_mse(m), s_) for f, (m, s_) in zip(g['fs'], g['scores'].tolist()))
+                scores.extend(score_rows(g['fs'], g['scores'].tolist()))
             for src, b in g['staged']:
                 src.give(b)
             if g['jpeg'] is not None:
@@ -517,6 +620,10 @@ def run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts):
             for b in g['out']:
                 sink.put(*b) if isinstance(b, tuple) else sink.put(b)
             stats['frames'] += len(g['out'])
+
+        def retire_all():
+            while flight:
+                retire()
 
         def retire_jpeg(dst, meta):
             """The files of a retired group: its sizes came with its event; exactly the compressed bytes of every frame are copied into
@@ -539,7 +646,8 @@ def run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts):
             return out
 
         def read_to(upto):
-            """Frames [nread, upto) of both streams, as far as they go, into the store -- ONE upload per file frame -- and classified."""
+            """Frames [nread, upto) of both streams, as far as they go, into the store -- ONE upload per file frame; their indices.
+            Behind the last frame the length is known: the refusals that need it, and the planner is told."""
             nonlocal nread, ended
             new = []
             while not ended and nread < upto:
@@ -555,68 +663,46 @@ def run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts):
                 stats['uploads'] += 2
                 new.append(nread)
                 nread += 1
-            if det is None:
-                for k in new:
-                    planner.push(k in cutset)
-            else:
-                if new and new[0] == 0:
-                    planner.push(False)                   # (frame 0 opens the first scene)
-                pairs = [k for k in new if k > 0]
-                if pairs:                                 # one ops.luma_sad call on the store's slots: no upload of its own
-                    t0 = time.time()
-                    sads = ops.luma_sad([store[k][0] for k in pairs], [store[k - 1][0] for k in pairs], lr.h, lr.w, lr.fmt).cpu().tolist()
-                    stats['device_wait'] += time.time() - t0
-                    for sad in sads:
-                        planner.push(det.push(sad))
-            if ended:
-                if nread == 0:
-                    raise ValueError('%s: no frames' % both)
-                try:
-                    scene.check_cuts(cuts, nread)
-                except ValueError as e:
-                    raise ValueError('videorun: %s (%d frames)' % (e, nread))
-                planner.finish()
+            return new
 
-        def down_scaled(wins):
-            """--in_down (down_scaled_windows), from the store: no upload of its own."""
-            return down_scaled_windows(small, store, wins, lr, down, decode, score_file is not None,
-                                       lambda new: stacked([store[i][j] for j in (0, 1) for i in new]))
+        def sads(pairs):
+            """One ops.luma_sad call on the store's slots: no upload of its own."""
+            t0 = time.time()
+            out = ops.luma_sad([store[k][0] for k in pairs], [store[k - 1][0] for k in pairs], lr.h, lr.w, lr.fmt).cpu().tolist()
+            stats['device_wait'] += time.time() - t0
+            return out
 
-        with torch.no_grad():
+        def windows(wins):
+            """Stacked on the device from the store, --in_down too: no upload of its own."""
+            if p.down is None:
+                return tuple(stacked([store[i][j] for w_ in wins for i in w_]).unflatten(0, (len(wins), t)) for j in (0, 1))
+            return down_scaled_windows(p, lr, small, store, wins, lambda new: stacked([store[i][j] for j in (0, 1) for i in new]))
+
+        with pipelined(p.net, True), torch.no_grad():
             while True:
                 if len(flight) >= D:
                     retire()
                 if not ended:
-                    read_to(planner.need())
+                    classify(planner, det, cutset, read_to(planner.need()), sads)
+                    if ended:
+                        if nread == 0:
+                            raise ValueError('videorun: %s and %s: no frames' % tuple(names))
+                        checked_cuts(cuts, nread)
+                        planner.finish()
                 group = planner.pop()
                 if group is None:
                     assert planner.done()
                     break
-                fs, wins, first = group
-                held = [store.pop(k) for k in [k for k in store if k < min(wins[0])]]     # below the oldest window still to come
+                held = [store.pop(k) for k in [k for k in store if k < min(group[1][0])]]     # below the oldest window still to come
                 stats['max_held'] = max(stats['max_held'], len(store) + len(held) + sum(len(g['held']) for g in flight))
-                if first and fs[0] > 0:                   # a scene is a clip of its own: the state of the last one ends here
-                    while flight:
-                        retire()
-                    net.Network.reset()
-                if down is None:
-                    lrs, rfs = (stacked([store[i][j] for w_ in wins for i in w_]).unflatten(0, (len(wins), t)) for j in (0, 1))
-                else:
-                    lrs, rfs = down_scaled(wins)
-                got = net.Network.forward_group(lrs, rfs, wins, is_first_frame=first)
+                lrs, rfs, got, sc_d, ys = group_step(p, group, windows, small, retire_all)
                 sc = None
-                if score_file is not None:                # (the unscaled result against the LR file frame: one 16-byte row per frame)
-                    sc_d = ops.score_frames([r[0] for r in got['result']], [small[f][2] for f in fs])
+                if sc_d is not None:
                     sc = torch.empty(sc_d.shape, dtype=sc_d.dtype).pin_memory()
                     sc.copy_(sc_d, non_blocking=True)
-                if size is None:
-                    ys = [y[0] for y in got['yuv']]
-                else:
-                    ys = resized_yuv(ops, [r[0] for r in got['result']], size, E.out_yuv, getattr(config, 'yuv_matrix', None) or 'bt709', out_range,
-                                     config.yuv_siting)
                 out, enc = [], None
-                if mjpeg:                                 # the encode goes out with the group; its sizes come back with its event
-                    dst, offsets, sizes = ops.jpeg_encode_device(ys, out_hw[0], out_hw[1], E.out_yuv, E.jpeg_quality)
+                if p.mjpeg:                               # the encode goes out with the group; its sizes come back with its event
+                    dst, offsets, sizes = ops.jpeg_encode_device(ys, out_hw[0], out_hw[1], p.out_yuv, p.quality)
                     meta = torch.empty((2, len(ys)), dtype=torch.int64).pin_memory()
                     meta[0].copy_(offsets, non_blocking=True)
                     meta[1].copy_(sizes, non_blocking=True)
@@ -627,110 +713,29 @@ def run_stream(config, lr_path, ref_path, out_path, net, threshold, cuts):
                         out_tens[id(out[-1])].copy_(y, non_blocking=True)
                 event = torch.cuda.Event()
                 event.record()
-                flight.append(dict(event=event, fs=fs, out=out, staged=staged, held=held, scores=sc, jpeg=enc, keep=(lrs, rfs, got, ys)))
+                flight.append(dict(event=event, fs=group[0], out=out, staged=staged, held=held, scores=sc, jpeg=enc, keep=(lrs, rfs, got, sc_d, ys)))
                 staged = []
                 stats['groups'] += 1
                 stats['max_in_flight'] = max(stats['max_in_flight'], len(flight))
-            while flight:
-                retire()
+            retire_all()
             sink.finish()
-        config.EVAL.scene_cuts = tuple(det.cuts) if det is not None else tuple(cuts)
-        if score_file is not None:
-            config.EVAL.scores = scores
-            write_scores(score_file, scores)
+        finish(config, p, det.cuts if det is not None else cuts, scores)
         finished = True
         return writer.frames, time.time() - wall0
     finally:
-        # no device work pending, no thread alive, whatever happened; the first error stays the one that is raised
+        # no thread alive, whatever happened (pipelined() has left no device work pending); the first error stays the one that is raised
+        for x in srcs + ([sink] if sink is not None else []):
+            x.close()
+        stats['read_wait'] = sum(s.waited for s in srcs)
+        stats['write_wait'] = sink.waited if sink is not None else 0.0
+        stats['wall'] = time.time() - wall0
+        config.EVAL.io_stats = stats
         try:
-            if was_pipelined is not None:
-                torch.cuda.synchronize()
-        finally:
-            for x in srcs + ([sink] if sink is not None else []):
-                x.close()
-            stats['read_wait'] = sum(s.waited for s in srcs)
-            stats['write_wait'] = sink.waited if sink is not None else 0.0
-            stats['wall'] = time.time() - wall0
-            config.EVAL.io_stats = stats
-            try:
-                if writer is not None:
-                    writer.close()
-            except ValueError:
-                if finished:                              # (behind an earlier error that one is the one to raise)
-                    raise
-            finally:
-                if was_pipelined is False:
-                    net.Network.set_pipelined(False)
-
-
-def prepare(config, lr, net=None):
-    """What both loops do between the LR header and the first frame: configure(), the network (built here unless passed in) with the
-    run's formats in its config, the refusals of a network that already runs otherwise.  Returns (net, device, t, G, the output's
-    range, the output's (h, w))."""
-    E = config.EVAL
-    configure(config, lr)
-    if net is None:
-        from . import SRNet
-        net = SRNet(config).to('cuda').eval()
-        if config.EVAL.ckpt_abs_name:
-            load_checkpoint(net, config.EVAL.ckpt_abs_name)
-    nc = net.Network.config
-    if nc is not config:                              # (a caller's net may carry a config of its own)
-        for k in ('input_yuv', 'input_yuv_range', 'input_yuv_siting', 'result_yuv', 'yuv_siting') + (
-                ('yuv_matrix', 'yuv_range') if getattr(E, 'out_format', None) == 'mjpeg' else ()):
-            setattr(nc, k, getattr(config, k))
-    down, size = E.in_down, E.out_size
-    if net.Network._engines and (net.Network._engines[0].input_yuv is None) != (down is not None):
-        raise RuntimeError('videorun: the network passed in already runs %s config.input_yuv; pass a fresh one' % ('with' if down else 'without'))
-    if net.Network._engines and size is not None and net.Network._engines[0].result_yuv is not None:
-        raise RuntimeError('videorun: the network passed in already runs with config.result_yuv; pass a fresh one')
-    dev = next(net.parameters()).device
-    t, G = int(config.frame_num), max(1, int(getattr(config.EVAL, 'frame_group', 4) or 1))
-    scale = int(config.scale)
-    out_range = getattr(config, 'yuv_range', None) or 'limited'
-    rh, rw = (lr.h * scale, lr.w * scale) if down is None else (lr.h // down * scale, lr.w // down * scale)
-    return net, dev, t, G, out_range, ((rh, rw) if size is None else (size[1], size[0]))
-
-
-def decode_args(config, lr):
-    """--in_down: fmt, matrix, range, chroma, siting of ops.yuv_to_frames for the files' frames."""
-    r_in = resolve_input(lr.fmt, getattr(config, 'input_yuv_matrix', None), getattr(config, 'input_yuv_range', None),
-                         getattr(config, 'input_yuv_chroma', None), lr.siting)
-    return r_in if len(r_in) == 5 else r_in + ('centre',)
-
-
-def down_scaled_windows(small, held, wins, lr, down, decode, keep_full, load):
-    """--in_down: the windows as RGB tensors [B, t, 3, h / K, w / K].  small: frame index -> (lr, ref) down-scaled (+ the LR decode
-    under keep_full: the ground truth of --score), kept for the frames in `held` (the frames the run still holds).  A file frame not
-    in it yet is decoded once at file size (ops.yuv_to_frames) and resized once (ops.resize_aa: uint8 from 8-bit files, float32 from
-    10-bit ones) -- the LR and the reference frames of a call together; load(new) -> their buffers on the device, [2 len(new), rows,
-    w], the LR frames first."""
-    from . import ops
-    for k in [k for k in small if k not in held]:
-        del small[k]
-    new = sorted({i for w_ in wins for i in w_ if i not in small})
-    if new:
-        full = ops.yuv_to_frames(load(new), lr.h, lr.w, *decode)
-        lo = ops.resize_aa(full, lr.h // down, lr.w // down, 'uint8' if depth_of(lr.fmt) == 8 else 'float32')
-        for q, i in enumerate(new):
-            small[i] = (lo[q], lo[len(new) + q], full[q] if keep_full else None)
-    return tuple(torch.stack([torch.stack([small[i][j] for i in w_]) for w_ in wins]) for j in (0, 1))
-
-
-def resized_yuv(ops, results, size, fmt, matrix, range, siting):
-    """--out_size: results [3, sh, sw] -> [B, rows, W] frames of `fmt` at size = (W, H): ops.resize_aa (clamped float32), then
-    ops.result_to_yuv -- one launch each per group."""
-    return ops.result_to_yuv(ops.resize_aa(results, size[1], size[0], 'float32', True), fmt, matrix, range, effective_siting(fmt, siting))
-
-
-def write_scores(path, scores):
-    """--score: `frame psnr ssim` per frame (repr of the float64s: they read back bit for bit), then `mean psnr ssim` -- the sums in
-    frame order over the count."""
-    with open(path, 'w') as f:
-        for fr, p, s_ in scores:
-            f.write('%d %r %r\n' % (fr, p, s_))
-        k = max(len(scores), 1)
-        f.write('mean %r %r\n' % (sum(p for _, p, _ in scores) / k, sum(s_ for _, _, s_ in scores) / k))
+            if writer is not None:
+                writer.close()
+        except ValueError:
+            if finished:                                  # (behind an earlier error that one is the one to raise)
+                raise
 
 
 def build_config(argv=None):
@@ -744,7 +749,7 @@ def build_config(argv=None):
     ap.add_argument('--out_format', default=None, choices=list(OUT_FORMATS),
                     help='y4m, or mjpeg: one baseline JPEG per frame, coded on the device, BT.601 full range as JFIF defines it '
                          '(default: by the extension of --out, .mjpeg / .mjpg is mjpeg)')
-    ap.add_argument('--jpeg_quality', type=int, default=90, metavar='Q', help='--out_format mjpeg: the quality 1..100 (default 90)')
+    ap.add_argument('--jpeg_quality', type=int, default=None, metavar='Q', help='--out_format mjpeg: the quality 1..100 (default 90)')
     ap.add_argument('--frame_num', type=int, default=5)
     ap.add_argument('--frame_group', type=int, default=4)
     ap.add_argument('--video_depth', type=int, default=None, choices=[8, 10], help='bits per sample of --out (default: the input files\')')
@@ -772,16 +777,14 @@ def build_config(argv=None):
     ap.add_argument('--out_size', type=str, default=None, metavar='WxH',
                     help='write the result at W x H (even; at least an eighth of the result per axis, up-scaling allowed) through the '
                          'antialiased bicubic instead of at scale x input')
-    ap.add_argument('--io', default='auto', choices=list(IO_MODES),
+    ap.add_argument('--io', default=None, choices=list(IO_MODES),
                     help="sync: read, run and write one after the other (regular files).  stream: reader and writer threads around the "
                          "network calls, every file frame uploaded once; --lr or --ref (one of them) and --out may be '-' or a FIFO.  "
                          "auto (default): stream when --lr, --ref or --out is '-' or no regular file, else sync")
-    ap.add_argument('--io_depth', type=int, default=2, metavar='D', help='--io stream: frame groups in flight, 1..4 (default 2)')
-    ap.add_argument('--io_timeout', type=float, default=120.0, metavar='S',
+    ap.add_argument('--io_depth', type=int, default=None, metavar='D', help='--io stream: frame groups in flight, 1..4 (default 2)')
+    ap.add_argument('--io_timeout', type=float, default=None, metavar='S',
                     help='--io stream: seconds an input may deliver nothing, or the output take nothing, before the run ends (default 120)')
     args = ap.parse_args(argv)
-    if args.scene_cut is not None and args.cuts is not None:
-        raise ValueError('videorun: --scene_cut and --cuts exclude each other')
     try:
         scene_cut = None if args.scene_cut is None else scene.check_threshold(args.scene_cut)
         cuts = None if args.cuts is None else scene.check_cuts(int(c) for c in args.cuts.split(',') if c.strip())
@@ -800,30 +803,21 @@ def build_config(argv=None):
     E.input_range_set = args.yuv_range is not None
     if args.yuv_range is not None:
         cfg.yuv_range = cfg.input_yuv_range = check_range(args.yuv_range)
-    E.ckpt_abs_name, E.frame_group, E.video_depth = args.ckpt_abs_name, args.frame_group, args.video_depth
-    E.scene_cut, E.cuts = scene_cut, cuts
-    E.in_siting, E.out_chroma, E.out_siting = args.in_siting, args.out_chroma, args.out_siting
-    E.in_down, E.score_file, E.out_size = check_in_down(args.in_down), args.score, check_out_size(args.out_size)
-    if E.score_file is not None and E.in_down != int(cfg.scale):
-        raise ValueError('videorun: --score needs --in_down %d, the scale of the config (got --in_down %s)' % (int(cfg.scale), E.in_down))
-    E.io_depth, E.io_timeout = check_io_depth(args.io_depth), check_io_timeout(args.io_timeout)
-    E.out_format, E.jpeg_quality = out_format(args.out_format, args.out), args.jpeg_quality
-    if E.out_format == 'mjpeg':
-        check_mjpeg(E)
-    E.io = io_mode(args.io, args.lr, args.ref, args.out)
+    E.scene_cut, E.cuts, E.score_file = scene_cut, cuts, args.score
+    for k in ('ckpt_abs_name', 'frame_group', 'video_depth', 'in_siting', 'out_chroma', 'out_siting', 'in_down', 'out_size', 'io', 'io_depth',
+              'io_timeout', 'out_format', 'jpeg_quality'):
+        setattr(E, k, getattr(args, k))
+    opt = options(cfg, (args.lr, args.ref, args.out))           # every refusal that needs no file, before one is opened; EVAL as checked
+    for k in ('in_down', 'out_size', 'io', 'io_depth', 'io_timeout', 'out_format', 'jpeg_quality'):
+        setattr(E, k, getattr(opt, k))
     cfg.device, cfg.cuda = 'cuda', True
     return cfg, args
 
 
 def main(argv=None):
     cfg, args = build_config(argv)
-    if cfg.EVAL.io == 'stream':
-        cfg.EVAL.out_range_from_input = not cfg.EVAL.input_range_set          # (the header is read once: by the reader run() opens)
-    elif not cfg.EVAL.input_range_set:
-        with Y4MReader(args.lr) as rd:
-            cfg.yuv_range = rd.range              # (the output keeps the input's range unless --yuv_range says otherwise)
+    cfg.EVAL.out_range_from_input = not cfg.EVAL.input_range_set      # (the header is read once: by the reader run() opens)
     if args.out == '-':                           # the frames own stdout: whatever the run prints goes to stderr
-        import contextlib
         with contextlib.redirect_stdout(sys.stderr):
             frames, seconds = run(cfg, args.lr, args.ref, sys.__stdout__.buffer)
     else:
