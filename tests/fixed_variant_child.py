@@ -4,8 +4,10 @@ started by it as ONE fresh process for the row that needs REFVSR_CONV48_WAVES=8 
     python fixed_variant_child.py KNOB_SET OUT.npz
 
 runs every run of every row of KNOB_SET under the environment it was given and writes, per run `t` (tag()): t.key / t.n_tiles / t.lds
-(what the library's query reports for the arguments that were launched), t.same (1: the inputs came back unchanged) and the raw
-results t.<map>.<output>.  It judges nothing: the parent compares.
+(what the library's query reports for the arguments that were launched), t.same (1: the inputs came back unchanged), the raw
+results t.<map>.<output>, and of the fenced second run (tests/footprint.py) t.fence ('' = every fence intact, every result fenced,
+no NaN, inputs and their fences unchanged, the same key / n_tiles / lds; else what was found) and t.equal (1: every raw result
+tensor equals the plain run's).  It judges nothing else: the parent compares.
 
 One run = one launch through the entry point of refvsr_amd.ops that the engine uses: the maps of a multi-map row are separately
 allocated tensors; a `walk` run goes to a plain side stream whose CU budget is 8 (refvsr_stream_set_cu_budget), set back to 0 in a
@@ -26,22 +28,26 @@ for p in (HERE, os.path.dirname(HERE)):
 
 import exact_cases as ec  # noqa: E402
 import fixed_variant_cases as fv  # noqa: E402
+import footprint as fp  # noqa: E402
 
 PROBE_WORDS, PROBE_TAIL, PROBE_MARK = 12, 64, 0x5a5a5a5a5a5a5a5a
 SETTER_ENV = ('REFVSR_RESBLOCK24_WAVES', 'REFVSR_RB24_STORE')
 
 
-def nhwc16(x, dev):
-    """float64 [C, H, W] of fp16 numbers -> device fp16 [H, W, Cs] (channel padding zero), with torch alone."""
+def nhwc16(x, dev, poison=None):
+    """float64 [C, H, W] of fp16 numbers -> device fp16 [H, W, Cs] (channel padding zero), with torch alone.  poison: None = an
+    allocation of its own, 'nan' | 'benign' = a view between the fences of footprint.fenced_input."""
     c, h, w = x.shape
     t = torch.zeros(h, w, ec.pad8(c), dtype=torch.float16)
     t[:, :, :c] = x.permute(1, 2, 0).to(torch.float16)
     assert torch.equal(t[:, :, :c].double(), x.permute(1, 2, 0)), 'input map is not fp16-representable'
-    return t.to(dev)
+    return t.to(dev) if poison is None else fp.fenced_input(t, dev, poison)
 
 
-def f32(t, dev=None):
+def f32(t, dev=None, poison=None):
     t = t.float().contiguous()
+    if poison is not None:
+        return fp.fenced_input(t, dev, poison)
     return t.to(dev) if dev is not None else t
 
 
@@ -122,21 +128,24 @@ def query(row, hw, stream):
     return key.value, n.value, lds.value
 
 
-def _conv(row, cases, dev):
-    """-> (inputs, launch) of a conv24 / conv32 / conv48 / conv_shuffle2 row"""
+def _conv(row, cases, dev, pz):
+    """-> (inputs, launch) of a conv24 / conv32 / conv48 / conv_shuffle2 row; launch() -> (the raw result tensors, fetch).  pz: None,
+    or 'nan' = every map (each of a multi-map row on its own) and the weights between NaN fences"""
     from refvsr_amd import ops
     from refvsr_amd.packing import pack_conv
     p0 = cases[0].p
     shuffle = row.entry == 'shuffle2'
     cw = ops.ConvWeights(pack_conv(f32(p0['w']), f32(p0['b']), list(row.cins), shuffle), dev, 'fp16' if row.wf else 'hi_lo')
     assert cw.blob24 is not None and cw.blob_wfmt == ('fp16' if row.wf else 'hi_lo'), 'no specialised kernel in this weight format'
+    if pz:
+        fp.fence_weights(cw)
     ins = {'blob': cw.blob24}
     for b, c in enumerate(cases):
         for k, s in enumerate(c.p['srcs']):
-            ins['src%d.%d' % (k, b)] = nhwc16(s, dev)
+            ins['src%d.%d' % (k, b)] = nhwc16(s, dev, pz)
         for k in ('mul', 'res'):
             if c.p.get(k) is not None:
-                ins['%s.%d' % (k, b)] = nhwc16(c.p[k], dev)
+                ins['%s.%d' % (k, b)] = nhwc16(c.p[k], dev, pz)
     lst = lambda k: [ins['%s.%d' % (k, b)] for b in range(len(cases))] if k + '.0' in ins else None
     kw = dict(act=p0['act'], post=p0['post'])
     co = row.cout // 4 if shuffle else row.cout
@@ -151,19 +160,21 @@ def _conv(row, cases, dev):
             out = ops.conv_b(cw, lst('src0'), lst('src1'), muls=lst('mul'), ress=lst('res'), **kw)
         else:
             out = [ops.conv(cw, s0, ins.get('src1.0'), mul=ins.get('mul.0'), res=ins.get('res.0'), **kw)]
-        return lambda: [{'out': planar64(o.cpu(), co)} for o in out]
+        return list(out), lambda: [{'out': planar64(o.cpu(), co)} for o in out]
     return ins, launch
 
 
-def _conf(row, cases, dev):
+def _conf(row, cases, dev, pz):
     from refvsr_amd import ops
     from refvsr_amd.packing import pack_conv
     p0 = cases[0].p
     cw = ops.ConvWeights(pack_conv(f32(p0['w']), f32(p0['b']), [16], False), dev, 'fp16' if row.wf else 'hi_lo')
     assert ops.conf_alpha_ok(cw, len(cases) if row.mm else None) and cw.blob_wfmt == ('fp16' if row.wf else 'hi_lo')
-    ins = {'blob': cw.blob24, 'w0': f32(p0['w0'], dev), 'b0': f32(p0['b0'], dev)}
+    if pz:
+        fp.fence_weights(cw)
+    ins = {'blob': cw.blob24, 'w0': f32(p0['w0'], dev, pz), 'b0': f32(p0['b0'], dev, pz)}
     for b, c in enumerate(cases):
-        ins['a.%d' % b], ins['b.%d' % b] = f32(c.p['conf_a'], dev), f32(c.p['conf_b'], dev)
+        ins['a.%d' % b], ins['b.%d' % b] = f32(c.p['conf_a'], dev, pz), f32(c.p['conf_b'], dev, pz)
     lst = lambda k: [ins['%s.%d' % (k, b)] for b in range(len(cases))]
     wm = row.up == 1
 
@@ -174,45 +185,49 @@ def _conf(row, cases, dev):
         else:
             out = ops.conf_alpha(ins['a.0'], ins['b.0'], row.up, ins['w0'], ins['b0'], cw, p0['slope0'], p0['slope1'], want_max=wm)
             out = [out if wm else (out,)]
-        return lambda: [dict([('out', planar64(o[0].cpu(), row.cout))] + ([('cmax', o[1].cpu().double())] if wm else [])) for o in out]
+        return [t for o in out for t in o], lambda: [dict([('out', planar64(o[0].cpu(), row.cout))] + ([('cmax', o[1].cpu().double())] if wm else [])) for o in out]
     return ins, launch
 
 
-def _head(row, cases, dev, formats):
+def _head(row, cases, dev, formats, pz):
     """refvsr_conv_last | refvsr_conv_hr_last with a zero base frame (its bicubic sample is exactly 0), in every result format asked"""
     from refvsr_amd import ops
     from refvsr_amd.packing import pack_conv_hr_last, pack_conv_last
     p = cases[0].p
-    x = nhwc16(p['x'], dev)
-    ins = {'x': x, 'base': torch.zeros(3, x.shape[0], x.shape[1], device=dev)}
+    x = nhwc16(p['x'], dev, pz)
+    ins = {'x': x, 'base': f32(torch.zeros(3, x.shape[0], x.shape[1]), dev, pz)}
     if row.entry == 'conv_last':
         ins['blob'] = pack_conv_last(f32(p['w']), f32(p['b'])).to(dev)
+        ins['blob'] = fp.fence_weights(ins['blob']) if pz else ins['blob']
         run = lambda dt: ops.conv_last(ins['blob'], x, ins['base'], dt)
     else:
         ins['blob'] = pack_conv_hr_last(f32(p['w1']), f32(p['b1']), f32(p['w2']), f32(p['b2'])).to(dev)
+        ins['blob'] = fp.fence_weights(ins['blob']) if pz else ins['blob']
         run = lambda dt: ops.conv_hr_last(ins['blob'], x, ins['base'], p['act'], dt)
 
     def launch():
         out = [(k, run(dt)) for k, dt in formats]
-        return lambda: [dict((k, o.cpu()) for k, o in out)]
+        return [o for _, o in out], lambda: [dict((k, o.cpu()) for k, o in out)]
     return ins, launch
 
 
-def _blocks(row, cases, dev):
+def _blocks(row, cases, dev, pz):
     from refvsr_amd import ops
     p0 = cases[0].p
     raw = [((f32(w1), f32(b1)), (f32(w2), f32(b2))) for (w1, b1, w2, b2) in p0['blocks']]
     chain = ops.Resblock24Chain(raw, dev, 'fp16' if row.wf else 'hi_lo')
+    if pz:
+        fp.fence_weights(chain)
     ins = {'blobs': chain.blobs}
     for b, c in enumerate(cases):
-        ins['x.%d' % b] = nhwc16(c.p['x'], dev)
+        ins['x.%d' % b] = nhwc16(c.p['x'], dev, pz)
 
     def launch():
         if row.batch:
             out = ops.resblock24_chain_b(chain, [ins['x.%d' % b] for b in range(len(cases))], p0['act'])
         else:
             out = [ops.resblock24_chain(chain, ins['x.0'], p0['act'])]
-        return lambda: [{'out': planar64(o.cpu(), 24)} for o in out]
+        return list(out), lambda: [{'out': planar64(o.cpu(), 24)} for o in out]
     return ins, launch
 
 
@@ -220,20 +235,43 @@ FORMATS = (('out', None), ('f16', 'float16'), ('u8', 'uint8'))
 
 
 def run_row(i, run, form, dev):
-    """One run of row i -> {'key', 'n_tiles', 'lds', 'same', 'tail' (probe rows), '<map>.<output>': raw result on the cpu}."""
+    """One run of row i and its fenced twin -> {'key', 'n_tiles', 'lds', 'same', 'tail' (probe rows), '<map>.<output>': raw result on
+    the cpu, 'fence': '' or what the fenced run found, 'equal': the fenced run's raw result tensors equal the plain run's}."""
+    res, raw = _run_row(i, run, form, dev, False)
+    res2, raw2 = _run_row(i, run, form, dev, True)
+    bad = [res2['fence']] if res2['fence'] else []
+    for k in ('key', 'n_tiles', 'lds'):
+        if res2[k] != res[k]:
+            bad.append('the fenced run reports %s %d, the plain run %d' % (k, res2[k], res[k]))
+    if not res2['same']:
+        bad.append('an input of the fenced run was written to')
+    if res2.get('tail', 1) != 1:
+        bad.append('the probe kernel of the fenced run wrote behind 12 x n_tiles words')
+    res['fence'] = '\n'.join(bad)
+    res['equal'] = int(len(raw) == len(raw2) and all(a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b) for a, b in zip(raw, raw2)))
+    return res
+
+
+def _run_row(i, run, form, dev, fenced):
+    """One launch of row i -> (the results as run_row describes them, [raw result tensors on the cpu]).  fenced: every input between
+    the fences of footprint.fenced_input, every allocation of ops between 0xA5 fences, entered inside the run's stream so that the
+    fence fills are ordered on it; 'fence' holds footprint.judge's verdict."""
+    from refvsr_amd import ops
     row = fv.ROWS[i]
+    pz = 'nan' if fenced else None
+    fp.reset_inputs()
     cases = fv.get_cases(i, run, form)
     hw = fv.shape(row, run)
     for k in SETTER_ENV:
         assert not os.environ.get(k), 'the rows set the resblock24 setters themselves: %s must not be set' % k
     if row.entry in ('conv_last', 'hr_last'):
-        ins, launch = _head(row, cases, dev, FORMATS if run == 'small' else FORMATS[:1])
+        ins, launch = _head(row, cases, dev, FORMATS if run == 'small' else FORMATS[:1], pz)
     elif row.entry == 'conf_alpha':
-        ins, launch = _conf(row, cases, dev)
+        ins, launch = _conf(row, cases, dev, pz)
     elif row.entry == 'rb24':
-        ins, launch = _blocks(row, cases, dev)
+        ins, launch = _blocks(row, cases, dev, pz)
     else:
-        ins, launch = _conv(row, cases, dev)
+        ins, launch = _conv(row, cases, dev, pz)
     before = dict((k, v.clone()) for k, v in ins.items())
     res = {}
     with setters(row, hw, dev) as probe:
@@ -241,14 +279,20 @@ def run_row(i, run, form, dev):
             res['key'], res['n_tiles'], res['lds'] = query(row, hw, stream)
             if probe is not None:
                 assert probe.numel() == PROBE_WORDS * res['n_tiles'] + PROBE_TAIL, 'probe buffer sized for another tile count'
-            fetch = launch()
+            if fenced:
+                with fp.fenced_outputs(ops) as fo:
+                    raw, fetch = launch()
+                    res['fence'] = fp.judge(fo, raw)
+            else:
+                raw, fetch = launch()
         if probe is not None:
             res['tail'] = int((probe[-PROBE_TAIL:].cpu() == PROBE_MARK).all())
     res['same'] = int(all(torch.equal(v, before[k]) for k, v in ins.items()))
     for b, outs in enumerate(fetch()):
         for k, v in outs.items():
             res['%d.%s' % (b, k)] = v
-    return res
+    fp.reset_inputs()
+    return res, [t.cpu() for t in raw]
 
 
 def main(knob, path):
@@ -260,7 +304,7 @@ def main(knob, path):
     out = {}
     for i, run, form in runs_of(knob):
         for k, v in run_row(i, run, form, dev).items():
-            out['%s.%s' % (tag(i, run, form), k)] = v.numpy() if isinstance(v, torch.Tensor) else np.int64(v)
+            out['%s.%s' % (tag(i, run, form), k)] = v.numpy() if isinstance(v, torch.Tensor) else np.array(v) if isinstance(v, str) else np.int64(v)
     out['seconds'] = np.float64(time.time() - t0)
     np.savez(path, **out)
     return 0

@@ -28,6 +28,7 @@ import block_variant_cases as bv
 import conv_variant_child as generic
 import exact_cases as ec
 import fixed_variant_child as child
+import footprint as fp
 from test_gpu_fixed_variants import REPORT as FIXED_REPORT
 
 pytestmark = pytest.mark.gpu
@@ -102,16 +103,19 @@ def query(row, hw, stream):
     return key.value, n.value, grid.value, lds.value
 
 
-def prepare(row, cases, dev):
-    """-> (inputs, launch): the device tensors of the launch and the call through refvsr_amd.ops"""
+def prepare(row, cases, dev, pz=None):
+    """-> (inputs, launch): the device tensors of the launch and the call through refvsr_amd.ops.  pz: None, or 'nan' = every map
+    (each map of a multi-map row on its own), the blobs, the weight packs and the biases between the NaN fences of tests/footprint.py"""
     from refvsr_amd import ops
     from refvsr_amd.packing import pack_conv
     p0 = cases[0].p
     raw = [((child.f32(w1), child.f32(b1)), (child.f32(w2), child.f32(b2))) for (w1, b1, w2, b2) in p0['blocks']]
-    ins = dict(('x.%d' % b, child.nhwc16(c.p['x'], dev)) for b, c in enumerate(cases))
+    ins = dict(('x.%d' % b, child.nhwc16(c.p['x'], dev, pz)) for b, c in enumerate(cases))
     xs = [ins['x.%d' % b] for b in range(len(cases))]
     if row.kernel == 'rb48':
         chain = ops.Resblock48Chain(raw, dev)
+        if pz:
+            fp.fence_weights(chain)
         ins['blobs'] = chain.blobs
         if row.batch:
             return ins, lambda: list(ops.resblock48_chain_b(chain, xs, p0['act']))
@@ -119,6 +123,9 @@ def prepare(row, cases, dev):
     assert ops.resblock_fits(row.c)
     pairs = [tuple(ops.ConvWeights(pack_conv(w, b, [row.c], False), dev, 'hi_lo') for (w, b) in blk) for blk in raw]
     for k, (a, b) in enumerate(pairs):
+        if pz:                                               # before ResblockChain takes the pointers
+            fp.fence_weights(a)
+            fp.fence_weights(b)
         ins.update({'w1.%d' % k: a.wpack, 'b1.%d' % k: a.bias, 'w2.%d' % k: b.wpack, 'b2.%d' % k: b.bias})
     if row.entry == 'chain':
         chain = ops.ResblockChain(pairs)
@@ -127,23 +134,35 @@ def prepare(row, cases, dev):
     return ins, lambda: [ops.resblock(pairs[0][0], pairs[0][1], xs[0], p0['act'], p0['post'])]
 
 
-def run_row(i, run, dev):
-    """One run of row i -> {'key', 'n_tiles', 'grid', 'lds', 'same', 'probe' (probe rows: the buffer on the cpu), 'out': [map]}."""
+def run_row(i, run, dev, fenced=False):
+    """One run of row i -> {'key', 'n_tiles', 'grid', 'lds', 'same', 'probe' (probe rows: the buffer on the cpu), 'out': [map], 'raw':
+    [the raw result tensors on the cpu]}.  fenced: every input between NaN fences and every allocation of ops (outputs and the
+    chain's scratch maps) between 0xA5 fences, entered inside the run's stream so that the fence fills are ordered on it; 'fence' holds
+    footprint.judge's verdict ('' = all is well)."""
+    from refvsr_amd import ops
     row = bv.ROWS[i]
     cases = bv.get_cases(i, run)
     hw = bv.shape(row, run)
-    ins, launch = prepare(row, cases, dev)
+    fp.reset_inputs()
+    ins, launch = prepare(row, cases, dev, 'nan' if fenced else None)
     before = dict((k, v.clone()) for k, v in ins.items())
     res = {}
     with setters(row, hw, run, dev) as probe:
         with child.walk_stream(run) as stream:
             res['key'], res['n_tiles'], res['grid'], res['lds'] = query(row, hw, stream)
             assert probe is None or probe.numel() == child.PROBE_WORDS * res['n_tiles'] + child.PROBE_TAIL, 'probe buffer sized for another tile count'
-            outs = launch()
+            if fenced:
+                with fp.fenced_outputs(ops) as fo:
+                    outs = launch()
+                    res['fence'] = fp.judge(fo, outs)
+            else:
+                outs = launch()
         if probe is not None:
             res['probe'] = probe.cpu()
     res['same'] = all(torch.equal(v, before[k]) for k, v in ins.items())
-    res['out'] = [child.planar64(o.cpu(), row.c) for o in outs]
+    res['raw'] = [o.cpu() for o in outs]
+    res['out'] = [child.planar64(o, row.c) for o in res['raw']]
+    fp.reset_inputs()
     return res
 
 
@@ -183,4 +202,14 @@ def judge(i, run, res, premise_ok):
 
 @pytest.mark.parametrize('i,run', RUNS, ids=['%02d-%s' % t for t in RUNS])
 def test_block_variant_run_is_planned_and_bit_equal(i, run, dev, premise):
-    judge(i, run, run_row(i, run, dev), premise)
+    res = run_row(i, run, dev)
+    judge(i, run, res, premise)
+    # the fenced second run (tests/footprint.py) must pass the same judgement, with the same plan and the same raw maps
+    res2 = run_row(i, run, dev, fenced=True)
+    name = bv.get_cases(i, run)[0].name
+    equal = len(res['raw']) == len(res2['raw']) and all(a.dtype == b.dtype and torch.equal(a, b) for a, b in zip(res['raw'], res2['raw']))
+    report('%-72s key=%-2d fenced run: fences=%s equal=%s' % (name, res2['key'], 'BROKEN' if res2['fence'] else 'ok', 'ok' if equal else 'NO'))
+    assert not res2['fence'], '%s, fenced run: %s' % (name, res2['fence'])
+    assert equal, '%s: the fenced run does not equal the plain run' % name
+    assert [res2[k] for k in ('key', 'n_tiles', 'grid', 'lds')] == [res[k] for k in ('key', 'n_tiles', 'grid', 'lds')], 'the plan moved with the pointers'
+    judge(i, run, res2, premise)

@@ -32,7 +32,7 @@ from test_gpu_ops import REPORT as OPS_REPORT
 pytestmark = pytest.mark.gpu
 
 REPORT = os.path.join(os.path.dirname(OPS_REPORT), 'gpu_conv_variants_report.txt')
-CHILD_SECONDS = 4.5                 # measured (2.2 to 4.5 s over four runs of both children): see the report
+CHILD_SECONDS = 2.9                 # measured with the fenced runs (2.1 to 2.9 s over two runs of both children): profiles/gpu_footprint_report.txt
 CHILD_TIMEOUT = max(60.0, 3 * CHILD_SECONDS)
 IDS = ['%02d' % i for i in range(len(cv.ROWS))]
 
@@ -110,8 +110,10 @@ def test_variant_row_is_planned_and_bit_equal(i, dev, premises, request):
             data, reason = request.getfixturevalue('children')[r.knob]
             assert data is not None, reason
             out, key, same = torch.from_numpy(data['out_' + tag]), int(data['key_' + tag]), bool(data['same_' + tag])
+            fence, equal = str(data['fence_' + tag]), bool(data['equal_' + tag])
         else:
             out, key, same = child.run_conv(c, dev)
+            fence, equal = child.fenced_twin(c, dev, out, key)
         assert key == cv.variant_key(r.variant), 'planned variant key %d, the row is for %d %s' % (key, cv.variant_key(r.variant), r.variant)
         assert same, 'an input was written to'
         if r.out == 'planar':
@@ -124,3 +126,7 @@ def test_variant_row_is_planned_and_bit_equal(i, dev, premises, request):
         ok, n, txt = ec.matches(got, c.want['out'], c, fp16, premises['f32' if f32 else 'fp16'])
         report('%-96s knob=%-6s key=%-5d %s mismatches=%s' % (c.name, r.knob or 'none', key, c.line(), txt))
         assert ok, '%s: %s' % (c.name, txt)
+        # the fenced second run (tests/footprint.py): NaN around every map, the weights and the bias, 0xA5 around the output
+        report('%-96s knob=%-6s key=%-5d fenced run: fences=%s equal=%s' % (c.name, r.knob or 'none', key, 'BROKEN' if fence else 'ok', 'ok' if equal else 'NO'))
+        assert not fence, '%s, fenced run: %s' % (c.name, fence)
+        assert equal, '%s: the fenced run does not equal the plain run' % c.name

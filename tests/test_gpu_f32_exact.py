@@ -18,13 +18,14 @@ import torch
 import conv_variant_child as child
 import exact_cases as ec
 import f32_cases as fc
+import footprint as fp
 from f32_cases import get_case
 from test_gpu_ops import REPORT as OPS_REPORT
 
 pytestmark = pytest.mark.gpu
 
 REPORT = os.path.join(os.path.dirname(OPS_REPORT), 'gpu_f32_exact_report.txt')
-GUARD, MARK = 64, 7.0               # elements behind a directly allocated output, and what they and the channel padding hold before the launch
+MARK = 7.0                          # what the fences around a directly allocated output and its channel padding hold before the launch
 
 
 def report(line):
@@ -49,22 +50,37 @@ def f32(t, dev):
     return t.float().contiguous().to(dev)
 
 
+def f32_fenced(t, dev):
+    """The same values as a view between NaN fences (tests/footprint.py)."""
+    return fp.fenced_input(t.float().contiguous(), dev, 'nan')
+
+
 def marked(shape, dtype, dev):
-    """(flat buffer of the shape's elements + GUARD, all MARK; its view of that shape)."""
+    """((flat buffer, lead), its view of that shape): the buffer is all MARK, and a lead and a tail of footprint.fence_bytes(bytes of
+    the shape) each lie before and behind the view."""
     n = 1
     for s in shape:
         n *= s
-    buf = torch.full((n + GUARD,), MARK, dtype=dtype, device=dev)
-    return buf, buf[:n].view(*shape)
+    esz = torch.empty((), dtype=dtype).element_size()
+    lead = fp.fence_bytes(n * esz) // esz
+    buf = torch.full((2 * lead + n,), MARK, dtype=dtype, device=dev)
+    view = buf[lead:lead + n].view(*shape)
+    assert view.data_ptr() % 16 == 0
+    return (buf, lead), view
 
 
-def guard_ok(buf):
-    return bool((buf[-GUARD:] == MARK).all())
+def guard_ok(marked_buf):
+    buf, lead = marked_buf
+    return bool((buf[:lead] == MARK).all()) and bool((buf[-lead:] == MARK).all())
 
 
 def run_mfma(c, dev):
     out, key, same = child.run_conv(c, dev)
     assert same, 'an input was written to'
+    fence, equal = child.fenced_twin(c, dev, out, key)
+    report('%-62s key=%-5d fenced run: fences=%s equal=%s' % (c.name, key, 'BROKEN' if fence else 'ok', 'ok' if equal else 'NO'))
+    assert not fence, '%s, fenced run: %s' % (c.name, fence)
+    assert equal, '%s: the fenced run does not equal the plain run' % c.name
     p = c.p
     co = p['w'].shape[0]
     if p['out'] == 'planar':
@@ -74,11 +90,13 @@ def run_mfma(c, dev):
 
 
 def run_direct(c, dev):
-    """refvsr_conv_direct_f32 into a marked buffer: the guard and, for the fp16 HWC store, channels cout .. out_c stay as they were."""
+    """refvsr_conv_direct_f32 from NaN-fenced inputs into a marked buffer: the fences before and behind the output and, for the fp16
+    HWC store, channels cout .. out_c stay as they were."""
     from refvsr_amd import hip
     from refvsr_amd.ops import _ptr, _stream
     p, r = c.p, c.run
-    x, w, b = f32(p['srcs'][0], dev), f32(p['w'], dev), f32(p['b'], dev)
+    fp.reset_inputs()
+    x, w, b = f32_fenced(p['srcs'][0], dev), f32_fenced(p['w'], dev), f32_fenced(p['b'], dev)
     keep = [t.clone() for t in (x, w, b)]
     co, ci, ks, _ = p['w'].shape
     h, wd = x.shape[1:]
@@ -88,9 +106,13 @@ def run_direct(c, dev):
     hip.check(hip.lib().refvsr_conv_direct_f32(_ptr(x), ci, h, wd, _ptr(w), _ptr(b), co, ks, p['stride'], ks // 2, p['act'], _ptr(out), int(bool(oc)), oc,
                                                _stream()), 'conv_direct_f32')
     torch.cuda.synchronize()
-    assert guard_ok(buf), 'written behind the output'
+    assert guard_ok(buf), 'written before or behind the output'
     assert all(torch.equal(a, k) for a, k in zip((x, w, b), keep)), 'an input was written to'
+    assert fp.inputs_unchanged() is None, fp.inputs_unchanged()
+    fp.reset_inputs()
     out = out.cpu()
+    assert not torch.isnan(out).any(), 'a NaN from an input fence reached the output'
+    report('%-62s fenced run: fences=ok' % c.name)
     if not oc:
         return {'out': out.double()}
     assert bool((out[:, :, co:] == MARK).all()), 'the channel padding of the fp16 HWC output was written to'
@@ -106,15 +128,26 @@ def run_c1x1(c, dev):
     out = ops.conv1x1_f32(x, w, b, p['act'])
     torch.cuda.synchronize()
     assert all(torch.equal(a, k) for a, k in zip((x, w, b), keep)), 'an input was written to'
+    # the fenced second run: NaN around the map, the weights and the bias, 0xA5 around the output
+    fp.reset_inputs()
+    xf, wf, bf = f32_fenced(p['srcs'][0].permute(1, 2, 0), dev), f32_fenced(p['w'][:, :, 0, 0], dev), f32_fenced(p['b'], dev)
+    with fp.fenced_outputs(ops) as fo:
+        out2 = ops.conv1x1_f32(xf, wf, bf, p['act'])
+        bad = fp.judge(fo, [out2], [out])
+    fp.reset_inputs()
+    report('%-62s fenced run: fences=%s equal=%s' % (c.name, 'BROKEN' if bad else 'ok', 'NO' if 'differs' in bad else 'ok'))
+    assert not bad, '%s, fenced run: %s' % (c.name, bad)
     return {'out': out.cpu().double()}
 
 
 def run_prep(c, dev):
-    """refvsr_frame_prep into marked buffers -> lr_n as 'out', ref_n, lr8, ref8 as [3, h, w]; the zero lanes are checked here."""
+    """refvsr_frame_prep from NaN-fenced inputs into marked buffers -> lr_n as 'out', ref_n, lr8, ref8 as [3, h, w]; the zero lanes
+    are checked here."""
     from refvsr_amd import hip
     from refvsr_amd.ops import _ptr, _stream
     p = c.p
-    lr, ref, w, b = f32(p['lr'], dev), f32(p['ref'], dev), f32(p['w'], dev), f32(p['b'], dev)
+    fp.reset_inputs()
+    lr, ref, w, b = f32_fenced(p['lr'], dev), f32_fenced(p['ref'], dev), f32_fenced(p['w'], dev), f32_fenced(p['b'], dev)
     keep = [t.clone() for t in (lr, ref, w, b)]
     h, wd = lr.shape[1:]
     hr, wr = ref.shape[1:]
@@ -124,11 +157,15 @@ def run_prep(c, dev):
     hip.check(hip.lib().refvsr_frame_prep(_ptr(lr), h, wd, _ptr(ref), hr, wr, _ptr(w), _ptr(b), _ptr(lr8), _ptr(ref8), _ptr(lr_n), _ptr(ref_n), _stream()),
               'frame_prep')
     torch.cuda.synchronize()
-    assert all(guard_ok(bf) for bf, _ in bufs), 'written behind an output (ref_n ends at the last whole 2 x 2 quad)'
+    assert all(guard_ok(bf) for bf, _ in bufs), 'written before or behind an output (ref_n ends at the last whole 2 x 2 quad)'
     assert all(torch.equal(a, k) for a, k in zip((lr, ref, w, b), keep)), 'an input was written to'
+    assert fp.inputs_unchanged() is None, fp.inputs_unchanged()
+    fp.reset_inputs()
+    report('%-62s fenced run: fences=ok' % c.name)
     res = {}
     for name, t in (('lr8', lr8), ('ref8', ref8), ('out', lr_n), ('ref_n', ref_n)):
         t = t.cpu()
+        assert not torch.isnan(t).any(), '%s: a NaN from an input fence reached the output' % name
         assert not t[:, :, 3:].any(), '%s: the zero lanes are not zero' % name
         res[name] = t[:, :, :3].permute(2, 0, 1).double().contiguous()
     return res

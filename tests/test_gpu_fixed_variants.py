@@ -36,7 +36,7 @@ from test_gpu_ops import REPORT as OPS_REPORT
 pytestmark = pytest.mark.gpu
 
 REPORT = os.path.join(os.path.dirname(OPS_REPORT), 'gpu_fixed_variants_report.txt')
-CHILD_SECONDS = 3.1                 # measured (2.1 to 3.1 s over three runs): see the report
+CHILD_SECONDS = 2.4                 # measured with the fenced runs (2.2 and 2.4 s over two runs): profiles/gpu_footprint_report.txt
 CHILD_TIMEOUT = max(60.0, 3 * CHILD_SECONDS)
 IDS = ['%02d' % i for i in range(len(fv.ROWS))]
 T0 = [None]
@@ -98,7 +98,7 @@ def _from_child(data, t):
     res = {}
     for k, v in data.items():
         if k.startswith(t + '.'):
-            res[k[len(t) + 1:]] = torch.from_numpy(v) if v.ndim else int(v)
+            res[k[len(t) + 1:]] = torch.from_numpy(v) if v.ndim else str(v) if v.dtype.kind == 'U' else int(v)
     return res
 
 
@@ -133,6 +133,12 @@ def judge(i, run, form, res, premise_ok):
         report('%-104s knob=%-4s key=%-13d tiles=%-3d %s mismatches=%s' % (c.name, r.knob or 'none', res['key'], res['n_tiles'], c.line(),
                                                                          '; '.join(l for l in lines if l.startswith('map %d ' % b) or not r.batch)))
     assert ok, '%s: %s' % (cases[0].name, '; '.join(lines))
+    # the fenced second run (tests/footprint.py): NaN around every map (each map of a multi-map row on its own), the blob and the
+    # fp32 operands, 0xA5 around every allocation of ops -- outputs in every result format and the chain's scratch maps
+    report('%-104s knob=%-4s key=%-13d fenced run: fences=%s equal=%s' % (cases[0].name, r.knob or 'none', res['key'], 'BROKEN' if res['fence'] else 'ok',
+                                                                         'ok' if res['equal'] else 'NO'))
+    assert not res['fence'], '%s, fenced run: %s' % (cases[0].name, res['fence'])
+    assert res['equal'], '%s: the fenced run does not equal the plain run' % cases[0].name
 
 
 @pytest.mark.parametrize('i', range(len(fv.ROWS)), ids=IDS)

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import footprint as fp
 import match_cases as mc
 from test_gpu_ops import REPORT as OPS_REPORT
 
@@ -47,32 +48,54 @@ def dev():
 
 
 class Inputs(object):
-    """Device copies of a case's inputs; unchanged() proves that no kernel wrote to one of them."""
+    """Device copies of a case's inputs; unchanged() proves that no kernel wrote to one of them.  fenced: every copy is a view
+    between the fences of footprint.fenced_input: NaN around rows, low rows, features and inverse norms, zeros ('benign') around what
+    a kernel turns into an address -- candidate tables, their values, flag lists."""
 
-    def __init__(self, dev):
-        self.dev, self.kept = dev, []
+    def __init__(self, dev, fenced=False):
+        self.dev, self.kept, self.fenced = dev, [], fenced
+        if fenced:
+            fp.reset_inputs()
 
     def _keep(self, t):
         self.kept.append((t, t.clone()))
         return t
 
-    def f16(self, a):
-        assert a.dtype == np.float16
-        return self._keep(torch.from_numpy(np.ascontiguousarray(a)).to(self.dev))
+    def _put(self, t, poison):
+        return fp.fenced_input(t, self.dev, poison) if self.fenced else t.to(self.dev)
 
-    def f32(self, a):
+    def f16(self, a, poison='nan'):
+        assert a.dtype == np.float16
+        return self._keep(self._put(torch.from_numpy(np.ascontiguousarray(a)), poison))
+
+    def f32(self, a, poison='nan'):
         t = torch.from_numpy(np.ascontiguousarray(a))
         assert torch.equal(t.float().double(), t), 'input is not fp32-representable'
-        return self._keep(t.float().to(self.dev))
+        return self._keep(self._put(t.float(), poison))
 
-    def i32(self, a):
+    def i32(self, a, poison='benign'):
         assert np.abs(a).max() < 2 ** 31
-        return self._keep(torch.from_numpy(np.ascontiguousarray(a)).to(torch.int32).to(self.dev))
+        return self._keep(self._put(torch.from_numpy(np.ascontiguousarray(a)).to(torch.int32), poison))
 
     def unchanged(self):
         torch.cuda.synchronize()
         for t, t0 in self.kept:
             assert torch.equal(t.view(torch.uint8), t0.view(torch.uint8)), 'an input tensor was written to'
+        if self.fenced:
+            assert fp.inputs_unchanged() is None, fp.inputs_unchanged()
+            fp.reset_inputs()
+
+
+def fenced_verdict(label, fo, results, plain, flagged=None):
+    """The fenced second run's assertions: every fence intact and every result fenced, the raw results equal to the plain run's, no
+    NaN (footprint.judge); one report line.  flagged = (fenced run's, plain run's) flag list: fenced like the others, compared as
+    the set it is (its order is the order the columns were flagged in)."""
+    bad = fp.judge(fo, results, plain)
+    if flagged is not None:
+        bad = '\n'.join(b for b in (bad, '\n'.join(fo.problems([flagged[0]])),
+                                    '' if np.array_equal(flagged_set(flagged[0]), flagged_set(flagged[1])) else 'the flagged set differs from the plain run') if b)
+    report('%-52s fenced run: fences=%s equal=%s' % (label, 'BROKEN' if bad else 'ok', 'NO' if 'differs' in bad else 'ok'))
+    assert not bad, '%s, fenced run: %s' % (label, bad)
 
 
 def bits32(a):
@@ -128,6 +151,12 @@ def test_top2_returns_the_reference_candidates(dev, name, splits):
     ref_rows, lr_rows = (inp.f16(r) for r in c.rows())
     ci, cv = ops.match_top2(ref_rows, c.n_ref, lr_rows, c.n_lr, splits)
     inp.unchanged()
+    inp2 = Inputs(dev, True)
+    ref_rows2, lr_rows2 = (inp2.f16(r) for r in c.rows())
+    with fp.fenced_outputs(ops) as fo:
+        got2 = ops.match_top2(ref_rows2, c.n_ref, lr_rows2, c.n_lr, splits)
+        fenced_verdict('%s splits=%d' % (name, splits), fo, got2, (ci, cv))
+    inp2.unchanged()
     ci, cv = ci.cpu().numpy().astype(np.int64), cv.cpu().numpy()
     wi, wv = c.want(splits)
     assert ci.shape == wi.shape == (c.n_lr, 2 * splits)
@@ -156,19 +185,31 @@ def feat_inputs(inp, fc):
                 ref_lo=ref_lo)
 
 
-def run_refine(dev, c, fc, cand, cand_val, margin, sparse_lo=False):
-    """ops.match_refine on host-built rows -> (idx, conf, flagged set or None) as numpy; the inputs must come back unchanged."""
+def _refine(dev, fc, cand, cand_val, margin, sparse_lo, fenced):
+    """One ops.match_refine call on host-built rows -> (conf, idx[, flagged]) as returned; the inputs must come back unchanged."""
     from refvsr_amd import ops
-    inp = Inputs(dev)
+    inp = Inputs(dev, fenced)
     t = feat_inputs(inp, fc)
     cand = inp.i32(cand)
     if margin is None:
-        conf, idx = ops.match_refine(t['lf'], t['rf'], t['il'], t['ir'], cand)
-        fl = None
+        got = ops.match_refine(t['lf'], t['rf'], t['il'], t['ir'], cand)
     else:
-        conf, idx, fl = ops.match_refine(t['lf'], t['rf'], t['il'], t['ir'], cand, inp.f32(cand_val), float(margin),
-                                         (t['lr_hi'], None if sparse_lo else t['lr_lo']), (t['ref_hi'], t['ref_lo']))
+        got = ops.match_refine(t['lf'], t['rf'], t['il'], t['ir'], cand, inp.f32(cand_val, 'benign'), float(margin),
+                               (t['lr_hi'], None if sparse_lo else t['lr_lo']), (t['ref_hi'], t['ref_lo']))
     inp.unchanged()
+    return got
+
+
+def run_refine(dev, c, fc, cand, cand_val, margin, sparse_lo=False):
+    """ops.match_refine on host-built rows -> (idx, conf, flagged set or None) as numpy; the inputs must come back unchanged.  Then
+    the fenced second run of the same call (its zeroed scratch and, with sparse_lo, the low rows it writes are fenced allocations)."""
+    from refvsr_amd import ops
+    got = _refine(dev, fc, cand, cand_val, margin, sparse_lo, False)
+    with fp.fenced_outputs(ops) as fo:
+        got2 = _refine(dev, fc, cand, cand_val, margin, sparse_lo, True)
+        fenced_verdict('%s margin=%s lr_lo=%s' % (c.name, margin, 'None' if sparse_lo else 'dense'), fo, got2[:2], got[:2],
+                       (got2[2], got[2]) if len(got) == 3 else None)
+    conf, idx, fl = got if len(got) == 3 else (got[0], got[1], None)
     return idx.cpu().numpy().astype(np.int64), conf.cpu().numpy(), None if fl is None else flagged_set(fl)
 
 
@@ -205,22 +246,34 @@ def test_exact_search_of_a_crafted_flagged_list(dev, name):
     from refvsr_amd import hip, ops
     c = mc.exact_case(name)
     fc = c.fc
-    inp = Inputs(dev)
-    t = feat_inputs(inp, fc)
-    fl = np.zeros(fc.n + 1, np.int64)
-    fl[0] = c.count
-    fl[1:1 + c.count] = c.flagged
-    assert fl[1:].max() < fc.n and fl.min() >= 0
-    fl = inp.i32(fl)
-    keys = torch.zeros(fc.n, dtype=torch.int64, device=dev)
+    fl0 = np.zeros(fc.n + 1, np.int64)
+    fl0[0] = c.count
+    fl0[1:1 + c.count] = c.flagged
+    assert fl0[1:].max() < fc.n and fl0.min() >= 0
     conf0 = torch.from_numpy(c.conf0)
     assert torch.equal(conf0.float().double(), conf0)
-    conf, idx = conf0.float().to(dev), torch.from_numpy(c.idx0).to(torch.int32).to(dev)
-    p = ops._ptr
-    hip.check(hip.lib().refvsr_match_exact(p(t['lf']), fc.h, fc.w, p(t['rf']), fc.hr, fc.wr, p(t['lr_hi']), p(t['lr_lo']), p(t['ref_hi']),
-                                           p(t['ref_lo']), p(t['il']), p(t['ir']), p(fl), p(keys), p(conf), p(idx), ops._stream()),
-              'match_exact')
-    inp.unchanged()
+
+    def go(fenced):
+        """the call on plain tensors, or on fenced inputs and hand-marked keys / conf / idx (the buffers the kernel reads and writes)"""
+        inp = Inputs(dev, fenced)
+        t = feat_inputs(inp, fc)
+        fl = inp.i32(fl0)
+        bufs = [torch.zeros(fc.n, dtype=torch.int64), conf0.float(), torch.from_numpy(c.idx0).to(torch.int32)]
+        recs = [fp.marked_buffer(b, dev) for b in bufs] if fenced else []
+        keys, conf, idx = [r.view for r in recs] if fenced else [b.to(dev) for b in bufs]
+        p = ops._ptr
+        hip.check(hip.lib().refvsr_match_exact(p(t['lf']), fc.h, fc.w, p(t['rf']), fc.hr, fc.wr, p(t['lr_hi']), p(t['lr_lo']), p(t['ref_hi']),
+                                               p(t['ref_lo']), p(t['il']), p(t['ir']), p(fl), p(keys), p(conf), p(idx), ops._stream()),
+                  'match_exact')
+        inp.unchanged()
+        for r in recs:
+            assert not r.damage(), 'written outside %s %s: %s' % (tuple(r.view.shape), r.view.dtype, r.damage())
+        return conf, idx
+
+    conf, idx = go(False)
+    conf2, idx2 = go(True)
+    assert torch.equal(conf2, conf) and torch.equal(idx2, idx) and not torch.isnan(conf2).any(), 'the fenced run does not equal the plain run'
+    report('%-52s fenced run: fences=ok equal=ok' % name)
     wi, wc, _ = c.want()
     check(c, [('conf', bits32(conf.cpu().numpy()) != bits32(wc), conf.cpu().numpy(), wc),
               ('idx', idx.cpu().numpy().astype(np.int64) != wi, idx.cpu().numpy(), wi)])
@@ -255,6 +308,26 @@ def test_patches_rows_norms_and_the_whole_chain(dev, name):
     conf, idx, fl = ops.match_refine(lf, rf, inv_lr, inv_ref, cand, cval, ops.MATCH_EXACT_MARGIN, (lr_rows, lr_lo), (ref_rows, ref_lo))
     inp.unchanged()
     kept.unchanged()
+    # the fenced second run of the whole chain: NaN around the feature maps; rows, low rows and norms are fenced allocations of ops
+    # whose fences begin behind the last pad row; want_lo on and off
+    inp2 = Inputs(dev, True)
+    lf2, rf2 = inp2.f32(fc.lf), inp2.f32(fc.rf)
+    with fp.fenced_outputs(ops) as fo:
+        ops.set_match_patches_kernel(fc.mode)
+        try:
+            pl = ops.match_patches(lf2, mc.COLBLOCK, want_lo=True)
+            pr = ops.match_patches(rf2, mc.ROWCHUNK, want_lo=True)
+            pl0 = ops.match_patches(lf2, mc.COLBLOCK)
+            pr0 = ops.match_patches(rf2, mc.ROWCHUNK)
+            torch.cuda.synchronize()
+        finally:
+            ops.set_match_patches_kernel(1)
+        assert len(pl0) == len(pr0) == 2
+        t2 = ops.match_top2(pr[0], fc.n_ref, pl[0], fc.n, 1)
+        r2 = ops.match_refine(lf2, rf2, pl[1], pr[1], t2[0], t2[1], ops.MATCH_EXACT_MARGIN, (pl[0], pl[2]), (pr[0], pr[2]))
+        fenced_verdict(name, fo, [pl, pr, pl0, pr0, t2, r2[:2]],
+                       [(lr_rows, inv_lr, lr_lo), (ref_rows, inv_ref, ref_lo), (lr_rows, inv_lr), (ref_rows, inv_ref), (cand, cval), (conf, idx)], (r2[2], fl))
+    inp2.unchanged()
     wci, wcv, wi, wc, wf = mc.patch_want(fc, float(np.float32(ops.MATCH_EXACT_MARGIN)))
     cand, cval = cand.cpu().numpy().astype(np.int64), cval.cpu().numpy()
     items += [('cand_val', bits32(cval) != bits32(wcv), cval, wcv), ('cand_idx', cand != wci, cand, wci)]

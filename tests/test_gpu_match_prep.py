@@ -135,6 +135,15 @@ def test_avgpool_pyramid_equals_five_pools(dev, h, w):
     for k in range(5):
         assert got[k].shape == want[k + 1].shape and got[k].is_contiguous()
         assert torch.equal(got[k], want[k + 1]), 'level %d' % (k + 1)
+    # the fenced second run (tests/footprint.py): NaN around the frame, 0xA5 around the one allocation that holds the five levels
+    import footprint as fp
+    fp.reset_inputs()
+    xf = fp.fenced_input(x.cpu(), dev, 'nan')
+    with fp.fenced_outputs(ops) as fo:
+        got2 = ops.avgpool_pyramid(xf)
+        bad = fp.judge(fo, got2, got)
+    fp.reset_inputs()
+    assert not bad, 'fenced run: ' + bad
 
 
 @pytest.mark.parametrize('h,w,hr,wr', [(2, 2, 2, 2), (6, 10, 6, 10), (34, 70, 34, 70), (6, 10, 7, 11)])

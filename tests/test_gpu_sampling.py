@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+import footprint as fp
 import sampling_cases as sc
 from sampling_cases import get_case
 from test_gpu_exact import nhwc16, planar64
@@ -54,30 +55,40 @@ def dev():
 
 # ---- feeding the kernels -------------------------------------------------------------------------------------------------------------
 class Inputs(object):
-    """Device copies of a case's inputs; unchanged() proves that no kernel wrote to one of them."""
+    """Device copies of a case's inputs; unchanged() proves that no kernel wrote to one of them.  fenced: every copy is a view
+    between the fences of footprint.fenced_input, of the poison kind its call names: 'nan' for data that enters arithmetic, 'benign'
+    (zeros) for what a kernel turns into a coordinate or an address -- flows, offsets and masks, affine parameters, indices."""
 
-    def __init__(self, dev):
-        self.dev, self.kept = dev, []
+    def __init__(self, dev, fenced=False):
+        self.dev, self.kept, self.fenced = dev, [], fenced
+        if fenced:
+            fp.reset_inputs()
 
     def _keep(self, t):
         self.kept.append((t, t.clone()))
         return t
 
-    def f16(self, a, cs=None):
-        return self._keep(nhwc16(torch.from_numpy(np.ascontiguousarray(a)), self.dev, cs))
+    def _put(self, t, poison):
+        return fp.fenced_input(t, self.dev, poison) if self.fenced else t.to(self.dev)
 
-    def f32(self, a):
+    def f16(self, a, cs=None, poison='nan'):
+        return self._keep(self._put(nhwc16(torch.from_numpy(np.ascontiguousarray(a)), 'cpu', cs), poison))
+
+    def f32(self, a, poison='nan'):
         t = torch.from_numpy(np.ascontiguousarray(a))
         assert torch.equal(t.float().double(), t), 'input is not fp32-representable'
-        return self._keep(t.float().to(self.dev))
+        return self._keep(self._put(t.float(), poison))
 
-    def i32(self, a):
-        return self._keep(torch.from_numpy(np.ascontiguousarray(a)).to(torch.int32).to(self.dev))
+    def i32(self, a, poison='benign'):
+        return self._keep(self._put(torch.from_numpy(np.ascontiguousarray(a)).to(torch.int32), poison))
 
     def unchanged(self):
         torch.cuda.synchronize()
         for t, t0 in self.kept:
             assert torch.equal(t, t0), 'an input was written to'
+        if self.fenced:
+            assert fp.inputs_unchanged() is None, fp.inputs_unchanged()
+            fp.reset_inputs()
 
 
 def np16(t, c):
@@ -89,68 +100,102 @@ def np32(t):
     return t.cpu().double().numpy()
 
 
-def run_case(c, dev):
-    """{output: float64 numpy array in the reference's layout} of case c through its ops.* entry point."""
+BENIGN = 'benign'
+
+
+def run_case(c, dev, fenced=False):
+    """({output: float64 numpy array in the reference's layout}, [the raw result tensors on the cpu], fence) of case c through its
+    ops.* entry point.  fenced: the inputs between fences (Inputs), every allocation of ops between 0xA5 fences; fence is
+    footprint.judge's verdict on fences, results, NaN and inputs ('' = all is well; always '' for a plain run)."""
+    from refvsr_amd import ops
+    if not fenced:
+        out, raw = _run_case(c, dev, Inputs(dev))
+        return out, raw, ''
+    I = Inputs(dev, True)
+    with fp.fenced_outputs(ops) as fo:
+        raw = []
+        out = _run_case(c, dev, I, raw)[0]
+        fence = fp.judge(fo, raw)
+    return out, [t.cpu() for t in raw], fence
+
+
+def _run_case(c, dev, I, raw=None):
     from refvsr_amd import hip, ops
-    p, I = c.p, Inputs(dev)
+    p = c.p
+    raw = [] if raw is None else raw
+
+    def K(t):                                                # keeps the raw result tensors as the entry point returned them
+        raw.extend(t if isinstance(t, (tuple, list)) else [t])
+        return t
     if c.op == 'warp':
         entry = c.run['entry']
         if entry == 'warp_planar':
-            out = {'out': np32(ops.warp_planar(I.f32(p['x']), I.f32(p['flow'])))}
+            out = {'out': np32(K(ops.warp_planar(I.f32(p['x']), I.f32(p['flow'], BENIGN))))}
         else:
             fn = ops.warp_nhwc16_up2 if entry == 'warp_nhwc16_up2' else ops.warp_nhwc16
-            out = {'out': np16(fn(I.f16(p['x']), I.f32(p['flow'])), p['x'].shape[0])}
+            out = {'out': np16(K(fn(I.f16(p['x']), I.f32(p['flow'], BENIGN))), p['x'].shape[0])}
     elif c.op == 'resize':
-        got = ops.resize(I.f32(p['x']), p['out_hw'], p['mode'], p.get('src_scale'), p.get('mean'), p.get('std'), p.get('chan_mul'),
-                         bool(p.get('clamp01')), c.run['nhwc16'])
+        got = K(ops.resize(I.f32(p['x']), p['out_hw'], p['mode'], p.get('src_scale'), p.get('mean'), p.get('std'), p.get('chan_mul'),
+                           bool(p.get('clamp01')), c.run['nhwc16']))
         out = {'out': np16(got, p['x'].shape[0]) if c.run['nhwc16'] else np32(got)}     # (np16: the channels 3 .. 7 must be zero)
     elif c.op == 'spynet':
         B = len(p['ref'])
         refs, supps = [I.f32(a) for a in p['ref']], [I.f32(a) for a in p['supp']]
-        prev = I.f32(np.stack(p['flow_prev'])) if p['flow_prev'] is not None else None
+        prev = I.f32(np.stack(p['flow_prev']), BENIGN) if p['flow_prev'] is not None else None
         if B == 1:
-            o8, up = ops.spynet_level_input(refs[0], supps[0], prev[0] if prev is not None else None)
+            o8, up = K(ops.spynet_level_input(refs[0], supps[0], prev[0] if prev is not None else None))
             o8, up = o8[None], up[None]
         else:
-            o8, up = ops.spynet_level_input_batch(refs, supps, prev)
+            o8, up = K(ops.spynet_level_input_batch(refs, supps, prev))
         out = {'out': np.stack([np16(o8[b], 8) for b in range(B)]), 'flow_up': np32(up)}
     elif c.op == 'aligned':
-        out = {'out': np16(ops.aligned_sample(I.f16(p['x']), I.f32(p['affine']), p['ks']), p['x'].shape[0])}
+        out = {'out': np16(K(ops.aligned_sample(I.f16(p['x']), I.f32(p['affine'], BENIGN), p['ks'])), p['x'].shape[0])}
     elif c.op == 'gather':
         gh, gw = p['idx'].shape
         idx = I.i32(p['idx'].reshape(-1))
         if c.run['kind'] == 'nhwc16':
-            out = {'out': np16(ops.block_gather_nhwc16(I.f16(p['value']), idx, gh, gw, p['s']), p['value'].shape[0])}
+            out = {'out': np16(K(ops.block_gather_nhwc16(I.f16(p['value']), idx, gh, gw, p['s'])), p['value'].shape[0])}
         elif c.run['kind'] == 'rgb16':
-            out = {'out': np16(ops.block_gather_rgb(I.f32(p['value']), idx, gh, gw, p['s']), 3)}
+            out = {'out': np16(K(ops.block_gather_rgb(I.f32(p['value']), idx, gh, gw, p['s'])), 3)}
         else:
-            out = {'out': np32(ops.block_gather_rgb(I.f32(p['value']), idx, gh, gw, p['s'], planar=True))}
+            out = {'out': np32(K(ops.block_gather_rgb(I.f32(p['value']), idx, gh, gw, p['s'], planar=True)))}
     elif c.op == 'dcn':
-        out = {'out': np16(ops.dcn_sample(I.f16(p['x']), I.f32(p['om']), p['dg']), 9 * p['x'].shape[0])}
+        out = {'out': np16(K(ops.dcn_sample(I.f16(p['x']), I.f32(p['om'], BENIGN), p['dg'])), 9 * p['x'].shape[0])}
     elif c.op == 'pool3s2':                                 # into channels [8, 8 + c) of a wider map: the others keep a sentinel
         x = I.f16(p['x'])
         h, w, ch = x.shape
         ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-        wide = torch.full((ho, wo, ch + 16), -77.0, dtype=torch.float16, device=dev)
+        wide = K(ops.torch.empty((ho, wo, ch + 16), dtype=torch.float16, device=dev).fill_(-77.0))  # (ops.torch: fenced in a fenced run)
         hip.check(hip.lib().refvsr_pool3s2_nhwc16(C.c_void_p(x.data_ptr()), h, w, ch, C.c_void_p(wide.data_ptr()), ch + 16, 8, int(p['is_max']),
                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'pool3s2')
         torch.cuda.synchronize()
         assert bool((wide[:, :, :8] == -77.0).all()) and bool((wide[:, :, 8 + ch:] == -77.0).all()), 'pool3s2 wrote outside its channels'
         out = {'out': np16(wide[:, :, 8:8 + ch].contiguous(), ch)}
     elif c.op == 'up2':
-        out = {'out': np16(ops.up2_bilinear_nhwc16(I.f16(p['x']), p['mul']), p['x'].shape[0])}
+        out = {'out': np16(K(ops.up2_bilinear_nhwc16(I.f16(p['x']), p['mul'])), p['x'].shape[0])}
     elif c.op == 'tsa_weight':
-        got = ops.tsa_weight([I.f16(a) for a in p['aligned']], [I.f16(a) for a in p['emb']], I.f16(p['emb_ref']))
+        got = K(ops.tsa_weight([I.f16(a) for a in p['aligned']], [I.f16(a) for a in p['emb']], I.f16(p['emb_ref'])))
         out = {'out': np16(got, got.shape[2])}
     elif c.op == 'tsa_blend':
-        out = {'out': np16(ops.tsa_blend(I.f16(p['feat']), I.f16(p['attn']), I.f16(p['add'])), p['feat'].shape[0])}
+        out = {'out': np16(K(ops.tsa_blend(I.f16(p['feat']), I.f16(p['attn']), I.f16(p['add']))), p['feat'].shape[0])}
     else:
         assert c.op == 'pool2'
         x = I.f32(p['x'])
-        got = ops.max2(x, I.f32(p['y'])) if p['kind'] == 'max2' else (ops.maxpool2(x) if p['kind'] == 'max' else ops.avgpool2(x))
+        got = K(ops.max2(x, I.f32(p['y'])) if p['kind'] == 'max2' else (ops.maxpool2(x) if p['kind'] == 'max' else ops.avgpool2(x)))
         out = {'out': np32(got)}
     I.unchanged()
-    return out
+    return out, [t.cpu() for t in raw]
+
+
+def fenced_twin(c, dev, raw, judge):
+    """The fenced second run of a case whose plain run returned the raw tensors `raw`: fences intact and every result fenced, raw
+    results equal to the plain run's, no NaN, inputs and their fences unchanged -- and the same judgement against the reference."""
+    got2, raw2, fence = run_case(c, dev, fenced=True)
+    equal = len(raw) == len(raw2) and all(a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b) for a, b in zip(raw, raw2))
+    report('%-58s fenced run: fences=%s equal=%s' % (c.name, 'BROKEN' if fence else 'ok', 'ok' if equal else 'NO'))
+    assert not fence, '%s, fenced run: %s' % (c.name, fence)
+    assert equal, '%s: the fenced run does not equal the plain run' % c.name
+    judge(c, got2, ' [fenced]')
 
 
 def check_exact(c, got, tag=''):
@@ -182,13 +227,17 @@ def check_general(c, got, tag=''):
 def test_kernel_equals_reference_bit_for_bit(dev, name):
     c = get_case(name)
     c.assert_strong()
-    check_exact(c, run_case(c, dev))
+    got, raw, _ = run_case(c, dev)
+    check_exact(c, got)
+    fenced_twin(c, dev, raw, check_exact)
 
 
 @pytest.mark.parametrize('name', sc.GENERAL)
 def test_kernel_within_the_reference_bracket(dev, name):
     c = get_case(name)
-    check_general(c, run_case(c, dev))
+    got, raw, _ = run_case(c, dev)
+    check_general(c, got)
+    fenced_twin(c, dev, raw, check_general)
 
 
 def test_pool3s2_pair_is_max_then_avg(dev):
