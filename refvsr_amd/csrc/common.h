@@ -309,6 +309,45 @@ __host__ __device__ __forceinline__ size_t rv_result_index(const int fmt, const 
 static inline bool rv_result_fmt_ok(const int fmt) {
     return fmt >= 0 && (fmt & ~(REFVSR_RESULT_FMT_MASK | REFVSR_RESULT_HWC)) == 0 && (fmt & REFVSR_RESULT_FMT_MASK) <= REFVSR_RESULT_U8;
 }
+// bytes of one sample of a checked result format
+static inline size_t rv_result_sample_bytes(const int fmt) {
+    const int f = fmt & REFVSR_RESULT_FMT_MASK;
+    return f == REFVSR_RESULT_F32 ? 4 : f == REFVSR_RESULT_F16 ? 2 : 1;
+}
+// f(RvType<T>{}, std::bool_constant<HWC>{}) for the sample type and the layout of a checked result format: the launchers that are
+// templates over both (yuv.hip, resize.hip) name their instance with `typename decltype(t)::type` and `decltype(hwc)::value`
+template <typename T>
+struct RvType { typedef T type; };
+template <class F>
+static auto rv_result_dispatch(const int fmt, F&& f) {
+    const int s = fmt & REFVSR_RESULT_FMT_MASK;
+    const bool hwc = (fmt & REFVSR_RESULT_HWC) != 0;
+    if (s == REFVSR_RESULT_F32) return hwc ? f(RvType<float>{}, std::true_type{}) : f(RvType<float>{}, std::false_type{});
+    if (s == REFVSR_RESULT_F16) return hwc ? f(RvType<f16>{}, std::true_type{}) : f(RvType<f16>{}, std::false_type{});
+    return hwc ? f(RvType<unsigned char>{}, std::true_type{}) : f(RvType<unsigned char>{}, std::false_type{});
+}
+// The frame tables of a launcher that reads nframes frames of sbytes bytes (samples of ssize bytes) and writes as many of dbytes
+// bytes (samples of dsize bytes): src[] and dst[] go to the argument struct's tables once every frame is there and aligned to its
+// samples, and no destination lies over a source or another destination.  `name` in front of the refusals.
+static int rv_frame_tables(const char* name, const void* const* src, void* const* dst, const int nframes, const size_t ssize,
+                           const size_t dsize, const size_t sbytes, const size_t dbytes, const void** a_src, void** a_dst) {
+    for (int i = 0; i < nframes; ++i) {
+        RV_CHECK(src[i] && dst[i], "%s: null pointer (frame %d)", name, i);
+        RV_CHECK(((uintptr_t)src[i] & (ssize - 1)) == 0 && ((uintptr_t)dst[i] & (dsize - 1)) == 0,
+                 "%s: source and destination must be aligned to their samples (frame %d)", name, i);
+        a_src[i] = src[i];
+        a_dst[i] = dst[i];
+    }
+    for (int i = 0; i < nframes; ++i) {
+        const uintptr_t d0 = (uintptr_t)dst[i];
+        for (int j = 0; j < nframes; ++j) {
+            const uintptr_t s0 = (uintptr_t)src[j], d1 = (uintptr_t)dst[j];
+            RV_CHECK(d0 + dbytes <= s0 || s0 + sbytes <= d0, "%s: destination %d overlaps source %d", name, i, j);
+            RV_CHECK(i == j || d0 + dbytes <= d1 || d1 + dbytes <= d0, "%s: destinations %d and %d overlap", name, i, j);
+        }
+    }
+    return 0;
+}
 
 // lane l: a[l] + a[l ^ 32]   (v_mov, v_permlane32_swap, v_add per register): the fold of an accumulator whose lanes 32-63 hold the
 // lo sums (resblock24.hip, conv24.hip).  The two results are taken out of the builtin's vector as plain unsigned values first:

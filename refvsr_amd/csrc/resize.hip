@@ -201,8 +201,7 @@ extern "C" int refvsr_resize_aa(const void* const* src, int src_fmt, void* const
     RV_CHECK((long long)h <= (long long)RS_MAX_RATIO * oh && (long long)w <= (long long)RS_MAX_RATIO * ow,
              "resize_aa: the down-scale ratio is at most %d per axis (got %d x %d -> %d x %d)", RS_MAX_RATIO, h, w, oh, ow);
     RV_CHECK(clamp == 0 || clamp == 1, "resize_aa: clamp must be 0 or 1 (got %d)", clamp);
-    const int f = src_fmt & REFVSR_RESULT_FMT_MASK;
-    const size_t es = f == REFVSR_RESULT_F32 ? 4 : f == REFVSR_RESULT_F16 ? 2 : 1, ds = dst_fmt == REFVSR_RESULT_F32 ? 4 : 1;
+    const size_t es = rv_result_sample_bytes(src_fmt), ds = rv_result_sample_bytes(dst_fmt);
     RV_CHECK((long long)h * w * 3 * (long long)es < (1ll << 31) && (long long)oh * ow * 3 * (long long)ds < (1ll << 31),
              "resize_aa: frame too large for 32-bit offsets");
     // a column's (row's) taps: at least one, at most 2 support + 1 of the axis -- what resize.py:aa_taps makes -- and never more than
@@ -213,24 +212,10 @@ extern "C" int refvsr_resize_aa(const void* const* src, int src_fmt, void* const
              span1_x < RS_MAX_TAPS ? span1_x : RS_MAX_TAPS, span1_y < RS_MAX_TAPS ? span1_y : RS_MAX_TAPS, maxcnt_x, maxcnt_y);
     RV_CHECK((((uintptr_t)lo_x | (uintptr_t)cnt_x | (uintptr_t)lo_y | (uintptr_t)cnt_y) & 3) == 0 && (((uintptr_t)wx | (uintptr_t)wy) & 7) == 0,
              "resize_aa: tap tables must be aligned to their elements");
-    const size_t sbytes = (size_t)h * w * 3 * es, dbytes = (size_t)oh * ow * 3 * ds;
     ResizeArgs a;
     memset(&a, 0, sizeof(a));
-    for (int i = 0; i < nframes; ++i) {
-        RV_CHECK(src[i] && dst[i], "resize_aa: null pointer (frame %d)", i);
-        RV_CHECK(((uintptr_t)src[i] & (es - 1)) == 0 && ((uintptr_t)dst[i] & (ds - 1)) == 0,
-                 "resize_aa: source and destination must be aligned to their samples (frame %d)", i);
-        a.src[i] = src[i];
-        a.dst[i] = dst[i];
-    }
-    for (int i = 0; i < nframes; ++i) {
-        const uintptr_t d0 = (uintptr_t)dst[i];
-        for (int j = 0; j < nframes; ++j) {
-            const uintptr_t s0 = (uintptr_t)src[j], d1 = (uintptr_t)dst[j];
-            RV_CHECK(d0 + dbytes <= s0 || s0 + sbytes <= d0, "resize_aa: destination %d overlaps source %d", i, j);
-            RV_CHECK(i == j || d0 + dbytes <= d1 || d1 + dbytes <= d0, "resize_aa: destinations %d and %d overlap", i, j);
-        }
-    }
+    const int rc = rv_frame_tables("resize_aa", src, dst, nframes, es, ds, (size_t)h * w * 3 * es, (size_t)oh * ow * 3 * ds, a.src, a.dst);
+    if (rc) return rc;
     a.lo_x = lo_x; a.cnt_x = cnt_x; a.wx = wx;
     a.lo_y = lo_y; a.cnt_y = cnt_y; a.wy = wy;
     a.h = h; a.w = w; a.oh = oh; a.ow = ow;
@@ -247,8 +232,7 @@ extern "C" int refvsr_resize_aa(const void* const* src, int src_fmt, void* const
     RV_CHECK(lds <= 160 * 1024, "resize_aa: tile does not fit the LDS (%zu bytes)", lds);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)(((ntiles + 7) / 8) * 8 * 3), (unsigned)nframes);
-    const bool hwc = (src_fmt & REFVSR_RESULT_HWC) != 0;
-    if (f == REFVSR_RESULT_F32) return hwc ? rs_launch_dst<float, true>(dst_fmt, a, grid, lds, st) : rs_launch_dst<float, false>(dst_fmt, a, grid, lds, st);
-    if (f == REFVSR_RESULT_F16) return hwc ? rs_launch_dst<f16, true>(dst_fmt, a, grid, lds, st) : rs_launch_dst<f16, false>(dst_fmt, a, grid, lds, st);
-    return hwc ? rs_launch_dst<unsigned char, true>(dst_fmt, a, grid, lds, st) : rs_launch_dst<unsigned char, false>(dst_fmt, a, grid, lds, st);
+    return rv_result_dispatch(src_fmt, [&](auto t, auto hwc) {
+        return rs_launch_dst<typename decltype(t)::type, decltype(hwc)::value>(dst_fmt, a, grid, lds, st);
+    });
 }

@@ -257,41 +257,27 @@ static int yuv_convert(const char* name, const void* const* src, int src_fmt, vo
     RV_CHECK(rv_result_fmt_ok(src_fmt), "%s: unknown result format %d", name, src_fmt);
     RV_CHECK(yuv_fmt_ok(yuv_fmt), "%s: unknown yuv format %d", name, yuv_fmt);
     RV_CHECK(yuv_geometry_ok(h, w), "%s: h, w must be even and positive (got %d x %d)", name, h, w);
-    const int f = src_fmt & REFVSR_RESULT_FMT_MASK;
-    const size_t es = f == REFVSR_RESULT_F32 ? 4 : f == REFVSR_RESULT_F16 ? 2 : 1;
+    const size_t es = rv_result_sample_bytes(src_fmt);
     RV_CHECK((long long)h * w * 3 * (long long)es < (1ll << 31), "%s: frame too large for 32-bit offsets", name);
-    const size_t sbytes = (size_t)h * w * 3 * es, dbytes = yuv_frame_bytes(h, w, yuv_fmt, sampling);
     YuvArgs a;
     memset(&a, 0, sizeof(a));
-    for (int i = 0; i < nframes; ++i) {
-        RV_CHECK(src[i] && dst[i], "%s: null pointer (frame %d)", name, i);
-        RV_CHECK(((uintptr_t)src[i] & (es - 1)) == 0 && ((uintptr_t)dst[i] & (yuv_sample_bytes(yuv_fmt) - 1)) == 0,
-                 "%s: source and destination must be aligned to their samples (frame %d)", name, i);
-        a.src[i] = src[i];
-        a.dst[i] = dst[i];
-    }
-    for (int i = 0; i < nframes; ++i) {
-        const uintptr_t d0 = (uintptr_t)dst[i];
-        for (int j = 0; j < nframes; ++j) {
-            const uintptr_t s0 = (uintptr_t)src[j], d1 = (uintptr_t)dst[j];
-            RV_CHECK(d0 + dbytes <= s0 || s0 + sbytes <= d0, "%s: destination %d overlaps source %d", name, i, j);
-            RV_CHECK(i == j || d0 + dbytes <= d1 || d1 + dbytes <= d0, "%s: destinations %d and %d overlap", name, i, j);
-        }
-    }
+    const int rc = rv_frame_tables(name, src, dst, nframes, es, yuv_sample_bytes(yuv_fmt), (size_t)h * w * 3 * es,
+                                   yuv_frame_bytes(h, w, yuv_fmt, sampling), a.src, a.dst);
+    if (rc) return rc;
     a.h = h;
     a.w = w;
     for (int i = 0; i < 9; ++i) a.k[i] = coef9[i];
     hipStream_t st = (hipStream_t)stream;
-    const int npx = f == REFVSR_RESULT_U8 ? YuvSrc<unsigned char>::NPX : YuvSrc<float>::NPX;
+    const int npx = (src_fmt & REFVSR_RESULT_FMT_MASK) == REFVSR_RESULT_U8 ? YuvSrc<unsigned char>::NPX : YuvSrc<float>::NPX;
     const long items = (long)(sampling == REFVSR_YUV_SAMPLING_420 ? h / 2 : h) * ((w + npx - 1) / npx);
     const long want = (items + 255) / 256;
     long cap = (long)rv_stream_cus(st) * 8 / nframes;                // eight workgroups per CU over all frames
     if (cap < 32) cap = 32;
     const dim3 grid((unsigned)(want < cap ? want : cap), (unsigned)nframes);
-    const bool hwc = (src_fmt & REFVSR_RESULT_HWC) != 0, left = siting == REFVSR_YUV_SITING_LEFT && sampling != REFVSR_YUV_SAMPLING_444;
-    if (f == REFVSR_RESULT_F32) hwc ? yuv_launch<float, true>(yuv_fmt, sampling, left, grid, st, a) : yuv_launch<float, false>(yuv_fmt, sampling, left, grid, st, a);
-    else if (f == REFVSR_RESULT_F16) hwc ? yuv_launch<f16, true>(yuv_fmt, sampling, left, grid, st, a) : yuv_launch<f16, false>(yuv_fmt, sampling, left, grid, st, a);
-    else hwc ? yuv_launch<unsigned char, true>(yuv_fmt, sampling, left, grid, st, a) : yuv_launch<unsigned char, false>(yuv_fmt, sampling, left, grid, st, a);
+    const bool left = siting == REFVSR_YUV_SITING_LEFT && sampling != REFVSR_YUV_SAMPLING_444;
+    rv_result_dispatch(src_fmt, [&](auto t, auto hwc) {
+        yuv_launch<typename decltype(t)::type, decltype(hwc)::value>(yuv_fmt, sampling, left, grid, st, a);
+    });
     RV_LAUNCH_CHECK();
     return 0;
 }

@@ -703,17 +703,87 @@ def max2(a, b):
     return out
 
 
+def _chunks(n, per):
+    """(s0, count) of the library calls over n frames, at most `per` frames each: the frames [s0, s0 + count) of every frame op's tables."""
+    for s0 in range(0, n, per):
+        yield s0, min(per, n - s0)
+
+
+class _Cache(dict):
+    """The frame ops' caches (workspaces per device, stream and geometry; device tables per geometry): built on a miss, all dropped once
+    more than 16 are held."""
+
+    def get_or_build(self, key, build):
+        v = self.get(key)
+        if v is None:
+            if len(self) > 16:
+                self.clear()
+            v = self[key] = build()
+        return v
+
+
+def _workspace(cache, dev, st, h, w, nbytes, what, too_small, esize=8):
+    """The cached workspace of one full launch per (device, stream, h, w): nbytes() bytes as floats of esize = 8 | 4 bytes; nbytes() = 0
+    is the library's refusal of the geometry: `too_small` says why."""
+    def build():
+        n = nbytes()
+        if n == 0:
+            raise RuntimeError('%s: %s (got %d x %d)' % (what, too_small, h, w))
+        return torch.empty(n // esize, dtype={8: torch.float64, 4: torch.float32}[esize], device=dev)
+    return cache.get_or_build((dev, st.value, h, w), build)
+
+
+_RESULT_CODES = dict(RESULT_DTYPES.values())          # torch dtype -> REFVSR_RESULT_*
+
+
+def _src_fmt(dtype, lay):
+    """REFVSR_RESULT_* | REFVSR_RESULT_HWC of result frames of the dtype and layout ('chw' | 'hwc')."""
+    return _RESULT_CODES[dtype] | (hip.RESULT_HWC if lay == 'hwc' else 0)
+
+
+def _check_dense(name, noun, f, lay):
+    """The frame f of a frame op's `noun` ('results' | 'frames') is dense and of the layout `lay` of the first (result_layout_of)."""
+    if lay is None or result_layout_of(f) != lay:
+        raise RuntimeError('%s: %s must be dense and of one layout, contiguous [3, h, w] or the channels-last view of [h, w, 3] '
+                           '(config.result_layout), got strides %s' % (name, noun, tuple(f.stride())))
+
+
+def _result_frames(name, frames, noun):
+    """The result frames of a frame op as a list, at least one, the first a cuda float32 | float16 | uint8 [3,h,w]: (frames, h, w).  The
+    caller's own checks of h and w come next, then _result_format."""
+    frames = list(frames)
+    if not frames:
+        raise RuntimeError('%s: at least one frame' % name)
+    f0 = frames[0]
+    if not (f0.is_cuda and f0.dtype in _RESULT_CODES and f0.dim() == 3 and f0.shape[0] == 3):
+        raise RuntimeError('%s: cuda float32 | float16 | uint8 %s [3,h,w] (got %s %s %s)' % (name, noun, f0.device.type, f0.dtype, tuple(f0.shape)))
+    _, h, w = f0.shape
+    return frames, h, w
+
+
+def _result_format(name, frames, noun):
+    """Every frame of _result_frames' list has the first's dtype and geometry, lies on a GPU and is dense in one layout: the source
+    format of them all."""
+    f0 = frames[0]
+    lay = result_layout_of(f0)
+    for f in frames:
+        if f.shape != f0.shape or f.dtype != f0.dtype or not f.is_cuda:
+            raise RuntimeError('%s: frames must all be %s [3, %d, %d] (got %s %s)' % (name, f0.dtype, f0.shape[1], f0.shape[2], f.dtype, tuple(f.shape)))
+        _check_dense(name, noun, f, lay)
+    return _src_fmt(f0.dtype, lay)
+
+
 def _pairs_equal(pairs, name, ok):
     """refvsr_<name> over (a, b) pairs of one size in bytes, ok(a, b) asserted per pair: one launch per 32 pairs, one D2H sync."""
     if not pairs:
         return []
     nbytes = pairs[0][0].numel() * pairs[0][0].dtype.itemsize
     flags = torch.ones(len(pairs), dtype=torch.int32, device=pairs[0][0].device)
-    for s0 in range(0, len(pairs), 32):
-        chunk = pairs[s0:s0 + 32]
+    for s0, n in _chunks(len(pairs), 32):
+        chunk = pairs[s0:s0 + n]
         for a, b in chunk:
             assert ok(a, b) and a.dtype == b.dtype == pairs[0][0].dtype and a.numel() == b.numel() == pairs[0][0].numel()
-        hip.check(getattr(hip.lib(), 'refvsr_' + name)(_parr([a for a, _ in chunk]), _parr([b for _, b in chunk]), len(chunk), nbytes,
+        hip.check(getattr(hip.lib(), 'refvsr_' + name)(_parr([a for a, _ in chunk]), _parr([b for _, b in chunk]), n, nbytes,
                                                        C.c_void_p(flags.data_ptr() + 4 * s0), _stream()), name)
     return [bool(v) for v in flags.cpu().tolist()]
 
@@ -757,9 +827,9 @@ def _decode_frames(pairs, name, what, ok, max_frames, launch):
     h, w = pairs[0][1].shape[1:]
     for src, dst in pairs:
         assert ok(src, h, w) and _planar(dst, 3).shape[1:] == (h, w), what
-    for s0 in range(0, len(pairs), max_frames):
-        chunk = pairs[s0:s0 + max_frames]
-        hip.check(launch(_parr([s_ for s_, _ in chunk]), _parr([d for _, d in chunk]), len(chunk), h, w), name)
+    for s0, n in _chunks(len(pairs), max_frames):
+        chunk = pairs[s0:s0 + n]
+        hip.check(launch(_parr([s_ for s_, _ in chunk]), _parr([d for _, d in chunk]), n, h, w), name)
 
 
 def _frames_of(x, nd, dense, align, h, w, decode):
@@ -797,7 +867,8 @@ def ingest_frames(x):
     return _frames_of(x, 3, lambda x_: u8_layout(x_) is not None, 4, x.shape[-2], x.shape[-1], ingest_u8)
 
 
-_SCORE_WS = {}        # (device, stream handle, h, w) -> workspace of one full refvsr_score_frames launch
+_SCORE_WS = _Cache()  # (device, stream handle, h, w) -> workspace of one full refvsr_score_frames launch
+_TOO_SMALL = 'frames must be at least 7 x 7'          # both scorers' refusal of a geometry (the SSIM window)
 
 
 def _score_inputs(outs, gts, what, down=1):
@@ -807,8 +878,7 @@ def _score_inputs(outs, gts, what, down=1):
     assert outs and len(outs) == len(gts), '%s: as many results as ground truths' % what
     a0, g0 = outs[0], gts[0]
     _, h, w = a0.shape if down == 1 else g0.shape
-    fmts = {torch.float32: hip.RESULT_F32, torch.float16: hip.RESULT_F16, torch.uint8: hip.RESULT_U8}
-    assert a0.dtype in fmts and g0.dtype in (torch.float32, torch.uint8), '%s: float32 | float16 | uint8 results, float32 | uint8 ground truth' % what
+    assert a0.dtype in _RESULT_CODES and g0.dtype in (torch.float32, torch.uint8), '%s: float32 | float16 | uint8 results, float32 | uint8 ground truth' % what
     lay = u8_layout(g0) if g0.dtype == torch.uint8 else hip.INGEST_PLANAR
     alay = result_layout_of(a0)
     for a, g in zip(outs, gts):
@@ -818,33 +888,10 @@ def _score_inputs(outs, gts, what, down=1):
             raise RuntimeError('%s: result %s and ground truth %s must both be [3, %d, %d] after the down-scale by %d (the result %d times that)'
                                % (what, tuple(a.shape), tuple(g.shape), h, w, down, down))
         assert a.is_cuda and g.is_cuda and a.dtype == a0.dtype and g.dtype == g0.dtype
-        if alay is None or result_layout_of(a) != alay:
-            raise RuntimeError('%s: results must be dense and of one layout, contiguous [3, h, w] or the channels-last view of [h, w, 3] '
-                               '(config.result_layout), got strides %s' % (what, tuple(a.stride())))
+        _check_dense(what, 'results', a, alay)
         assert (u8_layout(g) if g.dtype == torch.uint8 else (hip.INGEST_PLANAR if g.is_contiguous() else None)) == lay and lay is not None, \
             '%s: ground-truth frames must be dense and of one layout' % what
-    return outs, gts, h, w, fmts[a0.dtype] | (hip.RESULT_HWC if alay == 'hwc' else 0), fmts[g0.dtype], lay
-
-
-def _score_workspace(cache, dev, st, h, w, nbytes, what, esize=8, too_small='frames must be at least 7 x 7'):
-    """The cached workspace of one full launch per (device, stream, h, w): nbytes() bytes as floats of esize = 8 | 4 bytes."""
-    key = (dev, st.value, h, w)
-    ws = cache.get(key)
-    if ws is None:
-        if len(cache) > 16:
-            cache.clear()
-        nbytes = nbytes()
-        if nbytes == 0:
-            raise RuntimeError('%s: %s (got %d x %d)' % (what, too_small, h, w))
-        ws = cache[key] = torch.empty(nbytes // esize, dtype={8: torch.float64, 4: torch.float32}[esize], device=dev)
-    return ws
-
-
-def _score_launches(outs, gts, launch):
-    """launch(pa, pg, n, s0) per REFVSR_SCORE_MAX_FRAMES pairs: the pointer tables of the n pairs from s0 on."""
-    for s0 in range(0, len(outs), hip.SCORE_MAX_FRAMES):
-        n = min(hip.SCORE_MAX_FRAMES, len(outs) - s0)
-        launch(_parr(outs[s0:s0 + n]), _parr(gts[s0:s0 + n]), n, s0)
+    return outs, gts, h, w, _src_fmt(a0.dtype, alay), _RESULT_CODES[g0.dtype], lay
 
 
 def score_frames(outs, gts, win=7, down=1):
@@ -862,20 +909,19 @@ def score_frames(outs, gts, win=7, down=1):
     outs, gts, h, w, afmt, gfmt, lay = _score_inputs(outs, gts, 'score_frames', down)
     st = _stream()
     dev = outs[0].device
-    ws = _score_workspace(_SCORE_WS, dev, st, h, w, lambda: hip.lib().refvsr_score_workspace_bytes(hip.SCORE_MAX_FRAMES, h, w), 'score_frames')
+    ws = _workspace(_SCORE_WS, dev, st, h, w, lambda: hip.lib().refvsr_score_workspace_bytes(hip.SCORE_MAX_FRAMES, h, w), 'score_frames', _TOO_SMALL)
     scores = torch.empty((len(outs), 2), dtype=torch.float64, device=dev)
-
-    def launch(pa, pg, n, s0):
+    for s0, n in _chunks(len(outs), hip.SCORE_MAX_FRAMES):
+        pa, pg = _parr(outs[s0:s0 + n]), _parr(gts[s0:s0 + n])
         tail = (int(win), _ptr(ws), ws.numel() * 8, C.c_void_p(scores.data_ptr() + 16 * s0), st)
         if down == 1:
             hip.check(hip.lib().refvsr_score_frames(pa, afmt, pg, gfmt, lay, n, h, w, *tail), 'score_frames')
         else:
             hip.check(hip.lib().refvsr_score_frames_down(pa, afmt, pg, gfmt, lay, n, h, w, int(down), *tail), 'score_frames_down')
-    _score_launches(outs, gts, launch)
     return scores
 
 
-_REGION_WS = {}       # (device, stream handle, h, w) -> workspace of one full refvsr_score_regions launch
+_REGION_WS = _Cache()  # (device, stream handle, h, w) -> workspace of one full refvsr_score_regions launch
 
 
 def score_regions(outs, gts, rects):
@@ -890,16 +936,13 @@ def score_regions(outs, gts, rects):
     crects = (C.c_int * max(4 * nr, 1))(*[v for r in rects for v in r])
     st = _stream()
     dev = outs[0].device
-    ws = _score_workspace(_REGION_WS, dev, st, h, w,
-                          lambda: hip.lib().refvsr_score_regions_workspace_bytes(hip.SCORE_MAX_FRAMES, h, w, hip.SCORE_MAX_RECTS), 'score_regions')
+    ws = _workspace(_REGION_WS, dev, st, h, w, lambda: hip.lib().refvsr_score_regions_workspace_bytes(hip.SCORE_MAX_FRAMES, h, w, hip.SCORE_MAX_RECTS),
+                    'score_regions', _TOO_SMALL)
     sums = torch.empty((len(outs), nr, 2), dtype=torch.float64, device=dev)
-    _score_launches(outs, gts, lambda pa, pg, n, s0: hip.check(
-        hip.lib().refvsr_score_regions(pa, afmt, pg, gfmt, lay, n, h, w, crects, nr, _ptr(ws), ws.numel() * 8,
-                                       C.c_void_p(sums.data_ptr() + 16 * nr * s0), st), 'score_regions'))
+    for s0, n in _chunks(len(outs), hip.SCORE_MAX_FRAMES):
+        hip.check(hip.lib().refvsr_score_regions(_parr(outs[s0:s0 + n]), afmt, _parr(gts[s0:s0 + n]), gfmt, lay, n, h, w, crects, nr, _ptr(ws), ws.numel() * 8,
+                                                 C.c_void_p(sums.data_ptr() + 16 * nr * s0), st), 'score_regions')
     return sums
-
-
-_irange = range       # (result_to_yuv420 has an argument of that name)
 
 
 def result_to_yuv420(frames, fmt='nv12', matrix='bt709', range='limited'):
@@ -924,51 +967,32 @@ def result_to_yuv(frames, fmt='i422', matrix='bt709', range='limited', siting='c
         ps, sfmt, pd, n, h, w, yuv.FORMAT_IDS[yuv.twin_of(fmt)], samp, sit, coef, st))
 
 
-def _result_to_yuv(name, frames, fmt, matrix, range, launch):
+def _result_to_yuv(name, frames, fmt, matrix, range_, launch):
     """The body of result_to_yuv420 / result_to_yuv: the frames checked, the output [B] + yuv.frame_shape(h, w, fmt) allocated, one
     launch(src table, src format, dst table, n, h, w, coef9, stream) per REFVSR_YUV420_MAX_FRAMES frames."""
-    coef = (C.c_double * 9)(*yuv.coefficients(fmt, matrix, range))
-    frames = list(frames)
-    if not frames:
-        raise RuntimeError('%s: at least one frame' % name)
-    f0 = frames[0]
-    fmts = {torch.float32: hip.RESULT_F32, torch.float16: hip.RESULT_F16, torch.uint8: hip.RESULT_U8}
-    if not (f0.is_cuda and f0.dtype in fmts and f0.dim() == 3 and f0.shape[0] == 3):
-        raise RuntimeError('%s: cuda float32 | float16 | uint8 results [3,h,w] (got %s %s %s)' % (name, f0.device.type, f0.dtype, tuple(f0.shape)))
-    _, h, w = f0.shape
+    coef = (C.c_double * 9)(*yuv.coefficients(fmt, matrix, range_))
+    frames, h, w = _result_frames(name, frames, 'results')
     if h % 2 or w % 2:
         raise RuntimeError('%s: %s needs even h and w (got %d x %d)' % (name, '4:2:0' if fmt in yuv.FORMATS else fmt, h, w))
-    lay = result_layout_of(f0)
-    for f in frames:
-        if f.shape != f0.shape or f.dtype != f0.dtype or not f.is_cuda:
-            raise RuntimeError('%s: frames must all be %s [3, %d, %d] (got %s %s)' % (name, f0.dtype, h, w, f.dtype, tuple(f.shape)))
-        if lay is None or result_layout_of(f) != lay:
-            raise RuntimeError('%s: results must be dense and of one layout, contiguous [3, h, w] or the channels-last view of '
-                               '[h, w, 3] (config.result_layout), got strides %s' % (name, tuple(f.stride())))
-    sfmt = fmts[f0.dtype] | (hip.RESULT_HWC if lay == 'hwc' else 0)
-    out = torch.empty((len(frames),) + yuv.frame_shape(h, w, fmt), dtype=torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16, device=f0.device)
+    sfmt = _result_format(name, frames, 'results')
+    out = torch.empty((len(frames),) + yuv.frame_shape(h, w, fmt), dtype=torch.uint8 if yuv.depth_of(fmt) == 8 else torch.uint16, device=frames[0].device)
     st = _stream()
-    for s0 in _irange(0, len(frames), hip.YUV420_MAX_FRAMES):
-        chunk = frames[s0:s0 + hip.YUV420_MAX_FRAMES]
-        hip.check(launch(_parr(chunk), sfmt, _parr([out[s0 + i] for i in _irange(len(chunk))]), len(chunk), h, w, coef, st), name)
+    for s0, n in _chunks(len(frames), hip.YUV420_MAX_FRAMES):
+        hip.check(launch(_parr(frames[s0:s0 + n]), sfmt, _parr([out[s0 + i] for i in range(n)]), n, h, w, coef, st), name)
     return out
 
 
-_RESIZE_TAPS = {}     # (device, h, w, oh, ow) -> the device tap tables of one geometry (resize.aa_taps of both axes) and their widths
+_RESIZE_TAPS = _Cache()  # (device, h, w, oh, ow) -> the device tap tables of one geometry (resize.aa_taps of both axes) and their widths
 
 
 def _resize_taps(dev, h, w, oh, ow):
     """The cached device tables of resize_aa for one geometry: (lo_x, cnt_x, wx, lo_y, cnt_y, wy, maxcnt_x, maxcnt_y); built on the
     host by resize.aa_taps and uploaded once (the first call of a geometry copies; later calls launch only)."""
     from . import resize
-    key = (dev, h, w, oh, ow)
-    taps = _RESIZE_TAPS.get(key)
-    if taps is None:
-        if len(_RESIZE_TAPS) > 16:
-            _RESIZE_TAPS.clear()
+    def build():
         (lx, cx, wx), (ly, cy, wy) = resize.aa_taps(w, ow), resize.aa_taps(h, oh)
-        taps = _RESIZE_TAPS[key] = tuple(torch.from_numpy(np.ascontiguousarray(a_)).to(dev) for a_ in (lx, cx, wx, ly, cy, wy)) + (wx.shape[1], wy.shape[1])
-    return taps
+        return tuple(torch.from_numpy(np.ascontiguousarray(a_)).to(dev) for a_ in (lx, cx, wx, ly, cy, wy)) + (wx.shape[1], wy.shape[1])
+    return _RESIZE_TAPS.get_or_build((dev, h, w, oh, ow), build)
 
 
 def resize_aa(frames, oh, ow, out='float32', clamp=True):
@@ -982,35 +1006,21 @@ def resize_aa(frames, oh, ow, out='float32', clamp=True):
     from . import resize
     if out not in ('float32', 'uint8'):
         raise RuntimeError("resize_aa: out must be 'float32' or 'uint8' (got %r)" % (out,))
-    frames = list(frames)
-    if not frames:
-        raise RuntimeError('resize_aa: at least one frame')
-    f0 = frames[0]
-    fmts = {torch.float32: hip.RESULT_F32, torch.float16: hip.RESULT_F16, torch.uint8: hip.RESULT_U8}
-    if not (f0.is_cuda and f0.dtype in fmts and f0.dim() == 3 and f0.shape[0] == 3):
-        raise RuntimeError('resize_aa: cuda float32 | float16 | uint8 frames [3,h,w] (got %s %s %s)' % (f0.device.type, f0.dtype, tuple(f0.shape)))
-    _, h, w = f0.shape
+    frames, h, w = _result_frames('resize_aa', frames, 'frames')
     try:
         resize.check_sizes(h, oh, 'resize_aa')
         resize.check_sizes(w, ow, 'resize_aa')
         oh, ow = int(oh), int(ow)
     except (TypeError, ValueError) as e:
         raise RuntimeError(str(e) if isinstance(e, ValueError) else 'resize_aa: oh, ow must be integers (got %r, %r)' % (oh, ow))
-    lay = result_layout_of(f0)
-    for f in frames:
-        if f.shape != f0.shape or f.dtype != f0.dtype or not f.is_cuda:
-            raise RuntimeError('resize_aa: frames must all be %s [3, %d, %d] (got %s %s)' % (f0.dtype, h, w, f.dtype, tuple(f.shape)))
-        if lay is None or result_layout_of(f) != lay:
-            raise RuntimeError('resize_aa: frames must be dense and of one layout, contiguous [3, h, w] or the channels-last view of '
-                               '[h, w, 3] (config.result_layout), got strides %s' % (tuple(f.stride()),))
-    sfmt = fmts[f0.dtype] | (hip.RESULT_HWC if lay == 'hwc' else 0)
-    lx, cx, wx, ly, cy, wy, mx, my = _resize_taps(f0.device, h, w, oh, ow)
-    res = torch.empty((len(frames), 3, oh, ow), dtype=torch.float32 if out == 'float32' else torch.uint8, device=f0.device)
+    sfmt = _result_format('resize_aa', frames, 'frames')
+    dev = frames[0].device
+    lx, cx, wx, ly, cy, wy, mx, my = _resize_taps(dev, h, w, oh, ow)
+    res = torch.empty((len(frames), 3, oh, ow), dtype=torch.float32 if out == 'float32' else torch.uint8, device=dev)
     dfmt = hip.RESULT_F32 if out == 'float32' else hip.RESULT_U8
     st = _stream()
-    for s0 in _irange(0, len(frames), hip.RESIZE_MAX_FRAMES):
-        chunk = frames[s0:s0 + hip.RESIZE_MAX_FRAMES]
-        hip.check(hip.lib().refvsr_resize_aa(_parr(chunk), sfmt, _parr([res[s0 + i] for i in _irange(len(chunk))]), dfmt, len(chunk), h, w, oh, ow,
+    for s0, n in _chunks(len(frames), hip.RESIZE_MAX_FRAMES):
+        hip.check(hip.lib().refvsr_resize_aa(_parr(frames[s0:s0 + n]), sfmt, _parr([res[s0 + i] for i in range(n)]), dfmt, n, h, w, oh, ow,
                                              _ptr(lx), _ptr(cx), _ptr(wx), _ptr(ly), _ptr(cy), _ptr(wy), mx, my, 1 if clamp else 0, st), 'resize_aa')
     return res
 
@@ -1100,22 +1110,17 @@ def _yuv_to_frames(name, x, h, w, fmt, ingest):
     return _frames_of(x, 2, torch.Tensor.is_contiguous, dt.itemsize, h, w, ingest)
 
 
-_JPEG_TABLES = {}     # (device, quality, fmt) -> the device tables of refvsr_jpeg_encode: (qtables, dct, huffman LUT)
+_JPEG_TABLES = _Cache()  # (device, quality, fmt) -> the device tables of refvsr_jpeg_encode: (qtables, dct, huffman LUT)
 
 
 def _jpeg_tables(dev, quality, fmt):
     """The cached device tables of jpeg_encode for one (quality, fmt): the float64 quantisation tables [2, 64], the DCT matrix
     jpeg.dct_table() and jpeg.huffman_lut(), made on the host and uploaded once."""
     from . import jpeg
-    key = (dev, quality, fmt)
-    tabs = _JPEG_TABLES.get(key)
-    if tabs is None:
-        if len(_JPEG_TABLES) > 16:
-            _JPEG_TABLES.clear()
+    def build():
         q = np.stack(jpeg.quant_tables(quality)).astype(np.float64)
-        tabs = _JPEG_TABLES[key] = tuple(torch.from_numpy(np.ascontiguousarray(a_)).to(dev)
-                                          for a_ in (q, jpeg.dct_table(), jpeg.huffman_lut().view(np.int32)))
-    return tabs
+        return tuple(torch.from_numpy(np.ascontiguousarray(a_)).to(dev) for a_ in (q, jpeg.dct_table(), jpeg.huffman_lut().view(np.int32)))
+    return _JPEG_TABLES.get_or_build((dev, quality, fmt), build)
 
 
 def _jpeg_frames(name, yuv_frames, h, w, fmt, quality, restart):
@@ -1169,15 +1174,14 @@ def jpeg_encode_device(yuv_frames, h, w, fmt, quality=90, restart=None):
     dst = torch.empty(n * bound, dtype=torch.uint8, device=dev)
     meta = torch.empty((2, n), dtype=torch.int64, device=dev)
     st = _stream()
-    for s0 in _irange(0, n, hip.JPEG_MAX_FRAMES):
-        chunk = frames[s0:s0 + hip.JPEG_MAX_FRAMES]
-        wsb = lib.refvsr_jpeg_workspace_bytes(len(chunk), h, w, samp, restart)
+    for s0, k in _chunks(n, hip.JPEG_MAX_FRAMES):
+        wsb = lib.refvsr_jpeg_workspace_bytes(k, h, w, samp, restart)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        hip.check(lib.refvsr_jpeg_encode(_parr(chunk), len(chunk), h, w, samp, _ptr(qt), _ptr(dct), _ptr(lut), restart,
-                                         C.c_void_p(dst.data_ptr() + s0 * bound), len(chunk) * bound, C.c_void_p(meta.data_ptr() + 8 * (n + s0)),
+        hip.check(lib.refvsr_jpeg_encode(_parr(frames[s0:s0 + k]), k, h, w, samp, _ptr(qt), _ptr(dct), _ptr(lut), restart,
+                                         C.c_void_p(dst.data_ptr() + s0 * bound), k * bound, C.c_void_p(meta.data_ptr() + 8 * (n + s0)),
                                          C.c_void_p(meta.data_ptr() + 8 * s0), _ptr(ws), wsb, st), 'jpeg_encode')
         if s0:
-            meta[0, s0:s0 + len(chunk)] += s0 * bound                   # (a set's offsets count from its own first slot)
+            meta[0, s0:s0 + k] += s0 * bound                            # (a set's offsets count from its own first slot)
     return dst, meta[0], meta[1]
 
 
@@ -1191,14 +1195,14 @@ def jpeg_encode(yuv_frames, h, w, fmt, quality=90, restart=None):
     off, size = offsets.cpu().tolist(), sizes.cpu().tolist()
     head = jpeg.header(h, w, fmt, quality, restart)
     out = []
-    for s0 in _irange(0, len(frames), hip.JPEG_MAX_FRAMES):             # a launch set's frames lie back to back: one copy per set
+    for s0 in range(0, len(frames), hip.JPEG_MAX_FRAMES):               # a launch set's frames lie back to back: one copy per set
         s1 = min(s0 + hip.JPEG_MAX_FRAMES, len(frames))
         data = dst[off[s0]:off[s1 - 1] + size[s1 - 1]].cpu().numpy().tobytes()
-        out.extend(jpeg.assemble(head, data[off[i] - off[s0]:off[i] - off[s0] + size[i]]) for i in _irange(s0, s1))
+        out.extend(jpeg.assemble(head, data[off[i] - off[s0]:off[i] - off[s0] + size[i]]) for i in range(s0, s1))
     return out
 
 
-_SAD_WS = {}          # (device, stream handle, h, w) -> workspace of one full refvsr_luma_sad call
+_SAD_WS = _Cache()    # (device, stream handle, h, w) -> workspace of one full refvsr_luma_sad call
 
 
 def luma_sad(frames_a, frames_b, h, w, fmt):
@@ -1220,17 +1224,16 @@ def luma_sad(frames_a, frames_b, h, w, fmt):
             raise RuntimeError('luma_sad: dense cuda %s frames [%d, %d] of one GPU (got %s %s %s)'
                                % (fmt, shape[0], w, f.device.type, f.dtype, tuple(f.shape)))
     st = _stream()
-    ws = _score_workspace(_SAD_WS, dev, st, h, w, lambda: hip.lib().refvsr_luma_sad_workspace_bytes(hip.SCENE_MAX_PAIRS, h, w), 'luma_sad', 4,
-                          'frames must hold at most 2^29 pixels')
+    ws = _workspace(_SAD_WS, dev, st, h, w, lambda: hip.lib().refvsr_luma_sad_workspace_bytes(hip.SCENE_MAX_PAIRS, h, w), 'luma_sad',
+                    'frames must hold at most 2^29 pixels', 4)
     sad = torch.empty(len(fa), dtype=torch.int64, device=dev)
-    for s0 in _irange(0, len(fa), hip.SCENE_MAX_PAIRS):
-        n = min(hip.SCENE_MAX_PAIRS, len(fa) - s0)
+    for s0, n in _chunks(len(fa), hip.SCENE_MAX_PAIRS):
         hip.check(hip.lib().refvsr_luma_sad(_parr(fa[s0:s0 + n]), _parr(fb[s0:s0 + n]), n, h, w, yuv.FORMAT_IDS[yuv.twin_of(fmt)], _ptr(ws), ws.numel() * 4,
                                             C.c_void_p(sad.data_ptr() + 8 * s0), st), 'luma_sad')
     return sad
 
 
-_COLORMAP_WS = {}     # (device, stream handle, h, w) -> workspace of one full refvsr_conf_colormap launch
+_COLORMAP_WS = _Cache()  # (device, stream handle, h, w) -> workspace of one full refvsr_conf_colormap launch
 
 
 def colormap_table():
@@ -1257,11 +1260,10 @@ def conf_colormap(maps):
             raise RuntimeError('conf_colormap: maps must be single [.., %d, %d] maps of one geometry (got %s)' % (h, w, tuple(m.shape)))
     st = _stream()
     dev = maps[0].device
-    ws = _score_workspace(_COLORMAP_WS, dev, st, h, w, lambda: hip.lib().refvsr_conf_colormap_workspace_bytes(hip.COLORMAP_MAX_MAPS, h, w),
-                          'conf_colormap', 4, 'maps must hold 1 .. 2^31 - 1 samples')
+    ws = _workspace(_COLORMAP_WS, dev, st, h, w, lambda: hip.lib().refvsr_conf_colormap_workspace_bytes(hip.COLORMAP_MAX_MAPS, h, w),
+                    'conf_colormap', 'maps must hold 1 .. 2^31 - 1 samples', 4)
     outs = [torch.empty((h, w, 3), dtype=torch.uint8, device=dev) for _ in maps]
-    for s0 in range(0, len(maps), hip.COLORMAP_MAX_MAPS):
-        n = min(hip.COLORMAP_MAX_MAPS, len(maps) - s0)
+    for s0, n in _chunks(len(maps), hip.COLORMAP_MAX_MAPS):
         pm, po = _parr(maps[s0:s0 + n]), _parr(outs[s0:s0 + n])
         hip.check(hip.lib().refvsr_conf_colormap(pm, n, h, w, po, _ptr(ws), ws.numel() * 4, st), 'conf_colormap')
     return outs
@@ -1287,16 +1289,11 @@ class FingerprintTable(object):
         self.nchunks = len(ent)
         self.device = dev
         self.chunks = torch.from_numpy(ent.view(np.int64).reshape(-1, 2).copy()).to(dev)
-        self._ws = {}
+        self._ws = _Cache()
 
     def workspace(self, st):
-        ws = self._ws.get(st.value)
-        if ws is None:
-            if len(self._ws) > 16:
-                self._ws.clear()
-            ws = self._ws[st.value] = torch.empty(hip.lib().refvsr_param_fingerprint_workspace_bytes(self.nchunks) // 8 + 1, dtype=torch.int64,
-                                                  device=self.device)
-        return ws
+        return self._ws.get_or_build(st.value, lambda: torch.empty(hip.lib().refvsr_param_fingerprint_workspace_bytes(self.nchunks) // 8 + 1,
+                                                                   dtype=torch.int64, device=self.device))
 
 
 def param_fingerprint(tensors, out=None):
