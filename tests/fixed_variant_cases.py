@@ -14,6 +14,11 @@ is at least twice that bound plus one: every workgroup walks at least two tiles 
 the K loop, its barrier, and in the multi-map rows the step from one map to the next inside a workgroup.  Rows marked `tiny` run a
 third time at 7 x 5, below one tile: one row of every family that had no float64 comparison before.
 
+The four head rows (refvsr_conv_last at C = 24 | 48, the two HEAD rows of resblock24_kernel) run their small, walk and tiny shapes with
+a ZERO base frame of the output's own size (base_step = 1) and, besides, BASED runs with an exact non-zero base at x4 and at x2
+(exact_cases.head_base; `small_x4`, `walk_x2`, ...): shapes that are multiples of the factor and still leave partial tiles on both axes --
+small 20 x 44 | 36 x 76, walk h = TH a + 4, w = 32 b + 12 under the same tile-count rule, tiny 4 x 4 (x4: a 1 x 1 base) | 6 x 8 (x2).
+
 Multi-map rows carry B = 3 maps with separately built data (weights shared, as in the launch); every map has its own case and its own
 reference.  Cases come from exact_cases' builders; a case that is not strong at its first seed moves to the next one (the choice is
 made on the reference alone).  up = 2 rows have two cases per run, K and S (exact_cases._conf_case).
@@ -193,15 +198,15 @@ def n_tiles(row, hw):
     return -(-h // th) * -(-w // 32) * maps(row)
 
 
-def walk_shape(row):
-    """The smallest h = TH a + 3, w = 32 b + 13 (a, b >= 1; by the longer side in tiles, then by area: as many tile rows as tile
+def walk_shape(row, dh=3, dw=13):
+    """The smallest h = TH a + dh, w = 32 b + dw (3 and 13; the based runs of the heads: 4 and 12, multiples of both factors) (a, b >= 1; by the longer side in tiles, then by area: as many tile rows as tile
     columns, or one fewer) with n_tiles >= 2 walk_bound + 1.  up = 2: the
     conv's grid is twice the confidence maps, so the MAPS are (TH a + 6) / 2 x (32 b + 14) / 2: partial tiles again."""
     th, need, best = tile_h(row), 2 * walk_bound(row) + 1, None
     for a in range(1, 200):
         for b in range(1, 200):
             if (a + 1) * (b + 1) * maps(row) >= need:
-                hw = (th * a + 3, 32 * b + 13) if row.up == 1 else ((th * a + 6) // 2, (32 * b + 14) // 2)
+                hw = (th * a + dh, 32 * b + dw) if row.up == 1 else ((th * a + 6) // 2, (32 * b + 14) // 2)
                 if best is None or (max(a, b), hw[0] * hw[1]) < best[0]:
                     best = ((max(a, b), hw[0] * hw[1]), hw)
                 break
@@ -214,14 +219,39 @@ def small_shape(row):
 
 
 RUNS = ('small', 'walk', 'tiny')
+FACTORS = (4, 2)
+BASED_RUNS = tuple('%s_x%d' % (run, s) for run in RUNS for s in FACTORS)
+BASED_SMALL8, BASED_SMALL16 = (20, 44), (36, 76)
+BASED_TINY = {4: (4, 4), 2: (6, 8)}
+BASE_VALUES = {4: 'u', 2: 's'}              # exact_cases.BASE_SETS of the based runs
+
+
+def is_head(row):
+    return row.entry in ('conv_last', 'hr_last')
 
 
 def runs_of(row):
-    return RUNS if row.tiny else RUNS[:2]
+    """The zero-base runs of every row, then the based runs of the head rows."""
+    runs = RUNS if row.tiny else RUNS[:2]
+    return runs + tuple('%s_x%d' % (run, s) for run in runs for s in FACTORS) if is_head(row) else runs
+
+
+def kind(run):
+    """'small' | 'walk' | 'tiny' of a run, based or not."""
+    return run.split('_x')[0]
+
+
+def factor(run):
+    """The base's factor of a based run, None for a zero-base run."""
+    return int(run.split('_x')[1]) if '_x' in run else None
 
 
 def shape(row, run):
-    return {'small': small_shape, 'walk': walk_shape, 'tiny': lambda r: TINY}[run](row)
+    if factor(run) is None:
+        return {'small': small_shape, 'walk': walk_shape, 'tiny': lambda r: TINY}[run](row)
+    if kind(run) == 'small':
+        return BASED_SMALL16 if tile_h(row) == 16 else BASED_SMALL8
+    return walk_shape(row, 4, 12) if kind(run) == 'walk' else BASED_TINY[factor(run)]
 
 
 # ---- the cases ------------------------------------------------------------------------------------------------------------------------
@@ -233,7 +263,7 @@ def row_name(i, row):
     return 'variant %02d %s %s %s' % (i, row.kernel, v, row.entry) + (' up2' if row.up == 2 else '') + (' f16w' if row.wf else '') + (' B%d' % row.batch if row.batch else '')
 
 
-def _build(i, row, hw, seed, form, name):
+def _build(i, row, hw, seed, form, name, base=None):
     wfmt, primary = ('fp16', 'hi') if row.wf else ('hi_lo', 'f64')
     if row.entry in ('conv24', 'conv32', 'conv48', 'shuffle2'):
         c = None
@@ -246,9 +276,9 @@ def _build(i, row, hw, seed, form, name):
     if row.entry == 'conf_alpha':
         return ec._conf_case(name, seed, row.cout, hw, want_max=row.up == 1, wfmt=wfmt, up=row.up, staging=form == 'S')
     if row.entry == 'conv_last':
-        return ec._last_case(name, seed, row.cins[0], hw)
+        return ec._last_case(name, seed, row.cins[0], hw, base=base)
     if row.entry == 'hr_last':
-        return ec._hr_case(name, seed, hw, 'AB'[i % 2], 0.25)
+        return ec._hr_case(name, seed, hw, 'AB'[i % 2], 0.25, base=base, b_count=6 if base and hw == BASED_TINY[4] and i % 2 == 0 else ec.CTL_B_COUNT)
     return ec._blocks_case(name, seed, 'rb24', 24, hw, (ec.CASE_A, ec.CASE_B)[i % 2], slope(row), wfmt=wfmt)
 
 
@@ -270,12 +300,13 @@ def build_cases(i, run, form=None):
     strong, then per further map the first seed at which the map -- its own data, map 0's weights -- is strong."""
     row = ROWS[i]
     hw = shape(row, run)
-    base = 9000 + 64 * i + 16 * RUNS.index(run) + (8 if form == 'S' else 0)
+    base = 9000 + 64 * i + 16 * RUNS.index(kind(run)) + (8 if form == 'S' else 0) + (100000 * factor(run) if factor(run) else 0)
+    based = (factor(run), BASE_VALUES[factor(run)]) if factor(run) else None
     name = '%s %s%s %dx%d' % (row_name(i, row), run, ' ' + form if form else '', hw[0], hw[1])
     cases = []
     for b in range(maps(row)):
         for k in range(24):
-            c = _build(i, row, hw, base + b + 7919 * k, form, name + (' map %d' % b if row.batch else ''))
+            c = _build(i, row, hw, base + b + 7919 * k, form, name + (' map %d' % b if row.batch else ''), based)
             if b:
                 c.p.update((key_, cases[0].p[key_]) for key_ in WEIGHTS if key_ in c.p)
                 for key_ in ('full', 'hi', 'controls'):     # (the builder looked at the bound of its own weights)

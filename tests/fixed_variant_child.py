@@ -70,7 +70,7 @@ def runs_of(knob):
 def walk_stream(run):
     """The stream of a run: the current one, or for a walk run a side stream whose CU budget is 8 while the run lasts."""
     from refvsr_amd import hip, ops
-    if run != 'walk':
+    if fv.kind(run) != 'walk':
         yield ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         return
@@ -190,12 +190,16 @@ def _conf(row, cases, dev, pz):
 
 
 def _head(row, cases, dev, formats, pz):
-    """refvsr_conv_last | refvsr_conv_hr_last with a zero base frame (its bicubic sample is exactly 0), in every result format asked"""
+    """refvsr_conv_last | refvsr_conv_hr_last in every result format asked, with the base frame of the case: the exact non-zero map of a
+    based run ([3, h / s, w / s]: base_step = 1 / s), or a zero frame of the output's own size (its bicubic sample is exactly 0).  The
+    fenced twin puts the base between NaN fences like every other input; what detects a read past it is the bit equality with the
+    reference (a NaN that reaches the head's clamps comes out as 0, which footprint.no_nan cannot see)."""
     from refvsr_amd import ops
     from refvsr_amd.packing import pack_conv_hr_last, pack_conv_last
     p = cases[0].p
     x = nhwc16(p['x'], dev, pz)
-    ins = {'x': x, 'base': f32(torch.zeros(3, x.shape[0], x.shape[1]), dev, pz)}
+    base = p['base'] if p.get('base') is not None else torch.zeros(3, x.shape[0], x.shape[1])
+    ins = {'x': x, 'base': f32(base, dev, pz)}
     if row.entry == 'conv_last':
         ins['blob'] = pack_conv_last(f32(p['w']), f32(p['b'])).to(dev)
         ins['blob'] = fp.fence_weights(ins['blob']) if pz else ins['blob']
@@ -234,6 +238,14 @@ def _blocks(row, cases, dev, pz):
 FORMATS = (('out', None), ('f16', 'float16'), ('u8', 'uint8'))
 
 
+def formats_of(run):
+    """The result formats a head row is asked for: all three at the small shapes; fp32 alone at the zero-base walk and tiny shapes,
+    fp32 and uint8 at the based ones."""
+    if fv.kind(run) == 'small':
+        return FORMATS
+    return FORMATS[:1] if fv.factor(run) is None else (FORMATS[0], FORMATS[2])
+
+
 def run_row(i, run, form, dev):
     """One run of row i and its fenced twin -> {'key', 'n_tiles', 'lds', 'same', 'tail' (probe rows), '<map>.<output>': raw result on
     the cpu, 'fence': '' or what the fenced run found, 'equal': the fenced run's raw result tensors equal the plain run's}."""
@@ -265,7 +277,7 @@ def _run_row(i, run, form, dev, fenced):
     for k in SETTER_ENV:
         assert not os.environ.get(k), 'the rows set the resblock24 setters themselves: %s must not be set' % k
     if row.entry in ('conv_last', 'hr_last'):
-        ins, launch = _head(row, cases, dev, FORMATS if run == 'small' else FORMATS[:1], pz)
+        ins, launch = _head(row, cases, dev, formats_of(run), pz)
     elif row.entry == 'conf_alpha':
         ins, launch = _conf(row, cases, dev, pz)
     elif row.entry == 'rb24':

@@ -24,6 +24,8 @@ fence_weights(obj)                 re-homes the device weights of an ops.ConvWei
 Limits of what this proves:
   * A load past a map whose value a select discards is invisible here, and harmless unless it crosses into unmapped memory.  This
     module does not try to show that: nothing in it places a buffer against an unmapped page or otherwise invites a fault.
+  * A NaN that reaches a `fminf` / `fmaxf` clamp is invisible to no_nan(): `fminf(fmaxf(NaN, 0), 1)` is 0.  The base frame of the output
+    heads is the case: a read past it is detected by the bit equality with a reference whose base is not zero, not by this module.
   * A stray write farther away than one fence width (at least the output's own size, at least 64 KiB) is not seen.  The suites'
     shapes (19 x 45 and 33 x 70 maps against 4-, 8- and 16-row tiles, the 2 x 2 to 34 x 70 matching and sampling shapes) make a
     mis-strided store overrun by at most a tile's rows of the same map, which is within the fence.

@@ -3,6 +3,10 @@
     would see a missing lo term: (a) all lo terms dropped >= 5 % of the outputs, (b) one K-block's lo term >= 1 % and >= 8 outputs;
   * a float32 evaluation -- F.conv2d with hi and with lo, added -- equals the float64 reference exactly (the empirical side of the
     exactness argument: float32 sums in MKL-DNN's order lose nothing either);
+  * for the head cases with a non-zero base frame: the base's bicubic sample is exact (float32 = float64, either summation order, on
+    the 2^-24 grid), every class of sample and output occurs, every border and corner has a live output behind index-clamped taps,
+    every deliberate defect of the base term changes the reference ("control X changes N outputs in case Y"), and the general
+    family (bytes / 255) keeps its derived bound and its 1 % cap on the reference's own float32 replay;
   * the packers accept the weights and their fragments decode back to w exactly (hi + lo == w element by element, every K-block
     present once, padding zero) -- a packer that drops or misplaces one lo fragment fails here before any GPU is involved."""
 import math
@@ -49,6 +53,92 @@ def test_float32_emulation_equals_reference(name):
     for k, v in c.want.items():
         assert p32[k].dtype in (torch.float32, torch.float64)
         assert torch.equal(p32[k].double(), v), '%s: float32 arithmetic is not exact on this case (%s)' % (name, k)
+
+
+# ---- the output head with a non-zero base frame --------------------------------------------------------------------------------------
+def _one_sample(c):
+    return c.p['base'].shape[1] * c.p['base'].shape[2] == 1
+
+
+@pytest.mark.parametrize('name', ec.BASED)
+def test_based_case_base_is_exact_and_every_class_is_filled(name):
+    """On the case's own data: the bicubic sample is the same number in float32 and float64, rows first and columns first, and lies
+    on the 2^-24 grid (base_proof); samples below 0, above 1 and inside, outputs at 0, at 1 and inside, and outputs inside (0, 1)
+    whose sample was clamped all occur (a 1 x 1 map returns its one sample: no overshoot there); v + b is exact in float64."""
+    c = get_case(name)
+    p = c.p
+    assert p['base'].shape == (3, p['x'].shape[1] // p['s'], p['x'].shape[2] // p['s']) and p['s'] in (2, 4)
+    assert all(float(v) in ec.BASE_SETS['u'] for v in p['base'].unique()) or all(float(v) in ec.BASE_SETS['s'] for v in p['base'].unique())
+    assert not torch.equal(p['base'][0], p['base'][1]) and not torch.equal(p['base'][1], p['base'][2]) and not torch.equal(p['base'][0], p['base'][2])
+    cl = ec.head_classes(c)
+    print('%-40s samples <=0 / >=1 / inside %s  outputs 0 / 1 / inside %s  inside with a clamped sample %d' % (
+        name, cl['samples'], cl['outputs'], cl['inside_clamped']))
+    least = 1 if _one_sample(c) else 4
+    assert min(cl['samples']) >= least and min(cl['outputs']) >= least, cl
+    assert _one_sample(c) or cl['inside_clamped'] >= least, cl
+    pre = c.evaluate('f64')[0]['out']
+    assert torch.equal(pre.float().double(), pre) and torch.equal(c.evaluate('f32')[0]['out'].double(), pre)
+    raw = ec.base_proof(p)
+    assert float(raw.abs().max()) < 4.0 and c.bound < ec.LIMIT       # |v| < 2^24 g_v, |b| < 4 on the 2^-24 grid: v + b fits float64
+
+
+@pytest.mark.parametrize('name', ec.BASED)
+def test_based_case_borders_have_live_outputs(name):
+    """On each of the four borders and four corners at least one output whose taps were index-clamped has a reference value strictly
+    inside (0, 1): a wrong value read there changes it, and so does a fence's NaN that the clamps turn into 0."""
+    c = get_case(name)
+    n = ec.head_borders(c)
+    print('%-40s %s' % (name, '  '.join('%s %d' % (k, n[k]) for k in ec.BORDERS)))
+    assert set(n) == set(ec.BORDERS) and min(n.values()) >= 1, n
+
+
+@pytest.mark.parametrize('name', ec.BASED)
+def test_based_case_controls_change_the_reference(name):
+    """Every deliberate defect of the base term (exact_cases.head_base), applied to the REFERENCE: a map with more than one sample
+    must change under each of them, the 1 x 1 map (every tap on the one sample, weights summing to 1) under the wrong plane."""
+    c = get_case(name)
+    for ctl in ec.BASE_CONTROLS:
+        n = ec.base_control(c, ctl)
+        print('control %-8s changes %4d of %4d outputs in case %s' % (ctl, n, c.want['out'].numel(), name))
+        if ctl == 'plane' or not _one_sample(c):
+            assert n >= 1, (name, ctl)
+        else:
+            assert n == 0, (name, ctl)
+
+
+def test_based_table_covers_the_shapes_and_the_proof_has_teeth():
+    assert len(ec.BASED) == 20 and all(n in ec.NAMES for n in ec.BASED)
+    assert sorted(set((c.p['s'],) + tuple(c.p['base'].shape[1:]) for c in map(get_case, ec.BASED))) == [(2, 7, 3), (2, 9, 23), (4, 1, 1), (4, 2, 8), (4, 5, 11)]
+    p = dict(s=4, base=ec.base_map(ec.rng(3), (5, 11), (0.0, 0.25, 0.5, 0.75, 1.0)))
+    with pytest.raises(AssertionError):
+        ec.base_proof(p)                                                        # five levels: the fp32 bicubic at a step of 1/4 rounds
+    zero = get_case('conv_last C24 19x45')
+    assert 'base' not in zero.p and float(zero.p['b'][0]) == 0.5                # the zero-base cases keep their data
+
+
+@pytest.mark.parametrize('name', ec.GENERAL_NAMES)
+def test_general_family_bound_and_cap(name):
+    """Base = bytes / 255: the reference's own float32 replay (either summation order) stays within GENERAL_BOUND of the float64
+    reference, its stored formats inside the allowed intervals, and the elements at which a stored format leaves a choice stay
+    under the 1 % cap."""
+    g = ec.get_general(name)
+    b = g.p['base']
+    assert torch.equal((b.float() * 255.0).round() / 255.0, b.float()) and b.unique().numel() > 100
+    for tr in (False, True):
+        r = g.replay32(tr)
+        err = float((r - g.want).abs().max())
+        print('%-48s float32 replay (%s first): max error %.3f x 2^-24, bound %.1f x 2^-24' % (name, 'columns' if tr else 'rows', err * 2.0 ** 24, ec.GENERAL_BOUND * 2.0 ** 24))
+        assert err <= ec.GENERAL_BOUND
+        for fmt in ('float32', 'float16', 'uint8'):
+            lo, hi = g.allowed(fmt)
+            s = g.store(r, fmt)
+            assert bool(((s >= lo) & (s <= hi)).all()), fmt
+    for fmt in ('float16', 'uint8'):
+        lo, hi = g.allowed(fmt)
+        step = float((hi - lo).max())
+        print('%-48s %s: %.4f of the elements leave a choice' % (name, fmt, g.loose(fmt)))
+        assert g.loose(fmt) <= ec.GENERAL_CAP and (fmt != 'uint8' or step <= 1.0)
+    assert min(ec._count3(g.want)) >= 4
 
 
 def _rounded(c):

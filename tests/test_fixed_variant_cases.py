@@ -151,6 +151,23 @@ def test_shapes_of_the_runs():
         assert n >= 2 * bound + 1, 'row %d: %d tiles on at most %d workgroups' % (i, n, bound)
         assert (h * r.up) % th and (w * r.up) % 32 and h * r.up <= 120 and w * r.up <= 480
     assert fv.walk_shape(fv.ROWS[40]) == (75, 301)                       # the 24-channel head: 97 tiles needed, 10 x 10
+    # the based runs of the four head rows: multiples of both factors, partial tiles on both axes, the zero-base runs' tile counts
+    heads = [r for r in fv.ROWS if fv.is_head(r)]
+    assert [fv.ROWS.index(r) for r in heads] == [40, 41, 64, 65] and fv.BASED_RUNS == ('small_x4', 'small_x2', 'walk_x4', 'walk_x2', 'tiny_x4', 'tiny_x2')
+    for r in fv.ROWS:
+        based = [run for run in fv.runs_of(r) if fv.factor(run)]
+        assert based == ([k + '_x%d' % s for k in fv.runs_of(r) if not fv.factor(k) for s in (4, 2)] if fv.is_head(r) else [])
+        th = fv.tile_h(r)
+        for run in based:
+            h, w = fv.shape(r, run)
+            assert fv.factor(run) in (4, 2) and h % fv.factor(run) == 0 and w % fv.factor(run) == 0
+            if fv.kind(run) == 'tiny':
+                assert h < 8 and w < 32 and (h, w) == {4: (4, 4), 2: (6, 8)}[fv.factor(run)]
+                continue
+            assert h % 4 == 0 and w % 4 == 0 and h % th and w % 32 and h > th and w > 32, 'both factors divide, partial tiles on both axes'
+            zero = fv.shape(r, fv.kind(run))
+            assert fv.n_tiles(r, (h, w)) == fv.n_tiles(r, zero) and (h, w) == (zero[0] + 1, zero[1] - 1) if fv.kind(run) == 'walk' else (h, w) == ((36, 76) if th == 16 else (20, 44))
+    assert fv.shape(fv.ROWS[40], 'walk_x4') == (76, 300) and max(fv.shape(r, run)[0] * fv.shape(r, run)[1] for r in heads for run in fv.runs_of(r)) == 76 * 300
     # Multi-map rows: rank r of g workgroups walks tiles [r n / g, (r + 1) n / g) (rv_tile_range), map b starts at tile b n / 3: with
     # a grid that 3 divides the two coincide, otherwise one workgroup walks from one map into the next.  The grid is the cap when
     # the LDS bound is the occupancy; for every entry point at least one row has a bound that 3 does not divide
@@ -189,7 +206,15 @@ def test_cases_are_exact_and_strong(i):
                         if k in c.p:
                             assert c.p[k] is cases[0].p[k], 'the maps of a launch share the weights'
                     assert not torch.equal(c.want['out'], cases[0].want['out'])
-                if run == 'small' and c.primary != 'hi':
+                if fv.factor(run):
+                    assert c.p['s'] == fv.factor(run) and tuple(c.p['base'].shape) == (3, hw[0] // c.p['s'], hw[1] // c.p['s'])
+                    cl, one = ec.head_classes(c), c.p['base'].shape[1] * c.p['base'].shape[2] == 1     # (head_classes proves the base exact)
+                    assert min(cl['samples']) >= 1 and min(cl['outputs']) >= 1 and (one or cl['inside_clamped'] >= CLASS_MIN), cl
+                    assert min(ec.head_borders(c).values()) >= 1, 'a border without a live output'
+                    assert ec.base_control(c, 'plane') >= 1 and (one or all(ec.base_control(c, k) >= 1 for k in ('a', 'reflect', 'noclamp', 'step')))
+                else:
+                    assert 'base' not in c.p
+                if fv.kind(run) == 'small' and c.primary != 'hi':
                     assert (c.evaluate('f32')[0]['out'].double() == c.want['out']).all(), 'float32 arithmetic is not exact on this case'
                 if r.up == 2:
                     z, o, m = ec.conf_up2_classes(c.p)

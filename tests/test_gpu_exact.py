@@ -9,6 +9,11 @@ dropped) and the exactness bound in log2 granules.  Almost every lo value of the
 checkpoints (packing.py stores lo = fp16(w - hi) unscaled): the whole weight path depends on the MFMA taking fp16 subnormal
 operands unflushed, which the `subnormal` cases pin for the hi operand too.
 
+The output heads run with a zero base frame (the conv and the stores alone) and, in the `based` cases, with a non-zero base at x4
+and x2 whose bicubic sample is exact: those go through all three routes of engine.compute_up in every result format and layout,
+each launch twice (plain and fenced), and the `general` cases (base = bytes / 255) are held to a derived bound
+(profiles/gpu_head_base_report.txt).
+
 Multi-map, batched, workgroup-shape and store-mode variants are pinned bit-identical to the single launches by test_gpu_ops.py;
 each family is anchored here once.
 
@@ -153,18 +158,59 @@ def run_conf_alpha(c, dev, wfmt=None):
     return {'out': planar64(out, cw.cout)}
 
 
-def run_head(c, dev, result_dtype=None):
+ROUTES = ('conv_last', 'hr_last', 'fallback')
+FORMATS = (None, 'float16', 'uint8')
+
+
+def routes_of(c):
+    """The routes of engine.compute_up a head case can take: the fused tail only where the case has a conv_hr."""
+    return ROUTES if c.kind == 'hr_last' else (ROUTES[0], ROUTES[2])
+
+
+def run_head(c, dev, result_dtype=None, result_layout=None, route=None, fenced=False):
+    """One head case through one of the three routes by which engine.compute_up returns a frame:
+      'conv_last'  ops.conv_last (an hr_last case: behind ops.conv(conv_hr, act), engine.py:929)
+      'hr_last'    ops.conv_hr_last, the fused tail
+      'fallback'   ops.bicubic_scale + the planar ops.conv with res_planar and clamp + ops.convert_result (engine.py:934-935)
+    route None: the case's own entry point.  The base is the case's (a zero map of the output's size for the zero-base cases: its
+    bicubic sample is exactly 0).  fenced: every input (the base included) between the NaN fences of tests/footprint.py, every
+    allocation of ops between 0xA5 fences -> (result, footprint.judge's verdict without the comparison to a plain run)."""
+    import footprint as fp
     from refvsr_amd import ops
-    from refvsr_amd.packing import pack_conv_hr_last, pack_conv_last
+    from refvsr_amd.packing import pack_conv, pack_conv_hr_last, pack_conv_last
     p = c.p
-    x = nhwc16(p['x'], dev)
-    base = torch.zeros(3, x.shape[0], x.shape[1], device=dev)               # the bicubic sample of a zero map is exactly 0
-    if c.kind == 'conv_last':
-        got = ops.conv_last(pack_conv_last(f32(p['w']), f32(p['b'])).to(dev), x, base, result_dtype)
+    route = route or c.run['entry']
+    assert route in routes_of(c), (c.name, route)
+    put = (lambda t: fp.fenced_input(t.cpu(), dev, 'nan')) if fenced else (lambda t: t.to(dev))
+    weights = (lambda cw: fp.fence_weights(cw)) if fenced else (lambda cw: cw)
+    if fenced:
+        fp.reset_inputs()
+    x = put(nhwc16(p['x'], 'cpu'))
+    base = put(f32(p['base']) if p.get('base') is not None else torch.zeros(3, x.shape[0], x.shape[1]))
+    if route == 'hr_last':
+        blob = put(pack_conv_hr_last(f32(p['w1']), f32(p['b1']), f32(p['w2']), f32(p['b2'])))
+        launch = lambda: ops.conv_hr_last(blob, x, base, p['act'], result_dtype, result_layout)
     else:
-        blob = pack_conv_hr_last(f32(p['w1']), f32(p['b1']), f32(p['w2']), f32(p['b2'])).to(dev)
-        got = ops.conv_hr_last(blob, x, base, p['act'], result_dtype)
-    return got.cpu()
+        w, b = (p['w2'], p['b2']) if c.kind == 'hr_last' else (p['w'], p['b'])
+        cw_hr = weights(conv_weights(p['w1'], p['b1'], [24], dev)) if c.kind == 'hr_last' else None
+        src = lambda: ops.conv(cw_hr, x, act=p['act']) if cw_hr is not None else x
+        if route == 'conv_last':
+            blob = put(pack_conv_last(f32(w), f32(b)))
+            launch = lambda: ops.conv_last(blob, src(), base, result_dtype, result_layout)
+        else:
+            cw = weights(ops.ConvWeights(pack_conv(f32(w), f32(b), [w.shape[1]]), dev))
+            s = x.shape[0] // base.shape[1]
+            launch = lambda: ops.convert_result(ops.conv(cw, src(), planar_out=True, res_planar=ops.bicubic_scale(base, s, clamp01=True),
+                                                         clamp=(0.0, 1.0)), result_dtype, result_layout)
+    if not fenced:
+        return launch().cpu()
+    try:
+        with fp.fenced_outputs(ops) as fo:
+            got = launch()
+            verdict = fp.judge(fo, [got])
+    finally:
+        fp.reset_inputs()
+    return got.cpu(), verdict
 
 
 def run_case(c, dev, wfmt=None):
@@ -239,6 +285,69 @@ def test_head_result_formats(dev, premise, name):
         assert n16 == 0 and n8 == 0
     else:
         assert float((got16.double() - want16.double()).abs().max()) <= 2.0 ** -10 and int((got8.int() - want8.int()).abs().max()) <= 1
+
+
+def _want_of(v, fmt):
+    """The stored value of an exact fp32 head output v (float64 tensor) in a result format, as rv_store_result forms it."""
+    w16, w8 = ec.result_formats(v)
+    return {None: v.float(), 'float16': w16, 'uint8': w8}[fmt]
+
+
+@pytest.mark.parametrize('name', ec.BASED)
+def test_head_with_base_equals_reference_on_every_route(dev, premise, name):
+    """A NON-ZERO base frame at x4 and x2 through each route by which a frame leaves the network (run_head: ops.conv_last,
+    ops.conv_hr_last where the case has a conv_hr, and the unfused fallback), in float32, float16 and uint8, each planar and
+    channels-last: every stored value must be the reference's, bit for bit -- the bicubic term (coordinates at steps 1/4 and 1/2,
+    the 4 x 4 window and its index clamps on all borders, the plane of each channel, the first clamp) is exact on these maps
+    (tests/test_exact_cases.py).  Each launch runs a second time between fences (tests/footprint.py), the base NaN-fenced: the
+    fenced result must equal the plain one and no fence may change.  A read past the base is detected by EQUALITY WITH THE
+    REFERENCE (every border and corner has outputs strictly inside (0, 1) whose taps were index-clamped), not by no_nan: a NaN that
+    reaches `fminf(fmaxf(x, 0), 1)` comes out as 0."""
+    from refvsr_amd import ops
+    c = get_case(name)
+    c.assert_strong()
+    want = c.want['out']
+    bad = []
+    for route in routes_of(c):
+        for fmt in FORMATS:
+            for layout in ('chw', 'hwc'):
+                got = run_head(c, dev, fmt, layout, route)
+                got2, verdict = run_head(c, dev, fmt, layout, route, fenced=True)
+                w = _want_of(want, fmt)
+                assert got.dtype == w.dtype and got.shape == w.shape
+                assert ops.result_layout_of(got) == layout and ops.result_layout_of(got2) == layout
+                n, n2 = int((got != w).sum()), int((got2 != w).sum())
+                report('%-58s %-9s %-7s %s mismatches=%d fenced=%d fence=%s' % (c.name, route, fmt or 'float32', layout, n, n2, verdict or 'intact'))
+                if n or n2 or verdict or not torch.equal(got, got2):
+                    bad.append('%s %s %s: %d | fenced %d of %d differ; %s' % (route, fmt or 'float32', layout, n, n2, w.numel(), verdict))
+    assert premise[0], premise[1]
+    assert not bad, '%s: %s' % (c.name, '\n'.join(bad))
+
+
+@pytest.mark.parametrize('name', ec.GENERAL_NAMES)
+def test_head_with_byte_base_stays_within_the_derived_bound(dev, premise, name):
+    """Base = random bytes / 255 (what ingest_u8 hands the head) behind conv operands that are still exact, through every route,
+    format and layout: the float32 result within exact_cases.GENERAL_BOUND (10 x 2^-24: derived from the chain of roundings in
+    exact_cases.py, checked on the CPU against the reference's float32 replay) of the float64 reference; a float16 | uint8 result
+    between the stores of reference - bound and reference + bound, which differ at fewer than 1 % of the elements (for uint8: by
+    one code, only where 255 x reference lies within 255 x bound of a half-integer)."""
+    g = ec.get_general(name)
+    bad = []
+    for route in routes_of(g.case):
+        for fmt in FORMATS:
+            lo, hi = g.allowed(fmt or 'float32')
+            assert fmt is None or g.loose(fmt) <= ec.GENERAL_CAP
+            for layout in ('chw', 'hwc'):
+                got = run_head(g.case, dev, fmt, layout, route).double()
+                if fmt == 'float16':
+                    assert got.dtype == torch.float64
+                out = int(((got < lo) | (got > hi)).sum())
+                err = float((got / (255.0 if fmt == 'uint8' else 1.0) - g.want).abs().max())
+                report('%-58s %-9s %-7s %s outside=%d max |got - reference|=%.3g differs from the stored reference at %d' % (
+                    name, route, fmt or 'float32', layout, out, err, int((got != g.store(g.want, fmt or 'float32')).sum())))
+                if out:
+                    bad.append('%s %s %s: %d of %d outside the allowed interval (max error %.3g)' % (route, fmt or 'float32', layout, out, got.numel(), err))
+    assert not bad, '%s: %s' % (name, '\n'.join(bad))
 
 
 @pytest.mark.parametrize('name', [n for n in ec.NAMES if n.startswith('f16w')])

@@ -5,6 +5,9 @@ knob and setters), with the row's LDS bytes and the tile count its walk shape re
 one round-to-nearest-even for fp16 maps, no rounding for the fp32, fp16 and uint8 results of the heads, the conf_max by-product
 included where up = 1 -- on EVERY map of a multi-map launch, and (3) leave its inputs unchanged.  Every row runs at its small shape
 and at its walk shape (a side stream with a CU budget of 8: every workgroup takes two tiles or more), the marked rows at 7 x 5 too.
+The four head rows run these with a zero base frame and once more per factor (x4, x2) with an exact non-zero base
+(fixed_variant_cases: `small_x4`, `walk_x2`, ...): all three result formats at the small shapes, fp32 and uint8 at the walk and
+tiny ones, the fenced twin and the key / tile count / LDS equality unchanged (profiles/gpu_head_base_report.txt).
 
 Rows without a knob run in this process.  REFVSR_CONV48_WAVES is read once per process, so the 8-wave 48 -> 48 conv gets ONE fresh
 child (tests/fixed_variant_child.py), which writes its results to an .npz that this file judges.  A child that ends by a signal, a
@@ -36,7 +39,8 @@ from test_gpu_ops import REPORT as OPS_REPORT
 pytestmark = pytest.mark.gpu
 
 REPORT = os.path.join(os.path.dirname(OPS_REPORT), 'gpu_fixed_variants_report.txt')
-CHILD_SECONDS = 2.4                 # measured with the fenced runs (2.2 and 2.4 s over two runs): profiles/gpu_footprint_report.txt
+CHILD_SECONDS = 2.4                 # measured with the fenced runs (2.2 and 2.4 s over two runs): profiles/gpu_footprint_report.txt; re-measured with
+#                                     the based head runs in the file (they run in this process, not in the child): 2.1 s, profiles/gpu_head_base_report.txt
 CHILD_TIMEOUT = max(60.0, 3 * CHILD_SECONDS)
 IDS = ['%02d' % i for i in range(len(fv.ROWS))]
 T0 = [None]
@@ -109,7 +113,7 @@ def judge(i, run, form, res, premise_ok):
     hw = fv.shape(r, run)
     assert res['key'] == fv.key(r), 'planned variant key %d, the row is for %d %s' % (res['key'], fv.key(r), r.variant)
     assert res['lds'] == r.lds and res['n_tiles'] == fv.n_tiles(r, hw)
-    if run == 'walk':
+    if fv.kind(run) == 'walk':
         assert res['n_tiles'] >= 2 * fv.walk_bound(r) + 1, 'every workgroup must walk at least two tiles'
     assert res['same'], 'an input was written to'
     if r.setters.get('probe'):
@@ -117,8 +121,11 @@ def judge(i, run, form, res, premise_ok):
     ok, lines = True, []
     for b, c in enumerate(cases):
         want = dict(c.want)
-        if r.entry in ('conv_last', 'hr_last') and '%d.f16' % b in res:
-            want['f16'], want['u8'] = [t.double() for t in ec.result_formats(c.want['out'])]
+        if r.entry in ('conv_last', 'hr_last'):
+            assert ('base' in c.p) == (fv.factor(run) is not None) and sorted(k for k, _ in child.formats_of(run)) == sorted(
+                k[len('%d.' % b):] for k in res if k.startswith('%d.' % b))
+            stored = dict(zip(('f16', 'u8'), (t.double() for t in ec.result_formats(c.want['out']))))
+            want.update((k, stored[k]) for k, _ in child.formats_of(run) if k in stored)
         got = dict((k[len('%d.' % b):], v.double()) for k, v in res.items() if k.startswith('%d.' % b))
         assert set(got) == set(want), (sorted(got), sorted(want))
         for k in sorted(got):
